@@ -5,6 +5,7 @@ MI355X, with the achieved HBM rate of the dominant kernel (the fused int4 GEMV) 
 
   python bench.py --gpus N --steps K --warmup W                         (N = 1 default)
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...   (also accepted)
+  python bench.py ... --dump-outputs DIR    (also writes the timed chain's tokens and last logits as DIR/*.npy)
 
 A "step" is one generated token: embedding -> 32 x (rmsnorm, QKV GEMV, RoPE, sink-cache write,
 QK^T, softmax, PV, Wo, residual, rmsnorm, w1|w3 GEMV, SiLU*mul, w2 GEMV, residual) -> final norm
@@ -79,7 +80,27 @@ def parse():
                    help="validation aid for a 1-GPU box: the N stages run in THIS process on GPU 0 "
                         "(mc_pipeline_create_local: device-to-device hops), the same launches per stage "
                         "as the RCCL transport")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the timed chain computed as DIR/<name>.npy: tokens.npy (the K greedy "
+                        "tokens it returned, float64) and logits.npy (the output-head logits of its last step, float32)")
     return p.parse_args()
+
+
+def dump_outputs(out_dir, np, tokens, last_stage):
+    """--dump-outputs: the tokens the timed chain returned (every rank holds them; rank 0 writes them) and the logits of its last
+    step (read from the decoder of the last pipeline stage, on the rank that owns it).  Read after the clock has stopped."""
+    os.makedirs(out_dir, exist_ok=True)
+    names = []
+    if tokens is not None:
+        np.save(os.path.join(out_dir, "tokens.npy"), np.asarray(tokens, dtype=np.float64))
+        names.append("tokens")
+    if last_stage is not None:
+        lg = last_stage.logits()
+        if lg.dtype == np.uint16:  # bf16 bits -> float32, exact
+            lg = (lg.astype(np.uint32) << 16).view(np.float32)
+        np.save(os.path.join(out_dir, "logits.npy"), np.ascontiguousarray(lg, dtype=np.float32))
+        names.append("logits")
+    return names
 
 
 def algorithmic_bytes(m, wbits, group, seq_len, tbytes):
@@ -550,10 +571,22 @@ def main():
         tok = int(gen(tok, fill, W)[-1])
     sync_all()
     t0 = time.perf_counter()
-    tok = int(gen(tok, fill + W, K)[-1])
+    timed = gen(tok, fill + W, K)
     sync_all()
     dt = time.perf_counter() - t0
+    tok = int(timed[-1])
     tmax = sync_all(dt)
+    dumped = None
+    if args.dump_outputs:
+        last = None
+        if not piped:
+            last = dec
+        elif args.share_device:
+            last = stages[-1]
+        elif rank == world - 1:
+            last = dec
+        dumped = dump_outputs(args.dump_outputs, np, timed if rank == 0 else None, last)
+        sync_all()
     # Two more chains of the same K tokens, continuing past position seq_len (the sink ring turns: every token still attends to
     # max_seq_len rows, the same traffic): `value` stays the FIRST chain -- steps x ms_per_step is the region the driver can check --
     # and `value_spread` says how far apart three identical chains of this process land
@@ -585,6 +618,8 @@ def main():
         "whole_token": {"algorithmic_bytes": ab["total"], "achieved_GBs": ab["total"] * tok_s / 1e9,
                         "frac_of_hbm_peak": ab["total"] * tok_s / 1e9 / HBM_PEAK_GBS},
     }
+    if dumped is not None:
+        out["dumped_outputs"] = {"dir": os.path.abspath(args.dump_outputs), "names": dumped}
     if piped:
         # what the transport itself says (ncclCommCount / ncclCommUserRank; (-1, -1): stages sharing one process): the driver
         # can check that RCCL saw N ranks

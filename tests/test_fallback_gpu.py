@@ -2,18 +2,21 @@
 bound, and the decoder repeats the step on the launches that need no co-residency and stays on them ("the
 default product path must not need an environment variable to survive a busy GPU"; the reference delivers a failed command buffer
 through the future that is waited for, src/kernel_thread.cc:134-144 -- here the step is repeated instead of failing)."""
+import os
+import select
+import subprocess
+import sys
 import time
 
-import numpy as np
 import pytest
 
 import parity
 from test_context_gpu import FULL_WIDTH, SEED, random_cache
 import modelgen as mg
-import testkernels
 
 pytestmark = pytest.mark.gpu
 BF16 = 0
+HERE = os.path.dirname(os.path.abspath(__file__))
 
 
 @pytest.fixture(scope="module")
@@ -23,40 +26,36 @@ def acc():
     return mc.HardwareAccelerator(ordinal=0)
 
 
-_QUEUES = {}
+def hold_most_of_the_chip(seconds):
+    """Starts the "other user" of the GPU -- tests/hold_child.py, a process of its own: HIP deals this process's streams over a few
+    hardware queues, and a holder stream of this process may share the decoder's queue, whose launches then simply wait behind it in
+    order (seen as a 2.8 s step with no fall-back) -- and returns once its holders on 7 of 8 compute units are launched."""
+    p = subprocess.Popen([sys.executable, os.path.join(HERE, "hold_child.py"), HERE, os.path.dirname(HERE), str(seconds)],
+                         stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
+    line = p.stdout.readline() if select.select([p.stdout], [], [], 120)[0] else ""
+    if not line.startswith("held "):
+        p.kill()
+        _, err = p.communicate()
+        raise AssertionError(f"the holder process did not start: {line!r} {err[-4000:]}")
+    return p, int(line.split()[1])
 
 
-def two_queues():
-    """The decoder's stream and the "other user's" stream, ONCE per process: HIP deals its streams over a few hardware queues, and a
-    third or fifth stream of this process may share the holders' queue -- its launches then simply wait behind them in order (seen as a
-    2.8 s step with no fall-back when every test made its own pair)."""
-    import metalchat_amd as mc
-
-    if not _QUEUES:
-        _QUEUES["acc"] = mc.HardwareAccelerator(ordinal=0)
-        _QUEUES["acc2"] = mc.HardwareAccelerator(path=testkernels.build(), ordinal=0)   # a second queue with the test-only code object
-    return _QUEUES["acc"], _QUEUES["acc2"]
-
-
-def hold_most_of_the_chip(acc2, seconds):
-    # 7 of 8 compute units for `seconds`: what is left holds two, at most three of the 512-thread hand-off workgroups each -- not
-    # the 256 of the launch (half the chip is not enough: the 256 fit two to a CU on the other half).  The holders end by the
-    # clock: any blocking HIP call of this process (a synchronous copy) would wait for them, so nothing here polls or releases
-    import metalchat_amd as mc
-
-    nhold = acc2.compute_units() // 8 * 7
-    release = acc2.to_device(np.zeros(1, np.uint32))
-    started = acc2.to_device(np.zeros(2, np.uint32))
-    mc.KernelTask(acc2.load("mc_test_hold_cu"), (nhold * 64, 1, 1), (64, 1, 1), [release, started, np.uint64(int(seconds * 1e8))])()
-    time.sleep(0.2)
-    return release, started, nhold
+def end_hold(p, seconds):
+    """Waits for the holders to drain by their clock; returns how many of them started."""
+    try:
+        out, err = p.communicate(timeout=seconds + 120)
+    except subprocess.TimeoutExpired:
+        p.kill()
+        out, err = p.communicate()
+        raise AssertionError(f"the holder process did not end: {err[-4000:]}")
+    assert p.returncode == 0, err[-4000:]
+    return int(out.split()[-1])   # "started <n>"
 
 
 @pytest.mark.parametrize("shape", ["llama3-8b", "gemma-7b", "tinyllama"])
-def test_a_step_whose_handoffs_give_up_is_repeated_without_them(monkeypatch, shape):
+def test_a_step_whose_handoffs_give_up_is_repeated_without_them(monkeypatch, acc, shape):
     import metalchat_amd as mc
 
-    acc, acc2 = two_queues()   # (acc2: the "other user" of the GPU)
     wfmt, group = mc.WFMT_I4, 128
     if shape == "llama3-8b":
         cfg = dict(dtype=BF16, n_layers=2, vocab=2048, norm_eps=1e-5, max_seq_len=2048, **FULL_WIDTH["llama3-8b"])
@@ -93,7 +92,7 @@ def test_a_step_whose_handoffs_give_up_is_repeated_without_them(monkeypatch, sha
     dec = fresh()
     dec.launch_log(True)
  
-    release, started, nhold = hold_most_of_the_chip(acc2, 3.0)
+    hold, nhold = hold_most_of_the_chip(3.0)
     try:
         t0 = time.perf_counter()
         tok = dec.step(5, n)                      # most of the hand-off launch's workgroups cannot start: it gives up, the step is repeated
@@ -116,17 +115,16 @@ def test_a_step_whose_handoffs_give_up_is_repeated_without_them(monkeypatch, sha
         assert tok2 == want[1][0]
         parity.exact(dec.logits(), want[1][1], "the step after the fall-back")
     finally:
-        acc2.wait()
-    assert int(started.download(np.uint32, 1)[0]) == nhold
+        nstarted = end_hold(hold, 3.0)
+    assert nstarted == nhold
     dec.release()
 
 
-def test_the_fallback_is_temporary(monkeypatch):
+def test_the_fallback_is_temporary(monkeypatch, acc):
     # one transient stall must not cost every later token the one-launch blocks -- after MC_HANDOFF_REARM clean tokens (256 by default) the decoder
     # takes the hand-off launches again, with the same tokens as a decoder that never fell back
     import metalchat_amd as mc
 
-    acc, acc2 = two_queues()
     cfg = dict(dtype=BF16, n_layers=2, vocab=2048, norm_eps=1e-5, max_seq_len=2048, **FULL_WIDTH["llama3-8b"])
     kw = mg.decoder_kwargs(cfg, weight_format=mc.WFMT_I4, group_size=128)
     ref = mc.Decoder(acc, **kw)
@@ -138,12 +136,12 @@ def test_the_fallback_is_temporary(monkeypatch):
     monkeypatch.setenv("MC_HANDOFF_REARM", "8")
     dec = mc.Decoder(acc, **kw)
     dec.init_synthetic(SEED)
-    release, started, nhold = hold_most_of_the_chip(acc2, 2.0)
+    hold, nhold = hold_most_of_the_chip(2.0)
     try:
         got = list(dec.generate(3, 0, 12))   # gives up, repeated without hand-offs: 12 clean tokens >= 8 -> re-armed for the next call
         assert got == want[:12] and dec.handoff_fallbacks() == 1
     finally:
-        acc2.wait()
+        end_hold(hold, 2.0)
     assert dec.handoff_rearms() == 1 and dec.handoffs_active()
     dec.launch_log(True)
     assert list(dec.generate(got[-1], 12, 10)) == want[12:22]   # the chip is free again: the one-launch blocks, no fall-back
@@ -152,10 +150,9 @@ def test_the_fallback_is_temporary(monkeypatch):
     dec.release()
 
 
-def test_a_chain_whose_handoffs_give_up_is_repeated_without_them(monkeypatch):
+def test_a_chain_whose_handoffs_give_up_is_repeated_without_them(monkeypatch, acc):
     import metalchat_amd as mc
 
-    acc, acc2 = two_queues()
     cfg = dict(dtype=BF16, n_layers=2, vocab=2048, norm_eps=1e-5, max_seq_len=2048, **FULL_WIDTH["llama3-8b"])
     kw = mg.decoder_kwargs(cfg, weight_format=mc.WFMT_I4, group_size=128)
     monkeypatch.setenv("MC_ATTN_FUSED", "0")
@@ -166,14 +163,14 @@ def test_a_chain_whose_handoffs_give_up_is_repeated_without_them(monkeypatch):
     monkeypatch.delenv("MC_ATTN_FUSED")
     dec = mc.Decoder(acc, **kw)
     dec.init_synthetic(SEED)
-    release, started, nhold = hold_most_of_the_chip(acc2, 3.0)
+    hold, nhold = hold_most_of_the_chip(3.0)
     try:
         got = list(dec.generate(3, 0, 12))   # stays inside the cache: repeated from the state in front of the call
         assert dec.handoff_fallbacks() == 1
         assert got == want
     finally:
-        acc2.wait()
-    assert int(started.download(np.uint32, 1)[0]) == nhold
+        nstarted = end_hold(hold, 3.0)
+    assert nstarted == nhold
     # a later call: no hand-off launches, no further fall-back
     assert list(dec.generate(want[-1], 12, 4)) is not None and dec.handoff_fallbacks() == 1
     dec.release()
