@@ -883,7 +883,9 @@ struct mc_decoder {
             L.qkv.out != (cfg.n_heads + 2 * cfg.n_kv_heads) * hd || n_rep > 16 || pg < 64 || pg > 512)
             return 0;
         for (int t : {1, 2, 4}) {
-            // (wide ranges of a cache that is not whole ranges long -- S = 4040 -- would leave a ragged last range: the kernels clamp and mask it, no test covers it)
+            // (wide ranges of a cache that is not whole ranges long -- S = 4040 -- would leave a ragged last range: refused here; the form such a
+            //  context takes instead is pinned by tests/test_context_gpu.py::test_contexts_of_partial_ranges_against_the_oracle_and_the_form_they_take.
+            //  64-slot ranges with a short last one are taken: tests/test_attn_kernels_gpu.py runs them at S = 2040)
             if (nsplit % t || (t > 1 && cfg.max_seq_len % (64 * t)) || (t == 1 && !attn_fused()) || (t > 1 && !attn_i4_wide_on)) continue;
             const int ns = nsplit / t;
             const unsigned grid = (unsigned)(ns * (cfg.n_kv_heads << sh));

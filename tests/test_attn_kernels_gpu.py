@@ -8,7 +8,9 @@ contraction are added range by range), so the bound is the single-kernel one: ev
 
 Cases: Llama-3-8B (4 query heads per kv head, head_dim 128), TinyLlama (8 per kv head, head_dim 64), Gemma-7B shapes (MHA,
 head_dim 256), head_dim 32; caches that are full, nearly empty (most ranges of the launch have nothing to publish), and that end
-in the middle of a 64-slot range / 16-slot tile."""
+in the middle of a 64-slot range / 16-slot tile; and contexts that are not whole 64-slot ranges (max_seq_len 2040, 1000, 104: the decoder
+takes any multiple of 8, nsplit = ceil(S / 64), the last range short), with a guard of NaN behind every cache so that a read past max_seq
+that is not clamped shows in the output."""
 import numpy as np
 import pytest
 
@@ -40,6 +42,12 @@ def oracle_attention(q, k, v, n_rep, scale):
     return o.reshape(H, hd)
 
 
+# a guard of bf16 NaN behind each cache the tests hand a launch: the widest range (4 tiles of 64 slots) of head_dim 256 past the end.  A read
+# past max_seq that the kernel does not clamp lands in it and turns the output into NaN inside a buffer the test owns.
+GUARD = 4 * PB * 256
+NAN = 0x7FC0
+
+
 def device_caches(acc, k, v, max_seq):
     n, KV, hd = k.shape
     kc = np.zeros((KV, max_seq, hd), np.uint16)
@@ -50,7 +58,14 @@ def device_caches(acc, k, v, max_seq):
     rng = np.random.default_rng(9)
     kc[:, n:] = mo.encode(BF16, rng.normal(0, 30, (KV, max_seq - n, hd)).astype(np.float32))
     vt[:, :, n:] = mo.encode(BF16, rng.normal(0, 30, (KV, hd, max_seq - n)).astype(np.float32))
-    return acc.to_device(kc.reshape(-1)), acc.to_device(vt.reshape(-1))
+    guard = np.full(GUARD, NAN, np.uint16)
+    return acc.to_device(np.concatenate([kc.reshape(-1), guard])), acc.to_device(np.concatenate([vt.reshape(-1), guard]))
+
+
+def assert_guards_intact(kc, vt, size):
+    """No launch writes past the cache it is handed (size = KV * max_seq * hd elements)."""
+    for buf, name in ((kc, "K"), (vt, "V")):
+        parity.exact(buf.download(np.uint16, GUARD, offset=2 * size), np.full(GUARD, NAN, np.uint16), f"the guard behind the {name} cache")
 
 
 def state_buffer(acc, kv_len, epoch):
@@ -66,15 +81,24 @@ CASES = [
     (16, 16, 256, 2048, 2048), (16, 16, 256, 2048, 130),
     (8, 2, 32, 512, 500), (16, 1, 128, 1024, 1024),
 ]
+# contexts that are not whole 64-slot ranges (the decoder takes any multiple of 8: nsplit = ceil(S / 64), the last range short): the cache
+# full, one slot short of it, kv_len inside the short last range, one slot.  Slots past max_seq are read clamped and masked.
+RAGGED = [
+    (32, 8, 128, 2040, 2040), (32, 8, 128, 2040, 2039), (32, 8, 128, 2040, 2000), (32, 8, 128, 2040, 1),
+    (32, 4, 64, 1000, 1000), (32, 4, 64, 1000, 999), (32, 4, 64, 1000, 970), (32, 4, 64, 1000, 1),
+    (16, 16, 256, 1000, 1000), (16, 16, 256, 1000, 999), (16, 16, 256, 1000, 970), (16, 16, 256, 1000, 1),
+    (8, 2, 32, 104, 104), (8, 2, 32, 104, 103), (8, 2, 32, 104, 70), (8, 2, 32, 104, 1),
+]
 # hand-offs with / without the XCD-local fast path (handoff.h); 3: with it AND the kv heads dealt with a stride of the next multiple
 # of 8 (grid = nsplit x stride, the workgroups without a head leave at once: decoder.cc handoff_mode_alone)
 @pytest.mark.parametrize("fast", [1, 0, 3])
 @pytest.mark.parametrize("tiles", [1, 2])   # 64-slot ranges (mc_attn_fused_bfloat) / 128-slot ranges (mc_attn_fused_t2_bfloat: S = 8192 in the decoder)
-@pytest.mark.parametrize("H,KV,hd,max_seq,n", CASES + [(32, 8, 128, 8192, 8000)])
+@pytest.mark.parametrize("H,KV,hd,max_seq,n", CASES + [(32, 8, 128, 8192, 8000)] + RAGGED)
 def test_one_launch_attention_matches_the_oracle(acc, H, KV, hd, max_seq, n, fast, tiles):
     import metalchat_amd as mc
 
-    if tiles == 2 and (hd not in (64, 128) or max_seq % (2 * PB)):
+    # (the decoder's gate, attn_fused_t2: an even count of 64-slot ranges -- S = 2040 is 16 ranges of 128 slots, the last one 120 long)
+    if tiles == 2 and (hd not in (64, 128) or (max_seq + PB - 1) // PB % 2):
         pytest.skip("128-slot ranges are built for head_dim 64 and 128")
     rng = np.random.default_rng(H * 7 + hd + n)
     n_rep, nsplit = H // KV, (max_seq + PB * tiles - 1) // (PB * tiles)
@@ -103,9 +127,10 @@ def test_one_launch_attention_matches_the_oracle(acc, H, KV, hd, max_seq, n, fas
         got = out.download(np.uint16, H * hd)
         parity.check(BF16, got, ref, rel=2e-3, max_ulp=1, max_frac=0.03, scale_aware=True,
                      what=f"one-launch attention H{H} KV{KV} hd{hd} n{n} tag ({epoch}, {layer_tag}) mode {fast}")
+    assert_guards_intact(kc, vt, KV * max_seq * hd)
 
 
-@pytest.mark.parametrize("H,KV,hd,max_seq,n", CASES)
+@pytest.mark.parametrize("H,KV,hd,max_seq,n", CASES + RAGGED)
 def test_two_launch_attention_matches_the_oracle(acc, H, KV, hd, max_seq, n):
     import metalchat_amd as mc
 
@@ -137,6 +162,7 @@ def test_two_launch_attention_matches_the_oracle(acc, H, KV, hd, max_seq, n):
         got = out.download(np.uint16, H * hd)
         parity.check(BF16, got, ref, rel=2e-3, max_ulp=1, max_frac=0.03, scale_aware=True,
                      what=f"two-launch attention H{H} KV{KV} hd{hd} n{n} ranges {ranges}")
+    assert_guards_intact(kc, vt, KV * max_seq * hd)
 
 
 def test_a_hand_off_whose_producers_never_run_gives_up_and_reports(acc):
@@ -186,7 +212,8 @@ def test_a_hand_off_whose_producers_never_run_gives_up_and_reports(acc):
 
 
 @pytest.mark.parametrize("fast", [1, 0])
-@pytest.mark.parametrize("shape,n", [("llama3-8b", 2048), ("llama3-8b", 1000), ("llama3-8b", 3), ("hd64", 2047), ("llama3-8b-1024", 1024)])
+@pytest.mark.parametrize("shape,n", [("llama3-8b", 2048), ("llama3-8b", 1000), ("llama3-8b", 3), ("hd64", 2047), ("llama3-8b-1024", 1024),
+                                     ("llama3-8b-2040", 2040), ("llama3-8b-2040", 2039), ("llama3-8b-2040", 2000), ("llama3-8b-2040", 1)])
 def test_attention_and_wo_in_one_launch_matches_the_oracle(acc, shape, n, fast):
     """`mc_attn_wo_i4_bfloat_*` (attn_block_kernels.hip: the decode attention AND the Wo GEMV + residual of one block,
     nn/attention.h:191-205 + nn/transformer.h:132-133) launched BY NAME on a query row, a cache and a hidden row of its own, against
@@ -200,6 +227,8 @@ def test_attention_and_wo_in_one_launch_matches_the_oracle(acc, shape, n, fast):
         H, KV, hd, dim, max_seq = 32, 8, 64, 2048, 2048
     elif shape == "llama3-8b-1024":   # 128 workgroups: two row pairs of Wo per wave
         H, KV, hd, dim, max_seq = 32, 8, 128, 4096, 1024
+    elif shape == "llama3-8b-2040":   # the 32 ranges of S = 2048, the last one 56 slots long
+        H, KV, hd, dim, max_seq = 32, 8, 128, 4096, 2040
     else:
         H, KV, hd, dim, max_seq = 32, 8, 128, 4096, 2048
     cfg = mg.tiny_cfg(BF16, dim=dim, n_heads=H, n_kv_heads=KV, head_dim=hd, ffn_dim=256, n_layers=1, vocab=64, max_seq_len=max_seq)
@@ -242,6 +271,7 @@ def test_attention_and_wo_in_one_launch_matches_the_oracle(acc, shape, n, fast):
                      what=f"attention row of the one launch, {shape} n{n} tag ({epoch}, {layer_tag})")
         parity.check(BF16, hb.download(np.uint16, dim), ref.reshape(-1), rel=4e-3, max_ulp=2, max_frac=0.3, scale_aware=True,
                      what=f"attention + Wo + residual in one launch, {shape} n{n} tag ({epoch}, {layer_tag})")
+    assert_guards_intact(kc, vt, KV * max_seq * hd)
     dec.release()
 
 
@@ -257,9 +287,6 @@ def test_norm_qkv_rope_attention_and_wo_in_one_launch_matches_the_oracle(acc, n,
     rows appended to the cache (nn/cache.h:209-213), the attention of test_one_launch_attention_matches_the_oracle, Wo, add in T.
     The hidden row is dyadic, so the normalised row is the oracle's bit for bit (test_lin_kernels_gpu.py) and the cache rows the
     launch writes are held to the GEMV's single-kernel bound; the block's output to the composition bound of the suite."""
-    import metalchat_amd as mc
-    from test_lin_kernels_gpu import dyadic_row, oracle_rmsnorm
-
     # (the second shape: `mc_attn_qkv_wo_w_bfloat_hd64_k4_q4`, the same launch for PLAIN bfloat weights -- nn::linear, Llama-3.2-1B,
     #  the reference's default model, src/llama.cc:19-31)
     # (the third: TinyLlama's 4 kv heads x 8 query heads, launched as 8 VIRTUAL kv heads of 4 query heads -- kv_shift = 1, round 5,
@@ -267,12 +294,28 @@ def test_norm_qkv_rope_attention_and_wo_in_one_launch_matches_the_oracle(acc, n,
     # (the fourth and fifth: int8 weights, round 5 -- `mc_attn_qkv_wo_i8_bfloat_hd128_k4_q4_t1` with 64-slot ranges and `_t4` with 256-slot
     #  ranges at max_seq_len 8192, where the cache is filled up to n x 4 rows so that ranges are full, ragged and empty as in the others)
     # (the sixth and seventh: the int4 launch with 128- and 256-slot ranges, `_t2` / `_t4`, round 5 -- contexts of 4096 and 8192 slots)
-    int4 = shape.startswith("llama3-8b-int4")
-    int8 = shape.startswith("llama3-8b-int8")
     tiles = 4 if shape.endswith("-8192") else (2 if shape.endswith("-4096") else 1)
     # (... and the wide ranges of the int8 launch at S = 4096 and of the plain-bfloat launch: Llama-3.2-1B at 8192, TinyLlama's virtual heads at 4096)
-    H, KV, hd, dim, max_seq = (32, 8, 128, 4096, 2048 * tiles) if (int4 or int8) else (32, 4 if shape.startswith("tinyllama-bf16") else 8, 64, 2048, 2048 * tiles)
-    n = n * tiles
+    qkv_wo_block_against_the_oracle(acc, shape, n * tiles, fast, 2048 * tiles, tiles)
+
+
+@pytest.mark.parametrize("fast", [1, 0])
+@pytest.mark.parametrize("n", [2040, 2039, 2000, 1])
+@pytest.mark.parametrize("shape", ["llama3-8b-int4", "llama3.2-1b-bf16", "tinyllama-bf16", "llama3-8b-int8"])
+def test_norm_qkv_rope_attention_and_wo_in_one_launch_at_a_context_of_partial_ranges(acc, n, fast, shape):
+    """... at S = 2040, where the decoder takes the same launches with 64-slot ranges (nsplit = ceil(2040 / 64) = 32, as at 2048: the
+    bench's `mc_attn_qkv_wo_i4_bfloat_hd128_k2_q2`, `_i8_..._t1`, `_w_` on real and virtual kv heads) and the last range holds 56 slots: the
+    cache full, one slot short, the step's slot inside the short range, one slot."""
+    qkv_wo_block_against_the_oracle(acc, shape, n, fast, 2040, 1)
+
+
+def qkv_wo_block_against_the_oracle(acc, shape, n, fast, max_seq, tiles):
+    import metalchat_amd as mc
+    from test_lin_kernels_gpu import dyadic_row, oracle_rmsnorm
+
+    int4 = shape.startswith("llama3-8b-int4")
+    int8 = shape.startswith("llama3-8b-int8")
+    H, KV, hd, dim = (32, 8, 128, 4096) if (int4 or int8) else (32, 4 if shape.startswith("tinyllama-bf16") else 8, 64, 2048)
     vsh = 1 if shape.startswith("tinyllama-bf16") else 0
     KVV = KV << vsh
     half = hd // 2
@@ -285,7 +328,7 @@ def test_norm_qkv_rope_attention_and_wo_in_one_launch_matches_the_oracle(acc, n,
     qk_p, qk_s, qrows, qinf, _ = dec.weight_ptrs(0, "qkv")
     assert (rows, inf, qrows, qinf) == (dim, H * hd, (H + 2 * KV) * hd, dim)
     rng = np.random.default_rng(1000 + n)
-    n_rep, nsplit = H // KV, max_seq // (PB * tiles)
+    n_rep, nsplit = H // KV, (max_seq + PB * tiles - 1) // (PB * tiles)   # (as the decoder counts ranges: the last one may be short)
     slot, rrow, nrows = n - 1, 5, 8            # the step writes slot n - 1 and reads n slots
     x = dyadic_row(rng, dim)
     k = mo.encode(BF16, rng.normal(0, 0.4, (n, KV, hd)).astype(np.float32))
@@ -345,6 +388,7 @@ def test_norm_qkv_rope_attention_and_wo_in_one_launch_matches_the_oracle(acc, n,
                      what=f"attention row of the one launch, n{n} tag ({epoch}, {layer_tag})")
         parity.check(BF16, hb.download(np.uint16, dim), ref.reshape(-1), rel=4e-3, max_ulp=2, max_frac=0.3, scale_aware=True,
                      what=f"norm + wq|wk|wv + rope + attention + Wo + residual in one launch, n{n} tag ({epoch}, {layer_tag})")
+    assert_guards_intact(kc, vt, KV * max_seq * hd)
     dec.release()
 
 
@@ -368,7 +412,7 @@ def test_gemma_norms_rope_attention_and_wo_in_one_launch_matches_the_oracle(acc,
     wo_p, wo_s, rows, inf, _ = dec.weight_ptrs(0, "wo")
     assert (rows, inf) == (dim, H * hd)
     rng = np.random.default_rng(4000 + n + tiles)
-    n_rep, nsplit = H // KV, max_seq // (PB * tiles)
+    n_rep, nsplit = H // KV, (max_seq + PB * tiles - 1) // (PB * tiles)
     slot, rrow, nrows, eps = n - 1, 3, 6, 1e-6
     q0 = mo.encode(BF16, rng.normal(0, 1.5, (H, hd)).astype(np.float32))
     k0 = mo.encode(BF16, rng.normal(0, 0.7, (KV, hd)).astype(np.float32))
@@ -460,7 +504,7 @@ def test_gemma_block_from_the_row_to_wo_in_one_launch_matches_the_oracle(acc, po
     qk_p, qk_s, qrows, qinf, _ = dec.weight_ptrs(0, "qkv")
     assert (rows, inf, qrows, qinf) == (dim, H * hd, (H + 2 * KV) * hd, dim)
     rng = np.random.default_rng(7000 + n + post)
-    n_rep, nsplit = H // KV, max_seq // (PB * tiles)
+    n_rep, nsplit = H // KV, (max_seq + PB * tiles - 1) // (PB * tiles)
     slot, rrow, nrows, eps, mu = n - 1, 4, 6, 1e-6, 1.0
     L = mo.layout
     x = dyadic_row(rng, dim)
@@ -566,7 +610,7 @@ def test_llama3_70b_norm_qkv_rope_and_attention_in_one_launch_matches_the_oracle
     qk_p, qk_s, qrows, qinf, _ = dec.weight_ptrs(0, "qkv")
     assert (qrows, qinf) == ((H + 2 * KV) * hd, dim)
     rng = np.random.default_rng(2000 + n)
-    n_rep, nsplit = H // KV, max_seq // PB
+    n_rep, nsplit = H // KV, (max_seq + PB - 1) // PB
     slot, rrow, nrows = n - 1, 5, 8
     x = dyadic_row(rng, dim)
     k = mo.encode(BF16, rng.normal(0, 0.4, (n, KV, hd)).astype(np.float32))

@@ -3,6 +3,7 @@
 on the GPU: 4 kv heads as 8 virtual ones, 22 row pairs of w1|w3 per workgroup) and Llama-3.2-1B's (the reference's default model: 32 pairs) widths.
 
   * against the oracle: S = 2048, kv_len 2045 .. 2048 and rolls past the end, and position 40 (all but one range of the launch empty);
+    S = 2040 (the last range 56 slots long) across the end of the cache;
   * BIT FOR BIT the two launches it replaces (mc_attn_qkv_wo_w_bfloat_hd64_k4_q4 + mc_gemv_w_bfloat_ling4_p1_e2): hidden rows of every
     block, logits, tokens, both blocks' caches, near an empty cache, at position 70 and across the end of a full one;
   * graph replay == eager launches over a chain of tokens that crosses the end of the cache.
@@ -51,6 +52,22 @@ def test_chained_block_against_the_oracle(acc, monkeypatch, shape):
     agree = run_injected(acc, cfg, weights, 40, 8, dict(weight_format=mc.WFMT_T, group_size=0), rel_logits=7.8e-3,
                          max_ulp=3, max_frac=0.8, what=f"{shape} at position 40, chained")
     assert agree >= 7
+
+
+@pytest.mark.parametrize("shape", list(SHAPES))
+def test_chained_block_at_a_context_of_partial_ranges(acc, monkeypatch, shape):
+    # S = 2040: the 32 ranges of 2048 per (virtual) kv head, the last one 56 slots long -- the decoder keeps the chained launch; one block against the
+    # oracle from kv_len 2036 to seven steps past the end of the cache (the sink ring, pre_len 10)
+    import metalchat_amd as mc
+
+    monkeypatch.setenv("MC_CHAIN_W13", "1")
+    cfg = config(shape, n_layers=1, vocab=2048, max_seq_len=2040)
+    weights = t_weights_model(cfg, SEED)
+    names = set()
+    agree = run_injected(acc, cfg, weights, 2035, 12, dict(weight_format=mc.WFMT_T, group_size=0), rel_logits=7.8e-3,
+                         max_ulp=3, max_frac=0.8, what=f"{shape} S=2040, chained", launched=names)
+    assert agree >= 10
+    assert SHAPES[shape][1] in names and BLOCK not in names and W13 not in names, sorted(names)
 
 
 @pytest.mark.parametrize("shape", list(SHAPES))

@@ -697,15 +697,15 @@ def test_gemma_norm_and_rope_inside_the_attention_launch_equal_the_two_launches_
     parity.exact(out["qkn"][2], out["sep"][2], f"{shape}: V cache")
 
 
-@pytest.mark.parametrize("shape", ["llama3-8b", "llama3-8b-1024", "llama3-8b-768", "hd64", "gemma-hd256"])
+@pytest.mark.parametrize("shape", ["llama3-8b", "llama3-8b-1024", "llama3-8b-768", "hd64", "gemma-hd256", "llama3-8b-2040"])
 def test_attention_and_wo_in_one_launch_equal_the_two_launches_bit_for_bit(acc, monkeypatch, shape):
     # mc_attn_wo_i4_bfloat_* = mc_attn_fused_bfloat + the Wo GEMV (attn_block_kernels.hip): the same attention phases, the same row, the same per-row arithmetic -- hidden rows, logits, caches and tokens must be IDENTICAL to the two launches, near an empty
     # cache and across the end of a full one; the launch log shows which form ran.
     import metalchat_amd as mc
 
     base = dict(dtype=BF16, n_layers=2, vocab=2048, norm_eps=1e-5)
-    if shape == "llama3-8b":
-        cfg = dict(base, max_seq_len=2048, **FULL_WIDTH["llama3-8b"])
+    if shape in ("llama3-8b", "llama3-8b-2040"):   # (2040: the 32 ranges of 2048, the last one 56 slots long)
+        cfg = dict(base, max_seq_len=2040 if shape.endswith("2040") else 2048, **FULL_WIDTH["llama3-8b"])
         kernel = "mc_attn_wo_i4_bfloat_hd128_k2"
     elif shape == "llama3-8b-1024":  # 128 workgroups: every wave owns TWO row pairs of Wo (the most the kernel holds)
         cfg = dict(base, max_seq_len=1024, **FULL_WIDTH["llama3-8b"])
@@ -724,7 +724,7 @@ def test_attention_and_wo_in_one_launch_equal_the_two_launches_bit_for_bit(acc, 
     S = cfg["max_seq_len"]
     # "qkv": the default where it is built (round 4: wq|wk|wv, attention and Wo in ONE launch, mc_attn_qkv_wo_*);  "wo": the wq|wk|wv GEMV,
     # then attention + Wo in one launch;  "sep": the GEMV, mc_attn_fused_bfloat, then the Wo GEMV
-    qkv_kernel = {"llama3-8b": "mc_attn_qkv_wo_i4_bfloat_hd128_k2_q2",
+    qkv_kernel = {"llama3-8b": "mc_attn_qkv_wo_i4_bfloat_hd128_k2_q2", "llama3-8b-2040": "mc_attn_qkv_wo_i4_bfloat_hd128_k2_q2",
                   "gemma-hd256": "mc_attn_qkv_wo_qkn_i4_bfloat_hd256_k2_p1_t1"}.get(shape)   # (gemma3 with parity taps: every block starts at its pre-norm)
     out = {}
     forms = [("qkv", {}), ("wo", {"MC_ATTN_QKV": "0"}), ("sep", {"MC_ATTN_WO": "0"})]
@@ -844,7 +844,7 @@ def test_gemma_7b_attention_block_with_wo_inside_against_the_two_launches(acc, m
     parity.exact(out["wo", True][1][0][1], out["sep", True][1][0][1], "V cache of the first block")
 
 
-@pytest.mark.parametrize("shape", ["gemma-7b", "llama3-8b-int4-8192", "tinyllama-4096"])
+@pytest.mark.parametrize("shape", ["gemma-7b", "llama3-8b-int4-8192", "tinyllama-4096", "llama3-8b-int4-2040"])
 def test_graph_replay_of_the_round5_blocks_equals_eager_across_the_end_of_the_cache(acc, shape):
     # The launches this round added to the default path -- the gemma3 block (mc_attn_qkv_wo_qkn_*: `_p1_` then `_p2_`), the int4 block with 256-slot
     # ranges, the plain-bfloat block with 128-slot ranges on 8 virtual kv heads -- in mc_decoder_generate's hipGraph replay against the eager
@@ -858,6 +858,9 @@ def test_graph_replay_of_the_round5_blocks_equals_eager_across_the_end_of_the_ca
     elif shape == "llama3-8b-int4-8192":
         cfg = dict(dtype=BF16, n_layers=2, vocab=2048, max_seq_len=8192, norm_eps=1e-5, **FULL_WIDTH["llama3-8b"])
         fmt, kern = dict(weight_format=mc.WFMT_I4, group_size=128), "mc_attn_qkv_wo_i4_bfloat_hd128_k2_q2_t4"
+    elif shape == "llama3-8b-int4-2040":   # (the bench's block with the last of its 32 ranges 56 slots long)
+        cfg = dict(dtype=BF16, n_layers=2, vocab=2048, max_seq_len=2040, norm_eps=1e-5, **FULL_WIDTH["llama3-8b"])
+        fmt, kern = dict(weight_format=mc.WFMT_I4, group_size=128), "mc_attn_qkv_wo_i4_bfloat_hd128_k2_q2"
     else:
         cfg = dict(dtype=BF16, family=0, n_layers=2, vocab=32000, max_seq_len=4096, norm_eps=1e-5, dim=2048, n_heads=32, n_kv_heads=4, head_dim=64,
                    ffn_dim=5632, rope_theta=10000.0, attn_scale=64 ** -0.5)
@@ -877,3 +880,99 @@ def test_graph_replay_of_the_round5_blocks_equals_eager_across_the_end_of_the_ca
         dec.release()
     assert out[0][0] == out[1][0], shape
     parity.exact(out[0][1], out[1][1], f"{shape}: the last logits, graph replay vs eager")
+
+
+# ---- contexts that are not whole 64-slot ranges.  The decoder takes any max_seq_len that is a multiple of 8 and counts nsplit = ceil(S / 64) ranges,
+# the last one short; the kernels clamp their reads at max_seq and mask the slots past kv_len.  Each case: one full-width block against the oracle from
+# five slots before the end of the cache to seven steps past it (kv_len inside the short last range, then the sink ring: pre_len 10 at 2040, 9 at 1000,
+# 11 at 4032 .. 8120), and the launch form the admission gates in decoder.cc pick, by kernel name -- a change of gate has to change this table.
+# (form: kernels that must run, kernels that must not)
+def _shape_cfg(shape, S):
+    import metalchat_amd as mc
+
+    if shape.startswith("llama3-8b"):
+        cfg = dict(dtype=BF16, n_layers=1, vocab=2048, max_seq_len=S, norm_eps=1e-5, **FULL_WIDTH["llama3-8b"])
+        if shape == "llama3-8b-int8":
+            return cfg, synth_model(cfg, SEED, bits=8), dict(weight_format=mc.WFMT_I8, group_size=128), dict(rel_logits=5e-3, max_ulp=2, max_frac=0.7)
+        return cfg, synth_model(cfg, SEED), dict(weight_format=mc.WFMT_I4, group_size=128), dict(rel_logits=5e-3, max_ulp=2, max_frac=0.7)
+    if shape == "gemma-7b":
+        cfg = dict(dtype=BF16, n_layers=1, vocab=2048, max_seq_len=S, norm_eps=1e-5, dim=3072, n_heads=16, n_kv_heads=16, head_dim=256,
+                   ffn_dim=4096, family=1, rope_theta=10000.0, rope_sliding_theta=10000.0, sliding_stride=2, attn_scale=256 ** -0.5)
+        # (the bounds of test_gemma_7b_widths_at_the_benchmark_context)
+        return cfg, synth_model(cfg, SEED), dict(weight_format=mc.WFMT_I4, group_size=128), dict(rel_logits=5e-3, max_ulp=3, max_frac=0.7)
+    cfg = dict(dtype=BF16, family=0, n_layers=1, vocab=2048, max_seq_len=S, norm_eps=1e-5, dim=2048, n_heads=32,
+               n_kv_heads=8 if shape == "llama3.2-1b" else 4, head_dim=64, ffn_dim=8192 if shape == "llama3.2-1b" else 5632,
+               rope_theta=500000.0 if shape == "llama3.2-1b" else 10000.0, attn_scale=64 ** -0.5)
+    return cfg, t_weights_model(cfg, SEED), dict(weight_format=mc.WFMT_T, group_size=0), dict(rel_logits=7.8e-3, max_ulp=3, max_frac=0.8)
+
+
+QKV_WO = ("mc_attn_qkv_wo_i4_", "mc_attn_qkv_wo_i8_", "mc_attn_qkv_wo_w_", "mc_attn_qkv_wo_w13_", "mc_attn_qkv_wo_qkn_", "mc_attn_wo_qkn_")
+PARTIAL_RANGE_FORMS = {
+    # S = 2040: 32 ranges per kv head as at 2048 -- the one-launch blocks of the benchmark context, the last range 56 slots
+    ("llama3-8b-int4", 2040): ({"mc_attn_qkv_wo_i4_bfloat_hd128_k2_q2"}, {"mc_attn_fused_bfloat", "mc_gemv_i4_bfloat_lin2_p1_e4"}),
+    ("llama3-8b-int8", 2040): ({"mc_attn_qkv_wo_i8_bfloat_hd128_k4_q4_t1"}, {"mc_attn_fused_bfloat", "mc_gemv_i8_bfloat_ling4_p1_e4"}),
+    # (gemma3: attn_wo_qkn_tiles takes whole ranges only -- the attention with q_norm / k_norm inside, between the two GEMVs)
+    ("gemma-7b", 2040): ({"mc_attn_fused_qkn_bfloat"}, set(QKV_WO)),
+    # S = 1000: 16 ranges per kv head, as at 1024, and the same form as there -- so the steps up to the end of the cache are held BIT FOR BIT to a
+    # decoder with S = 1024 on the same rows (kv_len 996 .. 1000: the last range 40 slots long) instead of the oracle: measured at 4.7e-3 (int4),
+    # 1.04 x two scaled steps (int8) and 3.95e-3 (Llama-3.2-1B) from the oracle vector-wise, where run_injected allows 3.9e-3 -- the distance of
+    # these forms at a context of 1000 slots, whole ranges or not (see test_llama3_8b_int8_three_launch_layer_at_short_and_mid_contexts: 4.3e-3
+    # at position 300 with either form).
+    #   int4: 24 of the kv head's 384 wq|wk|wv row pairs per range, the block holds 16 -- the GEMV, then attention + Wo
+    ("llama3-8b-int4", 1000): ({"mc_attn_wo_i4_bfloat_hd128_k2", "mc_gemv_i4_bfloat_lin2_p1_e4"}, {"mc_attn_qkv_wo_i4_bfloat_hd128_k2_q2"}, 1024),
+    # (int8: 24 pairs per range against 16 -- the five launches)
+    ("llama3-8b-int8", 1000): ({"mc_attn_fused_bfloat", "mc_gemv_i8_bfloat_ling4_p1_e4"}, set(QKV_WO), 1024),
+    # (plain bfloat: 12 pairs per range against 8 -- the block leaves the one launch)
+    ("llama3.2-1b", 1000): ({"mc_gemv_w_bfloat_ling4_p1_e4", "mc_attn_fused_bfloat"}, set(QKV_WO), 1024),
+    ("tinyllama", 1000): ({"mc_gemv_w_bfloat_ling4_p1_e4", "mc_attn_fused_bfloat"}, set(QKV_WO)),
+    # (gemma3: 16 x 16 workgroups, one per CU -- the rope launch, then attention + Wo in one launch: round 4's form)
+    ("gemma-7b", 1000): ({"mc_attn_wo_i4_bfloat_hd256_k2", "mc_rope_kv_bfloat"}, set(QKV_WO)),
+    # Where the wide ranges are refused (decoder.cc: attn_qkv_wo_i4_wide_tiles, attn_qkv_wo_w_tiles, attn_qkv_wo_i8_tiles take S % (64 t) == 0 only;
+    # attn_fused_t2 an even nsplit).  What the decoder takes today:
+    #   S = 4040 (63 ranges and 8 slots: nsplit 64) and 4032 (63 whole ranges, odd): 64 / 63 x 8 workgroups of the one-launch attention between
+    #   the wq|wk|wv and Wo GEMVs -- five launches per layer, where 4096 takes the three of `_t2`
+    ("llama3-8b-int4", 4040): ({"mc_attn_fused_bfloat", "mc_gemv_i4_bfloat_lin2_p1_e4"}, set(QKV_WO)),
+    ("llama3-8b-int4", 4032): ({"mc_attn_fused_bfloat", "mc_gemv_i4_bfloat_lin2_p1_e4"}, set(QKV_WO)),
+    ("llama3.2-1b", 4040): ({"mc_gemv_w_bfloat_ling4_p1_e4", "mc_attn_fused_bfloat"}, set(QKV_WO)),
+    ("llama3.2-1b", 4032): ({"mc_gemv_w_bfloat_ling4_p1_e4", "mc_attn_fused_bfloat"}, set(QKV_WO)),
+    #   S = 8120 int8 (nsplit 127, odd; 1016 workgroups of 64 slots are more than can wait for one another): scores + P.V in two launches, the P.V
+    #   context ranges folded into the Wo GEMV -- where 8192 takes the three launches of `_t4`
+    ("llama3-8b-int8", 8120): ({"mc_attn_scores_bfloat", "mc_attn_pv_bfloat", "mc_gemv_i8_bfloat_ling4_p3_e1"}, set(QKV_WO) | {"mc_attn_fused_bfloat", "mc_attn_fused_t2_bfloat"}),
+}
+
+
+@pytest.mark.parametrize("shape,S", list(PARTIAL_RANGE_FORMS))
+def test_contexts_of_partial_ranges_against_the_oracle_and_the_form_they_take(acc, shape, S):
+    import metalchat_amd as mc
+
+    cfg, weights, fmt, bounds = _shape_cfg(shape, S)
+    want, never, *whole = PARTIAL_RANGE_FORMS[shape, S]
+    if not whole:
+        names = set()
+        agree = run_injected(acc, cfg, weights, S - 5, 12, fmt, what=f"{shape} S={S}", launched=names, **bounds)
+        assert agree >= 10
+    else:
+        out = {}
+        for cap in (S, whole[0]):
+            dec = mc.Decoder(acc, **mg.decoder_kwargs(dict(cfg, max_seq_len=cap), **fmt))
+            dec.init_synthetic(SEED)
+            dec.set_taps(True)
+            dec.launch_log(True)
+            k, v = random_cache(cfg, S - 5, 100)
+            dec.import_kv(0, k, v)
+            tok, rows = 7, []
+            for pos in range(S - 5, S):
+                tok = dec.step(tok, pos)
+                rows.append((tok, dec.logits().copy(), dec.hidden(0).copy(), dec.export_kv(0)))
+            out[cap] = (rows, set(dec.launched()))
+            dec.release()
+        names = out[S][1]
+        assert out[whole[0]][1] == names, (sorted(names), sorted(out[whole[0]][1]))
+        for i, ((ta, la, ha, (ka, va)), (tb, lb, hb, (kb, vb))) in enumerate(zip(out[S][0], out[whole[0]][0])):
+            assert ta == tb, i
+            parity.exact(ha, hb, f"{shape} kv_len {S - 4 + i}: hidden[0], S = {S} vs {whole[0]}")
+            parity.exact(la, lb, f"{shape} kv_len {S - 4 + i}: logits")
+            parity.exact(ka, kb, f"{shape} kv_len {S - 4 + i}: K cache")
+            parity.exact(va, vb, f"{shape} kv_len {S - 4 + i}: V cache")
+    assert want <= names, sorted(names)
+    assert not [n for n in names if n.startswith(tuple(never))], sorted(names)

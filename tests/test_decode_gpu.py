@@ -88,6 +88,23 @@ def test_sink_cache_ring_past_max_seq_len(acc, dt):
     assert agree >= 38
 
 
+def test_decoder_config_validation_of_the_cache_length(acc):
+    # decoder.cc mc_decoder_create: max_seq_len a positive multiple of 8, a sink prefix shorter than the cache
+    import metalchat_amd as mc
+
+    for S in (2044, 0):
+        with pytest.raises(mc.McError, match="max_seq_len must be a multiple of 8"):
+            mc.Decoder(acc, **mg.decoder_kwargs(mg.tiny_cfg(BF16, max_seq_len=S, n_layers=1)))
+    for pre in (16, 17):
+        with pytest.raises(mc.McError, match="sink prefix must be shorter than the cache"):
+            mc.Decoder(acc, **mg.decoder_kwargs(mg.tiny_cfg(BF16, max_seq_len=16, n_layers=1, sink_pre_len=pre)))
+    # the smallest legal cache (8 slots, pre_len = bit_width(8) - 1 = 3: one range of 64 slots holding 8) decodes past its end against the oracle
+    cfg = mg.tiny_cfg(BF16, max_seq_len=8, n_layers=1)
+    weights = mg.make_model(cfg, seed=19, quant="i4", group=32)
+    agree, _ = run_pair(acc, cfg, weights, 20, dict(weight_format=2, group_size=32), rel_hidden=5e-3, rel_logits=5e-3)
+    assert agree >= 18
+
+
 @pytest.mark.parametrize("dt,ranges", [(F32, 3), (BF16, 3), (BF16, 8)])
 def test_pv_context_ranges(acc, dt, ranges, monkeypatch):
     # long contexts split P.V over ranges of cache slots (fp32 partials + one reduce launch);

@@ -41,7 +41,7 @@ def tol(dt):
     return (1e-4, 1.0) if dt == F32 else (7.8e-3, 0.7)
 
 
-def check_against_oracle(acc, cfg, weights, dec_over, tokens, start_pos=0, window=0, follow=3, warm=(), expect_kernel=None):
+def check_against_oracle(acc, cfg, weights, dec_over, tokens, start_pos=0, window=0, follow=3, warm=(), expect_kernel=None, past_end=False):
     import metalchat_amd as mc
 
     dt = cfg["dtype"]
@@ -74,7 +74,7 @@ def check_against_oracle(acc, cfg, weights, dec_over, tokens, start_pos=0, windo
     # decode continues from the prompt
     tok, pos = otok, start_pos + len(tokens)
     for _ in range(follow):
-        if pos >= cfg["max_seq_len"]:
+        if pos >= cfg["max_seq_len"] and not past_end:   # (past_end: the decode steps go on into the sink ring)
             break
         o2, ol2 = om.step(tok, pos)
         g2 = dec.step(tok, pos)
@@ -622,6 +622,58 @@ def test_head_dim_64_prompt_attention_through_lds_tiles(acc, family, heads, kvh,
     check_against_oracle(acc, cfg, weights, dict(weight_format=2, group_size=32), tokens, window=window, follow=2, expect_kernel=kern)
     monkeypatch.setenv("MC_PF_ATTN_HEADS", "2")
     check_against_oracle(acc, cfg, weights, dict(weight_format=2, group_size=32), tokens, window=window, follow=1, expect_kernel="mc_pf_attn2_bfloat_hd64")
+
+
+@pytest.mark.parametrize("hd,heads,kvh,S,start,n,pair", [(128, 8, 2, 440, 0, 440, "1"), (128, 8, 1, 440, 40, 400, "0"),
+                                                          (256, 4, 4, 312, 0, 312, "1"), (256, 4, 2, 312, 40, 272, "0"),
+                                                          (64, 8, 1, 312, 0, 312, "1"), (64, 8, 2, 312, 40, 272, "1")])
+def test_prompt_attention_through_lds_tiles_at_a_cache_of_partial_key_tiles(acc, hd, heads, kvh, S, start, n, pair, monkeypatch):
+    """The LDS-tile prompt attention (mc_pf_attn8_bfloat_hd{128,256,64_h8,64_h4}) with a max_seq_len that is not whole 64-key tiles (440 = 6 tiles and
+    56 keys, 312 = 4 tiles and 56): a prompt that fills the cache exactly and a second chunk behind an earlier context that ends at max_seq_len, so
+    that the last K / V tile straddles the end of the cache (the tile loads clamp there).  The same prompt in a cache of whole tiles (448 / 320) must
+    give the same hidden rows, logits and cache rows BIT FOR BIT; the chunk behind a context is held to the oracle too, with decode steps past the
+    end of the cache (the sink ring)."""
+    import metalchat_amd as mc
+
+    over = dict(dim=256, n_heads=heads, n_kv_heads=kvh, head_dim=hd, ffn_dim=512, n_layers=2, vocab=384, max_seq_len=S)
+    if hd == 128:
+        monkeypatch.setenv("MC_PF_ATTN_HEADS", "8")
+        kern = "mc_pf_attn8_bfloat_hd128"
+    elif hd == 256:
+        over.update(family=1, rope_sliding_theta=10000.0, sliding_stride=2)
+        monkeypatch.setenv("MC_PF_ATTN8_ROWS256", "64")
+        kern = "mc_pf_attn8_bfloat_hd256"
+    else:
+        monkeypatch.setenv("MC_PF_ATTN8_ROWS64", "64")
+        kern = "mc_pf_attn8_bfloat_hd64_h8" if heads // kvh % 8 == 0 else "mc_pf_attn8_bfloat_hd64_h4"
+    monkeypatch.setenv("MC_PF_ATTN8_PAIR", pair)
+    cfg = mg.tiny_cfg(BF16, **over)
+    assert start + n == S and S % 64
+    weights = mg.make_model(cfg, seed=171 + hd, quant="i4", group=32)
+    warm = np.random.default_rng(S + 1).integers(0, cfg["vocab"], start).tolist()
+    tokens = np.random.default_rng(S + n).integers(0, cfg["vocab"], n).tolist()
+    out = {}
+    for cap in (S, (S + 63) // 64 * 64):
+        dec = mc.Decoder(acc, **mg.decoder_kwargs(dict(cfg, max_seq_len=cap), weight_format=2, group_size=32))
+        dec.load_model(weights)
+        dec.set_taps(True)
+        for p, t in enumerate(warm):
+            dec.step(t, p)
+        dec.launch_log(True)
+        tok = dec.prefill(tokens, start, 0)
+        assert kern in set(dec.launched()), (cap, sorted(set(dec.launched())))
+        out[cap] = (tok, dec.logits().copy(), [dec.hidden(l) for l in range(cfg["n_layers"])], [dec.export_kv(l) for l in range(cfg["n_layers"])])
+        dec.release()
+    (ta, la, ha, ca), (tb, lb, hb, cb) = out.values()
+    assert ta == tb
+    parity.exact(la, lb, f"logits, max_seq_len {S} vs whole tiles")
+    for l in range(cfg["n_layers"]):
+        parity.exact(ha[l], hb[l], f"hidden[{l}], max_seq_len {S} vs whole tiles")
+        parity.exact(ca[l][0], cb[l][0], f"K[{l}], max_seq_len {S} vs whole tiles")
+        parity.exact(ca[l][1], cb[l][1], f"V[{l}], max_seq_len {S} vs whole tiles")
+    if start:
+        check_against_oracle(acc, cfg, weights, dict(weight_format=2, group_size=32), tokens, start_pos=start, warm=warm, follow=3,
+                             expect_kernel=kern, past_end=True)
 
 
 def test_gemma_post_norms_fold_into_the_consumer_of_a_split_gemm(acc, monkeypatch):
