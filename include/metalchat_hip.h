@@ -362,6 +362,42 @@ mc_status mc_decoder_weight_ptrs(mc_decoder* d, int32_t layer, const char* name,
                                  void** scales, int32_t* rows, int32_t* in_features,
                                  int32_t* ngroups);
 
+/* ------------------------------------------------------------------------------------------
+ * Part 2b -- batched decode: B <= 8 sequences in lockstep over one decoder's weights.
+ * The reference's layers carry the batch already: nn::attention::operator() takes input[bs, len, dim]
+ * (include/metalchat/nn/attention.h:163-206) and nn::sink_cache holds [max_batch_size, max_seq_len, n_kv_heads, head_dim],
+ * writing cache[0:bs, start_pos:start_pos+len] at ONE start_pos for the whole batch (nn/cache.h:154-215); only nn::llama3
+ * pins max_batch_size = 1 (nn/llama.h:86).  A batch shares the decoder's weights (streamed once per step for all rows, never
+ * copied: mc_decoder_derived_weight_bytes does not change) and owns batch x n_layers caches of its own; the decoder, its
+ * cache and every mc_decoder_* call are untouched.  Launches go to the decoder's stream and its launch log
+ * (mc_decoder_launch_log).  A row's results do not depend on the batch size or on the other rows, bit for bit.  The batch
+ * must be released before its decoder.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct mc_batch mc_batch;
+/* 1 <= batch <= 8.  The decoder must be single-stage (layer_begin = 0, layer_end = n_layers), family llama3, dtype bf16,
+ * qmode exact, weight_format I4 (group % 128 == 0) or T, without LoRA adaptors, head_dim 128 or 64, every linear with
+ * out_features % 16 == 0 and in_features % 1024 == 0; otherwise MC_ERR_INVALID_ARGUMENT naming the reason. */
+mc_status mc_batch_create(mc_decoder* d, int32_t batch, mc_batch** out);
+void mc_batch_release(mc_batch* b);
+int32_t mc_batch_size(const mc_batch* b);
+/* copy the decoder's cache positions [0, n_valid) of every layer into row `row` (prompt once, fork B times);
+ * n_valid <= max_seq_len and <= the positions the decoder holds, and the decoder's cache must not have rolled */
+mc_status mc_batch_fork(mc_batch* b, int32_t row, int32_t n_valid);
+/* test aids, the reference's layout [n_valid, n_kv_heads, head_dim] of T, as mc_decoder_import_kv / export_kv; the batch's
+ * position is shared, so *n_valid of export is the batch's (the last import, fork or step) */
+mc_status mc_batch_import_kv(mc_batch* b, int32_t row, int32_t layer, const void* keys, const void* values, int32_t n_valid);
+mc_status mc_batch_export_kv(mc_batch* b, int32_t row, int32_t layer, void* keys, void* values, int32_t* n_valid);
+/* transform(input[B, 1], start_pos): tokens[B] in, next_tokens[B] out (greedy, or the decoder's sampler per row --
+ * mc_decoder_set_sampler, read at every step).  start_pos + 1 <= max_seq_len: a batch's cache does not roll. */
+mc_status mc_batch_step(mc_batch* b, const int32_t* tokens, int32_t start_pos, int32_t* next_tokens);
+/* n chained lockstep steps on the device, token feedback through HBM, one host sync; tokens_out[n][B];
+ * start_pos + n <= max_seq_len */
+mc_status mc_batch_generate(mc_batch* b, const int32_t* first_tokens, int32_t start_pos, int32_t n, int32_t* tokens_out);
+/* seed pair (i * B + r) % n_pairs for row r of token i of one call (mc_batch_step: i = 0); no pairs = (0, 0) */
+mc_status mc_batch_set_seeds(mc_batch* b, const uint64_t* seeds, int32_t n_pairs);
+/* after a step: [B][vocab] logits of T */
+mc_status mc_batch_get_logits(mc_batch* b, void* logits_T);
+
 /* Host-side helpers shared by tests and the synthetic initialiser. */
 /* value in [-7,7] (bits = 4) or [-127,127] (bits = 8), zero mean, of element (row, col) of matrix `matrix_id` */
 int32_t mc_synth_weight(uint64_t seed, uint32_t matrix_id, uint32_t row, uint32_t col, int32_t bits);

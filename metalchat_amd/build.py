@@ -20,8 +20,9 @@ SO = os.path.join(LIB, "libmetalchat_hip.so")
 
 KERNEL_SOURCES = [os.path.join(CSRC, "kernels", f) for f in (
     "metalchat_kernels.hip", "ref_kernels.hip", "gemv_kernels.hip", "decode_kernels.hip", "attn_block_kernels.hip",
-    "synth_kernels.hip", "sampler_kernels.hip", "prefill_kernels.hip", "common.h", "handoff.h", "gemv.h", "gemv_ksplit.h", "synth.h", "pf_gemm8.h")]
-HOST_SOURCES = [os.path.join(CSRC, f) for f in ("backend.cc", "decoder.cc", "model_io.cc", "text.cc", "json_min.h", "backend_impl.h")] + [
+    "synth_kernels.hip", "sampler_kernels.hip", "prefill_kernels.hip", "batch_kernels.hip", "common.h", "handoff.h", "gemv.h", "gemv_ksplit.h", "synth.h", "pf_gemm8.h")]
+HOST_SOURCES = [os.path.join(CSRC, f) for f in ("backend.cc", "decoder.cc", "batch.cc", "model_io.cc", "text.cc", "json_min.h", "backend_impl.h",
+                                                 "decoder_batch.h")] + [
     os.path.join(CSRC, "kernels", "synth.h"),
     os.path.join(os.path.dirname(HERE), "include", "metalchat_hip.h")]
 
@@ -56,7 +57,7 @@ def build_host(force: bool = False) -> str:
     os.makedirs(LIB, exist_ok=True)
     if force or _stale(SO, HOST_SOURCES):
         cmd = [hipcc(), "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unused-function",
-               os.path.join(CSRC, "backend.cc"), os.path.join(CSRC, "decoder.cc"),
+               os.path.join(CSRC, "backend.cc"), os.path.join(CSRC, "decoder.cc"), os.path.join(CSRC, "batch.cc"),
                os.path.join(CSRC, "model_io.cc"), os.path.join(CSRC, "text.cc"), "-ldl", "-o", SO]
         subprocess.check_call(cmd, cwd=CSRC)
     return SO

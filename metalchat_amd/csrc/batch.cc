@@ -1,0 +1,522 @@
+// Part 2b of include/metalchat_hip.h: batched decode -- B <= 8 sequences in lockstep over one decoder's weights.
+//
+// The reference's layers carry the batch dimension already: nn::attention::operator() takes input[bs, len, dim]
+// (include/metalchat/nn/attention.h:163-206) and nn::sink_cache holds [max_batch_size, max_seq_len, n_kv_heads, head_dim],
+// writing cache[0:bs, start_pos:start_pos+len] at ONE start_pos for the whole batch (nn/cache.h:154-215); only nn::llama3 pins
+// max_batch_size = 1 (nn/llama.h:86).  A batch here shares the decoder's weights (read through decoder_batch.h, never copied)
+// and owns B caches per layer.  Per token and layer it enqueues a fixed sequence of launches (batch_kernels.hip), none of which
+// waits for another workgroup:
+//   rmsnorm, wq|wk|wv, rope + cache write, scores, softmax + P.V, Wo + residual, rmsnorm, w1|w3 + SiLU.mul, w2 + residual
+// then the final norm, the head and the pick (greedy, or the decoder's default sampler) per row.  Every GEMV streams each
+// weight once for all B rows.
+#include "decoder_batch.h"
+
+#include <algorithm>
+#include <cstring>
+#include <memory>
+
+using namespace mcimpl;
+
+namespace {
+
+struct args {
+    std::vector<char> buf;
+    template <typename T> void
+    push(const T& v)
+    {
+        const size_t off = (buf.size() + alignof(T) - 1) / alignof(T) * alignof(T);
+        buf.resize(off + sizeof(T));
+        memcpy(buf.data() + off, &v, sizeof(T));
+    }
+};
+template <typename... A> std::vector<char>
+pack(const A&... a)
+{
+    args p;
+    (p.push(a), ...);
+    return p.buf;
+}
+
+// mirrors step_state (kernels/handoff.h)
+struct step_state_b {
+    int32_t token, pos, kv_len, write_slot, ring_base, step_index, rope_row, rolled, rope_start;
+    uint32_t epoch, err;
+    int32_t pad[1];
+};
+// mirrors sampler_params (kernels/sampler_kernels.hip)
+struct sampler_params_b {
+    uint32_t k, ncand, cap;
+    float inv_temp, top_p;
+    uint32_t nlists, kpad;
+};
+
+constexpr int BATCH_MAX = 8;
+constexpr unsigned BG_THREADS = 512; // mc_b_gemv_*: BG_WAVES = 8
+constexpr unsigned BG_K_UNIT = 1024; // in_features per workgroup slice: 8 waves x 128
+constexpr unsigned PB = 64;          // cache slots per scores workgroup (decode_kernels.hip)
+constexpr uint32_t SAMPLE_CAP = 4096;
+
+uint32_t
+sampler_chunk(uint32_t vocab, uint32_t kpad)
+{
+    uint32_t chunk = std::max(512u, kpad);
+    while (chunk < 2048u && (vocab + chunk - 1) / chunk > 1024u) chunk *= 2;
+    return chunk;
+}
+
+} // namespace
+
+struct mc_batch {
+    mc_decoder* d = nullptr;
+    decoder_parts p;
+    int B = 0;
+    int nsplit = 0;
+    size_t cache_elems = 0; // one row's cache of one layer: n_kv * max_seq * hd
+    std::vector<void*> allocs;
+    void *kc = nullptr, *vt = nullptr;    // [layer][B][n_kv][max_seq][hd], [layer][B][n_kv][hd][max_seq]
+    void *x = nullptr, *xn = nullptr;     // [B][dim]
+    void *qkv = nullptr;                  // [B][(H + 2 KV) hd]
+    void *q = nullptr, *att = nullptr;    // [B][H hd]
+    void *gate = nullptr;                 // [B][ffn]
+    void *logits = nullptr;               // [B][vocab]
+    float *expv = nullptr, *psum = nullptr; // [B][H][max_seq], [B][H][nsplit]
+    float *fcos = nullptr, *fsin = nullptr; // rope table rows [0, max_seq)
+    step_state_b* st = nullptr;           // the shared position
+    step_state_b* rows = nullptr;         // [B]: token and step_index of each row
+    uint64_t* cand = nullptr;             // [B][lists * kpad]
+    size_t cand_per_row = 0;
+    uint64_t* seeds = nullptr;
+    int n_seed_pairs = 0, seed_cap = 0;
+    int32_t* tokens_dev = nullptr;
+    int tokens_cap = 0;
+    std::vector<step_state_b> rows_host;
+
+    ~mc_batch()
+    {
+        (void)hipSetDevice(p.ordinal);
+        (void)hipStreamSynchronize(p.stream);
+        for (void* a : allocs) (void)hipFree(a);
+    }
+
+    template <typename P> mc_status
+    alloc(P** ptr, size_t bytes)
+    {
+        void* v = nullptr;
+        hipError_t e = hipMalloc(&v, bytes ? bytes : 16);
+        if (e != hipSuccess)
+            return fail(MC_ERR_ALLOC, std::string("hardware_memory_allocator: failed to allocate ") + std::to_string(bytes) +
+                                          " bytes: " + hipGetErrorString(e));
+        allocs.push_back(v);
+        MC_HIP(hipMemsetAsync(v, 0, bytes ? bytes : 16, p.stream));
+        *ptr = static_cast<P*>(v);
+        return MC_OK;
+    }
+    void
+    free_one(void* v)
+    {
+        auto it = std::find(allocs.begin(), allocs.end(), v);
+        if (it != allocs.end()) allocs.erase(it);
+        (void)hipFree(v);
+    }
+
+    mc_status
+    launch(const std::string& name, unsigned gx, unsigned gy, unsigned gz, unsigned bx, unsigned lds, const std::vector<char>& a)
+    {
+        return decoder_launch(d, name, gx, gy, gz, bx, lds, a);
+    }
+
+    char* kc_of(int layer, int row) const { return (char*)kc + ((size_t)layer * B + row) * cache_elems * 2; }
+    char* vt_of(int layer, int row) const { return (char*)vt + ((size_t)layer * B + row) * cache_elems * 2; }
+
+    // the shared step state at position `pos` (slot = pos: a batch's cache never turns)
+    mc_status
+    set_pos(int pos)
+    {
+        return launch("mc_step_set", 1, 1, 1, 64, 0,
+                      pack(st, (int32_t)-1, (int32_t)pos, (int32_t)p.cfg.max_seq_len, (int32_t)p.pre_len, (int32_t)0, (int32_t)1));
+    }
+
+    mc_status
+    gemv(const batch_linear& L, int epi, const void* xin, void* y, uint32_t ldy)
+    {
+        const std::string name = std::string("mc_b_gemv_") + (L.fmt == MC_WFMT_I4 ? "i4" : "w") + "_bfloat_e" + std::to_string(epi);
+        return launch(name, (unsigned)L.out / 16, 1, 1, BG_THREADS, 0,
+                      pack(L.w, L.scales, xin, y, (uint32_t)L.in, (uint32_t)L.ngroups, (uint32_t)L.group, (uint32_t)B, ldy));
+    }
+    mc_status
+    rmsnorm(const void* xin, const void* w, void* out)
+    {
+        return launch("mc_b_rmsnorm_bfloat", 1, B, 1, 1024, 0, pack(xin, w, out, (uint32_t)p.cfg.dim, p.cfg.norm_eps));
+    }
+
+    // one lockstep token at `pos` for every row; advance: a chained step (row r's step_index moves by B)
+    mc_status
+    enqueue_token(int pos, bool advance)
+    {
+        const mc_decoder_config& c = p.cfg;
+        const int H = c.n_heads, KV = c.n_kv_heads, hd = c.head_dim, n_rep = H / KV;
+        const float scale_T = [&] {
+            // T(attn_scale): the scalar_mul of attention.h:196 is evaluated in T
+            float f = c.attn_scale;
+            uint32_t u;
+            memcpy(&u, &f, 4);
+            u += 0x7fffu + ((u >> 16) & 1u);
+            u &= 0xFFFF0000u;
+            memcpy(&f, &u, 4);
+            return f;
+        }();
+        const uint64_t cstride = cache_elems;
+        mc_status s = set_pos(pos);
+        if (s != MC_OK) return s;
+        const bool q8 = p.emb_fmt != MC_WFMT_T;
+        s = launch("mc_b_embed_bfloat", (c.dim + 255) / 256, B, 1, 256, 0,
+                   pack(q8 ? nullptr : p.emb_table, p.emb_scales, q8 ? p.emb_table : nullptr, x, rows, (uint32_t)c.dim,
+                        (int32_t)(advance ? 1 : 0), (uint32_t)B));
+        if (s != MC_OK) return s;
+        for (size_t li = 0; li < p.layers.size(); li++) {
+            const batch_layer& L = p.layers[li];
+            const int l = (int)li;
+            if ((s = rmsnorm(x, L.attention_norm, xn)) != MC_OK) return s;
+            if ((s = gemv(L.qkv, 0, xn, qkv, (uint32_t)L.qkv.out)) != MC_OK) return s;
+            s = launch("mc_b_rope_kv_bfloat", H + 2 * KV, B, 1, hd / 2, 0,
+                       pack(qkv, q, (void*)kc_of(l, 0), (void*)vt_of(l, 0), fcos, fsin, st, (uint32_t)H, (uint32_t)KV, (uint32_t)hd,
+                            (uint32_t)c.max_seq_len, cstride));
+            if (s != MC_OK) return s;
+            s = launch("mc_b_attn_scores_bfloat", nsplit, KV, B, 256, 0,
+                       pack(q, (void*)kc_of(l, 0), expv, psum, st, (uint32_t)n_rep, (uint32_t)hd, (uint32_t)c.max_seq_len, scale_T,
+                            (uint32_t)nsplit, cstride));
+            if (s != MC_OK) return s;
+            s = launch("mc_b_attn_pv_bfloat", hd / 16, KV, B, 1024, 0,
+                       pack(expv, psum, (void*)vt_of(l, 0), att, st, (uint32_t)n_rep, (uint32_t)hd, (uint32_t)c.max_seq_len,
+                            (uint32_t)nsplit, cstride));
+            if (s != MC_OK) return s;
+            if ((s = gemv(L.wo, 1, att, x, (uint32_t)c.dim)) != MC_OK) return s;
+            if ((s = rmsnorm(x, L.ffn_norm, xn)) != MC_OK) return s;
+            if ((s = gemv(L.w13, 2, xn, gate, (uint32_t)(L.w13.out / 2))) != MC_OK) return s;
+            if ((s = gemv(L.w2, 1, gate, x, (uint32_t)c.dim)) != MC_OK) return s;
+        }
+        if ((s = rmsnorm(x, p.final_norm, xn)) != MC_OK) return s;
+        if ((s = gemv(p.output, 0, xn, logits, (uint32_t)c.vocab)) != MC_OK) return s;
+        const decoder_sampler sm = decoder_sampler_of(d);
+        if (sm.kind == MC_SAMPLER_GREEDY)
+            return launch("mc_b_argmax_bfloat", 1, B, 1, 1024, 0, pack(logits, (uint32_t)c.vocab, rows, tokens_dev));
+        // make_default_sampler per row (sampler_kernels.hip): per-chunk candidates, then one workgroup per row
+        uint32_t kpad = 1;
+        while (kpad < (uint32_t)sm.top_k) kpad *= 2;
+        const uint32_t k = (uint32_t)std::min(sm.top_k, c.vocab);
+        const uint32_t chunk = sampler_chunk((uint32_t)c.vocab, kpad), lists = ((uint32_t)c.vocab + chunk - 1) / chunk;
+        if (lists > 1024u || (size_t)lists * kpad > cand_per_row)
+            return fail(MC_ERR_RUNTIME, "sampler: the fused sampler handles rows of up to 2048 * 1024 logits");
+        s = launch("mc_b_topk_candidates_bfloat", lists, B, 1, 64, 0, pack(logits, (uint32_t)c.vocab, kpad, cand, chunk));
+        if (s != MC_OK) return s;
+        const sampler_params_b sp{k, lists * kpad, SAMPLE_CAP, sm.inv_temp_T, sm.top_p_T, lists, kpad};
+        return launch("mc_b_sample_bfloat", 1, B, 1, 128, SAMPLE_CAP * 8,
+                      pack(cand, sp, seeds, (uint32_t)n_seed_pairs, rows, tokens_dev));
+    }
+
+    // rows' tokens and step indices for token 0 of a call (step_index = r: seed pair r % n_pairs, tokens_out[0][r])
+    mc_status
+    start_rows(const int32_t* tokens)
+    {
+        rows_host.assign(B, step_state_b{});
+        for (int r = 0; r < B; r++) {
+            rows_host[r].token = tokens[r];
+            rows_host[r].step_index = r;
+        }
+        MC_HIP(hipMemcpyAsync(rows, rows_host.data(), sizeof(step_state_b) * B, hipMemcpyHostToDevice, p.stream));
+        return MC_OK;
+    }
+
+    mc_status
+    ensure_tokens(int n)
+    {
+        if (n * B <= tokens_cap) return MC_OK;
+        MC_HIP(hipStreamSynchronize(p.stream));
+        if (tokens_dev) free_one(tokens_dev);
+        tokens_dev = nullptr;
+        tokens_cap = 0;
+        mc_status s = alloc(&tokens_dev, sizeof(int32_t) * (size_t)n * B);
+        if (s != MC_OK) return s;
+        tokens_cap = n * B;
+        return MC_OK;
+    }
+
+    mc_status
+    check_tokens(const int32_t* tokens) const
+    {
+        for (int r = 0; r < B; r++)
+            if (tokens[r] < 0 || tokens[r] >= p.cfg.vocab)
+                return fail(MC_ERR_INVALID_ARGUMENT, "mc_batch: token id outside the vocabulary");
+        return MC_OK;
+    }
+};
+
+namespace {
+
+// the admission predicate of mc_batch_create: "" = admitted, else the reason
+std::string
+refusal(const decoder_parts& p)
+{
+    const mc_decoder_config& c = p.cfg;
+    if (c.family != MC_FAMILY_LLAMA3) return "only llama3 decoders can be batched";
+    if (c.dtype != MC_DTYPE_BF16) return "only bfloat16 decoders can be batched";
+    if (c.layer_begin != 0 || c.layer_end != c.n_layers) return "the decoder must own every layer (a pipeline stage cannot be batched)";
+    if (c.weight_format != MC_WFMT_I4 && c.weight_format != MC_WFMT_T)
+        return "only int4 (group % 128 == 0) and plain bfloat16 weights can be batched";
+    if (c.weight_format == MC_WFMT_I4 && c.group_size % 128 != 0) return "int4 weights need a group size that is a multiple of 128";
+    if (c.qmode != MC_QMODE_EXACT) return "only the exact quantised arithmetic (MC_QMODE_EXACT) can be batched";
+    if (c.head_dim != 128 && c.head_dim != 64) return "head_dim must be 128 or 64";
+    if (c.n_kv_heads <= 0 || c.n_heads % c.n_kv_heads != 0 || c.n_heads / c.n_kv_heads > 16)
+        return "n_heads must be a multiple of n_kv_heads, at most 16 per kv head";
+    if (c.max_seq_len < 64) return "max_seq_len must be at least 64";
+    if (p.emb_fmt != MC_WFMT_T && p.emb_fmt != MC_WFMT_I8) return "unsupported embedding format";
+    auto bad = [&](const batch_linear& L, const char* name) -> std::string {
+        if (L.lora) return std::string("LoRA adaptors are not supported (") + name + ")";
+        if (L.fmt != c.weight_format) return std::string("mixed weight formats (") + name + ")";
+        if (L.out % 16 != 0 || L.in % (int)BG_K_UNIT != 0)
+            return std::string(name) + ": the batched GEMV needs out_features % 16 == 0 and in_features % 1024 == 0";
+        if (L.fmt == MC_WFMT_I4 && L.group % 128 != 0) return std::string(name) + ": int4 group size must be a multiple of 128";
+        return "";
+    };
+    const int H = c.n_heads, KV = c.n_kv_heads, hd = c.head_dim;
+    for (const batch_layer& L : p.layers) {
+        for (auto [lin, name] : {std::pair<const batch_linear*, const char*>{&L.qkv, "wq|wk|wv"}, {&L.wo, "wo"}, {&L.w13, "w1|w3"},
+                                 {&L.w2, "w2"}}) {
+            std::string r = bad(*lin, name);
+            if (!r.empty()) return r;
+        }
+        if (L.qkv.out != (H + 2 * KV) * hd || L.qkv.in != c.dim || L.wo.in != H * hd || L.wo.out != c.dim ||
+            L.w13.out % 32 != 0 || L.w13.in != c.dim || L.w2.in != L.w13.out / 2 || L.w2.out != c.dim)
+            return "layer shapes do not chain";
+    }
+    std::string r = bad(p.output, "output");
+    if (!r.empty()) return r;
+    if (p.output.out != c.vocab || p.output.in != c.dim) return "output head shape";
+    return "";
+}
+
+mc_status
+find_row(mc_batch* b, int32_t row, int32_t layer, const char* what)
+{
+    if (!b) return fail(MC_ERR_INVALID_ARGUMENT, std::string(what) + ": null argument");
+    if (row < 0 || row >= b->B) return fail(MC_ERR_INVALID_ARGUMENT, std::string(what) + ": row out of range");
+    if (layer < 0 || layer >= (int)b->p.layers.size()) return fail(MC_ERR_INVALID_ARGUMENT, std::string(what) + ": layer out of range");
+    return MC_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+mc_status
+mc_batch_create(mc_decoder* d, int32_t batch, mc_batch** out)
+{
+    if (!d || !out) return fail(MC_ERR_INVALID_ARGUMENT, "mc_batch_create: null argument");
+    if (batch < 1 || batch > BATCH_MAX) return fail(MC_ERR_INVALID_ARGUMENT, "mc_batch_create: batch must lie in [1, 8]");
+    *out = nullptr;
+    decoder_parts parts;
+    mc_status s = decoder_parts_of(d, &parts);
+    if (s != MC_OK) return s;
+    const std::string why = refusal(parts);
+    if (!why.empty()) return fail(MC_ERR_INVALID_ARGUMENT, "mc_batch_create: " + why);
+    MC_HIP(hipSetDevice(parts.ordinal));
+    std::unique_ptr<mc_batch> b(new mc_batch);
+    b->d = d;
+    b->p = parts;
+    b->B = batch;
+    const mc_decoder_config& c = parts.cfg;
+    const int H = c.n_heads, KV = c.n_kv_heads, hd = c.head_dim, L = (int)parts.layers.size();
+    b->nsplit = (c.max_seq_len + PB - 1) / PB;
+    b->cache_elems = (size_t)KV * c.max_seq_len * hd;
+    const size_t cache_bytes = (size_t)L * batch * b->cache_elems * 2;
+    const int ffn = parts.layers.empty() ? 0 : parts.layers[0].w13.out / 2;
+    const uint32_t lists512 = ((uint32_t)c.vocab + 511) / 512;
+    b->cand_per_row = (size_t)std::max(lists512, 1u) * 128;
+    if ((s = b->alloc(&b->kc, cache_bytes)) != MC_OK || (s = b->alloc(&b->vt, cache_bytes)) != MC_OK ||
+        (s = b->alloc(&b->x, (size_t)batch * c.dim * 2)) != MC_OK || (s = b->alloc(&b->xn, (size_t)batch * c.dim * 2)) != MC_OK ||
+        (s = b->alloc(&b->qkv, (size_t)batch * (H + 2 * KV) * hd * 2)) != MC_OK ||
+        (s = b->alloc(&b->q, (size_t)batch * H * hd * 2)) != MC_OK || (s = b->alloc(&b->att, (size_t)batch * H * hd * 2)) != MC_OK ||
+        (s = b->alloc(&b->gate, (size_t)batch * ffn * 2)) != MC_OK ||
+        (s = b->alloc(&b->logits, (size_t)batch * c.vocab * 2)) != MC_OK ||
+        (s = b->alloc(&b->expv, sizeof(float) * batch * H * c.max_seq_len)) != MC_OK ||
+        (s = b->alloc(&b->psum, sizeof(float) * batch * H * b->nsplit)) != MC_OK ||
+        (s = b->alloc(&b->fcos, sizeof(float) * c.max_seq_len * (hd / 2))) != MC_OK ||
+        (s = b->alloc(&b->fsin, sizeof(float) * c.max_seq_len * (hd / 2))) != MC_OK ||
+        (s = b->alloc(&b->st, sizeof(step_state_b))) != MC_OK || (s = b->alloc(&b->rows, sizeof(step_state_b) * batch)) != MC_OK ||
+        (s = b->alloc(&b->cand, sizeof(uint64_t) * batch * b->cand_per_row)) != MC_OK)
+        return s;
+    // nn::rope's table for positions [0, max_seq_len) (a row depends on the absolute position only, nn/embedding.h:159-165)
+    s = b->launch("mc_rope_table", (hd / 2 + 63) / 64, c.max_seq_len, 1, 64, 0,
+                  pack(b->fcos, b->fsin, (uint32_t)c.max_seq_len, (uint32_t)hd, (uint32_t)0, c.rope_theta));
+    if (s != MC_OK) return s;
+    MC_HIP(hipStreamSynchronize(parts.stream));
+    *out = b.release();
+    return MC_OK;
+}
+
+void
+mc_batch_release(mc_batch* b)
+{
+    delete b;
+}
+
+int32_t
+mc_batch_size(const mc_batch* b)
+{
+    return b ? b->B : 0;
+}
+
+mc_status
+mc_batch_fork(mc_batch* b, int32_t row, int32_t n_valid)
+{
+    mc_status s = find_row(b, row, 0, "mc_batch_fork");
+    if (s != MC_OK) return s;
+    const mc_decoder_config& c = b->p.cfg;
+    if (n_valid < 1 || n_valid > c.max_seq_len) return fail(MC_ERR_INVALID_ARGUMENT, "mc_batch_fork: n_valid must lie in [1, max_seq_len]");
+    int kv_len = 0;
+    bool rolled = false;
+    if ((s = decoder_cache_state(b->d, &kv_len, &rolled)) != MC_OK) return s;
+    if (rolled) return fail(MC_ERR_INVALID_ARGUMENT, "mc_batch_fork: the decoder's cache has rolled (sink ring turned)");
+    if (n_valid > kv_len) return fail(MC_ERR_INVALID_ARGUMENT, "mc_batch_fork: the decoder's cache holds fewer than n_valid positions");
+    MC_HIP(hipSetDevice(b->p.ordinal));
+    const int KV = c.n_kv_heads, hd = c.head_dim, S = c.max_seq_len;
+    for (size_t l = 0; l < b->p.layers.size(); l++) {
+        const batch_layer& L = b->p.layers[l];
+        // K [kv][pos][hd]: n_valid * hd elements per kv head; Vt [kv * hd][pos]: n_valid elements per row
+        MC_HIP(hipMemcpy2DAsync(b->kc_of((int)l, row), (size_t)S * hd * 2, L.kc, (size_t)S * hd * 2, (size_t)n_valid * hd * 2, KV,
+                                hipMemcpyDeviceToDevice, b->p.stream));
+        MC_HIP(hipMemcpy2DAsync(b->vt_of((int)l, row), (size_t)S * 2, L.vt, (size_t)S * 2, (size_t)n_valid * 2, (size_t)KV * hd,
+                                hipMemcpyDeviceToDevice, b->p.stream));
+    }
+    if ((s = b->set_pos(n_valid - 1)) != MC_OK) return s;
+    MC_HIP(hipStreamSynchronize(b->p.stream));
+    return MC_OK;
+}
+
+mc_status
+mc_batch_import_kv(mc_batch* b, int32_t row, int32_t layer, const void* keys, const void* values, int32_t n_valid)
+{
+    mc_status s = find_row(b, row, layer, "mc_batch_import_kv");
+    if (s != MC_OK) return s;
+    if (!keys || !values) return fail(MC_ERR_INVALID_ARGUMENT, "mc_batch_import_kv: null argument");
+    const mc_decoder_config& c = b->p.cfg;
+    if (n_valid < 1 || n_valid > c.max_seq_len)
+        return fail(MC_ERR_INVALID_ARGUMENT, "mc_batch_import_kv: n_valid must lie in [1, max_seq_len]");
+    MC_HIP(hipSetDevice(b->p.ordinal));
+    const size_t nb = (size_t)n_valid * c.n_kv_heads * c.head_dim * 2;
+    void *kt = nullptr, *vtmp = nullptr;
+    MC_HIP(hipMalloc(&kt, nb));
+    hipError_t e = hipMalloc(&vtmp, nb);
+    if (e == hipSuccess) e = hipMemcpy(kt, keys, nb, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(vtmp, values, nb, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        s = b->launch("mc_kv_import_bfloat", 512, 1, 1, 256, 0,
+                      pack((void*)b->kc_of(layer, row), (void*)b->vt_of(layer, row), (const void*)kt, (const void*)vtmp,
+                           (uint32_t)n_valid, (uint32_t)c.n_kv_heads, (uint32_t)c.head_dim, (uint32_t)c.max_seq_len));
+        if (s == MC_OK) s = b->set_pos(n_valid - 1);
+        e = hipStreamSynchronize(b->p.stream);
+    }
+    (void)hipFree(kt);
+    (void)hipFree(vtmp);
+    if (e != hipSuccess) return hip_fail(e, "mc_batch_import_kv");
+    return s;
+}
+
+mc_status
+mc_batch_export_kv(mc_batch* b, int32_t row, int32_t layer, void* keys, void* values, int32_t* n_valid)
+{
+    mc_status s = find_row(b, row, layer, "mc_batch_export_kv");
+    if (s != MC_OK) return s;
+    const mc_decoder_config& c = b->p.cfg;
+    MC_HIP(hipSetDevice(b->p.ordinal));
+    const size_t bytes = (size_t)c.max_seq_len * c.n_kv_heads * c.head_dim * 2;
+    void *kt = nullptr, *vtmp = nullptr;
+    MC_HIP(hipMalloc(&kt, bytes));
+    hipError_t e = hipMalloc(&vtmp, bytes);
+    step_state_b st{};
+    if (e == hipSuccess) {
+        s = b->launch("mc_kv_export_bfloat", 512, 1, 1, 256, 0,
+                      pack((const void*)b->kc_of(layer, row), (const void*)b->vt_of(layer, row), kt, vtmp, (const void*)b->st,
+                           (uint32_t)c.n_kv_heads, (uint32_t)c.head_dim, (uint32_t)c.max_seq_len, (uint32_t)b->p.pre_len));
+        e = hipStreamSynchronize(b->p.stream);
+        if (s == MC_OK && e == hipSuccess) {
+            e = hipMemcpy(&st, b->st, sizeof st, hipMemcpyDeviceToHost);
+            const size_t nb = (size_t)st.kv_len * c.n_kv_heads * c.head_dim * 2;
+            if (e == hipSuccess && keys) e = hipMemcpy(keys, kt, nb, hipMemcpyDeviceToHost);
+            if (e == hipSuccess && values) e = hipMemcpy(values, vtmp, nb, hipMemcpyDeviceToHost);
+            if (n_valid) *n_valid = st.kv_len;
+        }
+    }
+    (void)hipFree(kt);
+    if (vtmp) (void)hipFree(vtmp);
+    if (e != hipSuccess) return hip_fail(e, "mc_batch_export_kv");
+    return s;
+}
+
+mc_status
+mc_batch_step(mc_batch* b, const int32_t* tokens, int32_t start_pos, int32_t* next_tokens)
+{
+    if (!b || !tokens) return fail(MC_ERR_INVALID_ARGUMENT, "mc_batch_step: null argument");
+    if (start_pos < 0 || start_pos + 1 > b->p.cfg.max_seq_len)
+        return fail(MC_ERR_INVALID_ARGUMENT, "mc_batch_step: start_pos + 1 must not exceed max_seq_len (a batch's cache does not roll)");
+    mc_status s = b->check_tokens(tokens);
+    if (s != MC_OK) return s;
+    MC_HIP(hipSetDevice(b->p.ordinal));
+    if ((s = b->ensure_tokens(1)) != MC_OK || (s = b->start_rows(tokens)) != MC_OK || (s = b->enqueue_token(start_pos, false)) != MC_OK)
+        return s;
+    MC_HIP(hipStreamSynchronize(b->p.stream));
+    if (next_tokens) MC_HIP(hipMemcpy(next_tokens, b->tokens_dev, sizeof(int32_t) * b->B, hipMemcpyDeviceToHost));
+    return MC_OK;
+}
+
+mc_status
+mc_batch_generate(mc_batch* b, const int32_t* first_tokens, int32_t start_pos, int32_t n, int32_t* tokens_out)
+{
+    if (!b || !first_tokens || !tokens_out) return fail(MC_ERR_INVALID_ARGUMENT, "mc_batch_generate: null argument");
+    if (n < 1) return fail(MC_ERR_INVALID_ARGUMENT, "mc_batch_generate: n must be positive");
+    if (start_pos < 0 || (int64_t)start_pos + n > b->p.cfg.max_seq_len)
+        return fail(MC_ERR_INVALID_ARGUMENT, "mc_batch_generate: start_pos + n must not exceed max_seq_len (a batch's cache does not roll)");
+    mc_status s = b->check_tokens(first_tokens);
+    if (s != MC_OK) return s;
+    MC_HIP(hipSetDevice(b->p.ordinal));
+    if ((s = b->ensure_tokens(n)) != MC_OK || (s = b->start_rows(first_tokens)) != MC_OK) return s;
+    for (int i = 0; i < n; i++)
+        if ((s = b->enqueue_token(start_pos + i, i > 0)) != MC_OK) return s;
+    MC_HIP(hipStreamSynchronize(b->p.stream));
+    MC_HIP(hipMemcpy(tokens_out, b->tokens_dev, sizeof(int32_t) * (size_t)n * b->B, hipMemcpyDeviceToHost));
+    return MC_OK;
+}
+
+mc_status
+mc_batch_set_seeds(mc_batch* b, const uint64_t* seeds, int32_t n_pairs)
+{
+    if (!b || (n_pairs > 0 && !seeds) || n_pairs < 0) return fail(MC_ERR_INVALID_ARGUMENT, "mc_batch_set_seeds: bad argument");
+    MC_HIP(hipSetDevice(b->p.ordinal));
+    if (n_pairs > b->seed_cap) {
+        MC_HIP(hipStreamSynchronize(b->p.stream));
+        if (b->seeds) b->free_one(b->seeds);
+        b->seeds = nullptr;
+        b->seed_cap = 0;
+        mc_status s = b->alloc(&b->seeds, sizeof(uint64_t) * 2 * n_pairs);
+        if (s != MC_OK) return s;
+        b->seed_cap = n_pairs;
+    }
+    if (n_pairs > 0) {
+        MC_HIP(hipStreamSynchronize(b->p.stream));
+        MC_HIP(hipMemcpy(b->seeds, seeds, sizeof(uint64_t) * 2 * n_pairs, hipMemcpyHostToDevice));
+    }
+    b->n_seed_pairs = n_pairs;
+    return MC_OK;
+}
+
+mc_status
+mc_batch_get_logits(mc_batch* b, void* logits_T)
+{
+    if (!b || !logits_T) return fail(MC_ERR_INVALID_ARGUMENT, "mc_batch_get_logits: null argument");
+    MC_HIP(hipSetDevice(b->p.ordinal));
+    MC_HIP(hipStreamSynchronize(b->p.stream));
+    MC_HIP(hipMemcpy(logits_T, b->logits, (size_t)b->B * b->p.cfg.vocab * 2, hipMemcpyDeviceToHost));
+    return MC_OK;
+}
+
+} // extern "C"

@@ -12,6 +12,7 @@
 // HBM so successive steps chain without a host round trip, and (optionally) replays one captured
 // hipGraph per token.
 #include "backend_impl.h"
+#include "decoder_batch.h"
 #include "kernels/synth.h"
 
 #include <cmath>
@@ -3819,3 +3820,87 @@ mc_synth_value(uint64_t seed, uint32_t matrix_id, uint32_t index, int32_t kind, 
 }
 
 } // extern "C"
+
+// ------------------------------------------------------------------------------------------------
+// What the batched decode (batch.cc) reads of a decoder: decoder_batch.h
+// ------------------------------------------------------------------------------------------------
+namespace mcimpl {
+
+static batch_linear
+batch_view(const linear_w& L)
+{
+    batch_linear b;
+    b.fmt = L.fmt;
+    b.out = L.out;
+    b.in = L.in;
+    b.group = L.group;
+    b.ngroups = L.ngroups;
+    b.w = L.w;
+    b.scales = L.scales;
+    b.lora = L.lora_cols != 0;
+    return b;
+}
+
+mc_status
+decoder_parts_of(mc_decoder* d, decoder_parts* out)
+{
+    mc_status s = check_ready(d);
+    if (s != MC_OK) return s;
+    out->cfg = d->cfg;
+    out->ordinal = d->dev->ordinal;
+    out->stream = d->stream;
+    out->pre_len = d->pre_len;
+    out->emb_fmt = d->emb_fmt;
+    out->emb_table = d->emb_table;
+    out->emb_scales = d->emb_scales;
+    out->output = batch_view(d->output);
+    out->final_norm = d->final_norm;
+    out->layers.clear();
+    for (const layer_w& L : d->layers) {
+        batch_layer b;
+        b.qkv = batch_view(L.qkv);
+        b.wo = batch_view(L.wo);
+        b.w13 = batch_view(L.w13);
+        b.w2 = batch_view(L.w2);
+        b.attention_norm = L.attention_norm;
+        b.ffn_norm = L.ffn_norm;
+        b.kc = L.kc;
+        b.vt = L.vt;
+        out->layers.push_back(b);
+    }
+    return MC_OK;
+}
+
+decoder_sampler
+decoder_sampler_of(const mc_decoder* d)
+{
+    decoder_sampler s;
+    s.kind = d->sampler_kind;
+    s.top_k = d->top_k;
+    s.inv_temp_T = d->inv_temp_T;
+    s.top_p_T = d->top_p_T;
+    return s;
+}
+
+mc_status
+decoder_cache_state(mc_decoder* d, int* kv_len, bool* rolled)
+{
+    MC_HIP(hipSetDevice(d->dev->ordinal));
+    step_state_h st{};
+    MC_HIP(hipMemcpyAsync(&st, d->state, sizeof st, hipMemcpyDeviceToHost, d->stream));
+    MC_HIP(hipStreamSynchronize(d->stream));
+    *kv_len = st.kv_len;
+    *rolled = d->ring_turned || st.rolled != 0 || st.ring_base != 0;
+    return MC_OK;
+}
+
+mc_status
+decoder_launch(mc_decoder* d, const std::string& name, unsigned gx, unsigned gy, unsigned gz, unsigned bx, unsigned lds,
+               const std::vector<char>& args)
+{
+    arg_pack a;
+    a.buf = args;
+    return d->launch(name, gx, gy, gz, bx, lds, std::move(a));
+}
+
+} // namespace mcimpl

@@ -1,0 +1,53 @@
+// What the batched decode (batch.cc, mc_batch_*) needs from a decoder (decoder.cc): the device addresses of its weights, norms,
+// embedding, head and caches as they lie in HBM, its sampler settings, and its launch path (the launch log included).  Nothing
+// here changes the decoder.
+#pragma once
+
+#include "backend_impl.h"
+
+namespace mcimpl {
+
+// one fused matrix as decoder.cc holds it: rows [out][in] in MC_WFMT_* format, bfloat scales in row quads
+struct batch_linear {
+    int fmt = MC_WFMT_T, out = 0, in = 0, group = 0, ngroups = 0;
+    const void* w = nullptr;
+    const void* scales = nullptr;
+    bool lora = false;
+};
+
+struct batch_layer {
+    batch_linear qkv, wo, w13, w2; // wq|wk|wv (q / k rows with the rotation partners adjacent), wo, w1/w3 interleaved, w2
+    const void* attention_norm = nullptr;
+    const void* ffn_norm = nullptr;
+    const void* kc = nullptr; // the decoder's own cache: K [n_kv][max_seq][hd], V transposed [n_kv][hd][max_seq]
+    const void* vt = nullptr;
+};
+
+struct decoder_parts {
+    mc_decoder_config cfg{};
+    int ordinal = 0;
+    hipStream_t stream = nullptr;
+    int pre_len = 0;
+    int emb_fmt = MC_WFMT_T; // MC_WFMT_T table of T, or MC_WFMT_I8 + one f32 scale per row
+    const void* emb_table = nullptr;
+    const float* emb_scales = nullptr;
+    batch_linear output;
+    const void* final_norm = nullptr;
+    std::vector<batch_layer> layers;
+};
+
+struct decoder_sampler {
+    int kind = MC_SAMPLER_GREEDY, top_k = 50;
+    float inv_temp_T = 0.0f, top_p_T = 0.0f;
+};
+
+// fails with MC_ERR_RUNTIME when the decoder's weights are not all loaded
+mc_status decoder_parts_of(mc_decoder* d, decoder_parts* out);
+decoder_sampler decoder_sampler_of(const mc_decoder* d);
+// the decoder's step state after everything enqueued so far (synchronises): valid cache rows and whether the ring has turned
+mc_status decoder_cache_state(mc_decoder* d, int* kv_len, bool* rolled);
+// a launch on the decoder's stream through its launch path (named ranges, mc_decoder_launch_log); args: the packed kernel arguments
+mc_status decoder_launch(mc_decoder* d, const std::string& name, unsigned gx, unsigned gy, unsigned gz, unsigned bx, unsigned lds,
+                         const std::vector<char>& args);
+
+} // namespace mcimpl

@@ -449,7 +449,7 @@ softmax_inv(const float* __restrict__ psum, float* inv_s, uint32_t kv, uint32_t 
 
 __device__ __forceinline__ void
 pv_finish_store(const f32x4_t& acc, float* part, void* out, int tbytes, uint32_t kv, uint32_t n_rep,
-                uint32_t hd, uint32_t db, float* parts, uint32_t n_heads)
+                uint32_t hd, uint32_t db, float* parts, uint32_t n_heads, uint32_t range, uint32_t nranges)
 {
     const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
     const uint32_t col = lane & 15, c = lane >> 4;
@@ -461,17 +461,18 @@ pv_finish_store(const f32x4_t& acc, float* part, void* out, int tbytes, uint32_t
         float v = part[(0 * 16 + head) * 16 + d];
         for (uint32_t w = 1; w < nw; w++) v += part[(w * 16 + head) * 16 + d]; // wave order
         const size_t o = (size_t)(kv * n_rep + head) * hd + db * 16 + d;
-        if (gridDim.z > 1) parts[(size_t)blockIdx.z * n_heads * hd + o] = v;
+        if (nranges > 1) parts[(size_t)range * n_heads * hd + o] = v;
         else if (tbytes == 2) static_cast<bf16_t*>(out)[o] = f2bf(v);
         else static_cast<float*>(out)[o] = v;
     }
 }
 
-extern "C" __global__ void __launch_bounds__(1024)
-mc_attn_pv_bfloat(const float* __restrict__ expv, const float* __restrict__ psum,
-                  const bf16_t* __restrict__ vt, bf16_t* __restrict__ out, const step_state* st,
-                  uint32_t n_rep, uint32_t hd, uint32_t max_seq, uint32_t nsplit, float* __restrict__ parts,
-                  uint32_t n_heads)
+// (range, nranges): this workgroup's context range and their count -- blockIdx.z / gridDim.z of mc_attn_pv_bfloat; the
+// batched form (batch_kernels.hip) has one range and its batch row on z
+__device__ __forceinline__ void
+attn_pv_bf_body(const float* __restrict__ expv, const float* __restrict__ psum, const bf16_t* __restrict__ vt,
+                bf16_t* __restrict__ out, const step_state* st, uint32_t n_rep, uint32_t hd, uint32_t max_seq,
+                uint32_t nsplit, float* __restrict__ parts, uint32_t n_heads, uint32_t range, uint32_t nranges)
 {
     __shared__ float part[16 * 16 * 16]; // up to 16 waves
     const uint32_t S = (uint32_t)st->kv_len;
@@ -483,8 +484,8 @@ mc_attn_pv_bfloat(const float* __restrict__ expv, const float* __restrict__ psum
     const float* erow = expv + (size_t)(kv * n_rep + col) * max_seq;
     const bf16_t* vrow = vt + ((size_t)kv * hd + db * 16 + col) * max_seq;
     const uint32_t nk_all = (S + 31) / 32;
-    const uint32_t kper = ((max_seq + 31) / 32 + gridDim.z - 1) / gridDim.z; // k-steps per context range
-    const uint32_t kbeg = blockIdx.z * kper, nk = min(nk_all, kbeg + kper);
+    const uint32_t kper = ((max_seq + 31) / 32 + nranges - 1) / nranges; // k-steps per context range
+    const uint32_t kbeg = range * kper, nk = min(nk_all, kbeg + kper);
 
     f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
     // four k-steps of this wave per round: all loads first, then the MFMAs.  The first round is
@@ -528,7 +529,15 @@ mc_attn_pv_bfloat(const float* __restrict__ expv, const float* __restrict__ psum
         t0 += 4 * nw;
         if (t0 < nk) request(t0);
     }
-    pv_finish_store(acc, part, out, 2, kv, n_rep, hd, db, parts, n_heads);
+    pv_finish_store(acc, part, out, 2, kv, n_rep, hd, db, parts, n_heads, range, nranges);
+}
+extern "C" __global__ void __launch_bounds__(1024)
+mc_attn_pv_bfloat(const float* __restrict__ expv, const float* __restrict__ psum,
+                  const bf16_t* __restrict__ vt, bf16_t* __restrict__ out, const step_state* st,
+                  uint32_t n_rep, uint32_t hd, uint32_t max_seq, uint32_t nsplit, float* __restrict__ parts,
+                  uint32_t n_heads)
+{
+    attn_pv_bf_body(expv, psum, vt, out, st, n_rep, hd, max_seq, nsplit, parts, n_heads, blockIdx.z, gridDim.z);
 }
 
 // T = float.  k-step = 16 slots: lane (col, c) holds slots p0 + 4c + i; MFMA i contracts slot
@@ -575,7 +584,7 @@ mc_attn_pv_float(const float* __restrict__ expv, const float* __restrict__ psum,
             acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a3, vb[u].w, acc, 0, 0, 0);
         }
     }
-    pv_finish_store(acc, part, out, 4, kv, n_rep, hd, db, parts, n_heads);
+    pv_finish_store(acc, part, out, 4, kv, n_rep, hd, db, parts, n_heads, blockIdx.z, gridDim.z);
 }
 
 // out[i] = T(sum over context ranges of parts[r][i]), ranges added in order

@@ -8,3 +8,4 @@
 #include "synth_kernels.hip"
 #include "sampler_kernels.hip"
 #include "prefill_kernels.hip"
+#include "batch_kernels.hip"

@@ -189,6 +189,16 @@ def capi() -> C.CDLL:
         "mc_interpreter_read": (i32, [vp, i32, C.c_char_p, sz, C.POINTER(sz), C.POINTER(i32), sz, C.POINTER(sz)]),
         "mc_interpreter_start_pos": (sz, [vp]),
         "mc_interpreter_pending": (i32, [vp, C.POINTER(i32), sz, C.POINTER(sz)]),
+        "mc_batch_create": (i32, [vp, i32, pvp]),
+        "mc_batch_release": (None, [vp]),
+        "mc_batch_size": (i32, [vp]),
+        "mc_batch_fork": (i32, [vp, i32, i32]),
+        "mc_batch_import_kv": (i32, [vp, i32, i32, vp, vp, i32]),
+        "mc_batch_export_kv": (i32, [vp, i32, i32, vp, vp, C.POINTER(i32)]),
+        "mc_batch_step": (i32, [vp, C.POINTER(i32), i32, C.POINTER(i32)]),
+        "mc_batch_generate": (i32, [vp, C.POINTER(i32), i32, i32, C.POINTER(i32)]),
+        "mc_batch_set_seeds": (i32, [vp, C.POINTER(u64), i32]),
+        "mc_batch_get_logits": (i32, [vp, vp]),
         "mc_synth_weight": (i32, [u64, u32, u32, u32, i32]),
         "mc_synth_scale": (f32, [u64, u32, u32, u32, i32, i32]),
         "mc_synth_value": (f32, [u64, u32, u32, i32, u32]),
@@ -754,6 +764,81 @@ class Decoder:
     def release(self):
         if self._h:
             capi().mc_decoder_release(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.release()
+        except Exception:
+            pass
+
+
+class Batch:
+    """Batched decode (Part 2b of the C ABI): B <= 8 sequences in lockstep over `decoder`'s weights, each with its own
+    cache (nn::attention with input[bs, 1, dim], include/metalchat/nn/attention.h:163-206).  Keeps the decoder alive."""
+
+    def __init__(self, decoder: Decoder, batch: int):
+        self.decoder = decoder
+        self.B = batch
+        self.cfg = decoder.cfg
+        self.np_T = decoder.np_T
+        self._h = C.c_void_p()
+        _check(capi().mc_batch_create(decoder._h, batch, C.byref(self._h)))
+
+    def size(self) -> int:
+        return capi().mc_batch_size(self._h)
+
+    def _tokens(self, tokens) -> np.ndarray:
+        t = np.ascontiguousarray(tokens, dtype=np.int32)
+        assert t.shape == (self.B,)
+        return t
+
+    def fork(self, row: int, n_valid: int):
+        """the decoder's cache positions [0, n_valid) of every layer into row `row`"""
+        _check(capi().mc_batch_fork(self._h, row, n_valid))
+
+    def import_kv(self, row: int, layer: int, keys: np.ndarray, values: np.ndarray):
+        k = np.ascontiguousarray(keys, dtype=self.np_T)
+        v = np.ascontiguousarray(values, dtype=self.np_T)
+        assert k.shape == v.shape and k.shape[1:] == (self.cfg["n_kv_heads"], self.cfg["head_dim"])
+        _check(capi().mc_batch_import_kv(self._h, row, layer, _np_ptr(k), _np_ptr(v), k.shape[0]))
+
+    def export_kv(self, row: int, layer: int):
+        c = self.cfg
+        shape = (c["max_seq_len"], c["n_kv_heads"], c["head_dim"])
+        k = np.zeros(shape, dtype=self.np_T)
+        v = np.zeros(shape, dtype=self.np_T)
+        n = C.c_int32()
+        _check(capi().mc_batch_export_kv(self._h, row, layer, _np_ptr(k), _np_ptr(v), C.byref(n)))
+        return k[: n.value], v[: n.value]
+
+    def step(self, tokens, start_pos: int) -> np.ndarray:
+        t = self._tokens(tokens)
+        out = np.zeros(self.B, dtype=np.int32)
+        _check(capi().mc_batch_step(self._h, t.ctypes.data_as(C.POINTER(C.c_int32)), start_pos,
+                                    out.ctypes.data_as(C.POINTER(C.c_int32))))
+        return out
+
+    def generate(self, first_tokens, start_pos: int, n: int) -> np.ndarray:
+        """n chained lockstep steps; returns tokens[n][B]"""
+        t = self._tokens(first_tokens)
+        out = np.zeros((n, self.B), dtype=np.int32)
+        _check(capi().mc_batch_generate(self._h, t.ctypes.data_as(C.POINTER(C.c_int32)), start_pos, n,
+                                        out.ctypes.data_as(C.POINTER(C.c_int32))))
+        return out
+
+    def set_seeds(self, pairs):
+        a = np.ascontiguousarray(np.asarray(pairs, dtype=np.uint64).reshape(-1, 2))
+        _check(capi().mc_batch_set_seeds(self._h, a.ctypes.data_as(C.POINTER(C.c_uint64)), a.shape[0]))
+
+    def logits(self) -> np.ndarray:
+        out = np.empty((self.B, self.cfg["vocab"]), dtype=self.np_T)
+        _check(capi().mc_batch_get_logits(self._h, _np_ptr(out)))
+        return out
+
+    def release(self):
+        if self._h:
+            capi().mc_batch_release(self._h)
             self._h = None
 
     def __del__(self):
