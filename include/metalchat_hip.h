@@ -398,6 +398,34 @@ mc_status mc_batch_set_seeds(mc_batch* b, const uint64_t* seeds, int32_t n_pairs
 /* after a step: [B][vocab] logits of T */
 mc_status mc_batch_get_logits(mc_batch* b, void* logits_T);
 
+/* ================================================================================================
+ * Part 2c -- ragged rows: the rows of an mc_batch, each at a position of its own.
+ * Several chats have prompts of different lengths, finish at different times and arrive at different times.  These calls
+ * decode every row at its own position, stop each row on its own stop id or at the end of its cache without ending the call
+ * for the others, and leave rows idle (position -1: their caches, lengths and state are not touched, their outputs are -1),
+ * so that a finished row can be refilled by a fork while the other rows keep their caches.
+ * The batch keeps each row's valid cache length: 0 at creation; n_valid after a fork or an import of that row; start_pos +
+ * steps for every row after a lockstep step or generate; positions[r] + tokens produced after a ragged call.  An active row
+ * needs 0 <= positions[r] <= its length and positions[r] < max_seq_len (a position below the length rewinds the row), and a
+ * token of the vocabulary; anything else -- or no active row, n < 1, n_stop < 0, a null pointer -- is refused with
+ * MC_ERR_INVALID_ARGUMENT naming the row and the reason before anything is enqueued.
+ * Sampling is the decoder's sampler, read at every call; token i of row r uses seed pair (i * B + r) % n_pairs, as a
+ * lockstep call does, so a ragged call whose rows all share one position computes the lockstep call's tokens, logits and
+ * K/V bit for bit.  Ragged calls do not move the lockstep calls' shared position.
+ * ------------------------------------------------------------------------------------------ */
+/* one step of every active row at positions[r]; next_tokens[B] (may be null): the picks, -1 for an idle row */
+mc_status mc_ragged_step(mc_batch* b, const int32_t* tokens, const int32_t* positions, int32_t* next_tokens);
+/* up to n chained steps per row on the device, one host sync.  Row r stops after its first produced token that is one of
+ * stop_ids[0, n_stop) (that token is written), or once it has written cache position max_seq_len - 1; the call itself is
+ * not refused for it.  tokens_out[n][B]: -1 after a row stopped and for an idle row; lengths[B]: the tokens row r produced
+ * (its cache length becomes positions[r] + lengths[r]). */
+mc_status mc_ragged_generate(mc_batch* b, const int32_t* first_tokens, const int32_t* positions, int32_t n,
+                             const int32_t* stop_ids, int32_t n_stop, int32_t* tokens_out, int32_t* lengths);
+/* the valid cache length of every row: lengths[B] */
+mc_status mc_ragged_lengths(const mc_batch* b, int32_t* lengths);
+/* row `row`'s own valid positions [0, length) in the layout of the batch's export_kv; *n_valid = the row's length */
+mc_status mc_ragged_export_kv(mc_batch* b, int32_t row, int32_t layer, void* keys, void* values, int32_t* n_valid);
+
 /* Host-side helpers shared by tests and the synthetic initialiser. */
 /* value in [-7,7] (bits = 4) or [-127,127] (bits = 8), zero mean, of element (row, col) of matrix `matrix_id` */
 int32_t mc_synth_weight(uint64_t seed, uint32_t matrix_id, uint32_t row, uint32_t col, int32_t bits);

@@ -9,6 +9,9 @@
 //   rmsnorm, wq|wk|wv, rope + cache write, scores, softmax + P.V, Wo + residual, rmsnorm, w1|w3 + SiLU.mul, w2 + residual
 // then the final norm, the head and the pick (greedy, or the decoder's default sampler) per row.  Every GEMV streams each
 // weight once for all B rows.
+// Part 2c (mc_ragged_*) runs the same sequence with every row at a position of its own: the per-row launches read rows[r]
+// instead of the shared state, one small launch (mc_b_rows_begin) starts each step in place of mc_step_set, and a row whose
+// position is -1, or which stopped on a stop id or at the end of its cache, is idle.
 #include "decoder_batch.h"
 
 #include <algorithm>
@@ -82,7 +85,7 @@ struct mc_batch {
     float *expv = nullptr, *psum = nullptr; // [B][H][max_seq], [B][H][nsplit]
     float *fcos = nullptr, *fsin = nullptr; // rope table rows [0, max_seq)
     step_state_b* st = nullptr;           // the shared position
-    step_state_b* rows = nullptr;         // [B]: token and step_index of each row
+    step_state_b* rows = nullptr;         // [B]: token and step_index of each row (ragged calls: the whole state of each row)
     uint64_t* cand = nullptr;             // [B][lists * kpad]
     size_t cand_per_row = 0;
     uint64_t* seeds = nullptr;
@@ -90,6 +93,10 @@ struct mc_batch {
     int32_t* tokens_dev = nullptr;
     int tokens_cap = 0;
     std::vector<step_state_b> rows_host;
+    std::vector<int32_t> lengths;         // [B]: valid cache positions of each row
+    int32_t* stop_dev = nullptr;          // the stop ids of a ragged call
+    int stop_cap = 0;
+    std::vector<int32_t> stop_host;
 
     ~mc_batch()
     {
@@ -149,9 +156,11 @@ struct mc_batch {
         return launch("mc_b_rmsnorm_bfloat", 1, B, 1, 1024, 0, pack(xin, w, out, (uint32_t)p.cfg.dim, p.cfg.norm_eps));
     }
 
-    // one lockstep token at `pos` for every row; advance: a chained step (row r's step_index moves by B)
+    // one lockstep token at `pos` for every row; advance: a chained step (row r's step_index moves by B).
+    // ragged: every row at its own rows[r].pos instead, the same launches with the per-row kernels; `pos` is not used, and
+    // mc_b_rows_begin starts the step (advance: retires the rows that stopped, moves the others on).
     mc_status
-    enqueue_token(int pos, bool advance)
+    enqueue_token(int pos, bool advance, bool ragged = false)
     {
         const mc_decoder_config& c = p.cfg;
         const int H = c.n_heads, KV = c.n_kv_heads, hd = c.head_dim, n_rep = H / KV;
@@ -166,28 +175,40 @@ struct mc_batch {
             return f;
         }();
         const uint64_t cstride = cache_elems;
-        mc_status s = set_pos(pos);
-        if (s != MC_OK) return s;
         const bool q8 = p.emb_fmt != MC_WFMT_T;
-        s = launch("mc_b_embed_bfloat", (c.dim + 255) / 256, B, 1, 256, 0,
-                   pack(q8 ? nullptr : p.emb_table, p.emb_scales, q8 ? p.emb_table : nullptr, x, rows, (uint32_t)c.dim,
-                        (int32_t)(advance ? 1 : 0), (uint32_t)B));
+        const void* emb = q8 ? nullptr : p.emb_table;
+        const void* emb_q8 = q8 ? p.emb_table : nullptr;
+        mc_status s;
+        if (ragged) {
+            s = launch("mc_b_rows_begin", 1, 1, 1, 64, 0,
+                       pack(rows, (const int32_t*)stop_dev, (int32_t)stop_host.size(), (int32_t)c.max_seq_len, (int32_t)B,
+                            (int32_t)(advance ? 1 : 0)));
+            if (s != MC_OK) return s;
+            s = launch("mc_b_embed_rows_bfloat", (c.dim + 255) / 256, B, 1, 256, 0, pack(emb, p.emb_scales, emb_q8, x, rows, (uint32_t)c.dim));
+        } else {
+            if ((s = set_pos(pos)) != MC_OK) return s;
+            s = launch("mc_b_embed_bfloat", (c.dim + 255) / 256, B, 1, 256, 0,
+                       pack(emb, p.emb_scales, emb_q8, x, rows, (uint32_t)c.dim, (int32_t)(advance ? 1 : 0), (uint32_t)B));
+        }
         if (s != MC_OK) return s;
+        // the per-row launches: the lockstep kernel reads the shared state, its _rows form row r's own
+        const std::string sfx = ragged ? "_rows_bfloat" : "_bfloat";
+        const step_state_b* state = ragged ? rows : st;
         for (size_t li = 0; li < p.layers.size(); li++) {
             const batch_layer& L = p.layers[li];
             const int l = (int)li;
             if ((s = rmsnorm(x, L.attention_norm, xn)) != MC_OK) return s;
             if ((s = gemv(L.qkv, 0, xn, qkv, (uint32_t)L.qkv.out)) != MC_OK) return s;
-            s = launch("mc_b_rope_kv_bfloat", H + 2 * KV, B, 1, hd / 2, 0,
-                       pack(qkv, q, (void*)kc_of(l, 0), (void*)vt_of(l, 0), fcos, fsin, st, (uint32_t)H, (uint32_t)KV, (uint32_t)hd,
+            s = launch("mc_b_rope_kv" + sfx, H + 2 * KV, B, 1, hd / 2, 0,
+                       pack(qkv, q, (void*)kc_of(l, 0), (void*)vt_of(l, 0), fcos, fsin, state, (uint32_t)H, (uint32_t)KV, (uint32_t)hd,
                             (uint32_t)c.max_seq_len, cstride));
             if (s != MC_OK) return s;
-            s = launch("mc_b_attn_scores_bfloat", nsplit, KV, B, 256, 0,
-                       pack(q, (void*)kc_of(l, 0), expv, psum, st, (uint32_t)n_rep, (uint32_t)hd, (uint32_t)c.max_seq_len, scale_T,
+            s = launch("mc_b_attn_scores" + sfx, nsplit, KV, B, 256, 0,
+                       pack(q, (void*)kc_of(l, 0), expv, psum, state, (uint32_t)n_rep, (uint32_t)hd, (uint32_t)c.max_seq_len, scale_T,
                             (uint32_t)nsplit, cstride));
             if (s != MC_OK) return s;
-            s = launch("mc_b_attn_pv_bfloat", hd / 16, KV, B, 1024, 0,
-                       pack(expv, psum, (void*)vt_of(l, 0), att, st, (uint32_t)n_rep, (uint32_t)hd, (uint32_t)c.max_seq_len,
+            s = launch("mc_b_attn_pv" + sfx, hd / 16, KV, B, 1024, 0,
+                       pack(expv, psum, (void*)vt_of(l, 0), att, state, (uint32_t)n_rep, (uint32_t)hd, (uint32_t)c.max_seq_len,
                             (uint32_t)nsplit, cstride));
             if (s != MC_OK) return s;
             if ((s = gemv(L.wo, 1, att, x, (uint32_t)c.dim)) != MC_OK) return s;
@@ -199,7 +220,7 @@ struct mc_batch {
         if ((s = gemv(p.output, 0, xn, logits, (uint32_t)c.vocab)) != MC_OK) return s;
         const decoder_sampler sm = decoder_sampler_of(d);
         if (sm.kind == MC_SAMPLER_GREEDY)
-            return launch("mc_b_argmax_bfloat", 1, B, 1, 1024, 0, pack(logits, (uint32_t)c.vocab, rows, tokens_dev));
+            return launch("mc_b_argmax" + sfx, 1, B, 1, 1024, 0, pack(logits, (uint32_t)c.vocab, rows, tokens_dev));
         // make_default_sampler per row (sampler_kernels.hip): per-chunk candidates, then one workgroup per row
         uint32_t kpad = 1;
         while (kpad < (uint32_t)sm.top_k) kpad *= 2;
@@ -210,7 +231,7 @@ struct mc_batch {
         s = launch("mc_b_topk_candidates_bfloat", lists, B, 1, 64, 0, pack(logits, (uint32_t)c.vocab, kpad, cand, chunk));
         if (s != MC_OK) return s;
         const sampler_params_b sp{k, lists * kpad, SAMPLE_CAP, sm.inv_temp_T, sm.top_p_T, lists, kpad};
-        return launch("mc_b_sample_bfloat", 1, B, 1, 128, SAMPLE_CAP * 8,
+        return launch("mc_b_sample" + sfx, 1, B, 1, 128, SAMPLE_CAP * 8,
                       pack(cand, sp, seeds, (uint32_t)n_seed_pairs, rows, tokens_dev));
     }
 
@@ -247,6 +268,57 @@ struct mc_batch {
         for (int r = 0; r < B; r++)
             if (tokens[r] < 0 || tokens[r] >= p.cfg.vocab)
                 return fail(MC_ERR_INVALID_ARGUMENT, "mc_batch: token id outside the vocabulary");
+        return MC_OK;
+    }
+
+    // a ragged call's positions and tokens: -1 = idle, else 0 <= pos <= the row's length and pos < max_seq_len, with a token
+    // of the vocabulary; at least one row active
+    mc_status
+    check_ragged(const char* what, const int32_t* tokens, const int32_t* positions) const
+    {
+        int active = 0;
+        for (int r = 0; r < B; r++) {
+            const int32_t pos = positions[r];
+            const std::string row = std::string(what) + ": row " + std::to_string(r) + ": ";
+            if (pos == -1) continue;
+            if (pos < -1) return fail(MC_ERR_INVALID_ARGUMENT, row + "position below -1 (-1 = idle)");
+            if (pos >= p.cfg.max_seq_len)
+                return fail(MC_ERR_INVALID_ARGUMENT, row + "position " + std::to_string(pos) + " must be below max_seq_len (a batch's cache does not roll)");
+            if (pos > lengths[r])
+                return fail(MC_ERR_INVALID_ARGUMENT, row + "position " + std::to_string(pos) + " is past the row's length " +
+                                                         std::to_string(lengths[r]) + " (its cache has no slots written beyond it)");
+            if (tokens[r] < 0 || tokens[r] >= p.cfg.vocab) return fail(MC_ERR_INVALID_ARGUMENT, row + "token id outside the vocabulary");
+            active++;
+        }
+        if (!active) return fail(MC_ERR_INVALID_ARGUMENT, std::string(what) + ": no active row (every position is -1)");
+        return MC_OK;
+    }
+
+    // token 0 of a ragged call: rows' tokens, positions and step indices (mc_b_rows_begin derives the rest), the stop ids,
+    // and -1 in every slot of tokens_out
+    mc_status
+    start_ragged(const int32_t* tokens, const int32_t* positions, const int32_t* stop_ids, int n_stop, int n)
+    {
+        rows_host.assign(B, step_state_b{});
+        for (int r = 0; r < B; r++) {
+            rows_host[r].pos = positions[r];
+            rows_host[r].token = positions[r] < 0 ? -1 : tokens[r];
+            rows_host[r].step_index = r;
+        }
+        MC_HIP(hipMemcpyAsync(rows, rows_host.data(), sizeof(step_state_b) * B, hipMemcpyHostToDevice, p.stream));
+        stop_host.assign(stop_ids, stop_ids + n_stop);
+        if (n_stop > stop_cap) {
+            MC_HIP(hipStreamSynchronize(p.stream));
+            if (stop_dev) free_one(stop_dev);
+            stop_dev = nullptr;
+            stop_cap = 0;
+            mc_status s = alloc(&stop_dev, sizeof(int32_t) * n_stop);
+            if (s != MC_OK) return s;
+            stop_cap = n_stop;
+        }
+        if (n_stop > 0)
+            MC_HIP(hipMemcpyAsync(stop_dev, stop_host.data(), sizeof(int32_t) * n_stop, hipMemcpyHostToDevice, p.stream));
+        MC_HIP(hipMemsetAsync(tokens_dev, 0xFF, sizeof(int32_t) * (size_t)n * B, p.stream));
         return MC_OK;
     }
 };
@@ -324,6 +396,7 @@ mc_batch_create(mc_decoder* d, int32_t batch, mc_batch** out)
     b->d = d;
     b->p = parts;
     b->B = batch;
+    b->lengths.assign(batch, 0);
     const mc_decoder_config& c = parts.cfg;
     const int H = c.n_heads, KV = c.n_kv_heads, hd = c.head_dim, L = (int)parts.layers.size();
     b->nsplit = (c.max_seq_len + PB - 1) / PB;
@@ -390,6 +463,7 @@ mc_batch_fork(mc_batch* b, int32_t row, int32_t n_valid)
     }
     if ((s = b->set_pos(n_valid - 1)) != MC_OK) return s;
     MC_HIP(hipStreamSynchronize(b->p.stream));
+    b->lengths[row] = n_valid;
     return MC_OK;
 }
 
@@ -419,6 +493,7 @@ mc_batch_import_kv(mc_batch* b, int32_t row, int32_t layer, const void* keys, co
     (void)hipFree(kt);
     (void)hipFree(vtmp);
     if (e != hipSuccess) return hip_fail(e, "mc_batch_import_kv");
+    if (s == MC_OK) b->lengths[row] = n_valid;
     return s;
 }
 
@@ -465,6 +540,7 @@ mc_batch_step(mc_batch* b, const int32_t* tokens, int32_t start_pos, int32_t* ne
     if ((s = b->ensure_tokens(1)) != MC_OK || (s = b->start_rows(tokens)) != MC_OK || (s = b->enqueue_token(start_pos, false)) != MC_OK)
         return s;
     MC_HIP(hipStreamSynchronize(b->p.stream));
+    b->lengths.assign(b->B, start_pos + 1);
     if (next_tokens) MC_HIP(hipMemcpy(next_tokens, b->tokens_dev, sizeof(int32_t) * b->B, hipMemcpyDeviceToHost));
     return MC_OK;
 }
@@ -483,6 +559,7 @@ mc_batch_generate(mc_batch* b, const int32_t* first_tokens, int32_t start_pos, i
     for (int i = 0; i < n; i++)
         if ((s = b->enqueue_token(start_pos + i, i > 0)) != MC_OK) return s;
     MC_HIP(hipStreamSynchronize(b->p.stream));
+    b->lengths.assign(b->B, start_pos + n);
     MC_HIP(hipMemcpy(tokens_out, b->tokens_dev, sizeof(int32_t) * (size_t)n * b->B, hipMemcpyDeviceToHost));
     return MC_OK;
 }
@@ -517,6 +594,94 @@ mc_batch_get_logits(mc_batch* b, void* logits_T)
     MC_HIP(hipStreamSynchronize(b->p.stream));
     MC_HIP(hipMemcpy(logits_T, b->logits, (size_t)b->B * b->p.cfg.vocab * 2, hipMemcpyDeviceToHost));
     return MC_OK;
+}
+
+// ---- Part 2c: ragged rows ----
+
+mc_status
+mc_ragged_step(mc_batch* b, const int32_t* tokens, const int32_t* positions, int32_t* next_tokens)
+{
+    if (!b || !tokens || !positions) return fail(MC_ERR_INVALID_ARGUMENT, "mc_ragged_step: null argument");
+    mc_status s = b->check_ragged("mc_ragged_step", tokens, positions);
+    if (s != MC_OK) return s;
+    MC_HIP(hipSetDevice(b->p.ordinal));
+    if ((s = b->ensure_tokens(1)) != MC_OK || (s = b->start_ragged(tokens, positions, nullptr, 0, 1)) != MC_OK ||
+        (s = b->enqueue_token(0, false, true)) != MC_OK)
+        return s;
+    MC_HIP(hipStreamSynchronize(b->p.stream));
+    for (int r = 0; r < b->B; r++)
+        if (positions[r] >= 0) b->lengths[r] = positions[r] + 1;
+    if (next_tokens) MC_HIP(hipMemcpy(next_tokens, b->tokens_dev, sizeof(int32_t) * b->B, hipMemcpyDeviceToHost));
+    return MC_OK;
+}
+
+mc_status
+mc_ragged_generate(mc_batch* b, const int32_t* first_tokens, const int32_t* positions, int32_t n, const int32_t* stop_ids,
+                   int32_t n_stop, int32_t* tokens_out, int32_t* lengths)
+{
+    if (!b || !first_tokens || !positions || !tokens_out || !lengths || (n_stop > 0 && !stop_ids))
+        return fail(MC_ERR_INVALID_ARGUMENT, "mc_ragged_generate: null argument");
+    if (n < 1) return fail(MC_ERR_INVALID_ARGUMENT, "mc_ragged_generate: n must be positive");
+    if (n_stop < 0) return fail(MC_ERR_INVALID_ARGUMENT, "mc_ragged_generate: n_stop must not be negative");
+    mc_status s = b->check_ragged("mc_ragged_generate", first_tokens, positions);
+    if (s != MC_OK) return s;
+    MC_HIP(hipSetDevice(b->p.ordinal));
+    if ((s = b->ensure_tokens(n)) != MC_OK || (s = b->start_ragged(first_tokens, positions, stop_ids, n_stop, n)) != MC_OK) return s;
+    for (int i = 0; i < n; i++)
+        if ((s = b->enqueue_token(0, i > 0, true)) != MC_OK) return s;
+    MC_HIP(hipStreamSynchronize(b->p.stream));
+    const int B = b->B;
+    MC_HIP(hipMemcpy(tokens_out, b->tokens_dev, sizeof(int32_t) * (size_t)n * B, hipMemcpyDeviceToHost));
+    // a row's tokens are a prefix of its column: -1 from the step after it stopped (an idle row: none)
+    for (int r = 0; r < B; r++) {
+        int32_t produced = 0;
+        while (produced < n && tokens_out[(size_t)produced * B + r] >= 0) produced++;
+        lengths[r] = produced;
+        if (positions[r] >= 0) b->lengths[r] = positions[r] + produced;
+    }
+    return MC_OK;
+}
+
+mc_status
+mc_ragged_lengths(const mc_batch* b, int32_t* lengths)
+{
+    if (!b || !lengths) return fail(MC_ERR_INVALID_ARGUMENT, "mc_ragged_lengths: null argument");
+    std::copy(b->lengths.begin(), b->lengths.end(), lengths);
+    return MC_OK;
+}
+
+mc_status
+mc_ragged_export_kv(mc_batch* b, int32_t row, int32_t layer, void* keys, void* values, int32_t* n_valid)
+{
+    mc_status s = find_row(b, row, layer, "mc_ragged_export_kv");
+    if (s != MC_OK) return s;
+    const mc_decoder_config& c = b->p.cfg;
+    const int32_t n = b->lengths[row];
+    if (n_valid) *n_valid = n;
+    if (n == 0) return MC_OK;
+    MC_HIP(hipSetDevice(b->p.ordinal));
+    // the export kernel reads kv_len (and a ring of 0) from a state of its own: row `row`'s length
+    step_state_b st{};
+    st.kv_len = n;
+    const size_t nb = (size_t)n * c.n_kv_heads * c.head_dim * 2;
+    void *kt = nullptr, *vtmp = nullptr, *stv = nullptr;
+    MC_HIP(hipMalloc(&stv, sizeof st));
+    hipError_t e = hipMalloc(&kt, nb);
+    if (e == hipSuccess) e = hipMalloc(&vtmp, nb);
+    if (e == hipSuccess) e = hipMemcpyAsync(stv, &st, sizeof st, hipMemcpyHostToDevice, b->p.stream);
+    if (e == hipSuccess) {
+        s = b->launch("mc_kv_export_bfloat", 512, 1, 1, 256, 0,
+                      pack((const void*)b->kc_of(layer, row), (const void*)b->vt_of(layer, row), kt, vtmp, (const void*)stv,
+                           (uint32_t)c.n_kv_heads, (uint32_t)c.head_dim, (uint32_t)c.max_seq_len, (uint32_t)b->p.pre_len));
+        e = hipStreamSynchronize(b->p.stream);
+        if (s == MC_OK && e == hipSuccess && keys) e = hipMemcpy(keys, kt, nb, hipMemcpyDeviceToHost);
+        if (s == MC_OK && e == hipSuccess && values) e = hipMemcpy(values, vtmp, nb, hipMemcpyDeviceToHost);
+    }
+    (void)hipFree(stv);
+    if (kt) (void)hipFree(kt);
+    if (vtmp) (void)hipFree(vtmp);
+    if (e != hipSuccess) return hip_fail(e, "mc_ragged_export_kv");
+    return s;
 }
 
 } // extern "C"

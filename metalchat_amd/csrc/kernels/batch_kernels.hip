@@ -216,8 +216,8 @@ mc_b_attn_pv_bfloat(const float* expv, const float* psum, const bf16_t* vt, bf16
 }
 
 // greedy pick per row: the first index of the maximum (make_key: value descending, then lower index), one workgroup per row
-extern "C" __global__ void __launch_bounds__(1024)
-mc_b_argmax_bfloat(const bf16_t* logits, uint32_t n, step_state* rows, int32_t* tokens_out)
+__device__ __forceinline__ void
+argmax_row_body(const bf16_t* logits, uint32_t n, step_state* rows, int32_t* tokens_out)
 {
     __shared__ unsigned long long wk[16];
     const uint32_t r = blockIdx.y;
@@ -233,6 +233,11 @@ mc_b_argmax_bfloat(const bf16_t* logits, uint32_t n, step_state* rows, int32_t* 
         rows[r].token = token;
         if (tokens_out) tokens_out[rows[r].step_index] = token;
     }
+}
+extern "C" __global__ void __launch_bounds__(1024)
+mc_b_argmax_bfloat(const bf16_t* logits, uint32_t n, step_state* rows, int32_t* tokens_out)
+{
+    argmax_row_body(logits, n, rows, tokens_out);
 }
 
 // make_default_sampler per row: launch 1 (grid (lists, B)) and launch 2 (grid (1, B)) of sampler_kernels.hip
@@ -251,6 +256,123 @@ mc_b_sample_bfloat(const uint64_t* cand, sampler_params p, const uint64_t* seeds
                    int32_t* tokens_out)
 {
     const uint32_t r = blockIdx.y;
+    sample_body<BF>(cand + (size_t)r * p.ncand, p, seeds, n_seed_pairs, reinterpret_cast<step_state_s*>(rows + r), tokens_out,
+                    nullptr);
+}
+
+// ------------------------------------------------------------------------------------------
+// Ragged rows (mc_ragged_*, Part 2c): every row at a position of its own.  rows[r] is then row r's whole step state -- pos,
+// kv_len = pos + 1, write_slot = pos and rope_row = pos (a batch's cache never turns and its rope table starts at position 0)
+// -- and rows[r].pos < 0 marks an IDLE row: no launch below reads its token, reads or writes its cache, or writes rows[r] or
+// tokens_out for it.  The launches are thin wrappers over the lockstep kernels' bodies given rows + r for the shared state, so
+// a row at position p computes the bits a lockstep batch computes at p.  The grids are the lockstep grids; an idle row's
+// workgroups exit at once, and scores workgroups past a row's kv_len exit as they always do, so a row costs its own length.
+// ------------------------------------------------------------------------------------------
+__device__ __forceinline__ bool
+row_idle(const step_state* rows, uint32_t r)
+{
+    return rows[r].pos < 0;
+}
+
+// starts a ragged step (in place of the lockstep mc_step_set), one thread per row.  advance = 0 (token 0 of a call): the host
+// wrote .token, .pos and .step_index; the rest is derived.  advance = 1 (a chained step): .token holds the row's previous pick.
+// The row turns idle if that pick is one of stop_ids[0, n_stop) or its last write was slot max_seq - 1; otherwise it moves to
+// pos + 1 and its step_index by B, as the lockstep advance does.
+extern "C" __global__ void __launch_bounds__(64)
+mc_b_rows_begin(step_state* rows, const int32_t* stop_ids, int32_t n_stop, int32_t max_seq, int32_t B, int32_t advance)
+{
+    const int32_t r = (int32_t)threadIdx.x;
+    if (r >= B || row_idle(rows, r)) return;
+    int32_t pos = rows[r].pos;
+    if (advance) {
+        bool stop = pos >= max_seq - 1;
+        const int32_t token = rows[r].token;
+        for (int32_t i = 0; i < n_stop && !stop; i++) stop = token == stop_ids[i];
+        if (stop) {
+            rows[r].pos = -1;
+            return;
+        }
+        pos += 1;
+        rows[r].pos = pos;
+        rows[r].step_index += B;
+    }
+    rows[r].kv_len = pos + 1;
+    rows[r].write_slot = pos;
+    rows[r].rope_row = pos;
+}
+
+// mc_b_embed_bfloat without the advance (mc_b_rows_begin did it); an idle row gets zeros and its token is never read
+extern "C" __global__ void
+mc_b_embed_rows_bfloat(const bf16_t* table, const float* q8_scales, const int8_t* q8_table, bf16_t* out, const step_state* rows,
+                       uint32_t dim)
+{
+    const uint32_t r = blockIdx.y, k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= dim) return;
+    bf16_t v = 0; // +0.0
+    if (!row_idle(rows, r)) {
+        const int32_t token = rows[r].token;
+        if (q8_table) v = f2bf(BF::rt((float)q8_table[(size_t)token * dim + k] * BF::rt(q8_scales[token])));
+        else v = table[(size_t)token * dim + k];
+    }
+    out[(size_t)r * dim + k] = v;
+}
+
+// mc_b_rope_kv_bfloat at row r's own slot and rope row
+extern "C" __global__ void
+mc_b_rope_kv_rows_bfloat(const bf16_t* qkv, bf16_t* q_out, bf16_t* kc, bf16_t* vt, const float* fcos, const float* fsin,
+                         const step_state* rows, uint32_t H, uint32_t KV, uint32_t hd, uint32_t max_seq, uint64_t cache_stride)
+{
+    const uint32_t r = blockIdx.y;
+    if (row_idle(rows, r)) return;
+    rope_kv_body<BF>(qkv + (size_t)r * (H + 2 * KV) * hd, q_out + (size_t)r * H * hd, kc + r * cache_stride, vt + r * cache_stride,
+                     fcos, fsin, nullptr, nullptr, rows + r, H, KV, hd, max_seq, 0.0f, 0.0f);
+}
+
+// mc_b_attn_scores_bfloat over row r's own kv_len
+extern "C" __global__ void __launch_bounds__(256)
+mc_b_attn_scores_rows_bfloat(const bf16_t* q, const bf16_t* kc, float* expv, float* psum, const step_state* rows, uint32_t n_rep,
+                             uint32_t hd, uint32_t max_seq, float scale, uint32_t nsplit, uint64_t cache_stride)
+{
+    const uint32_t r = blockIdx.z, H = gridDim.y * n_rep;
+    if (row_idle(rows, r)) return;
+    const bf16_t* qr = q + (size_t)r * H * hd;
+    const bf16_t* kr = kc + r * cache_stride;
+    float* er = expv + (size_t)r * H * max_seq;
+    float* pr = psum + (size_t)r * H * nsplit;
+    if (hd == 128) attn_scores_bf<128>(qr, kr, er, pr, nullptr, rows + r, n_rep, max_seq, scale, nsplit);
+    else if (hd == 64) attn_scores_bf<64>(qr, kr, er, pr, nullptr, rows + r, n_rep, max_seq, scale, nsplit);
+}
+
+// mc_b_attn_pv_bfloat over row r's own kv_len; an idle row's attention output is zeros (what Wo then reads for it)
+extern "C" __global__ void __launch_bounds__(1024)
+mc_b_attn_pv_rows_bfloat(const float* expv, const float* psum, const bf16_t* vt, bf16_t* out, const step_state* rows, uint32_t n_rep,
+                         uint32_t hd, uint32_t max_seq, uint32_t nsplit, uint64_t cache_stride)
+{
+    const uint32_t r = blockIdx.z, H = gridDim.y * n_rep;
+    if (row_idle(rows, r)) {
+        // this workgroup's part of the output: heads kv * n_rep + [0, n_rep), dims 16 blockIdx.x + [0, 16)
+        if (threadIdx.x < n_rep * 16)
+            out[(size_t)r * H * hd + (size_t)(blockIdx.y * n_rep + threadIdx.x / 16) * hd + blockIdx.x * 16 + threadIdx.x % 16] = 0;
+        return;
+    }
+    attn_pv_bf_body(expv + (size_t)r * H * max_seq, psum + (size_t)r * H * nsplit, vt + r * cache_stride, out + (size_t)r * H * hd,
+                    rows + r, n_rep, hd, max_seq, nsplit, nullptr, H, 0, 1);
+}
+
+extern "C" __global__ void __launch_bounds__(1024)
+mc_b_argmax_rows_bfloat(const bf16_t* logits, uint32_t n, step_state* rows, int32_t* tokens_out)
+{
+    if (row_idle(rows, blockIdx.y)) return;
+    argmax_row_body(logits, n, rows, tokens_out);
+}
+
+// launch 2 of the default sampler; launch 1 (mc_b_topk_candidates_bfloat) runs for every row, an idle one on zero logits
+extern "C" __global__ void
+mc_b_sample_rows_bfloat(const uint64_t* cand, sampler_params p, const uint64_t* seeds, uint32_t n_seed_pairs, step_state* rows,
+                        int32_t* tokens_out)
+{
+    const uint32_t r = blockIdx.y;
+    if (row_idle(rows, r)) return;
     sample_body<BF>(cand + (size_t)r * p.ncand, p, seeds, n_seed_pairs, reinterpret_cast<step_state_s*>(rows + r), tokens_out,
                     nullptr);
 }

@@ -199,6 +199,11 @@ def capi() -> C.CDLL:
         "mc_batch_generate": (i32, [vp, C.POINTER(i32), i32, i32, C.POINTER(i32)]),
         "mc_batch_set_seeds": (i32, [vp, C.POINTER(u64), i32]),
         "mc_batch_get_logits": (i32, [vp, vp]),
+        "mc_ragged_step": (i32, [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
+        "mc_ragged_generate": (i32, [vp, C.POINTER(i32), C.POINTER(i32), i32, C.POINTER(i32), i32, C.POINTER(i32),
+                                     C.POINTER(i32)]),
+        "mc_ragged_lengths": (i32, [vp, C.POINTER(i32)]),
+        "mc_ragged_export_kv": (i32, [vp, i32, i32, vp, vp, C.POINTER(i32)]),
         "mc_synth_weight": (i32, [u64, u32, u32, u32, i32]),
         "mc_synth_scale": (f32, [u64, u32, u32, u32, i32, i32]),
         "mc_synth_value": (f32, [u64, u32, u32, i32, u32]),
@@ -774,8 +779,9 @@ class Decoder:
 
 
 class Batch:
-    """Batched decode (Part 2b of the C ABI): B <= 8 sequences in lockstep over `decoder`'s weights, each with its own
-    cache (nn::attention with input[bs, 1, dim], include/metalchat/nn/attention.h:163-206).  Keeps the decoder alive."""
+    """Batched decode (Parts 2b and 2c of the C ABI): B <= 8 sequences over `decoder`'s weights, each with its own cache, in
+    lockstep or each row at its own position (nn::attention with input[bs, 1, dim], include/metalchat/nn/attention.h:163-206).
+    Keeps the decoder alive."""
 
     def __init__(self, decoder: Decoder, batch: int):
         self.decoder = decoder
@@ -826,6 +832,49 @@ class Batch:
         _check(capi().mc_batch_generate(self._h, t.ctypes.data_as(C.POINTER(C.c_int32)), start_pos, n,
                                         out.ctypes.data_as(C.POINTER(C.c_int32))))
         return out
+
+    # ---- ragged rows (Part 2c): every row at its own position; position -1 = the row is idle in that call
+
+    def _positions(self, positions) -> np.ndarray:
+        p = np.ascontiguousarray(positions, dtype=np.int32)
+        assert p.shape == (self.B,)
+        return p
+
+    def step_rows(self, tokens, positions) -> np.ndarray:
+        """one step of every active row at its own position; returns next[B] (-1 for an idle row)"""
+        t, p = self._tokens(tokens), self._positions(positions)
+        out = np.zeros(self.B, dtype=np.int32)
+        ptr = C.POINTER(C.c_int32)
+        _check(capi().mc_ragged_step(self._h, t.ctypes.data_as(ptr), p.ctypes.data_as(ptr), out.ctypes.data_as(ptr)))
+        return out
+
+    def generate_rows(self, first_tokens, positions, n: int, stop=()):
+        """up to n chained steps per row, each row stopping on its first token in `stop` or at the end of its cache;
+        returns (tokens[n][B], -1 after a row stopped; lengths[B], the tokens each row produced)"""
+        t, p = self._tokens(first_tokens), self._positions(positions)
+        s = np.ascontiguousarray(np.asarray(stop, dtype=np.int32).reshape(-1))
+        out = np.zeros((max(n, 0), self.B), dtype=np.int32)
+        lengths = np.zeros(self.B, dtype=np.int32)
+        ptr = C.POINTER(C.c_int32)
+        _check(capi().mc_ragged_generate(self._h, t.ctypes.data_as(ptr), p.ctypes.data_as(ptr), n, s.ctypes.data_as(ptr),
+                                         s.shape[0], out.ctypes.data_as(ptr), lengths.ctypes.data_as(ptr)))
+        return out, lengths
+
+    def lengths(self) -> np.ndarray:
+        """the valid cache length of every row"""
+        out = np.zeros(self.B, dtype=np.int32)
+        _check(capi().mc_ragged_lengths(self._h, out.ctypes.data_as(C.POINTER(C.c_int32))))
+        return out
+
+    def export_row_kv(self, row: int, layer: int):
+        """row `row`'s own valid positions of `layer`: (K, V) of [length, n_kv_heads, head_dim]"""
+        c = self.cfg
+        shape = (c["max_seq_len"], c["n_kv_heads"], c["head_dim"])
+        k = np.zeros(shape, dtype=self.np_T)
+        v = np.zeros(shape, dtype=self.np_T)
+        n = C.c_int32()
+        _check(capi().mc_ragged_export_kv(self._h, row, layer, _np_ptr(k), _np_ptr(v), C.byref(n)))
+        return k[: n.value], v[: n.value]
 
     def set_seeds(self, pairs):
         a = np.ascontiguousarray(np.asarray(pairs, dtype=np.uint64).reshape(-1, 2))
