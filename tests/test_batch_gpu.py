@@ -110,6 +110,20 @@ def test_llama32_1b_bfloat_rows_across_a_64_slot_boundary(acc):
     dec.release()
 
 
+@pytest.mark.parametrize("variant", ["int8-embedding", "int4-group-256"])
+def test_small_rows_against_the_oracle_at_other_admitted_formats(acc, variant):
+    """Admitted configurations no other batch test loads: an int8 embedding table (one f32 scale per row) and int4 weights in
+    groups of 256, each row against its own oracle."""
+    group = 256 if variant == "int4-group-256" else 128
+    weights = mg.make_model(SMALL, seed=13, quant="i4", group=group, emb_quant=variant == "int8-embedding")
+    dec = small_decoder(acc, SMALL, weights, group_size=group)
+    names = run_lockstep(acc, SMALL, weights, dec, 3, 60, 6, f"SMALL {variant} B=3")
+    assert {"mc_b_embed_bfloat", "mc_b_gemv_i4_bfloat_e0", "mc_b_gemv_i4_bfloat_e1", "mc_b_gemv_i4_bfloat_e2", "mc_b_rope_kv_bfloat",
+            "mc_b_attn_scores_bfloat", "mc_b_attn_pv_bfloat", "mc_b_argmax_bfloat"} <= names, sorted(names)
+    assert not [n for n in names if n.startswith("mc_gemv_")], sorted(names)
+    dec.release()
+
+
 def run_contents(acc, dec, contents, n_steps=3, pos0=40):
     """contents: list of (token, [(k, v) per layer]) -- one batch of len(contents) rows; returns per row (logits[n_steps], picks, k, v)"""
     import metalchat_amd as mc

@@ -59,12 +59,18 @@ def test_a_row_equals_a_single_row(acc, small):
     dec.release()
 
 
-@pytest.mark.parametrize("shape", ["small-int4", "llama32-1b-bf16"])
+@pytest.mark.parametrize("shape", ["small-int4", "llama32-1b-bf16", "small-int4-int8-embedding", "small-int4-group-256"])
 def test_rows_against_the_oracle(acc, small, shape):
-    cfg, weights = (SMALL, small) if shape == "small-int4" else (LLAMA32_1B, mg.make_model(LLAMA32_1B, seed=5))
+    group = 256 if shape == "small-int4-group-256" else 128
+    if shape == "small-int4":
+        cfg, weights = SMALL, small
+    elif shape == "llama32-1b-bf16":
+        cfg, weights = LLAMA32_1B, mg.make_model(LLAMA32_1B, seed=5)
+    else:   # admitted formats no other ragged test loads: an int8 embedding table, int4 groups of 256
+        cfg, weights = SMALL, mg.make_model(SMALL, seed=13, quant="i4", group=group, emb_quant=shape.endswith("int8-embedding"))
     L, B, n_steps = cfg["n_layers"], 4, 6
     lens = [60, 62, 125, 190]  # 64-slot boundaries crossed at steps 4, 2, 3 and 2
-    dec = small_decoder(acc, cfg, weights)
+    dec = small_decoder(acc, cfg, weights, **({"group_size": group} if cfg is SMALL else {}))
     oms = [mo.Model(cfg, weights) for _ in range(B)]
     caches = []
     for r in range(B):
