@@ -128,7 +128,8 @@ body(const args& a, ActFn&& act)
     tile_of(tile_n, tile_m);
     const uint32_t n0 = tile_n * BN, m0 = tile_m * BM;
     const uint32_t M = a.M, N = a.N, K = a.K;
-    // split-K (E_PART): workgroup z walks K tiles [z * tper, ...)
+    // split-K (E_PART): workgroup z walks K tiles [z * tper, ...).  K / BK rounds down, which is exact only because the decoder
+    // launches this GEMM for K % 64 == 0 alone (decoder.cc g8_ok); any other K takes pf_gemm_big_body, whose ranges round up
     const uint32_t TT = K / BK, tper = EPI == E_PART ? (TT + gridDim.z - 1) / gridDim.z : TT;
     const uint32_t tbeg = EPI == E_PART ? blockIdx.z * tper : 0u;
     const uint32_t T = tbeg < TT ? min(tper, TT - tbeg) : 0u;

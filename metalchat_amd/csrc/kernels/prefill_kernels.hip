@@ -535,8 +535,10 @@ pf_gemm_big_body(const void* __restrict__ wp, const void* __restrict__ sp, const
     const uint32_t glog = group ? 31u - __builtin_clz(group) : 31u;
     const size_t rowb = WF == PF_W_I4 ? K / 2 : (WF == PF_W_I8 ? K : (size_t)K * 2);
     // split-K (EPI 2): workgroup z of gridDim.z walks K range [z * kper, (z + 1) * kper) and stores
-    // its fp32 partial sums; mc_pf_splitk_reduce adds the partials in z order and finishes the rows
-    const uint32_t kper = EPI == 2 ? ((K / PFB_K + gridDim.z - 1) / gridDim.z) * PFB_K : K;
+    // its fp32 partial sums; mc_pf_splitk_reduce adds the partials in z order and finishes the rows.
+    // The ranges cover ceil(K / 64) chunks: K is only a multiple of 32, and a last chunk half past K
+    // has its X run zeroed in stage() (a range that starts past K stores zeros)
+    const uint32_t kper = EPI == 2 ? (((K + PFB_K - 1) / PFB_K + gridDim.z - 1) / gridDim.z) * PFB_K : K;
     const uint32_t kbeg = EPI == 2 ? blockIdx.z * kper : 0;
     const uint32_t kend = EPI == 2 ? min(K, kbeg + kper) : K;
     const uint32_t srow = tid >> 1, skk = (tid & 1) * 32; // staging of X: row, first k of the 32-run

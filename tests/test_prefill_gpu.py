@@ -121,6 +121,19 @@ def test_wide_model_takes_the_split_k_gemm(acc):
     check_against_oracle(acc, cfg, weights, dict(weight_format=2, group_size=128), tokens, follow=1)
 
 
+@pytest.mark.parametrize("dt,quant,fmt,group,n", [(BF16, q, fm, g, n) for q, fm, g in (("i8", 1, 32), ("i4", 2, 32), (None, 0, 0))
+                                                   for n in (40, 100, 300)] + [(F32, "i8", 1, 32, 100)])
+def test_k_32_past_a_multiple_of_64_through_the_split_k_gemm(acc, dt, quant, fmt, group, n):
+    # in_features 1056 (wq|wk|wv, w1|w3) and 2080 (w2): the ping-pong GEMM refuses them (K % 64 != 0), so the 128 / 256-row GEMM
+    # splits K (2 and 4 ranges) and its ranges must reach the last 32 columns; T = float takes the 64 x 64 tile and no split
+    cfg = mg.tiny_cfg(dt, dim=1056, n_heads=2, n_kv_heads=1, head_dim=32, ffn_dim=2080, n_layers=1, vocab=256, max_seq_len=320)
+    weights = mg.make_model(cfg, seed=113, quant=quant, group=group or 32)
+    tokens = np.random.default_rng(n + fmt).integers(0, cfg["vocab"], n).tolist()
+    f = {0: "w", 1: "i8", 2: "i4"}[fmt]
+    kern = f"mc_pf_gemm{256 if n >= 256 else 128}_{f}_bfloat_d2_e2" if dt == BF16 else f"mc_pf_gemm_{f}_float_e0"
+    check_against_oracle(acc, cfg, weights, dict(weight_format=fmt, group_size=group), tokens, follow=1, expect_kernel=kern)
+
+
 @pytest.mark.parametrize("dt", [F32, BF16])
 def test_gemma3_prompt_with_sliding_window(acc, dt):
     cfg = mg.tiny_cfg(dt, family=1, n_layers=3, rope_sliding_theta=10000.0, sliding_stride=2,
