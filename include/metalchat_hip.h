@@ -426,6 +426,26 @@ mc_status mc_ragged_lengths(const mc_batch* b, int32_t* lengths);
 /* row `row`'s own valid positions [0, length) in the layout of the batch's export_kv; *n_valid = the row's length */
 mc_status mc_ragged_export_kv(mc_batch* b, int32_t row, int32_t layer, void* keys, void* values, int32_t* n_valid);
 
+/* ================================================================================================
+ * Part 2d -- the packed prompt pass: the prompts of several rows of an mc_batch in ONE prompt pass over the decoder's weights.
+ * Every weight matrix is multiplied once for all of them (M = the sum of the lengths rows); only the rope + cache write and the
+ * attention know which row a prompt row belongs to.  Row r gets exactly what mc_decoder_prefill of its chunk at start_pos =
+ * positions[r] does to a decoder's cache -- the reference's mask included: only the chunk's own columns form the causal square,
+ * so a chunk at positions[r] > 0 does not see the row's earlier context (pf_visible) -- written to the row's own
+ * cache at [positions[r], positions[r] + lens[r]); its length becomes positions[r] + lens[r] (a position below the length
+ * rewinds the row, as in ragged calls).  Rows with lens[r] = 0 are not in the call: their caches, lengths and state stay.
+ * The decoder's cache, step state, sampler settings and taps stay as they were; its prompt scratch and derived weight copies
+ * serve the call as they serve mc_decoder_prefill.  Launches go to the decoder's stream and launch log.
+ * ------------------------------------------------------------------------------------------ */
+/* tokens: the chunks of the rows in the call, concatenated in row order (sum of lens ids); lens[B]: row r's chunk length, 0 =
+ * not in the call; positions[B]: where row r's chunk starts in its cache.  next_tokens[B] (may be null): each row's pick after
+ * its chunk's last row (the decoder's sampler read at the call, seed pair r % n_pairs), -1 for a row not in the call; the
+ * batch's logits (mc_batch_get_logits) are then the last-row logits of the rows in the call.  Refused with
+ * MC_ERR_INVALID_ARGUMENT naming the row and the reason, before anything is enqueued: a null pointer, no row in the call,
+ * lens[r] < 0, lens[r] == 1 (a one-token chunk is a ragged step), positions[r] < 0 or past the row's length, positions[r] +
+ * lens[r] > max_seq_len, a token outside the vocabulary, a sum of lens above max_seq_len (split such a call by rows). */
+mc_status mc_rows_prefill(mc_batch* b, const int32_t* tokens, const int32_t* lens, const int32_t* positions, int32_t* next_tokens);
+
 /* Host-side helpers shared by tests and the synthetic initialiser. */
 /* value in [-7,7] (bits = 4) or [-127,127] (bits = 8), zero mean, of element (row, col) of matrix `matrix_id` */
 int32_t mc_synth_weight(uint64_t seed, uint32_t matrix_id, uint32_t row, uint32_t col, int32_t bits);

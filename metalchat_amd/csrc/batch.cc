@@ -97,6 +97,9 @@ struct mc_batch {
     int32_t* stop_dev = nullptr;          // the stop ids of a ragged call
     int stop_cap = 0;
     std::vector<int32_t> stop_host;
+    int32_t* pp_tab = nullptr;            // a packed prompt pass (mc_rows_prefill): segment table [8][4], then the tile table [.][2]
+    int pp_tab_cap = 0;                   // (int32 entries)
+    std::vector<int32_t> pp_host;
 
     ~mc_batch()
     {
@@ -216,6 +219,16 @@ struct mc_batch {
             if ((s = gemv(L.w13, 2, xn, gate, (uint32_t)(L.w13.out / 2))) != MC_OK) return s;
             if ((s = gemv(L.w2, 1, gate, x, (uint32_t)c.dim)) != MC_OK) return s;
         }
+        return head(sfx);
+    }
+
+    // the final norm of x, the head and the pick per row (greedy, or the decoder's default sampler); sfx "_rows_bfloat": rows
+    // whose rows[r].pos is -1 get no pick
+    mc_status
+    head(const std::string& sfx)
+    {
+        const mc_decoder_config& c = p.cfg;
+        mc_status s;
         if ((s = rmsnorm(x, p.final_norm, xn)) != MC_OK) return s;
         if ((s = gemv(p.output, 0, xn, logits, (uint32_t)c.vocab)) != MC_OK) return s;
         const decoder_sampler sm = decoder_sampler_of(d);
@@ -593,6 +606,99 @@ mc_batch_get_logits(mc_batch* b, void* logits_T)
     MC_HIP(hipSetDevice(b->p.ordinal));
     MC_HIP(hipStreamSynchronize(b->p.stream));
     MC_HIP(hipMemcpy(logits_T, b->logits, (size_t)b->B * b->p.cfg.vocab * 2, hipMemcpyDeviceToHost));
+    return MC_OK;
+}
+
+// ---- Part 2d: the packed prompt pass ----
+
+mc_status
+mc_rows_prefill(mc_batch* b, const int32_t* tokens, const int32_t* lens, const int32_t* positions, int32_t* next_tokens)
+{
+    if (!b || !tokens || !lens || !positions) return fail(MC_ERR_INVALID_ARGUMENT, "mc_rows_prefill: null argument");
+    const mc_decoder_config& c = b->p.cfg;
+    const int B = b->B;
+    int64_t total = 0;
+    int nseg = 0, ntiles = 0;
+    for (int r = 0; r < B; r++) {
+        const std::string row = "mc_rows_prefill: row " + std::to_string(r) + ": ";
+        const int32_t len = lens[r], pos = positions[r];
+        if (len < 0) return fail(MC_ERR_INVALID_ARGUMENT, row + "length below 0 (0 = the row is not in the call)");
+        if (len == 0) continue;
+        if (len == 1) return fail(MC_ERR_INVALID_ARGUMENT, row + "a one-token chunk is a step: mc_ragged_step");
+        if (pos < 0) return fail(MC_ERR_INVALID_ARGUMENT, row + "position below 0");
+        if (pos > b->lengths[r])
+            return fail(MC_ERR_INVALID_ARGUMENT, row + "position " + std::to_string(pos) + " is past the row's length " +
+                                                     std::to_string(b->lengths[r]) + " (its cache has no slots written beyond it)");
+        if ((int64_t)pos + len > c.max_seq_len)
+            return fail(MC_ERR_INVALID_ARGUMENT, row + "position + length " + std::to_string((int64_t)pos + len) +
+                                                     " exceeds max_seq_len (a batch's cache does not roll)");
+        for (int32_t i = 0; i < len; i++)
+            if (tokens[total + i] < 0 || tokens[total + i] >= c.vocab)
+                return fail(MC_ERR_INVALID_ARGUMENT, row + "token id outside the vocabulary");
+        total += len;
+        nseg++;
+        ntiles += (len + 15) / 16;
+    }
+    if (nseg == 0) return fail(MC_ERR_INVALID_ARGUMENT, "mc_rows_prefill: no row in the call (every length is 0)");
+    if (total > c.max_seq_len)
+        return fail(MC_ERR_INVALID_ARGUMENT, "mc_rows_prefill: the rows' lengths add up to " + std::to_string(total) +
+                                                 ", more than max_seq_len (" + std::to_string(c.max_seq_len) + "): split the call by rows");
+    const int M = (int)total;
+    MC_HIP(hipSetDevice(b->p.ordinal));
+    // the segment table (row, position, offset, length; packed in row order) and the attention tiles (segment, first row)
+    b->pp_host.assign((size_t)BATCH_MAX * 4 + (size_t)ntiles * 2, 0);
+    int32_t* seg = b->pp_host.data();
+    int32_t* tile = seg + BATCH_MAX * 4;
+    b->rows_host.assign(B, step_state_b{});
+    for (int r = 0, off = 0, si = 0, ti = 0; r < B; r++) {
+        b->rows_host[r].pos = lens[r] > 0 ? positions[r] : -1;
+        b->rows_host[r].token = -1;
+        b->rows_host[r].step_index = r; // seed pair r % n_pairs, next_tokens[r]
+        if (lens[r] == 0) continue;
+        seg[4 * si + 0] = r;
+        seg[4 * si + 1] = positions[r];
+        seg[4 * si + 2] = off;
+        seg[4 * si + 3] = lens[r];
+        for (int t = 0; t < lens[r]; t += 16, ti++) {
+            tile[2 * ti] = si;
+            tile[2 * ti + 1] = t;
+        }
+        off += lens[r];
+        si++;
+    }
+    mc_status s;
+    if ((int)b->pp_host.size() > b->pp_tab_cap) {
+        MC_HIP(hipStreamSynchronize(b->p.stream));
+        if (b->pp_tab) b->free_one(b->pp_tab);
+        b->pp_tab = nullptr;
+        b->pp_tab_cap = 0;
+        // (enough for any call: at most max_seq_len rows in at most 8 segments)
+        const int cap = BATCH_MAX * 4 + 2 * (c.max_seq_len / 16 + BATCH_MAX);
+        if ((s = b->alloc(&b->pp_tab, sizeof(int32_t) * cap)) != MC_OK) return s;
+        b->pp_tab_cap = cap;
+    }
+    MC_HIP(hipMemcpyAsync(b->pp_tab, b->pp_host.data(), sizeof(int32_t) * b->pp_host.size(), hipMemcpyHostToDevice, b->p.stream));
+    MC_HIP(hipMemcpyAsync(b->rows, b->rows_host.data(), sizeof(step_state_b) * B, hipMemcpyHostToDevice, b->p.stream));
+    if ((s = b->ensure_tokens(1)) != MC_OK) return s;
+    MC_HIP(hipMemsetAsync(b->tokens_dev, 0xFF, sizeof(int32_t) * B, b->p.stream));
+    packed_prefill pk;
+    pk.segs = b->pp_tab;
+    pk.nseg = nseg;
+    pk.tiles = b->pp_tab + BATCH_MAX * 4;
+    pk.ntiles = ntiles;
+    pk.kc = b->kc;
+    pk.vt = b->vt;
+    pk.B = B;
+    pk.cache_stride = b->cache_elems;
+    pk.fcos = b->fcos;
+    pk.fsin = b->fsin;
+    pk.x_out = b->x;
+    if ((s = decoder_prefill_packed(b->d, tokens, M, pk)) != MC_OK) return s;
+    if ((s = b->head("_rows_bfloat")) != MC_OK) return s;
+    MC_HIP(hipStreamSynchronize(b->p.stream)); // (`tokens` is the caller's buffer; the tables are read by the launches)
+    for (int r = 0; r < B; r++)
+        if (lens[r] > 0) b->lengths[r] = positions[r] + lens[r];
+    if (next_tokens) MC_HIP(hipMemcpy(next_tokens, b->tokens_dev, sizeof(int32_t) * B, hipMemcpyDeviceToHost));
     return MC_OK;
 }
 

@@ -2004,8 +2004,12 @@ struct mc_decoder {
     // cache_pos: first cache row (= logical column) the M rows are written to; rope_pos: their sequence position
     // (they differ for a chunk behind a full cache: rows max_seq_len - M .., positions start_pos ..);
     // rows_in: hidden rows [M][dim] from the previous pipeline stage (device), null on the first stage
+    // pk (mc_rows_prefill): the M rows are the chunks of several batch rows (decoder_batch.h packed_prefill) -- the rope + cache
+    // write and the attention take the packed kernels (kernels/packed_kernels.hip) on the batch's caches and rope table, the
+    // taps and the head are skipped, and the last row of each chunk is gathered into pk->x_out.  cache_pos, rope_pos and window
+    // are not used then.
     mc_status
-    run_prefill(int M, int cache_pos, int rope_pos, int window, const void* rows_in)
+    run_prefill(int M, int cache_pos, int rope_pos, int window, const void* rows_in, const packed_prefill* pk = nullptr)
     {
         const int dim = cfg.dim, H = cfg.n_heads, KV = cfg.n_kv_heads, hd = cfg.head_dim;
         const int start_pos = cache_pos;
@@ -2028,7 +2032,8 @@ struct mc_decoder {
                        pack(emb_table, emb_scales, pf_tokens, pf_x, (uint32_t)dim, sc, (int32_t)(gemma ? 1 : 0)));
         if (s != MC_OK) return s;
         const size_t last = (size_t)(M - 1) * dim * tb;
-        if (want_taps) MC_HIP(hipMemcpyAsync(taps, (char*)pf_x + last, (size_t)dim * tb, hipMemcpyDeviceToDevice, stream));
+        const bool taps_on = want_taps && !pk;
+        if (taps_on) MC_HIP(hipMemcpyAsync(taps, (char*)pf_x + last, (size_t)dim * tb, hipMemcpyDeviceToDevice, stream));
         // (round 4) a GEMM that splits K hands its fp32 partial sums straight to the kernel that consumes its rows -- rope + cache
         // write, the next rmsnorm (with the residual), act * mul -- instead of to a reduce launch: gemm_to_parts
         const bool fold_norm = dim % 8 == 0 && dim / 8 <= 4 * 256;
@@ -2049,9 +2054,17 @@ struct mc_decoder {
             const unsigned rope_per = rope_v4 ? 2048u / (unsigned)hd : 1u; // heads of a row per workgroup of 256 threads
             const unsigned rope_gx = rope_v4 ? ((unsigned)(H + KV) * (unsigned)M + rope_per - 1) / rope_per + (unsigned)KV * (((unsigned)M + 15u) / 16u) // q / k units, then v tiles of 16 rows
                                              : 0u;
+            // packed rows: layer li of every batch row; the four-pair arithmetic whatever MC_PF_ROPE_PACK says (bit for bit the one-pair launch's)
+            void* pk_kc = pk ? (char*)pk->kc + (size_t)li * pk->B * pk->cache_stride * tb : nullptr;
+            void* pk_vt = pk ? (char*)pk->vt + (size_t)li * pk->B * pk->cache_stride * tb : nullptr;
+            const unsigned pk_gx = ((unsigned)(H + KV) * (unsigned)M + 2048u / (unsigned)hd - 1) / (2048u / (unsigned)hd) + (unsigned)KV * (((unsigned)M + 15u) / 16u);
             if (gemm_to_parts(L.qkv, pf_xn, M, &sp, &gs)) {
                 if (gs != MC_OK) return gs;
-                if (rope_v4)
+                if (pk)
+                    s = timed("rope_cache", [&] { return launch("mc_pp_rope_cache_parts_bfloat", pk_gx, 1, 1, 256, 0,
+                               pack((const void*)pf_part, sp, (uint32_t)M, pf_q, pk->segs, (uint32_t)pk->nseg, pk_kc, pk_vt, pk->cache_stride, pk->fcos,
+                                    pk->fsin, (uint32_t)H, (uint32_t)KV, (uint32_t)hd, (uint32_t)cfg.max_seq_len)); });
+                else if (rope_v4)
                     s = timed("rope_cache", [&] { return launch("mc_pf_rope_cache_parts_v4_bfloat", rope_gx, 1, 1, 256, 0,
                                pack((const void*)pf_part, sp, (uint32_t)M, pf_q, L.kc, L.vt, rope_cos[L.rope_table], rope_sin[L.rope_table],
                                     (uint32_t)H, (uint32_t)KV, (uint32_t)hd, (uint32_t)cfg.max_seq_len, (uint32_t)start_pos,
@@ -2064,7 +2077,11 @@ struct mc_decoder {
             } else {
                 s = timed("gemm_qkv", [&] { return gemm(L.qkv, 0, pf_xn, pf_qkv, nullptr, M); });
                 if (s != MC_OK) return s;
-                if (rope_v4)
+                if (pk)
+                    s = timed("rope_cache", [&] { return launch("mc_pp_rope_cache_bfloat", pk_gx, 1, 1, 256, 0,
+                               pack((const void*)pf_qkv, (uint32_t)M, pf_q, pk->segs, (uint32_t)pk->nseg, pk_kc, pk_vt, pk->cache_stride, pk->fcos, pk->fsin,
+                                    (uint32_t)H, (uint32_t)KV, (uint32_t)hd, (uint32_t)cfg.max_seq_len)); });
+                else if (rope_v4)
                     s = timed("rope_cache", [&] { return launch("mc_pf_rope_cache_v4_bfloat", rope_gx, 1, 1, 256, 0,
                                pack(pf_qkv, pf_q, L.kc, L.vt, rope_cos[L.rope_table], rope_sin[L.rope_table], (uint32_t)H, (uint32_t)KV, (uint32_t)hd,
                                     (uint32_t)cfg.max_seq_len, (uint32_t)start_pos, (uint32_t)(rope_pos - rope_start), (uint32_t)M, L.q_norm, L.k_norm,
@@ -2077,7 +2094,20 @@ struct mc_decoder {
             }
             if (s != MC_OK) return s;
             const uint32_t win = (gemma && L.rope_table == 1) ? (uint32_t)window : 0u;
-            if (tb == 2 && !pf_two_pass) {
+            if (pk) {
+                // one or two query heads per workgroup by the rule of one prompt below, over the tiles of all segments; the LDS-tile and
+                // four-head forms have no packed counterpart (DESIGN.md "The packed prompt pass")
+                s = timed("attention", [&] {
+                    const char* heads_env = getenv("MC_PF_ATTN_HEADS");
+                    const bool enough = (unsigned)pk->ntiles * (unsigned)(H / 2) >= 2u * (unsigned)dev->prop.multiProcessorCount;
+                    const bool two = (H / KV) % 2 == 0 && (heads_env ? atoi(heads_env) == 2 : enough);
+                    return launch(std::string(two ? "mc_pp_attn2_bfloat_hd" : "mc_pp_attn_bfloat_hd") + std::to_string(hd), (unsigned)pk->ntiles,
+                                  two ? H / 2 : H, 1, 256, 0,
+                                  pack(pf_q, pk->segs, pk->tiles, (const void*)pk_kc, (const void*)pk_vt, pk->cache_stride, pf_att, (uint32_t)H,
+                                       (uint32_t)(H / KV), (uint32_t)cfg.max_seq_len, scale_T, (const void*)pf_etab));
+                });
+                if (s != MC_OK) return s;
+            } else if (tb == 2 && !pf_two_pass) {
                 // fused: the probabilities stay on chip
                 s = timed("attention", [&] {
                     // two query heads of a kv head per workgroup where the grouping allows it: each K / V
@@ -2220,13 +2250,18 @@ struct mc_decoder {
                 s = timed("gemm_w2", [&] { return gemm(L.w2, 1, pf_g, pf_x, pf_h, M); });
             }
             if (s != MC_OK) return s;
-            if (want_taps)
+            if (taps_on)
                 MC_HIP(hipMemcpyAsync((char*)taps + (size_t)(li + 1) * dim * tb, (char*)pf_x + last, (size_t)dim * tb,
                                       hipMemcpyDeviceToDevice, stream));
         }
-        // only the last row goes through the head (llama.h:130-133); other stages hand all rows on (pf_x)
-        MC_HIP(hipMemcpyAsync(hidden, (char*)pf_x + last, (size_t)dim * tb, hipMemcpyDeviceToDevice, stream));
-        s = last_stage ? timed("head", [&] { return run_head(); }) : MC_OK;
+        if (pk) {
+            // the batch's head follows (batch.cc): the last row of each chunk into its batch row
+            s = launch("mc_pp_gather_last_bfloat", gd, (unsigned)pk->nseg, 1, 256, 0, pack((const void*)pf_x, pk->segs, pk->x_out, (uint32_t)dim));
+        } else {
+            // only the last row goes through the head (llama.h:130-133); other stages hand all rows on (pf_x)
+            MC_HIP(hipMemcpyAsync(hidden, (char*)pf_x + last, (size_t)dim * tb, hipMemcpyDeviceToDevice, stream));
+            s = last_stage ? timed("head", [&] { return run_head(); }) : MC_OK;
+        }
         if (pf_timing) {
             double tot = 0;
             for (auto& kv : pf_ms) tot += kv.second;
@@ -3901,6 +3936,17 @@ decoder_launch(mc_decoder* d, const std::string& name, unsigned gx, unsigned gy,
     arg_pack a;
     a.buf = args;
     return d->launch(name, gx, gy, gz, bx, lds, std::move(a));
+}
+
+mc_status
+decoder_prefill_packed(mc_decoder* d, const int32_t* tokens, int M, const packed_prefill& pk)
+{
+    mc_status s = check_ready(d);
+    if (s != MC_OK) return s;
+    MC_HIP(hipSetDevice(d->dev->ordinal));
+    if ((s = d->ensure_prefill(M, M)) != MC_OK) return s;
+    MC_HIP(hipMemcpyAsync(d->pf_tokens, tokens, (size_t)M * 4, hipMemcpyHostToDevice, d->stream));
+    return d->run_prefill(M, 0, 0, 0, nullptr, &pk);
 }
 
 } // namespace mcimpl

@@ -50,4 +50,23 @@ mc_status decoder_cache_state(mc_decoder* d, int* kv_len, bool* rolled);
 mc_status decoder_launch(mc_decoder* d, const std::string& name, unsigned gx, unsigned gy, unsigned gz, unsigned bx, unsigned lds,
                          const std::vector<char>& args);
 
+// The packed prompt pass (mc_rows_prefill, kernels/packed_kernels.hip): the chunks of several sequences as one prompt pass of
+// M = sum of their lengths rows.  The tables are on the device already (uploaded on the decoder's stream).
+struct packed_prefill {
+    const int32_t* segs = nullptr;  // [nseg][4]: batch row, position, offset of its first packed row, length (offsets ascending)
+    int nseg = 0;
+    const int32_t* tiles = nullptr; // [ntiles][2]: segment, first row of a 16-row attention tile inside it
+    int ntiles = 0;
+    void* kc = nullptr;             // caches of layer l, batch row r at kc / vt + (l * B + r) * cache_stride elements (batch.cc kc_of / vt_of)
+    void* vt = nullptr;
+    int B = 0;
+    uint64_t cache_stride = 0;
+    const float* fcos = nullptr;    // the batch's rope table, rows = positions [0, max_seq_len)
+    const float* fsin = nullptr;
+    void* x_out = nullptr;          // [B][dim]: the last row of each segment lands in its batch row
+};
+// run_prefill over `tokens` (M ids, host) with the packed rope + cache and attention launches, then the gather into x_out; the
+// decoder's cache, step state, sampler, taps and head are not touched (its prompt scratch is)
+mc_status decoder_prefill_packed(mc_decoder* d, const int32_t* tokens, int M, const packed_prefill& pk);
+
 } // namespace mcimpl

@@ -9,3 +9,4 @@
 #include "sampler_kernels.hip"
 #include "prefill_kernels.hip"
 #include "batch_kernels.hip"
+#include "packed_kernels.hip"

@@ -1146,7 +1146,7 @@ mc_pf_pv_float(const float* probs, const float* vt, float* out, uint32_t M, uint
 template <uint32_t HD, int NH>
 __device__ __forceinline__ void
 pf_attn_body(const bf16_t* Q, const bf16_t* kc, const bf16_t* vt, bf16_t* out, uint32_t M, uint32_t S, uint32_t H,
-             uint32_t n_rep, uint32_t max_seq, float scale, uint32_t window, const float* etab)
+             uint32_t n_rep, uint32_t max_seq, float scale, uint32_t window, const float* etab, uint32_t r0)
 {
     // NH query heads of ONE kv head per workgroup (grid.y = H / NH; NH divides n_rep): every K and V
     // fragment a wave loads is multiplied NH times -- the waves of this kernel spend two thirds of
@@ -1172,7 +1172,7 @@ pf_attn_body(const bf16_t* Q, const bf16_t* kc, const bf16_t* vt, bf16_t* out, u
     __shared__ float osum[4][16][OD + 1];
     const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint32_t l15 = lane & 15, lg = lane >> 4, kg = lg * 8;
-    const uint32_t r0 = blockIdx.x * 16, h0 = blockIdx.y * NH, kv = h0 / n_rep;
+    const uint32_t h0 = blockIdx.y * NH, kv = h0 / n_rep; // (r0: the row tile's first row -- blockIdx.x * 16 for one prompt)
     const bf16_t* kbase = kc + (size_t)kv * max_seq * HD;
     const bf16_t* vbase = vt + (size_t)kv * HD * max_seq;
     const uint32_t sq = S - M, rlast = min(r0 + 15, M - 1);
@@ -1372,7 +1372,7 @@ pf_attn_body(const bf16_t* Q, const bf16_t* kc, const bf16_t* vt, bf16_t* out, u
 template <uint32_t HD, int NH>
 __device__ __forceinline__ void
 pf_attn_kt_body(const bf16_t* Q, const bf16_t* kc, const bf16_t* vt, bf16_t* out, uint32_t M, uint32_t S, uint32_t H,
-                uint32_t n_rep, uint32_t max_seq, float scale, uint32_t window, const float* etab)
+                uint32_t n_rep, uint32_t max_seq, float scale, uint32_t window, const float* etab, uint32_t r0)
 {
     using T = BF;
     constexpr uint32_t DT = HD / 16, DK = HD / 32;
@@ -1385,7 +1385,7 @@ pf_attn_kt_body(const bf16_t* Q, const bf16_t* kc, const bf16_t* vt, bf16_t* out
     __shared__ float osum[4][16][OD + 1];
     const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint32_t l15 = lane & 15, lg = lane >> 4, kg = lg * 8;
-    const uint32_t r0 = blockIdx.x * 16, h0 = blockIdx.y * NH, kv = h0 / n_rep;
+    const uint32_t h0 = blockIdx.y * NH, kv = h0 / n_rep; // (r0: the row tile's first row -- blockIdx.x * 16 for one prompt)
     const bf16_t* kbase = kc + (size_t)kv * max_seq * HD;
     const bf16_t* vbase = vt + (size_t)kv * HD * max_seq;
     const uint32_t sq = S - M, rlast = min(r0 + 15, M - 1);
@@ -1543,14 +1543,14 @@ pf_attn_kt_body(const bf16_t* Q, const bf16_t* kc, const bf16_t* vt, bf16_t* out
                              uint32_t H, uint32_t n_rep, uint32_t max_seq, float scale, uint32_t window,          \
                              const float* etab)                                                                     \
     {                                                                                                               \
-        pf_attn_body<HD, 1>(Q, kc, vt, out, M, S, H, n_rep, max_seq, scale, window, etab);                          \
+        pf_attn_body<HD, 1>(Q, kc, vt, out, M, S, H, n_rep, max_seq, scale, window, etab, blockIdx.x * 16); \
     }                                                                                                               \
     extern "C" __global__ void __launch_bounds__(256)                                                               \
     mc_pf_attn2_bfloat_hd##HD(const bf16_t* Q, const bf16_t* kc, const bf16_t* vt, bf16_t* out, uint32_t M, uint32_t S, \
                               uint32_t H, uint32_t n_rep, uint32_t max_seq, float scale, uint32_t window,         \
                               const float* etab)                                                                    \
     {                                                                                                               \
-        pf_attn_kt_body<HD, 2>(Q, kc, vt, out, M, S, H, n_rep, max_seq, scale, window, etab);                       \
+        pf_attn_kt_body<HD, 2>(Q, kc, vt, out, M, S, H, n_rep, max_seq, scale, window, etab, blockIdx.x * 16); \
     }
 MC_PF_ATTN(32)
 MC_PF_ATTN(64)
@@ -1560,7 +1560,7 @@ extern "C" __global__ void __launch_bounds__(256)
 mc_pf_attn4_bfloat_hd128(const bf16_t* Q, const bf16_t* kc, const bf16_t* vt, bf16_t* out, uint32_t M, uint32_t S, uint32_t H, uint32_t n_rep,
                          uint32_t max_seq, float scale, uint32_t window, const float* etab)
 {
-    pf_attn_kt_body<128, 4>(Q, kc, vt, out, M, S, H, n_rep, max_seq, scale, window, etab);
+    pf_attn_kt_body<128, 4>(Q, kc, vt, out, M, S, H, n_rep, max_seq, scale, window, etab, blockIdx.x * 16);
 }
 
 // ---- long prompts (round 5): K and V tiles through LDS, 32 rows x 4 heads per workgroup, row tiles in pairs (mc_pf_attn8_bfloat_hd128).
@@ -2129,11 +2129,25 @@ mc_pf_rmsnorm2_parts_bfloat(const float* part, uint32_t splits, uint32_t M, cons
 // The TRANSPOSED V cache ([kv][d][slot]) is written by workgroups of their own, behind the q / k ones in the grid: 16 rows of one kv head, thread
 // (i = t % 16, g = t / 16) takes elements 8 g .. 8 g + 7 of row r0 + i -- for each of its eight stores the 16 threads of a g write 16 CONSECUTIVE
 // slots of one d (32 bytes) where a thread per element wrote 2 bytes every 4 KB.
-template <bool SPLITS>
+// Where row r of the M rows goes: its K / V cache bases, its cache slot and its rope table row.  One prompt (pf_rows_linear): one cache,
+// slot start_pos + r, table row rope_row0 + r; the packed rows of several sequences (packed_kernels.hip pp_rows): per segment.
+struct pf_rows_linear {
+    bf16_t* kc;
+    bf16_t* vt;
+    uint32_t start_pos, rope_row0;
+    __device__ __forceinline__ void
+    at(uint32_t r, bf16_t*& k, bf16_t*& v, uint32_t& slot, uint32_t& rope_row) const
+    {
+        k = kc;
+        v = vt;
+        slot = start_pos + r;
+        rope_row = rope_row0 + r;
+    }
+};
+template <bool SPLITS, typename Rows>
 __device__ __forceinline__ void
-pf_rope_cache_v4_body(const void* rows, uint32_t splits, uint32_t M, bf16_t* q_out, bf16_t* kc, bf16_t* vt, const float* fcos, const float* fsin,
-                      uint32_t H, uint32_t KV, uint32_t hd, uint32_t max_seq, uint32_t start_pos, uint32_t rope_row0, const bf16_t* q_norm,
-                      const bf16_t* k_norm, float eps, float mu)
+pf_rope_cache_v4_body(const void* rows, uint32_t splits, uint32_t M, bf16_t* q_out, const Rows& at, const float* fcos, const float* fsin,
+                      uint32_t H, uint32_t KV, uint32_t hd, uint32_t max_seq, const bf16_t* q_norm, const bf16_t* k_norm, float eps, float mu)
 {
     const uint32_t half = hd / 2, lpu = hd / 8, nb = H + KV, NQ = (H + 2 * KV) * hd, per = blockDim.x / lpu;
     const uint32_t gq = (nb * M + per - 1) / per; // workgroups of q / k units; behind them KV * ceil(M / 16) of v tiles
@@ -2152,7 +2166,10 @@ pf_rope_cache_v4_body(const void* rows, uint32_t splits, uint32_t M, bf16_t* q_o
     if (blockIdx.x >= gq) {
         const uint32_t vb = blockIdx.x - gq, kv = vb % KV, r = (vb / KV) * 16 + (threadIdx.x & 15u);
         if (r >= M) return;
-        bf16_t* dst = vt + (size_t)kv * hd * max_seq + start_pos + r;
+        bf16_t *kc, *vt;
+        uint32_t slot, rope_row;
+        at.at(r, kc, vt, slot, rope_row);
+        bf16_t* dst = vt + (size_t)kv * hd * max_seq + slot;
         for (uint32_t g = threadIdx.x >> 4; g < lpu; g += blockDim.x >> 4) {
             float x[8];
             load8((size_t)r * NQ + (size_t)(nb + kv) * hd + 8 * g, x);
@@ -2163,7 +2180,10 @@ pf_rope_cache_v4_body(const void* rows, uint32_t splits, uint32_t M, bf16_t* q_o
     }
     const uint32_t unit = blockIdx.x * per + threadIdx.x / lpu, l = threadIdx.x % lpu;
     if (unit >= nb * M) return;
-    const uint32_t b = unit % nb, r = unit / nb, slot = start_pos + r;
+    const uint32_t b = unit % nb, r = unit / nb;
+    bf16_t *kc, *vt;
+    uint32_t slot, rope_row;
+    at.at(r, kc, vt, slot, rope_row);
     // the unit's head in the row: q heads, then k heads (the fused matrix's row order)
     float x[8];
     load8((size_t)r * NQ + (size_t)b * hd + 8 * l, x);
@@ -2194,7 +2214,7 @@ pf_rope_cache_v4_body(const void* rows, uint32_t splits, uint32_t M, bf16_t* q_o
             x[2 * i + 1] = BF::rt((mu + w2) * x[2 * i + 1] * inv);
         }
     }
-    const size_t tr = (size_t)(rope_row0 + r) * half + 4 * l;
+    const size_t tr = (size_t)rope_row * half + 4 * l;
     const float4 c4 = *reinterpret_cast<const float4*>(fcos + tr), s4 = *reinterpret_cast<const float4*>(fsin + tr);
     const float c[4] = {c4.x, c4.y, c4.z, c4.w}, s[4] = {s4.x, s4.y, s4.z, s4.w};
     float o1[4], o2[4];
@@ -2213,14 +2233,14 @@ mc_pf_rope_cache_v4_bfloat(const bf16_t* qkv, bf16_t* q_out, bf16_t* kc, bf16_t*
                            uint32_t hd, uint32_t max_seq, uint32_t start_pos, uint32_t rope_row0, uint32_t M, const bf16_t* q_norm, const bf16_t* k_norm,
                            float eps, float mu)
 {
-    pf_rope_cache_v4_body<false>(qkv, 1, M, q_out, kc, vt, fcos, fsin, H, KV, hd, max_seq, start_pos, rope_row0, q_norm, k_norm, eps, mu);
+    pf_rope_cache_v4_body<false>(qkv, 1, M, q_out, pf_rows_linear{kc, vt, start_pos, rope_row0}, fcos, fsin, H, KV, hd, max_seq, q_norm, k_norm, eps, mu);
 }
 extern "C" __global__ void __launch_bounds__(256)
 mc_pf_rope_cache_parts_v4_bfloat(const float* part, uint32_t splits, uint32_t M, bf16_t* q_out, bf16_t* kc, bf16_t* vt, const float* fcos,
                                  const float* fsin, uint32_t H, uint32_t KV, uint32_t hd, uint32_t max_seq, uint32_t start_pos, uint32_t rope_row0,
                                  const bf16_t* q_norm, const bf16_t* k_norm, float eps, float mu)
 {
-    pf_rope_cache_v4_body<true>(part, splits, M, q_out, kc, vt, fcos, fsin, H, KV, hd, max_seq, start_pos, rope_row0, q_norm, k_norm, eps, mu);
+    pf_rope_cache_v4_body<true>(part, splits, M, q_out, pf_rows_linear{kc, vt, start_pos, rope_row0}, fcos, fsin, H, KV, hd, max_seq, q_norm, k_norm, eps, mu);
 }
 // w1|w3 partials -> act(a) * b (mc_pf_act_mul_bfloat with the reduce in front); ffn a multiple of 4
 extern "C" __global__ void
