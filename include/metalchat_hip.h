@@ -446,6 +446,20 @@ mc_status mc_ragged_export_kv(mc_batch* b, int32_t row, int32_t layer, void* key
  * lens[r] > max_seq_len, a token outside the vocabulary, a sum of lens above max_seq_len (split such a call by rows). */
 mc_status mc_rows_prefill(mc_batch* b, const int32_t* tokens, const int32_t* lens, const int32_t* positions, int32_t* next_tokens);
 
+/* ================================================================================================
+ * Part 2e -- chunks that see their row's context: the packed pass of Part 2d with ONE difference.  Chunk row i of row r
+ * (position p = positions[r] + i) attends to cache columns c <= p of row r, ALL of them: the columns below positions[r] are
+ * whatever the row's cache holds (from a fork, an import, steps, an earlier chunk or prompt pass).  Row r gets what lens[r]
+ * successive decode steps over its chunk compute -- each of the reference's steps sees the whole cache -- in one pass over
+ * the weights: a follow-up message fed to a live row, a long prompt fed in chunks between the other rows' steps.  At
+ * positions[r] == 0 the two calls mean the same thing (their bits may differ: the softmax sums are ordered differently).
+ * Everything else is Part 2d's: arguments, packing, seeds, next_tokens, the batch's logits, the lengths afterwards, the rewind
+ * by a position below the length, rows with lens[r] = 0 and the decoder untouched, and the refusals (the same conditions, the
+ * texts prefixed with this call's name; lens[r] == 1 stays refused: a one-token chunk is a ragged step).  A row's result does
+ * not depend on which other rows are in the call.  bfloat16, head_dim 64 and 128 (what a batch admits).
+ * ------------------------------------------------------------------------------------------ */
+mc_status mc_extend_rows(mc_batch* b, const int32_t* tokens, const int32_t* lens, const int32_t* positions, int32_t* next_tokens);
+
 /* Host-side helpers shared by tests and the synthetic initialiser. */
 /* value in [-7,7] (bits = 4) or [-127,127] (bits = 8), zero mean, of element (row, col) of matrix `matrix_id` */
 int32_t mc_synth_weight(uint64_t seed, uint32_t matrix_id, uint32_t row, uint32_t col, int32_t bits);

@@ -100,6 +100,11 @@ struct mc_batch {
     int32_t* pp_tab = nullptr;            // a packed prompt pass (mc_rows_prefill): segment table [8][4], then the tile table [.][2]
     int pp_tab_cap = 0;                   // (int32 entries)
     std::vector<int32_t> pp_host;
+    int32_t* px_tab = nullptr;            // mc_extend_rows: the range table [.][8] (kernels/extend_kernels.hip px_range)
+    int px_tab_cap = 0;                   // (int32 entries)
+    std::vector<int32_t> px_host, px_groups;
+    float *px_sums = nullptr, *px_part = nullptr; // scratch of one launch group: [px_slots][H][16], [px_slots][H][16][hd]
+    int px_slots = 0;
 
     ~mc_batch()
     {
@@ -611,16 +616,41 @@ mc_batch_get_logits(mc_batch* b, void* logits_T)
 
 // ---- Part 2d: the packed prompt pass ----
 
-mc_status
-mc_rows_prefill(mc_batch* b, const int32_t* tokens, const int32_t* lens, const int32_t* positions, int32_t* next_tokens)
+namespace {
+
+// How mc_extend_rows' attention deals the keys [0, S) of a 16-row tile over workgroups (kernels/extend_kernels.hip): the size of
+// a key range, a multiple of 128; S or more = one range.  The rule looks at the tile's own segment only -- never at what else is
+// in the call -- so that a row's bits depend on nothing but the row: a segment of at most two tiles (a short message) behind more
+// than 512 keys brings too few workgroups for its keys and takes two ranges; every other tile has one (measured: DESIGN.md
+// "Chunks that see their context").  MC_PX_KEYS is the experiment's handle: N = ranges of N keys for every tile, 0 = never split.
+int
+px_range_keys(int S, int len)
 {
-    if (!b || !tokens || !lens || !positions) return fail(MC_ERR_INVALID_ARGUMENT, "mc_rows_prefill: null argument");
+    if (const char* e = getenv("MC_PX_KEYS")) {
+        const int keys = atoi(e);
+        return keys <= 0 ? S : (keys + 127) / 128 * 128;
+    }
+    return len <= 32 && S > 512 ? ((S + 1) / 2 + 127) / 128 * 128 : S;
+}
+// the most ranges a tile can have in a cache of max_seq slots
+int
+px_ranges_max(int max_seq)
+{
+    const int keys = px_range_keys(max_seq, 2);
+    return (max_seq + keys - 1) / keys;
+}
+
+// mc_rows_prefill and mc_extend_rows: one body, `extend` selects the attention (and `who` the texts)
+mc_status
+rows_pass(mc_batch* b, const char* who_c, bool extend, const int32_t* tokens, const int32_t* lens, const int32_t* positions, int32_t* next_tokens)
+{
+    const std::string who = who_c;
     const mc_decoder_config& c = b->p.cfg;
     const int B = b->B;
     int64_t total = 0;
     int nseg = 0, ntiles = 0;
     for (int r = 0; r < B; r++) {
-        const std::string row = "mc_rows_prefill: row " + std::to_string(r) + ": ";
+        const std::string row = who + ": row " + std::to_string(r) + ": ";
         const int32_t len = lens[r], pos = positions[r];
         if (len < 0) return fail(MC_ERR_INVALID_ARGUMENT, row + "length below 0 (0 = the row is not in the call)");
         if (len == 0) continue;
@@ -639,9 +669,9 @@ mc_rows_prefill(mc_batch* b, const int32_t* tokens, const int32_t* lens, const i
         nseg++;
         ntiles += (len + 15) / 16;
     }
-    if (nseg == 0) return fail(MC_ERR_INVALID_ARGUMENT, "mc_rows_prefill: no row in the call (every length is 0)");
+    if (nseg == 0) return fail(MC_ERR_INVALID_ARGUMENT, who + ": no row in the call (every length is 0)");
     if (total > c.max_seq_len)
-        return fail(MC_ERR_INVALID_ARGUMENT, "mc_rows_prefill: the rows' lengths add up to " + std::to_string(total) +
+        return fail(MC_ERR_INVALID_ARGUMENT, who + ": the rows' lengths add up to " + std::to_string(total) +
                                                  ", more than max_seq_len (" + std::to_string(c.max_seq_len) + "): split the call by rows");
     const int M = (int)total;
     MC_HIP(hipSetDevice(b->p.ordinal));
@@ -693,6 +723,51 @@ mc_rows_prefill(mc_batch* b, const int32_t* tokens, const int32_t* lens, const i
     pk.fcos = b->fcos;
     pk.fsin = b->fsin;
     pk.x_out = b->x;
+    if (extend) {
+        // the range table: the keys [0, pos + last row of the tile] of every tile in ranges of px_range_keys, and the launch groups
+        const int per_tile = px_ranges_max(c.max_seq_len);
+        if (b->px_slots < per_tile) {
+            // scratch for one launch group, sized once: 64 MiB of partial outputs, and never less than one tile's ranges
+            MC_HIP(hipStreamSynchronize(b->p.stream));
+            if (b->px_sums) b->free_one(b->px_sums);
+            if (b->px_part) b->free_one(b->px_part);
+            b->px_sums = b->px_part = nullptr;
+            b->px_slots = 0;
+            const size_t per_slot = (size_t)c.n_heads * 16 * c.head_dim * sizeof(float);
+            const int slots = (int)std::min<size_t>(32768, std::max<size_t>((size_t)per_tile, ((size_t)64 << 20) / per_slot));
+            if ((s = b->alloc(&b->px_sums, sizeof(float) * slots * c.n_heads * 16)) != MC_OK) return s;
+            if ((s = b->alloc(&b->px_part, per_slot * slots)) != MC_OK) return s;
+            b->px_slots = slots;
+        }
+        b->px_host.clear();
+        b->px_groups.clear();
+        for (int ti = 0; ti < ntiles; ti++) {
+            const int si = tile[2 * ti], r0 = tile[2 * ti + 1], pos = seg[4 * si + 1], len = seg[4 * si + 3];
+            const int S = pos + std::min(r0 + 16, len), keys = px_range_keys(S, len), n = (S + keys - 1) / keys, first = (int)b->px_host.size() / 8;
+            if (b->px_groups.empty() || b->px_groups[b->px_groups.size() - 2] + n > b->px_slots) b->px_groups.insert(b->px_groups.end(), {first, 0, 0});
+            b->px_groups[b->px_groups.size() - 2] += n;
+            if (n > 1) b->px_groups.back() = 1;
+            for (int k = 0; k < n; k++)
+                b->px_host.insert(b->px_host.end(), {si, r0, k * keys, std::min((k + 1) * keys, S), first, n, 0, 0});
+        }
+        if ((int)b->px_host.size() > b->px_tab_cap) {
+            MC_HIP(hipStreamSynchronize(b->p.stream));
+            if (b->px_tab) b->free_one(b->px_tab);
+            b->px_tab = nullptr;
+            b->px_tab_cap = 0;
+            // (enough for any call: every tile of the largest call with the most ranges a tile can have)
+            const int cap = 8 * (c.max_seq_len / 16 + BATCH_MAX) * per_tile;
+            if ((s = b->alloc(&b->px_tab, sizeof(int32_t) * cap)) != MC_OK) return s;
+            b->px_tab_cap = cap;
+        }
+        MC_HIP(hipMemcpyAsync(b->px_tab, b->px_host.data(), sizeof(int32_t) * b->px_host.size(), hipMemcpyHostToDevice, b->p.stream));
+        pk.extend = true;
+        pk.ranges = b->px_tab;
+        pk.groups = b->px_groups.data();
+        pk.ngroups = (int)b->px_groups.size() / 3;
+        pk.sums = b->px_sums;
+        pk.part = b->px_part;
+    }
     if ((s = decoder_prefill_packed(b->d, tokens, M, pk)) != MC_OK) return s;
     if ((s = b->head("_rows_bfloat")) != MC_OK) return s;
     MC_HIP(hipStreamSynchronize(b->p.stream)); // (`tokens` is the caller's buffer; the tables are read by the launches)
@@ -700,6 +775,24 @@ mc_rows_prefill(mc_batch* b, const int32_t* tokens, const int32_t* lens, const i
         if (lens[r] > 0) b->lengths[r] = positions[r] + lens[r];
     if (next_tokens) MC_HIP(hipMemcpy(next_tokens, b->tokens_dev, sizeof(int32_t) * B, hipMemcpyDeviceToHost));
     return MC_OK;
+}
+
+} // namespace
+
+mc_status
+mc_rows_prefill(mc_batch* b, const int32_t* tokens, const int32_t* lens, const int32_t* positions, int32_t* next_tokens)
+{
+    if (!b || !tokens || !lens || !positions) return fail(MC_ERR_INVALID_ARGUMENT, "mc_rows_prefill: null argument");
+    return rows_pass(b, "mc_rows_prefill", false, tokens, lens, positions, next_tokens);
+}
+
+// ---- Part 2e: chunks that see their row's context ----
+
+mc_status
+mc_extend_rows(mc_batch* b, const int32_t* tokens, const int32_t* lens, const int32_t* positions, int32_t* next_tokens)
+{
+    if (!b || !tokens || !lens || !positions) return fail(MC_ERR_INVALID_ARGUMENT, "mc_extend_rows: null argument");
+    return rows_pass(b, "mc_extend_rows", true, tokens, lens, positions, next_tokens);
 }
 
 // ---- Part 2c: ragged rows ----

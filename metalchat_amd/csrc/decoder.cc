@@ -2094,7 +2094,34 @@ struct mc_decoder {
             }
             if (s != MC_OK) return s;
             const uint32_t win = (gemma && L.rope_table == 1) ? (uint32_t)window : 0u;
-            if (pk) {
+            if (pk && pk->extend) {
+                // chunks that see their context (mc_extend_rows, kernels/extend_kernels.hip): the exp sums of every key range, then
+                // p V over the ranges, then the ranges of a tile added in order; two query heads of a kv head per workgroup where
+                // the grouping allows it.  A group is as many whole tiles as the scratch holds (one group unless the call is huge).
+                s = timed("attention", [&] {
+                    const bool two = (H / KV) % 2 == 0;
+                    const std::string sfx = std::string(two ? "2" : "") + "_bfloat_hd" + std::to_string(hd);
+                    const unsigned gh = two ? H / 2 : H;
+                    for (int g = 0; g < pk->ngroups; g++) {
+                        const uint32_t e0 = (uint32_t)pk->groups[3 * g], ne = (uint32_t)pk->groups[3 * g + 1];
+                        mc_status ls = launch("mc_px_sums" + sfx, gh, ne, 1, 256, 0,
+                                              pack(pf_q, pk->segs, pk->ranges, e0, (const void*)pk_kc, pk->cache_stride, pk->sums, (uint32_t)H,
+                                                   (uint32_t)(H / KV), (uint32_t)cfg.max_seq_len, scale_T, (const void*)pf_etab));
+                        if (ls != MC_OK) return ls;
+                        ls = launch("mc_px_pv" + sfx, gh, ne, 1, 256, 0,
+                                    pack(pf_q, pk->segs, pk->ranges, e0, (const void*)pk_kc, (const void*)pk_vt, pk->cache_stride,
+                                         (const void*)pk->sums, pk->part, pf_att, (uint32_t)H, (uint32_t)(H / KV), (uint32_t)cfg.max_seq_len, scale_T,
+                                         (const void*)pf_etab));
+                        if (ls != MC_OK) return ls;
+                        if (!pk->groups[3 * g + 2]) continue; // no tile of the group is split: mc_px_pv wrote the outputs
+                        ls = launch("mc_px_reduce_bfloat_hd" + std::to_string(hd), H, ne, 1, 256, 0,
+                                    pack(pk->segs, pk->ranges, e0, (const void*)pk->part, pf_att, (uint32_t)H));
+                        if (ls != MC_OK) return ls;
+                    }
+                    return mc_status(MC_OK);
+                });
+                if (s != MC_OK) return s;
+            } else if (pk) {
                 // one or two query heads per workgroup by the rule of one prompt below, over the tiles of all segments; the LDS-tile and
                 // four-head forms have no packed counterpart (DESIGN.md "The packed prompt pass")
                 s = timed("attention", [&] {

@@ -50,7 +50,7 @@ mc_status decoder_cache_state(mc_decoder* d, int* kv_len, bool* rolled);
 mc_status decoder_launch(mc_decoder* d, const std::string& name, unsigned gx, unsigned gy, unsigned gz, unsigned bx, unsigned lds,
                          const std::vector<char>& args);
 
-// The packed prompt pass (mc_rows_prefill, kernels/packed_kernels.hip): the chunks of several sequences as one prompt pass of
+// The packed prompt pass (mc_rows_prefill and mc_extend_rows, kernels/packed_kernels.hip): the chunks of several sequences as one prompt pass of
 // M = sum of their lengths rows.  The tables are on the device already (uploaded on the decoder's stream).
 struct packed_prefill {
     const int32_t* segs = nullptr;  // [nseg][4]: batch row, position, offset of its first packed row, length (offsets ascending)
@@ -64,6 +64,14 @@ struct packed_prefill {
     const float* fcos = nullptr;    // the batch's rope table, rows = positions [0, max_seq_len)
     const float* fsin = nullptr;
     void* x_out = nullptr;          // [B][dim]: the last row of each segment lands in its batch row
+    // mc_extend_rows (kernels/extend_kernels.hip): chunk rows see their row's whole context.  The attention then takes the
+    // mc_px_* launches over the range table instead of mc_pp_attn* over the tile table.
+    bool extend = false;
+    const int32_t* ranges = nullptr; // device, [.][8]: px_range -- the key ranges of every tile, a tile's ranges adjacent
+    const int32_t* groups = nullptr; // HOST, [ngroups][3]: first range, range count, whether a tile has several ranges -- a launch
+    int ngroups = 0;                 //  group is whole tiles, at most as many ranges as the scratch has slots
+    float* sums = nullptr;           // scratch [slots][n_heads][16]: the exp row sums of a range
+    float* part = nullptr;           // scratch [slots][n_heads][16][head_dim]: the partial outputs of a range
 };
 // run_prefill over `tokens` (M ids, host) with the packed rope + cache and attention launches, then the gather into x_out; the
 // decoder's cache, step state, sampler, taps and head are not touched (its prompt scratch is)

@@ -10,3 +10,4 @@
 #include "prefill_kernels.hip"
 #include "batch_kernels.hip"
 #include "packed_kernels.hip"
+#include "extend_kernels.hip"

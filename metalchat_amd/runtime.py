@@ -205,6 +205,7 @@ def capi() -> C.CDLL:
         "mc_ragged_lengths": (i32, [vp, C.POINTER(i32)]),
         "mc_ragged_export_kv": (i32, [vp, i32, i32, vp, vp, C.POINTER(i32)]),
         "mc_rows_prefill": (i32, [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
+        "mc_extend_rows": (i32, [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
         "mc_synth_weight": (i32, [u64, u32, u32, u32, i32]),
         "mc_synth_scale": (f32, [u64, u32, u32, u32, i32, i32]),
         "mc_synth_value": (f32, [u64, u32, u32, i32, u32]),
@@ -882,15 +883,22 @@ class Batch:
     def prefill_rows(self, prompts, positions=None) -> np.ndarray:
         """prompts: B token arrays, None (or empty) for a row not in the call; positions: where each row's prompt starts in its
         cache (default 0).  Returns each row's pick after its last prompt token, -1 for a row not in the call."""
+        return self._rows_pass(capi().mc_rows_prefill, prompts, np.zeros(self.B, np.int32) if positions is None else positions)
+
+    def extend_rows(self, prompts, positions) -> np.ndarray:
+        """prefill_rows for chunks that see their row's context (Part 2e): row r's chunk starts at positions[r] and attends to
+        everything its cache holds below it -- a follow-up message on a live row, the next piece of a long prompt."""
+        return self._rows_pass(capi().mc_extend_rows, prompts, positions)
+
+    def _rows_pass(self, call, prompts, positions) -> np.ndarray:
         assert len(prompts) == self.B
         chunks = [np.asarray([] if p is None else p, dtype=np.int32).reshape(-1) for p in prompts]
         lens = np.array([c.shape[0] for c in chunks], dtype=np.int32)
         tokens = np.ascontiguousarray(np.concatenate(chunks + [np.zeros(1, np.int32)]))  # (never empty: a valid pointer)
-        p = self._positions(np.zeros(self.B, np.int32) if positions is None else positions)
+        p = self._positions(positions)
         out = np.zeros(self.B, dtype=np.int32)
         ptr = C.POINTER(C.c_int32)
-        _check(capi().mc_rows_prefill(self._h, tokens.ctypes.data_as(ptr), lens.ctypes.data_as(ptr), p.ctypes.data_as(ptr),
-                                      out.ctypes.data_as(ptr)))
+        _check(call(self._h, tokens.ctypes.data_as(ptr), lens.ctypes.data_as(ptr), p.ctypes.data_as(ptr), out.ctypes.data_as(ptr)))
         return out
 
     def set_seeds(self, pairs):
