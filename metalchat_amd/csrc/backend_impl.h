@@ -4,6 +4,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -57,6 +58,35 @@ struct launch_range {
     bool on = false;
 };
 bool trace_ranges_enabled();
+
+// kernel-argument packer: natural alignment of each argument, like the compiler's kernarg layout
+struct arg_pack {
+    std::vector<char> buf;
+    template <typename T> void
+    push(const T& v)
+    {
+        size_t off = (buf.size() + alignof(T) - 1) / alignof(T) * alignof(T);
+        buf.resize(off + sizeof(T));
+        memcpy(buf.data() + off, &v, sizeof(T));
+    }
+};
+template <typename... A> arg_pack
+pack(const A&... a)
+{
+    arg_pack p;
+    (p.push(a), ...);
+    return p;
+}
+
+// device memory for the length of one call (the staging buffers of a cache import / export): freed on every way out
+struct device_tmp {
+    void* ptr = nullptr;
+    device_tmp() = default;
+    device_tmp(const device_tmp&) = delete;
+    device_tmp& operator=(const device_tmp&) = delete;
+    ~device_tmp() { (void)hipFree(ptr); }
+    hipError_t alloc(size_t bytes) { return hipMalloc(&ptr, bytes); }
+};
 } // namespace mcimpl
 
 #define MC_HIP(expr)                                              \

@@ -20,55 +20,6 @@
 
 using namespace mcimpl;
 
-namespace {
-
-struct args {
-    std::vector<char> buf;
-    template <typename T> void
-    push(const T& v)
-    {
-        const size_t off = (buf.size() + alignof(T) - 1) / alignof(T) * alignof(T);
-        buf.resize(off + sizeof(T));
-        memcpy(buf.data() + off, &v, sizeof(T));
-    }
-};
-template <typename... A> std::vector<char>
-pack(const A&... a)
-{
-    args p;
-    (p.push(a), ...);
-    return p.buf;
-}
-
-// mirrors step_state (kernels/handoff.h)
-struct step_state_b {
-    int32_t token, pos, kv_len, write_slot, ring_base, step_index, rope_row, rolled, rope_start;
-    uint32_t epoch, err;
-    int32_t pad[1];
-};
-// mirrors sampler_params (kernels/sampler_kernels.hip)
-struct sampler_params_b {
-    uint32_t k, ncand, cap;
-    float inv_temp, top_p;
-    uint32_t nlists, kpad;
-};
-
-constexpr int BATCH_MAX = 8;
-constexpr unsigned BG_THREADS = 512; // mc_b_gemv_*: BG_WAVES = 8
-constexpr unsigned BG_K_UNIT = 1024; // in_features per workgroup slice: 8 waves x 128
-constexpr unsigned PB = 64;          // cache slots per scores workgroup (decode_kernels.hip)
-constexpr uint32_t SAMPLE_CAP = 4096;
-
-uint32_t
-sampler_chunk(uint32_t vocab, uint32_t kpad)
-{
-    uint32_t chunk = std::max(512u, kpad);
-    while (chunk < 2048u && (vocab + chunk - 1) / chunk > 1024u) chunk *= 2;
-    return chunk;
-}
-
-} // namespace
-
 struct mc_batch {
     mc_decoder* d = nullptr;
     decoder_parts p;
@@ -84,25 +35,26 @@ struct mc_batch {
     void *logits = nullptr;               // [B][vocab]
     float *expv = nullptr, *psum = nullptr; // [B][H][max_seq], [B][H][nsplit]
     float *fcos = nullptr, *fsin = nullptr; // rope table rows [0, max_seq)
-    step_state_b* st = nullptr;           // the shared position
-    step_state_b* rows = nullptr;         // [B]: token and step_index of each row (ragged calls: the whole state of each row)
+    step_state* st = nullptr;             // the shared position
+    step_state* rows = nullptr;           // [B]: token and step_index of each row (ragged calls: the whole state of each row)
     uint64_t* cand = nullptr;             // [B][lists * kpad]
     size_t cand_per_row = 0;
     uint64_t* seeds = nullptr;
-    int n_seed_pairs = 0, seed_cap = 0;
+    int n_seed_pairs = 0, seed_cap = 0;   // (capacity in pairs)
     int32_t* tokens_dev = nullptr;
     int tokens_cap = 0;
-    std::vector<step_state_b> rows_host;
+    std::vector<step_state> rows_host;
     std::vector<int32_t> lengths;         // [B]: valid cache positions of each row
     int32_t* stop_dev = nullptr;          // the stop ids of a ragged call
     int stop_cap = 0;
     std::vector<int32_t> stop_host;
-    int32_t* pp_tab = nullptr;            // a packed prompt pass (mc_rows_prefill): segment table [8][4], then the tile table [.][2]
-    int pp_tab_cap = 0;                   // (int32 entries)
-    std::vector<int32_t> pp_host;
-    int32_t* px_tab = nullptr;            // mc_extend_rows: the range table [.][8] (kernels/extend_kernels.hip px_range)
-    int px_tab_cap = 0;                   // (int32 entries)
-    std::vector<int32_t> px_host, px_groups;
+    char* pp_tab = nullptr;               // a packed prompt pass (mc_rows_prefill): pp_seg[BATCH_MAX], then the pp_tile table
+    int pp_tab_cap = 0;                   // (bytes)
+    std::vector<char> pp_host;            // the same bytes on the host: one upload
+    px_range* px_tab = nullptr;           // mc_extend_rows: the range table
+    int px_tab_cap = 0;
+    std::vector<px_range> px_host;
+    std::vector<px_group> px_groups;
     float *px_sums = nullptr, *px_part = nullptr; // scratch of one launch group: [px_slots][H][16], [px_slots][H][16][hd]
     int px_slots = 0;
 
@@ -133,12 +85,31 @@ struct mc_batch {
         if (it != allocs.end()) allocs.erase(it);
         (void)hipFree(v);
     }
+    // a buffer that only grows: `need` elements of `elem` bytes fit in `have`, or the stream drains and a zeroed buffer of `cap`
+    // elements takes its place (nothing in flight reads the old one then)
+    template <typename P> mc_status
+    reserve(P*& ptr, int& have, int need, int cap, size_t elem = sizeof(P))
+    {
+        if (need <= have) return MC_OK;
+        MC_HIP(hipStreamSynchronize(p.stream));
+        if (ptr) free_one(ptr);
+        ptr = nullptr;
+        have = 0;
+        mc_status s = alloc(&ptr, elem * (size_t)cap);
+        if (s != MC_OK) return s;
+        have = cap;
+        return MC_OK;
+    }
 
     mc_status
-    launch(const std::string& name, unsigned gx, unsigned gy, unsigned gz, unsigned bx, unsigned lds, const std::vector<char>& a)
+    launch(const std::string& name, unsigned gx, unsigned gy, unsigned gz, unsigned bx, unsigned lds, arg_pack&& a)
     {
-        return decoder_launch(d, name, gx, gy, gz, bx, lds, a);
+        return decoder_launch(d, name, gx, gy, gz, bx, lds, std::move(a));
     }
+
+    // the two tables inside pp_tab / pp_host.data()
+    static pp_seg* pp_segs(char* tab) { return reinterpret_cast<pp_seg*>(tab); }
+    static pp_tile* pp_tiles(char* tab) { return reinterpret_cast<pp_tile*>(tab + sizeof(pp_seg) * BATCH_MAX); }
 
     char* kc_of(int layer, int row) const { return (char*)kc + ((size_t)layer * B + row) * cache_elems * 2; }
     char* vt_of(int layer, int row) const { return (char*)vt + ((size_t)layer * B + row) * cache_elems * 2; }
@@ -201,7 +172,7 @@ struct mc_batch {
         if (s != MC_OK) return s;
         // the per-row launches: the lockstep kernel reads the shared state, its _rows form row r's own
         const std::string sfx = ragged ? "_rows_bfloat" : "_bfloat";
-        const step_state_b* state = ragged ? rows : st;
+        const step_state* state = ragged ? rows : st;
         for (size_t li = 0; li < p.layers.size(); li++) {
             const batch_layer& L = p.layers[li];
             const int l = (int)li;
@@ -240,45 +211,33 @@ struct mc_batch {
         if (sm.kind == MC_SAMPLER_GREEDY)
             return launch("mc_b_argmax" + sfx, 1, B, 1, 1024, 0, pack(logits, (uint32_t)c.vocab, rows, tokens_dev));
         // make_default_sampler per row (sampler_kernels.hip): per-chunk candidates, then one workgroup per row
-        uint32_t kpad = 1;
-        while (kpad < (uint32_t)sm.top_k) kpad *= 2;
-        const uint32_t k = (uint32_t)std::min(sm.top_k, c.vocab);
-        const uint32_t chunk = sampler_chunk((uint32_t)c.vocab, kpad), lists = ((uint32_t)c.vocab + chunk - 1) / chunk;
-        if (lists > 1024u || (size_t)lists * kpad > cand_per_row)
+        sampler_params sp;
+        uint32_t chunk;
+        if ((s = sampler_plan(sm.top_k, c.vocab, sm.inv_temp_T, sm.top_p_T, &sp, &chunk)) != MC_OK) return s;
+        if ((size_t)sp.nlists * sp.kpad > cand_per_row)
             return fail(MC_ERR_RUNTIME, "sampler: the fused sampler handles rows of up to 2048 * 1024 logits");
-        s = launch("mc_b_topk_candidates_bfloat", lists, B, 1, 64, 0, pack(logits, (uint32_t)c.vocab, kpad, cand, chunk));
+        s = launch("mc_b_topk_candidates_bfloat", sp.nlists, B, 1, 64, 0, pack(logits, (uint32_t)c.vocab, sp.kpad, cand, chunk));
         if (s != MC_OK) return s;
-        const sampler_params_b sp{k, lists * kpad, SAMPLE_CAP, sm.inv_temp_T, sm.top_p_T, lists, kpad};
-        return launch("mc_b_sample" + sfx, 1, B, 1, 128, SAMPLE_CAP * 8,
+        return launch("mc_b_sample" + sfx, 1, B, 1, 128, sp.cap * 8,
                       pack(cand, sp, seeds, (uint32_t)n_seed_pairs, rows, tokens_dev));
     }
 
-    // rows' tokens and step indices for token 0 of a call (step_index = r: seed pair r % n_pairs, tokens_out[0][r])
+    // rows' tokens and step indices for token 0 of a call (step_index = r: seed pair r % n_pairs, tokens_out[0][r]); a ragged
+    // call: their positions too (mc_b_rows_begin derives the rest), an idle row has no token
     mc_status
-    start_rows(const int32_t* tokens)
+    start_rows(const int32_t* tokens, const int32_t* positions = nullptr)
     {
-        rows_host.assign(B, step_state_b{});
+        rows_host.assign(B, step_state{});
         for (int r = 0; r < B; r++) {
-            rows_host[r].token = tokens[r];
+            if (positions) rows_host[r].pos = positions[r];
+            rows_host[r].token = positions && positions[r] < 0 ? -1 : tokens[r];
             rows_host[r].step_index = r;
         }
-        MC_HIP(hipMemcpyAsync(rows, rows_host.data(), sizeof(step_state_b) * B, hipMemcpyHostToDevice, p.stream));
+        MC_HIP(hipMemcpyAsync(rows, rows_host.data(), sizeof(step_state) * B, hipMemcpyHostToDevice, p.stream));
         return MC_OK;
     }
 
-    mc_status
-    ensure_tokens(int n)
-    {
-        if (n * B <= tokens_cap) return MC_OK;
-        MC_HIP(hipStreamSynchronize(p.stream));
-        if (tokens_dev) free_one(tokens_dev);
-        tokens_dev = nullptr;
-        tokens_cap = 0;
-        mc_status s = alloc(&tokens_dev, sizeof(int32_t) * (size_t)n * B);
-        if (s != MC_OK) return s;
-        tokens_cap = n * B;
-        return MC_OK;
-    }
+    mc_status ensure_tokens(int n) { return reserve(tokens_dev, tokens_cap, n * B, n * B); }
 
     mc_status
     check_tokens(const int32_t* tokens) const
@@ -312,28 +271,14 @@ struct mc_batch {
         return MC_OK;
     }
 
-    // token 0 of a ragged call: rows' tokens, positions and step indices (mc_b_rows_begin derives the rest), the stop ids,
-    // and -1 in every slot of tokens_out
+    // token 0 of a ragged call: the rows, the stop ids, and -1 in every slot of tokens_out
     mc_status
     start_ragged(const int32_t* tokens, const int32_t* positions, const int32_t* stop_ids, int n_stop, int n)
     {
-        rows_host.assign(B, step_state_b{});
-        for (int r = 0; r < B; r++) {
-            rows_host[r].pos = positions[r];
-            rows_host[r].token = positions[r] < 0 ? -1 : tokens[r];
-            rows_host[r].step_index = r;
-        }
-        MC_HIP(hipMemcpyAsync(rows, rows_host.data(), sizeof(step_state_b) * B, hipMemcpyHostToDevice, p.stream));
+        mc_status s = start_rows(tokens, positions);
+        if (s != MC_OK) return s;
         stop_host.assign(stop_ids, stop_ids + n_stop);
-        if (n_stop > stop_cap) {
-            MC_HIP(hipStreamSynchronize(p.stream));
-            if (stop_dev) free_one(stop_dev);
-            stop_dev = nullptr;
-            stop_cap = 0;
-            mc_status s = alloc(&stop_dev, sizeof(int32_t) * n_stop);
-            if (s != MC_OK) return s;
-            stop_cap = n_stop;
-        }
+        if ((s = reserve(stop_dev, stop_cap, n_stop, n_stop)) != MC_OK) return s;
         if (n_stop > 0)
             MC_HIP(hipMemcpyAsync(stop_dev, stop_host.data(), sizeof(int32_t) * n_stop, hipMemcpyHostToDevice, p.stream));
         MC_HIP(hipMemsetAsync(tokens_dev, 0xFF, sizeof(int32_t) * (size_t)n * B, p.stream));
@@ -394,6 +339,35 @@ find_row(mc_batch* b, int32_t row, int32_t layer, const char* what)
     return MC_OK;
 }
 
+// mc_batch_export_kv and mc_ragged_export_kv: row `row`'s cache of `layer` through mc_kv_export_bfloat, which takes kv_len (and
+// the ring) from the device step state `state`, into staging buffers of `cap` positions; then n positions to the host.
+// n < 0: n = that kv_len, read back behind the launch and reported in *n_out.
+mc_status
+export_kv(mc_batch* b, const char* what, int32_t row, int32_t layer, const step_state* state, int32_t cap, int32_t n, int32_t* n_out,
+          void* keys, void* values)
+{
+    const mc_decoder_config& c = b->p.cfg;
+    const size_t per_pos = (size_t)c.n_kv_heads * c.head_dim * 2;
+    device_tmp kt, vtmp;
+    hipError_t e = kt.alloc(cap * per_pos);
+    if (e == hipSuccess) e = vtmp.alloc(cap * per_pos);
+    if (e != hipSuccess) return hip_fail(e, what);
+    mc_status s = b->launch("mc_kv_export_bfloat", 512, 1, 1, 256, 0,
+                            pack((const void*)b->kc_of(layer, row), (const void*)b->vt_of(layer, row), kt.ptr, vtmp.ptr, (const void*)state,
+                                 (uint32_t)c.n_kv_heads, (uint32_t)c.head_dim, (uint32_t)c.max_seq_len, (uint32_t)b->p.pre_len));
+    e = hipStreamSynchronize(b->p.stream);
+    if (s == MC_OK && e == hipSuccess && n < 0) {
+        step_state st{};
+        e = hipMemcpy(&st, state, sizeof st, hipMemcpyDeviceToHost);
+        n = st.kv_len;
+        if (n_out) *n_out = n;
+    }
+    if (s == MC_OK && e == hipSuccess && keys) e = hipMemcpy(keys, kt.ptr, n * per_pos, hipMemcpyDeviceToHost);
+    if (s == MC_OK && e == hipSuccess && values) e = hipMemcpy(values, vtmp.ptr, n * per_pos, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return hip_fail(e, what);
+    return s;
+}
+
 } // namespace
 
 extern "C" {
@@ -433,7 +407,7 @@ mc_batch_create(mc_decoder* d, int32_t batch, mc_batch** out)
         (s = b->alloc(&b->psum, sizeof(float) * batch * H * b->nsplit)) != MC_OK ||
         (s = b->alloc(&b->fcos, sizeof(float) * c.max_seq_len * (hd / 2))) != MC_OK ||
         (s = b->alloc(&b->fsin, sizeof(float) * c.max_seq_len * (hd / 2))) != MC_OK ||
-        (s = b->alloc(&b->st, sizeof(step_state_b))) != MC_OK || (s = b->alloc(&b->rows, sizeof(step_state_b) * batch)) != MC_OK ||
+        (s = b->alloc(&b->st, sizeof(step_state))) != MC_OK || (s = b->alloc(&b->rows, sizeof(step_state) * batch)) != MC_OK ||
         (s = b->alloc(&b->cand, sizeof(uint64_t) * batch * b->cand_per_row)) != MC_OK)
         return s;
     // nn::rope's table for positions [0, max_seq_len) (a row depends on the absolute position only, nn/embedding.h:159-165)
@@ -496,20 +470,18 @@ mc_batch_import_kv(mc_batch* b, int32_t row, int32_t layer, const void* keys, co
         return fail(MC_ERR_INVALID_ARGUMENT, "mc_batch_import_kv: n_valid must lie in [1, max_seq_len]");
     MC_HIP(hipSetDevice(b->p.ordinal));
     const size_t nb = (size_t)n_valid * c.n_kv_heads * c.head_dim * 2;
-    void *kt = nullptr, *vtmp = nullptr;
-    MC_HIP(hipMalloc(&kt, nb));
-    hipError_t e = hipMalloc(&vtmp, nb);
-    if (e == hipSuccess) e = hipMemcpy(kt, keys, nb, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(vtmp, values, nb, hipMemcpyHostToDevice);
+    device_tmp kt, vtmp;
+    MC_HIP(kt.alloc(nb));
+    hipError_t e = vtmp.alloc(nb);
+    if (e == hipSuccess) e = hipMemcpy(kt.ptr, keys, nb, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(vtmp.ptr, values, nb, hipMemcpyHostToDevice);
     if (e == hipSuccess) {
         s = b->launch("mc_kv_import_bfloat", 512, 1, 1, 256, 0,
-                      pack((void*)b->kc_of(layer, row), (void*)b->vt_of(layer, row), (const void*)kt, (const void*)vtmp,
+                      pack((void*)b->kc_of(layer, row), (void*)b->vt_of(layer, row), (const void*)kt.ptr, (const void*)vtmp.ptr,
                            (uint32_t)n_valid, (uint32_t)c.n_kv_heads, (uint32_t)c.head_dim, (uint32_t)c.max_seq_len));
         if (s == MC_OK) s = b->set_pos(n_valid - 1);
         e = hipStreamSynchronize(b->p.stream);
     }
-    (void)hipFree(kt);
-    (void)hipFree(vtmp);
     if (e != hipSuccess) return hip_fail(e, "mc_batch_import_kv");
     if (s == MC_OK) b->lengths[row] = n_valid;
     return s;
@@ -520,30 +492,9 @@ mc_batch_export_kv(mc_batch* b, int32_t row, int32_t layer, void* keys, void* va
 {
     mc_status s = find_row(b, row, layer, "mc_batch_export_kv");
     if (s != MC_OK) return s;
-    const mc_decoder_config& c = b->p.cfg;
     MC_HIP(hipSetDevice(b->p.ordinal));
-    const size_t bytes = (size_t)c.max_seq_len * c.n_kv_heads * c.head_dim * 2;
-    void *kt = nullptr, *vtmp = nullptr;
-    MC_HIP(hipMalloc(&kt, bytes));
-    hipError_t e = hipMalloc(&vtmp, bytes);
-    step_state_b st{};
-    if (e == hipSuccess) {
-        s = b->launch("mc_kv_export_bfloat", 512, 1, 1, 256, 0,
-                      pack((const void*)b->kc_of(layer, row), (const void*)b->vt_of(layer, row), kt, vtmp, (const void*)b->st,
-                           (uint32_t)c.n_kv_heads, (uint32_t)c.head_dim, (uint32_t)c.max_seq_len, (uint32_t)b->p.pre_len));
-        e = hipStreamSynchronize(b->p.stream);
-        if (s == MC_OK && e == hipSuccess) {
-            e = hipMemcpy(&st, b->st, sizeof st, hipMemcpyDeviceToHost);
-            const size_t nb = (size_t)st.kv_len * c.n_kv_heads * c.head_dim * 2;
-            if (e == hipSuccess && keys) e = hipMemcpy(keys, kt, nb, hipMemcpyDeviceToHost);
-            if (e == hipSuccess && values) e = hipMemcpy(values, vtmp, nb, hipMemcpyDeviceToHost);
-            if (n_valid) *n_valid = st.kv_len;
-        }
-    }
-    (void)hipFree(kt);
-    if (vtmp) (void)hipFree(vtmp);
-    if (e != hipSuccess) return hip_fail(e, "mc_batch_export_kv");
-    return s;
+    // kv_len of the batch's shared state: the position of the last lockstep step, fork or import, whichever row that was for
+    return export_kv(b, "mc_batch_export_kv", row, layer, b->st, b->p.cfg.max_seq_len, -1, n_valid, keys, values);
 }
 
 mc_status
@@ -587,15 +538,8 @@ mc_batch_set_seeds(mc_batch* b, const uint64_t* seeds, int32_t n_pairs)
 {
     if (!b || (n_pairs > 0 && !seeds) || n_pairs < 0) return fail(MC_ERR_INVALID_ARGUMENT, "mc_batch_set_seeds: bad argument");
     MC_HIP(hipSetDevice(b->p.ordinal));
-    if (n_pairs > b->seed_cap) {
-        MC_HIP(hipStreamSynchronize(b->p.stream));
-        if (b->seeds) b->free_one(b->seeds);
-        b->seeds = nullptr;
-        b->seed_cap = 0;
-        mc_status s = b->alloc(&b->seeds, sizeof(uint64_t) * 2 * n_pairs);
-        if (s != MC_OK) return s;
-        b->seed_cap = n_pairs;
-    }
+    mc_status s = b->reserve(b->seeds, b->seed_cap, n_pairs, n_pairs, 2 * sizeof(uint64_t));
+    if (s != MC_OK) return s;
     if (n_pairs > 0) {
         MC_HIP(hipStreamSynchronize(b->p.stream));
         MC_HIP(hipMemcpy(b->seeds, seeds, sizeof(uint64_t) * 2 * n_pairs, hipMemcpyHostToDevice));
@@ -640,16 +584,15 @@ px_ranges_max(int max_seq)
     return (max_seq + keys - 1) / keys;
 }
 
-// mc_rows_prefill and mc_extend_rows: one body, `extend` selects the attention (and `who` the texts)
+// step 1 of rows_pass: the call's lengths, positions and tokens against the rows' caches; counts its packed rows, segments and tiles
 mc_status
-rows_pass(mc_batch* b, const char* who_c, bool extend, const int32_t* tokens, const int32_t* lens, const int32_t* positions, int32_t* next_tokens)
+rows_check(const mc_batch* b, const std::string& who, const int32_t* tokens, const int32_t* lens, const int32_t* positions, int* M, int* nseg,
+           int* ntiles)
 {
-    const std::string who = who_c;
     const mc_decoder_config& c = b->p.cfg;
-    const int B = b->B;
     int64_t total = 0;
-    int nseg = 0, ntiles = 0;
-    for (int r = 0; r < B; r++) {
+    *nseg = *ntiles = 0;
+    for (int r = 0; r < b->B; r++) {
         const std::string row = who + ": row " + std::to_string(r) + ": ";
         const int32_t len = lens[r], pos = positions[r];
         if (len < 0) return fail(MC_ERR_INVALID_ARGUMENT, row + "length below 0 (0 = the row is not in the call)");
@@ -666,56 +609,79 @@ rows_pass(mc_batch* b, const char* who_c, bool extend, const int32_t* tokens, co
             if (tokens[total + i] < 0 || tokens[total + i] >= c.vocab)
                 return fail(MC_ERR_INVALID_ARGUMENT, row + "token id outside the vocabulary");
         total += len;
-        nseg++;
-        ntiles += (len + 15) / 16;
+        (*nseg)++;
+        *ntiles += (len + PP_TILE_ROWS - 1) / PP_TILE_ROWS;
     }
-    if (nseg == 0) return fail(MC_ERR_INVALID_ARGUMENT, who + ": no row in the call (every length is 0)");
+    if (*nseg == 0) return fail(MC_ERR_INVALID_ARGUMENT, who + ": no row in the call (every length is 0)");
     if (total > c.max_seq_len)
         return fail(MC_ERR_INVALID_ARGUMENT, who + ": the rows' lengths add up to " + std::to_string(total) +
                                                  ", more than max_seq_len (" + std::to_string(c.max_seq_len) + "): split the call by rows");
-    const int M = (int)total;
-    MC_HIP(hipSetDevice(b->p.ordinal));
-    // the segment table (row, position, offset, length; packed in row order) and the attention tiles (segment, first row)
-    b->pp_host.assign((size_t)BATCH_MAX * 4 + (size_t)ntiles * 2, 0);
-    int32_t* seg = b->pp_host.data();
-    int32_t* tile = seg + BATCH_MAX * 4;
-    b->rows_host.assign(B, step_state_b{});
-    for (int r = 0, off = 0, si = 0, ti = 0; r < B; r++) {
+    *M = (int)total;
+    return MC_OK;
+}
+
+// step 2: the rows' states, the segment table (packed in row order) and the ntiles attention tiles of the segments
+void
+rows_tables(mc_batch* b, const int32_t* lens, const int32_t* positions, int ntiles)
+{
+    b->rows_host.assign(b->B, step_state{});
+    b->pp_host.assign(sizeof(pp_seg) * BATCH_MAX + sizeof(pp_tile) * ntiles, 0);
+    pp_seg* seg = mc_batch::pp_segs(b->pp_host.data());
+    pp_tile* tile = mc_batch::pp_tiles(b->pp_host.data());
+    for (int r = 0, off = 0, si = 0; r < b->B; r++) {
         b->rows_host[r].pos = lens[r] > 0 ? positions[r] : -1;
         b->rows_host[r].token = -1;
         b->rows_host[r].step_index = r; // seed pair r % n_pairs, next_tokens[r]
         if (lens[r] == 0) continue;
-        seg[4 * si + 0] = r;
-        seg[4 * si + 1] = positions[r];
-        seg[4 * si + 2] = off;
-        seg[4 * si + 3] = lens[r];
-        for (int t = 0; t < lens[r]; t += 16, ti++) {
-            tile[2 * ti] = si;
-            tile[2 * ti + 1] = t;
-        }
+        for (int t = 0; t < lens[r]; t += PP_TILE_ROWS) *tile++ = {si, t};
+        seg[si++] = {r, positions[r], off, lens[r]};
         off += lens[r];
-        si++;
     }
-    mc_status s;
-    if ((int)b->pp_host.size() > b->pp_tab_cap) {
-        MC_HIP(hipStreamSynchronize(b->p.stream));
-        if (b->pp_tab) b->free_one(b->pp_tab);
-        b->pp_tab = nullptr;
-        b->pp_tab_cap = 0;
-        // (enough for any call: at most max_seq_len rows in at most 8 segments)
-        const int cap = BATCH_MAX * 4 + 2 * (c.max_seq_len / 16 + BATCH_MAX);
-        if ((s = b->alloc(&b->pp_tab, sizeof(int32_t) * cap)) != MC_OK) return s;
-        b->pp_tab_cap = cap;
+}
+
+// step 3 (mc_extend_rows): the range table -- the keys [0, pos + last row of the tile] of every tile in ranges of px_range_keys --
+// and the launch groups: whole tiles, at most `slots` ranges each
+void
+rows_ranges(mc_batch* b, int ntiles, int slots)
+{
+    b->px_host.clear();
+    b->px_groups.clear();
+    for (int ti = 0; ti < ntiles; ti++) {
+        const pp_tile t = mc_batch::pp_tiles(b->pp_host.data())[ti];
+        const pp_seg g = mc_batch::pp_segs(b->pp_host.data())[t.seg];
+        const int S = g.pos + std::min(t.r0 + PP_TILE_ROWS, g.len), keys = px_range_keys(S, g.len), n = (S + keys - 1) / keys;
+        const int first = (int)b->px_host.size();
+        if (b->px_groups.empty() || b->px_groups.back().count + n > slots) b->px_groups.push_back({first, 0, false});
+        b->px_groups.back().count += n;
+        if (n > 1) b->px_groups.back().split = true;
+        for (int k = 0; k < n; k++) b->px_host.push_back({t.seg, t.r0, k * keys, std::min((k + 1) * keys, S), first, n, 0, 0});
     }
-    MC_HIP(hipMemcpyAsync(b->pp_tab, b->pp_host.data(), sizeof(int32_t) * b->pp_host.size(), hipMemcpyHostToDevice, b->p.stream));
-    MC_HIP(hipMemcpyAsync(b->rows, b->rows_host.data(), sizeof(step_state_b) * B, hipMemcpyHostToDevice, b->p.stream));
+}
+
+// mc_rows_prefill and mc_extend_rows: one body, `extend` selects the attention (and `who` the texts)
+mc_status
+rows_pass(mc_batch* b, const char* who, bool extend, const int32_t* tokens, const int32_t* lens, const int32_t* positions, int32_t* next_tokens)
+{
+    const mc_decoder_config& c = b->p.cfg;
+    const int B = b->B;
+    int M = 0, nseg = 0, ntiles = 0;
+    mc_status s = rows_check(b, who, tokens, lens, positions, &M, &nseg, &ntiles);
+    if (s != MC_OK) return s;
+    MC_HIP(hipSetDevice(b->p.ordinal));
+    rows_tables(b, lens, positions, ntiles);
+    // (enough for any call: at most max_seq_len rows in at most 8 segments)
+    const int tiles_max = c.max_seq_len / PP_TILE_ROWS + BATCH_MAX;
+    if ((s = b->reserve(b->pp_tab, b->pp_tab_cap, (int)b->pp_host.size(), (int)(sizeof(pp_seg) * BATCH_MAX + sizeof(pp_tile) * tiles_max))) != MC_OK)
+        return s;
+    MC_HIP(hipMemcpyAsync(b->pp_tab, b->pp_host.data(), b->pp_host.size(), hipMemcpyHostToDevice, b->p.stream));
+    packed_prefill pk;
+    pk.segs = mc_batch::pp_segs(b->pp_tab);
+    pk.nseg = nseg;
+    pk.tiles = mc_batch::pp_tiles(b->pp_tab);
+    pk.ntiles = ntiles;
+    MC_HIP(hipMemcpyAsync(b->rows, b->rows_host.data(), sizeof(step_state) * B, hipMemcpyHostToDevice, b->p.stream));
     if ((s = b->ensure_tokens(1)) != MC_OK) return s;
     MC_HIP(hipMemsetAsync(b->tokens_dev, 0xFF, sizeof(int32_t) * B, b->p.stream));
-    packed_prefill pk;
-    pk.segs = b->pp_tab;
-    pk.nseg = nseg;
-    pk.tiles = b->pp_tab + BATCH_MAX * 4;
-    pk.ntiles = ntiles;
     pk.kc = b->kc;
     pk.vt = b->vt;
     pk.B = B;
@@ -724,47 +690,22 @@ rows_pass(mc_batch* b, const char* who_c, bool extend, const int32_t* tokens, co
     pk.fsin = b->fsin;
     pk.x_out = b->x;
     if (extend) {
-        // the range table: the keys [0, pos + last row of the tile] of every tile in ranges of px_range_keys, and the launch groups
+        // scratch for one launch group, sized once: 64 MiB of partial outputs, and never less than one tile's ranges
         const int per_tile = px_ranges_max(c.max_seq_len);
-        if (b->px_slots < per_tile) {
-            // scratch for one launch group, sized once: 64 MiB of partial outputs, and never less than one tile's ranges
-            MC_HIP(hipStreamSynchronize(b->p.stream));
-            if (b->px_sums) b->free_one(b->px_sums);
-            if (b->px_part) b->free_one(b->px_part);
-            b->px_sums = b->px_part = nullptr;
-            b->px_slots = 0;
-            const size_t per_slot = (size_t)c.n_heads * 16 * c.head_dim * sizeof(float);
-            const int slots = (int)std::min<size_t>(32768, std::max<size_t>((size_t)per_tile, ((size_t)64 << 20) / per_slot));
-            if ((s = b->alloc(&b->px_sums, sizeof(float) * slots * c.n_heads * 16)) != MC_OK) return s;
-            if ((s = b->alloc(&b->px_part, per_slot * slots)) != MC_OK) return s;
-            b->px_slots = slots;
-        }
-        b->px_host.clear();
-        b->px_groups.clear();
-        for (int ti = 0; ti < ntiles; ti++) {
-            const int si = tile[2 * ti], r0 = tile[2 * ti + 1], pos = seg[4 * si + 1], len = seg[4 * si + 3];
-            const int S = pos + std::min(r0 + 16, len), keys = px_range_keys(S, len), n = (S + keys - 1) / keys, first = (int)b->px_host.size() / 8;
-            if (b->px_groups.empty() || b->px_groups[b->px_groups.size() - 2] + n > b->px_slots) b->px_groups.insert(b->px_groups.end(), {first, 0, 0});
-            b->px_groups[b->px_groups.size() - 2] += n;
-            if (n > 1) b->px_groups.back() = 1;
-            for (int k = 0; k < n; k++)
-                b->px_host.insert(b->px_host.end(), {si, r0, k * keys, std::min((k + 1) * keys, S), first, n, 0, 0});
-        }
-        if ((int)b->px_host.size() > b->px_tab_cap) {
-            MC_HIP(hipStreamSynchronize(b->p.stream));
-            if (b->px_tab) b->free_one(b->px_tab);
-            b->px_tab = nullptr;
-            b->px_tab_cap = 0;
-            // (enough for any call: every tile of the largest call with the most ranges a tile can have)
-            const int cap = 8 * (c.max_seq_len / 16 + BATCH_MAX) * per_tile;
-            if ((s = b->alloc(&b->px_tab, sizeof(int32_t) * cap)) != MC_OK) return s;
-            b->px_tab_cap = cap;
-        }
-        MC_HIP(hipMemcpyAsync(b->px_tab, b->px_host.data(), sizeof(int32_t) * b->px_host.size(), hipMemcpyHostToDevice, b->p.stream));
+        const size_t per_slot = (size_t)c.n_heads * PP_TILE_ROWS * c.head_dim * sizeof(float);
+        const int slots = (int)std::min<size_t>(32768, std::max<size_t>((size_t)per_tile, ((size_t)64 << 20) / per_slot));
+        int sums_slots = b->px_slots;
+        if ((s = b->reserve(b->px_sums, sums_slots, per_tile, slots, sizeof(float) * c.n_heads * PP_TILE_ROWS)) != MC_OK ||
+            (s = b->reserve(b->px_part, b->px_slots, per_tile, slots, per_slot)) != MC_OK)
+            return s;
+        rows_ranges(b, ntiles, b->px_slots);
+        // (enough for any call: every tile of the largest call with the most ranges a tile can have)
+        if ((s = b->reserve(b->px_tab, b->px_tab_cap, (int)b->px_host.size(), tiles_max * per_tile)) != MC_OK) return s;
+        MC_HIP(hipMemcpyAsync(b->px_tab, b->px_host.data(), sizeof(px_range) * b->px_host.size(), hipMemcpyHostToDevice, b->p.stream));
         pk.extend = true;
         pk.ranges = b->px_tab;
         pk.groups = b->px_groups.data();
-        pk.ngroups = (int)b->px_groups.size() / 3;
+        pk.ngroups = (int)b->px_groups.size();
         pk.sums = b->px_sums;
         pk.part = b->px_part;
     }
@@ -854,33 +795,18 @@ mc_ragged_export_kv(mc_batch* b, int32_t row, int32_t layer, void* keys, void* v
 {
     mc_status s = find_row(b, row, layer, "mc_ragged_export_kv");
     if (s != MC_OK) return s;
-    const mc_decoder_config& c = b->p.cfg;
     const int32_t n = b->lengths[row];
     if (n_valid) *n_valid = n;
     if (n == 0) return MC_OK;
     MC_HIP(hipSetDevice(b->p.ordinal));
     // the export kernel reads kv_len (and a ring of 0) from a state of its own: row `row`'s length
-    step_state_b st{};
+    step_state st{};
     st.kv_len = n;
-    const size_t nb = (size_t)n * c.n_kv_heads * c.head_dim * 2;
-    void *kt = nullptr, *vtmp = nullptr, *stv = nullptr;
-    MC_HIP(hipMalloc(&stv, sizeof st));
-    hipError_t e = hipMalloc(&kt, nb);
-    if (e == hipSuccess) e = hipMalloc(&vtmp, nb);
-    if (e == hipSuccess) e = hipMemcpyAsync(stv, &st, sizeof st, hipMemcpyHostToDevice, b->p.stream);
-    if (e == hipSuccess) {
-        s = b->launch("mc_kv_export_bfloat", 512, 1, 1, 256, 0,
-                      pack((const void*)b->kc_of(layer, row), (const void*)b->vt_of(layer, row), kt, vtmp, (const void*)stv,
-                           (uint32_t)c.n_kv_heads, (uint32_t)c.head_dim, (uint32_t)c.max_seq_len, (uint32_t)b->p.pre_len));
-        e = hipStreamSynchronize(b->p.stream);
-        if (s == MC_OK && e == hipSuccess && keys) e = hipMemcpy(keys, kt, nb, hipMemcpyDeviceToHost);
-        if (s == MC_OK && e == hipSuccess && values) e = hipMemcpy(values, vtmp, nb, hipMemcpyDeviceToHost);
-    }
-    (void)hipFree(stv);
-    if (kt) (void)hipFree(kt);
-    if (vtmp) (void)hipFree(vtmp);
+    device_tmp stv;
+    hipError_t e = stv.alloc(sizeof st);
+    if (e == hipSuccess) e = hipMemcpyAsync(stv.ptr, &st, sizeof st, hipMemcpyHostToDevice, b->p.stream);
     if (e != hipSuccess) return hip_fail(e, "mc_ragged_export_kv");
-    return s;
+    return export_kv(b, "mc_ragged_export_kv", row, layer, static_cast<const step_state*>(stv.ptr), n, n, nullptr, keys, values);
 }
 
 } // extern "C"

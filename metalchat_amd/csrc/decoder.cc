@@ -103,14 +103,6 @@ struct blaslt_plan {
     bool usable = false, tried = false;
 };
 
-constexpr int PB = 64; // cache slots per attention-scores workgroup (decode_kernels.hip)
-
-struct step_state_h {
-    int32_t token, pos, kv_len, write_slot, ring_base, step_index, rope_row, rolled, rope_start;
-    uint32_t epoch, err; // steps since creation (the tag of in-launch hand-offs); a hand-off that gave up (mc_attn_fused_T)
-    int32_t pad[1];
-};
-
 struct linear_w {
     int fmt = MC_WFMT_T;
     int out = 0, in = 0, group = 0; // group 0 = one scale per row
@@ -137,34 +129,17 @@ struct linear_w {
     float lora_scale = 0.0f;
 };
 
-// mirrors mc::gemv::postnorm_args (kernels/gemv.h)
-struct postnorm_args_h {
-    const void* post_w;
-    const void* res;
-    void* h_out;
-};
-
-// mirrors sampler_params (kernels/sampler_kernels.hip)
-struct sampler_params_h {
-    uint32_t k, ncand, cap;
-    float inv_temp, top_p;
-    uint32_t nlists, kpad;
-};
-
-// mirrors mc::gemv::qkv_epilogue (kernels/gemv.h)
-struct qkv_epilogue_h {
-    void* q_out;
-    void* kc;
-    void* vt;
-    const float* fcos;
-    const float* fsin;
-    const int32_t* state;
-    uint32_t H, KV, hd, max_seq;
+// EPI_STORE_PICK's two descriptors (kernels/gemv.h) and the words the first points at, as they lie in mc_decoder::pick_desc
+struct pick_block {
+    pick_epilogue atomic;   // key + ticket: the last workgroup of the head's launch finishes the pick
+    pick_epilogue per_wg;   // one key per workgroup (pick_keys), no ticket: folded by mc_argmax_keys behind the launch
+    unsigned long long key; // 0 between launches
+    uint32_t ticket;
 };
 
 struct layer_w {
     linear_w qkv, wo, w13, w2;
-    void* qkv_epi = nullptr; // device copy of qkv_epilogue_h
+    void* qkv_epi = nullptr; // device qkv_epilogue
     void* pn_attn = nullptr; // device postnorm_args: attention post-norm, residual = layer input, h_out = hidden_b
     void* pn_ffn = nullptr;  // device postnorm_args: ffn post-norm, residual = hidden_b, h_out = hidden
     void* attention_norm = nullptr;
@@ -206,25 +181,6 @@ bit_width(uint32_t v)
         v >>= 1;
     }
     return n;
-}
-
-// kernel-argument packer: natural alignment of each argument, like the compiler's kernarg layout
-struct arg_pack {
-    std::vector<char> buf;
-    template <typename T> void
-    push(const T& v)
-    {
-        size_t off = (buf.size() + alignof(T) - 1) / alignof(T) * alignof(T);
-        buf.resize(off + sizeof(T));
-        memcpy(buf.data() + off, &v, sizeof(T));
-    }
-};
-template <typename... A> arg_pack
-pack(const A&... a)
-{
-    arg_pack p;
-    (p.push(a), ...);
-    return p;
 }
 
 } // namespace
@@ -294,7 +250,7 @@ struct mc_decoder {
     bool lazy_pick = false;    // inside mc_decoder_generate: the pick of a token is folded by the NEXT token's embedding launch
     bool lazy_pick_on = true;  // MC_LAZY_PICK
     bool graph_lazy = false;   // the captured token was recorded with lazy_pick
-    std::unordered_map<const void*, postnorm_args_h> pn_host; // the same descriptors on the host (the linear-order kernels take the three pointers as arguments)
+    std::unordered_map<const void*, postnorm_args> pn_host; // the same descriptors on the host (the linear-order kernels take the three pointers as arguments)
     void* qkv = nullptr;        // T[(H+2KV)*hd]
     void* q_rot = nullptr;      // T[H*hd]
     void* attn_out = nullptr;   // T[H*hd]
@@ -328,7 +284,7 @@ struct mc_decoder {
     // that need no co-residency (attn_fused_on = false: scores, P.V and the GEMVs as launches of their own), drops the captured
     // graph and -- where the step can be repeated exactly -- runs it again (mc_decoder_step; mc_decoder_generate while the
     // ring has not turned inside the call).  handoff_fallbacks counts those events (mc_decoder_handoff_fallbacks).
-    step_state_h* state_bak = nullptr; // the step state in front of the call that may have to be repeated
+    step_state* state_bak = nullptr; // the step state in front of the call that may have to be repeated
     uint32_t* err_host = nullptr;      // pinned: state.err of a step nobody waited for (a non-last stage, next_token == NULL)
     hipEvent_t err_evt = nullptr;
     bool err_pending = false;
@@ -359,7 +315,7 @@ struct mc_decoder {
     unsigned attn_fused_max_wgs_per_cu = 2;
     bool attn_t2_on = true; // MC_ATTN_T2
     void* taps = nullptr;       // T[(n_own+1)*dim]
-    step_state_h* state = nullptr;
+    step_state* state = nullptr;
     int32_t* tokens_dev = nullptr;
     // the greedy pick inside the output head's launch (gemv.h EPI_STORE_PICK): two descriptors {key*, ticket*, state*, tokens_out*}
     // -- [0, 32) with the atomic key at [64, 72) and the ticket at [72, 76), both zero between launches; [32, 64) with pick_keys
@@ -967,7 +923,7 @@ struct mc_decoder {
 
     // a hand-off inside a launch that gave up (bounded waits, decode_kernels.hip): reported once, then cleared
     mc_status
-    check_handoffs(const step_state_h& st)
+    check_handoffs(const step_state& st)
     {
         if (!st.err) return MC_OK;
         return report_handoff(st.err);
@@ -1127,7 +1083,7 @@ struct mc_decoder {
         if (pro == 2 && (lin || lins)) {
             const auto it = pn_host.find(res);
             if (it == pn_host.end()) return fail(MC_ERR_RUNTIME, "gemv: unknown post-norm descriptor");
-            const postnorm_args_h& h = it->second;
+            const postnorm_args& h = it->second;
             return launch(name, wgs, 1, 1, block, lds,
                           pack(L.w, L.scales, x, y, (const void*)h.res, norm_w, (uint32_t)L.out, (uint32_t)L.in, (uint32_t)L.group,
                                cfg.norm_eps, mu, (const void*)h.post_w, (const void*)h.h_out, (uint32_t)0, 0.0f));
@@ -1246,7 +1202,7 @@ struct mc_decoder {
                 // gemma3, ONE launch from the row handed to the block to Wo's output: (the previous block's ffn post-norm + residual,)
                 // attention_norm, wq|wk|wv, q_norm / k_norm, rope, cache write, scores, softmax, P.V, wo (transformer.h:126-133,
                 // attention.h:170-205); the attention post-norm and its residual are the w1|w3 GEMV's prologue (or mc_rmsnorm_row below)
-                postnorm_args_h h{};
+                postnorm_args h{};
                 if (pending_pn) {
                     const auto it = pn_host.find(pending_pn);
                     if (it == pn_host.end()) return fail(MC_ERR_RUNTIME, "attention block: unknown post-norm descriptor");
@@ -1495,7 +1451,7 @@ struct mc_decoder {
         const bool pick = head_pick();
         mc_status s = pending_pn ? gemv(output, 2, 0, proj, logits, pending_pn, final_norm, mu)
                                  : gemv(output, 1, pick ? 5 : 0, hidden, logits,
-                                        pick ? (const void*)(pick_desc + (head_pick_mode == 2 ? 32 : 0)) : nullptr, final_norm, mu);
+                                        pick ? (const void*)(pick_desc + (head_pick_mode == 2 ? offsetof(pick_block, per_wg) : offsetof(pick_block, atomic))) : nullptr, final_norm, mu);
         pending_pn = nullptr;
         if (s != MC_OK) return s;
         if (pick && head_pick_mode == 2)
@@ -1505,26 +1461,14 @@ struct mc_decoder {
             return launch("mc_argmax_" + tname, 1, 1, 1, 1024, 0,
                           pack(logits, (uint32_t)cfg.vocab, state, tokens_dev));
         // make_default_sampler: per-chunk candidates, then one workgroup finishes the chain
-        uint32_t kpad = 1;
-        while (kpad < (uint32_t)top_k) kpad *= 2;
-        const uint32_t k = (uint32_t)std::min(top_k, cfg.vocab);
-        // chunks of 512 logits (1024 / 2048 where that would be more than 1024 lists), each sorted by ONE wave in registers; the
-        // second launch finds the k best of the sorted lists without sorting them all (sampler_kernels.hip)
-        const uint32_t chunk = sampler_chunk((uint32_t)cfg.vocab, kpad), lists = ((uint32_t)cfg.vocab + chunk - 1) / chunk;
-        if (lists > 1024u) return fail(MC_ERR_RUNTIME, "sampler: the fused sampler handles rows of up to 2048 * 1024 logits");
-        s = launch("mc_topk_candidates_" + tname, lists, 1, 1, 64, 0, pack(logits, (uint32_t)cfg.vocab, kpad, cand, chunk));
+        sampler_params p;
+        uint32_t chunk;
+        if ((s = sampler_plan(top_k, cfg.vocab, inv_temp_T, top_p_T, &p, &chunk)) != MC_OK) return s;
+        s = launch("mc_topk_candidates_" + tname, p.nlists, 1, 1, 64, 0, pack(logits, (uint32_t)cfg.vocab, p.kpad, cand, chunk));
         if (s != MC_OK) return s;
-        const sampler_params_h p{k, lists * kpad, 4096u, inv_temp_T, top_p_T, lists, kpad};
         return launch("mc_sample_" + tname, 1, 1, 1, 128, p.cap * 8,
                       pack(cand, p, seeds, (uint32_t)n_seed_pairs, state, tokens_dev,
                            want_taps ? sampler_taps : (float*)nullptr));
-    }
-    static uint32_t
-    sampler_chunk(uint32_t vocab, uint32_t kpad)
-    {
-        uint32_t chunk = std::max(512u, kpad);
-        while (chunk < 2048u && (vocab + chunk - 1) / chunk > 1024u) chunk *= 2;
-        return chunk;
     }
 
     // ---------------------------------------------------------------- prompt pass
@@ -2103,7 +2047,7 @@ struct mc_decoder {
                     const std::string sfx = std::string(two ? "2" : "") + "_bfloat_hd" + std::to_string(hd);
                     const unsigned gh = two ? H / 2 : H;
                     for (int g = 0; g < pk->ngroups; g++) {
-                        const uint32_t e0 = (uint32_t)pk->groups[3 * g], ne = (uint32_t)pk->groups[3 * g + 1];
+                        const uint32_t e0 = (uint32_t)pk->groups[g].first, ne = (uint32_t)pk->groups[g].count;
                         mc_status ls = launch("mc_px_sums" + sfx, gh, ne, 1, 256, 0,
                                               pack(pf_q, pk->segs, pk->ranges, e0, (const void*)pk_kc, pk->cache_stride, pk->sums, (uint32_t)H,
                                                    (uint32_t)(H / KV), (uint32_t)cfg.max_seq_len, scale_T, (const void*)pf_etab));
@@ -2113,7 +2057,7 @@ struct mc_decoder {
                                          (const void*)pk->sums, pk->part, pf_att, (uint32_t)H, (uint32_t)(H / KV), (uint32_t)cfg.max_seq_len, scale_T,
                                          (const void*)pf_etab));
                         if (ls != MC_OK) return ls;
-                        if (!pk->groups[3 * g + 2]) continue; // no tile of the group is split: mc_px_pv wrote the outputs
+                        if (!pk->groups[g].split) continue; // no tile of the group is split: mc_px_pv wrote the outputs
                         ls = launch("mc_px_reduce_bfloat_hd" + std::to_string(hd), H, ne, 1, 256, 0,
                                     pack(pk->segs, pk->ranges, e0, (const void*)pk->part, pf_att, (uint32_t)H));
                         if (ls != MC_OK) return ls;
@@ -2447,8 +2391,8 @@ mc_decoder_create(mc_device* dev, mc_library* lib, mc_queue* q, const mc_decoder
         A(d->attn_qkv_g, (size_t)(H + 2 * std::max(KV, 8)) * hd / 2 * 8 * 2); // (virtual kv heads: a K and a V row per virtual head)
     }
     A(d->taps, (size_t)(d->n_own + 1) * dim * tb);
-    A(d->state, sizeof(step_state_h));
-    A(d->state_bak, sizeof(step_state_h));
+    A(d->state, sizeof(step_state));
+    A(d->state_bak, sizeof(step_state));
     if (hipHostMalloc((void**)&d->err_host, 64, hipHostMallocDefault) == hipSuccess) {
         *d->err_host = 0;
         if (hipEventCreateWithFlags(&d->err_evt, hipEventDisableTiming) != hipSuccess) {
@@ -2459,12 +2403,14 @@ mc_decoder_create(mc_device* dev, mc_library* lib, mc_queue* q, const mc_decoder
     (void)hipGetLastError();
     d->tokens_cap = 1 << 16;
     A(d->tokens_dev, (size_t)d->tokens_cap * 4);
-    A(d->pick_desc, 128);
+    A(d->pick_desc, sizeof(pick_block));
     A(d->pick_keys, (size_t)mc_decoder::pick_slots * 8);
     {
-        const void* desc[8] = {d->pick_desc + 64, d->pick_desc + 72, d->state, d->tokens_dev, // [0, 32): atomic key + ticket
-                               d->pick_keys, nullptr, d->state, d->tokens_dev};                 // [32, 64): one key per workgroup
-        MC_HIP(hipMemcpy(d->pick_desc, desc, sizeof desc, hipMemcpyHostToDevice));
+        pick_block blk{};
+        blk.atomic = {(unsigned long long*)(d->pick_desc + offsetof(pick_block, key)), (uint32_t*)(d->pick_desc + offsetof(pick_block, ticket)),
+                     d->state, d->tokens_dev};
+        blk.per_wg = {(unsigned long long*)d->pick_keys, nullptr, d->state, d->tokens_dev};
+        MC_HIP(hipMemcpy(d->pick_desc, &blk, sizeof blk, hipMemcpyHostToDevice));
     }
     if (const char* e = getenv("MC_HEAD_PICK")) d->head_pick_mode = std::max(0, std::min(2, atoi(e)));
     d->head_pick_on = d->head_pick_mode != 0;
@@ -2489,14 +2435,13 @@ mc_decoder_create(mc_device* dev, mc_library* lib, mc_queue* q, const mc_decoder
                         ((gi + 1) % c.sliding_stride) != 0 && d->rope_cos[1])
                            ? 1
                            : 0;
-        qkv_epilogue_h e{d->q_rot, L.kc, L.vt, d->rope_cos[L.rope_table], d->rope_sin[L.rope_table],
-                         reinterpret_cast<const int32_t*>(d->state), (uint32_t)H, (uint32_t)KV,
-                         (uint32_t)hd, (uint32_t)c.max_seq_len};
+        qkv_epilogue e{d->q_rot, L.kc, L.vt, d->rope_cos[L.rope_table], d->rope_sin[L.rope_table], d->state, (uint32_t)H, (uint32_t)KV,
+                       (uint32_t)hd, (uint32_t)c.max_seq_len};
         A(L.qkv_epi, sizeof e);
         MC_HIP(hipMemcpyAsync(L.qkv_epi, &e, sizeof e, hipMemcpyHostToDevice, d->stream));
         MC_HIP(hipStreamSynchronize(d->stream)); // `e` is a stack temporary
-        A(L.pn_attn, sizeof(postnorm_args_h));
-        A(L.pn_ffn, sizeof(postnorm_args_h));
+        A(L.pn_attn, sizeof(postnorm_args));
+        A(L.pn_ffn, sizeof(postnorm_args));
     }
 #undef A
     MC_HIP(hipStreamSynchronize(d->stream));
@@ -2536,7 +2481,7 @@ mc_decoder_set_sampler(mc_decoder* d, int32_t kind, int32_t top_k, float tempera
         if (!d->last_stage) return fail(MC_ERR_INVALID_ARGUMENT, "decoder: only the last stage samples");
         MC_HIP(hipSetDevice(d->dev->ordinal));
         d->drop_graph();
-        const uint32_t chunks = ((uint32_t)d->cfg.vocab + 511u) / 512u; // (the most lists any top_k makes: sampler_chunk)
+        const uint32_t chunks = ((uint32_t)d->cfg.vocab + 511u) / 512u; // (the most lists any top_k makes: sampler_plan)
         if (!d->cand) {
             mc_status s = d->alloc((void**)&d->cand, (size_t)chunks * 128 * 8);
             if (s != MC_OK) return s;
@@ -2851,8 +2796,8 @@ check_ready(mc_decoder* d)
     if (d->cfg.family == MC_FAMILY_GEMMA3 && !d->pn_ready) {
         for (auto& L : d->layers) {
             if (!L.attention_post_norm || !L.ffn_post_norm) return fail(MC_ERR_RUNTIME, "decoder: post-norm weights are not loaded");
-            const postnorm_args_h a{L.attention_post_norm, d->hidden, d->hidden_b};
-            const postnorm_args_h f{L.ffn_post_norm, d->hidden_b, d->hidden};
+            const postnorm_args a{L.attention_post_norm, d->hidden, d->hidden_b};
+            const postnorm_args f{L.ffn_post_norm, d->hidden_b, d->hidden};
             MC_HIP(hipMemcpy(L.pn_attn, &a, sizeof a, hipMemcpyHostToDevice));
             MC_HIP(hipMemcpy(L.pn_ffn, &f, sizeof f, hipMemcpyHostToDevice));
             d->pn_host[L.pn_attn] = a;
@@ -2883,7 +2828,7 @@ mc_decoder_step(mc_decoder* d, int32_t token, int32_t start_pos, const void* hid
     for (int attempt = 0;; attempt++) {
         const bool handoffs = d->attn_fused() || d->attn_fused_t2();
         // (a step whose hand-offs give up is repeated on the launches that need no co-residency: the state in front of it)
-        if (handoffs) MC_HIP(hipMemcpyAsync(d->state_bak, d->state, sizeof(step_state_h), hipMemcpyDeviceToDevice, d->stream));
+        if (handoffs) MC_HIP(hipMemcpyAsync(d->state_bak, d->state, sizeof(step_state), hipMemcpyDeviceToDevice, d->stream));
         s = d->ensure_rope(start_pos);
         if (s != MC_OK) return s;
         s = d->launch("mc_step_set", 1, 1, 1, 64, 0,
@@ -2902,7 +2847,7 @@ mc_decoder_step(mc_decoder* d, int32_t token, int32_t start_pos, const void* hid
             d->note_clean_tokens(1);
             return MC_OK;
         }
-        step_state_h st;
+        step_state st;
         MC_HIP(hipMemcpyAsync(&st, d->state, sizeof st, hipMemcpyDeviceToHost, d->stream));
         MC_HIP(hipStreamSynchronize(d->stream));
         *next_token = st.token;
@@ -2913,7 +2858,7 @@ mc_decoder_step(mc_decoder* d, int32_t token, int32_t start_pos, const void* hid
         if (attempt > 0 || !handoffs) return d->check_handoffs(st);
         // the step again, from the state in front of it: its cache row goes to the same slot, every other row is untouched
         d->handoff_failed();
-        MC_HIP(hipMemcpyAsync(d->state, d->state_bak, sizeof(step_state_h), hipMemcpyDeviceToDevice, d->stream));
+        MC_HIP(hipMemcpyAsync(d->state, d->state_bak, sizeof(step_state), hipMemcpyDeviceToDevice, d->stream));
     }
 }
 
@@ -3018,7 +2963,7 @@ mc_decoder_generate(mc_decoder* d, int32_t first_token, int32_t start_pos, int32
     if (s != MC_OK) return s;
     d->query_occupancy();
     const bool handoffs = d->attn_fused() || d->attn_fused_t2();
-    if (handoffs) MC_HIP(hipMemcpyAsync(d->state_bak, d->state, sizeof(step_state_h), hipMemcpyDeviceToDevice, d->stream));
+    if (handoffs) MC_HIP(hipMemcpyAsync(d->state_bak, d->state, sizeof(step_state), hipMemcpyDeviceToDevice, d->stream));
     s = d->ensure_rope(start_pos);
     if (s != MC_OK) return s;
     s = d->launch("mc_step_set", 1, 1, 1, 64, 0,
@@ -3071,7 +3016,7 @@ mc_decoder_generate(mc_decoder* d, int32_t first_token, int32_t start_pos, int32
     if (tokens_out) {
         MC_HIP(hipMemcpyAsync(tokens_out, d->tokens_dev, (size_t)n * 4, hipMemcpyDeviceToHost, d->stream));
     }
-    step_state_h st;
+    step_state st;
     MC_HIP(hipMemcpyAsync(&st, d->state, sizeof st, hipMemcpyDeviceToHost, d->stream));
     MC_HIP(hipStreamSynchronize(d->stream));
     if (!st.err) {
@@ -3083,7 +3028,7 @@ mc_decoder_generate(mc_decoder* d, int32_t first_token, int32_t start_pos, int32
     // co-residency.  Past max_seq_len the failed chain has overwritten rows its own first steps attend to: reported instead.
     if (handoffs && start_pos + n <= d->cfg.max_seq_len) {
         d->handoff_failed();
-        MC_HIP(hipMemcpyAsync(d->state, d->state_bak, sizeof(step_state_h), hipMemcpyDeviceToDevice, d->stream));
+        MC_HIP(hipMemcpyAsync(d->state, d->state_bak, sizeof(step_state), hipMemcpyDeviceToDevice, d->stream));
         return mc_decoder_generate(d, first_token, start_pos, n, tokens_out);
     }
     return d->check_handoffs(st);
@@ -3184,23 +3129,21 @@ mc_decoder_export_kv(mc_decoder* d, int32_t layer, void* keys, void* values, int
     MC_HIP(hipSetDevice(d->dev->ordinal));
     const mc_decoder_config& c = d->cfg;
     const size_t bytes = (size_t)c.max_seq_len * c.n_kv_heads * c.head_dim * d->tb;
-    void *kt = nullptr, *vtmp = nullptr;
-    MC_HIP(hipMalloc(&kt, bytes));
-    MC_HIP(hipMalloc(&vtmp, bytes));
+    device_tmp kt, vtmp;
+    MC_HIP(kt.alloc(bytes));
+    MC_HIP(vtmp.alloc(bytes));
     s = d->launch("mc_kv_export_" + d->tname, 512, 1, 1, 256, 0,
-                  pack(L->kc, L->vt, kt, vtmp, d->state, (uint32_t)c.n_kv_heads, (uint32_t)c.head_dim,
+                  pack(L->kc, L->vt, kt.ptr, vtmp.ptr, d->state, (uint32_t)c.n_kv_heads, (uint32_t)c.head_dim,
                        (uint32_t)c.max_seq_len, (uint32_t)d->pre_len));
-    step_state_h st{};
+    step_state st{};
     hipError_t e = hipStreamSynchronize(d->stream);
     if (s == MC_OK && e == hipSuccess) {
         e = hipMemcpy(&st, d->state, sizeof st, hipMemcpyDeviceToHost);
         const size_t nb = (size_t)st.kv_len * c.n_kv_heads * c.head_dim * d->tb;
-        if (e == hipSuccess) e = hipMemcpy(keys, kt, nb, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(values, vtmp, nb, hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(keys, kt.ptr, nb, hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(values, vtmp.ptr, nb, hipMemcpyDeviceToHost);
         if (n_valid) *n_valid = st.kv_len;
     }
-    (void)hipFree(kt);
-    (void)hipFree(vtmp);
     if (s != MC_OK) return s;
     if (e != hipSuccess) return hip_fail(e, "mc_decoder_export_kv");
     return st.err ? d->report_handoff(st.err) : MC_OK;
@@ -3218,14 +3161,14 @@ mc_decoder_import_kv(mc_decoder* d, int32_t layer, const void* keys, const void*
         return fail(MC_ERR_INVALID_ARGUMENT, "mc_decoder_import_kv: n_valid must lie in [1, max_seq_len]");
     MC_HIP(hipSetDevice(d->dev->ordinal));
     const size_t nb = (size_t)n_valid * c.n_kv_heads * c.head_dim * d->tb;
-    void *kt = nullptr, *vtmp = nullptr;
-    MC_HIP(hipMalloc(&kt, nb));
-    hipError_t e = hipMalloc(&vtmp, nb);
-    if (e == hipSuccess) e = hipMemcpy(kt, keys, nb, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(vtmp, values, nb, hipMemcpyHostToDevice);
+    device_tmp kt, vtmp;
+    MC_HIP(kt.alloc(nb));
+    hipError_t e = vtmp.alloc(nb);
+    if (e == hipSuccess) e = hipMemcpy(kt.ptr, keys, nb, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(vtmp.ptr, values, nb, hipMemcpyHostToDevice);
     if (e == hipSuccess) {
         s = d->launch("mc_kv_import_" + d->tname, 512, 1, 1, 256, 0,
-                      pack(L->kc, L->vt, (const void*)kt, (const void*)vtmp, (uint32_t)n_valid, (uint32_t)c.n_kv_heads,
+                      pack(L->kc, L->vt, (const void*)kt.ptr, (const void*)vtmp.ptr, (uint32_t)n_valid, (uint32_t)c.n_kv_heads,
                            (uint32_t)c.head_dim, (uint32_t)c.max_seq_len));
         // the state of a decoder that has just decoded position n_valid - 1 on an unturned ring
         if (s == MC_OK)
@@ -3234,8 +3177,6 @@ mc_decoder_import_kv(mc_decoder* d, int32_t layer, const void* keys, const void*
                                (int32_t)d->rope_start, (int32_t)1));
         e = hipStreamSynchronize(d->stream);
     }
-    (void)hipFree(kt);
-    (void)hipFree(vtmp);
     if (e != hipSuccess) return hip_fail(e, "mc_decoder_import_kv");
     if (s != MC_OK) return s;
     d->ring_turned = false;
@@ -3384,7 +3325,7 @@ mc_decoder_time_gemv(mc_decoder* d, const char* which, int32_t repeats, float* t
             // the variant the token really launches: with the greedy pick inside (one key per workgroup into pick_keys;
             // the step state is not touched) when run_head() would take it
             const bool pick = d->head_pick();
-            r = d->gemv(d->output, 1, pick ? 5 : 0, d->hidden, d->logits, pick ? (const void*)(d->pick_desc + 32) : nullptr, d->final_norm, mu);
+            r = d->gemv(d->output, 1, pick ? 5 : 0, d->hidden, d->logits, pick ? (const void*)(d->pick_desc + offsetof(pick_block, per_wg)) : nullptr, d->final_norm, mu);
             if (r != MC_OK) return r;
             if (count) { bytes += linear_bytes(d->output); launches++; }
         }
@@ -3726,7 +3667,7 @@ mc_pipeline_generate(mc_pipeline* p, int32_t first_token, int32_t start_pos, int
         if (tokens_out) MC_HIP(hipMemcpyAsync(tokens_out, last->tokens_dev, (size_t)n * 4, hipMemcpyDeviceToHost, last->stream));
         for (mc_decoder* d : p->stages) {
             MC_HIP(hipSetDevice(d->dev->ordinal));
-            step_state_h st;
+            step_state st;
             MC_HIP(hipMemcpyAsync(&st, d->state, sizeof st, hipMemcpyDeviceToHost, d->stream));
             MC_HIP(hipStreamSynchronize(d->stream));
             s = d->check_handoffs(st);
@@ -3759,7 +3700,7 @@ mc_pipeline_generate(mc_pipeline* p, int32_t first_token, int32_t start_pos, int
     if (W > 1 && r == 0) MC_NCCL(api.Recv(d->tokens_dev, (size_t)n, ncclInt32, W - 1, p->comm, d->stream), "ncclRecv(tokens)");
     if (tokens_out && (r == 0 || r == W - 1))
         MC_HIP(hipMemcpyAsync(tokens_out, d->tokens_dev, (size_t)n * 4, hipMemcpyDeviceToHost, d->stream));
-    step_state_h st;
+    step_state st;
     MC_HIP(hipMemcpyAsync(&st, d->state, sizeof st, hipMemcpyDeviceToHost, d->stream));
     MC_HIP(hipStreamSynchronize(d->stream));
     s = d->check_handoffs(st);
@@ -3948,7 +3889,7 @@ mc_status
 decoder_cache_state(mc_decoder* d, int* kv_len, bool* rolled)
 {
     MC_HIP(hipSetDevice(d->dev->ordinal));
-    step_state_h st{};
+    step_state st{};
     MC_HIP(hipMemcpyAsync(&st, d->state, sizeof st, hipMemcpyDeviceToHost, d->stream));
     MC_HIP(hipStreamSynchronize(d->stream));
     *kv_len = st.kv_len;
@@ -3957,12 +3898,23 @@ decoder_cache_state(mc_decoder* d, int* kv_len, bool* rolled)
 }
 
 mc_status
-decoder_launch(mc_decoder* d, const std::string& name, unsigned gx, unsigned gy, unsigned gz, unsigned bx, unsigned lds,
-               const std::vector<char>& args)
+decoder_launch(mc_decoder* d, const std::string& name, unsigned gx, unsigned gy, unsigned gz, unsigned bx, unsigned lds, arg_pack&& args)
 {
-    arg_pack a;
-    a.buf = args;
-    return d->launch(name, gx, gy, gz, bx, lds, std::move(a));
+    return d->launch(name, gx, gy, gz, bx, lds, std::move(args));
+}
+
+mc_status
+sampler_plan(int top_k, int vocab, float inv_temp_T, float top_p_T, sampler_params* p, uint32_t* chunk)
+{
+    uint32_t kpad = 1;
+    while (kpad < (uint32_t)top_k) kpad *= 2;
+    const uint32_t k = (uint32_t)std::min(top_k, vocab);
+    *chunk = std::max(512u, kpad);
+    while (*chunk < 2048u && ((uint32_t)vocab + *chunk - 1) / *chunk > MC_SAMPLE_LISTS_MAX) *chunk *= 2;
+    const uint32_t lists = ((uint32_t)vocab + *chunk - 1) / *chunk;
+    if (lists > MC_SAMPLE_LISTS_MAX) return fail(MC_ERR_RUNTIME, "sampler: the fused sampler handles rows of up to 2048 * 1024 logits");
+    *p = sampler_params{k, lists * kpad, SAMPLE_CAP, inv_temp_T, top_p_T, lists, kpad};
+    return MC_OK;
 }
 
 mc_status

@@ -4,8 +4,11 @@
 #pragma once
 
 #include "backend_impl.h"
+#include "kernels/abi.h"
 
 namespace mcimpl {
+
+using namespace mc::abi;
 
 // one fused matrix as decoder.cc holds it: rows [out][in] in MC_WFMT_* format, bfloat scales in row quads
 struct batch_linear {
@@ -47,15 +50,24 @@ decoder_sampler decoder_sampler_of(const mc_decoder* d);
 // the decoder's step state after everything enqueued so far (synchronises): valid cache rows and whether the ring has turned
 mc_status decoder_cache_state(mc_decoder* d, int* kv_len, bool* rolled);
 // a launch on the decoder's stream through its launch path (named ranges, mc_decoder_launch_log); args: the packed kernel arguments
-mc_status decoder_launch(mc_decoder* d, const std::string& name, unsigned gx, unsigned gy, unsigned gz, unsigned bx, unsigned lds,
-                         const std::vector<char>& args);
+mc_status decoder_launch(mc_decoder* d, const std::string& name, unsigned gx, unsigned gy, unsigned gz, unsigned bx, unsigned lds, arg_pack&& args);
+// make_default_sampler's two launches over a row of `vocab` logits (sampler_kernels.hip): the candidate lists come from chunks of
+// 512 logits (1024 / 2048 where that would be more than MC_SAMPLE_LISTS_MAX lists), each sorted by ONE wave in registers, kpad =
+// top_k rounded up to a power of two keys per list; the second launch finds the k best of the sorted lists.  Fills the second
+// launch's parameters and the chunk of the first (its grid is p->nlists); fails where the row is too long for the second.
+mc_status sampler_plan(int top_k, int vocab, float inv_temp_T, float top_p_T, sampler_params* p, uint32_t* chunk);
 
 // The packed prompt pass (mc_rows_prefill and mc_extend_rows, kernels/packed_kernels.hip): the chunks of several sequences as one prompt pass of
 // M = sum of their lengths rows.  The tables are on the device already (uploaded on the decoder's stream).
+// a launch group of mc_extend_rows: whole tiles, at most as many ranges as the scratch has slots
+struct px_group {
+    int first = 0, count = 0; // its ranges: [first, first + count) of the range table
+    bool split = false;       // a tile of the group has several ranges (their partial outputs want mc_px_reduce)
+};
 struct packed_prefill {
-    const int32_t* segs = nullptr;  // [nseg][4]: batch row, position, offset of its first packed row, length (offsets ascending)
+    const pp_seg* segs = nullptr;   // [nseg]: the rows in the call, offsets ascending
     int nseg = 0;
-    const int32_t* tiles = nullptr; // [ntiles][2]: segment, first row of a 16-row attention tile inside it
+    const pp_tile* tiles = nullptr; // [ntiles]: the 16-row attention tiles of every segment
     int ntiles = 0;
     void* kc = nullptr;             // caches of layer l, batch row r at kc / vt + (l * B + r) * cache_stride elements (batch.cc kc_of / vt_of)
     void* vt = nullptr;
@@ -67,9 +79,9 @@ struct packed_prefill {
     // mc_extend_rows (kernels/extend_kernels.hip): chunk rows see their row's whole context.  The attention then takes the
     // mc_px_* launches over the range table instead of mc_pp_attn* over the tile table.
     bool extend = false;
-    const int32_t* ranges = nullptr; // device, [.][8]: px_range -- the key ranges of every tile, a tile's ranges adjacent
-    const int32_t* groups = nullptr; // HOST, [ngroups][3]: first range, range count, whether a tile has several ranges -- a launch
-    int ngroups = 0;                 //  group is whole tiles, at most as many ranges as the scratch has slots
+    const px_range* ranges = nullptr; // device: the key ranges of every tile, a tile's ranges adjacent
+    const px_group* groups = nullptr; // HOST, [ngroups]: the launch groups
+    int ngroups = 0;
     float* sums = nullptr;           // scratch [slots][n_heads][16]: the exp row sums of a range
     float* part = nullptr;           // scratch [slots][n_heads][16][head_dim]: the partial outputs of a range
 };

@@ -1,0 +1,109 @@
+// The host/kernel ABI: every struct and constant that both the host library (../*.cc) and the kernels (*.hip) must agree on, each
+// defined ONCE.  Kernels are looked up by name and their arguments are packed by hand (backend_impl.h pack()), so this header is
+// the only thing the compiler can check that boundary with.  Plain C++17 and HIP alike: PODs and constants over <stdint.h>, no
+// device code and no HIP types.  A layout that any code relies on by position is pinned by a static_assert below.
+#pragma once
+
+#include <stddef.h>
+#include <stdint.h>
+
+namespace mc {
+namespace abi {
+
+// ---- constants ----
+constexpr int PB = 64;                         // cache slots per attention-scores workgroup (decode_kernels.hip)
+constexpr int BATCH_MAX = 8;                   // rows of an mc_batch (batch_kernels.hip: the B columns of a 16-column MFMA tile)
+constexpr int BG_WAVES = 8;                    // mc_b_gemv_*: waves of a workgroup, each takes an equal slice of K
+constexpr unsigned BG_THREADS = 64 * BG_WAVES; // ... its block size
+constexpr unsigned BG_K_UNIT = 128 * BG_WAVES; // ... in_features per workgroup slice: a 128-weight chunk per wave
+constexpr int PP_TILE_ROWS = 16;               // chunk rows of one attention tile of the packed prompt pass (pp_tile, px_range)
+constexpr uint32_t SAMPLE_CAP = 4096;          // keys the sampler's dynamic LDS holds (sampler_params::cap)
+constexpr uint32_t MC_SAMPLE_LISTS_MAX = 1024; // sorted candidate lists the sampler's second launch takes
+
+// ---- the step state (handoff.h: the tag of in-launch hand-offs; decode_kernels.hip mc_step_set / mc_step_next) ----
+struct step_state {
+    int32_t token;      // input token of the current step
+    int32_t pos;        // start_pos of the current step
+    int32_t kv_len;     // valid cache slots after this step's write  = min(pos + 1, max_seq)
+    int32_t write_slot; // physical slot of this step's K/V row
+    int32_t ring_base;  // rotation of the post-sink ring
+    int32_t step_index; // index into tokens_out for chained generation
+    int32_t rope_row;   // pos - rope_table_start
+    int32_t rolled;     // number of rolls so far (debug)
+    int32_t rope_start; // first position of the rope table window (nn/embedding.h:190-198); moved by mc_step_rope
+    uint32_t epoch;     // counts the steps since the decoder was created (never reset): the tag of in-launch hand-offs
+    uint32_t err;       // set by a kernel whose in-launch hand-off gave up (mc_attn_fused_T); 0 = none
+    int32_t pad[1];
+};
+static_assert(sizeof(step_state) == 48 && alignof(step_state) == 4, "step_state: 12 words (arrays of it: one per batch row)");
+static_assert(offsetof(step_state, token) == 0 && offsetof(step_state, pos) == 4 && offsetof(step_state, kv_len) == 8 &&
+                  offsetof(step_state, write_slot) == 12 && offsetof(step_state, ring_base) == 16 &&
+                  offsetof(step_state, step_index) == 20 && offsetof(step_state, rope_row) == 24 && offsetof(step_state, rolled) == 28 &&
+                  offsetof(step_state, rope_start) == 32 && offsetof(step_state, epoch) == 36 && offsetof(step_state, err) == 40,
+              "step_state: tests and traces read its words by index");
+
+// ---- the default sampler (sampler_kernels.hip), passed BY VALUE: its size and alignment place the arguments behind it ----
+struct sampler_params {
+    uint32_t k;          // top-k (<= 128)
+    uint32_t ncand;      // candidate keys written by launch 1 = nlists * kpad
+    uint32_t cap;        // keys the dynamic LDS holds (a power of two >= 2 * kpad)
+    float inv_temp;      // T(1 / T(temperature))
+    float top_p;         // T(p)
+    uint32_t nlists;     // sorted candidate lists (workgroups of launch 1), <= MC_SAMPLE_LISTS_MAX
+    uint32_t kpad;       // keys per list
+};
+static_assert(sizeof(sampler_params) == 28 && alignof(sampler_params) == 4, "sampler_params is a by-value kernel argument");
+
+// ---- the descriptors a decode GEMV finds behind its `res` argument (gemv.h) ----
+// PRO_POSTNORM
+struct postnorm_args {
+    const void* post_w; // T[in]
+    const void* res;    // T[in]
+    void* h_out;        // T[in]
+};
+static_assert(sizeof(postnorm_args) == 24, "postnorm_args: three pointers");
+// EPI_STORE_PICK
+struct pick_epilogue {
+    unsigned long long* key; // 0 between launches
+    uint32_t* ticket;        // 0 between launches; NULL: `key` has one slot per workgroup and a one-workgroup launch folds them
+    step_state* state;       // the pick becomes its token, and tokens_out[its step_index]
+    int32_t* tokens_out;     // may be null
+};
+static_assert(sizeof(pick_epilogue) == 32 && offsetof(pick_epilogue, key) == 0 && offsetof(pick_epilogue, ticket) == 8 &&
+                  offsetof(pick_epilogue, state) == 16 && offsetof(pick_epilogue, tokens_out) == 24,
+              "pick_epilogue: four pointers");
+// EPI_QKV_ROPE
+struct qkv_epilogue {
+    void* q_out;        // T[H*hd]       rotated queries, natural order
+    void* kc;           // T[KV][max_seq][hd]
+    void* vt;           // T[KV][hd][max_seq]
+    const float* fcos;  // [rows][hd/2]
+    const float* fsin;
+    const step_state* state; // its write_slot and rope_row
+    uint32_t H, KV, hd, max_seq;
+};
+static_assert(sizeof(qkv_epilogue) == 64 && offsetof(qkv_epilogue, state) == 40 && offsetof(qkv_epilogue, H) == 48,
+              "qkv_epilogue: six pointers and four words (read whole with scalar loads)");
+
+// ---- the tables of the packed prompt pass (packed_kernels.hip, extend_kernels.hip) ----
+// one per row in the call, in packed order: batch row, position of its chunk, offset of its first packed row, length
+struct pp_seg {
+    int32_t row, pos, off, len;
+};
+static_assert(sizeof(pp_seg) == 16, "pp_seg: four words");
+// one 16-row attention tile: its segment, and its first row inside the segment
+struct alignas(8) pp_tile {
+    int32_t seg, r0;
+};
+static_assert(sizeof(pp_tile) == 8 && alignof(pp_tile) == 8 && offsetof(pp_tile, r0) == 4, "pp_tile: one 8-byte load");
+// one per (tile, key range) of mc_extend_rows
+struct px_range {
+    int32_t seg, r0;    // segment, first chunk row of the 16-row tile inside it
+    int32_t k_lo, k_hi; // keys [k_lo, k_hi) of the row's cache; k_lo a multiple of 128
+    int32_t first, n;   // the tile's ranges: indices [first, first + n) of this table
+    int32_t pad0, pad1;
+};
+static_assert(sizeof(px_range) == 32 && offsetof(px_range, k_lo) == 8 && offsetof(px_range, first) == 16, "px_range: eight words");
+
+} // namespace abi
+} // namespace mc

@@ -26,7 +26,6 @@ using namespace mc;
 // v_cvt_pk_bf16_f32 -- T(T(q) T(s)).  Scales: bfloat row quads [out/4][in/group][4]; group % 128 == 0 or 0 (one per row).
 // ------------------------------------------------------------------------------------------
 enum { BEPI_STORE = 0, BEPI_RESID = 1, BEPI_SILU_MUL = 2 };
-constexpr int BG_WAVES = 8;
 
 typedef __bf16 bg_bf16x8 __attribute__((ext_vector_type(8)));
 typedef float bg_f32x4 __attribute__((ext_vector_type(4)));
@@ -256,7 +255,7 @@ mc_b_sample_bfloat(const uint64_t* cand, sampler_params p, const uint64_t* seeds
                    int32_t* tokens_out)
 {
     const uint32_t r = blockIdx.y;
-    sample_body<BF>(cand + (size_t)r * p.ncand, p, seeds, n_seed_pairs, reinterpret_cast<step_state_s*>(rows + r), tokens_out,
+    sample_body<BF>(cand + (size_t)r * p.ncand, p, seeds, n_seed_pairs, rows + r, tokens_out,
                     nullptr);
 }
 
@@ -373,6 +372,6 @@ mc_b_sample_rows_bfloat(const uint64_t* cand, sampler_params p, const uint64_t* 
 {
     const uint32_t r = blockIdx.y;
     if (row_idle(rows, r)) return;
-    sample_body<BF>(cand + (size_t)r * p.ncand, p, seeds, n_seed_pairs, reinterpret_cast<step_state_s*>(rows + r), tokens_out,
+    sample_body<BF>(cand + (size_t)r * p.ncand, p, seeds, n_seed_pairs, rows + r, tokens_out,
                     nullptr);
 }

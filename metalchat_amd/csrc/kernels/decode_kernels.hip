@@ -259,7 +259,6 @@ mc_rope_table(float* fcos, float* fsin, uint32_t rows, uint32_t dim, uint32_t st
 // After the MFMA the valid scores sit in the first n_rep/4 lane groups; they are dealt out so that
 // lane (c, col) finishes head 4m + c of slot col: with n_rep = 4 every lane evaluates ONE exp.
 // ------------------------------------------------------------------------------------------
-constexpr int PB = 64; // cache slots per scores workgroup
 
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 typedef float f32x4_t __attribute__((ext_vector_type(4)));

@@ -22,12 +22,7 @@
 // tile's ranges; scratch slots are range indices relative to `ebase`, the first range of the launch (a call whose ranges exceed
 // the scratch is launched in groups of whole tiles).
 
-struct px_range {
-    int32_t seg, r0;    // segment, first chunk row of the 16-row tile inside it
-    int32_t k_lo, k_hi; // keys [k_lo, k_hi) of the row's cache; k_lo a multiple of 128
-    int32_t first, n;   // the tile's ranges: indices [first, first + n) of this table
-    int32_t pad0, pad1;
-};
+// (px_range: abi.h)
 
 // the scores of one range: shared by the two passes.  Lane (l15, lg) of a wave holds row r0 + l15 (S^T = K Q^T, as pf_attn_kt_body).
 template <uint32_t HD, int NH>

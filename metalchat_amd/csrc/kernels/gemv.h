@@ -29,6 +29,7 @@
 #define MC_ABL_NORM_NOXWAVE 0
 #endif
 
+#include "abi.h"
 #include "common.h"
 
 #include <type_traits>
@@ -56,23 +57,14 @@ constexpr int PARTS_R = 4;
 // `res` of the kernel carries a postnorm_args* (the epilogues e0 / e3 do not use it).
 // a barrier for hand-overs through LDS alone: no wait for the vector memory counter (see the post-norm prologue below)
 static __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-struct postnorm_args {
-    const void* post_w; // T[in]
-    const void* res;    // T[in]
-    void* h_out;        // T[in]
-};
+using abi::postnorm_args;
 enum { EPI_STORE = 0, EPI_RESID = 1, EPI_SILU_MUL = 2, EPI_GELU_MUL = 3, EPI_QKV_ROPE = 4, EPI_STORE_PICK = 5 };
 // EPI_STORE_PICK (linear-order kernels): EPI_STORE + the greedy pick of the stored row, so the output head needs no argmax
 // launch behind it.  `res` points at this descriptor.  Every lane that finishes a pair keeps the best (value, lowest index)
 // it has seen as ONE 64-bit key; a wave folds its lanes, the workgroup's waves meet in LDS, the last of them hands the
 // workgroup's key to `key` with an agent-scope atomic max and takes a ticket; the workgroup whose ticket is the last reads the
 // final key back, writes the token where mc_argmax_T writes it and clears key and ticket for the next launch.
-struct pick_epilogue {
-    unsigned long long* key; // 0 between launches
-    uint32_t* ticket;        // 0 between launches; NULL: `key` has one slot per workgroup and a one-workgroup launch folds them
-    int32_t* state;          // step_state: [0] = token, [5] = step_index
-    int32_t* tokens_out;     // may be null
-};
+using abi::pick_epilogue;
 // larger float <=> larger key; equal floats (-0 = +0) <=> the LOWER index wins: mc_argmax_T's "first index of the maximum"
 __device__ __forceinline__ unsigned long long
 pick_key(float v, uint32_t index)
@@ -88,15 +80,7 @@ pick_key(float v, uint32_t index)
 // HBM as a separate launch.  The q and k rows of the fused matrix are stored with the rotation
 // partners (j, j + hd/2) of a head ADJACENT (packed row head*hd + 2j + e <-> natural row
 // head*hd + j + e*hd/2), so one wavefront tile of four rows holds two complete pairs.
-struct qkv_epilogue {
-    void* q_out;        // T[H*hd]       rotated queries, natural order
-    void* kc;           // T[KV][max_seq][hd]
-    void* vt;           // T[KV][hd][max_seq]
-    const float* fcos;  // [rows][hd/2]
-    const float* fsin;
-    const int32_t* state; // step_state: [3] = write_slot, [6] = rope_row
-    uint32_t H, KV, hd, max_seq;
-};
+using abi::qkv_epilogue;
 
 typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
 
@@ -771,8 +755,8 @@ body(const void* __restrict__ wp, const void* __restrict__ sp, const void* __res
                 if (t == gridDim.x - 1) {
                     const unsigned long long fin = __hip_atomic_fetch_max(pe_.key, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     const int32_t token = (int32_t)(0xFFFFFFFFu - (uint32_t)fin);
-                    pe_.state[0] = token;
-                    if (pe_.tokens_out) pe_.tokens_out[pe_.state[5]] = token;
+                    pe_.state->token = token;
+                    if (pe_.tokens_out) pe_.tokens_out[pe_.state->step_index] = token;
                     __hip_atomic_store(pe_.key, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     __hip_atomic_store(pe_.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 }
@@ -826,7 +810,7 @@ body(const void* __restrict__ wp, const void* __restrict__ sp, const void* __res
             // (linear-order kernels read the descriptor once, at the top, with scalar loads: eo_q)
             const qkv_epilogue* q = LNCH ? &eo_q : static_cast<const qkv_epilogue*>(resp);
             const uint32_t H = q->H, KV = q->KV, hd = q->hd, half = hd / 2, ms = q->max_seq;
-            const uint32_t slot = LNCH ? eo_slot : (uint32_t)q->state[3], rrow = LNCH ? eo_rrow : (uint32_t)q->state[6];
+            const uint32_t slot = LNCH ? eo_slot : (uint32_t)q->state->write_slot, rrow = LNCH ? eo_rrow : (uint32_t)q->state->rope_row;
             typedef const __attribute__((address_space(1))) float* gfloat_p;
             typedef __attribute__((address_space(1))) S* gS_p;
             if (row < (H + KV) * hd) {
@@ -1146,9 +1130,9 @@ body(const void* __restrict__ wp, const void* __restrict__ sp, const void* __res
         }
         if (EPI == EPI_QKV_ROPE) {
             eo_q = *static_cast<const qkv_epilogue*>(resp);
-            const __attribute__((address_space(1))) int32_t* stp = (const __attribute__((address_space(1))) int32_t*)eo_q.state;
-            eo_slot = (uint32_t)stp[3];
-            eo_rrow = (uint32_t)stp[6];
+            const __attribute__((address_space(1))) abi::step_state* stp = (const __attribute__((address_space(1))) abi::step_state*)eo_q.state;
+            eo_slot = (uint32_t)stp->write_slot;
+            eo_rrow = (uint32_t)stp->rope_row;
             if (never) asm volatile("" ::"s"(eo_slot), "s"(eo_rrow), "s"(eo_q.H), "s"(eo_q.KV), "s"(eo_q.hd), "s"(eo_q.max_seq));
         }
         // packet t of pair pr: row 2 pr + t / LGEN, KiB t % LGEN of it (dead packets: one broadcast line of the buffer base)
@@ -1557,9 +1541,9 @@ body(const void* __restrict__ wp, const void* __restrict__ sp, const void* __res
             // weight tile in flight); pointers found in memory are generic: without the address-space cast a read through
             // them is a flat_load, which counts on both wait counters
             eo_q = *static_cast<const qkv_epilogue*>(resp);
-            const __attribute__((address_space(1))) int32_t* stp = (const __attribute__((address_space(1))) int32_t*)eo_q.state;
-            eo_slot = (uint32_t)stp[3];
-            eo_rrow = (uint32_t)stp[6];
+            const __attribute__((address_space(1))) abi::step_state* stp = (const __attribute__((address_space(1))) abi::step_state*)eo_q.state;
+            eo_slot = (uint32_t)stp->write_slot;
+            eo_rrow = (uint32_t)stp->rope_row;
             if (lin_never) asm volatile("" ::"s"(eo_slot), "s"(eo_rrow), "s"(eo_q.H), "s"(eo_q.KV), "s"(eo_q.hd), "s"(eo_q.max_seq));
         }
 

@@ -9,22 +9,11 @@
 // for one another must be co-resident: the host guarantees it (decoder.cc attn_fused(), attn_wo_fused(), chain_ok()).
 #pragma once
 
+#include "abi.h"
 #include "common.h"
 
-struct step_state {
-    int32_t token;      // input token of the current step
-    int32_t pos;        // start_pos of the current step
-    int32_t kv_len;     // valid cache slots after this step's write  = min(pos + 1, max_seq)
-    int32_t write_slot; // physical slot of this step's K/V row
-    int32_t ring_base;  // rotation of the post-sink ring
-    int32_t step_index; // index into tokens_out for chained generation
-    int32_t rope_row;   // pos - rope_table_start
-    int32_t rolled;     // number of rolls so far (debug)
-    int32_t rope_start; // first position of the rope table window (nn/embedding.h:190-198); moved by mc_step_rope
-    uint32_t epoch;     // counts the steps since the decoder was created (never reset): the tag of in-launch hand-offs
-    uint32_t err;       // set by a kernel whose in-launch hand-off gave up (mc_attn_fused_T); 0 = none
-    int32_t pad[1];
-};
+// the step state itself: abi.h (the host fills and reads it too)
+using namespace mc::abi;
 
 typedef __attribute__((address_space(1))) unsigned long long gu64_t;
 typedef __attribute__((address_space(1))) uint32_t gu32_t;

@@ -9,9 +9,7 @@
 // and its chunk sits at positions [pos, pos + len) -- cache slots and rope table rows alike (a batch's cache does not roll and
 // its rope table starts at position 0).
 
-struct pp_seg {
-    int32_t row, pos, off, len;
-};
+// (pp_seg and pp_tile: abi.h)
 
 // pf_rope_cache_v4_body's row map over the segment table: packed row r -> (its row's caches, slot, rope row)
 struct pp_rows {
@@ -57,25 +55,25 @@ mc_pp_rope_cache_parts_bfloat(const float* part, uint32_t splits, uint32_t M, bf
 // (only the chunk's own columns are visible, as in mc_decoder_prefill at start_pos = pos).
 #define MC_PP_ATTN(HD)                                                                                                                     \
     extern "C" __global__ void __launch_bounds__(256)                                                                                      \
-    mc_pp_attn_bfloat_hd##HD(const bf16_t* Q, const pp_seg* segs, const int2* tiles, const bf16_t* kc, const bf16_t* vt, uint64_t cache_stride, \
-                             bf16_t* out, uint32_t H, uint32_t n_rep, uint32_t max_seq, float scale, const float* etab)                     \
+    mc_pp_attn_bfloat_hd##HD(const bf16_t* Q, const pp_seg* segs, const pp_tile* tiles, const bf16_t* kc, const bf16_t* vt, uint64_t cache_stride, \
+                             bf16_t* out, uint32_t H, uint32_t n_rep, uint32_t max_seq, float scale, const float* etab)                    \
     {                                                                                                                                      \
-        const int2 t = tiles[blockIdx.x];                                                                                                  \
-        const pp_seg g = segs[t.x];                                                                                                        \
+        const pp_tile t = tiles[blockIdx.x];                                                                                               \
+        const pp_seg g = segs[t.seg];                                                                                                      \
         const size_t q0 = (size_t)g.off * H * HD;                                                                                          \
-        pf_attn_body<HD, 1>(Q + q0, kc + (size_t)g.row * cache_stride, vt + (size_t)g.row * cache_stride, out + q0, (uint32_t)g.len,         \
-                            (uint32_t)(g.pos + g.len), H, n_rep, max_seq, scale, 0u, etab, (uint32_t)t.y);                                   \
+        pf_attn_body<HD, 1>(Q + q0, kc + (size_t)g.row * cache_stride, vt + (size_t)g.row * cache_stride, out + q0, (uint32_t)g.len,       \
+                            (uint32_t)(g.pos + g.len), H, n_rep, max_seq, scale, 0u, etab, (uint32_t)t.r0);                                \
     }                                                                                                                                      \
     extern "C" __global__ void __launch_bounds__(256)                                                                                      \
-    mc_pp_attn2_bfloat_hd##HD(const bf16_t* Q, const pp_seg* segs, const int2* tiles, const bf16_t* kc, const bf16_t* vt,                  \
+    mc_pp_attn2_bfloat_hd##HD(const bf16_t* Q, const pp_seg* segs, const pp_tile* tiles, const bf16_t* kc, const bf16_t* vt,               \
                               uint64_t cache_stride, bf16_t* out, uint32_t H, uint32_t n_rep, uint32_t max_seq, float scale,               \
                               const float* etab)                                                                                           \
     {                                                                                                                                      \
-        const int2 t = tiles[blockIdx.x];                                                                                                  \
-        const pp_seg g = segs[t.x];                                                                                                        \
+        const pp_tile t = tiles[blockIdx.x];                                                                                               \
+        const pp_seg g = segs[t.seg];                                                                                                      \
         const size_t q0 = (size_t)g.off * H * HD;                                                                                          \
-        pf_attn_kt_body<HD, 2>(Q + q0, kc + (size_t)g.row * cache_stride, vt + (size_t)g.row * cache_stride, out + q0, (uint32_t)g.len,      \
-                               (uint32_t)(g.pos + g.len), H, n_rep, max_seq, scale, 0u, etab, (uint32_t)t.y);                                \
+        pf_attn_kt_body<HD, 2>(Q + q0, kc + (size_t)g.row * cache_stride, vt + (size_t)g.row * cache_stride, out + q0, (uint32_t)g.len,    \
+                               (uint32_t)(g.pos + g.len), H, n_rep, max_seq, scale, 0u, etab, (uint32_t)t.r0);                             \
     }
 MC_PP_ATTN(64)
 MC_PP_ATTN(128)

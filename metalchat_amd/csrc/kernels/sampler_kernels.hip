@@ -15,6 +15,7 @@
 // topk(50) -> nucleus(0.6, 0.9) -> multinomial(1)) fused into two launches on the decode stream,
 // with no host round trip (the reference synchronises three times per token and partial_sorts
 // the whole vocabulary on the CPU, nn/sampling.h:244-264).
+#include "abi.h"
 #include "common.h"
 
 using namespace mc;
@@ -467,27 +468,15 @@ topk_candidates_body(const typename T::S* logits, uint32_t n, uint32_t kpad, uin
 MC_TOPK_CANDIDATES(mc_topk_candidates_bfloat, BF)
 MC_TOPK_CANDIDATES(mc_topk_candidates_float, F32)
 
-struct sampler_params {
-    uint32_t k;          // top-k (<= 128)
-    uint32_t ncand;      // candidate keys written by launch 1 = nlists * kpad
-    uint32_t cap;        // keys the dynamic LDS holds (a power of two >= 2 * kpad)
-    float inv_temp;      // T(1 / T(temperature))
-    float top_p;         // T(p)
-    uint32_t nlists;     // sorted candidate lists (workgroups of launch 1), <= MC_SAMPLE_LISTS_MAX
-    uint32_t kpad;       // keys per list
-};
-constexpr uint32_t MC_SAMPLE_LISTS_MAX = 1024;
-
-struct step_state_s { // prefix of step_state (decode_kernels.hip)
-    int32_t token, pos, kv_len, write_slot, ring_base, step_index, rope_row, rolled;
-};
+// sampler_params, MC_SAMPLE_LISTS_MAX and the step state: abi.h
+using namespace mc::abi;
 
 // launch 2: one workgroup.  Dynamic LDS: ncand_pad keys.  taps (optional): 7*k floats, the
 // intermediates in the order of mco_sample_default.
 template <typename T>
 __device__ __forceinline__ void
 sample_body(const uint64_t* cand, sampler_params p, const uint64_t* seeds, uint32_t n_seed_pairs,
-            step_state_s* st, int32_t* tokens_out, float* taps)
+            step_state* st, int32_t* tokens_out, float* taps)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     uint64_t* keys = reinterpret_cast<uint64_t*>(smem);
@@ -700,13 +689,13 @@ sample_body(const uint64_t* cand, sampler_params p, const uint64_t* seeds, uint3
 }
 extern "C" __global__ void
 mc_sample_bfloat(const uint64_t* cand, sampler_params p, const uint64_t* seeds, uint32_t n_seed_pairs,
-                 step_state_s* st, int32_t* tokens_out, float* taps)
+                 step_state* st, int32_t* tokens_out, float* taps)
 {
     sample_body<BF>(cand, p, seeds, n_seed_pairs, st, tokens_out, taps);
 }
 extern "C" __global__ void
 mc_sample_float(const uint64_t* cand, sampler_params p, const uint64_t* seeds, uint32_t n_seed_pairs,
-                step_state_s* st, int32_t* tokens_out, float* taps)
+                step_state* st, int32_t* tokens_out, float* taps)
 {
     sample_body<F32>(cand, p, seeds, n_seed_pairs, st, tokens_out, taps);
 }

@@ -64,7 +64,7 @@ def steps(a, b):
 
 
 def states(n):
-    """n step_state records (kernels/handoff.h: 12 words), every word a distinct value so that a stray write shows"""
+    """n step_state records (kernels/abi.h: 12 words, pinned by its static_assert), every word a distinct value so that a stray write shows"""
     return (np.arange(n * 12, dtype=np.int32).reshape(n, 12) + 1000)
 
 
