@@ -178,6 +178,51 @@ def test_the_launch_log(acc, small):
     release(batch, oms, dec)
 
 
+def test_a_call_in_several_launch_groups(acc, monkeypatch):
+    """a call whose ranges exceed the scratch of one launch group (batch.cc rows_ranges: groups of whole tiles, the kernels' `ebase`):
+    eight rows of 200 tokens behind 1800 keys with ranges of 128 keys -- 13 tiles of 15 or 16 ranges per row, 1608 ranges, and a
+    scratch of 64 MiB / (8 heads * 16 rows * 128 * 4 bytes) = 1024 slots: two groups.  A row's bits depend on its own segment only,
+    so every row must come out bit for bit as it does extended alone, in a call of its own that fits one group (201 ranges)"""
+    monkeypatch.setenv("MC_PX_KEYS", "128")
+    cfg = dict(SMALL, max_seq_len=2048)
+    L, pos, n = cfg["n_layers"], 1800, 200
+    weights = mg.make_model(cfg, seed=13, quant="i4", group=128)
+    dec = small_decoder(acc, cfg, weights)
+    import metalchat_amd as mc
+
+    prompts = prompts_of(cfg, [n] * 8, 12)
+
+    def rows_behind_their_contexts():
+        b = mc.Batch(dec, 8)
+        for r in range(8):
+            for layer in range(L):
+                k, v = random_cache(cfg, pos, 1900 + 100 * r + layer)
+                b.import_kv(r, layer, k, v)
+        return b
+
+    together, alone = rows_behind_their_contexts(), rows_behind_their_contexts()
+    dec.launch_log(True)
+    picks = together.extend_rows(prompts, [pos] * 8)
+    names = dec.launched()
+    assert names.count("mc_px_sums2_bfloat_hd128") == 2 * L, names  # two launch groups per layer
+    assert names.count("mc_px_pv2_bfloat_hd128") == 2 * L and names.count("mc_px_reduce_bfloat_hd128") == 2 * L, names
+    logits = together.logits()
+    for r in range(8):
+        call = [None] * 8
+        call[r] = prompts[r]
+        dec.launch_log(True)
+        own = alone.extend_rows(call, [pos] * 8)
+        assert dec.launched().count("mc_px_sums2_bfloat_hd128") == L  # one group
+        assert own[r] == picks[r] and picks[r] >= 0, (r, own[r], picks[r])
+        parity.exact(logits[r], alone.logits()[r], f"row {r}: logits in two groups against the row alone")
+        for a, b, name in zip(together.export_row_kv(r, 0), alone.export_row_kv(r, 0), "KV"):
+            assert a.shape[0] == pos + n
+            parity.exact(a, b, f"row {r}: layer 0 {name} in two groups against the row alone")
+    together.release()
+    alone.release()
+    dec.release()
+
+
 def test_placement_does_not_matter(acc, small):
     dec = small_decoder(acc, SMALL, small)
     prompts = prompts_of(SMALL, LENS, 3)
