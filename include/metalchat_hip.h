@@ -460,6 +460,36 @@ mc_status mc_rows_prefill(mc_batch* b, const int32_t* tokens, const int32_t* len
  * ------------------------------------------------------------------------------------------ */
 mc_status mc_extend_rows(mc_batch* b, const int32_t* tokens, const int32_t* lens, const int32_t* positions, int32_t* next_tokens);
 
+/* ================================================================================================
+ * Part 2f -- speculative verify: Part 2e's pass with a greedy pick after EVERY chunk row and the acceptance on the device.  A
+ * draft (a smaller model on a second decoder, a prompt-lookup table, anything) proposes tokens for a row; the target checks all
+ * of them in one pass over its weights and keeps the longest prefix it would have produced itself.  Row r's chunk is c[0 .. n),
+ * n = lens[r]: c[0] is the row's last accepted token (not yet in its cache), c[1 .. n) are n - 1 drafted tokens.  The layer pass
+ * is mc_extend_rows': the same launches, the same K / V written to [positions[r], positions[r] + n).  Then every packed row goes
+ * through the final norm and the head -- one pass over the head's weights for all of them, each row's logits bit for bit what
+ * the batch's own head gives for that hidden row -- and pick[i] is the first index of the maximum of chunk row i's logits.
+ *   a_r = the largest a <= n - 1 with c[i + 1] == pick[i] for all i < a      (the drafts the target would have produced)
+ * Afterwards row r's length is positions[r] + a_r + 1: the slots of the rejected drafts stay written but lie past the length,
+ * the rewound state every rows call handles (a later call at the new length overwrites them).  mc_batch_get_logits then holds,
+ * for each row in the call, the logits of chunk row a_r.  Feed next_tokens[r] at position positions[r] + a_r + 1.
+ * Greedy only: with the decoder's sampler set to anything else the call is refused ("... greedy").  2 <= lens[r] <=
+ * 16 (MC_VERIFY_MAX_LEN of the kernel ABI) for a row in the call (one attention tile per row: at most 128 packed rows); a longer chunk is refused
+ * naming the row, and a one-token chunk (no drafts) stays a ragged step.  All of Part 2e's refusals apply with the texts
+ * prefixed "mc_verify_rows: ", nothing enqueued.  The scratch ([128][vocab] logits and [128][dim] rows) is allocated at the first
+ * call, so a batch that never verifies holds what it held.  The decoder, rows outside the call and the independence of a row's
+ * bits from B, placement and company are as in Part 2e -- whose pass has one place where the call as a whole reaches a row: with
+ * int4 weights the decoder multiplies a prompt pass of at most 64 rows by another GEMM than a longer one, and the two order their
+ * sums differently (a few elements differ in their last bits).  Calls on one side of that line agree bit for bit.
+ * ------------------------------------------------------------------------------------------ */
+/* tokens / lens / positions: exactly mc_extend_rows' (Part 2e).
+ * picks (sum of lens ids, packed like tokens; may be null): picks[off_r + i] = the greedy pick after chunk row i.
+ * accepted[B]: a_r; -1 for a row not in the call.
+ * next_tokens[B] (may be null): pick[a_r] -- the token to feed at position positions[r] + a_r + 1; -1 for a row not in the call. */
+mc_status mc_verify_rows(mc_batch* b, const int32_t* tokens, const int32_t* lens, const int32_t* positions,
+                         int32_t* accepted, int32_t* next_tokens, int32_t* picks);
+/* test aid: the [sum of lens][vocab] logits of T of the last mc_verify_rows call, packed like tokens */
+mc_status mc_verify_get_logits(mc_batch* b, void* logits_T);
+
 /* Host-side helpers shared by tests and the synthetic initialiser. */
 /* value in [-7,7] (bits = 4) or [-127,127] (bits = 8), zero mean, of element (row, col) of matrix `matrix_id` */
 int32_t mc_synth_weight(uint64_t seed, uint32_t matrix_id, uint32_t row, uint32_t col, int32_t bits);

@@ -57,6 +57,13 @@ struct mc_batch {
     std::vector<px_group> px_groups;
     float *px_sums = nullptr, *px_part = nullptr; // scratch of one launch group: [px_slots][H][16], [px_slots][H][16][hd]
     int px_slots = 0;
+    // mc_verify_rows, reserved at the first call: the normed rows [128][dim], their logits [128][vocab], and the call's results
+    // on the device: accepted[B], next_tokens[B], picks[128]
+    void *v_xn = nullptr, *v_logits = nullptr;
+    int32_t* v_out = nullptr;
+    int v_xn_cap = 0, v_logits_cap = 0, v_out_cap = 0;
+    int v_rows = 0;                       // packed rows of the last mc_verify_rows call (0: none yet)
+    std::vector<int32_t> v_host;
 
     ~mc_batch()
     {
@@ -220,6 +227,28 @@ struct mc_batch {
         if (s != MC_OK) return s;
         return launch("mc_b_sample" + sfx, 1, B, 1, 128, sp.cap * 8,
                       pack(cand, sp, seeds, (uint32_t)n_seed_pairs, rows, tokens_dev));
+    }
+
+    // mc_verify_rows: the final norm, the head and a greedy pick for each of the M packed rows `xrows` of a call, then per segment
+    // the acceptance of its drafts (`tokens`: the call's ids on the device) and the accepted row's logits into logits[row]
+    mc_status
+    verify_head(const void* xrows, const int32_t* tokens, int M, int nseg)
+    {
+        const mc_decoder_config& c = p.cfg;
+        const batch_linear& L = p.output;
+        mc_status s = launch("mc_b_rmsnorm_bfloat", 1, M, 1, 1024, 0, pack(xrows, p.final_norm, v_xn, (uint32_t)c.dim, c.norm_eps));
+        if (s != MC_OK) return s;
+        s = launch(std::string("mc_v_head_") + (L.fmt == MC_WFMT_I4 ? "i4" : "w") + "_bfloat", (unsigned)(L.out / 16 + VH_TILES - 1) / VH_TILES, 1, 1,
+                   BG_THREADS, 0,
+                   pack(L.w, L.scales, (const void*)v_xn, v_logits, (uint32_t)L.in, (uint32_t)L.ngroups, (uint32_t)L.group, (uint32_t)M,
+                        (uint32_t)L.out, (uint32_t)c.vocab));
+        if (s != MC_OK) return s;
+        int32_t* picks = v_out + 2 * B;
+        if ((s = launch("mc_v_argmax_bfloat", 1, M, 1, 1024, 0, pack((const void*)v_logits, (uint32_t)c.vocab, picks))) != MC_OK) return s;
+        const unsigned gx = std::min(64u, ((unsigned)c.vocab / 8 + 255) / 256);
+        return launch("mc_v_accept", gx, nseg, 1, 256, 0,
+                      pack((const pp_seg*)pp_segs(pp_tab), tokens, (const int32_t*)picks, (const void*)v_logits, (uint32_t)c.vocab, v_out, v_out + B,
+                           logits));
     }
 
     // rows' tokens and step indices for token 0 of a call (step_index = r: seed pair r % n_pairs, tokens_out[0][r]); a ragged
@@ -658,15 +687,28 @@ rows_ranges(mc_batch* b, int ntiles, int slots)
     }
 }
 
-// mc_rows_prefill and mc_extend_rows: one body, `extend` selects the attention (and `who` the texts)
+// what mc_verify_rows adds to the pass: a pick after every chunk row and the acceptance (next_tokens is the pass's own argument)
+struct verify_out {
+    int32_t* accepted; // [B]
+    int32_t* picks;    // [M], may be null
+};
+
+// mc_rows_prefill, mc_extend_rows and mc_verify_rows: one body, `extend` selects the attention (and `who` the texts), `v` the
+// head over every packed row in place of the head over each row's last
 mc_status
-rows_pass(mc_batch* b, const char* who, bool extend, const int32_t* tokens, const int32_t* lens, const int32_t* positions, int32_t* next_tokens)
+rows_pass(mc_batch* b, const char* who, bool extend, const int32_t* tokens, const int32_t* lens, const int32_t* positions, int32_t* next_tokens,
+          const verify_out* v = nullptr)
 {
     const mc_decoder_config& c = b->p.cfg;
     const int B = b->B;
     int M = 0, nseg = 0, ntiles = 0;
     mc_status s = rows_check(b, who, tokens, lens, positions, &M, &nseg, &ntiles);
     if (s != MC_OK) return s;
+    if (v)
+        for (int r = 0; r < B; r++)
+            if (lens[r] > MC_VERIFY_MAX_LEN)
+                return fail(MC_ERR_INVALID_ARGUMENT, std::string(who) + ": row " + std::to_string(r) + ": a chunk of " + std::to_string(lens[r]) +
+                                                         " tokens is longer than MC_VERIFY_MAX_LEN (" + std::to_string(MC_VERIFY_MAX_LEN) + ")");
     MC_HIP(hipSetDevice(b->p.ordinal));
     rows_tables(b, lens, positions, ntiles);
     // (enough for any call: at most max_seq_len rows in at most 8 segments)
@@ -709,9 +751,33 @@ rows_pass(mc_batch* b, const char* who, bool extend, const int32_t* tokens, cons
         pk.sums = b->px_sums;
         pk.part = b->px_part;
     }
+    const void* rows_all = nullptr;
+    const int32_t* ids = nullptr;
+    if (v) {
+        // (M <= 128 here; the scratch is sized for any call)
+        if ((s = b->reserve(b->v_xn, b->v_xn_cap, M, MC_VERIFY_MAX_ROWS, (size_t)c.dim * 2)) != MC_OK ||
+            (s = b->reserve(b->v_logits, b->v_logits_cap, M, MC_VERIFY_MAX_ROWS, (size_t)c.vocab * 2)) != MC_OK ||
+            (s = b->reserve(b->v_out, b->v_out_cap, 2 * B + M, 2 * BATCH_MAX + MC_VERIFY_MAX_ROWS)) != MC_OK)
+            return s;
+        MC_HIP(hipMemsetAsync(b->v_out, 0xFF, sizeof(int32_t) * 2 * B, b->p.stream)); // -1: a row not in the call
+        pk.rows_all = &rows_all;
+        pk.tokens_dev = &ids;
+    }
     if ((s = decoder_prefill_packed(b->d, tokens, M, pk)) != MC_OK) return s;
-    if ((s = b->head("_rows_bfloat")) != MC_OK) return s;
+    if ((s = v ? b->verify_head(rows_all, ids, M, nseg) : b->head("_rows_bfloat")) != MC_OK) return s;
     MC_HIP(hipStreamSynchronize(b->p.stream)); // (`tokens` is the caller's buffer; the tables are read by the launches)
+    if (v) {
+        b->v_rows = M;
+        b->v_host.resize(2 * B + M);
+        MC_HIP(hipMemcpy(b->v_host.data(), b->v_out, sizeof(int32_t) * b->v_host.size(), hipMemcpyDeviceToHost));
+        std::copy_n(b->v_host.begin(), B, v->accepted);
+        if (next_tokens) std::copy_n(b->v_host.begin() + B, B, next_tokens);
+        if (v->picks) std::copy_n(b->v_host.begin() + 2 * B, M, v->picks);
+        // the rejected drafts' slots stay written past the length: the rewound state every rows call handles
+        for (int r = 0; r < B; r++)
+            if (lens[r] > 0) b->lengths[r] = positions[r] + v->accepted[r] + 1;
+        return MC_OK;
+    }
     for (int r = 0; r < B; r++)
         if (lens[r] > 0) b->lengths[r] = positions[r] + lens[r];
     if (next_tokens) MC_HIP(hipMemcpy(next_tokens, b->tokens_dev, sizeof(int32_t) * B, hipMemcpyDeviceToHost));
@@ -734,6 +800,31 @@ mc_extend_rows(mc_batch* b, const int32_t* tokens, const int32_t* lens, const in
 {
     if (!b || !tokens || !lens || !positions) return fail(MC_ERR_INVALID_ARGUMENT, "mc_extend_rows: null argument");
     return rows_pass(b, "mc_extend_rows", true, tokens, lens, positions, next_tokens);
+}
+
+// ---- Part 2f: speculative verify ----
+
+mc_status
+mc_verify_rows(mc_batch* b, const int32_t* tokens, const int32_t* lens, const int32_t* positions, int32_t* accepted, int32_t* next_tokens,
+               int32_t* picks)
+{
+    if (!b || !tokens || !lens || !positions || !accepted) return fail(MC_ERR_INVALID_ARGUMENT, "mc_verify_rows: null argument");
+    if (decoder_sampler_of(b->d).kind != MC_SAMPLER_GREEDY)
+        return fail(MC_ERR_INVALID_ARGUMENT,
+                    "mc_verify_rows: the decoder's sampler is not greedy (accepting sampled drafts needs the draft's probabilities)");
+    const verify_out v{accepted, picks};
+    return rows_pass(b, "mc_verify_rows", true, tokens, lens, positions, next_tokens, &v);
+}
+
+mc_status
+mc_verify_get_logits(mc_batch* b, void* logits_T)
+{
+    if (!b || !logits_T) return fail(MC_ERR_INVALID_ARGUMENT, "mc_verify_get_logits: null argument");
+    if (!b->v_rows) return fail(MC_ERR_INVALID_ARGUMENT, "mc_verify_get_logits: no mc_verify_rows call on this batch yet");
+    MC_HIP(hipSetDevice(b->p.ordinal));
+    MC_HIP(hipStreamSynchronize(b->p.stream));
+    MC_HIP(hipMemcpy(logits_T, b->v_logits, (size_t)b->v_rows * b->p.cfg.vocab * 2, hipMemcpyDeviceToHost));
+    return MC_OK;
 }
 
 // ---- Part 2c: ragged rows ----

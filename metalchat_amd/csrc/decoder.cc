@@ -2228,6 +2228,8 @@ struct mc_decoder {
         if (pk) {
             // the batch's head follows (batch.cc): the last row of each chunk into its batch row
             s = launch("mc_pp_gather_last_bfloat", gd, (unsigned)pk->nseg, 1, 256, 0, pack((const void*)pf_x, pk->segs, pk->x_out, (uint32_t)dim));
+            if (pk->rows_all) *pk->rows_all = pf_x;
+            if (pk->tokens_dev) *pk->tokens_dev = pf_tokens;
         } else {
             // only the last row goes through the head (llama.h:130-133); other stages hand all rows on (pf_x)
             MC_HIP(hipMemcpyAsync(hidden, (char*)pf_x + last, (size_t)dim * tb, hipMemcpyDeviceToDevice, stream));

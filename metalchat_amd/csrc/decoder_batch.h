@@ -84,6 +84,10 @@ struct packed_prefill {
     int ngroups = 0;
     float* sums = nullptr;           // scratch [slots][n_heads][16]: the exp row sums of a range
     float* part = nullptr;           // scratch [slots][n_heads][16][head_dim]: the partial outputs of a range
+    // mc_verify_rows: the head runs over every packed row.  When set they receive the device addresses of all M rows after the
+    // last layer ([M][dim]) and of the call's M token ids -- the decoder's prompt scratch, valid until its next prompt pass.
+    const void** rows_all = nullptr;
+    const int32_t** tokens_dev = nullptr;
 };
 // run_prefill over `tokens` (M ids, host) with the packed rope + cache and attention launches, then the gather into x_out; the
 // decoder's cache, step state, sampler, taps and head are not touched (its prompt scratch is)

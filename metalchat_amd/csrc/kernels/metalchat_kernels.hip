@@ -11,3 +11,4 @@
 #include "batch_kernels.hip"
 #include "packed_kernels.hip"
 #include "extend_kernels.hip"
+#include "verify_kernels.hip"

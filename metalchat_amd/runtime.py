@@ -206,6 +206,8 @@ def capi() -> C.CDLL:
         "mc_ragged_export_kv": (i32, [vp, i32, i32, vp, vp, C.POINTER(i32)]),
         "mc_rows_prefill": (i32, [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
         "mc_extend_rows": (i32, [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
+        "mc_verify_rows": (i32, [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
+        "mc_verify_get_logits": (i32, [vp, vp]),
         "mc_synth_weight": (i32, [u64, u32, u32, u32, i32]),
         "mc_synth_scale": (f32, [u64, u32, u32, u32, i32, i32]),
         "mc_synth_value": (f32, [u64, u32, u32, i32, u32]),
@@ -890,16 +892,47 @@ class Batch:
         everything its cache holds below it -- a follow-up message on a live row, the next piece of a long prompt."""
         return self._rows_pass(capi().mc_extend_rows, prompts, positions)
 
-    def _rows_pass(self, call, prompts, positions) -> np.ndarray:
+    def _packed(self, prompts):
         assert len(prompts) == self.B
         chunks = [np.asarray([] if p is None else p, dtype=np.int32).reshape(-1) for p in prompts]
         lens = np.array([c.shape[0] for c in chunks], dtype=np.int32)
         tokens = np.ascontiguousarray(np.concatenate(chunks + [np.zeros(1, np.int32)]))  # (never empty: a valid pointer)
+        return tokens, lens
+
+    def _rows_pass(self, call, prompts, positions) -> np.ndarray:
+        tokens, lens = self._packed(prompts)
         p = self._positions(positions)
         out = np.zeros(self.B, dtype=np.int32)
         ptr = C.POINTER(C.c_int32)
         _check(call(self._h, tokens.ctypes.data_as(ptr), lens.ctypes.data_as(ptr), p.ctypes.data_as(ptr), out.ctypes.data_as(ptr)))
         return out
+
+    # ---- speculative verify (Part 2f): extend_rows with a greedy pick after every chunk row and the acceptance on the device
+
+    def verify_rows(self, prompts, positions):
+        """prompts[r] = [the row's last accepted token, then its drafted tokens] (2 to 16 ids), None for a row not in the call.
+        Returns (accepted[B], next_tokens[B], picks): accepted[r] drafts were what the target picks itself, next_tokens[r] is its
+        pick after them -- feed it at positions[r] + accepted[r] + 1, the row's new length; picks[r][i] is the pick after chunk
+        row i.  -1 / -1 / None for a row not in the call."""
+        tokens, lens = self._packed(prompts)
+        p = self._positions(positions)
+        accepted, nxt = np.zeros(self.B, dtype=np.int32), np.zeros(self.B, dtype=np.int32)
+        picks = np.zeros(tokens.shape[0], dtype=np.int32)
+        ptr = C.POINTER(C.c_int32)
+        _check(capi().mc_verify_rows(self._h, tokens.ctypes.data_as(ptr), lens.ctypes.data_as(ptr), p.ctypes.data_as(ptr),
+                                     accepted.ctypes.data_as(ptr), nxt.ctypes.data_as(ptr), picks.ctypes.data_as(ptr)))
+        self._verify_lens = lens
+        off = np.concatenate([[0], np.cumsum(lens)])
+        return accepted, nxt, [picks[off[r]:off[r + 1]].copy() if lens[r] else None for r in range(self.B)]
+
+    def verify_logits(self):
+        """test aid: the logits after every chunk row of the last verify_rows call -- per row [lens[r]][vocab], None for a row
+        that was not in it"""
+        lens = getattr(self, "_verify_lens", np.zeros(self.B, np.int32))
+        out = np.empty((max(int(lens.sum()), 1), self.cfg["vocab"]), dtype=self.np_T)
+        _check(capi().mc_verify_get_logits(self._h, _np_ptr(out)))
+        off = np.concatenate([[0], np.cumsum(lens)])
+        return [out[off[r]:off[r + 1]] if lens[r] else None for r in range(self.B)]
 
     def set_seeds(self, pairs):
         a = np.ascontiguousarray(np.asarray(pairs, dtype=np.uint64).reshape(-1, 2))
