@@ -15,6 +15,7 @@
 #include "decoder_batch.h"
 #include "kernels/synth.h"
 
+#include <climits>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -183,10 +184,202 @@ bit_width(uint32_t v)
     return n;
 }
 
+// Every switch of this file: the MC_* environment variables, read ONCE when a decoder is created (read_options below holds every getenv("MC_...") of
+// decoder.cc).  A switch keeps the name, default, clamp and meaning it was introduced with; the measurements behind a default stay next to its field.
+struct decoder_options {
+    // ---- the decode GEMVs (gemv())
+    int gemv_block = 256;        // MC_GEMV_BLOCK: threads of a classic GEMV workgroup (a multiple of 64 in [64, 1024], else 256)
+    int gemv_wgs_per_cu = 2;     // MC_GEMV_WGS_PER_CU (at least 1, else 2)
+    bool gemv_block_env = false; // MC_GEMV_BLOCK / MC_GEMV_WGS_PER_CU given: they apply to every kernel of the family
+    bool gemv_lin = true;        // MC_GEMV_LIN=0: classic kernels everywhere (A/B)
+    bool gemv_ling = true;       // MC_GEMV_LING=0: int8 / bfloat weights on the classic kernels (A/B)
+    bool i8_ling14 = true;       // MC_I8_LING14=0: int8 rows of 14 KiB (w2 of Llama-3-8B) on the classic kernel (A/B)
+    bool lin_split = true;       // MC_LIN_SPLIT=0: K = 3072 on the classic kernels (A/B)
+    bool ling_half = true;       // MC_LING_HALF=0: whole row pairs per wave whatever the matrix (A/B)
+    bool lin_k4_on = true;       // MC_LIN_K4=0: Gemma-7B's w2 on the one-pair-per-wave kernel (mc_gemv_i4_bfloat_lin12_*) instead of the K-split one (A/B, parity)
+    int lin_waves = 8;           // MC_LIN_WAVES (1 .. 16): tuning builds of the linear-order kernels with another workgroup size
+    bool gemv_full_grid = false; // MC_GEMV_FULLGRID=1: as many workgroups as CUs allow even when that leaves waves without a row group (kernels built with MC_GEMV_WAVEMAJOR)
+    int dbg_variant = 0;         // MC_GEMV_DBG=1 stream-only, 2 compute-only (tuning ablations)
+    int gemv_m4 = 2;             // MC_GEMV_M4: 0 = exact int4 on the VALU (v_dot2c), 1 = dot products on the 4x4x4 MFMA, 2 = dequantisation too where a SIMD holds > 1 wave, 3 = always
+    int time_gemv_layers = 0;    // MC_TIME_GEMV_LAYERS=n (tuning aid of mc_decoder_time_gemv): every "layer" of the pass uses the weights of layer
+                                 // i % n, so with a small n the matrices stay resident in the 256 MiB Infinity Cache; 0 = every layer its own
+    // ---- the decode attention block (plan_block)
+    bool attn_fused = true;      // MC_ATTN_FUSED=0: scores and P.V as two launches (A/B, parity).  What the configuration asked for: mc_decoder::attn_fused_on is
+                                 // what holds now (handoff_failed, note_clean_tokens)
+    // ... while the launch is at most this many 256-thread workgroups per CU (MC_ATTN_FUSED_WGS, 1 .. 4).  Measured: at S = 8192 with
+    // 64-slot ranges (128 ranges x 8 kv heads = 4 per CU, every hand-off gathering from 128 producers) the one launch took 27.8 us
+    // against 6.3 + 8.5 for the two -- long contexts keep the two-launch form (wider ranges were built and measured no better)
+    unsigned attn_fused_max_wgs_per_cu = 2;
+    bool attn_t2_on = true;      // MC_ATTN_T2
+    int rearm_after = 256;       // MC_HANDOFF_REARM: tokens without a hand-off launch after which a fallen-back decoder takes the one-launch blocks again (0: never;
+                                 // mc_decoder::rearm_after starts here and doubles)
+    bool handoff_fast = true;    // MC_HANDOFF_FAST=0: hand-offs A and B through the fabric only (A/B; handoff.h "the XCD-local fast path")
+    bool attn_wo_on = true;      // MC_ATTN_WO=0: the Wo GEMV as a launch of its own behind the one-launch attention (A/B, parity)
+    bool attn_wo_k4 = false;     // MC_ATTN_WO_K4 set: mc_attn_wo_i4_*_hd128_k4 (K = 8192, Llama-3-70B: measured slower than the two launches -- attn_block_kernels.hip)
+    bool attn_qkv_on = true;     // MC_ATTN_QKV=0: wq|wk|wv as a launch of its own in front of mc_attn_wo_* (A/B, parity)
+    // MC_ATTN_QKV_ONLY=1: the 70B shapes' wq|wk|wv GEMV inside the attention launch (mc_attn_qkv_i4_bfloat_hd128_q4).  Built in round 5 as VERDICT r04
+    // item 2 (iv) asked, bit for bit the two launches, and NOT faster: 21.25 us against 11.65 + 9.04 in the trace (profiles/r05_kernel_stats_70b_qkvin.csv),
+    // 127.4 / 127.1 against 128.0 / 127.9 tokens/s alternating on one box -- 160 KB of wq|wk|wv per workgroup are 7 us of multiplication in front of
+    // the first hand-off, which is what the GEMV launch lasts.  Off by default.
+    bool attn_qkv_only_on = false;
+    bool attn_i8_on = true;      // MC_ATTN_I8: int8 wq|wk|wv and Wo inside the attention launch (plan_block: qkv_wo_i8)
+    bool attn_i4_wide_on = true; // MC_ATTN_I4_WIDE: the int4 block with 128- / 256-slot ranges at S = 4096 / 8192 (plan_block: qkv_wo_i4 with tiles > 1)
+    bool kv_virtual_on = true;   // MC_KV_VIRTUAL: fewer than 8 kv heads launched as 8 virtual ones where wq|wk|wv is inside the attention launch (kv_virtual_shift)
+    bool chain_w13_on = true;    // MC_CHAIN_W13=0: ffn_norm + w1|w3 + act*mul as a launch of its own behind the plain-weight attention block (A/B, parity)
+    int chain_f = -1;            // MC_CHAIN_F: pairs per fetcher wave of that chain instead of the rule's (tuning: tools/ab_case_multi.sh); -1 = not given
+    bool attn_qkv_qkn_on = true; // MC_ATTN_QKV_QKN=0: gemma3's wq|wk|wv GEMV as a launch of its own in front of mc_attn_wo_qkn_* (A/B, parity)
+    bool attn_wo_qkn_on = true;  // MC_ATTN_WO_QKN=0: gemma3's q/k-norm + rope + cache write + attention as mc_attn_fused_qkn_T, Wo as a GEMV of its own (A/B, parity)
+    bool attn_qkn_on = true;     // MC_ATTN_QKN=0: gemma3's q/k-norm + rope + cache write as a launch of their own (mc_rope_kv_T) in front of the attention (A/B, parity)
+    bool gemma_fuse = true;      // MC_GEMMA_UNFUSED=1: keep the post-norms as launches of their own
+    bool pv_fold_on = true;      // MC_PV_FOLD=0: P.V ranges reduced by their own launch (A/B, parity)
+    int pv_block = 1024;         // MC_PV_BLOCK: threads of a P.V workgroup (16 waves: one round of loads per wave at S = 2048; a multiple of 64 in [256, 1024], else 1024)
+    int pv_ranges = 0;           // MC_PV_RANGES (1 .. 64): ranges of the P.V launch; 0 = not given, by the context length (mc_decoder_create)
+    // ---- the output head
+    int head_pick_mode = 2;
+    bool head_pick_on = true;    // MC_HEAD_PICK: 0 = mc_argmax_T behind the head (round 1); 1 = the pick wholly inside the head's launch (atomic max
+                                 // + ticket per workgroup: parity-green, 1448 vs 1449 us per token -- the atomics cost what the launch costs);
+                                 // 2 = one key per workgroup + mc_argmax_keys, a one-workgroup launch over 8 KB instead of 256 KB of logits
+    bool lazy_pick_on = true;    // MC_LAZY_PICK
+    // ---- the prompt pass
+    bool pf2_on = true;          // MC_PF2: short prompts from the quad-interleaved copy
+    int pf2_wgs_per_cu = 1;      // MC_PF2_WGS_PER_CU (at least 1): workgroups per CU pf2_split aims at
+    bool pf_attn8_on = true;     // MC_PF_ATTN8: the prompt attention with K / V tiles through LDS, from pf_attn8_rows rows on
+    int pf_attn8_rows = 1024;    // MC_PF_ATTN8_ROWS
+    int pf_attn8_rows64 = 1793;  // MC_PF_ATTN8_ROWS64 (head_dim 64: mc_pf_attn8_bfloat_hd64_h{8,4}; TinyLlama 2048 rows 8.35 against 8.95 ms, Llama-3.2-1B 6.57 against 7.0; 1536 - 1792 rows equal, 1024: 5.1 against 4.9 -- profiles/r06_pf_hd64_attn8_ab.log)
+    int pf_attn8_rows256 = 513;  // MC_PF_ATTN8_ROWS256 (head_dim 256: mc_pf_attn8_bfloat_hd256; Gemma-7B shapes: 2048 rows 35.5 against 44.4 ms, 1024: 19.0 against 21.3, 512: equal, 256: 9.0 against 8.85)
+    int pf_attn_heads = -1;      // MC_PF_ATTN_HEADS=1 / 2 / 4 / 8: the prompt attention kernel by its query heads per workgroup instead of by the rules of prefill(); -1 = not given
+    int pf_attn8_pair = -1;      // MC_PF_ATTN8_PAIR=0 / 1: row tiles of the LDS-tile attention one per workgroup / in pairs; -1 = not given, by the grid
+    int pf_plain_mode = -1;      // MC_PF_PLAIN_COPY: 1 = the 256 x 256 prompt GEMM multiplies quantised matrices from their dequantised bfloat16 copy (linear_w::wd, built on
+                                 // first use, 2 bytes per weight more HBM: the very values the quantised loop stages in LDS, same loop, same sums bit for bit -- without
+                                 // the dequantisation that competes with the MFMAs for the issue port), 0 = from the quantised rows; unset = 1 iff the copies of every
+                                 // block's matrices fit an eighth of the device's memory (Llama-3-8B: 14 of 288 GB, yes; 70B: 137 GB, no)
+    bool pf_rope_pack = true;    // MC_PF_ROPE_PACK (prefill: the rope + cache launch with four rotation pairs per thread)
+    bool pf_g8_on = true;        // MC_PF_GEMM8: prompts of pf_g8_rows rows and more take the 256 x 256 ping-pong GEMM (kernels/pf_gemm8.h)
+    int pf_g8_max_splits = 16, pf_g8_min_ktiles = 8; // MC_PF_GEMM8_MAXSPLIT, MC_PF_GEMM8_MINKT: K ranges of a launch (g8_splits)
+    int pf_g8_rows = 257;        // MC_PF_GEMM8_ROWS: from TWO row tiles on (round 5 measured 256 rows 7.42 ms with, 7.06 without -- one row of tiles leaves half the chip idle -- and 512 rows
+                                 // 10.13 against 11.66, and set 384; round 6, on the dequantised copies: 256 rows 6.87 without against 7.65 with, 320 rows 11.2 against 8.95, 383: 11.3 against 9.2 --
+                                 // profiles/r06_pf_rows_ab.log)
+    bool pf_small_gemm = false;  // MC_PF_SMALL_GEMM set: the round-1 prompt GEMM for every matrix (A/B)
+    bool pf_depth1 = false;      // MC_PF_DEPTH=1: the one-chunk build of the tiled prompt GEMM (A/B; two K chunks in flight measured best at every length)
+    bool pf_bm128 = false;       // MC_PF_BM128 set: the 128-row prompt tile for every length
+    bool pf_splits_old = false;  // MC_PF_SPLITS_OLD set: the plain doubling rule of gemm_splits
+    bool pf_no_splitk = false;   // MC_PF_NO_SPLITK set: no prompt GEMM splits K
+    bool pf_fold_on = true;      // MC_PF_FOLD: the split-K reduce of a prompt GEMM inside the kernel that consumes its rows
+    bool pf_norm2 = true;        // MC_PF_NORM2=0: the split-K reduce and gemma3's two norms behind it as three launches
+    bool pf_act_epi = true;      // MC_PF_ACT_EPI=0: the activation of a long prompt as a launch of its own
+    bool pf_gelu_table = true;   // MC_PF_GELU_TABLE=0: no table of T(gelu) (mc_decoder::pf_gtab): the fp64 tanh per element
+    bool pf_lib = false;         // MC_PF_BLASLT=1 (opt-in since round 5, a comparison aid): long prompts' large GEMMs in hipBLASLt on a dequantised bfloat16 copy of the matrix
+                                 // (gemm_lib; mc_decoder::pf_lib_on is what holds now: any failure of the library switches the path off)
+    bool pf_lib_force = false;   // MC_PF_BLASLT=2: every prompt GEMM that can, whatever its size
+    bool pf_lib_tune = false;    // MC_PF_BLASLT_TUNE=1: the fastest of the heuristic's first eight algorithms, timed once per shape, instead of its first
+                                 // (measured: inside the noise -- 512 rows 10.13 / 9.91 ms without, 10.04 / 10.00 with; 2048 rows 32.92 / 33.52, 32.55 / 32.92 --
+                                 // and a timed choice would make the order of the fp32 additions differ from run to run: off)
+    int pf_lib_rows = 160;       // MC_PF_BLASLT_ROWS: the shortest prompt chunk whose GEMMs may take the library (measured: 128 rows 5.01 ms without against
+                                 // 5.38 with, 160 rows 6.83 / 5.96, 192: 6.91 / 6.33, 224: 7.08 / 6.44 -- profiles/r04_prefill_blaslt.log)
+    int pf_lib_tiles = 48;       // MC_PF_BLASLT_TILES: the fewest 256 x 256 tiles of a launch the library takes (swept on whole prompts: profiles/r04_prefill_blaslt.log)
+    bool pf_lib_verbose = false; // MC_PF_BLASLT_VERBOSE set: say on stderr why the library path switched itself off, and which algorithm a tuned shape took
+    // MC_PF_TIMING=1: per-category GPU time of a prompt pass printed to stderr (tuning aid; it
+    // synchronises after every launch)
+    bool pf_timing = false;
+    bool pf_two_pass = false;    // MC_PF_TWO_PASS=1: scores + pv kernels with the probability scratch (always for T = float)
+};
+
+// the three shapes a switch takes: on / off with a default, an integer clamped to [lo, hi], "is it set at all"
+bool
+env_set(const char* name) { return getenv(name) != nullptr; }
+bool
+env_flag(const char* name, bool dflt) { return env_set(name) ? atoi(getenv(name)) != 0 : dflt; }
+int
+env_int(const char* name, int dflt, int lo = INT_MIN, int hi = INT_MAX) { return env_set(name) ? std::max(lo, std::min(hi, atoi(getenv(name)))) : dflt; }
+
+decoder_options
+read_options()
+{
+    decoder_options o;
+    o.gemv_block = env_int("MC_GEMV_BLOCK", o.gemv_block);
+    o.gemv_wgs_per_cu = env_int("MC_GEMV_WGS_PER_CU", o.gemv_wgs_per_cu);
+    o.gemv_block_env = env_set("MC_GEMV_BLOCK") || env_set("MC_GEMV_WGS_PER_CU");
+    if (o.gemv_block % 64 || o.gemv_block < 64 || o.gemv_block > 1024) o.gemv_block = 256;
+    if (o.gemv_wgs_per_cu < 1) o.gemv_wgs_per_cu = 2;
+    o.gemv_lin = env_flag("MC_GEMV_LIN", o.gemv_lin);
+    o.gemv_ling = env_flag("MC_GEMV_LING", o.gemv_ling);
+    o.i8_ling14 = env_flag("MC_I8_LING14", o.i8_ling14);
+    o.lin_split = env_flag("MC_LIN_SPLIT", o.lin_split);
+    o.ling_half = env_flag("MC_LING_HALF", o.ling_half);
+    o.lin_k4_on = env_flag("MC_LIN_K4", o.lin_k4_on);
+    o.lin_waves = env_int("MC_LIN_WAVES", o.lin_waves, 1, 16);
+    o.gemv_full_grid = env_flag("MC_GEMV_FULLGRID", o.gemv_full_grid);
+    o.dbg_variant = env_int("MC_GEMV_DBG", o.dbg_variant);
+    o.gemv_m4 = env_int("MC_GEMV_M4", o.gemv_m4);
+    o.time_gemv_layers = env_int("MC_TIME_GEMV_LAYERS", 0, 0);
+
+    o.attn_fused = env_flag("MC_ATTN_FUSED", o.attn_fused);
+    o.attn_fused_max_wgs_per_cu = (unsigned)env_int("MC_ATTN_FUSED_WGS", (int)o.attn_fused_max_wgs_per_cu, 1, 4);
+    o.attn_t2_on = env_flag("MC_ATTN_T2", o.attn_t2_on);
+    o.rearm_after = env_int("MC_HANDOFF_REARM", o.rearm_after, 0);
+    o.handoff_fast = env_flag("MC_HANDOFF_FAST", o.handoff_fast);
+    o.attn_wo_on = env_flag("MC_ATTN_WO", o.attn_wo_on);
+    o.attn_wo_k4 = env_set("MC_ATTN_WO_K4");
+    o.attn_qkv_on = env_flag("MC_ATTN_QKV", o.attn_qkv_on);
+    o.attn_qkv_only_on = env_flag("MC_ATTN_QKV_ONLY", o.attn_qkv_only_on);
+    o.attn_i8_on = env_flag("MC_ATTN_I8", o.attn_i8_on);
+    o.attn_i4_wide_on = env_flag("MC_ATTN_I4_WIDE", o.attn_i4_wide_on);
+    o.kv_virtual_on = env_flag("MC_KV_VIRTUAL", o.kv_virtual_on);
+    o.chain_w13_on = env_flag("MC_CHAIN_W13", o.chain_w13_on);
+    o.chain_f = env_int("MC_CHAIN_F", o.chain_f, 0);
+    o.attn_qkv_qkn_on = env_flag("MC_ATTN_QKV_QKN", o.attn_qkv_qkn_on);
+    o.attn_wo_qkn_on = env_flag("MC_ATTN_WO_QKN", o.attn_wo_qkn_on);
+    o.attn_qkn_on = env_flag("MC_ATTN_QKN", o.attn_qkn_on);
+    o.gemma_fuse = !env_flag("MC_GEMMA_UNFUSED", !o.gemma_fuse);
+    o.pv_fold_on = env_flag("MC_PV_FOLD", o.pv_fold_on);
+    o.pv_block = env_int("MC_PV_BLOCK", o.pv_block);
+    if (o.pv_block % 64 || o.pv_block < 256 || o.pv_block > 1024) o.pv_block = 1024;
+    o.pv_ranges = env_int("MC_PV_RANGES", o.pv_ranges, 1, 64);
+
+    o.head_pick_mode = env_int("MC_HEAD_PICK", o.head_pick_mode, 0, 2);
+    o.head_pick_on = o.head_pick_mode != 0;
+    o.lazy_pick_on = env_flag("MC_LAZY_PICK", o.lazy_pick_on);
+
+    o.pf2_on = env_flag("MC_PF2", o.pf2_on);
+    o.pf2_wgs_per_cu = env_int("MC_PF2_WGS_PER_CU", o.pf2_wgs_per_cu, 1);
+    o.pf_attn8_on = env_flag("MC_PF_ATTN8", o.pf_attn8_on);
+    o.pf_attn8_rows = env_int("MC_PF_ATTN8_ROWS", o.pf_attn8_rows, 1);
+    o.pf_attn8_rows64 = env_int("MC_PF_ATTN8_ROWS64", o.pf_attn8_rows64, 1);
+    o.pf_attn8_rows256 = env_int("MC_PF_ATTN8_ROWS256", o.pf_attn8_rows256, 1);
+    o.pf_attn_heads = env_int("MC_PF_ATTN_HEADS", o.pf_attn_heads, 0);
+    o.pf_attn8_pair = env_set("MC_PF_ATTN8_PAIR") ? (env_flag("MC_PF_ATTN8_PAIR", false) ? 1 : 0) : -1;
+    o.pf_plain_mode = env_set("MC_PF_PLAIN_COPY") ? (env_flag("MC_PF_PLAIN_COPY", false) ? 1 : 0) : -1;
+    o.pf_rope_pack = env_flag("MC_PF_ROPE_PACK", o.pf_rope_pack);
+    o.pf_g8_on = env_flag("MC_PF_GEMM8", o.pf_g8_on);
+    o.pf_g8_rows = env_int("MC_PF_GEMM8_ROWS", o.pf_g8_rows, 1);
+    o.pf_g8_max_splits = env_int("MC_PF_GEMM8_MAXSPLIT", o.pf_g8_max_splits, 1);
+    o.pf_g8_min_ktiles = env_int("MC_PF_GEMM8_MINKT", o.pf_g8_min_ktiles, 1);
+    o.pf_small_gemm = env_set("MC_PF_SMALL_GEMM");
+    o.pf_depth1 = env_int("MC_PF_DEPTH", 0) == 1;
+    o.pf_bm128 = env_set("MC_PF_BM128");
+    o.pf_splits_old = env_set("MC_PF_SPLITS_OLD");
+    o.pf_no_splitk = env_set("MC_PF_NO_SPLITK");
+    o.pf_fold_on = env_flag("MC_PF_FOLD", o.pf_fold_on);
+    o.pf_norm2 = env_flag("MC_PF_NORM2", o.pf_norm2);
+    o.pf_act_epi = env_flag("MC_PF_ACT_EPI", o.pf_act_epi);
+    o.pf_gelu_table = env_flag("MC_PF_GELU_TABLE", o.pf_gelu_table);
+    const int lib = env_int("MC_PF_BLASLT", 0);
+    o.pf_lib = lib != 0;
+    o.pf_lib_force = lib == 2;
+    o.pf_lib_tune = env_flag("MC_PF_BLASLT_TUNE", o.pf_lib_tune);
+    o.pf_lib_rows = env_int("MC_PF_BLASLT_ROWS", o.pf_lib_rows, 1);
+    o.pf_lib_tiles = env_int("MC_PF_BLASLT_TILES", o.pf_lib_tiles, 1);
+    o.pf_lib_verbose = env_set("MC_PF_BLASLT_VERBOSE");
+    o.pf_timing = env_flag("MC_PF_TIMING", o.pf_timing);
+    o.pf_two_pass = env_flag("MC_PF_TWO_PASS", o.pf_two_pass);
+    return o;
+}
+
 } // namespace
 
 struct mc_decoder {
     mc_decoder_config cfg;
+    decoder_options opt; // the MC_* switches, read once (read_options)
     mc_device* dev = nullptr;
     mc_library* lib = nullptr;
     mc_queue* q = nullptr;
@@ -213,42 +406,15 @@ struct mc_decoder {
     void* hidden_b = nullptr;   // T[dim]   gemma3: the row between the attention and the ffn half of a block
     const void* pending_pn = nullptr; // gemma3: postnorm_args the next pre-norm GEMV has to apply to `proj`
     uint64_t weights_gen = 1;  // bumped whenever weight rows change: the derived copies (linear_w::wq2) are rebuilt
-    bool pf2_on = true;        // MC_PF2: short prompts from the quad-interleaved copy
-    bool attn_i8_on = true;    // MC_ATTN_I8: int8 wq|wk|wv and Wo inside the attention launch (attn_qkv_wo_i8_tiles)
-    bool attn_i4_wide_on = true; // MC_ATTN_I4_WIDE: the int4 block with 128- / 256-slot ranges at S = 4096 / 8192 (attn_qkv_wo_i4_wide_tiles)
-    bool kv_virtual_on = true; // MC_KV_VIRTUAL: fewer than 8 kv heads launched as 8 virtual ones where wq|wk|wv is inside the attention launch (kv_virtual_shift)
-    bool pf_attn8_on = true;   // MC_PF_ATTN8: the prompt attention with K / V tiles through LDS, from pf_attn8_rows rows on
-    int pf_attn8_rows = 1024;  // MC_PF_ATTN8_ROWS
-    int pf_attn8_rows64 = 1793; // MC_PF_ATTN8_ROWS64 (head_dim 64: mc_pf_attn8_bfloat_hd64_h{8,4}; TinyLlama 2048 rows 8.35 against 8.95 ms, Llama-3.2-1B 6.57 against 7.0; 1536 - 1792 rows equal, 1024: 5.1 against 4.9 -- profiles/r06_pf_hd64_attn8_ab.log)
-    int pf_attn8_rows256 = 513; // MC_PF_ATTN8_ROWS256 (head_dim 256: mc_pf_attn8_bfloat_hd256; Gemma-7B shapes: 2048 rows 35.5 against 44.4 ms, 1024: 19.0 against 21.3, 512: equal, 256: 9.0 against 8.85)
-    int pf_plain_mode = -1;    // MC_PF_PLAIN_COPY: 1 = the 256 x 256 prompt GEMM multiplies quantised matrices from their dequantised bfloat16 copy (linear_w::wd, built on
-                               // first use, 2 bytes per weight more HBM: the very values the quantised loop stages in LDS, same loop, same sums bit for bit -- without
-                               // the dequantisation that competes with the MFMAs for the issue port), 0 = from the quantised rows; unset = 1 iff the copies of every
-                               // block's matrices fit an eighth of the device's memory (Llama-3-8B: 14 of 288 GB, yes; 70B: 137 GB, no)
     bool pf_plain_on = false;  // ... resolved when the first long prompt arrives (plain_copy_ok)
     bool pf_plain_known = false;
-    bool pf_rope_pack = true;  // MC_PF_ROPE_PACK (prefill: the rope + cache launch with four rotation pairs per thread)
-    bool pf_g8_on = true;      // MC_PF_GEMM8: prompts of pf_g8_rows rows and more take the 256 x 256 ping-pong GEMM (kernels/pf_gemm8.h)
-    int pf_g8_max_splits = 16, pf_g8_min_ktiles = 8; // MC_PF_GEMM8_MAXSPLIT, MC_PF_GEMM8_MINKT: K ranges of a launch (g8_splits)
-    int pf_g8_rows = 257;      // MC_PF_GEMM8_ROWS: from TWO row tiles on (round 5 measured 256 rows 7.42 ms with, 7.06 without -- one row of tiles leaves half the chip idle -- and 512 rows
-                               // 10.13 against 11.66, and set 384; round 6, on the dequantised copies: 256 rows 6.87 without against 7.65 with, 320 rows 11.2 against 8.95, 383: 11.3 against 9.2 --
-                               // profiles/r06_pf_rows_ab.log)
-    bool pf_lib_on = false;    // MC_PF_BLASLT=1 (opt-in since round 5, a comparison aid): long prompts' large GEMMs in hipBLASLt on a dequantised bfloat16 copy of the matrix (gemm_lib)
-    bool pf_lib_force = false;
-    bool pf_lib_tune = false;  // MC_PF_BLASLT_TUNE=1: the fastest of the heuristic's first eight algorithms, timed once per shape, instead of its first
-                               // (measured: inside the noise -- 512 rows 10.13 / 9.91 ms without, 10.04 / 10.00 with; 2048 rows 32.92 / 33.52, 32.55 / 32.92 --
-                               // and a timed choice would make the order of the fp32 additions differ from run to run: off)
-    int pf_lib_rows = 160;     // MC_PF_BLASLT_ROWS: the shortest prompt chunk whose GEMMs may take the library (measured: 128 rows 5.01 ms without against
-                               // 5.38 with, 160 rows 6.83 / 5.96, 192: 6.91 / 6.33, 224: 7.08 / 6.44 -- profiles/r04_prefill_blaslt.log)
-    int pf_lib_tiles = 48;     // MC_PF_BLASLT_TILES: the fewest 256 x 256 tiles of a launch the library takes (swept on whole prompts: profiles/r04_prefill_blaslt.log)
+    bool pf_lib_on = false;    // opt.pf_lib until the library fails (gemm_lib)
     hipblasLtHandle_t lt = nullptr;
     void* lt_ws = nullptr;
     static constexpr size_t lt_ws_bytes = 64u << 20;
     std::map<std::tuple<int, int, int, int>, blaslt_plan> lt_plans;
     int lt_calls = 0; // library multiplications issued (mc_decoder_launch_log names them "hipblasLtMatmul")
-    bool pf_fold_on = true;    // MC_PF_FOLD: the split-K reduce of a prompt GEMM inside the kernel that consumes its rows
     bool lazy_pick = false;    // inside mc_decoder_generate: the pick of a token is folded by the NEXT token's embedding launch
-    bool lazy_pick_on = true;  // MC_LAZY_PICK
     bool graph_lazy = false;   // the captured token was recorded with lazy_pick
     std::unordered_map<const void*, postnorm_args> pn_host; // the same descriptors on the host (the linear-order kernels take the three pointers as arguments)
     void* qkv = nullptr;        // T[(H+2KV)*hd]
@@ -266,19 +432,8 @@ struct mc_decoder {
     unsigned long long* attn_slab_g = nullptr; // [KV][nsplit][n_rep][hd] fp32 partial P.V sums
     unsigned long long* attn_row_g = nullptr;  // [H * hd / 2]          the finished attention row, two bf16 per granule (mc_attn_wo_*)
     unsigned long long* attn_hid_g = nullptr;  // [dim / 2]             the hidden row behind Wo, for the w1|w3 phase of mc_attn_qkv_wo_w13_w_* (hand-off D)
-    bool chain_w13_on = true;    // MC_CHAIN_W13=0: ffn_norm + w1|w3 + act*mul as a launch of its own behind the plain-weight attention block (A/B, parity)
     int occ_w13 = -1;
     unsigned long long* attn_qkv_g = nullptr;  // [KV][(n_rep + 2) hd / 2] the step's rotated queries and K / V row, two bf16 per granule (mc_attn_qkv_wo_*)
-    // MC_ATTN_QKV_ONLY=1: the 70B shapes' wq|wk|wv GEMV inside the attention launch (mc_attn_qkv_i4_bfloat_hd128_q4).  Built in round 5 as VERDICT r04
-    // item 2 (iv) asked, bit for bit the two launches, and NOT faster: 21.25 us against 11.65 + 9.04 in the trace (profiles/r05_kernel_stats_70b_qkvin.csv),
-    // 127.4 / 127.1 against 128.0 / 127.9 tokens/s alternating on one box -- 160 KB of wq|wk|wv per workgroup are 7 us of multiplication in front of
-    // the first hand-off, which is what the GEMV launch lasts.  Off by default.
-    bool attn_qkv_only_on = false;
-    bool attn_qkv_qkn_on = true; // MC_ATTN_QKV_QKN=0: gemma3's wq|wk|wv GEMV as a launch of its own in front of mc_attn_wo_qkn_* (A/B, parity)
-    bool attn_wo_qkn_on = true;  // MC_ATTN_WO_QKN=0: gemma3's q/k-norm + rope + cache write + attention as mc_attn_fused_qkn_T, Wo as a GEMV of its own (A/B, parity)
-    bool attn_qkn_on = true;     // MC_ATTN_QKN=0: gemma3's q/k-norm + rope + cache write as a launch of their own (mc_rope_kv_T) in front of the attention (A/B, parity)
-    bool lin_k4_on = true;       // MC_LIN_K4=0: Gemma-7B's w2 on the one-pair-per-wave kernel (mc_gemv_i4_bfloat_lin12_*) instead of the K-split one (A/B, parity)
-    bool attn_qkv_on = true;     // MC_ATTN_QKV=0: wq|wk|wv as a launch of its own in front of mc_attn_wo_* (A/B, parity)
     // ---- what happens when an in-launch hand-off gives up (its workgroups were not resident together: another stream or process
     // holds part of the chip).  The launch sets state.err and completes; the host then LATCHES the decoder onto the launches
     // that need no co-residency (attn_fused_on = false: scores, P.V and the GEMVs as launches of their own), drops the captured
@@ -292,12 +447,11 @@ struct mc_decoder {
     // ... and the fall-back is TEMPORARY (round 6): one transient stall (another stream holding CUs for 50 ms, a profiler pass) must not cost every
     // later token the one-launch blocks.  After `rearm_after` tokens without a hand-off launch the decoder takes them again (mc_decoder_handoff_rearms counts);
     // every further fall-back doubles the distance (a chip that is shared for good settles on the launches that need no co-residency), MC_HANDOFF_REARM=0: never
-    bool attn_fused_cfg = true;  // what the configuration asked for (MC_ATTN_FUSED)
     int rearm_after = 256, clean_tokens = 0, handoff_rearms = 0;
     void
     note_clean_tokens(int n)
     {
-        if (attn_fused_on || !attn_fused_cfg || rearm_after <= 0) return;
+        if (attn_fused_on || !opt.attn_fused || rearm_after <= 0) return;
         clean_tokens += n;
         if (clean_tokens < rearm_after) return;
         attn_fused_on = true;
@@ -306,14 +460,7 @@ struct mc_decoder {
         drop_graph(); // (captured with the launches that need no co-residency)
     }
     int occ_fused = -1, occ_wo = -1, occ_wo_w = -1, occ_wo_i8 = -1, occ_wo_qkn = -1, occ_qkv_qkn = -1, occ_qkv_only = -1, occ_wo_i4_wide = -1;   // co-resident workgroups per CU of the hand-off launches (the occupancy API's answer; -1: not asked yet)
-    bool handoff_fast = true;    // MC_HANDOFF_FAST=0: hand-offs A and B through the fabric only (A/B; handoff.h "the XCD-local fast path")
-    bool attn_wo_on = true;      // MC_ATTN_WO=0: the Wo GEMV as a launch of its own behind the one-launch attention (A/B, parity)
-    bool attn_fused_on = true;   // MC_ATTN_FUSED=0: scores and P.V as two launches (A/B, parity)
-    // ... while the launch is at most this many 256-thread workgroups per CU (MC_ATTN_FUSED_WGS).  Measured: at S = 8192 with
-    // 64-slot ranges (128 ranges x 8 kv heads = 4 per CU, every hand-off gathering from 128 producers) the one launch took 27.8 us
-    // against 6.3 + 8.5 for the two -- long contexts keep the two-launch form (wider ranges were built and measured no better)
-    unsigned attn_fused_max_wgs_per_cu = 2;
-    bool attn_t2_on = true; // MC_ATTN_T2
+    bool attn_fused_on = true;   // opt.attn_fused, until a hand-off gives up (handoff_failed) and again after rearm_after clean tokens (note_clean_tokens)
     void* taps = nullptr;       // T[(n_own+1)*dim]
     step_state* state = nullptr;
     int32_t* tokens_dev = nullptr;
@@ -323,10 +470,6 @@ struct mc_decoder {
     char* pick_desc = nullptr;
     unsigned long long* pick_keys = nullptr; // MC_HEAD_PICK=2: one key per workgroup of the head's launch, folded by mc_argmax_keys
     static constexpr unsigned pick_slots = 1024;
-    int head_pick_mode = 2;
-    bool head_pick_on = true;    // MC_HEAD_PICK: 0 = mc_argmax_T behind the head (round 1); 1 = the pick wholly inside the head's launch (atomic max
-                                 // + ticket per workgroup: parity-green, 1448 vs 1449 us per token -- the atomics cost what the launch costs);
-                                 // 2 = one key per workgroup + mc_argmax_keys, a one-workgroup launch over 8 KB instead of 256 KB of logits
     int tokens_cap = 0;
     // sampler (nn/sampling.h:303-313); kind 0 = greedy argmax, 1 = topk -> nucleus -> multinomial
     int sampler_kind = MC_SAMPLER_GREEDY;
@@ -350,17 +493,13 @@ struct mc_decoder {
     size_t pf_part_elems = 0;
     bool ring_turned = false;
     void *rot_k = nullptr, *rot_v = nullptr; // scratch of mc_kv_rotate (one layer's K and Vt)
-    // MC_PF_TIMING=1: per-category GPU time of a prompt pass printed to stderr (tuning aid; it
-    // synchronises after every launch)
-    bool pf_timing = false;
-    bool pf_two_pass = false; // MC_PF_TWO_PASS=1: scores + pv kernels with the probability scratch (always for T = float)
     hipEvent_t pf_e0 = nullptr, pf_e1 = nullptr;
     std::map<std::string, double> pf_ms;
 
     template <typename F> mc_status
     timed(const char* cat, F&& f)
     {
-        if (!pf_timing) return f();
+        if (!opt.pf_timing) return f();
         if (!pf_e0) {
             MC_HIP(hipEventCreate(&pf_e0));
             MC_HIP(hipEventCreate(&pf_e1));
@@ -387,21 +526,6 @@ struct mc_decoder {
     hipGraphExec_t graph_exec = nullptr;
 
     std::vector<void*> allocs;
-    int gemv_block = 256;
-    int gemv_wgs_per_cu = 2;
-    bool gemv_lin = true;        // MC_GEMV_LIN=0: classic kernels everywhere (A/B)
-    bool gemv_ling = true;       // MC_GEMV_LING=0: int8 / bfloat weights on the classic kernels (A/B)
-    bool i8_ling14 = true;       // MC_I8_LING14=0: int8 rows of 14 KiB (w2 of Llama-3-8B) on the classic kernel (A/B)
-    bool lin_split = true;       // MC_LIN_SPLIT=0: K = 3072 on the classic kernels (A/B)
-    bool ling_half = true;       // MC_LING_HALF=0: whole row pairs per wave whatever the matrix (A/B)
-    bool pv_fold_on = true;      // MC_PV_FOLD=0: P.V ranges reduced by their own launch (A/B, parity)
-    int lin_waves = 8;           // MC_LIN_WAVES: tuning builds of the linear-order kernels with another workgroup size
-    bool gemv_block_env = false; // MC_GEMV_BLOCK / MC_GEMV_WGS_PER_CU given: they apply to every kernel of the family
-    bool gemv_full_grid = false; // MC_GEMV_FULLGRID=1: as many workgroups as CUs allow even when that leaves waves without a row group (kernels built with MC_GEMV_WAVEMAJOR)
-    int dbg_variant = 0; // MC_GEMV_DBG=1 stream-only, 2 compute-only (tuning ablations)
-    int pv_block = 1024;   // MC_PV_BLOCK: threads of a P.V workgroup (16 waves: one round of loads per wave at S = 2048)
-    int gemv_m4 = 2;       // MC_GEMV_M4: 0 = exact int4 on the VALU (v_dot2c), 1 = dot products on the 4x4x4 MFMA, 2 = dequantisation too where a SIMD holds > 1 wave, 3 = always
-    bool gemma_fuse = true; // MC_GEMMA_UNFUSED=1: keep the post-norms as launches of their own
     bool pn_ready = false;
     // test / measurement aids: the names of the kernels launched eagerly since the log was switched on (a replayed graph
     // launches what was logged when it was captured), and "tell me the kernel gemv() would launch" (no launch)
@@ -621,30 +745,30 @@ struct mc_decoder {
     bool
     lin_ok(const linear_w& L) const
     {
-        const bool m4 = L.fmt == MC_WFMT_I4 && tb == 2 && cfg.qmode == MC_QMODE_EXACT && gemv_m4 && !dbg_variant;
+        const bool m4 = L.fmt == MC_WFMT_I4 && tb == 2 && cfg.qmode == MC_QMODE_EXACT && opt.gemv_m4 && !opt.dbg_variant;
         const bool m4d_ok = m4 && (L.group == 0 || L.group % 128 == 0) && L.in % 128 == 0;
         const int nch = L.in % 2048 == 0 ? L.in / 2048 : 0;
-        return gemv_lin && m4d_ok && L.out % 4 == 0 && (nch == 1 || nch == 2 || nch == 4 || nch == 7 || nch == 12 || nch == 14);
+        return opt.gemv_lin && m4d_ok && L.out % 4 == 0 && (nch == 1 || nch == 2 || nch == 4 || nch == 7 || nch == 12 || nch == 14);
     }
     // ... rows of 1.5 KiB (K = 3072: Gemma-7B's QKV and w1|w3), two to a 3 KiB super row (gemv.h LSPLIT, `_lin3s_`)
     bool
     lin_split_ok(const linear_w& L) const
     {
-        const bool m4 = L.fmt == MC_WFMT_I4 && tb == 2 && cfg.qmode == MC_QMODE_EXACT && gemv_m4 && !dbg_variant;
-        return gemv_lin && lin_split && m4 && L.group == 128 && L.in == 3072 && L.out % 4 == 0 && lin_waves == 8 && !L.lora_cols;
+        const bool m4 = L.fmt == MC_WFMT_I4 && tb == 2 && cfg.qmode == MC_QMODE_EXACT && opt.gemv_m4 && !opt.dbg_variant;
+        return opt.gemv_lin && opt.lin_split && m4 && L.group == 128 && L.in == 3072 && L.out % 4 == 0 && opt.lin_waves == 8 && !L.lora_cols;
     }
     // ... or the linear-order kernels of the VALU-dequantising formats (gemv.h LGEN): int8 / plain bfloat weights on
     // bfloat rows, rows of 4 / 14 (int8) or 4 / 8 / 11 / 16 (bfloat) whole KiB; returns that count, 0 = no
     int
     ling_kib(const linear_w& L) const
     {
-        if (!gemv_lin || !gemv_ling || tb != 2 || dbg_variant || L.out % 4 != 0) return 0;
+        if (!opt.gemv_lin || !opt.gemv_ling || tb != 2 || opt.dbg_variant || L.out % 4 != 0) return 0;
         const size_t rb = row_bytes(L.fmt, L.in);
         if (rb % 1024) return 0;
         const int n = (int)(rb / 1024);
         if (L.fmt == MC_WFMT_I8) {
             const bool g_ok = L.group == 0 || (L.group % 16 == 0 && (L.group & (L.group - 1)) == 0);
-            return g_ok && (n == 4 || (n == 14 && i8_ling14)) ? n : 0;
+            return g_ok && (n == 4 || (n == 14 && opt.i8_ling14)) ? n : 0;
         }
         if (L.fmt == MC_WFMT_T) return (n == 4 || n == 8 || n == 11 || n == 16) ? n : 0;
         return 0;
@@ -655,22 +779,28 @@ struct mc_decoder {
     bool
     pv_fold(const linear_w& wo) const
     {
-        return pv_fold_on && (lin_ok(wo) || ling_kib(wo)) && !wo.lora_cols && cfg.max_seq_len <= 16384;
+        return opt.pv_fold_on && (lin_ok(wo) || ling_kib(wo)) && !wo.lora_cols && cfg.max_seq_len <= 16384;
     }
 
+    // ---------------------------------------------------------------- the decode attention block: which launches (plan_block)
+    // The gates every launch with an in-launch hand-off shares: the switch (MC_ATTN_FUSED, and the latch of handoff_failed), bfloat rows -- the granule
+    // buffers attn_psum_g / attn_slab_g / attn_row_g / attn_qkv_g / attn_hid_g exist for them only, all or none (mc_decoder_create) -- and layer tags of one byte
+    bool
+    handoffs_ok() const { return attn_fused_on && attn_psum_g && tb == 2 && n_own <= 254; }
+    // 256-thread attention workgroups per CU that may wait for one another.
+    // Co-residency from what a CU can HOLD of the real kernel (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor, asked once:
+    // query_occupancy), capped by what was measured to pay (opt.attn_fused_max_wgs_per_cu).  The API is advisory (ROCm 7.2 reads
+    // one block per CU high for SGPR-heavy 256-thread kernels, MI355X_MICROARCH.md), and another stream can take CUs away
+    // at any time: a launch that is not resident after all gives up and the host falls back (handoff_failed).
+    unsigned
+    fused_wgs_per_cu() const { return std::min(opt.attn_fused_max_wgs_per_cu, occ_fused < 0 ? opt.attn_fused_max_wgs_per_cu : (unsigned)occ_fused); }
     // scores + softmax + P.V in one launch: bfloat rows, layer tags of one byte, and a grid that is certainly co-resident (its
-    // workgroups wait for one another) and gathers from few producers: at most attn_fused_max_wgs_per_cu 256-thread workgroups
+    // workgroups wait for one another) and gathers from few producers: at most opt.attn_fused_max_wgs_per_cu 256-thread workgroups
     // of 64 cache slots per CU
     bool
     attn_fused() const
     {
-        // co-residency from what a CU can HOLD of the real kernel (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor, asked once:
-        // query_occupancy), capped by what was measured to pay (attn_fused_max_wgs_per_cu).  The API is advisory (ROCm 7.2 reads
-        // one block per CU high for SGPR-heavy 256-thread kernels, MI355X_MICROARCH.md), and another stream can take CUs away
-        // at any time: a launch that is not resident after all gives up and the host falls back (handoff_failed).
-        const unsigned per_cu = std::min(attn_fused_max_wgs_per_cu, occ_fused < 0 ? attn_fused_max_wgs_per_cu : (unsigned)occ_fused);
-        return attn_fused_on && attn_psum_g && tb == 2 && n_own <= 254 &&
-               (unsigned)(nsplit * cfg.n_kv_heads) <= per_cu * (unsigned)dev->prop.multiProcessorCount;
+        return handoffs_ok() && (unsigned)(nsplit * cfg.n_kv_heads) <= fused_wgs_per_cu() * (unsigned)dev->prop.multiProcessorCount;
     }
     // ... with 128-slot ranges (mc_attn_fused_t2_bfloat: two score tiles per wave) where the 64-slot ranges are too many workgroups to
     // be resident together -- Llama-3-8B at S = 8192: 1024 -> 512.  Round 3 measured that form at 14.8 us against 6.3 + 8.5 for
@@ -678,10 +808,9 @@ struct mc_decoder {
     bool
     attn_fused_t2() const
     {
-        const unsigned per_cu = std::min(attn_fused_max_wgs_per_cu, occ_fused < 0 ? attn_fused_max_wgs_per_cu : (unsigned)occ_fused);
-        return attn_t2_on && attn_fused_on && attn_psum_g && tb == 2 && n_own <= 254 && !attn_fused() && nsplit % 2 == 0 &&
+        return opt.attn_t2_on && handoffs_ok() && !attn_fused() && nsplit % 2 == 0 &&
                (cfg.head_dim == 128 || cfg.head_dim == 64) && cfg.n_kv_heads % 8 == 0 &&
-               (unsigned)(nsplit / 2 * cfg.n_kv_heads) <= per_cu * (unsigned)dev->prop.multiProcessorCount;
+               (unsigned)(nsplit / 2 * cfg.n_kv_heads) <= fused_wgs_per_cu() * (unsigned)dev->prop.multiProcessorCount;
     }
     void
     query_occupancy()
@@ -714,7 +843,7 @@ struct mc_decoder {
     {
         (void)hipMemsetAsync(&state->err, 0, 4, stream);
         (void)hipStreamSynchronize(stream);
-        attn_fused_on = false; // (attn_wo_fused and attn_qkv_wo_fused need attn_fused)
+        attn_fused_on = false; // (handoffs_ok: every form of plan_block with a hand-off needs it)
         drop_graph();
         handoff_fallbacks++;
         clean_tokens = 0;
@@ -727,43 +856,13 @@ struct mc_decoder {
     bool
     attn_wo_fused(const linear_w& wo) const
     {
-        if (!attn_wo_on || !attn_fused() || occ_wo == 0 || !lin_ok(wo) || wo.lora_cols || wo.out % 2 != 0) return false;
+        if (!opt.attn_wo_on || !attn_fused() || occ_wo == 0 || !lin_ok(wo) || wo.lora_cols || wo.out % 2 != 0) return false;
         const int hd = cfg.head_dim, k = wo.in / 2048;
         // (K = 8192, Llama-3-70B: measured slower than the two launches -- attn_block_kernels.hip)
-        const bool built = (hd == 128 && k == 2) || (hd == 64 && k == 1) || (hd == 256 && k == 2) || (hd == 128 && k == 4 && getenv("MC_ATTN_WO_K4"));
+        const bool built = (hd == 128 && k == 2) || (hd == 64 && k == 1) || (hd == 256 && k == 2) || (hd == 128 && k == 4 && opt.attn_wo_k4);
         // (one 512-thread workgroup per CU: the kernels hold up to 132 VGPRs, two such workgroups would not be resident together)
         return built && wo.in == cfg.n_heads * hd && (unsigned)wo.out / 2 <= 2u * 8u * (unsigned)(nsplit * cfg.n_kv_heads) &&
                (unsigned)(nsplit * cfg.n_kv_heads) <= (unsigned)dev->prop.multiProcessorCount;
-    }
-
-    // gemma3 (round 5): q_norm / k_norm + rotation + cache write + attention + Wo in ONE launch from the raw wq|wk|wv rows
-    // (mc_attn_wo_qkn_i4_bfloat_hd256_k2_t{1,2,4}: one 512-thread workgroup per CU, ranges of 64, 128 or 256 slots -- Gemma-7B's 16 kv heads at
-    // S = 2048 are 16 x 16).  Returns the 64-slot tiles per range, 0: not this form.
-    int
-    attn_wo_qkn_tiles(const linear_w& wo) const
-    {
-        if (!attn_wo_qkn_on || !attn_wo_on || !attn_qkn_on || !attn_fused_on || !attn_psum_g || !attn_row_g || tb != 2 || n_own > 254) return 0;
-        if (cfg.family != MC_FAMILY_GEMMA3 || cfg.head_dim != 256 || occ_wo_qkn == 0 || !lin_ok(wo) || wo.lora_cols || wo.out % 2 != 0) return 0;
-        if (wo.in != 4096 || wo.in != cfg.n_heads * cfg.head_dim || cfg.n_heads / cfg.n_kv_heads > 16) return 0;
-        for (int tiles = 1; tiles <= 4; tiles *= 2) { // (64-, 128-, 256-slot ranges: S = 1024, 2048, 4096 at Gemma-7B's 16 kv heads)
-            if (nsplit % tiles != 0 || cfg.max_seq_len % (64 * tiles) != 0) continue;
-            const unsigned grid = (unsigned)(nsplit / tiles * cfg.n_kv_heads);
-            if (grid <= (unsigned)dev->prop.multiProcessorCount && (unsigned)wo.out / 2 <= 2u * 8u * grid) return tiles;
-        }
-        return 0;
-    }
-
-    // ... with wq|wk|wv and the block's norms in the launch too (mc_attn_qkv_wo_qkn_i4_bfloat_hd256_k2_p{1,2}_t2, attn_block_kernels.hip
-    // qkv_qkn_in_launch): rows of 1.5 KiB (K = 3072), the kv head's (n_rep + 2) hd / 2 rotation pairs dealt evenly over its ranges, at most
-    // three per wave, one thread per pair in the hand-off
-    bool
-    attn_qkv_wo_qkn_ok(const layer_w& L) const
-    {
-        const int tiles = attn_wo_qkn_tiles(L.wo);
-        if (!attn_qkv_qkn_on || !attn_qkv_on || !attn_qkv_g || occ_qkv_qkn == 0 || tiles == 0) return false;
-        if (!lin_split_ok(L.qkv) || L.qkv.lora_cols || L.qkv.in != 3072 || cfg.dim != 3072 || L.qkv.group != L.wo.group) return false;
-        const int hd = cfg.head_dim, n_rep = cfg.n_heads / cfg.n_kv_heads, pg = (n_rep + 2) * hd / 2, ns = nsplit / tiles;
-        return L.qkv.out == (cfg.n_heads + 2 * cfg.n_kv_heads) * hd && pg <= 512 && pg % ns == 0 && pg / ns <= 24;
     }
 
     // The XCD-local fast path of hand-offs A / B / Q (handoff.h) pays where the workgroups of one kv head CAN share an XCD: they
@@ -771,10 +870,7 @@ struct mc_decoder {
     // TinyLlama's 4 kv heads half of every head's ranges sit on another XCD and are found only by the occasional look at the
     // fabric copy: mc_attn_fused_bfloat 24.1 us against 7.0 without the fast path (profiles/r04_kernel_stats_tinyllama_fastpath_regression.csv)
     bool
-    handoff_fast_here() const
-    {
-        return handoff_fast && cfg.n_kv_heads % 8 == 0;
-    }
+    handoff_fast_here() const { return opt.handoff_fast && cfg.n_kv_heads % 8 == 0; }
     // ... and for the launches that are the attention ALONE (mc_attn_fused_T: no GEMV phase that needs every workgroup of the
     // grid) any other head count is dealt with a stride of the next multiple of 8 -- bit 1 of the kernel's `fastpath` argument; the
     // grid is nsplit x that stride and the workgroups without a head leave at once -- when the heads that then share an XCD
@@ -782,36 +878,11 @@ struct mc_decoder {
     uint32_t
     handoff_mode_alone() const
     {
-        if (!handoff_fast) return 0u;
+        if (!opt.handoff_fast) return 0u;
         const unsigned KV = (unsigned)cfg.n_kv_heads;
         if (KV % 8u == 0u) return 1u;
-        const unsigned per_cu = std::min(attn_fused_max_wgs_per_cu, occ_fused < 0 ? attn_fused_max_wgs_per_cu : (unsigned)occ_fused);
-        const bool fits = (unsigned)nsplit * ((KV + 7u) / 8u) <= per_cu * (unsigned)dev->prop.multiProcessorCount / 8u;
+        const bool fits = (unsigned)nsplit * ((KV + 7u) / 8u) <= fused_wgs_per_cu() * (unsigned)dev->prop.multiProcessorCount / 8u;
         return fits ? 3u : 0u;
-    }
-
-    // ... with wq|wk|wv in the same launch too (attn_block_kernels.hip qkv_in_launch): the built shape, the kv head's
-    // (n_rep + 2) hd / 2 row pairs dealt evenly over its nsplit workgroups, at most two per wave
-    bool
-    attn_qkv_wo_fused(const layer_w& L) const
-    {
-        if (!attn_qkv_on || !attn_qkv_g || !attn_wo_fused(L.wo) || !lin_ok(L.qkv) || L.qkv.lora_cols || cfg.family == MC_FAMILY_GEMMA3) return false;
-        const int hd = cfg.head_dim, n_rep = cfg.n_heads / cfg.n_kv_heads, pg = (n_rep + 2) * hd / 2;
-        const bool built = hd == 128 && L.wo.in == 4096 && L.qkv.in == 4096;
-        return built && L.qkv.group == L.wo.group && pg % nsplit == 0 && pg / nsplit <= 16 && n_rep <= 16 &&
-               L.qkv.out == (cfg.n_heads + 2 * cfg.n_kv_heads) * hd && pg >= 64 && pg <= 512;
-    }
-
-    // ... WITHOUT Wo (round 5, mc_attn_qkv_i4_bfloat_hd128_q4: Llama-3-70B -- its Wo rows of 4 KiB stay a GEMV, attn_wo_fused): rows of 4 KiB for
-    // wq|wk|wv too (K = 8192), up to three pairs per wave, the kv head's pairs gathered in two passes of 512
-    bool
-    attn_qkv_only_ok(const layer_w& L) const
-    {
-        if (!attn_qkv_on || !attn_qkv_only_on || !attn_qkv_g || !attn_fused() || tb != 2 || cfg.family == MC_FAMILY_GEMMA3 || occ_qkv_only == 0) return false;
-        if (!lin_ok(L.qkv) || L.qkv.lora_cols || L.qkv.in != 8192 || cfg.dim != 8192 || cfg.head_dim != 128 || cfg.n_kv_heads % 8 != 0) return false;
-        const int hd = cfg.head_dim, n_rep = cfg.n_heads / cfg.n_kv_heads, pg = (n_rep + 2) * hd / 2;
-        return (unsigned)(nsplit * cfg.n_kv_heads) <= (unsigned)dev->prop.multiProcessorCount && n_rep <= 16 && pg <= 1024 && pg % nsplit == 0 &&
-               pg / nsplit <= 24 && pg / nsplit >= 8 && L.qkv.out == (cfg.n_heads + 2 * cfg.n_kv_heads) * hd;
     }
 
     // VIRTUAL kv heads of the launches with wq|wk|wv inside (decode_kernels.hip attn_fused_bf, kv_shift): a model with 1, 2 or 4 kv heads is
@@ -821,49 +892,44 @@ struct mc_decoder {
     kv_virtual_shift() const
     {
         const int KV = cfg.n_kv_heads, n_rep = cfg.n_heads / KV;
-        if (!kv_virtual_on || KV >= 8 || 8 % KV != 0 || n_rep % (8 / KV) != 0) return 0;
+        if (!opt.kv_virtual_on || KV >= 8 || 8 % KV != 0 || n_rep % (8 / KV) != 0) return 0;
         return KV == 4 ? 1 : (KV == 2 ? 2 : 3);
     }
-    // ... the same launch for PLAIN bfloat weights (mc_attn_qkv_wo_w_bfloat_hd64_k4_q4: Llama-3.2-1B, the reference's default model):
-    // rows of 4 KiB (K = 2048), at most ONE row pair per wave in either GEMV phase
-    bool
-    attn_qkv_wo_w_fused(const layer_w& L) const { return attn_qkv_wo_w_tiles(L) != 0; }
-    // ... as the 64-slot tiles per range: 1 (S <= 2048), 2 or 4 (round 5: S = 4096 / 8192 with 128- / 256-slot ranges, mc_attn_qkv_wo_w_*_t{2,4}); 0 = not this form
-    int
-    attn_qkv_wo_w_tiles(const layer_w& L) const
+
+    // The row-pair deal of the launches with wq|wk|wv inside: a kv head's (n_rep + 2) hd / 2 row pairs of wq|wk|wv (its query heads' rows, its K and
+    // its V row) go evenly over the head's `ns` workgroups, at most `cap` to each
+    static bool
+    deal_ok(int pg, int ns, int cap) { return pg % ns == 0 && pg / ns <= cap; }
+    // The fewest 64-slot tiles per range among `cands` with WHOLE ranges (nsplit / t of them per head, `heads` heads) on at most one workgroup per
+    // CU that `ok(t, ns, grid)` takes; 0 = none.
+    // (wide ranges of a cache that is not whole ranges long -- S = 4040 -- would leave a ragged last range: refused here; the form such a
+    //  context takes instead is pinned by tests/test_context_gpu.py::test_contexts_of_partial_ranges_against_the_oracle_and_the_form_they_take.
+    //  64-slot ranges with a short last one are taken: tests/test_attn_kernels_gpu.py runs them at S = 2040)
+    template <typename F> int
+    whole_range_tiles(std::initializer_list<int> cands, int heads, F&& ok) const
     {
-        if (!attn_qkv_on || !attn_wo_on || !attn_qkv_g || !attn_fused_on || !attn_psum_g || n_own > 254 || tb != 2 || cfg.family == MC_FAMILY_GEMMA3) return 0;
-        if (L.qkv.fmt != MC_WFMT_T || L.wo.fmt != MC_WFMT_T || L.qkv.lora_cols || L.wo.lora_cols || occ_wo_w == 0) return 0;
-        const int sh = kv_virtual_shift();
-        const int hd = cfg.head_dim, n_rep = (cfg.n_heads / cfg.n_kv_heads) >> sh, pg = (n_rep + 2) * hd / 2;
-        if (hd != 64 || L.wo.in != 2048 || L.qkv.in != 2048 || L.wo.in != cfg.n_heads * hd || L.wo.out % 2 != 0 ||
-            L.qkv.out != (cfg.n_heads + 2 * cfg.n_kv_heads) * hd || n_rep > 16 || pg < 64 || pg > 512)
-            return 0;
-        for (int t : {1, 2, 4}) {
-            // (wide ranges of a cache that is not whole ranges long -- S = 4040 -- would leave a ragged last range: refused here; the form such a
-            //  context takes instead is pinned by tests/test_context_gpu.py::test_contexts_of_partial_ranges_against_the_oracle_and_the_form_they_take.
-            //  64-slot ranges with a short last one are taken: tests/test_attn_kernels_gpu.py runs them at S = 2040)
-            if (nsplit % t || (t > 1 && cfg.max_seq_len % (64 * t)) || (t == 1 && !attn_fused()) || (t > 1 && !attn_i4_wide_on)) continue;
+        for (int t : cands) {
+            if (nsplit % t || (t > 1 && cfg.max_seq_len % (64 * t))) continue;
             const int ns = nsplit / t;
-            const unsigned grid = (unsigned)(ns * (cfg.n_kv_heads << sh));
-            if (grid <= (unsigned)dev->prop.multiProcessorCount && pg % ns == 0 && pg / ns <= 8 && (unsigned)L.wo.out / 2 <= 8u * grid) return t;
+            const unsigned grid = (unsigned)(ns * heads);
+            if (grid <= (unsigned)dev->prop.multiProcessorCount && ok(t, ns, grid)) return t;
         }
         return 0;
     }
 
-    // ... AND ffn_norm + w1|w3 + act*mul as the next phase of that launch (round 6, mc_attn_qkv_wo_w13_w_bfloat_hd64_k4_q4_f{3p3,4p4}, attn_block_kernels.hip):
+    // ffn_norm + w1|w3 + act*mul as the next phase of the plain-weight block's launch (round 6, mc_attn_qkv_wo_w13_w_bfloat_hd64_k4_q4_f{3p3,4p4}, attn_block_kernels.hip):
     // behind the Wo phase half the waves of every workgroup fetch w1|w3 row pairs into registers while the other half waits for the hidden row.
-    // 64-slot ranges, exactly one workgroup per CU, w1|w3 plain bfloat with K = 2048, no adaptor.  Returns 10 F + P (pairs per fetcher wave, most pairs of a poller wave), 0 = no.
+    // For that block with 64-slot ranges on `grid` workgroups: exactly one workgroup per CU, w1|w3 plain bfloat with K = 2048, no adaptor.
+    // Returns 10 F + P (pairs per fetcher wave, most pairs of a poller wave), 0 = no.
     int
-    attn_qkv_wo_w13_w_fetch(const layer_w& L) const
+    chain_w13_fetch(const layer_w& L, unsigned grid) const
     {
-        if (!chain_w13_on || !attn_hid_g || occ_w13 <= 0 || attn_qkv_wo_w_tiles(L) != 1 || L.w13.fmt != MC_WFMT_T || L.w13.lora_cols) return 0;
-        const unsigned grid = (unsigned)(nsplit * (cfg.n_kv_heads << kv_virtual_shift()));
-        if (cfg.dim != 2048 || L.w13.in != 2048 || L.w13.out % 2 || grid != (unsigned)dev->prop.multiProcessorCount || lin_waves != 8) return 0;
+        if (!opt.chain_w13_on || occ_w13 <= 0 || L.w13.fmt != MC_WFMT_T || L.w13.lora_cols) return 0;
+        if (cfg.dim != 2048 || L.w13.in != 2048 || L.w13.out % 2 || grid != (unsigned)dev->prop.multiProcessorCount || opt.lin_waves != 8) return 0;
         const unsigned nb = ((unsigned)L.w13.out / 2 + grid - 1) / grid; // pairs of the fullest workgroup
         // (the fetchers F each, the pollers the rest, at most P each.  Returns 10 F + P.)
         unsigned f = nb <= 24u ? 3u : 4u;
-        if (const char* e = getenv("MC_CHAIN_F")) f = (unsigned)atoi(e); // (tuning: tools/ab_case_multi.sh)
+        if (opt.chain_f >= 0) f = (unsigned)opt.chain_f; // (MC_CHAIN_F)
         if (f < 1u || 4u * f > nb) return 0;
         const unsigned p_ = (nb - 4u * f + 3u) / 4u; // the fullest poller
         // built: f3p3 (22 pairs per workgroup: TinyLlama) and f4p4 (32: Llama-3.2-1B) -- the even deals, the measured best (attn_block_kernels.hip)
@@ -871,47 +937,157 @@ struct mc_decoder {
         return pcap && p_ <= pcap ? (int)(10u * f + pcap) : 0;
     }
 
-    // ... the same launch for INT8 weights (round 5, mc_attn_qkv_wo_i8_bfloat_hd128_k4_q4_t{1,4}: Llama-3-8B int8): rows of 4 KiB (K = 4096),
-    // one 512-thread workgroup per CU -- 64-slot ranges up to S = 2048 (t1), 256-slot ranges at S = 8192 (t4: 32 ranges x 8 kv heads).
-    // Returns the 64-slot tiles per scoring wave (1 or 4), 0 = not this form.
-    int
-    attn_qkv_wo_i8_tiles(const layer_w& L) const
+    // What run_layers() launches for the first half of one block -- from the row handed to the block to the finished attention row, or past Wo
+    // where the form holds it.  Computed per layer per eager step: the fall-back latch (handoff_failed), the re-arm (note_clean_tokens), taps and a
+    // late occupancy answer all change it between tokens.
+    enum class block_form { // (by the numbers of plan_block's list)
+        qkv_wo_w13_w, qkv_wo_w, qkv_wo_i8, qkv_wo_i4 /* 4, 5 */, qkv_only, qkv_wo_qkn /* 8 */,
+        wo_qkn, wo_i4, fused, fused_qkn, fused_t2, scores_pv // 7, 9 -- wq|wk|wv as a GEMV -- by their attention tail a - e
+    };
+    struct block_plan {
+        block_form form = block_form::scores_pv;
+        std::string name;     // the kernel of the form's attention launch
+        int tiles = 1, vsh = 0, ns = 1; // 64-slot tiles per range; log2 of the virtual kv heads per cache head (kv_virtual_shift); ranges per kv head: nsplit / tiles
+        unsigned grid = 0;    // workgroups of that launch
+        uint32_t fast = 0;    // its `fastpath` argument (handoff.h)
+        int chain_f = 0, chain_p = 0; // qkv_wo_w13_w: pairs per fetcher wave, most pairs of a poller wave
+        bool qkv_gemv = false, rope_kv = false; // wq|wk|wv is a GEMV in front of the launch (7, 9); ... and gemma3's q/k-norm + rope + cache write a launch of their own (mc_rope_kv_T) behind it
+        bool wo_gemv = false, pv_fold = false;  // Wo is a GEMV behind the launch; ... whose prologue adds the range sums of P.V (pv_fold)
+    };
+    block_plan
+    plan_block(const layer_w& L) const
     {
-        if (!attn_qkv_on || !attn_wo_on || !attn_i8_on || !attn_fused_on || !attn_qkv_g || !attn_psum_g || tb != 2 || n_own > 254 || cfg.family == MC_FAMILY_GEMMA3) return 0;
-        if (L.qkv.fmt != MC_WFMT_I8 || L.wo.fmt != MC_WFMT_I8 || L.qkv.lora_cols || L.wo.lora_cols || occ_wo_i8 == 0) return 0;
-        auto group_ok = [](const linear_w& W) { return W.group == 0 || (W.group >= 16 && (W.group & (W.group - 1)) == 0); };
-        if (!group_ok(L.qkv) || !group_ok(L.wo) || L.qkv.group != L.wo.group) return 0;
-        const int hd = cfg.head_dim, n_rep = cfg.n_heads / cfg.n_kv_heads, pg = (n_rep + 2) * hd / 2;
-        if (hd != 128 || L.wo.in != 4096 || L.qkv.in != 4096 || L.wo.in != cfg.n_heads * hd || L.wo.out % 2 != 0 ||
-            L.qkv.out != (cfg.n_heads + 2 * cfg.n_kv_heads) * hd || cfg.n_kv_heads % 8 != 0 || n_rep > 16)
-            return 0;
-        for (int t : {1, 2, 4}) {
-            if (nsplit % t || (t > 1 && cfg.max_seq_len % (64 * t))) continue; // (whole ranges only: attn_qkv_wo_w_tiles)
-            const int ns = nsplit / t;
-            const unsigned grid = (unsigned)(ns * cfg.n_kv_heads);
-            if (grid <= (unsigned)dev->prop.multiProcessorCount && pg % ns == 0 && pg / ns <= 16 && (unsigned)L.wo.out / 2 <= 8u * grid) return t;
-        }
-        return 0;
-    }
+        // The forms in priority order: the first whose conditions hold is the block's.
+        //   1. plain weights, the whole chain: mc_attn_qkv_wo_w13_w_* (only where form 2 has 64-slot ranges)
+        //   2. mc_attn_qkv_wo_w_* (_t2 / _t4)
+        //   3. mc_attn_qkv_wo_i8_*_t{1,2,4}
+        //   4. mc_attn_qkv_wo_i4_*
+        //   5. ... with wide ranges, _t{2,4}
+        //   6. llama only: mc_attn_qkv_i4_*_hd128_q4, then Wo as a GEMV
+        //   7. llama: the wq|wk|wv GEMV with the rope epilogue (p1_e4), then an attention tail
+        //   8. gemma3: mc_attn_qkv_wo_qkn_*_p{1,2}_t*
+        //   9. gemma3: the wq|wk|wv GEMV (p2_e0 while a post-norm is pending, else p1_e0), then an attention tail
+        // The attention tails of 7 and 9:
+        //   a. mc_attn_wo_qkn_* (gemma3, head_dim 256)
+        //   b. mc_attn_wo_i4_*
+        //   c. mc_attn_fused (_qkn where gemma3's norms go inside, otherwise behind mc_rope_kv)
+        //   d. mc_attn_fused_t2
+        //   e. scores + P.V, the range sums folded into Wo's prologue or reduced by their own launch
+        // 1 - 5 and 8 end behind Wo (llama: + residual, in `hidden`; gemma3: in `proj`), so do a and b; the others leave the attention row to a Wo GEMV.
+        const bool gemma = cfg.family == MC_FAMILY_GEMMA3;
+        const int H = cfg.n_heads, KV = cfg.n_kv_heads, hd = cfg.head_dim, n_rep = H / KV;
+        const int pg = (n_rep + 2) * hd / 2; // row pairs of wq|wk|wv per kv head (deal_ok)
+        const linear_w &qkv = L.qkv, &wo = L.wo;
+        // ---- the shared gates
+        const bool fused = attn_fused(); // (implies handoffs_ok)
+        const bool qkv_rows_ok = qkv.out == (H + 2 * KV) * hd, wo_rows_ok = wo.in == H * hd && wo.out % 2 == 0;
+        // wq|wk|wv AND Wo inside the attention launch (1 - 5): both switches, no adaptor on either matrix, llama
+        const bool qkv_wo_in = handoffs_ok() && opt.attn_qkv_on && opt.attn_wo_on && !gemma && !qkv.lora_cols && !wo.lora_cols && qkv_rows_ok && wo_rows_ok;
+        // ... int4, the built shape (Llama-3-8B: rows of 2 KiB, mc_attn_qkv_wo_i4_bfloat_hd128_k2_q2*)
+        const bool i4_shape = lin_ok(wo) && lin_ok(qkv) && hd == 128 && wo.in == 4096 && qkv.in == 4096 && qkv.group == wo.group && n_rep <= 16;
+        block_plan P;
+        // (the name is built by the arm that returns, and moved: no string is made for a form that is not taken)
+        auto one_launch = [&](block_form form, int tiles, int vsh, std::string name) -> block_plan&& {
+            P.form = form;
+            P.name = std::move(name);
+            P.tiles = tiles;
+            P.vsh = vsh;
+            P.ns = nsplit / tiles;
+            P.grid = (unsigned)(P.ns * (KV << vsh));
+            P.fast = (vsh ? opt.handoff_fast : handoff_fast_here()) ? 1u : 0u;
+            return std::move(P);
+        };
 
-    // ... the int4 launch with WIDE ranges (round 5, mc_attn_qkv_wo_i4_bfloat_hd128_k2_q2_t{2,4}): contexts whose 64-slot ranges are more workgroups
-    // than CUs -- Llama-3-8B at S = 4096 / 8192 -- as 128- / 256-slot ranges, one 512-thread workgroup per CU.  Returns the tiles (2 or 4), 0 = not this form.
-    int
-    attn_qkv_wo_i4_wide_tiles(const layer_w& L) const
-    {
-        if (!attn_qkv_on || !attn_wo_on || !attn_i4_wide_on || !attn_fused_on || !attn_qkv_g || !attn_psum_g || !attn_row_g || tb != 2 || n_own > 254) return 0;
-        if (cfg.family == MC_FAMILY_GEMMA3 || occ_wo_i4_wide == 0 || !lin_ok(L.wo) || !lin_ok(L.qkv) || L.qkv.lora_cols || L.wo.lora_cols) return 0;
-        const int hd = cfg.head_dim, n_rep = cfg.n_heads / cfg.n_kv_heads, pg = (n_rep + 2) * hd / 2;
-        if (hd != 128 || L.wo.in != 4096 || L.qkv.in != 4096 || L.wo.in != cfg.n_heads * hd || L.wo.out % 2 != 0 || L.qkv.group != L.wo.group ||
-            L.qkv.out != (cfg.n_heads + 2 * cfg.n_kv_heads) * hd || cfg.n_kv_heads % 8 != 0 || n_rep > 16)
-            return 0;
-        for (int t : {2, 4}) {
-            if (nsplit % t || cfg.max_seq_len % (64 * t)) continue; // (whole ranges only: attn_qkv_wo_w_tiles)
-            const int ns = nsplit / t;
-            const unsigned grid = (unsigned)(ns * cfg.n_kv_heads);
-            if (grid <= (unsigned)dev->prop.multiProcessorCount && pg % ns == 0 && pg / ns <= 16 && pg >= 64 && (unsigned)L.wo.out / 2 <= 16u * grid) return t;
+        // 1, 2: PLAIN bfloat weights (mc_attn_qkv_wo_w_bfloat_hd64_k4_q4: Llama-3.2-1B, the reference's default model): rows of 4 KiB (K = 2048), at most
+        // ONE row pair per wave in either GEMV phase; fewer than 8 kv heads are launched as 8 virtual ones.  64-slot ranges (S <= 2048) or, round 5, 128- / 256-slot
+        // ranges at S = 4096 / 8192 (_t{2,4}; they share MC_ATTN_I4_WIDE with the int4 form)
+        if (qkv_wo_in && qkv.fmt == MC_WFMT_T && wo.fmt == MC_WFMT_T && occ_wo_w != 0 && hd == 64 && wo.in == 2048 && qkv.in == 2048) {
+            const int vsh = kv_virtual_shift(), pgv = ((n_rep >> vsh) + 2) * hd / 2;
+            const int t = (n_rep >> vsh) > 16 || pgv < 64 || pgv > 512 ? 0 : whole_range_tiles({1, 2, 4}, KV << vsh, [&](int t_, int ns, unsigned grid) {
+                return (t_ == 1 ? fused : opt.attn_i4_wide_on) && deal_ok(pgv, ns, 8) && (unsigned)wo.out / 2 <= 8u * grid;
+            });
+            const int chain = t == 1 ? chain_w13_fetch(L, (unsigned)(nsplit * (KV << vsh))) : 0;
+            if (chain) {
+                P.chain_f = chain / 10;
+                P.chain_p = chain % 10;
+                return one_launch(block_form::qkv_wo_w13_w, 1, vsh, "mc_attn_qkv_wo_w13_w_bfloat_hd64_k4_q4_f" + std::to_string(P.chain_f) + "p" + std::to_string(P.chain_p));
+            }
+            if (t) return one_launch(block_form::qkv_wo_w, t, vsh, std::string("mc_attn_qkv_wo_w_bfloat_hd64_k4_q4") + (t > 1 ? "_t" + std::to_string(t) : std::string()));
         }
-        return 0;
+        // 3: INT8 weights (round 5, mc_attn_qkv_wo_i8_bfloat_hd128_k4_q4_t{1,4}: Llama-3-8B int8): rows of 4 KiB (K = 4096),
+        // one 512-thread workgroup per CU -- 64-slot ranges up to S = 2048 (t1), 256-slot ranges at S = 8192 (t4: 32 ranges x 8 kv heads)
+        if (qkv_wo_in && opt.attn_i8_on && qkv.fmt == MC_WFMT_I8 && wo.fmt == MC_WFMT_I8 && occ_wo_i8 != 0) {
+            auto group_ok = [](const linear_w& W) { return W.group == 0 || (W.group >= 16 && (W.group & (W.group - 1)) == 0); };
+            const bool built = group_ok(qkv) && group_ok(wo) && qkv.group == wo.group && hd == 128 && wo.in == 4096 && qkv.in == 4096 && KV % 8 == 0 && n_rep <= 16;
+            const int t = !built ? 0 : whole_range_tiles({1, 2, 4}, KV, [&](int, int ns, unsigned grid) {
+                return deal_ok(pg, ns, 16) && (unsigned)wo.out / 2 <= 8u * grid;
+            });
+            if (t) return one_launch(block_form::qkv_wo_i8, t, 0, "mc_attn_qkv_wo_i8_bfloat_hd128_k4_q4_t" + std::to_string(t));
+        }
+        if (qkv_wo_in && i4_shape) {
+            auto name = [&] { return "mc_attn_qkv_wo_i4_" + tname + "_hd128_k" + std::to_string(wo.in / 2048) + "_q" + std::to_string(qkv.in / 2048); };
+            // 4: INT4 (attn_block_kernels.hip qkv_in_launch): where Wo goes into the launch of 64-slot ranges (attn_wo_fused), the kv head's row pairs
+            // dealt over its nsplit workgroups, at most two per wave
+            if (attn_wo_fused(wo) && deal_ok(pg, nsplit, 16) && pg >= 64 && pg <= 512) return one_launch(block_form::qkv_wo_i4, 1, 0, name());
+            // 5: ... with WIDE ranges (round 5, mc_attn_qkv_wo_i4_bfloat_hd128_k2_q2_t{2,4}): contexts whose 64-slot ranges are more workgroups
+            // than CUs -- Llama-3-8B at S = 4096 / 8192 -- as 128- / 256-slot ranges, one 512-thread workgroup per CU
+            const int t = !opt.attn_i4_wide_on || occ_wo_i4_wide == 0 || KV % 8 != 0 ? 0 : whole_range_tiles({2, 4}, KV, [&](int, int ns, unsigned grid) {
+                return deal_ok(pg, ns, 16) && pg >= 64 && (unsigned)wo.out / 2 <= 16u * grid;
+            });
+            if (t) return one_launch(block_form::qkv_wo_i4, t, 0, name() + "_t" + std::to_string(t));
+        }
+        // 6: wq|wk|wv in the launch WITHOUT Wo (round 5, mc_attn_qkv_i4_bfloat_hd128_q4: Llama-3-70B -- its Wo rows of 4 KiB stay a GEMV, attn_wo_fused): rows of
+        // 4 KiB for wq|wk|wv too (K = 8192), up to three pairs per wave, the kv head's pairs gathered in two passes of 512.  MC_ATTN_QKV_ONLY=1 only.
+        if (!gemma && fused && opt.attn_qkv_on && opt.attn_qkv_only_on && occ_qkv_only != 0 && lin_ok(qkv) && !qkv.lora_cols && qkv_rows_ok && qkv.in == 8192 &&
+            cfg.dim == 8192 && hd == 128 && KV % 8 == 0 && (unsigned)(nsplit * KV) <= (unsigned)dev->prop.multiProcessorCount && n_rep <= 16 && pg <= 1024 &&
+            deal_ok(pg, nsplit, 24) && pg / nsplit >= 8) {
+            P.wo_gemv = true;
+            return one_launch(block_form::qkv_only, 1, 0, "mc_attn_qkv_i4_" + tname + "_hd128_q4");
+        }
+        // gemma3 (round 5): q_norm / k_norm + rotation + cache write + attention + Wo in ONE launch from the raw wq|wk|wv rows
+        // (mc_attn_wo_qkn_i4_bfloat_hd256_k2_t{1,2,4}: one 512-thread workgroup per CU, whole ranges of 64, 128 or 256 slots -- S = 1024, 2048, 4096 at
+        // Gemma-7B's 16 kv heads, 16 x 16 workgroups at S = 2048)
+        int qkn_tiles = 0;
+        if (gemma && handoffs_ok() && opt.attn_wo_qkn_on && opt.attn_wo_on && opt.attn_qkn_on && hd == 256 && occ_wo_qkn != 0 && lin_ok(wo) && !wo.lora_cols &&
+            wo_rows_ok && wo.in == 4096 && n_rep <= 16)
+            qkn_tiles = whole_range_tiles({1, 2, 4}, KV, [&](int t_, int, unsigned grid) {
+                return (t_ > 1 || cfg.max_seq_len % 64 == 0) && (unsigned)wo.out / 2 <= 2u * 8u * grid;
+            });
+        // 8: ... with wq|wk|wv and the block's norms in the launch too (mc_attn_qkv_wo_qkn_i4_bfloat_hd256_k2_p{1,2}_t*, attn_block_kernels.hip
+        // qkv_qkn_in_launch): rows of 1.5 KiB (K = 3072), the kv head's rotation pairs dealt evenly over its ranges, at most three per wave, one thread
+        // per pair in the hand-off.  _p2: the previous block's ffn post-norm + residual is its prologue.
+        if (qkn_tiles && opt.attn_qkv_qkn_on && opt.attn_qkv_on && occ_qkv_qkn != 0 && lin_split_ok(qkv) && !qkv.lora_cols && qkv.in == 3072 && cfg.dim == 3072 &&
+            qkv.group == wo.group && qkv_rows_ok && pg <= 512 && deal_ok(pg, nsplit / qkn_tiles, 24))
+            return one_launch(block_form::qkv_wo_qkn, qkn_tiles, 0,
+                              "mc_attn_qkv_wo_qkn_i4_" + tname + "_hd256_k2_p" + (pending_pn ? "2" : "1") + "_t" + std::to_string(qkn_tiles));
+
+        // 7, 9: wq|wk|wv as a GEMV, then the tail
+        P.qkv_gemv = true;
+        if (qkn_tiles) return one_launch(block_form::wo_qkn, qkn_tiles, 0, "mc_attn_wo_qkn_i4_" + tname + "_hd256_k2_t" + std::to_string(qkn_tiles)); // a
+        // (gemma3 normalises q and k per head before the rotation, attention.h:174-175: that needs whole heads, so rope + cache write are a launch of
+        //  their own -- except inside the one-launch attention where that is what follows: mc_attn_fused_qkn_bfloat, decode_kernels.hip q_from_qkv_rows)
+        P.rope_kv = gemma;
+        if (attn_wo_fused(wo)) return one_launch(block_form::wo_i4, 1, 0, "mc_attn_wo_i4_" + tname + "_hd" + std::to_string(hd) + "_k" + std::to_string(wo.in / 2048)); // b
+        P.wo_gemv = true;
+        if (fused) { // c
+            if (gemma && opt.attn_qkn_on && (hd == 128 || hd == 256)) {
+                P.rope_kv = false;
+                return one_launch(block_form::fused_qkn, 1, 0, "mc_attn_fused_qkn_" + tname);
+            }
+            one_launch(block_form::fused, 1, 0, "mc_attn_fused_" + tname);
+            P.fast = handoff_mode_alone();
+            P.grid = (unsigned)nsplit * ((P.fast & 2u) ? ((unsigned)KV + 7u) & ~7u : (unsigned)KV);
+            return P;
+        }
+        if (attn_fused_t2()) { // d
+            one_launch(block_form::fused_t2, 2, 0, "mc_attn_fused_t2_" + tname);
+            P.fast = opt.handoff_fast ? 1u : 0u;
+            return P;
+        }
+        P.form = block_form::scores_pv; // e
+        P.name = "mc_attn_scores_" + tname;
+        P.pv_fold = pv_fold(wo);
+        return P;
     }
 
     // dynamic LDS of a linear-order int4 GEMV (gemv(): the padded row, the scratch, the parked sums of eight waves)
@@ -975,15 +1151,15 @@ struct mc_decoder {
         std::string name = "mc_gemv_";
         name += L.fmt == MC_WFMT_I4 ? "i4_" : (L.fmt == MC_WFMT_I8 ? "i8_" : "w_");
         name += tname;
-        unsigned block = (unsigned)gemv_block, waves = block / 64;
-        unsigned cap = (unsigned)(dev->prop.multiProcessorCount * gemv_wgs_per_cu);
+        unsigned block = (unsigned)opt.gemv_block, waves = block / 64;
+        unsigned cap = (unsigned)(dev->prop.multiProcessorCount * opt.gemv_wgs_per_cu);
         if (L.fmt == MC_WFMT_I4 && tb == 2 && cfg.qmode == MC_QMODE_FAST) name += "_fast";
-        // Grid: one workgroup per four row groups, capped at gemv_wgs_per_cu workgroups per CU (a
+        // Grid: one workgroup per four row groups, capped at opt.gemv_wgs_per_cu workgroups per CU (a
         // whole multiple of the CU count: what has to balance is the work per CU -- its SIMDs
         // time-share their waves -- so 3.5 row groups per wave on every CU beats an even 4 per
         // wave on 448 workgroups, measured 19.0 vs 21.4 us on the 60 MB w1|w3 matrix).
         const unsigned ng = (L.out + 3) / 4;
-        unsigned wgs = gemv_full_grid ? ng : (ng + waves - 1) / waves;
+        unsigned wgs = opt.gemv_full_grid ? ng : (ng + waves - 1) / waves;
         if (wgs > cap) wgs = cap;
         if (wgs == 0) wgs = 1;
         // exact int4 on bfloat rows: dot products on the 4x4x4 MFMA (_m4); with scale groups that are
@@ -991,10 +1167,10 @@ struct mc_decoder {
         // a SIMD holds more than one wave of the launch: the MFMA -> cvt_pk -> MFMA chain of a weight
         // is longer than the VALU one and a lone wave per SIMD (Wo, w2: 1024 row groups) has nobody
         // to hide it behind (8.2 vs 8.5 us per launch, profiles/r01_kernel_stats.csv).
-        const bool m4 = L.fmt == MC_WFMT_I4 && tb == 2 && cfg.qmode == MC_QMODE_EXACT && gemv_m4 && !dbg_variant;
+        const bool m4 = L.fmt == MC_WFMT_I4 && tb == 2 && cfg.qmode == MC_QMODE_EXACT && opt.gemv_m4 && !opt.dbg_variant;
         const bool m4d_ok = m4 && (L.group == 0 || L.group % 128 == 0) && L.in % 128 == 0;
         const bool shared_simd = std::min(wgs * waves, ng) > 4u * (unsigned)dev->prop.multiProcessorCount; // waves that own a row group
-        const bool m4d = m4d_ok && (gemv_m4 >= 3 || (gemv_m4 == 2 && shared_simd));
+        const bool m4d = m4d_ok && (opt.gemv_m4 >= 3 || (opt.gemv_m4 == 2 && shared_simd));
         // linear-order main loop (gemv.h): rows of whole KiB (K a multiple of 2048: 1, 2, 4, 7 or 14 KiB), whole row groups
         const int nch = L.in % 2048 == 0 ? L.in / 2048 : 0;
         // (an adapted linear behind a post-norm: the linear-order `_p2_` kernels take the post-norm's pointers in the adaptor's
@@ -1007,15 +1183,15 @@ struct mc_decoder {
         if (pro == 3 && !lin && !ling) return fail(MC_ERR_RUNTIME, "gemv: the partial-sum prologue exists for the linear-order kernels only");
         if (ling) {
             name += "_ling" + std::to_string(ling);
-            block = 64u * (unsigned)lin_waves;
-            waves = (unsigned)lin_waves;
+            block = 64u * (unsigned)opt.lin_waves;
+            waves = (unsigned)opt.lin_waves;
             const unsigned cus = (unsigned)dev->prop.multiProcessorCount;
-            cap = cus * (gemv_block_env ? (unsigned)gemv_wgs_per_cu : 1u);
+            cap = cus * (opt.gemv_block_env ? (unsigned)opt.gemv_wgs_per_cu : 1u);
             const unsigned np = (unsigned)L.out / 2;
             wgs = (np + waves - 1) / waves;
             // fewer pairs than half the waves a full grid has (the 2048-row matrices of the small models) and an epilogue that
             // treats the rows of a pair separately: one ROW per wave (gemv.h LGEN, `half`)
-            if (ling_half && (epi == 0 || epi == 1) && !L.lora_cols && 2u * np <= cap * waves && (unsigned)L.out % 2 == 0)
+            if (opt.ling_half && (epi == 0 || epi == 1) && !L.lora_cols && 2u * np <= cap * waves && (unsigned)L.out % 2 == 0)
                 wgs = std::max(wgs, std::min(cap, ((unsigned)L.out + waves - 1) / waves));
             if (wgs > cap) wgs = cap;
             if (wgs > cus) wgs = wgs / cus * cus;
@@ -1023,10 +1199,10 @@ struct mc_decoder {
         if (lins) {
             // the loop's unit is a quad of rows (two super rows); one eight-wave workgroup per CU as below
             name += "_lin3s";
-            block = 64u * (unsigned)lin_waves;
-            waves = (unsigned)lin_waves;
+            block = 64u * (unsigned)opt.lin_waves;
+            waves = (unsigned)opt.lin_waves;
             const unsigned cus = (unsigned)dev->prop.multiProcessorCount;
-            cap = cus * (gemv_block_env ? (unsigned)gemv_wgs_per_cu : 1u);
+            cap = cus * (opt.gemv_block_env ? (unsigned)opt.gemv_wgs_per_cu : 1u);
             const unsigned nq = (unsigned)L.out / 4;
             wgs = (nq + waves - 1) / waves;
             if (wgs > cap) wgs = cap;
@@ -1035,7 +1211,7 @@ struct mc_decoder {
         // long rows, few of them (Gemma-7B's w2: 1536 pairs of 12 KiB rows = one pair per wave on 192 CUs): the K range of a pair over four waves of a
         // workgroup on EVERY CU (gemv_ksplit.h) -- at most eight pairs per workgroup, plain store or residual add, no adaptor
         const unsigned cus_ = (unsigned)dev->prop.multiProcessorCount;
-        const bool k4 = lin && lin_k4_on && nch == 12 && pro == 0 && (epi == 0 || epi == 1) && !L.lora_cols && lin_waves == 8 &&
+        const bool k4 = lin && opt.lin_k4_on && nch == 12 && pro == 0 && (epi == 0 || epi == 1) && !L.lora_cols && opt.lin_waves == 8 &&
                         (unsigned)L.out / 2 >= 4u * cus_ && ((unsigned)L.out / 2 + cus_ - 1) / cus_ <= 8u;
         if (lin) {
             name += "_lin" + std::to_string(nch) + (k4 ? "k4" : "");
@@ -1043,9 +1219,9 @@ struct mc_decoder {
             // between the row requests and the first weight requests (gemv.h MC_GEMV_XBAR), always ahead of the weight
             // stream in the CU's in-order memory pipe (w1|w3: 16.2 us against 17.3 with two four-wave workgroups)
             // (the kernels are built for exactly this workgroup size, gemv_kernels.hip MC_LIN_WAVES: no blockDim load)
-            block = 64u * (unsigned)lin_waves;
-            waves = (unsigned)lin_waves;
-            cap = (unsigned)dev->prop.multiProcessorCount * (gemv_block_env ? (unsigned)gemv_wgs_per_cu : 1u);
+            block = 64u * (unsigned)opt.lin_waves;
+            waves = (unsigned)opt.lin_waves;
+            cap = (unsigned)dev->prop.multiProcessorCount * (opt.gemv_block_env ? (unsigned)opt.gemv_wgs_per_cu : 1u);
             // a CU takes in ~25 GB/s whatever its waves do, so what matters is equal BYTES PER CU: a whole multiple of
             // the CU count, at least one row pair per wave (the kernel cuts the pairs into equal contiguous ranges)
             const unsigned cus = (unsigned)dev->prop.multiProcessorCount;
@@ -1057,8 +1233,8 @@ struct mc_decoder {
         }
         else if (lins) {}
         else if (m4) name += m4d ? "_m4d" : "_m4";
-        if (L.fmt == MC_WFMT_I4 && tb == 2 && dbg_variant && ((pro == 1 && epi == 2) || (pro == 0 && epi == 0)))
-            name += dbg_variant == 1 ? "_dbgstream" : "_dbgnoload";
+        if (L.fmt == MC_WFMT_I4 && tb == 2 && opt.dbg_variant && ((pro == 1 && epi == 2) || (pro == 0 && epi == 0)))
+            name += opt.dbg_variant == 1 ? "_dbgstream" : "_dbgnoload";
         name += "_p" + std::to_string(pro) + "_e" + std::to_string(epi);
         // LDS: activation row zero-padded to whole chunks (64 lanes x 16 B of packed weights) + scratch
         const unsigned kpl = L.fmt == MC_WFMT_I4 ? 32 : (L.fmt == MC_WFMT_I8 ? 16 : (tb == 2 ? 8 : 4));
@@ -1117,6 +1293,14 @@ struct mc_decoder {
         return launch("mc_step_rope", 1, 1, 1, 64, 0, pack(state, (int32_t)rope_start));
     }
 
+    // gemma3's post-norm of `proj` as a launch of its own: hidden = res + norm(proj) w
+    mc_status
+    post_norm_row(const void* norm_w, const void* res)
+    {
+        const float mu = cfg.family == MC_FAMILY_GEMMA3 ? 1.0f : 0.0f;
+        return launch("mc_rmsnorm_row_" + tname, 1, 1, 1, 1024, 0, pack(proj, norm_w, res, hidden, (uint32_t)cfg.dim, cfg.norm_eps, mu));
+    }
+
     mc_status
     run_layers(const void* x_in)
     {
@@ -1130,7 +1314,7 @@ struct mc_decoder {
         // gemma3: post-norms folded into the prologue of the GEMV that consumes them (gemv.h PRO 2) --
         // 7 launches per block instead of 9.  Not with parity taps (they want every block output in
         // HBM) and only while the row fits the prologue's register path.
-        const bool fuse_pn = gemma && !want_taps && gemma_fuse && (size_t)dim * tb / 16 <= (size_t)4 * gemv_block;
+        const bool fuse_pn = gemma && !want_taps && opt.gemma_fuse && (size_t)dim * tb / 16 <= (size_t)4 * opt.gemv_block;
         pending_pn = nullptr;
         if (fuse_pn && x != hidden && n_own > 0) {
             // the residual pointers of the fused prologues are fixed at `hidden`: a later pipeline
@@ -1140,92 +1324,16 @@ struct mc_decoder {
         }
         for (int li = 0; li < n_own; li++) {
             layer_w& L = layers[li];
-            const int w_tiles = attn_qkv_wo_w_tiles(L);
-            const bool qkv_w_in = w_tiles != 0;
-            const int i8_tiles = qkv_w_in ? 0 : attn_qkv_wo_i8_tiles(L);
-            const bool i4_in = !qkv_w_in && !i8_tiles && attn_qkv_wo_fused(L);
-            const int i4_tiles = (qkv_w_in || i8_tiles || i4_in) ? 0 : attn_qkv_wo_i4_wide_tiles(L);
-            const bool qkv_in = qkv_w_in || i8_tiles || i4_in || i4_tiles;
-            bool qkn_in = false, gq = false, q_only = false;
-            int qkn_wo = 0;
-            const int chain_f = w_tiles == 1 ? attn_qkv_wo_w13_w_fetch(L) : 0;
-            if (chain_f) {
-                // ... and ffn_norm, w1|w3, act*mul (transformer.h:135-137, 53-59) too: the block up to the gate row in ONE launch
-                const int vsh = kv_virtual_shift();
-                s = launch("mc_attn_qkv_wo_w13_w_bfloat_hd64_k4_q4_f" + std::to_string(chain_f / 10) + "p" + std::to_string(chain_f % 10), (unsigned)(nsplit * (KV << vsh)), 1, 1, 512, 0,
-                           pack((const void*)L.kc, (const void*)L.vt, attn_out, attn_psum_g, attn_slab_g, attn_row_g, attn_qkv_g, state,
-                                (uint32_t)(n_rep >> vsh), (uint32_t)(KV << vsh), (uint32_t)cfg.max_seq_len, scale_T, (uint32_t)nsplit, (uint32_t)(li + 1),
-                                (const void*)L.wo.w, (const void*)L.wo.scales, x, hidden, (uint32_t)L.wo.out, (uint32_t)L.wo.group,
-                                (const void*)L.attention_norm, (const void*)L.qkv.w, (const void*)L.qkv.scales,
-                                (const float*)rope_cos[L.rope_table], (const float*)rope_sin[L.rope_table], cfg.norm_eps, mu,
-                                (uint32_t)((vsh ? handoff_fast : handoff_fast_here()) ? 1 : 0), (void*)nullptr, (uint32_t)vsh, attn_hid_g,
-                                (const void*)L.w13.w, (const void*)L.ffn_norm, gate, (uint32_t)L.w13.out, (void*)nullptr));
-                if (s != MC_OK) return s;
-            } else if (qkv_in) {
-                // attention_norm, wq|wk|wv, rope, cache write, scores, softmax, P.V, wo + residual (transformer.h:130-133,
-                // attention.h:170-205) in ONE launch: every hand-off but the last stays inside one kv head
-                // (plain weights: fewer than 8 kv heads are launched as 8 virtual ones, kv_virtual_shift)
-                const int vsh = qkv_w_in ? kv_virtual_shift() : 0;
-                const bool vfast = vsh ? handoff_fast : handoff_fast_here();
-                // (int8: ranges of 64 i8_tiles slots -- nsplit / i8_tiles of them per kv head)
-                const int ns = i8_tiles ? nsplit / i8_tiles : (i4_tiles ? nsplit / i4_tiles : (w_tiles ? nsplit / w_tiles : nsplit));
-                s = launch(qkv_w_in ? std::string("mc_attn_qkv_wo_w_bfloat_hd64_k4_q4") + (w_tiles > 1 ? "_t" + std::to_string(w_tiles) : std::string())
-                           : i8_tiles ? "mc_attn_qkv_wo_i8_bfloat_hd128_k4_q4_t" + std::to_string(i8_tiles)
-                                    : "mc_attn_qkv_wo_i4_" + tname + "_hd" + std::to_string(hd) + "_k" + std::to_string(L.wo.in / 2048) + "_q" +
-                                          std::to_string(L.qkv.in / 2048) + (i4_tiles ? "_t" + std::to_string(i4_tiles) : std::string()),
-                           (unsigned)(ns * (KV << vsh)), 1, 1, 512, 0,
-                           pack((const void*)L.kc, (const void*)L.vt, attn_out, attn_psum_g, attn_slab_g, attn_row_g, attn_qkv_g, state,
-                                (uint32_t)(n_rep >> vsh), (uint32_t)(KV << vsh), (uint32_t)cfg.max_seq_len, scale_T, (uint32_t)ns, (uint32_t)(li + 1),
-                                (const void*)L.wo.w, (const void*)L.wo.scales, x, hidden, (uint32_t)L.wo.out, (uint32_t)L.wo.group,
-                                (const void*)L.attention_norm, (const void*)L.qkv.w, (const void*)L.qkv.scales,
-                                (const float*)rope_cos[L.rope_table], (const float*)rope_sin[L.rope_table], cfg.norm_eps, mu,
-                                (uint32_t)(vfast ? 1 : 0), (void*)nullptr, (uint32_t)vsh));
-                if (s != MC_OK) return s;
-            } else if (!gemma && (q_only = attn_qkv_only_ok(L))) {
-                // attention_norm, wq|wk|wv, rope, cache write, scores, softmax, P.V (transformer.h:130, attention.h:170-203) in ONE launch;
-                // Wo + residual from the finished row below
-                s = launch("mc_attn_qkv_i4_" + tname + "_hd128_q4", (unsigned)(nsplit * KV), 1, 1, 512, 0,
-                           pack((const void*)L.kc, (const void*)L.vt, attn_out, attn_psum_g, attn_slab_g, attn_qkv_g, state, (uint32_t)n_rep,
-                                (uint32_t)KV, (uint32_t)cfg.max_seq_len, scale_T, (uint32_t)nsplit, (uint32_t)(li + 1), x, (uint32_t)L.qkv.group,
-                                (const void*)L.attention_norm, (const void*)L.qkv.w, (const void*)L.qkv.scales,
-                                (const float*)rope_cos[L.rope_table], (const float*)rope_sin[L.rope_table], cfg.norm_eps, mu,
-                                (uint32_t)(handoff_fast_here() ? 1 : 0), (void*)nullptr));
-                if (s != MC_OK) return s;
-                s = gemv(L.wo, 0, 1, attn_out, hidden, x, nullptr, mu);
-                if (s != MC_OK) return s;
-            } else if (!gemma) {
+            const block_plan P = plan_block(L);
+            const float* rcos = rope_cos[L.rope_table];
+            const float* rsin = rope_sin[L.rope_table];
+            if (P.qkv_gemv && !gemma) {
                 // attention_norm + wq|wk|wv + rope + cache write in ONE launch
                 // (transformer.h:130, attention.h:170-177)
                 s = gemv(L.qkv, 1, 4, x, qkv, L.qkv_epi, L.attention_norm, mu);
                 if (s != MC_OK) return s;
-            } else if ((gq = attn_qkv_wo_qkn_ok(L))) {
-                // gemma3, ONE launch from the row handed to the block to Wo's output: (the previous block's ffn post-norm + residual,)
-                // attention_norm, wq|wk|wv, q_norm / k_norm, rope, cache write, scores, softmax, P.V, wo (transformer.h:126-133,
-                // attention.h:170-205); the attention post-norm and its residual are the w1|w3 GEMV's prologue (or mc_rmsnorm_row below)
-                postnorm_args h{};
-                if (pending_pn) {
-                    const auto it = pn_host.find(pending_pn);
-                    if (it == pn_host.end()) return fail(MC_ERR_RUNTIME, "attention block: unknown post-norm descriptor");
-                    h = it->second;
-                }
-                const int tiles = attn_wo_qkn_tiles(L.wo), ns = nsplit / tiles;
-                s = launch(std::string("mc_attn_qkv_wo_qkn_i4_") + tname + "_hd256_k2_p" + (pending_pn ? "2" : "1") + "_t" + std::to_string(tiles),
-                           (unsigned)(ns * KV), 1, 1, 512, 0,
-                           pack((const void*)L.kc, (const void*)L.vt, attn_out, attn_psum_g, attn_slab_g, attn_row_g, attn_qkv_g, state,
-                                (uint32_t)n_rep, (uint32_t)KV, (uint32_t)cfg.max_seq_len, scale_T, (uint32_t)ns, (uint32_t)(li + 1),
-                                (const void*)L.wo.w, (const void*)L.wo.scales, pending_pn ? (const void*)proj : x, proj, (uint32_t)L.wo.out,
-                                (uint32_t)L.wo.group, (const void*)L.attention_norm, (const void*)L.qkv.w, (const void*)L.qkv.scales,
-                                (const float*)rope_cos[L.rope_table], (const float*)rope_sin[L.rope_table], cfg.norm_eps, mu,
-                                (uint32_t)(handoff_fast_here() ? 1 : 0), (void*)nullptr, (const void*)L.q_norm, (const void*)L.k_norm,
-                                (const void*)h.post_w, (const void*)h.res, (void*)h.h_out));
-                if (s != MC_OK) return s;
-                if (pending_pn) {
-                    pending_pn = nullptr;
-                    x = hidden;
-                }
-            } else {
-                // gemma3 normalises q and k per head before the rotation (attention.h:174-175):
-                // that needs whole heads, so rope + cache write stay a launch of their own
+            } else if (P.qkv_gemv) {
+                // gemma3: attention_norm + wq|wk|wv; q_norm / k_norm, rope and the cache write follow, in the attention launch or as mc_rope_kv
                 // (fused flow: the previous block's ffn post-norm + residual is applied by this
                 // kernel's prologue, PRO 2, and its workgroup 0 leaves the block input in `hidden`)
                 if (pending_pn) {
@@ -1236,11 +1344,7 @@ struct mc_decoder {
                     s = gemv(L.qkv, 1, 0, x, qkv, nullptr, L.attention_norm, mu);
                 }
                 if (s != MC_OK) return s;
-                // q_norm / k_norm + rope + cache write: inside the one-launch attention where that is what follows
-                // (mc_attn_fused_qkn_bfloat, decode_kernels.hip q_from_qkv_rows), a launch of their own otherwise
-                qkn_wo = attn_wo_qkn_tiles(L.wo);
-                qkn_in = !qkn_wo && attn_qkn_on && tb == 2 && (hd == 128 || hd == 256) && attn_fused() && !attn_wo_fused(L.wo);
-                if (!qkn_in && !qkn_wo) {
+                if (P.rope_kv) {
                     s = launch("mc_rope_kv_" + tname, H + 2 * KV, 1, 1, hd / 2, 0,
                                pack(qkv, q_rot, L.kc, L.vt, rope_cos[L.rope_table], rope_sin[L.rope_table],
                                     L.q_norm, L.k_norm, state, (uint32_t)H, (uint32_t)KV, (uint32_t)hd,
@@ -1248,121 +1352,132 @@ struct mc_decoder {
                     if (s != MC_OK) return s;
                 }
             }
-            if (qkv_in || q_only) {
-            } else if (gq) {
-                if (!fuse_pn) {
-                    s = launch("mc_rmsnorm_row_" + tname, 1, 1, 1, 1024, 0,
-                               pack(proj, L.attention_post_norm, x, hidden, (uint32_t)dim, cfg.norm_eps, mu));
-                    if (s != MC_OK) return s;
+            switch (P.form) {
+            case block_form::qkv_wo_w13_w:
+            case block_form::qkv_wo_w:
+            case block_form::qkv_wo_i8:
+            case block_form::qkv_wo_i4: {
+                // attention_norm, wq|wk|wv, rope, cache write, scores, softmax, P.V, wo + residual (transformer.h:130-133,
+                // attention.h:170-205) in ONE launch: every hand-off but the last stays inside one kv head
+                // (plain weights: fewer than 8 kv heads are launched as 8 virtual ones, kv_virtual_shift; P.ns ranges of 64 P.tiles slots per kv head)
+                arg_pack a = pack((const void*)L.kc, (const void*)L.vt, attn_out, attn_psum_g, attn_slab_g, attn_row_g, attn_qkv_g, state,
+                                  (uint32_t)(n_rep >> P.vsh), (uint32_t)(KV << P.vsh), (uint32_t)cfg.max_seq_len, scale_T, (uint32_t)P.ns, (uint32_t)(li + 1),
+                                  (const void*)L.wo.w, (const void*)L.wo.scales, x, hidden, (uint32_t)L.wo.out, (uint32_t)L.wo.group,
+                                  (const void*)L.attention_norm, (const void*)L.qkv.w, (const void*)L.qkv.scales,
+                                  rcos, rsin, cfg.norm_eps, mu,
+                                  P.fast, (void*)nullptr, (uint32_t)P.vsh);
+                // ... and ffn_norm, w1|w3, act*mul (transformer.h:135-137, 53-59) too: the block up to the gate row in ONE launch
+                auto more = [&a](const auto&... v) { (a.push(v), ...); };
+                if (P.form == block_form::qkv_wo_w13_w) more(attn_hid_g, (const void*)L.w13.w, (const void*)L.ffn_norm, gate, (uint32_t)L.w13.out, (void*)nullptr);
+                s = launch(P.name, P.grid, 1, 1, 512, 0, std::move(a));
+                break;
+            }
+            case block_form::qkv_only:
+                // attention_norm, wq|wk|wv, rope, cache write, scores, softmax, P.V (transformer.h:130, attention.h:170-203) in ONE launch;
+                // Wo + residual from the finished row below
+                s = launch(P.name, P.grid, 1, 1, 512, 0,
+                           pack((const void*)L.kc, (const void*)L.vt, attn_out, attn_psum_g, attn_slab_g, attn_qkv_g, state, (uint32_t)n_rep,
+                                (uint32_t)KV, (uint32_t)cfg.max_seq_len, scale_T, (uint32_t)P.ns, (uint32_t)(li + 1), x, (uint32_t)L.qkv.group,
+                                (const void*)L.attention_norm, (const void*)L.qkv.w, (const void*)L.qkv.scales,
+                                rcos, rsin, cfg.norm_eps, mu,
+                                P.fast, (void*)nullptr));
+                break;
+            case block_form::qkv_wo_qkn: {
+                // gemma3, ONE launch from the row handed to the block to Wo's output: (the previous block's ffn post-norm + residual,)
+                // attention_norm, wq|wk|wv, q_norm / k_norm, rope, cache write, scores, softmax, P.V, wo (transformer.h:126-133,
+                // attention.h:170-205); the attention post-norm and its residual are the w1|w3 GEMV's prologue (or post_norm_row below)
+                postnorm_args h{};
+                if (pending_pn) {
+                    const auto it = pn_host.find(pending_pn);
+                    if (it == pn_host.end()) return fail(MC_ERR_RUNTIME, "attention block: unknown post-norm descriptor");
+                    h = it->second;
                 }
-            } else if (qkn_wo) {
+                s = launch(P.name, P.grid, 1, 1, 512, 0,
+                           pack((const void*)L.kc, (const void*)L.vt, attn_out, attn_psum_g, attn_slab_g, attn_row_g, attn_qkv_g, state,
+                                (uint32_t)n_rep, (uint32_t)KV, (uint32_t)cfg.max_seq_len, scale_T, (uint32_t)P.ns, (uint32_t)(li + 1),
+                                (const void*)L.wo.w, (const void*)L.wo.scales, pending_pn ? (const void*)proj : x, proj, (uint32_t)L.wo.out,
+                                (uint32_t)L.wo.group, (const void*)L.attention_norm, (const void*)L.qkv.w, (const void*)L.qkv.scales,
+                                rcos, rsin, cfg.norm_eps, mu,
+                                P.fast, (void*)nullptr, (const void*)L.q_norm, (const void*)L.k_norm,
+                                (const void*)h.post_w, (const void*)h.res, (void*)h.h_out));
+                if (pending_pn) {
+                    pending_pn = nullptr;
+                    x = hidden;
+                }
+                break;
+            }
+            case block_form::wo_qkn:
                 // q_norm / k_norm, rope, cache write, scores, softmax, P.V, wo (attention.h:170-205) in ONE launch; the post-norm and the
-                // residual are the next GEMV's prologue (or mc_rmsnorm_row below)
-                const int ns = nsplit / qkn_wo;
-                s = launch("mc_attn_wo_qkn_i4_" + tname + "_hd256_k2_t" + std::to_string(qkn_wo), (unsigned)(ns * KV), 1, 1, 512, 0,
+                // residual are the next GEMV's prologue (or post_norm_row below)
+                s = launch(P.name, P.grid, 1, 1, 512, 0,
                            pack((const void*)qkv, (const void*)L.kc, (const void*)L.vt, attn_out, attn_psum_g, attn_slab_g, attn_row_g, state,
-                                (uint32_t)n_rep, (uint32_t)KV, (uint32_t)cfg.max_seq_len, scale_T, (uint32_t)ns, (uint32_t)(li + 1),
+                                (uint32_t)n_rep, (uint32_t)KV, (uint32_t)cfg.max_seq_len, scale_T, (uint32_t)P.ns, (uint32_t)(li + 1),
                                 (const void*)L.wo.w, (const void*)L.wo.scales, (const void*)nullptr, proj, (uint32_t)L.wo.out, (uint32_t)L.wo.group,
-                                (uint32_t)0, (uint32_t)(handoff_fast_here() ? 1 : 0), (void*)nullptr, (const void*)L.q_norm, (const void*)L.k_norm,
-                                (const float*)rope_cos[L.rope_table], (const float*)rope_sin[L.rope_table], cfg.norm_eps, mu));
-                if (s != MC_OK) return s;
-                if (!fuse_pn) {
-                    s = launch("mc_rmsnorm_row_" + tname, 1, 1, 1, 1024, 0,
-                               pack(proj, L.attention_post_norm, x, hidden, (uint32_t)dim, cfg.norm_eps, mu));
-                    if (s != MC_OK) return s;
-                }
-            } else if (attn_wo_fused(L.wo)) {
+                                (uint32_t)0, P.fast, (void*)nullptr, (const void*)L.q_norm, (const void*)L.k_norm,
+                                rcos, rsin, cfg.norm_eps, mu));
+                break;
+            case block_form::wo_i4:
                 // scores, softmax, P.V, wo + residual  (attention.h:191-205, transformer.h:132-133) in ONE launch
-                s = launch("mc_attn_wo_i4_" + tname + "_hd" + std::to_string(hd) + "_k" + std::to_string(L.wo.in / 2048),
-                           (unsigned)(nsplit * KV), 1, 1, 512, 0,
+                s = launch(P.name, P.grid, 1, 1, 512, 0,
                            pack(q_rot, L.kc, L.vt, attn_out, attn_psum_g, attn_slab_g, attn_row_g, state, (uint32_t)n_rep, (uint32_t)KV,
-                                (uint32_t)cfg.max_seq_len, scale_T, (uint32_t)nsplit, (uint32_t)(li + 1), (const void*)L.wo.w,
+                                (uint32_t)cfg.max_seq_len, scale_T, (uint32_t)P.ns, (uint32_t)(li + 1), (const void*)L.wo.w,
                                 (const void*)L.wo.scales, gemma ? (const void*)nullptr : x, gemma ? proj : hidden, (uint32_t)L.wo.out,
-                                (uint32_t)L.wo.group, (uint32_t)(gemma ? 0 : 1), (uint32_t)(handoff_fast_here() ? 1 : 0), (void*)nullptr));
-                if (s != MC_OK) return s;
-                if (gemma && !fuse_pn) {
-                    s = launch("mc_rmsnorm_row_" + tname, 1, 1, 1, 1024, 0,
-                               pack(proj, L.attention_post_norm, x, hidden, (uint32_t)dim, cfg.norm_eps, mu));
-                    if (s != MC_OK) return s;
-                }
-            } else if (attn_fused()) {
-                // scores, softmax, P.V                 (attention.h:191-203) in ONE launch, then Wo from the finished row
-                if (qkn_in)
-                    s = launch("mc_attn_fused_qkn_" + tname, (unsigned)(nsplit * KV), 1, 1, 256, 0,
-                               pack((const void*)qkv, L.kc, L.vt, attn_out, attn_psum_g, attn_slab_g, state, (uint32_t)n_rep, (uint32_t)KV,
-                                    (uint32_t)hd, (uint32_t)cfg.max_seq_len, scale_T, (uint32_t)nsplit, (uint32_t)(li + 1),
-                                    (uint32_t)(handoff_fast_here() ? 1 : 0), (const void*)L.q_norm, (const void*)L.k_norm,
-                                    (const float*)rope_cos[L.rope_table], (const float*)rope_sin[L.rope_table], cfg.norm_eps, mu));
-                else {
-                    const uint32_t mode = handoff_mode_alone();
-                    const unsigned stride = (mode & 2u) ? ((unsigned)KV + 7u) & ~7u : (unsigned)KV;
-                    s = launch("mc_attn_fused_" + tname, (unsigned)nsplit * stride, 1, 1, 256, 0,
-                               pack(q_rot, L.kc, L.vt, attn_out, attn_psum_g, attn_slab_g, state, (uint32_t)n_rep, (uint32_t)KV, (uint32_t)hd,
-                                    (uint32_t)cfg.max_seq_len, scale_T, (uint32_t)nsplit, (uint32_t)(li + 1), (void*)nullptr, mode));
-                }
-                if (s != MC_OK) return s;
-                s = gemma ? gemv(L.wo, 0, 0, attn_out, proj, nullptr, nullptr, mu) : gemv(L.wo, 0, 1, attn_out, hidden, x, nullptr, mu);
-                if (s != MC_OK) return s;
-                if (gemma && !fuse_pn) {
-                    s = launch("mc_rmsnorm_row_" + tname, 1, 1, 1, 1024, 0,
-                               pack(proj, L.attention_post_norm, x, hidden, (uint32_t)dim, cfg.norm_eps, mu));
-                    if (s != MC_OK) return s;
-                }
-            } else if (attn_fused_t2()) {
-                // ... in ONE launch of 128-slot ranges, then Wo from the finished row
-                s = launch("mc_attn_fused_t2_" + tname, (unsigned)(nsplit / 2 * KV), 1, 1, 256, 0,
+                                (uint32_t)L.wo.group, (uint32_t)(gemma ? 0 : 1), P.fast, (void*)nullptr));
+                break;
+            case block_form::fused_qkn:
+                // q_norm / k_norm, rope, cache write, scores, softmax, P.V (attention.h:170-203) in ONE launch, then Wo from the finished row
+                s = launch(P.name, P.grid, 1, 1, 256, 0,
+                           pack((const void*)qkv, L.kc, L.vt, attn_out, attn_psum_g, attn_slab_g, state, (uint32_t)n_rep, (uint32_t)KV,
+                                (uint32_t)hd, (uint32_t)cfg.max_seq_len, scale_T, (uint32_t)P.ns, (uint32_t)(li + 1),
+                                P.fast, (const void*)L.q_norm, (const void*)L.k_norm,
+                                rcos, rsin, cfg.norm_eps, mu));
+                break;
+            case block_form::fused:
+            case block_form::fused_t2:
+                // scores, softmax, P.V                 (attention.h:191-203) in ONE launch of 64- or 128-slot ranges, then Wo from the finished row
+                s = launch(P.name, P.grid, 1, 1, 256, 0,
                            pack(q_rot, L.kc, L.vt, attn_out, attn_psum_g, attn_slab_g, state, (uint32_t)n_rep, (uint32_t)KV, (uint32_t)hd,
-                                (uint32_t)cfg.max_seq_len, scale_T, (uint32_t)(nsplit / 2), (uint32_t)(li + 1), (void*)nullptr,
-                                (uint32_t)(handoff_fast ? 1 : 0)));
+                                (uint32_t)cfg.max_seq_len, scale_T, (uint32_t)P.ns, (uint32_t)(li + 1), (void*)nullptr, P.fast));
+                break;
+            case block_form::scores_pv: {
+                // scores, softmax denominators         (attention.h:195-200)
+                s = launch(P.name, nsplit, KV, 1, 256, 0,
+                           pack(q_rot, L.kc, expv, psum, (void*)nullptr, state, (uint32_t)n_rep,
+                                (uint32_t)hd, (uint32_t)cfg.max_seq_len, scale_T, (uint32_t)nsplit));
                 if (s != MC_OK) return s;
-                s = gemv(L.wo, 0, 1, attn_out, hidden, x, nullptr, mu);
-                if (s != MC_OK) return s;
-            } else {
-            // scores, softmax denominators         (attention.h:195-200)
-            s = launch("mc_attn_scores_" + tname, nsplit, KV, 1, 256, 0,
-                       pack(q_rot, L.kc, expv, psum, (void*)nullptr, state, (uint32_t)n_rep,
-                            (uint32_t)hd, (uint32_t)cfg.max_seq_len, scale_T, (uint32_t)nsplit));
+                // softmax normalisation + P.V          (attention.h:200-203)
+                const int ranges = P.pv_fold ? 4 : pv_ranges;
+                // folded: one round of loads per wave (four k-steps of 32 slots each)
+                const int fold_waves = std::max(4, std::min(16, ((cfg.max_seq_len + 31) / 32 / 4 + 3) / 4));
+                s = launch("mc_attn_pv_" + tname, hd / 16, KV, ranges, P.pv_fold ? 64 * fold_waves : opt.pv_block, 0,
+                           pack(expv, psum, L.vt, attn_out, state, (uint32_t)n_rep, (uint32_t)hd,
+                                (uint32_t)cfg.max_seq_len, (uint32_t)nsplit, pv_parts, (uint32_t)H));
+                if (s == MC_OK && ranges > 1 && !P.pv_fold)
+                    s = launch("mc_attn_pv_reduce_" + tname, (H * hd + 255) / 256, 1, 1, 256, 0,
+                               pack((const void*)pv_parts, attn_out, (uint32_t)(H * hd), (uint32_t)ranges));
+                break;
+            }
+            }
             if (s != MC_OK) return s;
-            // softmax normalisation + P.V          (attention.h:200-203)
-            const bool fold = pv_fold(L.wo);
-            const int ranges = fold ? 4 : pv_ranges;
-            // folded: one round of loads per wave (four k-steps of 32 slots each)
-            const int fold_waves = std::max(4, std::min(16, ((cfg.max_seq_len + 31) / 32 / 4 + 3) / 4));
-            s = launch("mc_attn_pv_" + tname, hd / 16, KV, ranges, fold ? 64 * fold_waves : pv_block, 0,
-                       pack(expv, psum, L.vt, attn_out, state, (uint32_t)n_rep, (uint32_t)hd,
-                            (uint32_t)cfg.max_seq_len, (uint32_t)nsplit, pv_parts, (uint32_t)H));
-            if (s != MC_OK) return s;
-            if (ranges > 1 && !fold) {
-                s = launch("mc_attn_pv_reduce_" + tname, (H * hd + 255) / 256, 1, 1, 256, 0,
-                           pack((const void*)pv_parts, attn_out, (uint32_t)(H * hd), (uint32_t)ranges));
+            // wo (+ post norm) + residual          (attention.h:205, transformer.h:132-133), where the launches above stopped at the attention row:
+            // llama with the residual into `hidden`, gemma3 into `proj` like the forms that hold Wo
+            if (P.wo_gemv) {
+                const void* wo_x = P.pv_fold ? (const void*)pv_parts : (const void*)attn_out;
+                const int wo_pro = P.pv_fold ? 3 : 0;
+                s = gemma ? gemv(L.wo, wo_pro, 0, wo_x, proj, nullptr, nullptr, mu) : gemv(L.wo, wo_pro, 1, wo_x, hidden, x, nullptr, mu);
                 if (s != MC_OK) return s;
             }
-            // wo (+ post norm) + residual          (attention.h:205, transformer.h:132-133)
-            const void* wo_x = fold ? (const void*)pv_parts : (const void*)attn_out;
-            const int wo_pro = fold ? 3 : 0;
-            if (!gemma) {
-                s = gemv(L.wo, wo_pro, 1, wo_x, hidden, x, nullptr, mu);
+            // gemma3: the attention post-norm + residual, unless it is the w1|w3 GEMV's prologue
+            if (gemma && !fuse_pn) {
+                s = post_norm_row(L.attention_post_norm, x);
                 if (s != MC_OK) return s;
-            } else {
-                s = gemv(L.wo, wo_pro, 0, wo_x, proj, nullptr, nullptr, mu);
-                if (s != MC_OK) return s;
-                if (!fuse_pn) {
-                    s = launch("mc_rmsnorm_row_" + tname, 1, 1, 1, 1024, 0,
-                               pack(proj, L.attention_post_norm, x, hidden, (uint32_t)dim, cfg.norm_eps, mu));
-                    if (s != MC_OK) return s;
-                }
-            }
             }
             // ffn_norm + w1|w3 + act*mul           (transformer.h:135-137, 53-59)
-            if (chain_f) {
-                s = MC_OK; // (a phase of the launch above)
-            } else if (gemma && fuse_pn) {
-                // attention post-norm + residual (-> hidden_b) + ffn_norm in the prologue
-                s = gemv(L.w13, 2, 3, proj, gate, L.pn_attn, L.ffn_norm, mu);
-            } else {
-                s = gemv(L.w13, 1, gemma ? 3 : 2, hidden, gate, nullptr, L.ffn_norm, mu);
+            // (qkv_wo_w13_w: a phase of the launch above; gemma3 with folded post-norms: attention post-norm + residual (-> hidden_b) + ffn_norm in the prologue)
+            if (P.form != block_form::qkv_wo_w13_w) {
+                s = gemma && fuse_pn ? gemv(L.w13, 2, 3, proj, gate, L.pn_attn, L.ffn_norm, mu) : gemv(L.w13, 1, gemma ? 3 : 2, hidden, gate, nullptr, L.ffn_norm, mu);
+                if (s != MC_OK) return s;
             }
-            if (s != MC_OK) return s;
             // w2 (+ post norm) + residual          (transformer.h:59, 138-139)
             if (!gemma) {
                 s = gemv(L.w2, 0, 1, gate, hidden, hidden, nullptr, mu);
@@ -1371,8 +1486,7 @@ struct mc_decoder {
                 s = gemv(L.w2, 0, 0, gate, proj, nullptr, nullptr, mu);
                 if (s != MC_OK) return s;
                 if (!fuse_pn) {
-                    s = launch("mc_rmsnorm_row_" + tname, 1, 1, 1, 1024, 0,
-                               pack(proj, L.ffn_post_norm, hidden, hidden, (uint32_t)dim, cfg.norm_eps, mu));
+                    s = post_norm_row(L.ffn_post_norm, hidden);
                     if (s != MC_OK) return s;
                 } else if (li + 1 < n_own || last_stage) {
                     // ffn post-norm + residual (hidden_b) is left to the next pre-norm GEMV: the next
@@ -1380,8 +1494,7 @@ struct mc_decoder {
                     pending_pn = L.pn_ffn;
                 } else {
                     // the row leaves this pipeline stage: materialise it
-                    s = launch("mc_rmsnorm_row_" + tname, 1, 1, 1, 1024, 0,
-                               pack(proj, L.ffn_post_norm, (const void*)hidden_b, hidden, (uint32_t)dim, cfg.norm_eps, mu));
+                    s = post_norm_row(L.ffn_post_norm, hidden_b);
                     if (s != MC_OK) return s;
                 }
             }
@@ -1431,13 +1544,13 @@ struct mc_decoder {
     bool
     lazy_pick_ok() const
     {
-        return lazy_pick_on && first_stage && last_stage && head_pick() && head_pick_mode == 2 && emb_fmt == MC_WFMT_T && !want_taps;
+        return opt.lazy_pick_on && first_stage && last_stage && head_pick() && opt.head_pick_mode == 2 && emb_fmt == MC_WFMT_T && !want_taps;
     }
     // does the greedy pick ride in the head's own launch (gemv.h EPI_STORE_PICK)?
     bool
     head_pick() const
     {
-        return sampler_kind == MC_SAMPLER_GREEDY && head_pick_on && !pending_pn && lin_waves == 8 && !output.lora_cols &&
+        return sampler_kind == MC_SAMPLER_GREEDY && opt.head_pick_on && !pending_pn && opt.lin_waves == 8 && !output.lora_cols &&
                (lin_ok(output) || ling_kib(output)) && cfg.vocab % 2 == 0;
     }
 
@@ -1451,10 +1564,10 @@ struct mc_decoder {
         const bool pick = head_pick();
         mc_status s = pending_pn ? gemv(output, 2, 0, proj, logits, pending_pn, final_norm, mu)
                                  : gemv(output, 1, pick ? 5 : 0, hidden, logits,
-                                        pick ? (const void*)(pick_desc + (head_pick_mode == 2 ? offsetof(pick_block, per_wg) : offsetof(pick_block, atomic))) : nullptr, final_norm, mu);
+                                        pick ? (const void*)(pick_desc + (opt.head_pick_mode == 2 ? offsetof(pick_block, per_wg) : offsetof(pick_block, atomic))) : nullptr, final_norm, mu);
         pending_pn = nullptr;
         if (s != MC_OK) return s;
-        if (pick && head_pick_mode == 2)
+        if (pick && opt.head_pick_mode == 2)
             return lazy_pick ? MC_OK : fold_pick();
         if (pick) return MC_OK;
         if (sampler_kind == MC_SAMPLER_GREEDY)
@@ -1505,13 +1618,13 @@ struct mc_decoder {
             s = launch("mc_exp_table_bfloat", 256, 1, 1, 256, 0, pack(pf_etab));
             if (s != MC_OK) return s;
         }
-        if (tb == 2 && cfg.family == MC_FAMILY_GEMMA3 && !pf_gtab && !(getenv("MC_PF_GELU_TABLE") && atoi(getenv("MC_PF_GELU_TABLE")) == 0)) {
+        if (tb == 2 && cfg.family == MC_FAMILY_GEMMA3 && !pf_gtab && opt.pf_gelu_table) {
             s = alloc((void**)&pf_gtab, 65536 * sizeof(float), false);
             if (s != MC_OK) return s;
             s = launch("mc_gelu_table_bfloat", 256, 1, 1, 256, 0, pack(pf_gtab));
             if (s != MC_OK) return s;
         }
-        const size_t need = (tb == 2 && !pf_two_pass) ? 0 : (size_t)H * M * S;
+        const size_t need = (tb == 2 && !opt.pf_two_pass) ? 0 : (size_t)H * M * S;
         if (need > pf_probs_elems) {
             MC_HIP(hipStreamSynchronize(stream));
             release(&pf_probs);
@@ -1527,8 +1640,7 @@ struct mc_decoder {
     unsigned
     gemm_row_tile(int M) const
     {
-        const char* depth_env = getenv("MC_PF_DEPTH");
-        return tb == 2 && M >= 256 && !(depth_env && atoi(depth_env) == 1) && !getenv("MC_PF_BM128") ? 256u : 128u;
+        return tb == 2 && M >= 256 && !opt.pf_depth1 && !opt.pf_bm128 ? 256u : 128u;
     }
     unsigned
     gemm_splits(const linear_w& L, int M) const
@@ -1541,20 +1653,19 @@ struct mc_decoder {
         // (round 4) ... but not past the point where the extra workgroups only start another round: 96 tiles on 256 CUs take one
         // round of K/2 at 2 splits and two rounds of K/4 at 4 -- the same time, with twice the partials written and read back
         // (MC_PF_SPLITS_OLD=1: the plain doubling rule)
-        const bool old_rule = getenv("MC_PF_SPLITS_OLD") != nullptr;
-        if (!old_rule && splits > 1) {
+        if (!opt.pf_splits_old && splits > 1) {
             auto rounds = [&](unsigned sp) { return (tiles * sp + want - 1) / want; };
             const unsigned half = splits / 2;
             if (rounds(splits) * half >= rounds(half) * splits) splits = half; // rounds(s)/s >= rounds(s/2)/(s/2)
         }
-        return getenv("MC_PF_NO_SPLITK") ? 1u : splits;
+        return opt.pf_no_splitk ? 1u : splits;
     }
     // Short prompts (<= 64 rows) on int4 weights: the weight-streaming GEMM over the quad-interleaved copy (prefill_kernels.hip
     // mc_pf2_gemm_i4_bfloat: matrix-pipe dequantisation straight into MFMA operands, no LDS image of W)
     bool
     pf2_ok(const linear_w& L, int M) const
     {
-        return pf2_on && tb == 2 && L.fmt == MC_WFMT_I4 && cfg.qmode == MC_QMODE_EXACT && M <= 64 && L.group == 128 && L.in % 128 == 0 &&
+        return opt.pf2_on && tb == 2 && L.fmt == MC_WFMT_I4 && cfg.qmode == MC_QMODE_EXACT && M <= 64 && L.group == 128 && L.in % 128 == 0 &&
                L.in >= 256;
     }
     mc_status
@@ -1578,8 +1689,7 @@ struct mc_decoder {
     {
         const unsigned nwg = ((unsigned)L.out + 127u) / 128u, KT = (unsigned)L.in / 128u;
         const unsigned cus = (unsigned)dev->prop.multiProcessorCount;
-        const char* te = getenv("MC_PF2_WGS_PER_CU");
-        const unsigned target = cus * (te ? (unsigned)std::max(1, atoi(te)) : 1u);
+        const unsigned target = cus * (unsigned)opt.pf2_wgs_per_cu;
         splits = std::max(1u, std::min(16u, (target + nwg - 1) / nwg));
         ktper = std::max(2u, (KT + splits - 1) / splits);
         splits = (KT + ktper - 1) / ktper;
@@ -1607,11 +1717,11 @@ struct mc_decoder {
                            (const void*)L.lora_b, (uint32_t)L.lora_cols, L.lora_scale));
     }
     // ---- the 256 x 256 ping-pong GEMM (round 5, kernels/pf_gemm8.h): bfloat16 rows, no adaptor, K in whole tiles of 64, scale groups
-    // of whole 16-runs; from pf_g8_rows rows on (below that the 128-row tiles keep more workgroups busy)
+    // of whole 16-runs; from opt.pf_g8_rows rows on (below that the 128-row tiles keep more workgroups busy)
     bool
     g8_ok(const linear_w& L, int M) const
     {
-        if (!pf_g8_on || tb != 2 || L.lora_cols || M < pf_g8_rows || getenv("MC_PF_SMALL_GEMM")) return false;
+        if (!opt.pf_g8_on || tb != 2 || L.lora_cols || M < opt.pf_g8_rows || opt.pf_small_gemm) return false;
         if (L.in % 64 != 0 || L.out % 4 != 0) return false;
         if (L.fmt != MC_WFMT_T && L.group && (L.group < 32 || (L.group & (L.group - 1)) != 0)) return false;
         if ((size_t)L.out * L.in * 2 > 0xFFFFFFFFull || (size_t)M * L.in * 2 > 0xFFFFFFFFull) return false; // (32-bit buffer offsets)
@@ -1623,16 +1733,16 @@ struct mc_decoder {
     {
         const unsigned tiles = ((L.out + 255) / 256) * ((M + 255) / 256), cus = (unsigned)dev->prop.multiProcessorCount;
         unsigned splits = 1;
-        while (splits < (unsigned)pf_g8_max_splits && tiles * splits * 2 <= cus && (unsigned)L.in / 64u / (splits * 2) >= (unsigned)pf_g8_min_ktiles) splits *= 2;
-        return getenv("MC_PF_NO_SPLITK") ? 1u : splits;
+        while (splits < (unsigned)opt.pf_g8_max_splits && tiles * splits * 2 <= cus && (unsigned)L.in / 64u / (splits * 2) >= (unsigned)opt.pf_g8_min_ktiles) splits *= 2;
+        return opt.pf_no_splitk ? 1u : splits;
     }
-    // the quantised matrices of long prompts as dequantised bfloat16 copies (pf_plain_mode above)
+    // the quantised matrices of long prompts as dequantised bfloat16 copies (opt.pf_plain_mode above)
     bool
     plain_copy_ok()
     {
         if (!pf_plain_known) {
             pf_plain_known = true;
-            if (pf_plain_mode >= 0) pf_plain_on = pf_plain_mode != 0;
+            if (opt.pf_plain_mode >= 0) pf_plain_on = opt.pf_plain_mode != 0;
             else {
                 size_t need = 0;
                 auto one = [&](const linear_w& L) {
@@ -1681,11 +1791,11 @@ struct mc_decoder {
     bool
     lib_ok(const linear_w& L, int M) const
     {
-        if (!pf_lib_on || tb != 2 || L.lora_cols || getenv("MC_PF_SMALL_GEMM")) return false;
+        if (!pf_lib_on || tb != 2 || L.lora_cols || opt.pf_small_gemm) return false;
         if (L.fmt != MC_WFMT_T && (L.in % 16 != 0 || (L.group && (L.group & (L.group - 1)) != 0))) return false;
         if (L.in % 8 != 0 || L.out % 8 != 0) return false;
-        if (pf_lib_force) return true; // (MC_PF_BLASLT=2: every prompt GEMM that can, whatever its size -- how the tests reach it on small models)
-        return M >= pf_lib_rows && (size_t)((L.out + 255) / 256) * (size_t)((M + 255) / 256) >= (size_t)pf_lib_tiles;
+        if (opt.pf_lib_force) return true; // (MC_PF_BLASLT=2: every prompt GEMM that can, whatever its size -- how the tests reach it on small models)
+        return M >= opt.pf_lib_rows && (size_t)((L.out + 255) / 256) * (size_t)((M + 255) / 256) >= (size_t)opt.pf_lib_tiles;
     }
     mc_status
     ensure_wd(const linear_w& Lc, const void** wd)
@@ -1715,7 +1825,7 @@ struct mc_decoder {
         blaslt_api& api = blaslt();
         auto off = [&](const char* why) {
             pf_lib_on = false;
-            if (getenv("MC_PF_BLASLT_VERBOSE")) fprintf(stderr, "metalchat_hip: hipBLASLt path switched off: %s\n", why);
+            if (opt.pf_lib_verbose) fprintf(stderr, "metalchat_hip: hipBLASLt path switched off: %s\n", why);
             return false;
         };
         if (!api.ok) return off("library or symbols not found");
@@ -1745,7 +1855,7 @@ struct mc_decoder {
             int found = 0;
             constexpr int NCAND = 8;
             hipblasLtMatmulHeuristicResult_t cand[NCAND] = {};
-            good = good && api.Heuristic(lt, pl.desc, pl.a, pl.b, pl.c, pl.c, pref, pf_lib_tune ? NCAND : 1, cand, &found) == HIPBLAS_STATUS_SUCCESS && found > 0;
+            good = good && api.Heuristic(lt, pl.desc, pl.a, pl.b, pl.c, pl.c, pref, opt.pf_lib_tune ? NCAND : 1, cand, &found) == HIPBLAS_STATUS_SUCCESS && found > 0;
             if (pref) (void)api.PrefDestroy(pref);
             if (good) pl.algo = cand[0];
             if (good && found > 1) {
@@ -1774,7 +1884,7 @@ struct mc_decoder {
                         }
                     }
                     if (best_i >= 0) pl.algo = cand[best_i];
-                    if (getenv("MC_PF_BLASLT_VERBOSE"))
+                    if (opt.pf_lib_verbose)
                         fprintf(stderr, "metalchat_hip: hipBLASLt %d x %d x %d%s: candidate %d of %d, %.1f us\n", M, L.out, L.in, f32_out ? " (fp32 rows)" : "",
                                 best_i, found, best * 1e3f / 3.0f);
                 }
@@ -1798,7 +1908,7 @@ struct mc_decoder {
     gemm_to_parts(const linear_w& L, const void* X, int M, unsigned* splits_out, mc_status* st)
     {
         *st = MC_OK;
-        if (!pf_fold_on || tb != 2 || L.lora_cols || getenv("MC_PF_SMALL_GEMM")) return false;
+        if (!opt.pf_fold_on || tb != 2 || L.lora_cols || opt.pf_small_gemm) return false;
         if (lib_ok(L, M)) {
             // the library GEMM leaves its fp32 sums as the ONE partial the consumers add up
             const size_t need1 = (size_t)M * L.out;
@@ -1848,8 +1958,7 @@ struct mc_decoder {
             return true;
         }
         const std::string f = L.fmt == MC_WFMT_I4 ? "i4_" : (L.fmt == MC_WFMT_I8 ? "i8_" : "w_");
-        const char* depth_env = getenv("MC_PF_DEPTH");
-        const std::string deep = depth_env && atoi(depth_env) == 1 ? "" : "_d2";
+        const std::string deep = opt.pf_depth1 ? "" : "_d2";
         const unsigned bm = gemm_row_tile(M);
         *st = launch(std::string(bm == 256 ? "mc_pf_gemm256_" : "mc_pf_gemm128_") + f + tname + deep + "_e2", (L.out + 127) / 128, (M + bm - 1) / bm,
                      splits, 2 * bm, 0,
@@ -1893,14 +2002,13 @@ struct mc_decoder {
                           pack((const void*)pf_part, Y, epi == 1 ? res : (const void*)nullptr, (uint32_t)M, (uint32_t)L.out, splits, (const void*)nullptr,
                                (const void*)nullptr, (uint32_t)0, 0.0f));
         }
-        const bool big = tb == 2 && !getenv("MC_PF_SMALL_GEMM");
+        const bool big = tb == 2 && !opt.pf_small_gemm;
         const std::string f = L.fmt == MC_WFMT_I4 ? "i4_" : (L.fmt == MC_WFMT_I8 ? "i8_" : "w_");
         const void* la = L.lora_cols ? pf_lora : nullptr;
         if (pf2_ok(L, M) && epi != 2) return gemm_pf2(L, epi, X, Y, res, M, la);
         // two K chunks in flight per workgroup (prefill_kernels.hip: measured best at every length);
         // MC_PF_DEPTH=1 selects the one-chunk build for A/B runs
-        const char* depth_env = getenv("MC_PF_DEPTH");
-        const std::string deep = depth_env && atoi(depth_env) == 1 ? "" : "_d2";
+        const std::string deep = opt.pf_depth1 ? "" : "_d2";
         // 256 rows of X per workgroup from 256 rows on (prefill_kernels.hip pf_gemm_big_body, BM): the W tile is dequantised once
         // per workgroup, and at 128 rows that vector work is ~ 0.8 of the matrix pipe's time
         const unsigned bm = big ? gemm_row_tile(M) : 128u;
@@ -1993,7 +2101,7 @@ struct mc_decoder {
             xn_ready = false;
             // rope + cache write: four rotation pairs per thread (prefill_kernels.hip pf_rope_cache_v4_body: a quarter of the waves of the one-pair
             // launch, which is bound by the rate waves start at, and the transposed V cache written 16 slots at a time); MC_PF_ROPE_PACK=0: the launch of rounds 1-5
-            const bool rope_v4 = pf_rope_pack && tb == 2 && hd % 8 == 0 && hd <= 2048 && 2048 % hd == 0 &&
+            const bool rope_v4 = opt.pf_rope_pack && tb == 2 && hd % 8 == 0 && hd <= 2048 && 2048 % hd == 0 &&
                                  ((!L.q_norm && !L.k_norm) || hd == 128 || hd == 256); // (q / k norms: the head sizes whose sum order the kernel reproduces)
             const unsigned rope_per = rope_v4 ? 2048u / (unsigned)hd : 1u; // heads of a row per workgroup of 256 threads
             const unsigned rope_gx = rope_v4 ? ((unsigned)(H + KV) * (unsigned)M + rope_per - 1) / rope_per + (unsigned)KV * (((unsigned)M + 15u) / 16u) // q / k units, then v tiles of 16 rows
@@ -2069,55 +2177,55 @@ struct mc_decoder {
                 // one or two query heads per workgroup by the rule of one prompt below, over the tiles of all segments; the LDS-tile and
                 // four-head forms have no packed counterpart (DESIGN.md "The packed prompt pass")
                 s = timed("attention", [&] {
-                    const char* heads_env = getenv("MC_PF_ATTN_HEADS");
+                    const bool heads_given = opt.pf_attn_heads >= 0;
                     const bool enough = (unsigned)pk->ntiles * (unsigned)(H / 2) >= 2u * (unsigned)dev->prop.multiProcessorCount;
-                    const bool two = (H / KV) % 2 == 0 && (heads_env ? atoi(heads_env) == 2 : enough);
+                    const bool two = (H / KV) % 2 == 0 && (heads_given ? opt.pf_attn_heads == 2 : enough);
                     return launch(std::string(two ? "mc_pp_attn2_bfloat_hd" : "mc_pp_attn_bfloat_hd") + std::to_string(hd), (unsigned)pk->ntiles,
                                   two ? H / 2 : H, 1, 256, 0,
                                   pack(pf_q, pk->segs, pk->tiles, (const void*)pk_kc, (const void*)pk_vt, pk->cache_stride, pf_att, (uint32_t)H,
                                        (uint32_t)(H / KV), (uint32_t)cfg.max_seq_len, scale_T, (const void*)pf_etab));
                 });
                 if (s != MC_OK) return s;
-            } else if (tb == 2 && !pf_two_pass) {
+            } else if (tb == 2 && !opt.pf_two_pass) {
                 // fused: the probabilities stay on chip
                 s = timed("attention", [&] {
                     // two query heads of a kv head per workgroup where the grouping allows it: each K / V
                     // fragment is loaded once for both (MC_PF_ATTN_HEADS=1: one head per workgroup)
                     // (measured: 2048 rows 15.8 -> 14.0 ms, 512 rows 2.05 -> 1.56 ms per prompt; with too few
                     // workgroups to fill the chip -- 128 rows -- it loses, 0.46 -> 0.61 ms)
-                    const char* heads_env = getenv("MC_PF_ATTN_HEADS");
+                    const bool heads_given = opt.pf_attn_heads >= 0;
                     const bool enough = (unsigned)((M + 15) / 16) * (unsigned)(H / 2) >= 2u * (unsigned)dev->prop.multiProcessorCount;
-                    const bool two = (H / KV) % 2 == 0 && hd <= 128 && (heads_env ? atoi(heads_env) == 2 : enough);
+                    const bool two = (H / KV) % 2 == 0 && hd <= 128 && (heads_given ? opt.pf_attn_heads == 2 : enough);
                     // four query heads per workgroup (head_dim 128, 360 registers: one workgroup per CU): at 1024 rows and more
                     // the launch is bound by the K / V fragments its waves pull out of L2 (1.6 GB per layer at 2048 rows, ~ 6 TB/s),
                     // and four heads per fragment halve them again: 2048 rows 44.5 -> 42.6 ms, 1024: 22.75 -> 22.3, 512: 11.8 -> 11.7
                     const bool four = (H / KV) % 4 == 0 && hd == 128 &&
-                                      (heads_env ? atoi(heads_env) == 4
+                                      (heads_given ? opt.pf_attn_heads == 4
                                                  : (unsigned)((M + 15) / 16) * (unsigned)(H / 4) >= (unsigned)dev->prop.multiProcessorCount);
                     // long prompts (round 5): K / V tiles through LDS, 32 rows x 4 heads per workgroup (prefill_kernels.hip pf_attn_lds_body)
                     const bool eight = (H / KV) % 4 == 0 && hd == 128 && cfg.max_seq_len % 8 == 0 &&
-                                       (heads_env ? atoi(heads_env) == 8 : (pf_attn8_on && M >= pf_attn8_rows));
+                                       (heads_given ? opt.pf_attn_heads == 8 : (opt.pf_attn8_on && M >= opt.pf_attn8_rows));
                     // (row tiles of 32 rows, dealt in pairs -- tile x with tile (last - x): equal work under the causal mask -- when the
                     //  pairs still cover the CUs; MC_PF_ATTN8_PAIR=0 / 1 forces either)
                     const unsigned ntl = (unsigned)(M + 31) / 32u;
-                    const char* pair_env = getenv("MC_PF_ATTN8_PAIR");
-                    const bool pair = pair_env ? atoi(pair_env) != 0 : ((ntl + 1u) / 2u) * (unsigned)(H / 4) >= (unsigned)dev->prop.multiProcessorCount;
+                    const bool pair_given = opt.pf_attn8_pair >= 0;
+                    const bool pair = pair_given ? opt.pf_attn8_pair != 0 : ((ntl + 1u) / 2u) * (unsigned)(H / 4) >= (unsigned)dev->prop.multiProcessorCount;
                     // head_dim 256 (round 6; Gemma-7B: a kv head per query head): the same K / V tiles through LDS for 64 rows of ONE head, four waves
                     // (MC_PF_ATTN8_ROWS256: from how many rows; MC_PF_ATTN_HEADS=1: never)
-                    const bool eight256 = hd == 256 && cfg.max_seq_len % 8 == 0 && (heads_env ? atoi(heads_env) == 8 : (pf_attn8_on && M >= pf_attn8_rows256));
+                    const bool eight256 = hd == 256 && cfg.max_seq_len % 8 == 0 && (heads_given ? opt.pf_attn_heads == 8 : (opt.pf_attn8_on && M >= opt.pf_attn8_rows256));
                     if (eight256) {
                         const unsigned ntl64 = (unsigned)(M + 63) / 64u;
-                        const bool pair64 = pair_env ? atoi(pair_env) != 0 : ((ntl64 + 1u) / 2u) * (unsigned)H >= (unsigned)dev->prop.multiProcessorCount;
+                        const bool pair64 = pair_given ? opt.pf_attn8_pair != 0 : ((ntl64 + 1u) / 2u) * (unsigned)H >= (unsigned)dev->prop.multiProcessorCount;
                         return launch("mc_pf_attn8_bfloat_hd256", pair64 ? (ntl64 + 1u) / 2u : ntl64, H, 1, 256, 0,
                                       pack(pf_q, L.kc, L.vt, pf_att, (uint32_t)M, (uint32_t)S, (uint32_t)H, (uint32_t)(H / KV),
                                            (uint32_t)cfg.max_seq_len, scale_T, win, (const void*)pf_etab));
                     }
                     // head_dim 64 (round 6; TinyLlama-1.1B: 8 query heads per kv head, Llama-3.2-1B: 4): 8 heads x 16 rows or 4 heads x 32 rows per workgroup
                     const unsigned nh64 = (H / KV) % 8 == 0 ? 8u : ((H / KV) % 4 == 0 ? 4u : 0u);
-                    const bool eight64 = hd == 64 && nh64 && cfg.max_seq_len % 8 == 0 && (heads_env ? atoi(heads_env) == 8 : (pf_attn8_on && M >= pf_attn8_rows64));
+                    const bool eight64 = hd == 64 && nh64 && cfg.max_seq_len % 8 == 0 && (heads_given ? opt.pf_attn_heads == 8 : (opt.pf_attn8_on && M >= opt.pf_attn8_rows64));
                     if (eight64) {
                         const unsigned rt64 = 128u / nh64, ntl = ((unsigned)M + rt64 - 1u) / rt64;
-                        const bool pr = pair_env ? atoi(pair_env) != 0 : ((ntl + 1u) / 2u) * ((unsigned)H / nh64) >= (unsigned)dev->prop.multiProcessorCount;
+                        const bool pr = pair_given ? opt.pf_attn8_pair != 0 : ((ntl + 1u) / 2u) * ((unsigned)H / nh64) >= (unsigned)dev->prop.multiProcessorCount;
                         return launch(nh64 == 8 ? "mc_pf_attn8_bfloat_hd64_h8" : "mc_pf_attn8_bfloat_hd64_h4", pr ? (ntl + 1u) / 2u : ntl, (unsigned)H / nh64, 1, 512, 0,
                                       pack(pf_q, L.kc, L.vt, pf_att, (uint32_t)M, (uint32_t)S, (uint32_t)H, (uint32_t)(H / KV),
                                            (uint32_t)cfg.max_seq_len, scale_T, win, (const void*)pf_etab));
@@ -2147,7 +2255,7 @@ struct mc_decoder {
             }
             // gemma3's post norms: the reduce of a split Wo / w2, the post norm with the residual and the next norm in one launch
             // (prefill_kernels.hip mc_pf_rmsnorm2_parts_bfloat; MC_PF_NORM2=0: the three launches)
-            const bool norm2 = fold_norm && tb == 2 && !(getenv("MC_PF_NORM2") && atoi(getenv("MC_PF_NORM2")) == 0);
+            const bool norm2 = fold_norm && tb == 2 && opt.pf_norm2;
             if (L.attention_post_norm && norm2 && gemm_to_parts(L.wo, pf_att, M, &sp, &gs)) {
                 if (gs != MC_OK) return gs;
                 s = timed("norm", [&] { return launch("mc_pf_rmsnorm2_parts_bfloat", M, 1, 1, 256, 0,
@@ -2177,11 +2285,10 @@ struct mc_decoder {
             const unsigned act_pp = 8u / (unsigned)tb; // pairs per thread (one 16-byte packet)
             // silu(w1 x) * (w3 x) in the epilogue of an unsplit 256-row GEMM (prefill_kernels.hip pf_gemm_big_body EPI 3; the
             // table of exponentials rides in `res`).  MC_PF_ACT_EPI=0: the separate launch
-            const bool act_epi_on = !(getenv("MC_PF_ACT_EPI") && atoi(getenv("MC_PF_ACT_EPI")) == 0);
             // (gemma: gelu from the table of round 6 -- the 256 x 256 GEMM's e4 epilogue only; without the table the separate launch with its fp64 tanh)
-            const bool act_epi = act_epi_on && tb == 2 && !L.w13.lora_cols && !getenv("MC_PF_SMALL_GEMM") && !pf2_ok(L.w13, M) &&
+            const bool act_epi = opt.pf_act_epi && tb == 2 && !L.w13.lora_cols && !opt.pf_small_gemm && !pf2_ok(L.w13, M) &&
                                  (g8_ok(L.w13, M) ? g8_splits(L.w13, M) == 1 && cfg.ffn_dim % 2 == 0 && (!gemma || pf_gtab)
-                                                  : !gemma && gemm_row_tile(M) == 256 && gemm_splits(L.w13, M) == 1 && !(getenv("MC_PF_DEPTH") && atoi(getenv("MC_PF_DEPTH")) == 1)) &&
+                                                  : !gemma && gemm_row_tile(M) == 256 && gemm_splits(L.w13, M) == 1 && !opt.pf_depth1) &&
                                  !lib_ok(L.w13, M); // (the opt-in library GEMM + the separate activation launch)
             const void* act_tab = gemma ? (const void*)pf_gtab : (const void*)pf_etab; // (gelu without a table: nullptr, the kernels evaluate it)
             if (act_epi) {
@@ -2235,7 +2342,7 @@ struct mc_decoder {
             MC_HIP(hipMemcpyAsync(hidden, (char*)pf_x + last, (size_t)dim * tb, hipMemcpyDeviceToDevice, stream));
             s = last_stage ? timed("head", [&] { return run_head(); }) : MC_OK;
         }
-        if (pf_timing) {
+        if (opt.pf_timing) {
             double tot = 0;
             for (auto& kv : pf_ms) tot += kv.second;
             fprintf(stderr, "[prefill M=%d] GPU ms:", M);
@@ -2306,60 +2413,10 @@ mc_decoder_create(mc_device* dev, mc_library* lib, mc_queue* q, const mc_decoder
     d->n_own = c.layer_end - c.layer_begin;
     d->first_stage = c.layer_begin == 0;
     d->last_stage = c.layer_end == c.n_layers;
-    if (const char* e = getenv("MC_GEMV_BLOCK")) { d->gemv_block = atoi(e); d->gemv_block_env = true; }
-    if (const char* e = getenv("MC_GEMV_WGS_PER_CU")) { d->gemv_wgs_per_cu = atoi(e); d->gemv_block_env = true; }
-    if (const char* e = getenv("MC_GEMV_DBG")) d->dbg_variant = atoi(e);
-    if (const char* e = getenv("MC_GEMV_FULLGRID")) d->gemv_full_grid = atoi(e) != 0;
-    if (const char* e = getenv("MC_GEMV_LIN")) d->gemv_lin = atoi(e) != 0;
-    if (const char* e = getenv("MC_PV_FOLD")) d->pv_fold_on = atoi(e) != 0;
-    if (const char* e = getenv("MC_ATTN_FUSED")) d->attn_fused_on = atoi(e) != 0;
-    d->attn_fused_cfg = d->attn_fused_on;
-    if (const char* e = getenv("MC_HANDOFF_REARM")) d->rearm_after = std::max(0, atoi(e));
-    if (const char* e = getenv("MC_ATTN_WO")) d->attn_wo_on = atoi(e) != 0;
-    if (const char* e = getenv("MC_HANDOFF_FAST")) d->handoff_fast = atoi(e) != 0;
-    if (const char* e = getenv("MC_ATTN_QKV")) d->attn_qkv_on = atoi(e) != 0;
-    if (const char* e = getenv("MC_LIN_K4")) d->lin_k4_on = atoi(e) != 0;
-    if (const char* e = getenv("MC_CHAIN_W13")) d->chain_w13_on = atoi(e) != 0;
-    if (const char* e = getenv("MC_ATTN_QKN")) d->attn_qkn_on = atoi(e) != 0;
-    if (const char* e = getenv("MC_ATTN_WO_QKN")) d->attn_wo_qkn_on = atoi(e) != 0;
-    if (const char* e = getenv("MC_ATTN_QKV_QKN")) d->attn_qkv_qkn_on = atoi(e) != 0;
-    if (const char* e = getenv("MC_ATTN_QKV_ONLY")) d->attn_qkv_only_on = atoi(e) != 0;
-    if (const char* e = getenv("MC_ATTN_I4_WIDE")) d->attn_i4_wide_on = atoi(e) != 0;
-    if (const char* e = getenv("MC_LAZY_PICK")) d->lazy_pick_on = atoi(e) != 0;
-    if (const char* e = getenv("MC_PF2")) d->pf2_on = atoi(e) != 0;
-    if (const char* e = getenv("MC_KV_VIRTUAL")) d->kv_virtual_on = atoi(e) != 0;
-    if (const char* e = getenv("MC_ATTN_I8")) d->attn_i8_on = atoi(e) != 0;
-    if (const char* e = getenv("MC_PF_ATTN8")) d->pf_attn8_on = atoi(e) != 0;
-    if (const char* e = getenv("MC_PF_ATTN8_ROWS")) d->pf_attn8_rows = std::max(1, atoi(e));
-    if (const char* e = getenv("MC_PF_ATTN8_ROWS64")) d->pf_attn8_rows64 = std::max(1, atoi(e));
-    if (const char* e = getenv("MC_PF_ATTN8_ROWS256")) d->pf_attn8_rows256 = std::max(1, atoi(e));
-    if (const char* e = getenv("MC_PF_GEMM8")) d->pf_g8_on = atoi(e) != 0;
-    if (const char* e = getenv("MC_PF_ROPE_PACK")) d->pf_rope_pack = atoi(e) != 0;
-    if (const char* e = getenv("MC_PF_PLAIN_COPY")) d->pf_plain_mode = atoi(e) != 0 ? 1 : 0;
-    if (const char* e = getenv("MC_PF_GEMM8_ROWS")) d->pf_g8_rows = std::max(1, atoi(e));
-    if (const char* e = getenv("MC_PF_GEMM8_MAXSPLIT")) d->pf_g8_max_splits = std::max(1, atoi(e));
-    if (const char* e = getenv("MC_PF_GEMM8_MINKT")) d->pf_g8_min_ktiles = std::max(1, atoi(e));
-    if (const char* e = getenv("MC_PF_BLASLT")) {
-        d->pf_lib_on = atoi(e) != 0;
-        d->pf_lib_force = atoi(e) == 2;
-    }
-    if (const char* e = getenv("MC_PF_BLASLT_TUNE")) d->pf_lib_tune = atoi(e) != 0;
-    if (const char* e = getenv("MC_PF_BLASLT_ROWS")) d->pf_lib_rows = std::max(1, atoi(e));
-    if (const char* e = getenv("MC_PF_BLASLT_TILES")) d->pf_lib_tiles = std::max(1, atoi(e));
-    if (const char* e = getenv("MC_PF_FOLD")) d->pf_fold_on = atoi(e) != 0;
-    if (const char* e = getenv("MC_ATTN_T2")) d->attn_t2_on = atoi(e) != 0;
-    if (const char* e = getenv("MC_ATTN_FUSED_WGS")) d->attn_fused_max_wgs_per_cu = (unsigned)std::max(1, std::min(4, atoi(e)));
-    if (const char* e = getenv("MC_LING_HALF")) d->ling_half = atoi(e) != 0;
-    if (const char* e = getenv("MC_LIN_SPLIT")) d->lin_split = atoi(e) != 0;
-    if (const char* e = getenv("MC_I8_LING14")) d->i8_ling14 = atoi(e) != 0;
-    if (const char* e = getenv("MC_GEMV_LING")) d->gemv_ling = atoi(e) != 0;
-    if (const char* e = getenv("MC_LIN_WAVES")) d->lin_waves = std::max(1, std::min(16, atoi(e)));
-    if (const char* e = getenv("MC_GEMMA_UNFUSED")) d->gemma_fuse = atoi(e) == 0;
-    if (const char* e = getenv("MC_GEMV_M4")) d->gemv_m4 = atoi(e);
-    if (const char* e = getenv("MC_PV_BLOCK")) d->pv_block = atoi(e);
-    if (d->pv_block % 64 || d->pv_block < 256 || d->pv_block > 1024) d->pv_block = 1024;
-    if (d->gemv_block % 64 || d->gemv_block < 64 || d->gemv_block > 1024) d->gemv_block = 256;
-    if (d->gemv_wgs_per_cu < 1) d->gemv_wgs_per_cu = 2;
+    d->opt = read_options();
+    d->attn_fused_on = d->opt.attn_fused;
+    d->rearm_after = d->opt.rearm_after;
+    d->pf_lib_on = d->opt.pf_lib;
 
     const size_t tb = d->tb;
     const int dim = c.dim, H = c.n_heads, KV = c.n_kv_heads, hd = c.head_dim;
@@ -2382,7 +2439,7 @@ mc_decoder_create(mc_device* dev, mc_library* lib, mc_queue* q, const mc_decoder
     // slots (four rounds of loads); from 8192 slots on, ranges of 2048 slots + one reduce launch
     // (S = 8192, int8 weights: 1 range 369, 2: 391, 4: 402, 8: 383, 16: 347 tokens/s)
     d->pv_ranges = c.max_seq_len >= 8192 ? std::min(16, c.max_seq_len / 2048) : 1;
-    if (const char* e = getenv("MC_PV_RANGES")) d->pv_ranges = std::max(1, std::min(64, atoi(e)));
+    if (d->opt.pv_ranges) d->pv_ranges = d->opt.pv_ranges;
     A(d->pv_parts, (size_t)std::max(d->pv_ranges, 4) * H * hd * 4);
     if (d->tb == 2) {
         // (twice: the XCD-local `fast` copy of every granule sits behind the `slow` one, handoff.h)
@@ -2414,8 +2471,6 @@ mc_decoder_create(mc_device* dev, mc_library* lib, mc_queue* q, const mc_decoder
         blk.per_wg = {(unsigned long long*)d->pick_keys, nullptr, d->state, d->tokens_dev};
         MC_HIP(hipMemcpy(d->pick_desc, &blk, sizeof blk, hipMemcpyHostToDevice));
     }
-    if (const char* e = getenv("MC_HEAD_PICK")) d->head_pick_mode = std::max(0, std::min(2, atoi(e)));
-    d->head_pick_on = d->head_pick_mode != 0;
     d->rope_rows = 2 * c.max_seq_len; // nn/embedding.h:171: _M_seq_len(max_seq_len * 2)
     A(d->rope_cos[0], (size_t)d->rope_rows * (hd / 2) * 4);
     A(d->rope_sin[0], (size_t)d->rope_rows * (hd / 2) * 4);
@@ -2423,8 +2478,6 @@ mc_decoder_create(mc_device* dev, mc_library* lib, mc_queue* q, const mc_decoder
         A(d->rope_cos[1], (size_t)d->rope_rows * (hd / 2) * 4);
         A(d->rope_sin[1], (size_t)d->rope_rows * (hd / 2) * 4);
     }
-    if (const char* e = getenv("MC_PF_TIMING")) d->pf_timing = atoi(e) != 0;
-    if (const char* e = getenv("MC_PF_TWO_PASS")) d->pf_two_pass = atoi(e) != 0;
     d->layers.resize(d->n_own);
     for (int i = 0; i < d->n_own; i++) {
         layer_w& L = d->layers[i];
@@ -3238,26 +3291,13 @@ mc_decoder_gemv_kernel_name(mc_decoder* d, const char* which, char* buf, size_t 
     if (!d || !which || !buf || !cap) return fail(MC_ERR_INVALID_ARGUMENT, "mc_decoder_gemv_kernel_name: bad argument");
     std::string name;
     if (std::string(which) == "attn") {
-        // the decode attention of the first owned block: one launch with Wo, one launch, or scores + P.V (run_layers)
+        // the decode attention of the first owned block: one launch with Wo, one launch, or scores + P.V (plan_block)
         mc_status s0 = check_ready(d);
         if (s0 != MC_OK) return s0;
         if (d->layers.empty()) return fail(MC_ERR_INVALID_ARGUMENT, "mc_decoder_gemv_kernel_name: this stage owns no block");
-        const linear_w& wo = d->layers[0].wo;
         d->query_occupancy();
-        const layer_w& L0 = d->layers[0];
-        const int wt = d->attn_qkv_wo_w_tiles(L0), i4w = d->attn_qkv_wo_i4_wide_tiles(L0);
-        const std::string i4name = "mc_attn_qkv_wo_i4_" + d->tname + "_hd" + std::to_string(d->cfg.head_dim) + "_k" + std::to_string(wo.in / 2048) + "_q" +
-                                   std::to_string(L0.qkv.in / 2048);
-        const int chf = wt == 1 ? d->attn_qkv_wo_w13_w_fetch(L0) : 0; // (round 6: ffn_norm + w1|w3 + act*mul in the launch too)
-        name = chf ? "mc_attn_qkv_wo_w13_w_bfloat_hd64_k4_q4_f" + std::to_string(chf / 10) + "p" + std::to_string(chf % 10)
-               : wt ? std::string("mc_attn_qkv_wo_w_bfloat_hd64_k4_q4") + (wt > 1 ? "_t" + std::to_string(wt) : std::string())
-               : d->attn_qkv_wo_i8_tiles(L0) ? "mc_attn_qkv_wo_i8_bfloat_hd128_k4_q4_t" + std::to_string(d->attn_qkv_wo_i8_tiles(L0))
-               : d->attn_qkv_wo_fused(L0) ? i4name
-               : i4w ? i4name + "_t" + std::to_string(i4w)
-               : d->attn_wo_fused(wo) ? "mc_attn_wo_i4_" + d->tname + "_hd" + std::to_string(d->cfg.head_dim) + "_k" + std::to_string(wo.in / 2048)
-               : d->attn_fused()    ? "mc_attn_fused_" + d->tname
-               : d->attn_fused_t2() ? "mc_attn_fused_t2_" + d->tname
-                                    : "mc_attn_scores_" + d->tname + " + mc_attn_pv_" + d->tname;
+        const mc_decoder::block_plan P = d->plan_block(d->layers[0]);
+        name = P.form == mc_decoder::block_form::scores_pv ? P.name + " + mc_attn_pv_" + d->tname : P.name;
         const size_t n0 = std::min(cap - 1, name.size());
         memcpy(buf, name.data(), n0);
         buf[n0] = 0;
@@ -3289,10 +3329,7 @@ mc_decoder_time_gemv(mc_decoder* d, const char* which, int32_t repeats, float* t
     const bool gemma = d->cfg.family == MC_FAMILY_GEMMA3;
     double bytes = 0;
     int launches = 0;
-    // MC_TIME_GEMV_LAYERS=n (tuning aid): every "layer" of the pass uses the weights of layer
-    // i % n, so with a small n the matrices stay resident in the 256 MiB Infinity Cache
-    const char* lim_env = getenv("MC_TIME_GEMV_LAYERS");
-    const size_t lim = lim_env && atoi(lim_env) > 0 ? (size_t)atoi(lim_env) : d->layers.size();
+    const size_t lim = d->opt.time_gemv_layers ? (size_t)d->opt.time_gemv_layers : d->layers.size(); // (MC_TIME_GEMV_LAYERS)
     auto pass = [&](bool count) -> mc_status {
         mc_status r = MC_OK;
         for (size_t li = 0; li < d->layers.size(); li++) {

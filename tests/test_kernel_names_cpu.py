@@ -60,18 +60,18 @@ def test_decode_and_reference_kernels_present(symbols):
               # ... with the Wo GEMV behind it (decoder.cc attn_wo_fused: head_dim x KiB per Wo row)
               "mc_attn_wo_i4_bfloat_hd128_k2", "mc_attn_wo_i4_bfloat_hd64_k1", "mc_attn_wo_i4_bfloat_hd256_k2",
               "mc_attn_qkv_wo_i4_bfloat_hd128_k2_q2",  # wq|wk|wv, attention and Wo in one launch (round 4)
-              "mc_attn_qkv_wo_i4_bfloat_hd128_k2_q2_t2", "mc_attn_qkv_wo_i4_bfloat_hd128_k2_q2_t4",  # ... 128- / 256-slot ranges (attn_qkv_wo_i4_wide_tiles)
-              "mc_attn_qkv_wo_w_bfloat_hd64_k4_q4",    # ... for plain bfloat weights (decoder.cc attn_qkv_wo_w_fused)
-              "mc_attn_qkv_wo_w13_w_bfloat_hd64_k4_q4_f3p3", "mc_attn_qkv_wo_w13_w_bfloat_hd64_k4_q4_f4p4",  # ... + ffn_norm + w1|w3 + act*mul (round 6: attn_qkv_wo_w13_w_fetch)
+              "mc_attn_qkv_wo_i4_bfloat_hd128_k2_q2_t2", "mc_attn_qkv_wo_i4_bfloat_hd128_k2_q2_t4",  # ... 128- / 256-slot ranges (decoder.cc plan_block, form 5)
+              "mc_attn_qkv_wo_w_bfloat_hd64_k4_q4",    # ... for plain bfloat weights (decoder.cc plan_block, form 2)
+              "mc_attn_qkv_wo_w13_w_bfloat_hd64_k4_q4_f3p3", "mc_attn_qkv_wo_w13_w_bfloat_hd64_k4_q4_f4p4",  # ... + ffn_norm + w1|w3 + act*mul (round 6: decoder.cc plan_block form 1, chain_w13_fetch)
               "mc_gemv_i4_bfloat_lin12k4_p0_e0", "mc_gemv_i4_bfloat_lin12k4_p0_e1",  # Gemma-7B's w2: the K range of a pair over four waves (gemv_ksplit.h)
-              "mc_attn_qkv_i4_bfloat_hd128_q4",        # ... without Wo, rows of 4 KiB (Llama-3-70B; decoder.cc attn_qkv_only_ok)
+              "mc_attn_qkv_i4_bfloat_hd128_q4",        # ... without Wo, rows of 4 KiB (Llama-3-70B; decoder.cc plan_block, form 6)
               "mc_attn_qkv_wo_i8_bfloat_hd128_k4_q4_t1", "mc_attn_qkv_wo_i8_bfloat_hd128_k4_q4_t2", "mc_attn_qkv_wo_i8_bfloat_hd128_k4_q4_t4",
-              "mc_attn_qkv_wo_w_bfloat_hd64_k4_q4_t2", "mc_attn_qkv_wo_w_bfloat_hd64_k4_q4_t4",   # wide ranges of the plain-bfloat launch (attn_qkv_wo_w_tiles)  # ... for int8 weights (attn_qkv_wo_i8_tiles)
+              "mc_attn_qkv_wo_w_bfloat_hd64_k4_q4_t2", "mc_attn_qkv_wo_w_bfloat_hd64_k4_q4_t4",   # wide ranges of the plain-bfloat launch (plan_block, form 2)  # ... for int8 weights (plan_block, form 3)
               "mc_attn_fused_qkn_bfloat",              # gemma3: q/k-norm + rope + cache write inside the one-launch attention
-              "mc_attn_wo_qkn_i4_bfloat_hd256_k2_t1", "mc_attn_wo_qkn_i4_bfloat_hd256_k2_t2",  # ... with Wo in the launch too (attn_wo_qkn_tiles)
+              "mc_attn_wo_qkn_i4_bfloat_hd256_k2_t1", "mc_attn_wo_qkn_i4_bfloat_hd256_k2_t2",  # ... with Wo in the launch too (plan_block, tail a)
               "mc_attn_qkv_wo_qkn_i4_bfloat_hd256_k2_p1_t2", "mc_attn_qkv_wo_qkn_i4_bfloat_hd256_k2_p2_t2",
               "mc_attn_qkv_wo_qkn_i4_bfloat_hd256_k2_p1_t1", "mc_attn_qkv_wo_qkn_i4_bfloat_hd256_k2_p2_t1",
-              "mc_attn_qkv_wo_qkn_i4_bfloat_hd256_k2_p1_t4", "mc_attn_qkv_wo_qkn_i4_bfloat_hd256_k2_p2_t4", "mc_attn_wo_qkn_i4_bfloat_hd256_k2_t4",  # ... and wq|wk|wv + the norms (attn_qkv_wo_qkn_ok)
+              "mc_attn_qkv_wo_qkn_i4_bfloat_hd256_k2_p1_t4", "mc_attn_qkv_wo_qkn_i4_bfloat_hd256_k2_p2_t4", "mc_attn_wo_qkn_i4_bfloat_hd256_k2_t4",  # ... and wq|wk|wv + the norms (plan_block, form 8)
               "mc_attn_fused_t2_bfloat",               # 128-slot ranges (decoder.cc attn_fused_t2: S = 8192)
               # the prompt pass on the quad-interleaved weight copy and its consumers with the split-K reduce inside (round 4)
               "mc_pf2_repack_i4", "mc_pf2_gemm_i4_bfloat", "mc_pf_rope_cache_parts_bfloat", "mc_pf_rope_cache_v4_bfloat", "mc_pf_rope_cache_parts_v4_bfloat", "mc_pf_act_mul_parts_bfloat",
