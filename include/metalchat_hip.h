@@ -487,8 +487,41 @@ mc_status mc_extend_rows(mc_batch* b, const int32_t* tokens, const int32_t* lens
  * next_tokens[B] (may be null): pick[a_r] -- the token to feed at position positions[r] + a_r + 1; -1 for a row not in the call. */
 mc_status mc_verify_rows(mc_batch* b, const int32_t* tokens, const int32_t* lens, const int32_t* positions,
                          int32_t* accepted, int32_t* next_tokens, int32_t* picks);
-/* test aid: the [sum of lens][vocab] logits of T of the last mc_verify_rows call, packed like tokens */
+/* test aid: the [sum of lens][vocab] logits of T of the last mc_verify_rows or (Part 2g) mc_tree_verify call on the batch,
+ * packed like its tokens; refused while the batch has made neither call */
 mc_status mc_verify_get_logits(mc_batch* b, void* logits_T);
+
+/* ================================================================================================
+ * Part 2g -- speculative verify over a draft TREE per row.  Part 2f spends a row's 15 drafts on one guess, and everything behind
+ * the first wrong draft is lost; a tree of the same <= 16 nodes carries alternatives at the shallow depths where rejections
+ * happen (several prompt-lookup matches, a small model's runner-up picks) at the same price: the same packed rows, the same one
+ * pass over the weights and the head.  Row r's chunk is nodes [0, n), n = lens[r], 2 <= n <= 16 (MC_VERIFY_MAX_LEN): node 0 is the
+ * row's last accepted token (not yet in its cache), nodes [1, n) are drafts, and parents[off_r + i] names node i's parent:
+ * parents[off_r] == -1 and 0 <= parents[off_r + i] < i for i >= 1 -- topological order, so a node's index is at least its depth.
+ *   depth(0) = 0, depth(i) = depth(parent(i)) + 1;  node i sits at position positions[r] + depth(i) (its rope position)
+ *   node i attends to every cache column below positions[r], and among the chunk's nodes to its ancestors and itself -- nothing else
+ *   pick[i] = the target's greedy pick after node i: what a chain of decode steps over the path root -> i computes
+ * Acceptance, on the device: cur = 0; among cur's children in ascending node index the first j with tokens[j] == pick[cur]
+ * becomes cur; stop when there is none.  a_r = depth(cur).  Equal tokens on two siblings are legal (the lower index wins); a match
+ * under a rejected node never counts.  During the pass node i's K / V live in cache slot positions[r] + i; afterwards the accepted
+ * path's K / V are moved to slots positions[r] + d, d = 0 .. a_r, in every layer (one launch, no host round trip), the row's
+ * length is positions[r] + a_r + 1, and mc_batch_get_logits holds the logits of the last accepted node for each row in the call.
+ * Slots past the new length may hold what the call wrote there: the rewound state every rows call handles.
+ * A tree that is a chain (parents = -1, 0, 1, ...) computes Part 2f's call bit for bit: the same K / V, logits, picks, accepted.
+ * Any other tree holds a path's keys in other slots than a chain would, so its sums take another order: the same values within
+ * the rounding of the arithmetic, not the same bits.
+ * Greedy only, refused as in Part 2f.  All of Part 2e's refusals apply with the texts prefixed "mc_tree_verify: ", and, naming the
+ * row: a root whose parent is not -1, a parent outside [0, i), a chunk longer than 16; a null pointer (parents included) is
+ * refused as a null argument.  MC_ERR_INVALID_ARGUMENT, nothing enqueued.  Scratch, the decoder, rows outside the call, and the
+ * independence of a row's bits from B, placement and company are as in Part 2f.
+ * ------------------------------------------------------------------------------------------ */
+/* tokens / lens / positions: packed exactly as in Part 2f; parents: packed like tokens.
+ * accepted[B]: a_r.  next_tokens[B] (may be null): pick[cur], to feed at position positions[r] + a_r + 1.
+ * paths[B][MC_VERIFY_MAX_LEN] (may be null): the accepted node at each depth 0 .. a_r, -1 behind it.
+ * picks (sum of lens ids, packed like tokens; may be null): the greedy pick after every node.
+ * Rows not in the call: -1 in accepted, next_tokens and all of their paths row. */
+mc_status mc_tree_verify(mc_batch* b, const int32_t* tokens, const int32_t* parents, const int32_t* lens, const int32_t* positions,
+                         int32_t* accepted, int32_t* next_tokens, int32_t* paths, int32_t* picks);
 
 /* Host-side helpers shared by tests and the synthetic initialiser. */
 /* value in [-7,7] (bits = 4) or [-127,127] (bits = 8), zero mean, of element (row, col) of matrix `matrix_id` */

@@ -48,7 +48,8 @@ struct mc_batch {
     int32_t* stop_dev = nullptr;          // the stop ids of a ragged call
     int stop_cap = 0;
     std::vector<int32_t> stop_host;
-    char* pp_tab = nullptr;               // a packed prompt pass (mc_rows_prefill): pp_seg[BATCH_MAX], then the pp_tile table
+    char* pp_tab = nullptr;               // a packed prompt pass (mc_rows_prefill): pp_seg[BATCH_MAX], then the pp_tile table,
+                                          // then (mc_tree_verify) one tv_node per packed row
     int pp_tab_cap = 0;                   // (bytes)
     std::vector<char> pp_host;            // the same bytes on the host: one upload
     px_range* px_tab = nullptr;           // mc_extend_rows: the range table
@@ -57,12 +58,12 @@ struct mc_batch {
     std::vector<px_group> px_groups;
     float *px_sums = nullptr, *px_part = nullptr; // scratch of one launch group: [px_slots][H][16], [px_slots][H][16][hd]
     int px_slots = 0;
-    // mc_verify_rows, reserved at the first call: the normed rows [128][dim], their logits [128][vocab], and the call's results
-    // on the device: accepted[B], next_tokens[B], picks[128]
+    // mc_verify_rows and mc_tree_verify, reserved at the first call: the normed rows [128][dim], their logits [128][vocab], and the
+    // call's results on the device: accepted[B], next_tokens[B], picks[M], then (mc_tree_verify) paths[B][MC_VERIFY_MAX_LEN]
     void *v_xn = nullptr, *v_logits = nullptr;
     int32_t* v_out = nullptr;
     int v_xn_cap = 0, v_logits_cap = 0, v_out_cap = 0;
-    int v_rows = 0;                       // packed rows of the last mc_verify_rows call (0: none yet)
+    int v_rows = 0;                       // packed rows of the last mc_verify_rows / mc_tree_verify call (0: none yet)
     std::vector<int32_t> v_host;
 
     ~mc_batch()
@@ -117,6 +118,7 @@ struct mc_batch {
     // the two tables inside pp_tab / pp_host.data()
     static pp_seg* pp_segs(char* tab) { return reinterpret_cast<pp_seg*>(tab); }
     static pp_tile* pp_tiles(char* tab) { return reinterpret_cast<pp_tile*>(tab + sizeof(pp_seg) * BATCH_MAX); }
+    static tv_node* tv_nodes(char* tab, int ntiles) { return reinterpret_cast<tv_node*>(pp_tiles(tab) + ntiles); }
 
     char* kc_of(int layer, int row) const { return (char*)kc + ((size_t)layer * B + row) * cache_elems * 2; }
     char* vt_of(int layer, int row) const { return (char*)vt + ((size_t)layer * B + row) * cache_elems * 2; }
@@ -230,9 +232,11 @@ struct mc_batch {
     }
 
     // mc_verify_rows: the final norm, the head and a greedy pick for each of the M packed rows `xrows` of a call, then per segment
-    // the acceptance of its drafts (`tokens`: the call's ids on the device) and the accepted row's logits into logits[row]
+    // the acceptance of its drafts (`tokens`: the call's ids on the device) and the accepted row's logits into logits[row].
+    // nodes (mc_tree_verify): the chunks are trees -- the walk in place of the prefix rule, then the accepted path's K / V
+    // moved into place in every layer, both reading the device's own results
     mc_status
-    verify_head(const void* xrows, const int32_t* tokens, int M, int nseg)
+    verify_head(const void* xrows, const int32_t* tokens, int M, int nseg, const tv_node* nodes = nullptr)
     {
         const mc_decoder_config& c = p.cfg;
         const batch_linear& L = p.output;
@@ -246,9 +250,18 @@ struct mc_batch {
         int32_t* picks = v_out + 2 * B;
         if ((s = launch("mc_v_argmax_bfloat", 1, M, 1, 1024, 0, pack((const void*)v_logits, (uint32_t)c.vocab, picks))) != MC_OK) return s;
         const unsigned gx = std::min(64u, ((unsigned)c.vocab / 8 + 255) / 256);
-        return launch("mc_v_accept", gx, nseg, 1, 256, 0,
-                      pack((const pp_seg*)pp_segs(pp_tab), tokens, (const int32_t*)picks, (const void*)v_logits, (uint32_t)c.vocab, v_out, v_out + B,
-                           logits));
+        if (!nodes)
+            return launch("mc_v_accept", gx, nseg, 1, 256, 0,
+                          pack((const pp_seg*)pp_segs(pp_tab), tokens, (const int32_t*)picks, (const void*)v_logits, (uint32_t)c.vocab, v_out, v_out + B,
+                               logits));
+        int32_t* paths = picks + M;
+        s = launch("mc_tv_accept", gx, nseg, 1, 256, 0,
+                   pack((const pp_seg*)pp_segs(pp_tab), tokens, nodes, (const int32_t*)picks, (const void*)v_logits, (uint32_t)c.vocab, v_out,
+                        v_out + B, paths, logits));
+        if (s != MC_OK) return s;
+        return launch("mc_tv_compact_bfloat", ((unsigned)(c.n_kv_heads * c.head_dim) + 255) / 256, nseg, (unsigned)p.layers.size(), 256, 0,
+                      pack((const pp_seg*)pp_segs(pp_tab), (const int32_t*)v_out, (const int32_t*)paths, kc, vt, (uint64_t)cache_elems,
+                           (uint32_t)B, (uint32_t)c.n_kv_heads, (uint32_t)c.head_dim, (uint32_t)c.max_seq_len));
     }
 
     // rows' tokens and step indices for token 0 of a call (step_index = r: seed pair r % n_pairs, tokens_out[0][r]); a ragged
@@ -691,10 +704,40 @@ rows_ranges(mc_batch* b, int ntiles, int slots)
 struct verify_out {
     int32_t* accepted; // [B]
     int32_t* picks;    // [M], may be null
+    // mc_tree_verify: the chunks are trees
+    const int32_t* parents = nullptr; // [M], packed like the tokens
+    int32_t* paths = nullptr;         // [B][MC_VERIFY_MAX_LEN], may be null
 };
 
-// mc_rows_prefill, mc_extend_rows and mc_verify_rows: one body, `extend` selects the attention (and `who` the texts), `v` the
-// head over every packed row in place of the head over each row's last
+// mc_tree_verify: every row's `parents` (root -1, then 0 <= parent < i), and the node table behind the tiles of pp_host
+mc_status
+tree_check(const mc_batch* b, const std::string& who, const int32_t* parents, const int32_t* lens)
+{
+    for (int r = 0, off = 0; r < b->B; off += lens[r], r++) {
+        const std::string row = who + ": row " + std::to_string(r) + ": ";
+        if (lens[r] == 0) continue;
+        if (parents[off] != -1) return fail(MC_ERR_INVALID_ARGUMENT, row + "the parent of node 0 (the root) must be -1, not " + std::to_string(parents[off]));
+        for (int32_t i = 1; i < lens[r]; i++)
+            if (parents[off + i] < 0 || parents[off + i] >= i)
+                return fail(MC_ERR_INVALID_ARGUMENT, row + "the parent of node " + std::to_string(i) + " is " + std::to_string(parents[off + i]) +
+                                                         ", outside [0, " + std::to_string(i) + ") (nodes come in topological order)");
+    }
+    return MC_OK;
+}
+void
+tree_nodes(mc_batch* b, const int32_t* parents, const int32_t* lens, int ntiles, int M)
+{
+    b->pp_host.resize(b->pp_host.size() + sizeof(tv_node) * M);
+    tv_node* node = mc_batch::tv_nodes(b->pp_host.data(), ntiles);
+    for (int r = 0, off = 0; r < b->B; off += lens[r], r++)
+        for (int32_t i = 0; i < lens[r]; i++) {
+            const int32_t par = parents[off + i];
+            node[off + i] = i == 0 ? tv_node{0, 1u} : tv_node{node[off + par].depth + 1, node[off + par].anc | (1u << i)};
+        }
+}
+
+// mc_rows_prefill, mc_extend_rows, mc_verify_rows and mc_tree_verify: one body, `extend` selects the attention (and `who` the
+// texts), `v` the head over every packed row in place of the head over each row's last, v->parents the tree form of that
 mc_status
 rows_pass(mc_batch* b, const char* who, bool extend, const int32_t* tokens, const int32_t* lens, const int32_t* positions, int32_t* next_tokens,
           const verify_out* v = nullptr)
@@ -709,11 +752,14 @@ rows_pass(mc_batch* b, const char* who, bool extend, const int32_t* tokens, cons
             if (lens[r] > MC_VERIFY_MAX_LEN)
                 return fail(MC_ERR_INVALID_ARGUMENT, std::string(who) + ": row " + std::to_string(r) + ": a chunk of " + std::to_string(lens[r]) +
                                                          " tokens is longer than MC_VERIFY_MAX_LEN (" + std::to_string(MC_VERIFY_MAX_LEN) + ")");
+    const bool tree = v && v->parents;
+    if (tree && (s = tree_check(b, who, v->parents, lens)) != MC_OK) return s;
     MC_HIP(hipSetDevice(b->p.ordinal));
     rows_tables(b, lens, positions, ntiles);
+    if (tree) tree_nodes(b, v->parents, lens, ntiles, M);
     // (enough for any call: at most max_seq_len rows in at most 8 segments)
     const int tiles_max = c.max_seq_len / PP_TILE_ROWS + BATCH_MAX;
-    if ((s = b->reserve(b->pp_tab, b->pp_tab_cap, (int)b->pp_host.size(), (int)(sizeof(pp_seg) * BATCH_MAX + sizeof(pp_tile) * tiles_max))) != MC_OK)
+    if ((s = b->reserve(b->pp_tab, b->pp_tab_cap, (int)b->pp_host.size(), (int)(sizeof(pp_seg) * BATCH_MAX + sizeof(pp_tile) * tiles_max + sizeof(tv_node) * MC_VERIFY_MAX_ROWS))) != MC_OK)
         return s;
     MC_HIP(hipMemcpyAsync(b->pp_tab, b->pp_host.data(), b->pp_host.size(), hipMemcpyHostToDevice, b->p.stream));
     packed_prefill pk;
@@ -721,6 +767,7 @@ rows_pass(mc_batch* b, const char* who, bool extend, const int32_t* tokens, cons
     pk.nseg = nseg;
     pk.tiles = mc_batch::pp_tiles(b->pp_tab);
     pk.ntiles = ntiles;
+    if (tree) pk.nodes = mc_batch::tv_nodes(b->pp_tab, ntiles);
     MC_HIP(hipMemcpyAsync(b->rows, b->rows_host.data(), sizeof(step_state) * B, hipMemcpyHostToDevice, b->p.stream));
     if ((s = b->ensure_tokens(1)) != MC_OK) return s;
     MC_HIP(hipMemsetAsync(b->tokens_dev, 0xFF, sizeof(int32_t) * B, b->p.stream));
@@ -757,22 +804,25 @@ rows_pass(mc_batch* b, const char* who, bool extend, const int32_t* tokens, cons
         // (M <= 128 here; the scratch is sized for any call)
         if ((s = b->reserve(b->v_xn, b->v_xn_cap, M, MC_VERIFY_MAX_ROWS, (size_t)c.dim * 2)) != MC_OK ||
             (s = b->reserve(b->v_logits, b->v_logits_cap, M, MC_VERIFY_MAX_ROWS, (size_t)c.vocab * 2)) != MC_OK ||
-            (s = b->reserve(b->v_out, b->v_out_cap, 2 * B + M, 2 * BATCH_MAX + MC_VERIFY_MAX_ROWS)) != MC_OK)
+            (s = b->reserve(b->v_out, b->v_out_cap, 2 * B + M + MC_VERIFY_MAX_LEN * B, 2 * BATCH_MAX + MC_VERIFY_MAX_ROWS + MC_VERIFY_MAX_LEN * BATCH_MAX)) !=
+                MC_OK)
             return s;
         MC_HIP(hipMemsetAsync(b->v_out, 0xFF, sizeof(int32_t) * 2 * B, b->p.stream)); // -1: a row not in the call
+        if (tree) MC_HIP(hipMemsetAsync(b->v_out + 2 * B + M, 0xFF, sizeof(int32_t) * MC_VERIFY_MAX_LEN * B, b->p.stream)); // ... its path
         pk.rows_all = &rows_all;
         pk.tokens_dev = &ids;
     }
     if ((s = decoder_prefill_packed(b->d, tokens, M, pk)) != MC_OK) return s;
-    if ((s = v ? b->verify_head(rows_all, ids, M, nseg) : b->head("_rows_bfloat")) != MC_OK) return s;
+    if ((s = v ? b->verify_head(rows_all, ids, M, nseg, pk.nodes) : b->head("_rows_bfloat")) != MC_OK) return s;
     MC_HIP(hipStreamSynchronize(b->p.stream)); // (`tokens` is the caller's buffer; the tables are read by the launches)
     if (v) {
         b->v_rows = M;
-        b->v_host.resize(2 * B + M);
+        b->v_host.resize(2 * B + M + (tree ? MC_VERIFY_MAX_LEN * B : 0));
         MC_HIP(hipMemcpy(b->v_host.data(), b->v_out, sizeof(int32_t) * b->v_host.size(), hipMemcpyDeviceToHost));
         std::copy_n(b->v_host.begin(), B, v->accepted);
         if (next_tokens) std::copy_n(b->v_host.begin() + B, B, next_tokens);
         if (v->picks) std::copy_n(b->v_host.begin() + 2 * B, M, v->picks);
+        if (v->paths) std::copy_n(b->v_host.begin() + 2 * B + M, MC_VERIFY_MAX_LEN * B, v->paths);
         // the rejected drafts' slots stay written past the length: the rewound state every rows call handles
         for (int r = 0; r < B; r++)
             if (lens[r] > 0) b->lengths[r] = positions[r] + v->accepted[r] + 1;
@@ -814,6 +864,20 @@ mc_verify_rows(mc_batch* b, const int32_t* tokens, const int32_t* lens, const in
                     "mc_verify_rows: the decoder's sampler is not greedy (accepting sampled drafts needs the draft's probabilities)");
     const verify_out v{accepted, picks};
     return rows_pass(b, "mc_verify_rows", true, tokens, lens, positions, next_tokens, &v);
+}
+
+// ---- Part 2g: speculative verify over a draft tree per row ----
+
+mc_status
+mc_tree_verify(mc_batch* b, const int32_t* tokens, const int32_t* parents, const int32_t* lens, const int32_t* positions, int32_t* accepted,
+               int32_t* next_tokens, int32_t* paths, int32_t* picks)
+{
+    if (!b || !tokens || !parents || !lens || !positions || !accepted) return fail(MC_ERR_INVALID_ARGUMENT, "mc_tree_verify: null argument");
+    if (decoder_sampler_of(b->d).kind != MC_SAMPLER_GREEDY)
+        return fail(MC_ERR_INVALID_ARGUMENT,
+                    "mc_tree_verify: the decoder's sampler is not greedy (accepting sampled drafts needs the draft's probabilities)");
+    const verify_out v{accepted, picks, parents, paths};
+    return rows_pass(b, "mc_tree_verify", true, tokens, lens, positions, next_tokens, &v);
 }
 
 mc_status

@@ -2113,9 +2113,11 @@ struct mc_decoder {
             if (gemm_to_parts(L.qkv, pf_xn, M, &sp, &gs)) {
                 if (gs != MC_OK) return gs;
                 if (pk)
-                    s = timed("rope_cache", [&] { return launch("mc_pp_rope_cache_parts_bfloat", pk_gx, 1, 1, 256, 0,
-                               pack((const void*)pf_part, sp, (uint32_t)M, pf_q, pk->segs, (uint32_t)pk->nseg, pk_kc, pk_vt, pk->cache_stride, pk->fcos,
-                                    pk->fsin, (uint32_t)H, (uint32_t)KV, (uint32_t)hd, (uint32_t)cfg.max_seq_len)); });
+                    s = timed("rope_cache", [&] {
+                        arg_pack a = pack((const void*)pf_part, sp, (uint32_t)M, pf_q, pk->segs, (uint32_t)pk->nseg, pk_kc, pk_vt, pk->cache_stride, pk->fcos,
+                                          pk->fsin, (uint32_t)H, (uint32_t)KV, (uint32_t)hd, (uint32_t)cfg.max_seq_len);
+                        if (pk->nodes) a.push(pk->nodes);
+                        return launch(pk->nodes ? "mc_tv_rope_cache_parts_bfloat" : "mc_pp_rope_cache_parts_bfloat", pk_gx, 1, 1, 256, 0, std::move(a)); });
                 else if (rope_v4)
                     s = timed("rope_cache", [&] { return launch("mc_pf_rope_cache_parts_v4_bfloat", rope_gx, 1, 1, 256, 0,
                                pack((const void*)pf_part, sp, (uint32_t)M, pf_q, L.kc, L.vt, rope_cos[L.rope_table], rope_sin[L.rope_table],
@@ -2130,9 +2132,11 @@ struct mc_decoder {
                 s = timed("gemm_qkv", [&] { return gemm(L.qkv, 0, pf_xn, pf_qkv, nullptr, M); });
                 if (s != MC_OK) return s;
                 if (pk)
-                    s = timed("rope_cache", [&] { return launch("mc_pp_rope_cache_bfloat", pk_gx, 1, 1, 256, 0,
-                               pack((const void*)pf_qkv, (uint32_t)M, pf_q, pk->segs, (uint32_t)pk->nseg, pk_kc, pk_vt, pk->cache_stride, pk->fcos, pk->fsin,
-                                    (uint32_t)H, (uint32_t)KV, (uint32_t)hd, (uint32_t)cfg.max_seq_len)); });
+                    s = timed("rope_cache", [&] {
+                        arg_pack a = pack((const void*)pf_qkv, (uint32_t)M, pf_q, pk->segs, (uint32_t)pk->nseg, pk_kc, pk_vt, pk->cache_stride, pk->fcos, pk->fsin,
+                                          (uint32_t)H, (uint32_t)KV, (uint32_t)hd, (uint32_t)cfg.max_seq_len);
+                        if (pk->nodes) a.push(pk->nodes);
+                        return launch(pk->nodes ? "mc_tv_rope_cache_bfloat" : "mc_pp_rope_cache_bfloat", pk_gx, 1, 1, 256, 0, std::move(a)); });
                 else if (rope_v4)
                     s = timed("rope_cache", [&] { return launch("mc_pf_rope_cache_v4_bfloat", rope_gx, 1, 1, 256, 0,
                                pack(pf_qkv, pf_q, L.kc, L.vt, rope_cos[L.rope_table], rope_sin[L.rope_table], (uint32_t)H, (uint32_t)KV, (uint32_t)hd,
@@ -2150,20 +2154,23 @@ struct mc_decoder {
                 // chunks that see their context (mc_extend_rows, kernels/extend_kernels.hip): the exp sums of every key range, then
                 // p V over the ranges, then the ranges of a tile added in order; two query heads of a kv head per workgroup where
                 // the grouping allows it.  A group is as many whole tiles as the scratch holds (one group unless the call is huge).
+                // Chunks that are trees (mc_tree_verify, pk->nodes): the mc_tv_* forms of the first two, the node table behind their arguments.
                 s = timed("attention", [&] {
                     const bool two = (H / KV) % 2 == 0;
                     const std::string sfx = std::string(two ? "2" : "") + "_bfloat_hd" + std::to_string(hd);
                     const unsigned gh = two ? H / 2 : H;
                     for (int g = 0; g < pk->ngroups; g++) {
                         const uint32_t e0 = (uint32_t)pk->groups[g].first, ne = (uint32_t)pk->groups[g].count;
-                        mc_status ls = launch("mc_px_sums" + sfx, gh, ne, 1, 256, 0,
-                                              pack(pf_q, pk->segs, pk->ranges, e0, (const void*)pk_kc, pk->cache_stride, pk->sums, (uint32_t)H,
-                                                   (uint32_t)(H / KV), (uint32_t)cfg.max_seq_len, scale_T, (const void*)pf_etab));
+                        arg_pack as = pack(pf_q, pk->segs, pk->ranges, e0, (const void*)pk_kc, pk->cache_stride, pk->sums, (uint32_t)H,
+                                           (uint32_t)(H / KV), (uint32_t)cfg.max_seq_len, scale_T, (const void*)pf_etab);
+                        if (pk->nodes) as.push(pk->nodes);
+                        mc_status ls = launch((pk->nodes ? "mc_tv_sums" : "mc_px_sums") + sfx, gh, ne, 1, 256, 0, std::move(as));
                         if (ls != MC_OK) return ls;
-                        ls = launch("mc_px_pv" + sfx, gh, ne, 1, 256, 0,
-                                    pack(pf_q, pk->segs, pk->ranges, e0, (const void*)pk_kc, (const void*)pk_vt, pk->cache_stride,
-                                         (const void*)pk->sums, pk->part, pf_att, (uint32_t)H, (uint32_t)(H / KV), (uint32_t)cfg.max_seq_len, scale_T,
-                                         (const void*)pf_etab));
+                        arg_pack ap = pack(pf_q, pk->segs, pk->ranges, e0, (const void*)pk_kc, (const void*)pk_vt, pk->cache_stride,
+                                           (const void*)pk->sums, pk->part, pf_att, (uint32_t)H, (uint32_t)(H / KV), (uint32_t)cfg.max_seq_len, scale_T,
+                                           (const void*)pf_etab);
+                        if (pk->nodes) ap.push(pk->nodes);
+                        ls = launch((pk->nodes ? "mc_tv_pv" : "mc_px_pv") + sfx, gh, ne, 1, 256, 0, std::move(ap));
                         if (ls != MC_OK) return ls;
                         if (!pk->groups[g].split) continue; // no tile of the group is split: mc_px_pv wrote the outputs
                         ls = launch("mc_px_reduce_bfloat_hd" + std::to_string(hd), H, ne, 1, 256, 0,

@@ -88,6 +88,9 @@ struct packed_prefill {
     // last layer ([M][dim]) and of the call's M token ids -- the decoder's prompt scratch, valid until its next prompt pass.
     const void** rows_all = nullptr;
     const int32_t** tokens_dev = nullptr;
+    // mc_tree_verify (kernels/tree_kernels.hip): the chunks are trees.  One tv_node per packed row, on the device; the rope + cache
+    // write and the extend attention then take their mc_tv_* names, with the table as one more argument behind their own.
+    const tv_node* nodes = nullptr;
 };
 // run_prefill over `tokens` (M ids, host) with the packed rope + cache and attention launches, then the gather into x_out; the
 // decoder's cache, step state, sampler, taps and head are not touched (its prompt scratch is)

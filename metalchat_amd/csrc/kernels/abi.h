@@ -107,6 +107,14 @@ struct px_range {
     int32_t pad0, pad1;
 };
 static_assert(sizeof(px_range) == 32 && offsetof(px_range, k_lo) == 8 && offsetof(px_range, first) == 16, "px_range: eight words");
+// one per packed row of mc_tree_verify (tree_kernels.hip): node i of its segment's draft tree
+struct alignas(8) tv_node {
+    int32_t depth; // edges from the root (node 0): the node sits at position pos + depth
+    uint32_t anc;  // bit j: node j of the segment is an ancestor of this node, or the node itself
+};
+static_assert(sizeof(tv_node) == 8 && alignof(tv_node) == 8 && offsetof(tv_node, depth) == 0 && offsetof(tv_node, anc) == 4,
+              "tv_node: two words, one 8-byte load");
+static_assert(MC_VERIFY_MAX_LEN <= 32, "tv_node::anc holds one bit per node of a chunk");
 
 } // namespace abi
 } // namespace mc

@@ -25,12 +25,15 @@
 // (px_range: abi.h)
 
 // the scores of one range: shared by the two passes.  Lane (l15, lg) of a wave holds row r0 + l15 (S^T = K Q^T, as pf_attn_kt_body).
-template <uint32_t HD, int NH>
+// TREE (tree_kernels.hip, mc_tree_verify): the chunk rows are the nodes of a draft tree, and a live row sees the keys below pos
+// and, among the chunk's own slots [pos, pos + 16), those of its ancestors and itself (tv_node::anc) -- the one difference.
+template <uint32_t HD, int NH, bool TREE = false>
 struct px_tile {
     static constexpr uint32_t DK = HD / 32;
     const bf16_t* kbase;
     uint32_t l15, lg, kg;
-    uint32_t pos_r; // the last visible key of this lane's row (pos + r), or 0 with `live` false
+    uint32_t pos_r; // the last visible key of this lane's row (pos + r), or 0 with `live` false; TREE: pos, the chunk's first slot
+    uint32_t anc;   // TREE only: this lane's row's tv_node::anc
     bool live;      // this lane's row is a row of the chunk
     uint32_t S;     // keys of the row's cache that any row of the tile may see: [0, S)
     float scale;
@@ -59,19 +62,20 @@ struct px_tile {
 #pragma unroll
         for (int i = 0; i < 4; i++) {
             const uint32_t key = blk + lg * 8 + h * 4 + i;
-            const bool vis = bool(int(live) & int(key <= pos_r));
+            const bool vis = TREE ? bool(int(live) & (int(key < pos_r) | (int(key < pos_r + 16u) & int((anc >> ((key - pos_r) & 15u)) & 1u))))
+                                  : bool(int(live) & int(key <= pos_r));
 #pragma unroll
             for (int j = 0; j < NH; j++) sv[j][i] = vis ? sv[j][i] : -INFINITY;
         }
     }
 };
 
-template <uint32_t HD, int NH>
-__device__ __forceinline__ px_tile<HD, NH>
+template <uint32_t HD, int NH, bool TREE = false>
+__device__ __forceinline__ px_tile<HD, NH, TREE>
 px_tile_of(const bf16_t* Q, const pp_seg& g, const px_range& e, const bf16_t* kc, uint64_t cache_stride, uint32_t H, uint32_t n_rep,
-           uint32_t max_seq, float scale, uint32_t h0)
+           uint32_t max_seq, float scale, uint32_t h0, const tv_node* nodes = nullptr)
 {
-    px_tile<HD, NH> t;
+    px_tile<HD, NH, TREE> t;
     const uint32_t lane = threadIdx.x & 63;
     t.l15 = lane & 15;
     t.lg = lane >> 4;
@@ -79,7 +83,12 @@ px_tile_of(const bf16_t* Q, const pp_seg& g, const px_range& e, const bf16_t* kc
     t.kbase = kc + (size_t)g.row * cache_stride + (size_t)(h0 / n_rep) * max_seq * HD;
     const uint32_t r = (uint32_t)e.r0 + t.l15, len = (uint32_t)g.len;
     t.live = r < len;
-    t.pos_r = t.live ? (uint32_t)g.pos + r : 0u;
+    if (TREE) {
+        t.pos_r = (uint32_t)g.pos;
+        t.anc = t.live ? nodes[(uint32_t)g.off + r].anc : 0u;
+    } else {
+        t.pos_r = t.live ? (uint32_t)g.pos + r : 0u;
+    }
     t.S = (uint32_t)g.pos + min((uint32_t)e.r0 + 16u, len);
     t.scale = scale;
     const uint32_t qr = (uint32_t)g.off + min(r, len - 1);
@@ -92,10 +101,10 @@ px_tile_of(const bf16_t* Q, const pp_seg& g, const px_range& e, const bf16_t* kc
 }
 
 // grid (H / NH, ranges of the launch), 256 threads
-template <uint32_t HD, int NH>
+template <uint32_t HD, int NH, bool TREE = false>
 __device__ __forceinline__ void
 px_sums_body(const bf16_t* Q, const pp_seg* segs, const px_range* tab, uint32_t ebase, const bf16_t* kc, uint64_t cache_stride, float* sums,
-             uint32_t H, uint32_t n_rep, uint32_t max_seq, float scale, const float* etab)
+             uint32_t H, uint32_t n_rep, uint32_t max_seq, float scale, const float* etab, const tv_node* nodes = nullptr)
 {
     constexpr uint32_t DK = HD / 32;
     __shared__ float wsum[NH][4][16];
@@ -105,7 +114,7 @@ px_sums_body(const bf16_t* Q, const pp_seg* segs, const px_range* tab, uint32_t 
     const px_range e = tab[ebase + blockIdx.y];
     const pp_seg g = segs[e.seg];
     const uint32_t wave = threadIdx.x >> 6, h0 = blockIdx.x * NH;
-    const px_tile<HD, NH> t = px_tile_of<HD, NH>(Q, g, e, kc, cache_stride, H, n_rep, max_seq, scale, h0);
+    const px_tile<HD, NH, TREE> t = px_tile_of<HD, NH, TREE>(Q, g, e, kc, cache_stride, H, n_rep, max_seq, scale, h0, nodes);
     const uint32_t b_lo = (uint32_t)e.k_lo / 32, b_end = ((uint32_t)e.k_hi + 31) / 32;
     float rsum[NH];
 #pragma unroll
@@ -139,10 +148,11 @@ px_sums_body(const bf16_t* Q, const pp_seg* segs, const px_range* tab, uint32_t 
 }
 
 // grid (H / NH, ranges of the launch), 256 threads
-template <uint32_t HD, int NH>
+template <uint32_t HD, int NH, bool TREE = false>
 __device__ __forceinline__ void
 px_pv_body(const bf16_t* Q, const pp_seg* segs, const px_range* tab, uint32_t ebase, const bf16_t* kc, const bf16_t* vt, uint64_t cache_stride,
-           const float* sums, float* part, bf16_t* out, uint32_t H, uint32_t n_rep, uint32_t max_seq, float scale, const float* etab)
+           const float* sums, float* part, bf16_t* out, uint32_t H, uint32_t n_rep, uint32_t max_seq, float scale, const float* etab,
+           const tv_node* nodes = nullptr)
 {
     constexpr uint32_t DT = HD / 16, DK = HD / 32;
     __shared__ float inv_sum[NH][16];
@@ -156,7 +166,7 @@ px_pv_body(const bf16_t* Q, const pp_seg* segs, const px_range* tab, uint32_t eb
     const px_range e = tab[ebase + blockIdx.y];
     const pp_seg g = segs[e.seg];
     const uint32_t wave = threadIdx.x >> 6, h0 = blockIdx.x * NH;
-    const px_tile<HD, NH> t = px_tile_of<HD, NH>(Q, g, e, kc, cache_stride, H, n_rep, max_seq, scale, h0);
+    const px_tile<HD, NH, TREE> t = px_tile_of<HD, NH, TREE>(Q, g, e, kc, cache_stride, H, n_rep, max_seq, scale, h0, nodes);
     const bf16_t* vbase = vt + (size_t)g.row * cache_stride + (size_t)(h0 / n_rep) * HD * max_seq;
     const uint32_t b_lo = (uint32_t)e.k_lo / 32, b_end = ((uint32_t)e.k_hi + 31) / 32;
     if (threadIdx.x < 16 * NH) {

@@ -12,3 +12,4 @@
 #include "packed_kernels.hip"
 #include "extend_kernels.hip"
 #include "verify_kernels.hip"
+#include "tree_kernels.hip"

@@ -208,6 +208,7 @@ def capi() -> C.CDLL:
         "mc_extend_rows": (i32, [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
         "mc_verify_rows": (i32, [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
         "mc_verify_get_logits": (i32, [vp, vp]),
+        "mc_tree_verify": (i32, [vp] + [C.POINTER(i32)] * 8),
         "mc_synth_weight": (i32, [u64, u32, u32, u32, i32]),
         "mc_synth_scale": (f32, [u64, u32, u32, u32, i32, i32]),
         "mc_synth_value": (f32, [u64, u32, u32, i32, u32]),
@@ -925,9 +926,33 @@ class Batch:
         off = np.concatenate([[0], np.cumsum(lens)])
         return accepted, nxt, [picks[off[r]:off[r + 1]].copy() if lens[r] else None for r in range(self.B)]
 
+    # ---- speculative verify over a draft tree per row (Part 2g)
+
+    def verify_tree(self, chunks, parents, positions):
+        """chunks[r] = the tokens of row r's draft tree, node 0 the row's last accepted token (2 to 16 ids), parents[r][i] the
+        parent of node i (-1 for node 0, else below i); None for a row not in the call.  Returns (accepted[B], next_tokens[B],
+        picks, paths): the target followed accepted[r] drafts down the tree -- paths[r] names the node at each depth 0 ..
+        accepted[r] -- and next_tokens[r] is its pick after the last of them: feed it at positions[r] + accepted[r] + 1, the
+        row's new length.  picks[r][i] is the pick after node i.  -1 / -1 / None / None for a row not in the call."""
+        tokens, lens = self._packed(chunks)
+        par, plens = self._packed(parents)
+        assert list(plens) == list(lens), "verify_tree: one parent per node"
+        p = self._positions(positions)
+        accepted, nxt = np.zeros(self.B, dtype=np.int32), np.zeros(self.B, dtype=np.int32)
+        picks = np.zeros(tokens.shape[0], dtype=np.int32)
+        paths = np.zeros((self.B, 16), dtype=np.int32)
+        ptr = C.POINTER(C.c_int32)
+        _check(capi().mc_tree_verify(self._h, tokens.ctypes.data_as(ptr), par.ctypes.data_as(ptr), lens.ctypes.data_as(ptr),
+                                     p.ctypes.data_as(ptr), accepted.ctypes.data_as(ptr), nxt.ctypes.data_as(ptr),
+                                     paths.ctypes.data_as(ptr), picks.ctypes.data_as(ptr)))
+        self._verify_lens = lens
+        off = np.concatenate([[0], np.cumsum(lens)])
+        return (accepted, nxt, [picks[off[r]:off[r + 1]].copy() if lens[r] else None for r in range(self.B)],
+                [paths[r, :accepted[r] + 1].copy() if lens[r] else None for r in range(self.B)])
+
     def verify_logits(self):
-        """test aid: the logits after every chunk row of the last verify_rows call -- per row [lens[r]][vocab], None for a row
-        that was not in it"""
+        """test aid: the logits after every chunk row (node) of the last verify_rows or verify_tree call -- per row
+        [lens[r]][vocab], None for a row that was not in it"""
         lens = getattr(self, "_verify_lens", np.zeros(self.B, np.int32))
         out = np.empty((max(int(lens.sum()), 1), self.cfg["vocab"]), dtype=self.np_T)
         _check(capi().mc_verify_get_logits(self._h, _np_ptr(out)))
