@@ -363,7 +363,7 @@ mc_status mc_decoder_weight_ptrs(mc_decoder* d, int32_t layer, const char* name,
                                  int32_t* ngroups);
 
 /* ------------------------------------------------------------------------------------------
- * Part 2b -- batched decode: B <= 8 sequences in lockstep over one decoder's weights.
+ * Part 2b -- batched decode: B <= 8 sequences in lockstep over one decoder's weights (B <= 64: Part 2h, the same handle).
  * The reference's layers carry the batch already: nn::attention::operator() takes input[bs, len, dim]
  * (include/metalchat/nn/attention.h:163-206) and nn::sink_cache holds [max_batch_size, max_seq_len, n_kv_heads, head_dim],
  * writing cache[0:bs, start_pos:start_pos+len] at ONE start_pos for the whole batch (nn/cache.h:154-215); only nn::llama3
@@ -374,7 +374,7 @@ mc_status mc_decoder_weight_ptrs(mc_decoder* d, int32_t layer, const char* name,
  * must be released before its decoder.
  * ------------------------------------------------------------------------------------------ */
 typedef struct mc_batch mc_batch;
-/* 1 <= batch <= 8.  The decoder must be single-stage (layer_begin = 0, layer_end = n_layers), family llama3, dtype bf16,
+/* 1 <= batch <= 8 (up to 64: mc_wide_batch_create, Part 2h).  The decoder must be single-stage (layer_begin = 0, layer_end = n_layers), family llama3, dtype bf16,
  * qmode exact, weight_format I4 (group % 128 == 0) or T, without LoRA adaptors, head_dim 128 or 64, every linear with
  * out_features % 16 == 0 and in_features % 1024 == 0; otherwise MC_ERR_INVALID_ARGUMENT naming the reason. */
 mc_status mc_batch_create(mc_decoder* d, int32_t batch, mc_batch** out);
@@ -522,6 +522,26 @@ mc_status mc_verify_get_logits(mc_batch* b, void* logits_T);
  * Rows not in the call: -1 in accepted, next_tokens and all of their paths row. */
 mc_status mc_tree_verify(mc_batch* b, const int32_t* tokens, const int32_t* parents, const int32_t* lens, const int32_t* positions,
                          int32_t* accepted, int32_t* next_tokens, int32_t* paths, int32_t* picks);
+
+/* ================================================================================================
+ * Part 2h -- wide batches: up to 64 rows per step.  mc_batch_create's 8 rows are the columns of ONE 16-column MFMA tile; a wide
+ * batch multiplies every linear layer for all of its rows in one pass over the weights with up to four such column groups
+ * (mc_wb_gemv_*), so 64 chats pay the weight stream once per token and not eight times.  The row contract does not change: a
+ * row's tokens, logits and K / V do not depend on the batch size, on the row's index or on the other rows, bit for bit -- across
+ * the two creation calls and across the 16-row line at which the launch changes (up to 16 rows still run mc_batch_create's
+ * launches).  Row r of a wide batch computes what row r % 8 of a batch of 8 computes from the same cache and tokens.
+ * Everything of Parts 2b - 2g runs on the handle with B up to 64; seeds, idle rows, stop ids, lengths and refusals are as there.
+ * One bound becomes reachable: a verify call (Parts 2f, 2g) holds at most 128 packed rows (MC_VERIFY_MAX_ROWS of the kernel ABI),
+ * which eight rows of at most 16 tokens never exceed and 64 rows can; such a call is refused with MC_ERR_INVALID_ARGUMENT,
+ *   "...: the chunks add up to N rows, more than MC_VERIFY_MAX_ROWS (128): split the call by rows"
+ * nothing enqueued and no row's length changed.  mc_rows_prefill and mc_extend_rows keep their own bound, a sum of lengths no
+ * greater than max_seq_len.  Memory scales with batch as in Part 2b: batch x n_layers caches and the per-row scratch.
+ * ------------------------------------------------------------------------------------------ */
+/* 1 <= batch <= 64 (MC_WIDE_BATCH_MAX of the kernel ABI).  Admission exactly as mc_batch_create (the same conditions and texts,
+ * prefixed "mc_wide_batch_create: "); a batch outside the range: "mc_wide_batch_create: batch must lie in [1, 64]", checked
+ * before anything of the decoder is looked at, as mc_batch_create does.  With batch <= 8 the call makes exactly what
+ * mc_batch_create makes.  The handle is an mc_batch: every call of Parts 2b - 2g takes it, mc_batch_release frees it. */
+mc_status mc_wide_batch_create(mc_decoder* d, int32_t batch, mc_batch** out);
 
 /* Host-side helpers shared by tests and the synthetic initialiser. */
 /* value in [-7,7] (bits = 4) or [-127,127] (bits = 8), zero mean, of element (row, col) of matrix `matrix_id` */

@@ -20,7 +20,7 @@ SO = os.path.join(LIB, "libmetalchat_hip.so")
 
 KERNEL_SOURCES = [os.path.join(CSRC, "kernels", f) for f in (
     "metalchat_kernels.hip", "ref_kernels.hip", "gemv_kernels.hip", "decode_kernels.hip", "attn_block_kernels.hip",
-    "synth_kernels.hip", "sampler_kernels.hip", "prefill_kernels.hip", "batch_kernels.hip", "packed_kernels.hip", "extend_kernels.hip", "verify_kernels.hip", "tree_kernels.hip", "common.h", "abi.h", "handoff.h", "gemv.h", "gemv_ksplit.h", "synth.h", "pf_gemm8.h")]
+    "synth_kernels.hip", "sampler_kernels.hip", "prefill_kernels.hip", "batch_kernels.hip", "packed_kernels.hip", "extend_kernels.hip", "verify_kernels.hip", "wide_kernels.hip", "tree_kernels.hip", "common.h", "abi.h", "handoff.h", "gemv.h", "gemv_ksplit.h", "synth.h", "pf_gemm8.h")]
 HOST_SOURCES = [os.path.join(CSRC, f) for f in ("backend.cc", "decoder.cc", "batch.cc", "model_io.cc", "text.cc", "json_min.h", "backend_impl.h",
                                                  "decoder_batch.h")] + [
     os.path.join(CSRC, "kernels", "synth.h"), os.path.join(CSRC, "kernels", "abi.h"),

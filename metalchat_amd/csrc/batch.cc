@@ -1,4 +1,5 @@
-// Part 2b of include/metalchat_hip.h: batched decode -- B <= 8 sequences in lockstep over one decoder's weights.
+// Part 2b of include/metalchat_hip.h: batched decode -- B sequences in lockstep over one decoder's weights (B <= 8 from
+// mc_batch_create, B <= 64 from Part 2h's mc_wide_batch_create).
 //
 // The reference's layers carry the batch dimension already: nn::attention::operator() takes input[bs, len, dim]
 // (include/metalchat/nn/attention.h:163-206) and nn::sink_cache holds [max_batch_size, max_seq_len, n_kv_heads, head_dim],
@@ -8,7 +9,7 @@
 // waits for another workgroup:
 //   rmsnorm, wq|wk|wv, rope + cache write, scores, softmax + P.V, Wo + residual, rmsnorm, w1|w3 + SiLU.mul, w2 + residual
 // then the final norm, the head and the pick (greedy, or the decoder's default sampler) per row.  Every GEMV streams each
-// weight once for all B rows.
+// weight once for all B rows: mc_batch::gemv() picks the launch by B, and nothing else here knows where that line runs.
 // Part 2c (mc_ragged_*) runs the same sequence with every row at a position of its own: the per-row launches read rows[r]
 // instead of the shared state, one small launch (mc_b_rows_begin) starts each step in place of mc_step_set, and a row whose
 // position is -1, or which stopped on a stop id or at the end of its cache, is idle.
@@ -25,6 +26,8 @@ struct mc_batch {
     decoder_parts p;
     int B = 0;
     int nsplit = 0;
+    int wb_cus = 0;         // compute units of the device, and MC_WB_TILES (0: by wb_tiles' rule), both read once at creation
+    int wb_tiles_env = 0;
     size_t cache_elems = 0; // one row's cache of one layer: n_kv * max_seq * hd
     std::vector<void*> allocs;
     void *kc = nullptr, *vt = nullptr;    // [layer][B][n_kv][max_seq][hd], [layer][B][n_kv][hd][max_seq]
@@ -48,7 +51,7 @@ struct mc_batch {
     int32_t* stop_dev = nullptr;          // the stop ids of a ragged call
     int stop_cap = 0;
     std::vector<int32_t> stop_host;
-    char* pp_tab = nullptr;               // a packed prompt pass (mc_rows_prefill): pp_seg[BATCH_MAX], then the pp_tile table,
+    char* pp_tab = nullptr;               // a packed prompt pass (mc_rows_prefill): pp_seg[MC_WIDE_BATCH_MAX], then the pp_tile table,
                                           // then (mc_tree_verify) one tv_node per packed row
     int pp_tab_cap = 0;                   // (bytes)
     std::vector<char> pp_host;            // the same bytes on the host: one upload
@@ -117,7 +120,7 @@ struct mc_batch {
 
     // the two tables inside pp_tab / pp_host.data()
     static pp_seg* pp_segs(char* tab) { return reinterpret_cast<pp_seg*>(tab); }
-    static pp_tile* pp_tiles(char* tab) { return reinterpret_cast<pp_tile*>(tab + sizeof(pp_seg) * BATCH_MAX); }
+    static pp_tile* pp_tiles(char* tab) { return reinterpret_cast<pp_tile*>(tab + sizeof(pp_seg) * MC_WIDE_BATCH_MAX); }
     static tv_node* tv_nodes(char* tab, int ntiles) { return reinterpret_cast<tv_node*>(pp_tiles(tab) + ntiles); }
 
     char* kc_of(int layer, int row) const { return (char*)kc + ((size_t)layer * B + row) * cache_elems * 2; }
@@ -131,12 +134,29 @@ struct mc_batch {
                       pack(st, (int32_t)-1, (int32_t)pos, (int32_t)p.cfg.max_seq_len, (int32_t)p.pre_len, (int32_t)0, (int32_t)1));
     }
 
+    // 16-row weight tiles per workgroup of mc_wb_gemv_* for a matrix of `out` rows: the most of 8, 4, 2 that still brings a
+    // workgroup to every compute unit, else 1 (measured: DESIGN.md "Wide batches").  MC_WB_TILES is the experiment's handle.
+    int
+    wb_tiles(int out) const
+    {
+        if (wb_tiles_env) return wb_tiles_env;
+        for (int t = 8; t > 1; t /= 2)
+            if ((out / 16 + t - 1) / t >= wb_cus) return t;
+        return 1;
+    }
+
+    // y[r] = epi(W x[r]) for the B rows.  The ONE place that knows the 16-row line: up to 16 rows are the columns of mc_b_gemv_*'s
+    // single MFMA tile (it masks with m < B); more go through mc_wb_gemv_*, whose rows carry the same bits (wide_kernels.hip)
     mc_status
     gemv(const batch_linear& L, int epi, const void* xin, void* y, uint32_t ldy)
     {
-        const std::string name = std::string("mc_b_gemv_") + (L.fmt == MC_WFMT_I4 ? "i4" : "w") + "_bfloat_e" + std::to_string(epi);
-        return launch(name, (unsigned)L.out / 16, 1, 1, BG_THREADS, 0,
-                      pack(L.w, L.scales, xin, y, (uint32_t)L.in, (uint32_t)L.ngroups, (uint32_t)L.group, (uint32_t)B, ldy));
+        const std::string tail = std::string(L.fmt == MC_WFMT_I4 ? "i4" : "w") + "_bfloat_e" + std::to_string(epi);
+        if (B <= 16)
+            return launch("mc_b_gemv_" + tail, (unsigned)L.out / 16, 1, 1, BG_THREADS, 0,
+                          pack(L.w, L.scales, xin, y, (uint32_t)L.in, (uint32_t)L.ngroups, (uint32_t)L.group, (uint32_t)B, ldy));
+        const int tiles = wb_tiles(L.out);
+        return launch("mc_wb_gemv_" + tail, (unsigned)(L.out / 16 + tiles - 1) / tiles, 1, 1, BG_THREADS, 0,
+                      pack(L.w, L.scales, xin, y, (uint32_t)L.in, (uint32_t)L.ngroups, (uint32_t)L.group, (uint32_t)B, (uint32_t)L.out, ldy));
     }
     mc_status
     rmsnorm(const void* xin, const void* w, void* out)
@@ -414,19 +434,25 @@ export_kv(mc_batch* b, const char* what, int32_t row, int32_t layer, const step_
 
 extern "C" {
 
-mc_status
-mc_batch_create(mc_decoder* d, int32_t batch, mc_batch** out)
+// mc_batch_create and mc_wide_batch_create: `who` names the caller in the texts, `cap` is its largest batch
+static mc_status
+batch_create(const std::string& who, int cap, mc_decoder* d, int32_t batch, mc_batch** out)
 {
-    if (!d || !out) return fail(MC_ERR_INVALID_ARGUMENT, "mc_batch_create: null argument");
-    if (batch < 1 || batch > BATCH_MAX) return fail(MC_ERR_INVALID_ARGUMENT, "mc_batch_create: batch must lie in [1, 8]");
+    if (!d || !out) return fail(MC_ERR_INVALID_ARGUMENT, who + ": null argument");
+    if (batch < 1 || batch > cap) return fail(MC_ERR_INVALID_ARGUMENT, who + ": batch must lie in [1, " + std::to_string(cap) + "]");
     *out = nullptr;
     decoder_parts parts;
     mc_status s = decoder_parts_of(d, &parts);
     if (s != MC_OK) return s;
     const std::string why = refusal(parts);
-    if (!why.empty()) return fail(MC_ERR_INVALID_ARGUMENT, "mc_batch_create: " + why);
+    if (!why.empty()) return fail(MC_ERR_INVALID_ARGUMENT, who + ": " + why);
     MC_HIP(hipSetDevice(parts.ordinal));
     std::unique_ptr<mc_batch> b(new mc_batch);
+    MC_HIP(hipDeviceGetAttribute(&b->wb_cus, hipDeviceAttributeMultiprocessorCount, parts.ordinal));
+    if (const char* e = getenv("MC_WB_TILES")) {
+        const int t = atoi(e);
+        if (t == 1 || t == 2 || t == 4 || t == 8) b->wb_tiles_env = t;
+    }
     b->d = d;
     b->p = parts;
     b->B = batch;
@@ -459,6 +485,20 @@ mc_batch_create(mc_decoder* d, int32_t batch, mc_batch** out)
     MC_HIP(hipStreamSynchronize(parts.stream));
     *out = b.release();
     return MC_OK;
+}
+
+mc_status
+mc_batch_create(mc_decoder* d, int32_t batch, mc_batch** out)
+{
+    return batch_create("mc_batch_create", BATCH_MAX, d, batch, out);
+}
+
+// ---- Part 2h: wide batches ----
+
+mc_status
+mc_wide_batch_create(mc_decoder* d, int32_t batch, mc_batch** out)
+{
+    return batch_create("mc_wide_batch_create", MC_WIDE_BATCH_MAX, d, batch, out);
 }
 
 void
@@ -667,7 +707,7 @@ void
 rows_tables(mc_batch* b, const int32_t* lens, const int32_t* positions, int ntiles)
 {
     b->rows_host.assign(b->B, step_state{});
-    b->pp_host.assign(sizeof(pp_seg) * BATCH_MAX + sizeof(pp_tile) * ntiles, 0);
+    b->pp_host.assign(sizeof(pp_seg) * MC_WIDE_BATCH_MAX + sizeof(pp_tile) * ntiles, 0);
     pp_seg* seg = mc_batch::pp_segs(b->pp_host.data());
     pp_tile* tile = mc_batch::pp_tiles(b->pp_host.data());
     for (int r = 0, off = 0, si = 0; r < b->B; r++) {
@@ -752,14 +792,18 @@ rows_pass(mc_batch* b, const char* who, bool extend, const int32_t* tokens, cons
             if (lens[r] > MC_VERIFY_MAX_LEN)
                 return fail(MC_ERR_INVALID_ARGUMENT, std::string(who) + ": row " + std::to_string(r) + ": a chunk of " + std::to_string(lens[r]) +
                                                          " tokens is longer than MC_VERIFY_MAX_LEN (" + std::to_string(MC_VERIFY_MAX_LEN) + ")");
+    // (eight rows of at most 16 tokens never get here; a wide batch can: mc_v_head_* holds MC_VERIFY_MAX_ROWS rows)
+    if (v && M > MC_VERIFY_MAX_ROWS)
+        return fail(MC_ERR_INVALID_ARGUMENT, std::string(who) + ": the chunks add up to " + std::to_string(M) + " rows, more than MC_VERIFY_MAX_ROWS (" +
+                                                 std::to_string(MC_VERIFY_MAX_ROWS) + "): split the call by rows");
     const bool tree = v && v->parents;
     if (tree && (s = tree_check(b, who, v->parents, lens)) != MC_OK) return s;
     MC_HIP(hipSetDevice(b->p.ordinal));
     rows_tables(b, lens, positions, ntiles);
     if (tree) tree_nodes(b, v->parents, lens, ntiles, M);
-    // (enough for any call: at most max_seq_len rows in at most 8 segments)
-    const int tiles_max = c.max_seq_len / PP_TILE_ROWS + BATCH_MAX;
-    if ((s = b->reserve(b->pp_tab, b->pp_tab_cap, (int)b->pp_host.size(), (int)(sizeof(pp_seg) * BATCH_MAX + sizeof(pp_tile) * tiles_max + sizeof(tv_node) * MC_VERIFY_MAX_ROWS))) != MC_OK)
+    // (enough for any call: at most max_seq_len rows in at most MC_WIDE_BATCH_MAX segments, one per row of the batch)
+    const int tiles_max = c.max_seq_len / PP_TILE_ROWS + MC_WIDE_BATCH_MAX;
+    if ((s = b->reserve(b->pp_tab, b->pp_tab_cap, (int)b->pp_host.size(), (int)(sizeof(pp_seg) * MC_WIDE_BATCH_MAX + sizeof(pp_tile) * tiles_max + sizeof(tv_node) * MC_VERIFY_MAX_ROWS))) != MC_OK)
         return s;
     MC_HIP(hipMemcpyAsync(b->pp_tab, b->pp_host.data(), b->pp_host.size(), hipMemcpyHostToDevice, b->p.stream));
     packed_prefill pk;
@@ -804,7 +848,7 @@ rows_pass(mc_batch* b, const char* who, bool extend, const int32_t* tokens, cons
         // (M <= 128 here; the scratch is sized for any call)
         if ((s = b->reserve(b->v_xn, b->v_xn_cap, M, MC_VERIFY_MAX_ROWS, (size_t)c.dim * 2)) != MC_OK ||
             (s = b->reserve(b->v_logits, b->v_logits_cap, M, MC_VERIFY_MAX_ROWS, (size_t)c.vocab * 2)) != MC_OK ||
-            (s = b->reserve(b->v_out, b->v_out_cap, 2 * B + M + MC_VERIFY_MAX_LEN * B, 2 * BATCH_MAX + MC_VERIFY_MAX_ROWS + MC_VERIFY_MAX_LEN * BATCH_MAX)) !=
+            (s = b->reserve(b->v_out, b->v_out_cap, 2 * B + M + MC_VERIFY_MAX_LEN * B, 2 * MC_WIDE_BATCH_MAX + MC_VERIFY_MAX_ROWS + MC_VERIFY_MAX_LEN * MC_WIDE_BATCH_MAX)) !=
                 MC_OK)
             return s;
         MC_HIP(hipMemsetAsync(b->v_out, 0xFF, sizeof(int32_t) * 2 * B, b->p.stream)); // -1: a row not in the call

@@ -12,13 +12,15 @@ namespace abi {
 
 // ---- constants ----
 constexpr int PB = 64;                         // cache slots per attention-scores workgroup (decode_kernels.hip)
-constexpr int BATCH_MAX = 8;                   // rows of an mc_batch (batch_kernels.hip: the B columns of a 16-column MFMA tile)
+constexpr int BATCH_MAX = 8;                   // rows of an mc_batch made by mc_batch_create
+constexpr int MC_WIDE_BATCH_MAX = 64;          // rows of one made by mc_wide_batch_create: mc_b_rows_begin is ONE 64-thread workgroup, a
+                                               // thread per row (up to 16 rows: the B columns of mc_b_gemv_*'s MFMA tile; more: mc_wb_gemv_*)
 constexpr int BG_WAVES = 8;                    // mc_b_gemv_*: waves of a workgroup, each takes an equal slice of K
 constexpr unsigned BG_THREADS = 64 * BG_WAVES; // ... its block size
 constexpr unsigned BG_K_UNIT = 128 * BG_WAVES; // ... in_features per workgroup slice: a 128-weight chunk per wave
 constexpr int PP_TILE_ROWS = 16;               // chunk rows of one attention tile of the packed prompt pass (pp_tile, px_range)
 constexpr int MC_VERIFY_MAX_LEN = PP_TILE_ROWS; // tokens of one row's chunk in mc_verify_rows: one attention tile per row
-constexpr int MC_VERIFY_MAX_ROWS = BATCH_MAX * MC_VERIFY_MAX_LEN; // ... so at most 128 packed rows (mc_v_head_*: 8 column groups)
+constexpr int MC_VERIFY_MAX_ROWS = 128;        // packed rows of one verify call (mc_v_head_*: 8 column groups of 16)
 constexpr int VH_TILES = 4;                    // 16-row weight tiles per workgroup of mc_v_head_* (verify_kernels.hip)
 constexpr uint32_t SAMPLE_CAP = 4096;          // keys the sampler's dynamic LDS holds (sampler_params::cap)
 constexpr uint32_t MC_SAMPLE_LISTS_MAX = 1024; // sorted candidate lists the sampler's second launch takes

@@ -12,4 +12,5 @@
 #include "packed_kernels.hip"
 #include "extend_kernels.hip"
 #include "verify_kernels.hip"
+#include "wide_kernels.hip"
 #include "tree_kernels.hip"

@@ -190,6 +190,7 @@ def capi() -> C.CDLL:
         "mc_interpreter_start_pos": (sz, [vp]),
         "mc_interpreter_pending": (i32, [vp, C.POINTER(i32), sz, C.POINTER(sz)]),
         "mc_batch_create": (i32, [vp, i32, pvp]),
+        "mc_wide_batch_create": (i32, [vp, i32, pvp]),
         "mc_batch_release": (None, [vp]),
         "mc_batch_size": (i32, [vp]),
         "mc_batch_fork": (i32, [vp, i32, i32]),
@@ -786,15 +787,16 @@ class Decoder:
 class Batch:
     """Batched decode (Parts 2b and 2c of the C ABI): B <= 8 sequences over `decoder`'s weights, each with its own cache, in
     lockstep or each row at its own position (nn::attention with input[bs, 1, dim], include/metalchat/nn/attention.h:163-206).
-    Keeps the decoder alive."""
+    wide=True (Part 2h): B <= 64, the same rows bit for bit.  Keeps the decoder alive."""
 
-    def __init__(self, decoder: Decoder, batch: int):
+    def __init__(self, decoder: Decoder, batch: int, wide: bool = False):
         self.decoder = decoder
         self.B = batch
         self.cfg = decoder.cfg
         self.np_T = decoder.np_T
         self._h = C.c_void_p()
-        _check(capi().mc_batch_create(decoder._h, batch, C.byref(self._h)))
+        create = capi().mc_wide_batch_create if wide else capi().mc_batch_create
+        _check(create(decoder._h, batch, C.byref(self._h)))
 
     def size(self) -> int:
         return capi().mc_batch_size(self._h)
