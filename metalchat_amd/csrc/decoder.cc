@@ -32,6 +32,13 @@ using namespace mcimpl;
 
 namespace {
 
+// more kernel arguments behind a pack() whose head depends on the form of a launch
+template <typename... A> void
+push_all(arg_pack& p, const A&... a)
+{
+    (p.push(a), ...);
+}
+
 // The ROCm library GEMM behind the prompt pass of LONG prompts (gemm_lib below).  A plain bfloat16 GEMM with fp32 sums is what
 // hipBLASLt exists for; the hand-written prompt kernels stay for everything the library is not better at (prefill_kernels.hip).
 struct blaslt_api {
@@ -1585,6 +1592,18 @@ struct mc_decoder {
     }
 
     // ---------------------------------------------------------------- prompt pass
+    // a scratch buffer that only grows (pf_part, pf_lora, pf_probs): the stream has finished with the old one before it is given back
+    mc_status
+    grow(void** p, size_t* have, size_t need, size_t elem_bytes)
+    {
+        if (need <= *have) return MC_OK;
+        MC_HIP(hipStreamSynchronize(stream));
+        release(p);
+        *have = 0;
+        mc_status s = alloc(p, need * elem_bytes, false);
+        if (s == MC_OK) *have = need;
+        return s;
+    }
     mc_status
     ensure_prefill(int M, int S)
     {
@@ -1625,18 +1644,11 @@ struct mc_decoder {
             if (s != MC_OK) return s;
         }
         const size_t need = (tb == 2 && !opt.pf_two_pass) ? 0 : (size_t)H * M * S;
-        if (need > pf_probs_elems) {
-            MC_HIP(hipStreamSynchronize(stream));
-            release(&pf_probs);
-            s = alloc(&pf_probs, need * tb, false);
-            if (s != MC_OK) return s;
-            pf_probs_elems = need;
-        }
-        return MC_OK;
+        return grow(&pf_probs, &pf_probs_elems, need, tb);
     }
 
     // Y[M, L.out] = T(X[M, L.in] Wd^T) (+ res): the fused matrices of the decode GEMV, same HBM layout
-    // K splits the big prompt GEMM takes for this matrix at M rows (gemm() below), and the row tile
+    // K splits the big prompt GEMM takes for this matrix at M rows (plan_gemm() below), and the row tile
     unsigned
     gemm_row_tile(int M) const
     {
@@ -1694,28 +1706,6 @@ struct mc_decoder {
         ktper = std::max(2u, (KT + splits - 1) / splits);
         splits = (KT + ktper - 1) / ktper;
     }
-    mc_status
-    gemm_pf2(const linear_w& L, int epi, const void* X, void* Y, const void* res, int M, const void* la)
-    {
-        mc_status s = ensure_pf2(L);
-        if (s != MC_OK) return s;
-        unsigned splits, ktper;
-        pf2_split(L, splits, ktper);
-        const size_t need = (size_t)splits * M * L.out;
-        if (need > pf_part_elems) {
-            MC_HIP(hipStreamSynchronize(stream));
-            release((void**)&pf_part);
-            s = alloc((void**)&pf_part, need * 4, false);
-            if (s != MC_OK) return s;
-            pf_part_elems = need;
-        }
-        s = launch("mc_pf2_gemm_i4_" + tname, ((unsigned)L.out + 127u) / 128u, 1, splits, 512, 0,
-                   pack((const void*)L.wq2, (const void*)L.scales, X, (void*)pf_part, (uint32_t)M, (uint32_t)L.out, (uint32_t)L.in, ktper));
-        if (s != MC_OK) return s;
-        return launch("mc_pf_splitk_reduce_" + tname, (L.out + 255) / 256, M, 1, 256, 0,
-                      pack((const void*)pf_part, Y, epi == 1 ? res : (const void*)nullptr, (uint32_t)M, (uint32_t)L.out, splits, la,
-                           (const void*)L.lora_b, (uint32_t)L.lora_cols, L.lora_scale));
-    }
     // ---- the 256 x 256 ping-pong GEMM (round 5, kernels/pf_gemm8.h): bfloat16 rows, no adaptor, K in whole tiles of 64, scale groups
     // of whole 16-runs; from opt.pf_g8_rows rows on (below that the 128-row tiles keep more workgroups busy)
     bool
@@ -1760,23 +1750,6 @@ struct mc_decoder {
             }
         }
         return pf_plain_on;
-    }
-    mc_status
-    g8_launch(const linear_w& L, int epi, const void* X, void* Y, const void* res, int M, unsigned splits)
-    {
-        if (L.fmt != MC_WFMT_T && plain_copy_ok()) {
-            const void* wd = nullptr;
-            if (ensure_wd(L, &wd) == MC_OK)
-                return launch("mc_pf_gemm8_w_bfloat_e" + std::to_string(epi), (L.out + 255) / 256, (M + 255) / 256, splits, 512, 0,
-                              pack(wd, (const void*)nullptr, X, Y, res, (uint32_t)M, (uint32_t)L.out, (uint32_t)L.in, (uint32_t)0, (const void*)nullptr,
-                                   (const void*)nullptr, (uint32_t)0, 0.0f));
-            pf_plain_on = false; // (no memory for the copy: the quantised rows from here on)
-            (void)hipGetLastError(); // (the failed allocation's residue: RCCL reads it between its own calls)
-        }
-        const std::string f = L.fmt == MC_WFMT_I4 ? "i4" : (L.fmt == MC_WFMT_I8 ? "i8" : "w");
-        return launch("mc_pf_gemm8_" + f + "_bfloat_e" + std::to_string(epi), (L.out + 255) / 256, (M + 255) / 256, splits, 512, 0,
-                      pack(L.w, L.scales, X, Y, res, (uint32_t)M, (uint32_t)L.out, (uint32_t)L.in, (uint32_t)L.group, (const void*)nullptr,
-                           (const void*)nullptr, (uint32_t)0, 0.0f));
     }
     // ---- the library GEMM of long prompts
     // Measured on MI355X (tools/blaslt_probe.py, profiles/r04_blaslt_probe.log; WBITS=16 tools/prefill_bench.py): the hand-written
@@ -1901,148 +1874,156 @@ struct mc_decoder {
         if (log_on) launch_log.push_back("hipblasLtMatmul");
         return true;
     }
-    // A prompt GEMM that splits K, stopped at its fp32 partial sums (pf_part, [splits][M][out]): the kernel that consumes the rows
-    // adds them itself (prefill_kernels.hip mc_pf_*_parts_bfloat) and the reduce launch is saved.  false: this matrix at this M
-    // does not split (or carries an adaptor, or T = float): the caller takes gemm().
-    bool
-    gemm_to_parts(const linear_w& L, const void* X, int M, unsigned* splits_out, mc_status* st)
+    // ---- the prompt GEMM plan: which kernel family multiplies X[M][L.in] by this matrix, with what tiles and K ranges.  The one place that
+    // chooses: gemm_run() launches what it says, run_prefill() asks it about w1|w3.  epi: 0 store, 1 + residual, 2 stop at the fp32
+    // partial sums (gemm_to_parts), 3 / 4 silu / gelu * mul.  No launch, no allocation, no kernel name (names are built where they are launched).
+    enum class gemm_family { lib, stream, g8, tiled, tile64 };
+    struct gemm_plan {
+        gemm_family fam = gemm_family::tile64;
+        unsigned bm = 64;                      // rows of X per workgroup
+        unsigned splits = 1, ktper = 0;        // K ranges (grid z; lib: the one partial); stream: K steps of 128 per range
+        unsigned gx = 0, gy = 0, block = 256;  // the family's launch
+    };
+    gemm_plan
+    plan_gemm(const linear_w& L, int M, int epi) const
     {
-        *st = MC_OK;
-        if (!opt.pf_fold_on || tb != 2 || L.lora_cols || opt.pf_small_gemm) return false;
-        if (lib_ok(L, M)) {
-            // the library GEMM leaves its fp32 sums as the ONE partial the consumers add up
-            const size_t need1 = (size_t)M * L.out;
-            if (need1 > pf_part_elems) {
-                const hipError_t e = hipStreamSynchronize(stream);
-                if (e != hipSuccess) {
-                    *st = hip_fail(e, "hipStreamSynchronize");
-                    return true;
+        // The families in priority order: the first whose gate holds multiplies.
+        //   1. lib: hipBLASLt on the dequantised copy (lib_ok) -- a plain store (epi 0) or its fp32 sums as ONE partial (epi 2), nothing else
+        //   2. stream: mc_pf2_gemm_i4_* (pf2_ok: int4, <= 64 rows; K ranges by pf2_split) -- no epilogue of its own, always through the reduce
+        //   3. g8: the 256 x 256 ping-pong mc_pf_gemm8_* (g8_ok; K ranges by g8_splits) -- an activation epilogue (epi >= 3) does not split
+        //   4. tiled: mc_pf_gemm{128,256}_* (row tile by gemm_row_tile, K ranges by gemm_splits) -- every other bfloat16 prompt: a short one
+        //      is bound by the weight stream, and the unpipelined 64 x 64 tile needed 32-42 ms for 8-64 rows where this one needs 5
+        //   5. tile64: mc_pf_gemm_* -- T = float (the parity path) and MC_PF_SMALL_GEMM=1; never splits
+        gemm_plan P;
+        const unsigned out = (unsigned)L.out;
+        if ((epi == 0 || epi == 2) && lib_ok(L, M)) {
+            P.fam = gemm_family::lib;
+        } else if (pf2_ok(L, M)) {
+            P.fam = gemm_family::stream;
+            pf2_split(L, P.splits, P.ktper);
+            P.gx = (out + 127u) / 128u;
+            P.gy = 1;
+            P.block = 512;
+        } else if (g8_ok(L, M)) {
+            P.fam = gemm_family::g8;
+            P.bm = 256;
+            P.splits = epi >= 3 ? 1u : g8_splits(L, M);
+            P.gx = (out + 255u) / 256u;
+            P.gy = ((unsigned)M + 255u) / 256u;
+            P.block = 512;
+        } else if (tb == 2 && !opt.pf_small_gemm) {
+            // 256 rows of X per workgroup from 256 rows on (prefill_kernels.hip pf_gemm_big_body, BM): the W tile is dequantised once
+            // per workgroup, and at 128 rows that vector work is ~ 0.8 of the matrix pipe's time
+            // A 128 x 128 tile walks K serially (~1.5 us per 64-wide chunk), so a grid that does not
+            // oversubscribe the CUs several times is latency-bound: split K until it does.
+            P.fam = gemm_family::tiled;
+            P.bm = gemm_row_tile(M);
+            P.splits = gemm_splits(L, M);
+            P.gx = (out + 127u) / 128u;
+            P.gy = ((unsigned)M + P.bm - 1u) / P.bm;
+            P.block = 2 * P.bm;
+        } else {
+            P.gx = (out + 63u) / 64u;
+            P.gy = ((unsigned)M + 63u) / 64u;
+        }
+        return P;
+    }
+    // One plan, one launch per family, one reduce.  epi 2 stops at the partial sums in pf_part ([splits][M][out]); the answer's `splits`
+    // is then how many the consumer adds up, 0 when this matrix at this M leaves none (nothing was launched: the caller takes gemm()).
+    struct gemm_done {
+        mc_status st;
+        unsigned splits;
+    };
+    gemm_done
+    gemm_run(const linear_w& L, int epi, const void* X, void* Y, const void* res, int M)
+    {
+        const bool stop = epi == 2;
+        gemm_plan P = plan_gemm(L, M, epi);
+        if (P.fam == gemm_family::lib) {
+            // (the library GEMM leaves its fp32 sums as the ONE partial the consumers add up)
+            mc_status s = stop ? grow((void**)&pf_part, &pf_part_elems, (size_t)M * L.out, 4) : MC_OK;
+            if (s != MC_OK) return {s, 1};
+            if (gemm_lib(L, X, stop ? (void*)pf_part : Y, M, stop)) return {MC_OK, 1};
+            P = plan_gemm(L, M, epi); // (pf_lib_on went false for good: the prompt kernels take over)
+        }
+        if (stop && P.splits < 2) return {MC_OK, 0};
+        const bool parts = stop || P.splits > 1 || P.fam == gemm_family::stream;
+        mc_status s = parts ? grow((void**)&pf_part, &pf_part_elems, (size_t)P.splits * M * L.out, 4) : MC_OK;
+        if (s != MC_OK) return {s, P.splits};
+        // the kernel writes T rows with the caller's epilogue, or fp32 partials (e2: no residual, no adaptor -- the reduce carries them)
+        void* dst = parts ? (void*)pf_part : Y;
+        const void* kres = parts ? nullptr : res;
+        const bool lora = L.lora_cols != 0;
+        const void *la = lora ? (const void*)pf_lora : nullptr, *lb = lora ? (const void*)L.lora_b : nullptr;
+        const float lscale = lora ? L.lora_scale : 0.0f;
+        const void *kla = parts ? nullptr : la, *klb = parts ? nullptr : lb;
+        const uint32_t kcols = parts ? 0u : (uint32_t)L.lora_cols;
+        const float kscale = parts ? 0.0f : lscale;
+        const char* f = L.fmt == MC_WFMT_I4 ? "i4_" : (L.fmt == MC_WFMT_I8 ? "i8_" : "w_");
+        const std::string e = "_e" + std::to_string(parts ? 2 : epi);
+        switch (P.fam) {
+        case gemm_family::stream:
+            s = ensure_pf2(L);
+            if (s != MC_OK) break;
+            s = launch("mc_pf2_gemm_i4_" + tname, P.gx, P.gy, P.splits, P.block, 0,
+                       pack((const void*)L.wq2, (const void*)L.scales, X, dst, (uint32_t)M, (uint32_t)L.out, (uint32_t)L.in, P.ktper));
+            break;
+        case gemm_family::g8: {
+            // (round 6) the quantised matrices of long prompts as dequantised bfloat16 copies where memory allows (plain_copy_ok)
+            const void *w = L.w, *sc = L.scales, *wd = nullptr;
+            uint32_t group = (uint32_t)L.group;
+            if (L.fmt != MC_WFMT_T && plain_copy_ok()) {
+                if (ensure_wd(L, &wd) == MC_OK) {
+                    w = wd;
+                    sc = nullptr;
+                    group = 0;
+                    f = "w_";
+                } else {
+                    pf_plain_on = false; // (no memory for the copy: the quantised rows from here on)
+                    (void)hipGetLastError(); // (the failed allocation's residue: RCCL reads it between its own calls)
                 }
-                release((void**)&pf_part);
-                *st = alloc((void**)&pf_part, need1 * 4, false);
-                if (*st != MC_OK) return true;
-                pf_part_elems = need1;
             }
-            if (gemm_lib(L, X, pf_part, M, true)) {
-                *splits_out = 1;
-                return true;
-            }
+            s = launch(std::string("mc_pf_gemm8_") + f + "bfloat" + e, P.gx, P.gy, P.splits, P.block, 0,
+                       pack(w, sc, X, dst, kres, (uint32_t)M, (uint32_t)L.out, (uint32_t)L.in, group, (const void*)nullptr, (const void*)nullptr,
+                            (uint32_t)0, 0.0f));
+            break;
         }
-        const bool small = pf2_ok(L, M), g8 = !small && g8_ok(L, M);
-        unsigned splits = 1, ktper = 0;
-        if (small) pf2_split(L, splits, ktper);
-        else splits = g8 ? g8_splits(L, M) : gemm_splits(L, M);
-        if (splits < 2) return false;
-        const size_t need = (size_t)splits * M * L.out;
-        if (need > pf_part_elems) {
-            const hipError_t e = hipStreamSynchronize(stream);
-            if (e != hipSuccess) {
-                *st = hip_fail(e, "hipStreamSynchronize");
-                return true;
-            }
-            release((void**)&pf_part);
-            *st = alloc((void**)&pf_part, need * 4, false);
-            if (*st != MC_OK) return true;
-            pf_part_elems = need;
+        default: {
+            // two K chunks in flight per workgroup (prefill_kernels.hip: measured best at every length);
+            // MC_PF_DEPTH=1 selects the one-chunk build for A/B runs
+            const bool big = P.fam == gemm_family::tiled;
+            const std::string deep = big && !opt.pf_depth1 ? "_d2" : "";
+            s = launch((big ? (P.bm == 256 ? "mc_pf_gemm256_" : "mc_pf_gemm128_") : "mc_pf_gemm_") + (f + tname) + deep + e, P.gx, P.gy, P.splits,
+                       P.block, 0,
+                       pack(L.w, L.scales, X, dst, kres, (uint32_t)M, (uint32_t)L.out, (uint32_t)L.in, (uint32_t)L.group, kla, klb, kcols, kscale));
         }
-        *splits_out = splits;
-        if (g8) {
-            *st = g8_launch(L, 2, X, pf_part, nullptr, M, splits);
-            return true;
         }
-        if (small) {
-            *st = ensure_pf2(L);
-            if (*st != MC_OK) return true;
-            *st = launch("mc_pf2_gemm_i4_" + tname, ((unsigned)L.out + 127u) / 128u, 1, splits, 512, 0,
-                         pack((const void*)L.wq2, (const void*)L.scales, X, (void*)pf_part, (uint32_t)M, (uint32_t)L.out, (uint32_t)L.in, ktper));
-            return true;
-        }
-        const std::string f = L.fmt == MC_WFMT_I4 ? "i4_" : (L.fmt == MC_WFMT_I8 ? "i8_" : "w_");
-        const std::string deep = opt.pf_depth1 ? "" : "_d2";
-        const unsigned bm = gemm_row_tile(M);
-        *st = launch(std::string(bm == 256 ? "mc_pf_gemm256_" : "mc_pf_gemm128_") + f + tname + deep + "_e2", (L.out + 127) / 128, (M + bm - 1) / bm,
-                     splits, 2 * bm, 0,
-                     pack(L.w, L.scales, X, (void*)pf_part, (const void*)nullptr, (uint32_t)M, (uint32_t)L.out, (uint32_t)L.in,
-                          (uint32_t)L.group, (const void*)nullptr, (const void*)nullptr, (uint32_t)0, 0.0f));
-        return true;
+        if (s != MC_OK || stop || !parts) return {s, P.splits};
+        s = launch("mc_pf_splitk_reduce_" + tname, (L.out + 255) / 256, M, 1, 256, 0,
+                   pack((const void*)pf_part, Y, epi == 1 ? res : (const void*)nullptr, (uint32_t)M, (uint32_t)L.out, P.splits, la, lb,
+                        (uint32_t)L.lora_cols, lscale));
+        return {s, P.splits};
+    }
+    // A prompt GEMM that splits K, stopped at its fp32 partial sums: the kernel that consumes the rows adds them itself
+    // (prefill_kernels.hip mc_pf_*_parts_bfloat) and the reduce launch is saved.  splits 0: this matrix at this M does not split
+    // (or carries an adaptor, or T = float): the caller takes gemm().
+    gemm_done
+    gemm_to_parts(const linear_w& L, const void* X, int M)
+    {
+        if (!opt.pf_fold_on || tb != 2 || L.lora_cols || opt.pf_small_gemm) return {MC_OK, 0};
+        return gemm_run(L, 2, X, nullptr, nullptr, M);
     }
     mc_status
     gemm(const linear_w& L, int epi, const void* X, void* Y, const void* res, int M)
     {
         if (L.lora_cols) {
             // la = T(X A^T): the stacked adaptor inputs, [M][nseg * rank]
-            if ((size_t)M * L.lora_cols > pf_lora_elems) {
-                MC_HIP(hipStreamSynchronize(stream));
-                release(&pf_lora);
-                mc_status s = alloc(&pf_lora, (size_t)M * L.lora_cols * tb, false);
-                if (s != MC_OK) return s;
-                pf_lora_elems = (size_t)M * L.lora_cols;
-            }
-            mc_status s = gemm(*L.lora_a, 0, X, pf_lora, nullptr, M);
+            mc_status s = grow(&pf_lora, &pf_lora_elems, (size_t)M * L.lora_cols, tb);
+            if (s != MC_OK) return s;
+            s = gemm(*L.lora_a, 0, X, pf_lora, nullptr, M);
             if (s != MC_OK) return s;
         }
-        // every bf16 prompt takes the pipelined 128 x 128 MFMA tiling: a short prompt is bound by the
-        // weight stream, and the unpipelined 64 x 64 tile (kept for T = float, the parity path) needed
-        // 32-42 ms for 8-64 rows where this one needs 5
-        if (epi == 0 && lib_ok(L, M) && gemm_lib(L, X, Y, M, false)) return MC_OK;
-        if (g8_ok(L, M) && !(pf2_ok(L, M) && epi != 2)) {
-            const unsigned splits = epi >= 3 ? 1u : g8_splits(L, M);
-            if (splits == 1) return g8_launch(L, epi, X, Y, res, M, 1);
-            const size_t need = (size_t)splits * M * L.out;
-            if (need > pf_part_elems) {
-                MC_HIP(hipStreamSynchronize(stream));
-                release((void**)&pf_part);
-                mc_status s = alloc((void**)&pf_part, need * 4, false);
-                if (s != MC_OK) return s;
-                pf_part_elems = need;
-            }
-            mc_status s = g8_launch(L, 2, X, pf_part, nullptr, M, splits);
-            if (s != MC_OK) return s;
-            return launch("mc_pf_splitk_reduce_" + tname, (L.out + 255) / 256, M, 1, 256, 0,
-                          pack((const void*)pf_part, Y, epi == 1 ? res : (const void*)nullptr, (uint32_t)M, (uint32_t)L.out, splits, (const void*)nullptr,
-                               (const void*)nullptr, (uint32_t)0, 0.0f));
-        }
-        const bool big = tb == 2 && !opt.pf_small_gemm;
-        const std::string f = L.fmt == MC_WFMT_I4 ? "i4_" : (L.fmt == MC_WFMT_I8 ? "i8_" : "w_");
-        const void* la = L.lora_cols ? pf_lora : nullptr;
-        if (pf2_ok(L, M) && epi != 2) return gemm_pf2(L, epi, X, Y, res, M, la);
-        // two K chunks in flight per workgroup (prefill_kernels.hip: measured best at every length);
-        // MC_PF_DEPTH=1 selects the one-chunk build for A/B runs
-        const std::string deep = opt.pf_depth1 ? "" : "_d2";
-        // 256 rows of X per workgroup from 256 rows on (prefill_kernels.hip pf_gemm_big_body, BM): the W tile is dequantised once
-        // per workgroup, and at 128 rows that vector work is ~ 0.8 of the matrix pipe's time
-        const unsigned bm = big ? gemm_row_tile(M) : 128u;
-        const std::string gname = bm == 256 ? "mc_pf_gemm256_" : "mc_pf_gemm128_";
-        if (big) {
-            // A 128 x 128 tile walks K serially (~1.5 us per 64-wide chunk), so a grid that does not
-            // oversubscribe the CUs several times is latency-bound: split K until it does.
-            const unsigned splits = gemm_splits(L, M);
-            if (splits > 1) {
-                const size_t need = (size_t)splits * M * L.out;
-                if (need > pf_part_elems) {
-                    MC_HIP(hipStreamSynchronize(stream));
-                    release((void**)&pf_part);
-                    mc_status s = alloc((void**)&pf_part, need * 4, false);
-                    if (s != MC_OK) return s;
-                    pf_part_elems = need;
-                }
-                mc_status s = launch(gname + f + tname + deep + "_e2", (L.out + 127) / 128, (M + bm - 1) / bm, splits,
-                                     2 * bm, 0,
-                                     pack(L.w, L.scales, X, (void*)pf_part, (const void*)nullptr, (uint32_t)M,
-                                          (uint32_t)L.out, (uint32_t)L.in, (uint32_t)L.group, (const void*)nullptr,
-                                          (const void*)nullptr, (uint32_t)0, 0.0f));
-                if (s != MC_OK) return s;
-                return launch("mc_pf_splitk_reduce_" + tname, (L.out + 255) / 256, M, 1, 256, 0,
-                              pack((const void*)pf_part, Y, epi == 1 ? res : (const void*)nullptr, (uint32_t)M,
-                                   (uint32_t)L.out, splits, la, (const void*)L.lora_b, (uint32_t)L.lora_cols,
-                                   L.lora_scale));
-            }
-        }
-        const std::string name = (big ? gname : "mc_pf_gemm_") + f + tname + (big ? deep : "") + "_e" + std::to_string(epi);
-        const unsigned tile = big ? 128 : 64, tile_m = big ? bm : 64;
-        return launch(name, (L.out + tile - 1) / tile, (M + tile_m - 1) / tile_m, 1, big ? 2 * bm : 256, 0,
-                      pack(L.w, L.scales, X, Y, res, (uint32_t)M, (uint32_t)L.out, (uint32_t)L.in, (uint32_t)L.group,
-                           la, (const void*)L.lora_b, (uint32_t)L.lora_cols, L.lora_scale));
+        return gemm_run(L, epi, X, Y, res, M).st;
     }
 
     mc_status
@@ -2050,6 +2031,134 @@ struct mc_decoder {
     {
         return launch("mc_pf_rmsnorm_" + tname, M, 1, 1, 256, 0,
                       pack(x, w, res, y, (uint32_t)cfg.dim, cfg.norm_eps, mu));
+    }
+
+    // wq|wk|wv of the M rows in pf_xn, then rope + cache write (q rows into pf_q, k and v into kc / vt) in the one form that fits -- packed / tree (pk), four
+    // pairs per thread, one pair -- reading the GEMM's rows (pf_qkv) or, where it split K, its partial sums
+    mc_status
+    qkv_rope_cache(const layer_w& L, void* kc, void* vt, int M, int start_pos, int rope_pos, float mu, const packed_prefill* pk)
+    {
+        const int H = cfg.n_heads, KV = cfg.n_kv_heads, hd = cfg.head_dim;
+        const gemm_done g = gemm_to_parts(L.qkv, pf_xn, M);
+        if (g.st != MC_OK) return g.st;
+        const bool parts = g.splits > 0;
+        if (!parts) {
+            mc_status s = timed("gemm_qkv", [&] { return gemm(L.qkv, 0, pf_xn, pf_qkv, nullptr, M); });
+            if (s != MC_OK) return s;
+        }
+        // rope + cache write: four rotation pairs per thread (prefill_kernels.hip pf_rope_cache_v4_body: a quarter of the waves of the one-pair
+        // launch, which is bound by the rate waves start at, and the transposed V cache written 16 slots at a time); MC_PF_ROPE_PACK=0: the launch of rounds 1-5
+        const bool rope_v4 = opt.pf_rope_pack && tb == 2 && hd % 8 == 0 && hd <= 2048 && 2048 % hd == 0 &&
+                             ((!L.q_norm && !L.k_norm) || hd == 128 || hd == 256); // (q / k norms: the head sizes whose sum order the kernel reproduces)
+        std::string name;
+        unsigned gx = 0, gy = 1, block = 256;
+        arg_pack a = parts ? pack((const void*)pf_part, g.splits, (uint32_t)M, pf_q) : (pk ? pack((const void*)pf_qkv, (uint32_t)M, pf_q) : pack(pf_qkv, pf_q));
+        if (pk || rope_v4) {
+            const unsigned per = 2048u / (unsigned)hd; // heads of a row per workgroup of 256 threads
+            gx = ((unsigned)(H + KV) * (unsigned)M + per - 1) / per + (unsigned)KV * (((unsigned)M + 15u) / 16u); // q / k units, then v tiles of 16 rows
+        }
+        if (pk) {
+            // packed rows (kc, vt: this layer of every batch row): the four-pair arithmetic whatever MC_PF_ROPE_PACK says (bit for bit the one-pair launch's)
+            name = pk->nodes ? (parts ? "mc_tv_rope_cache_parts_bfloat" : "mc_tv_rope_cache_bfloat")
+                             : (parts ? "mc_pp_rope_cache_parts_bfloat" : "mc_pp_rope_cache_bfloat");
+            push_all(a, pk->segs, (uint32_t)pk->nseg, kc, vt, pk->cache_stride, pk->fcos, pk->fsin, (uint32_t)H, (uint32_t)KV, (uint32_t)hd,
+                     (uint32_t)cfg.max_seq_len);
+            if (pk->nodes) a.push(pk->nodes);
+        } else if (rope_v4) {
+            name = parts ? "mc_pf_rope_cache_parts_v4_bfloat" : "mc_pf_rope_cache_v4_bfloat";
+            push_all(a, kc, vt, rope_cos[L.rope_table], rope_sin[L.rope_table], (uint32_t)H, (uint32_t)KV, (uint32_t)hd, (uint32_t)cfg.max_seq_len,
+                     (uint32_t)start_pos, (uint32_t)(rope_pos - rope_start));
+            if (!parts) a.push((uint32_t)M);
+            push_all(a, L.q_norm, L.k_norm, cfg.norm_eps, mu);
+        } else {
+            name = (parts ? "mc_pf_rope_cache_parts_" : "mc_pf_rope_cache_") + tname;
+            gx = H + 2 * KV;
+            gy = M;
+            block = hd / 2;
+            push_all(a, kc, vt, rope_cos[L.rope_table], rope_sin[L.rope_table], L.q_norm, L.k_norm, (uint32_t)H, (uint32_t)KV, (uint32_t)hd,
+                     (uint32_t)cfg.max_seq_len, (uint32_t)start_pos, (uint32_t)(rope_pos - rope_start), cfg.norm_eps, mu);
+        }
+        return timed("rope_cache", [&] { return launch(name, gx, gy, 1, block, 0, std::move(a)); });
+    }
+
+    // the fused attention launch of ONE prompt of M rows (the probabilities stay on chip): which kernel, its grid and block
+    struct attn_plan {
+        std::string name;
+        unsigned gx, gy, block;
+    };
+    attn_plan
+    plan_attention(int M) const
+    {
+        const int H = cfg.n_heads, KV = cfg.n_kv_heads, hd = cfg.head_dim;
+        // two query heads of a kv head per workgroup where the grouping allows it: each K / V
+        // fragment is loaded once for both (MC_PF_ATTN_HEADS=1: one head per workgroup)
+        // (measured: 2048 rows 15.8 -> 14.0 ms, 512 rows 2.05 -> 1.56 ms per prompt; with too few
+        // workgroups to fill the chip -- 128 rows -- it loses, 0.46 -> 0.61 ms)
+        const bool heads_given = opt.pf_attn_heads >= 0;
+        const bool enough = (unsigned)((M + 15) / 16) * (unsigned)(H / 2) >= 2u * (unsigned)dev->prop.multiProcessorCount;
+        const bool two = (H / KV) % 2 == 0 && hd <= 128 && (heads_given ? opt.pf_attn_heads == 2 : enough);
+        // four query heads per workgroup (head_dim 128, 360 registers: one workgroup per CU): at 1024 rows and more
+        // the launch is bound by the K / V fragments its waves pull out of L2 (1.6 GB per layer at 2048 rows, ~ 6 TB/s),
+        // and four heads per fragment halve them again: 2048 rows 44.5 -> 42.6 ms, 1024: 22.75 -> 22.3, 512: 11.8 -> 11.7
+        const bool four = (H / KV) % 4 == 0 && hd == 128 &&
+                          (heads_given ? opt.pf_attn_heads == 4
+                                       : (unsigned)((M + 15) / 16) * (unsigned)(H / 4) >= (unsigned)dev->prop.multiProcessorCount);
+        // long prompts (round 5): K / V tiles through LDS, 32 rows x 4 heads per workgroup (prefill_kernels.hip pf_attn_lds_body)
+        const bool eight = (H / KV) % 4 == 0 && hd == 128 && cfg.max_seq_len % 8 == 0 &&
+                           (heads_given ? opt.pf_attn_heads == 8 : (opt.pf_attn8_on && M >= opt.pf_attn8_rows));
+        // (row tiles of 32 rows, dealt in pairs -- tile x with tile (last - x): equal work under the causal mask -- when the
+        //  pairs still cover the CUs; MC_PF_ATTN8_PAIR=0 / 1 forces either)
+        const unsigned ntl = (unsigned)(M + 31) / 32u;
+        const bool pair_given = opt.pf_attn8_pair >= 0;
+        const bool pair = pair_given ? opt.pf_attn8_pair != 0 : ((ntl + 1u) / 2u) * (unsigned)(H / 4) >= (unsigned)dev->prop.multiProcessorCount;
+        // head_dim 256 (round 6; Gemma-7B: a kv head per query head): the same K / V tiles through LDS for 64 rows of ONE head, four waves
+        // (MC_PF_ATTN8_ROWS256: from how many rows; MC_PF_ATTN_HEADS=1: never)
+        const bool eight256 = hd == 256 && cfg.max_seq_len % 8 == 0 && (heads_given ? opt.pf_attn_heads == 8 : (opt.pf_attn8_on && M >= opt.pf_attn8_rows256));
+        if (eight256) {
+            const unsigned ntl64 = (unsigned)(M + 63) / 64u;
+            const bool pair64 = pair_given ? opt.pf_attn8_pair != 0 : ((ntl64 + 1u) / 2u) * (unsigned)H >= (unsigned)dev->prop.multiProcessorCount;
+            return {"mc_pf_attn8_bfloat_hd256", pair64 ? (ntl64 + 1u) / 2u : ntl64, (unsigned)H, 256};
+        }
+        // head_dim 64 (round 6; TinyLlama-1.1B: 8 query heads per kv head, Llama-3.2-1B: 4): 8 heads x 16 rows or 4 heads x 32 rows per workgroup
+        const unsigned nh64 = (H / KV) % 8 == 0 ? 8u : ((H / KV) % 4 == 0 ? 4u : 0u);
+        const bool eight64 = hd == 64 && nh64 && cfg.max_seq_len % 8 == 0 && (heads_given ? opt.pf_attn_heads == 8 : (opt.pf_attn8_on && M >= opt.pf_attn8_rows64));
+        if (eight64) {
+            const unsigned rt64 = 128u / nh64, ntl = ((unsigned)M + rt64 - 1u) / rt64;
+            const bool pr = pair_given ? opt.pf_attn8_pair != 0 : ((ntl + 1u) / 2u) * ((unsigned)H / nh64) >= (unsigned)dev->prop.multiProcessorCount;
+            return {nh64 == 8 ? "mc_pf_attn8_bfloat_hd64_h8" : "mc_pf_attn8_bfloat_hd64_h4", pr ? (ntl + 1u) / 2u : ntl, (unsigned)H / nh64, 512};
+        }
+        if (eight) return {"mc_pf_attn8_bfloat_hd128", pair ? (ntl + 1u) / 2u : ntl, (unsigned)H / 4, 512};
+        if (four) return {"mc_pf_attn4_bfloat_hd128", ((unsigned)M + 15) / 16, (unsigned)H / 4, 256};
+        return {std::string(two ? "mc_pf_attn2_bfloat_hd" : "mc_pf_attn_bfloat_hd") + std::to_string(hd), ((unsigned)M + 15) / 16, (unsigned)(two ? H / 2 : H), 256};
+    }
+
+    // Wo and w2: out = T(res + y), y = T(X W^T) or gemma3's post norm of it (post_w; null: llama) -- and where the GEMM splits K its
+    // reduce, the residual and the NEXT rmsnorm (next_w) of out into pf_xn are the one launch that consumes the partial sums.
+    // *xn_done: pf_xn was written.  label: the timed() category of the GEMM where it is a launch of its own.
+    mc_status
+    gemm_residual(const linear_w& W, const void* X, const void* res, void* out, const void* post_w, const void* next_w, const char* label, int M, float mu,
+                  bool* xn_done)
+    {
+        const int dim = cfg.dim;
+        *xn_done = false;
+        // gemma3's post norms: the reduce of a split Wo / w2, the post norm with the residual and the next norm in one launch
+        // (prefill_kernels.hip mc_pf_rmsnorm2_parts_bfloat, which takes no next norm too; MC_PF_NORM2=0: the three launches)
+        // llama: h = T(x + T(sum of the partials)) -> out, rmsnorm(h) -> pf_xn: the reduce, the residual and the next norm in one launch
+        const bool fold_norm = dim % 8 == 0 && dim / 8 <= 4 * 256;
+        const bool fold = post_w ? fold_norm && tb == 2 && opt.pf_norm2 : fold_norm && next_w;
+        const gemm_done g = fold ? gemm_to_parts(W, X, M) : gemm_done{MC_OK, 0};
+        if (g.st != MC_OK) return g.st;
+        if (g.splits) {
+            *xn_done = next_w != nullptr;
+            arg_pack a = pack((const void*)pf_part, g.splits, (uint32_t)M, res, out);
+            if (post_w) a.push(post_w);
+            push_all(a, next_w, pf_xn, (uint32_t)dim, cfg.norm_eps, mu);
+            return timed("norm", [&] { return launch(post_w ? "mc_pf_rmsnorm2_parts_bfloat" : "mc_pf_rmsnorm_parts_" + tname, M, 1, 1, 256, 0, std::move(a)); });
+        }
+        if (!post_w) return timed(label, [&] { return gemm(W, 1, X, out, res, M); });
+        mc_status s = timed(label, [&] { return gemm(W, 0, X, pf_proj, nullptr, M); });
+        if (s != MC_OK) return s;
+        return norm_rows(pf_proj, post_w, res, out, M, mu);
     }
 
     // nn::llama3 / nn::gemma3 operator() on M > 1 rows (llama.h:113-134, gemma.h:110-137)
@@ -2088,10 +2197,7 @@ struct mc_decoder {
         if (taps_on) MC_HIP(hipMemcpyAsync(taps, (char*)pf_x + last, (size_t)dim * tb, hipMemcpyDeviceToDevice, stream));
         // (round 4) a GEMM that splits K hands its fp32 partial sums straight to the kernel that consumes its rows -- rope + cache
         // write, the next rmsnorm (with the residual), act * mul -- instead of to a reduce launch: gemm_to_parts
-        const bool fold_norm = dim % 8 == 0 && dim / 8 <= 4 * 256;
         bool xn_ready = false; // pf_xn already holds this block's normalised input (the previous block's w2 consumer wrote it)
-        unsigned sp = 1;
-        mc_status gs;
         for (int li = 0; li < n_own; li++) {
             layer_w& L = layers[li];
             if (!xn_ready) {
@@ -2099,55 +2205,10 @@ struct mc_decoder {
                 if (s != MC_OK) return s;
             }
             xn_ready = false;
-            // rope + cache write: four rotation pairs per thread (prefill_kernels.hip pf_rope_cache_v4_body: a quarter of the waves of the one-pair
-            // launch, which is bound by the rate waves start at, and the transposed V cache written 16 slots at a time); MC_PF_ROPE_PACK=0: the launch of rounds 1-5
-            const bool rope_v4 = opt.pf_rope_pack && tb == 2 && hd % 8 == 0 && hd <= 2048 && 2048 % hd == 0 &&
-                                 ((!L.q_norm && !L.k_norm) || hd == 128 || hd == 256); // (q / k norms: the head sizes whose sum order the kernel reproduces)
-            const unsigned rope_per = rope_v4 ? 2048u / (unsigned)hd : 1u; // heads of a row per workgroup of 256 threads
-            const unsigned rope_gx = rope_v4 ? ((unsigned)(H + KV) * (unsigned)M + rope_per - 1) / rope_per + (unsigned)KV * (((unsigned)M + 15u) / 16u) // q / k units, then v tiles of 16 rows
-                                             : 0u;
-            // packed rows: layer li of every batch row; the four-pair arithmetic whatever MC_PF_ROPE_PACK says (bit for bit the one-pair launch's)
+            // packed rows: layer li of every batch row's caches
             void* pk_kc = pk ? (char*)pk->kc + (size_t)li * pk->B * pk->cache_stride * tb : nullptr;
             void* pk_vt = pk ? (char*)pk->vt + (size_t)li * pk->B * pk->cache_stride * tb : nullptr;
-            const unsigned pk_gx = ((unsigned)(H + KV) * (unsigned)M + 2048u / (unsigned)hd - 1) / (2048u / (unsigned)hd) + (unsigned)KV * (((unsigned)M + 15u) / 16u);
-            if (gemm_to_parts(L.qkv, pf_xn, M, &sp, &gs)) {
-                if (gs != MC_OK) return gs;
-                if (pk)
-                    s = timed("rope_cache", [&] {
-                        arg_pack a = pack((const void*)pf_part, sp, (uint32_t)M, pf_q, pk->segs, (uint32_t)pk->nseg, pk_kc, pk_vt, pk->cache_stride, pk->fcos,
-                                          pk->fsin, (uint32_t)H, (uint32_t)KV, (uint32_t)hd, (uint32_t)cfg.max_seq_len);
-                        if (pk->nodes) a.push(pk->nodes);
-                        return launch(pk->nodes ? "mc_tv_rope_cache_parts_bfloat" : "mc_pp_rope_cache_parts_bfloat", pk_gx, 1, 1, 256, 0, std::move(a)); });
-                else if (rope_v4)
-                    s = timed("rope_cache", [&] { return launch("mc_pf_rope_cache_parts_v4_bfloat", rope_gx, 1, 1, 256, 0,
-                               pack((const void*)pf_part, sp, (uint32_t)M, pf_q, L.kc, L.vt, rope_cos[L.rope_table], rope_sin[L.rope_table],
-                                    (uint32_t)H, (uint32_t)KV, (uint32_t)hd, (uint32_t)cfg.max_seq_len, (uint32_t)start_pos,
-                                    (uint32_t)(rope_pos - rope_start), L.q_norm, L.k_norm, cfg.norm_eps, mu)); });
-                else
-                s = timed("rope_cache", [&] { return launch("mc_pf_rope_cache_parts_" + tname, H + 2 * KV, M, 1, hd / 2, 0,
-                           pack((const void*)pf_part, sp, (uint32_t)M, pf_q, L.kc, L.vt, rope_cos[L.rope_table], rope_sin[L.rope_table], L.q_norm,
-                                L.k_norm, (uint32_t)H, (uint32_t)KV, (uint32_t)hd, (uint32_t)cfg.max_seq_len,
-                                (uint32_t)start_pos, (uint32_t)(rope_pos - rope_start), cfg.norm_eps, mu)); });
-            } else {
-                s = timed("gemm_qkv", [&] { return gemm(L.qkv, 0, pf_xn, pf_qkv, nullptr, M); });
-                if (s != MC_OK) return s;
-                if (pk)
-                    s = timed("rope_cache", [&] {
-                        arg_pack a = pack((const void*)pf_qkv, (uint32_t)M, pf_q, pk->segs, (uint32_t)pk->nseg, pk_kc, pk_vt, pk->cache_stride, pk->fcos, pk->fsin,
-                                          (uint32_t)H, (uint32_t)KV, (uint32_t)hd, (uint32_t)cfg.max_seq_len);
-                        if (pk->nodes) a.push(pk->nodes);
-                        return launch(pk->nodes ? "mc_tv_rope_cache_bfloat" : "mc_pp_rope_cache_bfloat", pk_gx, 1, 1, 256, 0, std::move(a)); });
-                else if (rope_v4)
-                    s = timed("rope_cache", [&] { return launch("mc_pf_rope_cache_v4_bfloat", rope_gx, 1, 1, 256, 0,
-                               pack(pf_qkv, pf_q, L.kc, L.vt, rope_cos[L.rope_table], rope_sin[L.rope_table], (uint32_t)H, (uint32_t)KV, (uint32_t)hd,
-                                    (uint32_t)cfg.max_seq_len, (uint32_t)start_pos, (uint32_t)(rope_pos - rope_start), (uint32_t)M, L.q_norm, L.k_norm,
-                                    cfg.norm_eps, mu)); });
-                else
-                s = timed("rope_cache", [&] { return launch("mc_pf_rope_cache_" + tname, H + 2 * KV, M, 1, hd / 2, 0,
-                           pack(pf_qkv, pf_q, L.kc, L.vt, rope_cos[L.rope_table], rope_sin[L.rope_table], L.q_norm,
-                                L.k_norm, (uint32_t)H, (uint32_t)KV, (uint32_t)hd, (uint32_t)cfg.max_seq_len,
-                                (uint32_t)start_pos, (uint32_t)(rope_pos - rope_start), cfg.norm_eps, mu)); });
-            }
+            s = qkv_rope_cache(L, pk ? pk_kc : L.kc, pk ? pk_vt : L.vt, M, start_pos, rope_pos, mu, pk);
             if (s != MC_OK) return s;
             const uint32_t win = (gemma && L.rope_table == 1) ? (uint32_t)window : 0u;
             if (pk && pk->extend) {
@@ -2196,56 +2257,8 @@ struct mc_decoder {
             } else if (tb == 2 && !opt.pf_two_pass) {
                 // fused: the probabilities stay on chip
                 s = timed("attention", [&] {
-                    // two query heads of a kv head per workgroup where the grouping allows it: each K / V
-                    // fragment is loaded once for both (MC_PF_ATTN_HEADS=1: one head per workgroup)
-                    // (measured: 2048 rows 15.8 -> 14.0 ms, 512 rows 2.05 -> 1.56 ms per prompt; with too few
-                    // workgroups to fill the chip -- 128 rows -- it loses, 0.46 -> 0.61 ms)
-                    const bool heads_given = opt.pf_attn_heads >= 0;
-                    const bool enough = (unsigned)((M + 15) / 16) * (unsigned)(H / 2) >= 2u * (unsigned)dev->prop.multiProcessorCount;
-                    const bool two = (H / KV) % 2 == 0 && hd <= 128 && (heads_given ? opt.pf_attn_heads == 2 : enough);
-                    // four query heads per workgroup (head_dim 128, 360 registers: one workgroup per CU): at 1024 rows and more
-                    // the launch is bound by the K / V fragments its waves pull out of L2 (1.6 GB per layer at 2048 rows, ~ 6 TB/s),
-                    // and four heads per fragment halve them again: 2048 rows 44.5 -> 42.6 ms, 1024: 22.75 -> 22.3, 512: 11.8 -> 11.7
-                    const bool four = (H / KV) % 4 == 0 && hd == 128 &&
-                                      (heads_given ? opt.pf_attn_heads == 4
-                                                 : (unsigned)((M + 15) / 16) * (unsigned)(H / 4) >= (unsigned)dev->prop.multiProcessorCount);
-                    // long prompts (round 5): K / V tiles through LDS, 32 rows x 4 heads per workgroup (prefill_kernels.hip pf_attn_lds_body)
-                    const bool eight = (H / KV) % 4 == 0 && hd == 128 && cfg.max_seq_len % 8 == 0 &&
-                                       (heads_given ? opt.pf_attn_heads == 8 : (opt.pf_attn8_on && M >= opt.pf_attn8_rows));
-                    // (row tiles of 32 rows, dealt in pairs -- tile x with tile (last - x): equal work under the causal mask -- when the
-                    //  pairs still cover the CUs; MC_PF_ATTN8_PAIR=0 / 1 forces either)
-                    const unsigned ntl = (unsigned)(M + 31) / 32u;
-                    const bool pair_given = opt.pf_attn8_pair >= 0;
-                    const bool pair = pair_given ? opt.pf_attn8_pair != 0 : ((ntl + 1u) / 2u) * (unsigned)(H / 4) >= (unsigned)dev->prop.multiProcessorCount;
-                    // head_dim 256 (round 6; Gemma-7B: a kv head per query head): the same K / V tiles through LDS for 64 rows of ONE head, four waves
-                    // (MC_PF_ATTN8_ROWS256: from how many rows; MC_PF_ATTN_HEADS=1: never)
-                    const bool eight256 = hd == 256 && cfg.max_seq_len % 8 == 0 && (heads_given ? opt.pf_attn_heads == 8 : (opt.pf_attn8_on && M >= opt.pf_attn8_rows256));
-                    if (eight256) {
-                        const unsigned ntl64 = (unsigned)(M + 63) / 64u;
-                        const bool pair64 = pair_given ? opt.pf_attn8_pair != 0 : ((ntl64 + 1u) / 2u) * (unsigned)H >= (unsigned)dev->prop.multiProcessorCount;
-                        return launch("mc_pf_attn8_bfloat_hd256", pair64 ? (ntl64 + 1u) / 2u : ntl64, H, 1, 256, 0,
-                                      pack(pf_q, L.kc, L.vt, pf_att, (uint32_t)M, (uint32_t)S, (uint32_t)H, (uint32_t)(H / KV),
-                                           (uint32_t)cfg.max_seq_len, scale_T, win, (const void*)pf_etab));
-                    }
-                    // head_dim 64 (round 6; TinyLlama-1.1B: 8 query heads per kv head, Llama-3.2-1B: 4): 8 heads x 16 rows or 4 heads x 32 rows per workgroup
-                    const unsigned nh64 = (H / KV) % 8 == 0 ? 8u : ((H / KV) % 4 == 0 ? 4u : 0u);
-                    const bool eight64 = hd == 64 && nh64 && cfg.max_seq_len % 8 == 0 && (heads_given ? opt.pf_attn_heads == 8 : (opt.pf_attn8_on && M >= opt.pf_attn8_rows64));
-                    if (eight64) {
-                        const unsigned rt64 = 128u / nh64, ntl = ((unsigned)M + rt64 - 1u) / rt64;
-                        const bool pr = pair_given ? opt.pf_attn8_pair != 0 : ((ntl + 1u) / 2u) * ((unsigned)H / nh64) >= (unsigned)dev->prop.multiProcessorCount;
-                        return launch(nh64 == 8 ? "mc_pf_attn8_bfloat_hd64_h8" : "mc_pf_attn8_bfloat_hd64_h4", pr ? (ntl + 1u) / 2u : ntl, (unsigned)H / nh64, 1, 512, 0,
-                                      pack(pf_q, L.kc, L.vt, pf_att, (uint32_t)M, (uint32_t)S, (uint32_t)H, (uint32_t)(H / KV),
-                                           (uint32_t)cfg.max_seq_len, scale_T, win, (const void*)pf_etab));
-                    }
-                    if (eight)
-                        return launch("mc_pf_attn8_bfloat_hd128", pair ? (ntl + 1u) / 2u : ntl, H / 4, 1, 512, 0,
-                                      pack(pf_q, L.kc, L.vt, pf_att, (uint32_t)M, (uint32_t)S, (uint32_t)H, (uint32_t)(H / KV),
-                                           (uint32_t)cfg.max_seq_len, scale_T, win, (const void*)pf_etab));
-                    if (four)
-                        return launch("mc_pf_attn4_bfloat_hd128", (M + 15) / 16, H / 4, 1, 256, 0,
-                                      pack(pf_q, L.kc, L.vt, pf_att, (uint32_t)M, (uint32_t)S, (uint32_t)H, (uint32_t)(H / KV),
-                                           (uint32_t)cfg.max_seq_len, scale_T, win, (const void*)pf_etab));
-                    return launch(std::string(two ? "mc_pf_attn2_bfloat_hd" : "mc_pf_attn_bfloat_hd") + std::to_string(hd), (M + 15) / 16, two ? H / 2 : H, 1, 256, 0,
+                    const attn_plan A = plan_attention(M);
+                    return launch(A.name, A.gx, A.gy, 1, A.block, 0,
                                   pack(pf_q, L.kc, L.vt, pf_att, (uint32_t)M, (uint32_t)S, (uint32_t)H, (uint32_t)(H / KV),
                                        (uint32_t)cfg.max_seq_len, scale_T, win, (const void*)pf_etab));
                 });
@@ -2260,31 +2273,10 @@ struct mc_decoder {
                                 (uint32_t)hd, (uint32_t)cfg.max_seq_len, win)); });
                 if (s != MC_OK) return s;
             }
-            // gemma3's post norms: the reduce of a split Wo / w2, the post norm with the residual and the next norm in one launch
-            // (prefill_kernels.hip mc_pf_rmsnorm2_parts_bfloat; MC_PF_NORM2=0: the three launches)
-            const bool norm2 = fold_norm && tb == 2 && opt.pf_norm2;
-            if (L.attention_post_norm && norm2 && gemm_to_parts(L.wo, pf_att, M, &sp, &gs)) {
-                if (gs != MC_OK) return gs;
-                s = timed("norm", [&] { return launch("mc_pf_rmsnorm2_parts_bfloat", M, 1, 1, 256, 0,
-                           pack((const void*)pf_part, sp, (uint32_t)M, (const void*)pf_x, pf_h, (const void*)L.attention_post_norm, (const void*)L.ffn_norm,
-                                pf_xn, (uint32_t)dim, cfg.norm_eps, mu)); });
-            } else if (L.attention_post_norm) {
-                s = timed("gemm_wo", [&] { return gemm(L.wo, 0, pf_att, pf_proj, nullptr, M); });
-                if (s != MC_OK) return s;
-                s = norm_rows(pf_proj, L.attention_post_norm, pf_x, pf_h, M, mu);
-                if (s != MC_OK) return s;
-                s = timed("norm", [&] { return norm_rows(pf_h, L.ffn_norm, nullptr, pf_xn, M, mu); });
-            } else if (fold_norm && gemm_to_parts(L.wo, pf_att, M, &sp, &gs)) {
-                if (gs != MC_OK) return gs;
-                // h = T(x + T(sum of the partials)) -> pf_h, rmsnorm(h) -> pf_xn: the reduce, the residual and the ffn norm in one launch
-                s = timed("norm", [&] { return launch("mc_pf_rmsnorm_parts_" + tname, M, 1, 1, 256, 0,
-                           pack((const void*)pf_part, sp, (uint32_t)M, (const void*)pf_x, pf_h, (const void*)L.ffn_norm, pf_xn, (uint32_t)dim,
-                                cfg.norm_eps, mu)); });
-            } else {
-                s = timed("gemm_wo", [&] { return gemm(L.wo, 1, pf_att, pf_h, pf_x, M); });
-                if (s != MC_OK) return s;
-                s = timed("norm", [&] { return norm_rows(pf_h, L.ffn_norm, nullptr, pf_xn, M, mu); });
-            }
+            bool xn_done;
+            s = gemm_residual(L.wo, pf_att, pf_x, pf_h, L.attention_post_norm, L.ffn_norm, "gemm_wo", M, mu, &xn_done);
+            if (s != MC_OK) return s;
+            if (!xn_done) s = timed("norm", [&] { return norm_rows(pf_h, L.ffn_norm, nullptr, pf_xn, M, mu); });
             if (s != MC_OK) return s;
             // (act(w1 x) * (w3 x) in the GEMM's epilogue was built -- the even lane of a column pair finishing it -- and measured
             //  SLOWER: 13.60 against 13.26 ms per 512-row prompt, 52.0 against 50.6 at 2048 rows: half the lanes idle through the
@@ -2293,17 +2285,19 @@ struct mc_decoder {
             // silu(w1 x) * (w3 x) in the epilogue of an unsplit 256-row GEMM (prefill_kernels.hip pf_gemm_big_body EPI 3; the
             // table of exponentials rides in `res`).  MC_PF_ACT_EPI=0: the separate launch
             // (gemma: gelu from the table of round 6 -- the 256 x 256 GEMM's e4 epilogue only; without the table the separate launch with its fp64 tanh)
-            const bool act_epi = opt.pf_act_epi && tb == 2 && !L.w13.lora_cols && !opt.pf_small_gemm && !pf2_ok(L.w13, M) &&
-                                 (g8_ok(L.w13, M) ? g8_splits(L.w13, M) == 1 && cfg.ffn_dim % 2 == 0 && (!gemma || pf_gtab)
-                                                  : !gemma && gemm_row_tile(M) == 256 && gemm_splits(L.w13, M) == 1 && !opt.pf_depth1) &&
-                                 !lib_ok(L.w13, M); // (the opt-in library GEMM + the separate activation launch)
+            const gemm_plan p13 = plan_gemm(L.w13, M, 0);
+            const bool act_epi = opt.pf_act_epi && !L.w13.lora_cols && p13.splits == 1 &&
+                                 (p13.fam == gemm_family::g8 ? cfg.ffn_dim % 2 == 0 && (!gemma || pf_gtab)
+                                                             : p13.fam == gemm_family::tiled && !gemma && p13.bm == 256 && !opt.pf_depth1);
             const void* act_tab = gemma ? (const void*)pf_gtab : (const void*)pf_etab; // (gelu without a table: nullptr, the kernels evaluate it)
+            // (the library GEMM writes bfloat16 rows for the separate activation launch: half the bytes of fp32 partials)
+            const gemm_done g13 = !act_epi && cfg.ffn_dim % 4 == 0 && p13.fam != gemm_family::lib ? gemm_to_parts(L.w13, pf_xn, M) : gemm_done{MC_OK, 0};
+            if (g13.st != MC_OK) return g13.st;
             if (act_epi) {
                 s = timed("gemm_w13_act", [&] { return gemm(L.w13, gemma ? 4 : 3, pf_xn, pf_g, act_tab, M); });
-            } else if (cfg.ffn_dim % 4 == 0 && !lib_ok(L.w13, M) && gemm_to_parts(L.w13, pf_xn, M, &sp, &gs)) { // (library: bfloat16 rows out, half the bytes of fp32 partials)
-                if (gs != MC_OK) return gs;
+            } else if (g13.splits) {
                 s = timed("act_mul", [&] { return launch("mc_pf_act_mul_parts_" + tname, (cfg.ffn_dim / 4 + 255) / 256 + 1, M, 1, 256, 0,
-                           pack((const void*)pf_part, sp, (uint32_t)M, pf_g, (uint32_t)cfg.ffn_dim, (int32_t)(gemma ? 1 : 0), act_tab)); });
+                           pack((const void*)pf_part, g13.splits, (uint32_t)M, pf_g, (uint32_t)cfg.ffn_dim, (int32_t)(gemma ? 1 : 0), act_tab)); });
             } else {
                 s = timed("gemm_w13", [&] { return gemm(L.w13, 0, pf_xn, pf_g2, nullptr, M); });
                 if (s != MC_OK) return s;
@@ -2312,28 +2306,9 @@ struct mc_decoder {
                                    : pack(pf_g2, pf_g, (uint32_t)cfg.ffn_dim, (int32_t)(gemma ? 1 : 0))); });
             }
             if (s != MC_OK) return s;
-            if (L.ffn_post_norm && norm2 && gemm_to_parts(L.w2, pf_g, M, &sp, &gs)) {
-                if (gs != MC_OK) return gs;
-                // x = T(h + post_norm(T(sum))) -> pf_x (the block's output), and the NEXT block's attention norm of it -> pf_xn
-                const void* wn = li + 1 < n_own ? (const void*)layers[li + 1].attention_norm : (const void*)nullptr;
-                s = timed("norm", [&] { return launch("mc_pf_rmsnorm2_parts_bfloat", M, 1, 1, 256, 0,
-                           pack((const void*)pf_part, sp, (uint32_t)M, (const void*)pf_h, pf_x, (const void*)L.ffn_post_norm, wn, pf_xn, (uint32_t)dim,
-                                cfg.norm_eps, mu)); });
-                xn_ready = wn != nullptr;
-            } else if (L.ffn_post_norm) {
-                s = timed("gemm_w2", [&] { return gemm(L.w2, 0, pf_g, pf_proj, nullptr, M); });
-                if (s != MC_OK) return s;
-                s = norm_rows(pf_proj, L.ffn_post_norm, pf_h, pf_x, M, mu);
-            } else if (fold_norm && li + 1 < n_own && gemm_to_parts(L.w2, pf_g, M, &sp, &gs)) {
-                if (gs != MC_OK) return gs;
-                // x = T(h + T(sum)) -> pf_x (the block's output), and the NEXT block's attention norm of it -> pf_xn
-                s = timed("norm", [&] { return launch("mc_pf_rmsnorm_parts_" + tname, M, 1, 1, 256, 0,
-                           pack((const void*)pf_part, sp, (uint32_t)M, (const void*)pf_h, pf_x, (const void*)layers[li + 1].attention_norm, pf_xn,
-                                (uint32_t)dim, cfg.norm_eps, mu)); });
-                xn_ready = true;
-            } else {
-                s = timed("gemm_w2", [&] { return gemm(L.w2, 1, pf_g, pf_x, pf_h, M); });
-            }
+            // x = T(h + ...) -> pf_x (the block's output), and the NEXT block's attention norm of it -> pf_xn where the fold wrote it
+            const void* wn = li + 1 < n_own ? (const void*)layers[li + 1].attention_norm : (const void*)nullptr;
+            s = gemm_residual(L.w2, pf_g, pf_h, pf_x, L.ffn_post_norm, wn, "gemm_w2", M, mu, &xn_ready);
             if (s != MC_OK) return s;
             if (taps_on)
                 MC_HIP(hipMemcpyAsync((char*)taps + (size_t)(li + 1) * dim * tb, (char*)pf_x + last, (size_t)dim * tb,

@@ -768,7 +768,7 @@ MC_PF_GEMM_BIG(mc_pf_gemm128_w_bfloat_e2, PF_W_T, 2)
 // two chunks in flight per workgroup (204 VGPRs, two workgroups per CU): the default -- faster than one
 // chunk (144 VGPRs, three per CU) at every prompt length, 6.3 vs 6.9 ms at 128 rows, 14.5 vs 16.2 at
 // 512, 54.0 vs 55.5 at 2048; three chunks (220 VGPRs) lose again: 7.0 / 15.7 / 56.7 ms
-// 256 rows of X per workgroup (eight waves): mc_pf_gemm256_* -- prompts of 256 rows and more (decoder.cc gemm())
+// 256 rows of X per workgroup (eight waves): mc_pf_gemm256_* -- prompts of 256 rows and more (decoder.cc plan_gemm / gemm_row_tile)
 #define MC_PF_GEMM_256(NAME, WF, EPI)                                                                   \
     extern "C" __global__ void __launch_bounds__(512)                                                   \
     NAME(const void* w, const void* scales, const bf16_t* X, bf16_t* Y, const bf16_t* res, uint32_t M,  \
