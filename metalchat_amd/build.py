@@ -22,7 +22,7 @@ KERNEL_SOURCES = [os.path.join(CSRC, "kernels", f) for f in (
     "metalchat_kernels.hip", "ref_kernels.hip", "gemv_kernels.hip", "decode_kernels.hip", "attn_block_kernels.hip",
     "synth_kernels.hip", "sampler_kernels.hip", "prefill_kernels.hip", "batch_kernels.hip", "packed_kernels.hip", "extend_kernels.hip", "verify_kernels.hip", "wide_kernels.hip", "tree_kernels.hip", "common.h", "abi.h", "handoff.h", "gemv.h", "gemv_ksplit.h", "synth.h", "pf_gemm8.h")]
 HOST_SOURCES = [os.path.join(CSRC, f) for f in ("backend.cc", "decoder.cc", "batch.cc", "model_io.cc", "text.cc", "json_min.h", "backend_impl.h",
-                                                 "decoder_batch.h")] + [
+                                                 "decoder_batch.h", "decoder_options.h", "gemv_plan.h")] + [
     os.path.join(CSRC, "kernels", "synth.h"), os.path.join(CSRC, "kernels", "abi.h"),
     os.path.join(os.path.dirname(HERE), "include", "metalchat_hip.h")]
 
@@ -103,6 +103,19 @@ def build_text_test(force: bool = False) -> str:
         subprocess.check_call(["g++", "-std=c++17", "-O1", "-I" + os.path.join(root, "include"), src,
                                "-o", out, "-L" + LIB, "-lmetalchat_hip",
                                "-Wl,-rpath," + LIB, "-Wl,-rpath,/opt/rocm/lib", "-pthread"])
+    return out
+
+
+def build_gemv_plan_test(force: bool = False) -> str:
+    """tests/cpp/test_gemv_plan: plan_gemv() (csrc/gemv_plan.h) from the command line -- a plain g++ program, no HIP and no host library.
+    Not part of build_all(): nothing of the package needs it, tests/test_gemv_plan_cpu.py builds it (a second or two) when it runs."""
+    root = os.path.dirname(HERE)
+    src = os.path.join(root, "tests", "cpp", "test_gemv_plan.cc")
+    out = os.path.join(root, "tests", "cpp", "test_gemv_plan")
+    deps = [src, os.path.join(CSRC, "gemv_plan.h"), os.path.join(CSRC, "decoder_options.h"),
+            os.path.join(root, "include", "metalchat_hip.h")]
+    if force or _stale(out, deps):
+        subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", src, "-o", out])
     return out
 
 

@@ -13,6 +13,7 @@
 // hipGraph per token.
 #include "backend_impl.h"
 #include "decoder_batch.h"
+#include "gemv_plan.h" // decoder_options / read_options (decoder_options.h) and plan_gemv
 #include "kernels/synth.h"
 
 #include <climits>
@@ -191,197 +192,6 @@ bit_width(uint32_t v)
     return n;
 }
 
-// Every switch of this file: the MC_* environment variables, read ONCE when a decoder is created (read_options below holds every getenv("MC_...") of
-// decoder.cc).  A switch keeps the name, default, clamp and meaning it was introduced with; the measurements behind a default stay next to its field.
-struct decoder_options {
-    // ---- the decode GEMVs (gemv())
-    int gemv_block = 256;        // MC_GEMV_BLOCK: threads of a classic GEMV workgroup (a multiple of 64 in [64, 1024], else 256)
-    int gemv_wgs_per_cu = 2;     // MC_GEMV_WGS_PER_CU (at least 1, else 2)
-    bool gemv_block_env = false; // MC_GEMV_BLOCK / MC_GEMV_WGS_PER_CU given: they apply to every kernel of the family
-    bool gemv_lin = true;        // MC_GEMV_LIN=0: classic kernels everywhere (A/B)
-    bool gemv_ling = true;       // MC_GEMV_LING=0: int8 / bfloat weights on the classic kernels (A/B)
-    bool i8_ling14 = true;       // MC_I8_LING14=0: int8 rows of 14 KiB (w2 of Llama-3-8B) on the classic kernel (A/B)
-    bool lin_split = true;       // MC_LIN_SPLIT=0: K = 3072 on the classic kernels (A/B)
-    bool ling_half = true;       // MC_LING_HALF=0: whole row pairs per wave whatever the matrix (A/B)
-    bool lin_k4_on = true;       // MC_LIN_K4=0: Gemma-7B's w2 on the one-pair-per-wave kernel (mc_gemv_i4_bfloat_lin12_*) instead of the K-split one (A/B, parity)
-    int lin_waves = 8;           // MC_LIN_WAVES (1 .. 16): tuning builds of the linear-order kernels with another workgroup size
-    bool gemv_full_grid = false; // MC_GEMV_FULLGRID=1: as many workgroups as CUs allow even when that leaves waves without a row group (kernels built with MC_GEMV_WAVEMAJOR)
-    int dbg_variant = 0;         // MC_GEMV_DBG=1 stream-only, 2 compute-only (tuning ablations)
-    int gemv_m4 = 2;             // MC_GEMV_M4: 0 = exact int4 on the VALU (v_dot2c), 1 = dot products on the 4x4x4 MFMA, 2 = dequantisation too where a SIMD holds > 1 wave, 3 = always
-    int time_gemv_layers = 0;    // MC_TIME_GEMV_LAYERS=n (tuning aid of mc_decoder_time_gemv): every "layer" of the pass uses the weights of layer
-                                 // i % n, so with a small n the matrices stay resident in the 256 MiB Infinity Cache; 0 = every layer its own
-    // ---- the decode attention block (plan_block)
-    bool attn_fused = true;      // MC_ATTN_FUSED=0: scores and P.V as two launches (A/B, parity).  What the configuration asked for: mc_decoder::attn_fused_on is
-                                 // what holds now (handoff_failed, note_clean_tokens)
-    // ... while the launch is at most this many 256-thread workgroups per CU (MC_ATTN_FUSED_WGS, 1 .. 4).  Measured: at S = 8192 with
-    // 64-slot ranges (128 ranges x 8 kv heads = 4 per CU, every hand-off gathering from 128 producers) the one launch took 27.8 us
-    // against 6.3 + 8.5 for the two -- long contexts keep the two-launch form (wider ranges were built and measured no better)
-    unsigned attn_fused_max_wgs_per_cu = 2;
-    bool attn_t2_on = true;      // MC_ATTN_T2
-    int rearm_after = 256;       // MC_HANDOFF_REARM: tokens without a hand-off launch after which a fallen-back decoder takes the one-launch blocks again (0: never;
-                                 // mc_decoder::rearm_after starts here and doubles)
-    bool handoff_fast = true;    // MC_HANDOFF_FAST=0: hand-offs A and B through the fabric only (A/B; handoff.h "the XCD-local fast path")
-    bool attn_wo_on = true;      // MC_ATTN_WO=0: the Wo GEMV as a launch of its own behind the one-launch attention (A/B, parity)
-    bool attn_wo_k4 = false;     // MC_ATTN_WO_K4 set: mc_attn_wo_i4_*_hd128_k4 (K = 8192, Llama-3-70B: measured slower than the two launches -- attn_block_kernels.hip)
-    bool attn_qkv_on = true;     // MC_ATTN_QKV=0: wq|wk|wv as a launch of its own in front of mc_attn_wo_* (A/B, parity)
-    // MC_ATTN_QKV_ONLY=1: the 70B shapes' wq|wk|wv GEMV inside the attention launch (mc_attn_qkv_i4_bfloat_hd128_q4).  Built in round 5 as VERDICT r04
-    // item 2 (iv) asked, bit for bit the two launches, and NOT faster: 21.25 us against 11.65 + 9.04 in the trace (profiles/r05_kernel_stats_70b_qkvin.csv),
-    // 127.4 / 127.1 against 128.0 / 127.9 tokens/s alternating on one box -- 160 KB of wq|wk|wv per workgroup are 7 us of multiplication in front of
-    // the first hand-off, which is what the GEMV launch lasts.  Off by default.
-    bool attn_qkv_only_on = false;
-    bool attn_i8_on = true;      // MC_ATTN_I8: int8 wq|wk|wv and Wo inside the attention launch (plan_block: qkv_wo_i8)
-    bool attn_i4_wide_on = true; // MC_ATTN_I4_WIDE: the int4 block with 128- / 256-slot ranges at S = 4096 / 8192 (plan_block: qkv_wo_i4 with tiles > 1)
-    bool kv_virtual_on = true;   // MC_KV_VIRTUAL: fewer than 8 kv heads launched as 8 virtual ones where wq|wk|wv is inside the attention launch (kv_virtual_shift)
-    bool chain_w13_on = true;    // MC_CHAIN_W13=0: ffn_norm + w1|w3 + act*mul as a launch of its own behind the plain-weight attention block (A/B, parity)
-    int chain_f = -1;            // MC_CHAIN_F: pairs per fetcher wave of that chain instead of the rule's (tuning: tools/ab_case_multi.sh); -1 = not given
-    bool attn_qkv_qkn_on = true; // MC_ATTN_QKV_QKN=0: gemma3's wq|wk|wv GEMV as a launch of its own in front of mc_attn_wo_qkn_* (A/B, parity)
-    bool attn_wo_qkn_on = true;  // MC_ATTN_WO_QKN=0: gemma3's q/k-norm + rope + cache write + attention as mc_attn_fused_qkn_T, Wo as a GEMV of its own (A/B, parity)
-    bool attn_qkn_on = true;     // MC_ATTN_QKN=0: gemma3's q/k-norm + rope + cache write as a launch of their own (mc_rope_kv_T) in front of the attention (A/B, parity)
-    bool gemma_fuse = true;      // MC_GEMMA_UNFUSED=1: keep the post-norms as launches of their own
-    bool pv_fold_on = true;      // MC_PV_FOLD=0: P.V ranges reduced by their own launch (A/B, parity)
-    int pv_block = 1024;         // MC_PV_BLOCK: threads of a P.V workgroup (16 waves: one round of loads per wave at S = 2048; a multiple of 64 in [256, 1024], else 1024)
-    int pv_ranges = 0;           // MC_PV_RANGES (1 .. 64): ranges of the P.V launch; 0 = not given, by the context length (mc_decoder_create)
-    // ---- the output head
-    int head_pick_mode = 2;
-    bool head_pick_on = true;    // MC_HEAD_PICK: 0 = mc_argmax_T behind the head (round 1); 1 = the pick wholly inside the head's launch (atomic max
-                                 // + ticket per workgroup: parity-green, 1448 vs 1449 us per token -- the atomics cost what the launch costs);
-                                 // 2 = one key per workgroup + mc_argmax_keys, a one-workgroup launch over 8 KB instead of 256 KB of logits
-    bool lazy_pick_on = true;    // MC_LAZY_PICK
-    // ---- the prompt pass
-    bool pf2_on = true;          // MC_PF2: short prompts from the quad-interleaved copy
-    int pf2_wgs_per_cu = 1;      // MC_PF2_WGS_PER_CU (at least 1): workgroups per CU pf2_split aims at
-    bool pf_attn8_on = true;     // MC_PF_ATTN8: the prompt attention with K / V tiles through LDS, from pf_attn8_rows rows on
-    int pf_attn8_rows = 1024;    // MC_PF_ATTN8_ROWS
-    int pf_attn8_rows64 = 1793;  // MC_PF_ATTN8_ROWS64 (head_dim 64: mc_pf_attn8_bfloat_hd64_h{8,4}; TinyLlama 2048 rows 8.35 against 8.95 ms, Llama-3.2-1B 6.57 against 7.0; 1536 - 1792 rows equal, 1024: 5.1 against 4.9 -- profiles/r06_pf_hd64_attn8_ab.log)
-    int pf_attn8_rows256 = 513;  // MC_PF_ATTN8_ROWS256 (head_dim 256: mc_pf_attn8_bfloat_hd256; Gemma-7B shapes: 2048 rows 35.5 against 44.4 ms, 1024: 19.0 against 21.3, 512: equal, 256: 9.0 against 8.85)
-    int pf_attn_heads = -1;      // MC_PF_ATTN_HEADS=1 / 2 / 4 / 8: the prompt attention kernel by its query heads per workgroup instead of by the rules of prefill(); -1 = not given
-    int pf_attn8_pair = -1;      // MC_PF_ATTN8_PAIR=0 / 1: row tiles of the LDS-tile attention one per workgroup / in pairs; -1 = not given, by the grid
-    int pf_plain_mode = -1;      // MC_PF_PLAIN_COPY: 1 = the 256 x 256 prompt GEMM multiplies quantised matrices from their dequantised bfloat16 copy (linear_w::wd, built on
-                                 // first use, 2 bytes per weight more HBM: the very values the quantised loop stages in LDS, same loop, same sums bit for bit -- without
-                                 // the dequantisation that competes with the MFMAs for the issue port), 0 = from the quantised rows; unset = 1 iff the copies of every
-                                 // block's matrices fit an eighth of the device's memory (Llama-3-8B: 14 of 288 GB, yes; 70B: 137 GB, no)
-    bool pf_rope_pack = true;    // MC_PF_ROPE_PACK (prefill: the rope + cache launch with four rotation pairs per thread)
-    bool pf_g8_on = true;        // MC_PF_GEMM8: prompts of pf_g8_rows rows and more take the 256 x 256 ping-pong GEMM (kernels/pf_gemm8.h)
-    int pf_g8_max_splits = 16, pf_g8_min_ktiles = 8; // MC_PF_GEMM8_MAXSPLIT, MC_PF_GEMM8_MINKT: K ranges of a launch (g8_splits)
-    int pf_g8_rows = 257;        // MC_PF_GEMM8_ROWS: from TWO row tiles on (round 5 measured 256 rows 7.42 ms with, 7.06 without -- one row of tiles leaves half the chip idle -- and 512 rows
-                                 // 10.13 against 11.66, and set 384; round 6, on the dequantised copies: 256 rows 6.87 without against 7.65 with, 320 rows 11.2 against 8.95, 383: 11.3 against 9.2 --
-                                 // profiles/r06_pf_rows_ab.log)
-    bool pf_small_gemm = false;  // MC_PF_SMALL_GEMM set: the round-1 prompt GEMM for every matrix (A/B)
-    bool pf_depth1 = false;      // MC_PF_DEPTH=1: the one-chunk build of the tiled prompt GEMM (A/B; two K chunks in flight measured best at every length)
-    bool pf_bm128 = false;       // MC_PF_BM128 set: the 128-row prompt tile for every length
-    bool pf_splits_old = false;  // MC_PF_SPLITS_OLD set: the plain doubling rule of gemm_splits
-    bool pf_no_splitk = false;   // MC_PF_NO_SPLITK set: no prompt GEMM splits K
-    bool pf_fold_on = true;      // MC_PF_FOLD: the split-K reduce of a prompt GEMM inside the kernel that consumes its rows
-    bool pf_norm2 = true;        // MC_PF_NORM2=0: the split-K reduce and gemma3's two norms behind it as three launches
-    bool pf_act_epi = true;      // MC_PF_ACT_EPI=0: the activation of a long prompt as a launch of its own
-    bool pf_gelu_table = true;   // MC_PF_GELU_TABLE=0: no table of T(gelu) (mc_decoder::pf_gtab): the fp64 tanh per element
-    bool pf_lib = false;         // MC_PF_BLASLT=1 (opt-in since round 5, a comparison aid): long prompts' large GEMMs in hipBLASLt on a dequantised bfloat16 copy of the matrix
-                                 // (gemm_lib; mc_decoder::pf_lib_on is what holds now: any failure of the library switches the path off)
-    bool pf_lib_force = false;   // MC_PF_BLASLT=2: every prompt GEMM that can, whatever its size
-    bool pf_lib_tune = false;    // MC_PF_BLASLT_TUNE=1: the fastest of the heuristic's first eight algorithms, timed once per shape, instead of its first
-                                 // (measured: inside the noise -- 512 rows 10.13 / 9.91 ms without, 10.04 / 10.00 with; 2048 rows 32.92 / 33.52, 32.55 / 32.92 --
-                                 // and a timed choice would make the order of the fp32 additions differ from run to run: off)
-    int pf_lib_rows = 160;       // MC_PF_BLASLT_ROWS: the shortest prompt chunk whose GEMMs may take the library (measured: 128 rows 5.01 ms without against
-                                 // 5.38 with, 160 rows 6.83 / 5.96, 192: 6.91 / 6.33, 224: 7.08 / 6.44 -- profiles/r04_prefill_blaslt.log)
-    int pf_lib_tiles = 48;       // MC_PF_BLASLT_TILES: the fewest 256 x 256 tiles of a launch the library takes (swept on whole prompts: profiles/r04_prefill_blaslt.log)
-    bool pf_lib_verbose = false; // MC_PF_BLASLT_VERBOSE set: say on stderr why the library path switched itself off, and which algorithm a tuned shape took
-    // MC_PF_TIMING=1: per-category GPU time of a prompt pass printed to stderr (tuning aid; it
-    // synchronises after every launch)
-    bool pf_timing = false;
-    bool pf_two_pass = false;    // MC_PF_TWO_PASS=1: scores + pv kernels with the probability scratch (always for T = float)
-};
-
-// the three shapes a switch takes: on / off with a default, an integer clamped to [lo, hi], "is it set at all"
-bool
-env_set(const char* name) { return getenv(name) != nullptr; }
-bool
-env_flag(const char* name, bool dflt) { return env_set(name) ? atoi(getenv(name)) != 0 : dflt; }
-int
-env_int(const char* name, int dflt, int lo = INT_MIN, int hi = INT_MAX) { return env_set(name) ? std::max(lo, std::min(hi, atoi(getenv(name)))) : dflt; }
-
-decoder_options
-read_options()
-{
-    decoder_options o;
-    o.gemv_block = env_int("MC_GEMV_BLOCK", o.gemv_block);
-    o.gemv_wgs_per_cu = env_int("MC_GEMV_WGS_PER_CU", o.gemv_wgs_per_cu);
-    o.gemv_block_env = env_set("MC_GEMV_BLOCK") || env_set("MC_GEMV_WGS_PER_CU");
-    if (o.gemv_block % 64 || o.gemv_block < 64 || o.gemv_block > 1024) o.gemv_block = 256;
-    if (o.gemv_wgs_per_cu < 1) o.gemv_wgs_per_cu = 2;
-    o.gemv_lin = env_flag("MC_GEMV_LIN", o.gemv_lin);
-    o.gemv_ling = env_flag("MC_GEMV_LING", o.gemv_ling);
-    o.i8_ling14 = env_flag("MC_I8_LING14", o.i8_ling14);
-    o.lin_split = env_flag("MC_LIN_SPLIT", o.lin_split);
-    o.ling_half = env_flag("MC_LING_HALF", o.ling_half);
-    o.lin_k4_on = env_flag("MC_LIN_K4", o.lin_k4_on);
-    o.lin_waves = env_int("MC_LIN_WAVES", o.lin_waves, 1, 16);
-    o.gemv_full_grid = env_flag("MC_GEMV_FULLGRID", o.gemv_full_grid);
-    o.dbg_variant = env_int("MC_GEMV_DBG", o.dbg_variant);
-    o.gemv_m4 = env_int("MC_GEMV_M4", o.gemv_m4);
-    o.time_gemv_layers = env_int("MC_TIME_GEMV_LAYERS", 0, 0);
-
-    o.attn_fused = env_flag("MC_ATTN_FUSED", o.attn_fused);
-    o.attn_fused_max_wgs_per_cu = (unsigned)env_int("MC_ATTN_FUSED_WGS", (int)o.attn_fused_max_wgs_per_cu, 1, 4);
-    o.attn_t2_on = env_flag("MC_ATTN_T2", o.attn_t2_on);
-    o.rearm_after = env_int("MC_HANDOFF_REARM", o.rearm_after, 0);
-    o.handoff_fast = env_flag("MC_HANDOFF_FAST", o.handoff_fast);
-    o.attn_wo_on = env_flag("MC_ATTN_WO", o.attn_wo_on);
-    o.attn_wo_k4 = env_set("MC_ATTN_WO_K4");
-    o.attn_qkv_on = env_flag("MC_ATTN_QKV", o.attn_qkv_on);
-    o.attn_qkv_only_on = env_flag("MC_ATTN_QKV_ONLY", o.attn_qkv_only_on);
-    o.attn_i8_on = env_flag("MC_ATTN_I8", o.attn_i8_on);
-    o.attn_i4_wide_on = env_flag("MC_ATTN_I4_WIDE", o.attn_i4_wide_on);
-    o.kv_virtual_on = env_flag("MC_KV_VIRTUAL", o.kv_virtual_on);
-    o.chain_w13_on = env_flag("MC_CHAIN_W13", o.chain_w13_on);
-    o.chain_f = env_int("MC_CHAIN_F", o.chain_f, 0);
-    o.attn_qkv_qkn_on = env_flag("MC_ATTN_QKV_QKN", o.attn_qkv_qkn_on);
-    o.attn_wo_qkn_on = env_flag("MC_ATTN_WO_QKN", o.attn_wo_qkn_on);
-    o.attn_qkn_on = env_flag("MC_ATTN_QKN", o.attn_qkn_on);
-    o.gemma_fuse = !env_flag("MC_GEMMA_UNFUSED", !o.gemma_fuse);
-    o.pv_fold_on = env_flag("MC_PV_FOLD", o.pv_fold_on);
-    o.pv_block = env_int("MC_PV_BLOCK", o.pv_block);
-    if (o.pv_block % 64 || o.pv_block < 256 || o.pv_block > 1024) o.pv_block = 1024;
-    o.pv_ranges = env_int("MC_PV_RANGES", o.pv_ranges, 1, 64);
-
-    o.head_pick_mode = env_int("MC_HEAD_PICK", o.head_pick_mode, 0, 2);
-    o.head_pick_on = o.head_pick_mode != 0;
-    o.lazy_pick_on = env_flag("MC_LAZY_PICK", o.lazy_pick_on);
-
-    o.pf2_on = env_flag("MC_PF2", o.pf2_on);
-    o.pf2_wgs_per_cu = env_int("MC_PF2_WGS_PER_CU", o.pf2_wgs_per_cu, 1);
-    o.pf_attn8_on = env_flag("MC_PF_ATTN8", o.pf_attn8_on);
-    o.pf_attn8_rows = env_int("MC_PF_ATTN8_ROWS", o.pf_attn8_rows, 1);
-    o.pf_attn8_rows64 = env_int("MC_PF_ATTN8_ROWS64", o.pf_attn8_rows64, 1);
-    o.pf_attn8_rows256 = env_int("MC_PF_ATTN8_ROWS256", o.pf_attn8_rows256, 1);
-    o.pf_attn_heads = env_int("MC_PF_ATTN_HEADS", o.pf_attn_heads, 0);
-    o.pf_attn8_pair = env_set("MC_PF_ATTN8_PAIR") ? (env_flag("MC_PF_ATTN8_PAIR", false) ? 1 : 0) : -1;
-    o.pf_plain_mode = env_set("MC_PF_PLAIN_COPY") ? (env_flag("MC_PF_PLAIN_COPY", false) ? 1 : 0) : -1;
-    o.pf_rope_pack = env_flag("MC_PF_ROPE_PACK", o.pf_rope_pack);
-    o.pf_g8_on = env_flag("MC_PF_GEMM8", o.pf_g8_on);
-    o.pf_g8_rows = env_int("MC_PF_GEMM8_ROWS", o.pf_g8_rows, 1);
-    o.pf_g8_max_splits = env_int("MC_PF_GEMM8_MAXSPLIT", o.pf_g8_max_splits, 1);
-    o.pf_g8_min_ktiles = env_int("MC_PF_GEMM8_MINKT", o.pf_g8_min_ktiles, 1);
-    o.pf_small_gemm = env_set("MC_PF_SMALL_GEMM");
-    o.pf_depth1 = env_int("MC_PF_DEPTH", 0) == 1;
-    o.pf_bm128 = env_set("MC_PF_BM128");
-    o.pf_splits_old = env_set("MC_PF_SPLITS_OLD");
-    o.pf_no_splitk = env_set("MC_PF_NO_SPLITK");
-    o.pf_fold_on = env_flag("MC_PF_FOLD", o.pf_fold_on);
-    o.pf_norm2 = env_flag("MC_PF_NORM2", o.pf_norm2);
-    o.pf_act_epi = env_flag("MC_PF_ACT_EPI", o.pf_act_epi);
-    o.pf_gelu_table = env_flag("MC_PF_GELU_TABLE", o.pf_gelu_table);
-    const int lib = env_int("MC_PF_BLASLT", 0);
-    o.pf_lib = lib != 0;
-    o.pf_lib_force = lib == 2;
-    o.pf_lib_tune = env_flag("MC_PF_BLASLT_TUNE", o.pf_lib_tune);
-    o.pf_lib_rows = env_int("MC_PF_BLASLT_ROWS", o.pf_lib_rows, 1);
-    o.pf_lib_tiles = env_int("MC_PF_BLASLT_TILES", o.pf_lib_tiles, 1);
-    o.pf_lib_verbose = env_set("MC_PF_BLASLT_VERBOSE");
-    o.pf_timing = env_flag("MC_PF_TIMING", o.pf_timing);
-    o.pf_two_pass = env_flag("MC_PF_TWO_PASS", o.pf_two_pass);
-    return o;
-}
-
 } // namespace
 
 struct mc_decoder {
@@ -535,10 +345,9 @@ struct mc_decoder {
     std::vector<void*> allocs;
     bool pn_ready = false;
     // test / measurement aids: the names of the kernels launched eagerly since the log was switched on (a replayed graph
-    // launches what was logged when it was captured), and "tell me the kernel gemv() would launch" (no launch)
+    // launches what was logged when it was captured)
     bool log_on = false;
     std::vector<std::string> launch_log;
-    std::string* capture_name = nullptr;
 
     ~mc_decoder()
     {
@@ -747,39 +556,16 @@ struct mc_decoder {
     }
 
     // ---------------------------------------------------------------- launches
-    // does this linear take the linear-order kernels (gemv.h)?  int4 on bfloat rows, exact arithmetic, scale groups of
-    // whole 128-weight lane blocks, rows of 1, 2, 4, 7, 12 or 14 whole KiB, whole row groups
+    // which kernel a decode GEMV takes is decided in gemv_plan.h (plan_gemv); these three gates of it are also what the launches around a GEMV ask
+    gemv_env genv{}; // fixed at create time
+    static gemv_shape
+    shape_of(const linear_w& L) { return {L.fmt, L.out, L.in, L.group, L.lora_cols}; }
     bool
-    lin_ok(const linear_w& L) const
-    {
-        const bool m4 = L.fmt == MC_WFMT_I4 && tb == 2 && cfg.qmode == MC_QMODE_EXACT && opt.gemv_m4 && !opt.dbg_variant;
-        const bool m4d_ok = m4 && (L.group == 0 || L.group % 128 == 0) && L.in % 128 == 0;
-        const int nch = L.in % 2048 == 0 ? L.in / 2048 : 0;
-        return opt.gemv_lin && m4d_ok && L.out % 4 == 0 && (nch == 1 || nch == 2 || nch == 4 || nch == 7 || nch == 12 || nch == 14);
-    }
-    // ... rows of 1.5 KiB (K = 3072: Gemma-7B's QKV and w1|w3), two to a 3 KiB super row (gemv.h LSPLIT, `_lin3s_`)
+    lin_ok(const linear_w& L) const { return ::lin_ok(shape_of(L), genv); }
     bool
-    lin_split_ok(const linear_w& L) const
-    {
-        const bool m4 = L.fmt == MC_WFMT_I4 && tb == 2 && cfg.qmode == MC_QMODE_EXACT && opt.gemv_m4 && !opt.dbg_variant;
-        return opt.gemv_lin && opt.lin_split && m4 && L.group == 128 && L.in == 3072 && L.out % 4 == 0 && opt.lin_waves == 8 && !L.lora_cols;
-    }
-    // ... or the linear-order kernels of the VALU-dequantising formats (gemv.h LGEN): int8 / plain bfloat weights on
-    // bfloat rows, rows of 4 / 14 (int8) or 4 / 8 / 11 / 16 (bfloat) whole KiB; returns that count, 0 = no
+    lin_split_ok(const linear_w& L) const { return ::lin_split_ok(shape_of(L), genv); }
     int
-    ling_kib(const linear_w& L) const
-    {
-        if (!opt.gemv_lin || !opt.gemv_ling || tb != 2 || opt.dbg_variant || L.out % 4 != 0) return 0;
-        const size_t rb = row_bytes(L.fmt, L.in);
-        if (rb % 1024) return 0;
-        const int n = (int)(rb / 1024);
-        if (L.fmt == MC_WFMT_I8) {
-            const bool g_ok = L.group == 0 || (L.group % 16 == 0 && (L.group & (L.group - 1)) == 0);
-            return g_ok && (n == 4 || (n == 14 && opt.i8_ling14)) ? n : 0;
-        }
-        if (L.fmt == MC_WFMT_T) return (n == 4 || n == 8 || n == 11 || n == 16) ? n : 0;
-        return 0;
-    }
+    ling_kib(const linear_w& L) const { return ::ling_kib(shape_of(L), genv); }
     // P.V over four ranges of cache slots (256 workgroups instead of 64: a CU takes in ~ 25 GB/s, and 64 of them need
     // ~ 4 us for the V cache of one layer at S = 2048) with the range sums added by the Wo GEMV's prologue (gemv.h
     // PRO_PARTS) instead of a reduce launch
@@ -1097,13 +883,6 @@ struct mc_decoder {
         return P;
     }
 
-    // dynamic LDS of a linear-order int4 GEMV (gemv(): the padded row, the scratch, the parked sums of eight waves)
-    static unsigned
-    lin_lds_bytes(const linear_w& L)
-    {
-        return (unsigned)((size_t)(L.in + 2047) / 2048 * 2048 * 2 / 16 * 17) + 128u + 8u * 512u;
-    }
-
     // a hand-off inside a launch that gave up (bounded waits, decode_kernels.hip): reported once, then cleared
     mc_status
     check_handoffs(const step_state& st)
@@ -1151,127 +930,28 @@ struct mc_decoder {
         if (hipEventRecord(err_evt, stream) == hipSuccess) err_pending = true;
     }
 
+    // one decode GEMV: what plan_gemv (gemv_plan.h) says -- kernel, grid, workgroup, LDS -- behind the adaptor's own GEMV where the linear has one
     mc_status
     gemv(const linear_w& L, int pro, int epi, const void* x, void* y, const void* res,
          const void* norm_w, float mu)
     {
-        std::string name = "mc_gemv_";
-        name += L.fmt == MC_WFMT_I4 ? "i4_" : (L.fmt == MC_WFMT_I8 ? "i8_" : "w_");
-        name += tname;
-        unsigned block = (unsigned)opt.gemv_block, waves = block / 64;
-        unsigned cap = (unsigned)(dev->prop.multiProcessorCount * opt.gemv_wgs_per_cu);
-        if (L.fmt == MC_WFMT_I4 && tb == 2 && cfg.qmode == MC_QMODE_FAST) name += "_fast";
-        // Grid: one workgroup per four row groups, capped at opt.gemv_wgs_per_cu workgroups per CU (a
-        // whole multiple of the CU count: what has to balance is the work per CU -- its SIMDs
-        // time-share their waves -- so 3.5 row groups per wave on every CU beats an even 4 per
-        // wave on 448 workgroups, measured 19.0 vs 21.4 us on the 60 MB w1|w3 matrix).
-        const unsigned ng = (L.out + 3) / 4;
-        unsigned wgs = opt.gemv_full_grid ? ng : (ng + waves - 1) / waves;
-        if (wgs > cap) wgs = cap;
-        if (wgs == 0) wgs = 1;
-        // exact int4 on bfloat rows: dot products on the 4x4x4 MFMA (_m4); with scale groups that are
-        // whole 128-weight lane blocks the dequantisation goes there too (_m4d, gemv.h Q_M4D) -- when
-        // a SIMD holds more than one wave of the launch: the MFMA -> cvt_pk -> MFMA chain of a weight
-        // is longer than the VALU one and a lone wave per SIMD (Wo, w2: 1024 row groups) has nobody
-        // to hide it behind (8.2 vs 8.5 us per launch, profiles/r01_kernel_stats.csv).
-        const bool m4 = L.fmt == MC_WFMT_I4 && tb == 2 && cfg.qmode == MC_QMODE_EXACT && opt.gemv_m4 && !opt.dbg_variant;
-        const bool m4d_ok = m4 && (L.group == 0 || L.group % 128 == 0) && L.in % 128 == 0;
-        const bool shared_simd = std::min(wgs * waves, ng) > 4u * (unsigned)dev->prop.multiProcessorCount; // waves that own a row group
-        const bool m4d = m4d_ok && (opt.gemv_m4 >= 3 || (opt.gemv_m4 == 2 && shared_simd));
-        // linear-order main loop (gemv.h): rows of whole KiB (K a multiple of 2048: 1, 2, 4, 7 or 14 KiB), whole row groups
-        const int nch = L.in % 2048 == 0 ? L.in / 2048 : 0;
-        // (an adapted linear behind a post-norm: the linear-order `_p2_` kernels take the post-norm's pointers in the adaptor's
-        //  argument slots, gemv.h -- the classic kernels serve that combination)
-        const bool lin = lin_ok(L) && !(pro == 2 && L.lora_cols);
-        const int pe_code = pro * 10 + epi;
-        const bool lins = !lin && lin_split_ok(L) &&
-                          (pe_code == 0 || pe_code == 10 || pe_code == 1 || pe_code == 12 || pe_code == 13 || pe_code == 14 || pe_code == 20 || pe_code == 23);
-        const int ling = lin || lins || pro == 2 ? 0 : ling_kib(L);
-        if (pro == 3 && !lin && !ling) return fail(MC_ERR_RUNTIME, "gemv: the partial-sum prologue exists for the linear-order kernels only");
-        if (ling) {
-            name += "_ling" + std::to_string(ling);
-            block = 64u * (unsigned)opt.lin_waves;
-            waves = (unsigned)opt.lin_waves;
-            const unsigned cus = (unsigned)dev->prop.multiProcessorCount;
-            cap = cus * (opt.gemv_block_env ? (unsigned)opt.gemv_wgs_per_cu : 1u);
-            const unsigned np = (unsigned)L.out / 2;
-            wgs = (np + waves - 1) / waves;
-            // fewer pairs than half the waves a full grid has (the 2048-row matrices of the small models) and an epilogue that
-            // treats the rows of a pair separately: one ROW per wave (gemv.h LGEN, `half`)
-            if (opt.ling_half && (epi == 0 || epi == 1) && !L.lora_cols && 2u * np <= cap * waves && (unsigned)L.out % 2 == 0)
-                wgs = std::max(wgs, std::min(cap, ((unsigned)L.out + waves - 1) / waves));
-            if (wgs > cap) wgs = cap;
-            if (wgs > cus) wgs = wgs / cus * cus;
-        }
-        if (lins) {
-            // the loop's unit is a quad of rows (two super rows); one eight-wave workgroup per CU as below
-            name += "_lin3s";
-            block = 64u * (unsigned)opt.lin_waves;
-            waves = (unsigned)opt.lin_waves;
-            const unsigned cus = (unsigned)dev->prop.multiProcessorCount;
-            cap = cus * (opt.gemv_block_env ? (unsigned)opt.gemv_wgs_per_cu : 1u);
-            const unsigned nq = (unsigned)L.out / 4;
-            wgs = (nq + waves - 1) / waves;
-            if (wgs > cap) wgs = cap;
-            if (wgs > cus) wgs = wgs / cus * cus;
-        }
-        // long rows, few of them (Gemma-7B's w2: 1536 pairs of 12 KiB rows = one pair per wave on 192 CUs): the K range of a pair over four waves of a
-        // workgroup on EVERY CU (gemv_ksplit.h) -- at most eight pairs per workgroup, plain store or residual add, no adaptor
-        const unsigned cus_ = (unsigned)dev->prop.multiProcessorCount;
-        const bool k4 = lin && opt.lin_k4_on && nch == 12 && pro == 0 && (epi == 0 || epi == 1) && !L.lora_cols && opt.lin_waves == 8 &&
-                        (unsigned)L.out / 2 >= 4u * cus_ && ((unsigned)L.out / 2 + cus_ - 1) / cus_ <= 8u;
-        if (lin) {
-            name += "_lin" + std::to_string(nch) + (k4 ? "k4" : "");
-            // ONE workgroup of eight waves per CU: the activation row is staged once per CU and, with the raw barrier
-            // between the row requests and the first weight requests (gemv.h MC_GEMV_XBAR), always ahead of the weight
-            // stream in the CU's in-order memory pipe (w1|w3: 16.2 us against 17.3 with two four-wave workgroups)
-            // (the kernels are built for exactly this workgroup size, gemv_kernels.hip MC_LIN_WAVES: no blockDim load)
-            block = 64u * (unsigned)opt.lin_waves;
-            waves = (unsigned)opt.lin_waves;
-            cap = (unsigned)dev->prop.multiProcessorCount * (opt.gemv_block_env ? (unsigned)opt.gemv_wgs_per_cu : 1u);
-            // a CU takes in ~25 GB/s whatever its waves do, so what matters is equal BYTES PER CU: a whole multiple of
-            // the CU count, at least one row pair per wave (the kernel cuts the pairs into equal contiguous ranges)
-            const unsigned cus = (unsigned)dev->prop.multiProcessorCount;
-            const unsigned np = (unsigned)L.out / 2;
-            wgs = (np + waves - 1) / waves;
-            if (wgs > cap) wgs = cap;
-            if (wgs > cus) wgs = wgs / cus * cus;
-            if (k4) wgs = cus;
-        }
-        else if (lins) {}
-        else if (m4) name += m4d ? "_m4d" : "_m4";
-        if (L.fmt == MC_WFMT_I4 && tb == 2 && opt.dbg_variant && ((pro == 1 && epi == 2) || (pro == 0 && epi == 0)))
-            name += opt.dbg_variant == 1 ? "_dbgstream" : "_dbgnoload";
-        name += "_p" + std::to_string(pro) + "_e" + std::to_string(epi);
-        // LDS: activation row zero-padded to whole chunks (64 lanes x 16 B of packed weights) + scratch
-        const unsigned kpl = L.fmt == MC_WFMT_I4 ? 32 : (L.fmt == MC_WFMT_I8 ? 16 : (tb == 2 ? 8 : 4));
-        const unsigned chunk = 64 * kpl;
-        unsigned lds = (unsigned)((size_t)((L.in + chunk - 1) / chunk) * chunk * tb);
-        if (lins) lds = 3u * chunk * (unsigned)tb; // the row twice: [x, x] = three chunks of 2048
-        if (m4d || lin || lins) lds = lds / 16 * 17; // 16 bytes of padding per 256 for the transposed reads
-        lds += 128;
-        if (lin || ling || lins) lds += waves * 512; // parked row sums: 64 pairs x 8 bytes per wave (gemv.h PARKB)
-        // EPI_STORE_PICK leaves one key per workgroup in pick_keys (pick_slots of them, folded by mc_argmax_keys)
-        if (epi == 5 && wgs > pick_slots) wgs = pick_slots;
-        if (capture_name) {
-            *capture_name = name;
-            return MC_OK;
-        }
+        const gemv_plan P = plan_gemv(shape_of(L), genv, pro, epi);
+        if (P.error) return fail(MC_ERR_RUNTIME, P.error);
         if (L.lora_cols) {
             // a = T(A x): the stacked adaptor inputs through the same kernel family (same prologue,
             // so a pre-norm GEMV and its adaptor see the identical normalised row)
             mc_status s = gemv(*L.lora_a, pro, 0, x, L.lora_vec, pro == 2 ? res : nullptr, norm_w, mu);
             if (s != MC_OK) return s;
         }
-        if (pro == 2 && (lin || lins)) {
+        if (P.postnorm_by_value) {
             const auto it = pn_host.find(res);
             if (it == pn_host.end()) return fail(MC_ERR_RUNTIME, "gemv: unknown post-norm descriptor");
             const postnorm_args& h = it->second;
-            return launch(name, wgs, 1, 1, block, lds,
+            return launch(P.name, P.wgs, 1, 1, P.block, P.lds,
                           pack(L.w, L.scales, x, y, (const void*)h.res, norm_w, (uint32_t)L.out, (uint32_t)L.in, (uint32_t)L.group,
                                cfg.norm_eps, mu, (const void*)h.post_w, (const void*)h.h_out, (uint32_t)0, 0.0f));
         }
-        return launch(name, wgs, 1, 1, block, lds,
+        return launch(P.name, P.wgs, 1, 1, P.block, P.lds,
                       pack(L.w, L.scales, x, y, res, norm_w, (uint32_t)L.out, (uint32_t)L.in,
                            (uint32_t)L.group, cfg.norm_eps, mu, (const void*)L.lora_vec,
                            (const void*)L.lora_b, (uint32_t)L.lora_cols, L.lora_scale));
@@ -2396,6 +2076,7 @@ mc_decoder_create(mc_device* dev, mc_library* lib, mc_queue* q, const mc_decoder
     d->first_stage = c.layer_begin == 0;
     d->last_stage = c.layer_end == c.n_layers;
     d->opt = read_options();
+    d->genv = gemv_env{d->tb, (int)c.qmode, (unsigned)dev->prop.multiProcessorCount, mc_decoder::pick_slots, &d->opt};
     d->attn_fused_on = d->opt.attn_fused;
     d->rearm_after = d->opt.rearm_after;
     d->pf_lib_on = d->opt.pf_lib;
@@ -3267,6 +2948,43 @@ mc_decoder_launch_log_read(mc_decoder* d, char* buf, size_t cap)
     return all.size() + 1;
 }
 
+// The decode GEMVs of one pass of mc_decoder_time_gemv(which), in launch order: "qkv", "wo", "w13", "w2" of every owned block (MC_TIME_GEMV_LAYERS=n: with the
+// weights of block i % n), then "head" on the last stage; "all" = every one.  Each is the variant the token really launches: gemma3's plain stores; Wo with the
+// residual epilogue, and the partial-sum prologue when P.V is folded (its result goes to `proj`, so the hidden row stays what it was); the head with the greedy
+// pick inside (one key per workgroup into pick_keys; the step state is not touched) when run_head() would take it.
+struct timed_gemv {
+    const char* which;
+    const linear_w* L;
+    int pro, epi;
+    const void* x;
+    void* y;
+    const void* res;
+    const void* norm_w;
+};
+static std::vector<timed_gemv>
+timed_gemvs(mc_decoder* d, const std::string& w)
+{
+    const bool gemma = d->cfg.family == MC_FAMILY_GEMMA3;
+    const size_t lim = d->opt.time_gemv_layers ? (size_t)d->opt.time_gemv_layers : d->layers.size(); // (MC_TIME_GEMV_LAYERS)
+    std::vector<timed_gemv> all;
+    for (size_t li = 0; li < d->layers.size(); li++) {
+        const layer_w& L = d->layers[li % lim];
+        const bool fold = !d->attn_fused() && !d->attn_fused_t2() && d->pv_fold(L.wo);
+        all.push_back({"qkv", &L.qkv, 1, gemma ? 0 : 4, d->hidden, d->qkv, gemma ? nullptr : L.qkv_epi, L.attention_norm});
+        all.push_back({"wo", &L.wo, fold ? 3 : 0, gemma ? 0 : 1, fold ? (const void*)d->pv_parts : (const void*)d->attn_out, d->proj, gemma ? nullptr : d->hidden, nullptr});
+        all.push_back({"w13", &L.w13, 1, gemma ? 3 : 2, d->hidden, d->gate, nullptr, L.ffn_norm});
+        all.push_back({"w2", &L.w2, 0, gemma ? 0 : 1, d->gate, d->proj, gemma ? nullptr : d->hidden, nullptr});
+    }
+    if (d->last_stage) {
+        const bool pick = d->head_pick();
+        all.push_back({"head", &d->output, 1, pick ? 5 : 0, d->hidden, d->logits, pick ? (const void*)(d->pick_desc + offsetof(pick_block, per_wg)) : nullptr, d->final_norm});
+    }
+    std::vector<timed_gemv> out;
+    for (const timed_gemv& g : all)
+        if (w == "all" || w == g.which) out.push_back(g);
+    return out;
+}
+
 mc_status
 mc_decoder_gemv_kernel_name(mc_decoder* d, const char* which, char* buf, size_t cap)
 {
@@ -3285,14 +3003,15 @@ mc_decoder_gemv_kernel_name(mc_decoder* d, const char* which, char* buf, size_t 
         buf[n0] = 0;
         return MC_OK;
     }
-    d->capture_name = &name;
-    float ms = 0.0f;
-    mc_status s = mc_decoder_time_gemv(d, which, 1, &ms, nullptr, nullptr);
-    d->capture_name = nullptr;
+    mc_status s = check_ready(d);
     if (s != MC_OK) return s;
-    if (name.empty()) return fail(MC_ERR_INVALID_ARGUMENT, std::string("mc_decoder_gemv_kernel_name: no such GEMV '") + which + "'");
-    const size_t n = std::min(cap - 1, name.size());
-    memcpy(buf, name.data(), n);
+    const std::vector<timed_gemv> table = timed_gemvs(d, which);
+    if (table.empty()) return fail(MC_ERR_INVALID_ARGUMENT, std::string("mc_decoder_gemv_kernel_name: no such GEMV '") + which + "'");
+    const timed_gemv& g = table.front();
+    const gemv_plan P = plan_gemv(mc_decoder::shape_of(*g.L), d->genv, g.pro, g.epi);
+    if (P.error) return fail(MC_ERR_RUNTIME, P.error);
+    const size_t n = std::min(cap - 1, P.name.size());
+    memcpy(buf, P.name.data(), n);
     buf[n] = 0;
     return MC_OK;
 }
@@ -3306,65 +3025,29 @@ mc_decoder_time_gemv(mc_decoder* d, const char* which, int32_t repeats, float* t
     mc_status s = check_ready(d);
     if (s != MC_OK) return s;
     MC_HIP(hipSetDevice(d->dev->ordinal));
-    const std::string w = which;
     const float mu = d->cfg.family == MC_FAMILY_GEMMA3 ? 1.0f : 0.0f;
-    const bool gemma = d->cfg.family == MC_FAMILY_GEMMA3;
+    const std::vector<timed_gemv> table = timed_gemvs(d, which);
     double bytes = 0;
-    int launches = 0;
-    const size_t lim = d->opt.time_gemv_layers ? (size_t)d->opt.time_gemv_layers : d->layers.size(); // (MC_TIME_GEMV_LAYERS)
-    auto pass = [&](bool count) -> mc_status {
-        mc_status r = MC_OK;
-        for (size_t li = 0; li < d->layers.size(); li++) {
-            layer_w& L = d->layers[li % lim];
-            if (w == "qkv" || w == "all") {
-                r = gemma ? d->gemv(L.qkv, 1, 0, d->hidden, d->qkv, nullptr, L.attention_norm, mu)
-                          : d->gemv(L.qkv, 1, 4, d->hidden, d->qkv, L.qkv_epi, L.attention_norm, mu);
-                if (r != MC_OK) return r;
-                if (count) { bytes += linear_bytes(L.qkv); launches++; }
-            }
-            if (w == "wo" || w == "all") {
-                // the variant the token really launches (residual epilogue; the partial-sum prologue when P.V is folded);
-                // the result goes to `proj`, so the hidden row stays what it was
-                const bool fold = !d->attn_fused() && !d->attn_fused_t2() && d->pv_fold(L.wo);
-                r = d->gemv(L.wo, fold ? 3 : 0, gemma ? 0 : 1, fold ? (const void*)d->pv_parts : (const void*)d->attn_out, d->proj,
-                            gemma ? nullptr : d->hidden, nullptr, mu);
-                if (r != MC_OK) return r;
-                if (count) { bytes += linear_bytes(L.wo); launches++; }
-            }
-            if (w == "w13" || w == "all") {
-                r = d->gemv(L.w13, 1, gemma ? 3 : 2, d->hidden, d->gate, nullptr, L.ffn_norm, mu);
-                if (r != MC_OK) return r;
-                if (count) { bytes += linear_bytes(L.w13); launches++; }
-            }
-            if (w == "w2" || w == "all") {
-                r = d->gemv(L.w2, 0, gemma ? 0 : 1, d->gate, d->proj, gemma ? nullptr : d->hidden, nullptr, mu);
-                if (r != MC_OK) return r;
-                if (count) { bytes += linear_bytes(L.w2); launches++; }
-            }
-        }
-        if ((w == "head" || w == "all") && d->last_stage) {
-            // the variant the token really launches: with the greedy pick inside (one key per workgroup into pick_keys;
-            // the step state is not touched) when run_head() would take it
-            const bool pick = d->head_pick();
-            r = d->gemv(d->output, 1, pick ? 5 : 0, d->hidden, d->logits, pick ? (const void*)(d->pick_desc + offsetof(pick_block, per_wg)) : nullptr, d->final_norm, mu);
+    for (const timed_gemv& g : table) bytes += linear_bytes(*g.L);
+    auto pass = [&]() -> mc_status {
+        for (const timed_gemv& g : table) {
+            mc_status r = d->gemv(*g.L, g.pro, g.epi, g.x, g.y, g.res, g.norm_w, mu);
             if (r != MC_OK) return r;
-            if (count) { bytes += linear_bytes(d->output); launches++; }
         }
-        return r;
+        return MC_OK;
     };
-    s = pass(true); // warm-up + byte count
+    s = pass(); // warm-up
     if (s != MC_OK) return s;
-    if (d->capture_name) return MC_OK; // mc_decoder_gemv_kernel_name: the pass above launched nothing
     MC_HIP(hipEventRecord(d->q->t0, d->stream));
     for (int i = 0; i < repeats; i++) {
-        s = pass(false);
+        s = pass();
         if (s != MC_OK) return s;
     }
     MC_HIP(hipEventRecord(d->q->t1, d->stream));
     MC_HIP(hipEventSynchronize(d->q->t1));
     MC_HIP(hipEventElapsedTime(total_ms, d->q->t0, d->q->t1));
     if (bytes_per_pass) *bytes_per_pass = bytes;
-    if (launches_per_pass) *launches_per_pass = launches;
+    if (launches_per_pass) *launches_per_pass = (int32_t)table.size();
     return MC_OK;
 }
 

@@ -1,7 +1,7 @@
 """Every kernel the decoder can ask the code object for exists in it (no GPU needed: the names are read out of the built
 metalchat.hsaco).  The host forms GEMV names from (format, dtype, arithmetic, linear-order row length, prologue, epilogue) in
-decoder.cc::gemv(); a combination it may form but gemv_kernels.hip does not instantiate would only fail on the GPU, for the
-one model shape that reaches it."""
+csrc/gemv_plan.h plan_gemv(); a combination it may form but gemv_kernels.hip does not instantiate would only fail on the GPU, for the
+one model shape that reaches it.  (Which name a given shape gets, with its grid and LDS bytes: test_gemv_plan_cpu.py.)"""
 import itertools
 import os
 import subprocess
@@ -38,13 +38,13 @@ def test_classic_gemv_family_is_complete(symbols):
 
 def test_linear_order_families_are_complete(symbols):
     want = []
-    for nch in (1, 2, 4, 7, 12, 14):  # decoder.cc lin_ok(): int4 rows of whole KiB
+    for nch in (1, 2, 4, 7, 12, 14):  # gemv_plan.h lin_ok(): int4 rows of whole KiB
         want += [f"mc_gemv_i4_bfloat_lin{nch}_{pe}" for pe in PE + PE_FOLD + PE_PICK]
-    for nch in (4, 14):  # decoder.cc ling_kib(): int8
+    for nch in (4, 14):  # gemv_plan.h ling_kib(): int8
         want += [f"mc_gemv_i8_bfloat_ling{nch}_{pe}" for pe in PE + PE_FOLD + PE_PICK if not pe.startswith("p2")]
     for nch in (4, 8, 11, 16):  # ... and plain bfloat weights
         want += [f"mc_gemv_w_bfloat_ling{nch}_{pe}" for pe in PE + PE_FOLD + PE_PICK if not pe.startswith("p2")]
-    # rows of 1.5 KiB, two to a super row (gemv.h LSPLIT; decoder.cc lin_split_ok: K = 3072)
+    # rows of 1.5 KiB, two to a super row (gemv.h LSPLIT; gemv_plan.h lin_split_ok: K = 3072)
     want += [f"mc_gemv_i4_bfloat_lin3s_{pe}" for pe in PE]
     missing = [n for n in want if n not in symbols]
     assert not missing, missing

@@ -49,7 +49,7 @@ def classic_name(family, pro, epi):
 
 
 def lds_bytes(family, K, classic=False):
-    """decoder.cc gemv(): the activation row padded to whole chunks (int4: + 16 bytes per 256 for the transposed reads),
+    """csrc/gemv_plan.h plan_gemv(): the activation row padded to whole chunks (int4: + 16 bytes per 256 for the transposed reads),
     128 bytes of reduction scratch, 512 bytes of parked row sums per wave."""
     fmt = family.split("_")[0]
     chunk = {"i4": 2048, "i8": 1024, "w": 512}[fmt]
