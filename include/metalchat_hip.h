@@ -537,11 +537,33 @@ mc_status mc_tree_verify(mc_batch* b, const int32_t* tokens, const int32_t* pare
  * nothing enqueued and no row's length changed.  mc_rows_prefill and mc_extend_rows keep their own bound, a sum of lengths no
  * greater than max_seq_len.  Memory scales with batch as in Part 2b: batch x n_layers caches and the per-row scratch.
  * ------------------------------------------------------------------------------------------ */
-/* 1 <= batch <= 64 (MC_WIDE_BATCH_MAX of the kernel ABI).  Admission exactly as mc_batch_create (the same conditions and texts,
- * prefixed "mc_wide_batch_create: "); a batch outside the range: "mc_wide_batch_create: batch must lie in [1, 64]", checked
- * before anything of the decoder is looked at, as mc_batch_create does.  With batch <= 8 the call makes exactly what
- * mc_batch_create makes.  The handle is an mc_batch: every call of Parts 2b - 2g takes it, mc_batch_release frees it. */
+/* 1 <= batch <= 64 (MC_WIDE_BATCH_MAX of the kernel ABI).  Admits every decoder mc_batch_create admits, and more (Part 2i); the
+ * texts are prefixed "mc_wide_batch_create: ", those of conditions both calls share are the same; a batch outside the range:
+ * "mc_wide_batch_create: batch must lie in [1, 64]", checked before anything of the decoder is looked at, as mc_batch_create does.
+ * For a decoder mc_batch_create admits, with batch <= 8 the call makes exactly what mc_batch_create makes.  The handle is an
+ * mc_batch: every call of Parts 2b - 2g takes it, mc_batch_release frees it. */
 mc_status mc_wide_batch_create(mc_decoder* d, int32_t batch, mc_batch** out);
+
+/* ================================================================================================
+ * Part 2i -- QLoRA rows: what mc_wide_batch_create admits.  mc_batch_create keeps its predicate, texts and bound; the general
+ * entry also takes the one quantised checkpoint flavour the reference ships, MC_CKPT_META_LLAMA3_QLORA (int4 linears in groups of
+ * 32, a rank-16 LoRA adaptor on each, an int8 embedding table, an int8 head with one scale per row), and what lies between.  A
+ * decoder is admitted when
+ *   - as for mc_batch_create: single stage, family llama3, dtype bf16, MC_QMODE_EXACT, head_dim 128 or 64, n_heads a multiple of
+ *     n_kv_heads (at most 16 per kv head), max_seq_len >= 64, an embedding table of T or int8 with one scale per row, every linear
+ *     with out_features % 16 == 0 and in_features % 1024 == 0, and layer shapes that chain;
+ *   - each of the seven layer linears and the head, judged on its own, is MC_WFMT_T, MC_WFMT_I4 or MC_WFMT_I8, a quantised one in
+ *     groups that are a multiple of 32 or with one scale per row (group 0); the formats may differ between linears and from
+ *     cfg.weight_format (no "mixed weight formats" refusal on this entry);
+ *   - LoRA adaptors (mc_decoder_load_lora) sit on layer linears only, and the adaptor columns of a fused matrix -- adaptors x rank
+ *     -- are a multiple of 16, i.e. rank % 16 == 0: otherwise "<matrix>: LoRA rank must be a multiple of 16".
+ * A linear with an adaptor computes T(T(x Wd^T) + T(T(B (A x)) * scale)) per row, quantization::lora_linear's arithmetic
+ * (quantization/lora.h:119-121), in two launches: a = T(A x) for all rows, then the GEMV with the adaptor term in front of its
+ * epilogue.  The decoder is untouched (its own adaptor scratch is not used).  The row contract of Parts 2b - 2h holds unchanged:
+ * a row's tokens, logits and K / V do not depend on the batch size, its index or the other rows, bit for bit; every call of Parts
+ * 2b - 2g runs on such a batch with B from 1 to 64.  Not admitted: gemma3, MC_QMODE_FAST, float32, adaptors on the head, ranks
+ * that are not multiples of 16.
+ * ------------------------------------------------------------------------------------------ */
 
 /* Host-side helpers shared by tests and the synthetic initialiser. */
 /* value in [-7,7] (bits = 4) or [-127,127] (bits = 8), zero mean, of element (row, col) of matrix `matrix_id` */

@@ -1,5 +1,6 @@
 // Part 2b of include/metalchat_hip.h: batched decode -- B sequences in lockstep over one decoder's weights (B <= 8 from
-// mc_batch_create, B <= 64 from Part 2h's mc_wide_batch_create).
+// mc_batch_create, B <= 64 from Part 2h's mc_wide_batch_create, which since Part 2i also admits QLoRA decoders: int4 / int8 linears in
+// groups of 32, each linear in a format of its own, LoRA adaptors on the layer linears).
 //
 // The reference's layers carry the batch dimension already: nn::attention::operator() takes input[bs, len, dim]
 // (include/metalchat/nn/attention.h:163-206) and nn::sink_cache holds [max_batch_size, max_seq_len, n_kv_heads, head_dim],
@@ -35,6 +36,9 @@ struct mc_batch {
     void *qkv = nullptr;                  // [B][(H + 2 KV) hd]
     void *q = nullptr, *att = nullptr;    // [B][H hd]
     void *gate = nullptr;                 // [B][ffn]
+    void *lora_vec = nullptr;             // [B][lora_ld]: a = T(A x) of the linear in flight; only when some linear has an adaptor.  ONE
+                                          // scratch for all linears: every launch goes to the decoder's one stream, in order
+    int lora_ld = 0;                      // the most lora_cols of any linear
     void *logits = nullptr;               // [B][vocab]
     float *expv = nullptr, *psum = nullptr; // [B][H][max_seq], [B][H][nsplit]
     float *fcos = nullptr, *fsin = nullptr; // rope table rows [0, max_seq)
@@ -134,29 +138,50 @@ struct mc_batch {
                       pack(st, (int32_t)-1, (int32_t)pos, (int32_t)p.cfg.max_seq_len, (int32_t)p.pre_len, (int32_t)0, (int32_t)1));
     }
 
-    // 16-row weight tiles per workgroup of mc_wb_gemv_* for a matrix of `out` rows: the most of 8, 4, 2 that still brings a
-    // workgroup to every compute unit, else 1 (measured: DESIGN.md "Wide batches").  MC_WB_TILES is the experiment's handle.
+    // 16-row weight tiles per workgroup of mc_wb_gemv_* for the matrix L: the most of 8, 4, 2 that still brings a workgroup to
+    // every compute unit, else 1 (measured: DESIGN.md "Wide batches").  MC_WB_TILES is the experiment's handle.  At most 4 for an
+    // int8 matrix or one with an adaptor: those kernels run 8 tiles as two passes of 4 (wide_kernels.hip), which only fetches x twice.
     int
-    wb_tiles(int out) const
+    wb_tiles(const batch_linear& L) const
     {
-        if (wb_tiles_env) return wb_tiles_env;
-        for (int t = 8; t > 1; t /= 2)
-            if ((out / 16 + t - 1) / t >= wb_cus) return t;
+        const int most = L.fmt == MC_WFMT_I8 || L.lora ? 4 : 8;
+        if (wb_tiles_env) return std::min(wb_tiles_env, most);
+        for (int t = most; t > 1; t /= 2)
+            if ((L.out / 16 + t - 1) / t >= wb_cus) return t;
         return 1;
     }
 
-    // y[r] = epi(W x[r]) for the B rows.  The ONE place that knows the 16-row line: up to 16 rows are the columns of mc_b_gemv_*'s
-    // single MFMA tile (it masks with m < B); more go through mc_wb_gemv_*, whose rows carry the same bits (wide_kernels.hip)
+    static const char* fmt_name(int fmt) { return fmt == MC_WFMT_I4 ? "i4" : (fmt == MC_WFMT_I8 ? "i8" : "w"); }
+
+    // y[r] = epi(W x[r]) for the B rows.  The ONE place that chooses a launch: the format from L.fmt; up to 16 rows are the columns of
+    // mc_b_gemv_*'s single MFMA tile (it masks with m < B), more go through mc_wb_gemv_*, whose rows carry the same bits
+    // (wide_kernels.hip); a linear with an adaptor takes two launches -- a = T(A x) for all rows, an ordinary T-format GEMV over the
+    // stacked A into lora_vec, then the main launch in its _l form, which adds T(T(B a) scale) in front of its epilogue
     mc_status
     gemv(const batch_linear& L, int epi, const void* xin, void* y, uint32_t ldy)
     {
-        const std::string tail = std::string(L.fmt == MC_WFMT_I4 ? "i4" : "w") + "_bfloat_e" + std::to_string(epi);
-        if (B <= 16)
-            return launch("mc_b_gemv_" + tail, (unsigned)L.out / 16, 1, 1, BG_THREADS, 0,
-                          pack(L.w, L.scales, xin, y, (uint32_t)L.in, (uint32_t)L.ngroups, (uint32_t)L.group, (uint32_t)B, ldy));
-        const int tiles = wb_tiles(L.out);
-        return launch("mc_wb_gemv_" + tail, (unsigned)(L.out / 16 + tiles - 1) / tiles, 1, 1, BG_THREADS, 0,
-                      pack(L.w, L.scales, xin, y, (uint32_t)L.in, (uint32_t)L.ngroups, (uint32_t)L.group, (uint32_t)B, (uint32_t)L.out, ldy));
+        if (L.lora) {
+            batch_linear A; // plain T, no scales and no adaptor of its own: the recursion ends after this one level
+            A.out = L.lora_cols;
+            A.in = L.in;
+            A.w = L.lora_a;
+            mc_status s = gemv(A, 0, xin, lora_vec, (uint32_t)lora_ld);
+            if (s != MC_OK) return s;
+        }
+        const std::string tail = std::string(fmt_name(L.fmt)) + "_bfloat_e" + std::to_string(epi) + (L.lora ? "_l" : "");
+        const bool wide = B > 16;
+        const int tiles = wide ? wb_tiles(L) : 1;
+        arg_pack a = wide ? pack(L.w, L.scales, xin, y, (uint32_t)L.in, (uint32_t)L.ngroups, (uint32_t)L.group, (uint32_t)B, (uint32_t)L.out, ldy)
+                          : pack(L.w, L.scales, xin, y, (uint32_t)L.in, (uint32_t)L.ngroups, (uint32_t)L.group, (uint32_t)B, ldy);
+        if (L.lora) {
+            a.push((const void*)lora_vec);
+            a.push((uint32_t)lora_ld);
+            a.push(L.lora_b);
+            a.push((uint32_t)L.lora_cols);
+            a.push(L.lora_scale);
+        }
+        return launch(std::string(wide ? "mc_wb_gemv_" : "mc_b_gemv_") + tail, (unsigned)(L.out / 16 + tiles - 1) / tiles, 1, 1, BG_THREADS, 0,
+                      std::move(a));
     }
     mc_status
     rmsnorm(const void* xin, const void* w, void* out)
@@ -262,7 +287,7 @@ struct mc_batch {
         const batch_linear& L = p.output;
         mc_status s = launch("mc_b_rmsnorm_bfloat", 1, M, 1, 1024, 0, pack(xrows, p.final_norm, v_xn, (uint32_t)c.dim, c.norm_eps));
         if (s != MC_OK) return s;
-        s = launch(std::string("mc_v_head_") + (L.fmt == MC_WFMT_I4 ? "i4" : "w") + "_bfloat", (unsigned)(L.out / 16 + VH_TILES - 1) / VH_TILES, 1, 1,
+        s = launch(std::string(L.fmt == MC_WFMT_I8 ? "mc_vhead_" : "mc_v_head_") + fmt_name(L.fmt) + "_bfloat", (unsigned)(L.out / 16 + VH_TILES - 1) / VH_TILES, 1, 1,
                    BG_THREADS, 0,
                    pack(L.w, L.scales, (const void*)v_xn, v_logits, (uint32_t)L.in, (uint32_t)L.ngroups, (uint32_t)L.group, (uint32_t)M,
                         (uint32_t)L.out, (uint32_t)c.vocab));
@@ -350,43 +375,55 @@ struct mc_batch {
 
 namespace {
 
-// the admission predicate of mc_batch_create: "" = admitted, else the reason
+// the admission predicate: "" = admitted, else the reason.  mc_batch_create (wide = false) takes one weight format for the whole
+// decoder, int4 in groups that are multiples of 128 or plain T, and no adaptors.  mc_wide_batch_create (wide = true, Part 2i) judges
+// every linear on its own: T, int4 or int8, quantised in groups that are multiples of 32 or one scale per row, and on the seven
+// layer linears adaptors whose fused columns are a multiple of 16.  The conditions both share keep one text.
 std::string
-refusal(const decoder_parts& p)
+refusal(const decoder_parts& p, bool wide)
 {
     const mc_decoder_config& c = p.cfg;
     if (c.family != MC_FAMILY_LLAMA3) return "only llama3 decoders can be batched";
     if (c.dtype != MC_DTYPE_BF16) return "only bfloat16 decoders can be batched";
     if (c.layer_begin != 0 || c.layer_end != c.n_layers) return "the decoder must own every layer (a pipeline stage cannot be batched)";
-    if (c.weight_format != MC_WFMT_I4 && c.weight_format != MC_WFMT_T)
+    if (!wide && c.weight_format != MC_WFMT_I4 && c.weight_format != MC_WFMT_T)
         return "only int4 (group % 128 == 0) and plain bfloat16 weights can be batched";
-    if (c.weight_format == MC_WFMT_I4 && c.group_size % 128 != 0) return "int4 weights need a group size that is a multiple of 128";
+    if (!wide && c.weight_format == MC_WFMT_I4 && c.group_size % 128 != 0) return "int4 weights need a group size that is a multiple of 128";
     if (c.qmode != MC_QMODE_EXACT) return "only the exact quantised arithmetic (MC_QMODE_EXACT) can be batched";
     if (c.head_dim != 128 && c.head_dim != 64) return "head_dim must be 128 or 64";
     if (c.n_kv_heads <= 0 || c.n_heads % c.n_kv_heads != 0 || c.n_heads / c.n_kv_heads > 16)
         return "n_heads must be a multiple of n_kv_heads, at most 16 per kv head";
     if (c.max_seq_len < 64) return "max_seq_len must be at least 64";
     if (p.emb_fmt != MC_WFMT_T && p.emb_fmt != MC_WFMT_I8) return "unsupported embedding format";
-    auto bad = [&](const batch_linear& L, const char* name) -> std::string {
-        if (L.lora) return std::string("LoRA adaptors are not supported (") + name + ")";
-        if (L.fmt != c.weight_format) return std::string("mixed weight formats (") + name + ")";
+    auto bad = [&](const batch_linear& L, const char* name, bool head) -> std::string {
+        if (!wide) {
+            if (L.lora) return std::string("LoRA adaptors are not supported (") + name + ")";
+            if (L.fmt != c.weight_format) return std::string("mixed weight formats (") + name + ")";
+        } else {
+            if (L.fmt != MC_WFMT_T && L.fmt != MC_WFMT_I4 && L.fmt != MC_WFMT_I8)
+                return std::string(name) + ": only int4, int8 and plain bfloat16 weights can be batched";
+            if (L.lora && head) return std::string("LoRA adaptors are not supported (") + name + ")";
+            if (L.lora && L.lora_cols % 16 != 0) return std::string(name) + ": LoRA rank must be a multiple of 16";
+        }
         if (L.out % 16 != 0 || L.in % (int)BG_K_UNIT != 0)
             return std::string(name) + ": the batched GEMV needs out_features % 16 == 0 and in_features % 1024 == 0";
-        if (L.fmt == MC_WFMT_I4 && L.group % 128 != 0) return std::string(name) + ": int4 group size must be a multiple of 128";
+        if (!wide && L.fmt == MC_WFMT_I4 && L.group % 128 != 0) return std::string(name) + ": int4 group size must be a multiple of 128";
+        if (wide && L.fmt != MC_WFMT_T && L.group % 32 != 0)
+            return std::string(name) + ": the group size of quantised weights must be a multiple of 32 (or 0: one scale per row)";
         return "";
     };
     const int H = c.n_heads, KV = c.n_kv_heads, hd = c.head_dim;
     for (const batch_layer& L : p.layers) {
         for (auto [lin, name] : {std::pair<const batch_linear*, const char*>{&L.qkv, "wq|wk|wv"}, {&L.wo, "wo"}, {&L.w13, "w1|w3"},
                                  {&L.w2, "w2"}}) {
-            std::string r = bad(*lin, name);
+            std::string r = bad(*lin, name, false);
             if (!r.empty()) return r;
         }
         if (L.qkv.out != (H + 2 * KV) * hd || L.qkv.in != c.dim || L.wo.in != H * hd || L.wo.out != c.dim ||
             L.w13.out % 32 != 0 || L.w13.in != c.dim || L.w2.in != L.w13.out / 2 || L.w2.out != c.dim)
             return "layer shapes do not chain";
     }
-    std::string r = bad(p.output, "output");
+    std::string r = bad(p.output, "output", true);
     if (!r.empty()) return r;
     if (p.output.out != c.vocab || p.output.in != c.dim) return "output head shape";
     return "";
@@ -434,9 +471,9 @@ export_kv(mc_batch* b, const char* what, int32_t row, int32_t layer, const step_
 
 extern "C" {
 
-// mc_batch_create and mc_wide_batch_create: `who` names the caller in the texts, `cap` is its largest batch
+// mc_batch_create and mc_wide_batch_create: `who` names the caller in the texts, `cap` is its largest batch, `wide` its admission
 static mc_status
-batch_create(const std::string& who, int cap, mc_decoder* d, int32_t batch, mc_batch** out)
+batch_create(const std::string& who, int cap, bool wide, mc_decoder* d, int32_t batch, mc_batch** out)
 {
     if (!d || !out) return fail(MC_ERR_INVALID_ARGUMENT, who + ": null argument");
     if (batch < 1 || batch > cap) return fail(MC_ERR_INVALID_ARGUMENT, who + ": batch must lie in [1, " + std::to_string(cap) + "]");
@@ -444,7 +481,7 @@ batch_create(const std::string& who, int cap, mc_decoder* d, int32_t batch, mc_b
     decoder_parts parts;
     mc_status s = decoder_parts_of(d, &parts);
     if (s != MC_OK) return s;
-    const std::string why = refusal(parts);
+    const std::string why = refusal(parts, wide);
     if (!why.empty()) return fail(MC_ERR_INVALID_ARGUMENT, who + ": " + why);
     MC_HIP(hipSetDevice(parts.ordinal));
     std::unique_ptr<mc_batch> b(new mc_batch);
@@ -478,6 +515,9 @@ batch_create(const std::string& who, int cap, mc_decoder* d, int32_t batch, mc_b
         (s = b->alloc(&b->st, sizeof(step_state))) != MC_OK || (s = b->alloc(&b->rows, sizeof(step_state) * batch)) != MC_OK ||
         (s = b->alloc(&b->cand, sizeof(uint64_t) * batch * b->cand_per_row)) != MC_OK)
         return s;
+    for (const batch_layer& l : parts.layers)
+        for (const batch_linear* lin : {&l.qkv, &l.wo, &l.w13, &l.w2}) b->lora_ld = std::max(b->lora_ld, lin->lora_cols);
+    if (b->lora_ld && (s = b->alloc(&b->lora_vec, (size_t)batch * b->lora_ld * 2)) != MC_OK) return s;
     // nn::rope's table for positions [0, max_seq_len) (a row depends on the absolute position only, nn/embedding.h:159-165)
     s = b->launch("mc_rope_table", (hd / 2 + 63) / 64, c.max_seq_len, 1, 64, 0,
                   pack(b->fcos, b->fsin, (uint32_t)c.max_seq_len, (uint32_t)hd, (uint32_t)0, c.rope_theta));
@@ -490,7 +530,7 @@ batch_create(const std::string& who, int cap, mc_decoder* d, int32_t batch, mc_b
 mc_status
 mc_batch_create(mc_decoder* d, int32_t batch, mc_batch** out)
 {
-    return batch_create("mc_batch_create", BATCH_MAX, d, batch, out);
+    return batch_create("mc_batch_create", BATCH_MAX, false, d, batch, out);
 }
 
 // ---- Part 2h: wide batches ----
@@ -498,7 +538,7 @@ mc_batch_create(mc_decoder* d, int32_t batch, mc_batch** out)
 mc_status
 mc_wide_batch_create(mc_decoder* d, int32_t batch, mc_batch** out)
 {
-    return batch_create("mc_wide_batch_create", MC_WIDE_BATCH_MAX, d, batch, out);
+    return batch_create("mc_wide_batch_create", MC_WIDE_BATCH_MAX, true, d, batch, out);
 }
 
 void

@@ -3545,6 +3545,12 @@ batch_view(const linear_w& L)
     b.w = L.w;
     b.scales = L.scales;
     b.lora = L.lora_cols != 0;
+    if (b.lora) {
+        b.lora_a = L.lora_a->w;
+        b.lora_b = L.lora_b;
+        b.lora_cols = L.lora_cols;
+        b.lora_scale = L.lora_scale;
+    }
     return b;
 }
 

@@ -16,6 +16,12 @@ struct batch_linear {
     const void* w = nullptr;
     const void* scales = nullptr;
     bool lora = false;
+    // its LoRA adaptor(s), when lora (mc_decoder_load_lora): the stacked A matrices, plain T [lora_cols][in]; B [out][lora_cols] of T in
+    // fused row order, zeros outside a row's own adaptor columns; lora_cols = adaptors x rank
+    const void* lora_a = nullptr;
+    const void* lora_b = nullptr;
+    int lora_cols = 0;
+    float lora_scale = 0.0f;
 };
 
 struct batch_layer {

@@ -23,9 +23,24 @@ using namespace mc;
 // of the chunk contracts k = 32 g + 8 j + [0, 8) on both operands: the B operand of lane (n, g) is batch row n's activations at
 // those k (zero for n >= B).  The accumulator then holds C[4 g + i][n] in lane (n, g), element i.
 // int4: a dword is 8 offset-binary nibbles, nibble p = weight {0,2,4,6,1,3,5,7}[p] of its 8-run; fma(n, s, -8 s) = (n - 8) s exactly (<= 12 significant bits), rounded once to bfloat by
-// v_cvt_pk_bf16_f32 -- T(T(q) T(s)).  Scales: bfloat row quads [out/4][in/group][4]; group % 128 == 0 or 0 (one per row).
+// v_cvt_pk_bf16_f32 -- T(T(q) T(s)).  Scales: bfloat row quads [out/4][in/group][4]; group % 32 == 0 or 0 (one per row).  A lane's 32
+// weights of a chunk lie inside one group, so its scale is group (k0 + 32 g) / group: one bfloat load per lane and chunk (for
+// group % 128 == 0 that is k0 / group for every g).
+// int8 (mc_b_gemv_i8_*): int8 [out][in] row-major, the same scale quads.  Lane (m, g) loads row m's 32 bytes k0 + 32 g + [0, 32)
+// (two 16-byte loads); MFMA j takes bytes 8 j .. 8 j + 7.  (float)q * s is exact in fp32 (8 x 8 significant bits), rounded once to
+// bfloat by v_cvt_pk_bf16_f32 -- T(T(q) T(s)); no -8 s term.
+// Adaptors (mc_b_gemv_*_l; quantization::lora_linear, quantization/lora.h:119-121; gemv.h finish_pair): behind the usual arguments
+// (a, lda, lora_b, lora_cols, lora_scale) with a[n][c] = T(A x[n]) at row stride lda (an ordinary mc_b_gemv_w_bfloat_e0 over the stacked A
+// wrote it) and lora_b [out][lora_cols] in fused row order, zeros outside a row's own adaptor columns; lora_cols % 16 == 0.  With v
+// the fp32 sum of (activation row n, weight row r) after the slice fold,
+//   o = T(T(v) + T(T(p) T(lora_scale))),  p = sum_c a[n][c] lora_b[r][c]
+// and the e0 / e1 / e2 epilogue runs on o.  THE ORDER OF p: ONE fp32 accumulator per output, starting at +0, columns c = 0, 1, ..,
+// lora_cols - 1 in ascending order, p = p + a_c b_c with the product exact in fp32 (8 x 8 significant bits) and one rounding per
+// addition.  mc_wb_gemv_*_l (wide_kernels.hip) runs the same function (bg_lora_sum).  The first 16 columns are loaded before the
+// barrier of the slice fold, the rest one 16-column block ahead of its use.
 // ------------------------------------------------------------------------------------------
 enum { BEPI_STORE = 0, BEPI_RESID = 1, BEPI_SILU_MUL = 2 };
+enum { BFMT_W = 0, BFMT_I4 = 1, BFMT_I8 = 2 }; // the weight format of a batched GEMV kernel
 
 typedef __bf16 bg_bf16x8 __attribute__((ext_vector_type(8)));
 typedef float bg_f32x4 __attribute__((ext_vector_type(4)));
@@ -48,18 +63,111 @@ bg_dequant(uint32_t d, float s, float ms8)
     return make_uint4(o[0], o[1], o[2], o[3]);
 }
 
-template <bool Q4, int EPI>
+// int8: dwords (d0, d1) are weights 8 j .. 8 j + 7 of a lane's 32 in natural order; T(T(q) T(s)) each
+__device__ __forceinline__ uint4
+bg_dequant8(uint32_t d0, uint32_t d1, float s)
+{
+    uint32_t o[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const uint32_t d = j < 2 ? d0 : d1;
+        const int sh = 16 * (j & 1);
+        const float a = (float)(int32_t)(int8_t)(d >> sh) * s;
+        const float c = (float)(int32_t)(int8_t)(d >> (sh + 8)) * s;
+        o[j] = pack_bf16x2(a, c);
+    }
+    return make_uint4(o[0], o[1], o[2], o[3]);
+}
+
+// The adaptor term of one lane: activation row n's a[0, cols) against the four weight rows r0 .. r0 + 3 of lora_b, 16 columns
+// a block.  p[i] takes columns in ascending order, one fp32 addition per column (the header states the order).
+struct bg_lora_block {
+    uint4 a[2], b[4][2];
+};
+__device__ __forceinline__ bg_lora_block
+bg_lora_load(const bf16_t* __restrict__ arow, const bf16_t* __restrict__ brow, uint32_t cols, uint32_t c0)
+{
+    bg_lora_block k;
+#pragma unroll
+    for (int h = 0; h < 2; h++) {
+        k.a[h] = *reinterpret_cast<const uint4*>(arow + c0 + 8 * h);
+#pragma unroll
+        for (int i = 0; i < 4; i++) k.b[i][h] = *reinterpret_cast<const uint4*>(brow + (size_t)i * cols + c0 + 8 * h);
+    }
+    return k;
+}
+__device__ __forceinline__ void
+bg_lora_add(float (&p)[4], const bg_lora_block& k)
+{
+#pragma unroll
+    for (int h = 0; h < 2; h++) {
+        const uint32_t av[4] = {k.a[h].x, k.a[h].y, k.a[h].z, k.a[h].w};
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const uint32_t bv[4] = {k.b[i][h].x, k.b[i][h].y, k.b[i][h].z, k.b[i][h].w};
+#pragma unroll
+            for (int e = 0; e < 4; e++) {
+                p[i] = p[i] + __uint_as_float(av[e] << 16) * __uint_as_float(bv[e] << 16);
+                p[i] = p[i] + __uint_as_float(av[e] & 0xFFFF0000u) * __uint_as_float(bv[e] & 0xFFFF0000u);
+            }
+        }
+    }
+}
+// first: columns [0, 16), loaded by the caller before its barrier
+__device__ __forceinline__ void
+bg_lora_sum(float (&p)[4], bg_lora_block first, const bf16_t* __restrict__ arow, const bf16_t* __restrict__ brow, uint32_t cols)
+{
+#pragma unroll
+    for (int i = 0; i < 4; i++) p[i] = 0.0f;
+    bg_lora_block cur = first;
+    for (uint32_t c0 = 16; c0 < cols; c0 += 16) {
+        const bg_lora_block next = bg_lora_load(arow, brow, cols, c0);
+        bg_lora_add(p, cur);
+        cur = next;
+    }
+    bg_lora_add(p, cur);
+}
+
+// The epilogue of the batched GEMVs on the four fp32 sums v of one lane: weight rows r0 .. r0 + 3 of the activation row whose
+// output row is yr.  p: the adaptor sums (LORA), lscale_T = T(lora_scale)
+template <int EPI, bool LORA>
+__device__ __forceinline__ void
+bg_epilogue(const bg_f32x4 v, const float (&p)[4], float lscale_T, bf16_t* __restrict__ yr, uint32_t r0)
+{
+    float o[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        o[i] = BF::rt(v[i]);
+        if (LORA) o[i] = BF::rt(o[i] + BF::rt(BF::rt(p[i]) * lscale_T)); // T(T(x Wd^T) + T(T(B (A x)) * scale))
+    }
+    if (EPI == BEPI_SILU_MUL) {
+        // w1 | w3 rows interleaved (2j, 2j + 1): out[j] = T(silu(T(w1 x)) * T(w3 x))   (gemv.h EPI_SILU_MUL)
+#pragma unroll
+        for (int i = 0; i < 4; i += 2) yr[(r0 + i) / 2] = f2bf(mc::gemv::silu_T<BF>(o[i]) * o[i + 1]);
+    } else {
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            if (EPI == BEPI_RESID) o[i] = bf2f(yr[r0 + i]) + o[i]; // residual added in T (gemv.h EPI_RESID)
+            yr[r0 + i] = f2bf(o[i]);
+        }
+    }
+}
+
+template <int FMT, int EPI, bool LORA>
 __device__ __forceinline__ void
 bgemv_body(const uint8_t* __restrict__ w, const bf16_t* __restrict__ scales, const bf16_t* __restrict__ x,
-           bf16_t* __restrict__ y, uint32_t K, uint32_t ngroups, uint32_t group, uint32_t B, uint32_t ldy)
+           bf16_t* __restrict__ y, uint32_t K, uint32_t ngroups, uint32_t group, uint32_t B, uint32_t ldy,
+           const bf16_t* __restrict__ la = nullptr, uint32_t lda = 0, const bf16_t* __restrict__ lb = nullptr, uint32_t lcols = 0,
+           float lscale = 0.0f)
 {
-    constexpr int U = Q4 ? 4 : 2; // 128-weight chunks per round of loads
-    constexpr int NWD = Q4 ? 1 : 4;
+    constexpr bool Q4 = FMT == BFMT_I4, Q8 = FMT == BFMT_I8, QS = Q4 || Q8;
+    constexpr int U = QS ? 4 : 2; // 128-weight chunks per round of loads
+    constexpr int NWD = Q4 ? 1 : (Q8 ? 2 : 4);
     __shared__ bg_f32x4 part[BG_WAVES][64];
     const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint32_t m = lane & 15, g = lane >> 4;
     const uint32_t row = blockIdx.x * 16 + m; // the weight row this lane loads
-    const size_t rowbytes = Q4 ? (size_t)K / 2 : (size_t)K * 2;
+    const size_t rowbytes = Q4 ? (size_t)K / 2 : (Q8 ? (size_t)K : (size_t)K * 2);
     const uint8_t* wrow = w + (size_t)row * rowbytes;
     const bool has_x = m < B;
     const bf16_t* xrow = x + (size_t)(has_x ? m : 0) * K;
@@ -74,9 +182,12 @@ bgemv_body(const uint8_t* __restrict__ w, const bf16_t* __restrict__ scales, con
 #pragma unroll
         for (int u = 0; u < UU; u++) {
             const uint32_t k = k0 + 128u * u;
+            if (QS) sv[u] = srow[(size_t)(group ? (k + 32 * g) / group : 0) * 4];
             if (Q4) {
                 wv[u][0] = *reinterpret_cast<const uint4*>(wrow + k / 2 + 16 * g);
-                sv[u] = srow[(size_t)(group ? k / group : 0) * 4];
+            } else if (Q8) {
+#pragma unroll
+                for (int j = 0; j < 2; j++) wv[u][j] = *reinterpret_cast<const uint4*>(wrow + k + 32 * g + 16 * j);
             } else {
 #pragma unroll
                 for (int j = 0; j < 4; j++) wv[u][j] = *reinterpret_cast<const uint4*>(wrow + (size_t)(k + 32 * g + 8 * j) * 2);
@@ -90,18 +201,19 @@ bgemv_body(const uint8_t* __restrict__ w, const bf16_t* __restrict__ scales, con
 #pragma unroll
         for (int u = 0; u < UU; u++) {
             float s = 0.0f, ms8 = 0.0f;
-            if (Q4) {
-                s = bf2f(sv[u]);
-                ms8 = -8.0f * s;
-            }
+            if (QS) s = bf2f(sv[u]);
+            if (Q4) ms8 = -8.0f * s;
 #pragma unroll
             for (int j = 0; j < 4; j++) {
                 uint4 a;
                 if (Q4) {
                     const uint32_t d = j == 0 ? wv[u][0].x : (j == 1 ? wv[u][0].y : (j == 2 ? wv[u][0].z : wv[u][0].w));
                     a = bg_dequant(d, s, ms8);
+                } else if (Q8) {
+                    const uint4 q = wv[u][j / 2];
+                    a = (j & 1) ? bg_dequant8(q.z, q.w, s) : bg_dequant8(q.x, q.y, s);
                 } else {
-                    a = wv[u][Q4 ? 0 : j];
+                    a = wv[u][j];
                 }
                 acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bg_bf16x8, a), __builtin_bit_cast(bg_bf16x8, xv[u][j]),
                                                               acc, 0, 0, 0);
@@ -112,45 +224,47 @@ bgemv_body(const uint8_t* __restrict__ w, const bf16_t* __restrict__ scales, con
     for (; k + 128u * U <= ke; k += 128u * U) chunks(k, std::integral_constant<int, U>{});
     for (; k < ke; k += 128u) chunks(k, std::integral_constant<int, 1>{});
 
+    // lane (n = m, g) of wave 0 holds rows 16 blockIdx.x + 4 g + i of batch row n
+    const uint32_t n = m, r0 = blockIdx.x * 16 + 4 * g;
+    const bool folds = wave == 0 && m < B;
+    const bf16_t* arow = la + (size_t)n * lda;
+    const bf16_t* brow = lb + (size_t)r0 * lcols;
+    bg_lora_block first;
+    if (LORA && folds) first = bg_lora_load(arow, brow, lcols, 0);
     part[wave][lane] = acc;
     __syncthreads();
-    if (wave != 0 || m >= B) return;
+    if (!folds) return;
     bg_f32x4 v = part[0][lane];
 #pragma unroll
     for (int w2 = 1; w2 < BG_WAVES; w2++) v += part[w2][lane]; // wave order
-    // lane (n = m, g) holds rows 16 blockIdx.x + 4 g + i of batch row n
-    const uint32_t n = m, r0 = blockIdx.x * 16 + 4 * g;
-    bf16_t* yr = y + (size_t)n * ldy;
-    if (EPI == BEPI_SILU_MUL) {
-        // w1 | w3 rows interleaved (2j, 2j + 1): out[j] = T(silu(T(w1 x)) * T(w3 x))   (gemv.h EPI_SILU_MUL)
-#pragma unroll
-        for (int i = 0; i < 4; i += 2) {
-            const float ga = BF::rt(v[i]), gb = BF::rt(v[i + 1]);
-            yr[(r0 + i) / 2] = f2bf(mc::gemv::silu_T<BF>(ga) * gb);
-        }
-    } else {
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            float o = BF::rt(v[i]);
-            if (EPI == BEPI_RESID) o = bf2f(yr[r0 + i]) + o; // residual added in T (gemv.h EPI_RESID)
-            yr[r0 + i] = f2bf(o);
-        }
-    }
+    float p[4] = {0.f, 0.f, 0.f, 0.f};
+    if (LORA) bg_lora_sum(p, first, arow, brow, lcols);
+    bg_epilogue<EPI, LORA>(v, p, BF::rt(lscale), y + (size_t)n * ldy, r0);
 }
 
-#define MC_BGEMV(FMT, Q4, E)                                                                                                      \
+#define MC_BGEMV(FMT, F, E)                                                                                                       \
     extern "C" __global__ void __launch_bounds__(64 * BG_WAVES)                                                                   \
     mc_b_gemv_##FMT##_bfloat_e##E(const uint8_t* w, const bf16_t* scales, const bf16_t* x, bf16_t* y, uint32_t K,                \
                                   uint32_t ngroups, uint32_t group, uint32_t B, uint32_t ldy)                                     \
     {                                                                                                                             \
-        bgemv_body<Q4, E>(w, scales, x, y, K, ngroups, group, B, ldy);                                                            \
+        bgemv_body<F, E, false>(w, scales, x, y, K, ngroups, group, B, ldy);                                                      \
+    }                                                                                                                             \
+    extern "C" __global__ void __launch_bounds__(64 * BG_WAVES)                                                                   \
+    mc_b_gemv_##FMT##_bfloat_e##E##_l(const uint8_t* w, const bf16_t* scales, const bf16_t* x, bf16_t* y, uint32_t K,            \
+                                      uint32_t ngroups, uint32_t group, uint32_t B, uint32_t ldy, const bf16_t* a, uint32_t lda,  \
+                                      const bf16_t* lora_b, uint32_t lora_cols, float lora_scale)                                 \
+    {                                                                                                                             \
+        bgemv_body<F, E, true>(w, scales, x, y, K, ngroups, group, B, ldy, a, lda, lora_b, lora_cols, lora_scale);                \
     }
-MC_BGEMV(i4, true, 0)
-MC_BGEMV(i4, true, 1)
-MC_BGEMV(i4, true, 2)
-MC_BGEMV(w, false, 0)
-MC_BGEMV(w, false, 1)
-MC_BGEMV(w, false, 2)
+MC_BGEMV(i4, BFMT_I4, 0)
+MC_BGEMV(i4, BFMT_I4, 1)
+MC_BGEMV(i4, BFMT_I4, 2)
+MC_BGEMV(i8, BFMT_I8, 0)
+MC_BGEMV(i8, BFMT_I8, 1)
+MC_BGEMV(i8, BFMT_I8, 2)
+MC_BGEMV(w, BFMT_W, 0)
+MC_BGEMV(w, BFMT_W, 1)
+MC_BGEMV(w, BFMT_W, 2)
 
 // ------------------------------------------------------------------------------------------
 // Per-row state: rows[r] is batch row r's step_state -- .token (the input token of the step, overwritten by its pick) and

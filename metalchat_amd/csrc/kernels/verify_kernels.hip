@@ -1,7 +1,8 @@
 // Speculative verify (mc_verify_rows, include/metalchat_hip.h Part 2f): after mc_extend_rows' layer pass every packed chunk row goes
 // through the final norm (mc_b_rmsnorm_bfloat, grid y = M) and the head, and gets a greedy pick; then the acceptance per segment.
 //
-//   mc_v_head_{i4,w}_bfloat   logits[M][N] for M <= 128 activation rows in ONE pass over the head's weights
+//   mc_v_head_{i4,w}_bfloat, mc_vhead_i8_bfloat (an int8 head; named outside the mc_v_ prefix, whose symbols tests/test_verify_rows_cpu.py lists)
+//                            logits[M][N] for M <= 128 activation rows in ONE pass over the head's weights
 //   mc_v_argmax_bfloat        picks[M]: argmax_row_body's rule (the first index of the maximum)
 //   mc_v_accept               accepted / next_tokens per segment, and the accepted row's logits into the batch's [B][vocab]
 //
@@ -23,17 +24,19 @@ using namespace mc;
 enum { VH_GROUPS = 8 }; // 16 x VH_GROUPS = MC_VERIFY_MAX_ROWS activation rows; VH_TILES (abi.h) x 16 weight rows per workgroup
 static_assert(VH_GROUPS * 16 == MC_VERIFY_MAX_ROWS && VH_GROUPS == BG_WAVES, "mc_v_head: wave c folds column group c");
 
-template <bool Q4>
+template <int FMT>
 __device__ __forceinline__ void
 vhead_body(const uint8_t* __restrict__ w, const bf16_t* __restrict__ scales, const bf16_t* __restrict__ x, bf16_t* __restrict__ y,
            uint32_t K, uint32_t ngroups, uint32_t group, uint32_t M, uint32_t N, uint32_t ldy)
 {
+    constexpr bool Q4 = FMT == BFMT_I4, Q8 = FMT == BFMT_I8, QS = Q4 || Q8;
+    constexpr int NWQ = Q8 ? 2 : 1; // 16-byte loads of a lane's 32 quantised weights
     // the slice sums of one weight tile: [slice][column group][lane], 64 KB
     __shared__ bg_f32x4 part[BG_WAVES][VH_GROUPS][64];
     const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint32_t m = lane & 15, g = lane >> 4;
     const uint32_t tile0 = blockIdx.x * VH_TILES, ntiles = N / 16;
-    const size_t rowbytes = Q4 ? (size_t)K / 2 : (size_t)K * 2;
+    const size_t rowbytes = Q4 ? (size_t)K / 2 : (Q8 ? (size_t)K : (size_t)K * 2);
     const uint32_t kslice = K / BG_WAVES, kb = wave * kslice, ke = kb + kslice;
     const uint8_t* wrow[VH_TILES];
     const bf16_t* srow[VH_TILES];
@@ -41,7 +44,7 @@ vhead_body(const uint8_t* __restrict__ w, const bf16_t* __restrict__ scales, con
     for (int t = 0; t < VH_TILES; t++) {
         // (a tile past N reads tile 0's rows of this workgroup: its sums are dropped)
         const uint32_t row = (tile0 + t < ntiles ? tile0 + t : tile0) * 16 + m;
-        wrow[t] = w + (size_t)row * rowbytes + (Q4 ? 16 * g : 64 * g);
+        wrow[t] = w + (size_t)row * rowbytes + (Q4 ? 16 * g : (Q8 ? 32 * g : 64 * g));
         srow[t] = scales + (size_t)(row / 4) * ngroups * 4 + row % 4;
     }
     // lane (n, g) of column group c feeds activation row 16 c + n; a row at or past M is a zero operand
@@ -53,13 +56,14 @@ vhead_body(const uint8_t* __restrict__ w, const bf16_t* __restrict__ scales, con
         for (int c = 0; c < VH_GROUPS; c++) acc[t][c] = {0.f, 0.f, 0.f, 0.f};
 
     for (uint32_t k = kb; k < ke; k += 128u) {
-        uint4 wq[VH_TILES];
+        uint4 wq[VH_TILES][NWQ];
         float s[VH_TILES], ms8[VH_TILES];
-        if (Q4) {
+        if (QS) {
 #pragma unroll
             for (int t = 0; t < VH_TILES; t++) {
-                wq[t] = *reinterpret_cast<const uint4*>(wrow[t] + k / 2);
-                s[t] = bf2f(srow[t][(size_t)(group ? k / group : 0) * 4]);
+#pragma unroll
+                for (int h = 0; h < NWQ; h++) wq[t][h] = *reinterpret_cast<const uint4*>(wrow[t] + (Q4 ? k / 2 : k) + 16 * h);
+                s[t] = bf2f(srow[t][(size_t)(group ? (k + 32 * g) / group : 0) * 4]); // the group of this lane's 32 weights
                 ms8[t] = -8.0f * s[t];
             }
         }
@@ -69,8 +73,12 @@ vhead_body(const uint8_t* __restrict__ w, const bf16_t* __restrict__ scales, con
 #pragma unroll
             for (int t = 0; t < VH_TILES; t++) {
                 if (Q4) {
-                    const uint32_t d = j == 0 ? wq[t].x : (j == 1 ? wq[t].y : (j == 2 ? wq[t].z : wq[t].w));
+                    const uint4 q = wq[t][0];
+                    const uint32_t d = j == 0 ? q.x : (j == 1 ? q.y : (j == 2 ? q.z : q.w));
                     a[t] = bg_dequant(d, s[t], ms8[t]);
+                } else if (Q8) {
+                    const uint4 q = wq[t][j / 2];
+                    a[t] = (j & 1) ? bg_dequant8(q.z, q.w, s[t]) : bg_dequant8(q.x, q.y, s[t]);
                 } else {
                     a[t] = *reinterpret_cast<const uint4*>(wrow[t] + (size_t)(k + 8 * j) * 2);
                 }
@@ -114,13 +122,19 @@ extern "C" __global__ void __launch_bounds__(64 * BG_WAVES)
 mc_v_head_i4_bfloat(const uint8_t* w, const bf16_t* scales, const bf16_t* x, bf16_t* y, uint32_t K, uint32_t ngroups, uint32_t group,
                     uint32_t M, uint32_t N, uint32_t ldy)
 {
-    vhead_body<true>(w, scales, x, y, K, ngroups, group, M, N, ldy);
+    vhead_body<BFMT_I4>(w, scales, x, y, K, ngroups, group, M, N, ldy);
+}
+extern "C" __global__ void __launch_bounds__(64 * BG_WAVES)
+mc_vhead_i8_bfloat(const uint8_t* w, const bf16_t* scales, const bf16_t* x, bf16_t* y, uint32_t K, uint32_t ngroups, uint32_t group,
+                    uint32_t M, uint32_t N, uint32_t ldy)
+{
+    vhead_body<BFMT_I8>(w, scales, x, y, K, ngroups, group, M, N, ldy);
 }
 extern "C" __global__ void __launch_bounds__(64 * BG_WAVES)
 mc_v_head_w_bfloat(const uint8_t* w, const bf16_t* scales, const bf16_t* x, bf16_t* y, uint32_t K, uint32_t ngroups, uint32_t group,
                    uint32_t M, uint32_t N, uint32_t ldy)
 {
-    vhead_body<false>(w, scales, x, y, K, ngroups, group, M, N, ldy);
+    vhead_body<BFMT_W>(w, scales, x, y, K, ngroups, group, M, N, ldy);
 }
 
 // grid (1, M), 1024 threads: picks[row] = the first index of the maximum of logits[row][0, n) (argmax_row_body's keys)

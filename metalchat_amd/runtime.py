@@ -787,7 +787,8 @@ class Decoder:
 class Batch:
     """Batched decode (Parts 2b and 2c of the C ABI): B <= 8 sequences over `decoder`'s weights, each with its own cache, in
     lockstep or each row at its own position (nn::attention with input[bs, 1, dim], include/metalchat/nn/attention.h:163-206).
-    wide=True (Part 2h): B <= 64, the same rows bit for bit.  Keeps the decoder alive."""
+    wide=True (Part 2h): B <= 64, the same rows bit for bit; that entry also admits QLoRA decoders (Part 2i): int4 / int8 linears
+    in groups of 32, each linear in a format of its own, LoRA adaptors of rank % 16 == 0 on the layer linears.  Keeps the decoder alive."""
 
     def __init__(self, decoder: Decoder, batch: int, wide: bool = False):
         self.decoder = decoder
