@@ -372,6 +372,9 @@ mc_status mc_decoder_weight_ptrs(mc_decoder* d, int32_t layer, const char* name,
  * cache and every mc_decoder_* call are untouched.  Launches go to the decoder's stream and its launch log
  * (mc_decoder_launch_log).  A row's results do not depend on the batch size or on the other rows, bit for bit.  The batch
  * must be released before its decoder.
+ * The lockstep calls keep start_pos + n <= max_seq_len whatever mc_rolling_set says (Part 2j: only ragged rows roll; a
+ * caller past the end uses ragged calls with equal positions).  mc_batch_export_kv of a row that has rolled returns that row's
+ * own view, as mc_ragged_export_kv does.
  * ------------------------------------------------------------------------------------------ */
 typedef struct mc_batch mc_batch;
 /* 1 <= batch <= 8 (up to 64: mc_wide_batch_create, Part 2h).  The decoder must be single-stage (layer_begin = 0, layer_end = n_layers), family llama3, dtype bf16,
@@ -412,6 +415,8 @@ mc_status mc_batch_get_logits(mc_batch* b, void* logits_T);
  * Sampling is the decoder's sampler, read at every call; token i of row r uses seed pair (i * B + r) % n_pairs, as a
  * lockstep call does, so a ragged call whose rows all share one position computes the lockstep call's tokens, logits and
  * K/V bit for bit.  Ragged calls do not move the lockstep calls' shared position.
+ * All of this is the default.  Part 2j (mc_rolling_set) lifts "positions[r] < max_seq_len" and the stop at the end of
+ * the cache for a batch that opts in: its rows decode on nn::sink_cache's ring, as the batch-1 decoder does.
  * ------------------------------------------------------------------------------------------ */
 /* one step of every active row at positions[r]; next_tokens[B] (may be null): the picks, -1 for an idle row */
 mc_status mc_ragged_step(mc_batch* b, const int32_t* tokens, const int32_t* positions, int32_t* next_tokens);
@@ -564,6 +569,44 @@ mc_status mc_wide_batch_create(mc_decoder* d, int32_t batch, mc_batch** out);
  * 2b - 2g runs on such a batch with B from 1 to 64.  Not admitted: gemma3, MC_QMODE_FAST, float32, adaptors on the head, ranks
  * that are not multiples of 16.
  * ------------------------------------------------------------------------------------------ */
+
+/* ================================================================================================
+ * Part 2j -- rolling rows: the ragged rows of a batch decode past max_seq_len, opt-in per batch.  nn::sink_cache carries the batch
+ * dimension and rolls for it (nn/cache.h:154-215): once start_pos >= max_seq_len the first pre_len rows stay, the rest rotates left
+ * and the new row takes the last slot.  mc_decoder_* does that on a zero-copy ring; with rolling enabled mc_ragged_step and
+ * mc_ragged_generate do it per row, so a chat that outlives its cache stays in its batch.  With S = max_seq_len, post = S - pre_len:
+ *   positions   an active row may sit at any positions[r] >= 0.  Below S nothing changes.  At p >= S the row is in the state the
+ *               decoder reaches after p - S + 1 single-step rolls from a linear cache: ring_base = (p - S + 1) % post, the new row
+ *               goes to slot pre_len + (post - 1 + ring_base) % post, and S positions are attended.  Rows get past the end by single
+ *               steps only, so the state follows from p and the batch keeps nothing but the lengths.
+ *   stopping    a row stops on its stop ids only, never for the end of its cache.  lengths[r] of mc_ragged_generate and
+ *               mc_ragged_lengths are absolute and may exceed S.
+ *   rope        cos / sin of the absolute position, bit for bit the row mc_rope_table writes for it, made on the device at the
+ *               start of every step (chained steps included: no host round trip).
+ *   rewinds     once a row's length exceeds S its evicted positions are gone: positions[r] must equal the length, or be 0 (a
+ *               restart).  Anything between is refused with MC_ERR_INVALID_ARGUMENT,
+ *                 "...: row r: position p lies below the row's length n and the row has rolled"
+ *               nothing enqueued, by every rows call of Parts 2c - 2g and in either mode.  "past the row's length" stays.
+ *   export      mc_ragged_export_kv (and mc_batch_export_kv for such a row) returns the logical view of min(length, S) positions:
+ *               the sink rows, then the ring unrolled, as mc_decoder_export_kv does; *n_valid = min(length, S).
+ *   the rest    mc_batch_import_kv, mc_batch_fork, and mc_rows_prefill / mc_extend_rows at position 0 make a rolled row linear
+ *               again, as they overwrite any row.  The packed passes and both verify calls keep positions[r] + lens[r] <= S with
+ *               their texts, so they refuse a rolled row: a follow-up turn on a rolled row is fed by ragged steps.  The lockstep
+ *               calls keep their bound in both modes.  mc_batch_fork still refuses a decoder whose ring has turned.
+ * The row contract holds unchanged: a row's tokens, logits and K / V do not depend on B, on its index or on the other rows --
+ * rolled, not rolled or idle -- bit for bit, for B from 1 to 64 and every decoder mc_wide_batch_create admits.  A row that stays
+ * below S computes the same bits with rolling on and off.  Not covered: chunks on rolled rows (the reference's chunk past the end
+ * rotates by its length, which is not what that many steps compute), lockstep rolling, forking a rolled decoder, gemma3.
+ * The calls carry a prefix of their own, mc_rolling_, as every part's do.
+ * ------------------------------------------------------------------------------------------ */
+/* 0 (default): rows stop at the end of their cache and positions[r] < max_seq_len.  1: ragged rows roll.  Any other value is refused.
+ * Switching back to 0 keeps the rows; one whose length exceeds max_seq_len can then only be restarted at 0. */
+mc_status mc_rolling_set(mc_batch* b, int32_t enable);
+int32_t mc_rolling_enabled(const mc_batch* b); /* 0 for a null batch */
+/* copy row src's valid cache -- the min(length, max_seq_len) physical slots of every layer -- and its length onto row dst of the same
+ * batch.  Works on a rolled row, whose ring follows from its length: the one way to branch a chat that has rolled.  Refused: a null
+ * batch, a row out of range, dst == src. */
+mc_status mc_rolling_fork_row(mc_batch* b, int32_t dst, int32_t src);
 
 /* Host-side helpers shared by tests and the synthetic initialiser. */
 /* value in [-7,7] (bits = 4) or [-127,127] (bits = 8), zero mean, of element (row, col) of matrix `matrix_id` */

@@ -14,9 +14,13 @@
 // Part 2c (mc_ragged_*) runs the same sequence with every row at a position of its own: the per-row launches read rows[r]
 // instead of the shared state, one small launch (mc_b_rows_begin) starts each step in place of mc_step_set, and a row whose
 // position is -1, or which stopped on a stop id or at the end of its cache, is idle.
+// Part 2j (mc_rolling_set): the ragged rows of a batch decode past max_seq_len on nn::sink_cache's ring (nn/cache.h:187-204).
+// A row's ring state is a function of its position -- rows get past the end by single steps only -- so the batch keeps its lengths
+// and nothing else: mc_b_rows_begin_rolling derives the state and writes the row's rope row, every other launch is the ragged one.
 #include "decoder_batch.h"
 
 #include <algorithm>
+#include <climits>
 #include <cstring>
 #include <memory>
 
@@ -42,6 +46,8 @@ struct mc_batch {
     void *logits = nullptr;               // [B][vocab]
     float *expv = nullptr, *psum = nullptr; // [B][H][max_seq], [B][H][nsplit]
     float *fcos = nullptr, *fsin = nullptr; // rope table rows [0, max_seq)
+    float *rcos = nullptr, *rsin = nullptr; // [B][hd / 2]: a rolling batch's rope row of each row, written by every step's first launch
+    bool rolling = false;                   // mc_rolling_set
     step_state* st = nullptr;             // the shared position
     step_state* rows = nullptr;           // [B]: token and step_index of each row (ragged calls: the whole state of each row)
     uint64_t* cand = nullptr;             // [B][lists * kpad]
@@ -212,10 +218,16 @@ struct mc_batch {
         const void* emb = q8 ? nullptr : p.emb_table;
         const void* emb_q8 = q8 ? p.emb_table : nullptr;
         mc_status s;
+        const bool roll = ragged && rolling;
         if (ragged) {
-            s = launch("mc_b_rows_begin", 1, 1, 1, 64, 0,
-                       pack(rows, (const int32_t*)stop_dev, (int32_t)stop_host.size(), (int32_t)c.max_seq_len, (int32_t)B,
-                            (int32_t)(advance ? 1 : 0)));
+            if (roll)
+                s = launch("mc_b_rows_begin_rolling", B, 1, 1, 64, 0,
+                           pack(rows, (const int32_t*)stop_dev, (int32_t)stop_host.size(), (int32_t)c.max_seq_len, (int32_t)p.pre_len,
+                                (int32_t)(advance ? 1 : 0), rcos, rsin, (uint32_t)hd, c.rope_theta));
+            else
+                s = launch("mc_b_rows_begin", 1, 1, 1, 64, 0,
+                           pack(rows, (const int32_t*)stop_dev, (int32_t)stop_host.size(), (int32_t)c.max_seq_len, (int32_t)B,
+                                (int32_t)(advance ? 1 : 0)));
             if (s != MC_OK) return s;
             s = launch("mc_b_embed_rows_bfloat", (c.dim + 255) / 256, B, 1, 256, 0, pack(emb, p.emb_scales, emb_q8, x, rows, (uint32_t)c.dim));
         } else {
@@ -233,8 +245,8 @@ struct mc_batch {
             if ((s = rmsnorm(x, L.attention_norm, xn)) != MC_OK) return s;
             if ((s = gemv(L.qkv, 0, xn, qkv, (uint32_t)L.qkv.out)) != MC_OK) return s;
             s = launch("mc_b_rope_kv" + sfx, H + 2 * KV, B, 1, hd / 2, 0,
-                       pack(qkv, q, (void*)kc_of(l, 0), (void*)vt_of(l, 0), fcos, fsin, state, (uint32_t)H, (uint32_t)KV, (uint32_t)hd,
-                            (uint32_t)c.max_seq_len, cstride));
+                       pack(qkv, q, (void*)kc_of(l, 0), (void*)vt_of(l, 0), roll ? rcos : fcos, roll ? rsin : fsin, state, (uint32_t)H,
+                            (uint32_t)KV, (uint32_t)hd, (uint32_t)c.max_seq_len, cstride));
             if (s != MC_OK) return s;
             s = launch("mc_b_attn_scores" + sfx, nsplit, KV, B, 256, 0,
                        pack(q, (void*)kc_of(l, 0), expv, psum, state, (uint32_t)n_rep, (uint32_t)hd, (uint32_t)c.max_seq_len, scale_T,
@@ -335,10 +347,19 @@ struct mc_batch {
         return MC_OK;
     }
 
-    // a ragged call's positions and tokens: -1 = idle, else 0 <= pos <= the row's length and pos < max_seq_len, with a token
-    // of the vocabulary; at least one row active
+    // a row whose length exceeds max_seq_len has rolled: its evicted positions are gone, so it is continued at its length or
+    // restarted at 0 and nothing between ("" = fine, else the refusal behind the row's name)
+    std::string
+    rolled_rewind(int r, int64_t pos) const
+    {
+        if (lengths[r] <= p.cfg.max_seq_len || pos == 0 || pos >= lengths[r]) return "";
+        return "position " + std::to_string(pos) + " lies below the row's length " + std::to_string(lengths[r]) + " and the row has rolled";
+    }
+
+    // a ragged call's positions and tokens: -1 = idle, else 0 <= pos <= the row's length and pos < max_seq_len (a rolling batch:
+    // any pos, as long as the n steps of the call stay inside int32), with a token of the vocabulary; at least one row active
     mc_status
-    check_ragged(const char* what, const int32_t* tokens, const int32_t* positions) const
+    check_ragged(const char* what, const int32_t* tokens, const int32_t* positions, int32_t n) const
     {
         int active = 0;
         for (int r = 0; r < B; r++) {
@@ -346,11 +367,14 @@ struct mc_batch {
             const std::string row = std::string(what) + ": row " + std::to_string(r) + ": ";
             if (pos == -1) continue;
             if (pos < -1) return fail(MC_ERR_INVALID_ARGUMENT, row + "position below -1 (-1 = idle)");
-            if (pos >= p.cfg.max_seq_len)
+            if (!rolling && pos >= p.cfg.max_seq_len)
                 return fail(MC_ERR_INVALID_ARGUMENT, row + "position " + std::to_string(pos) + " must be below max_seq_len (a batch's cache does not roll)");
+            if (rolling && (int64_t)pos + n > INT32_MAX)
+                return fail(MC_ERR_INVALID_ARGUMENT, row + "position " + std::to_string(pos) + " + n leaves the range of positions");
             if (pos > lengths[r])
                 return fail(MC_ERR_INVALID_ARGUMENT, row + "position " + std::to_string(pos) + " is past the row's length " +
                                                          std::to_string(lengths[r]) + " (its cache has no slots written beyond it)");
+            if (const std::string why = rolled_rewind(r, pos); !why.empty()) return fail(MC_ERR_INVALID_ARGUMENT, row + why);
             if (tokens[r] < 0 || tokens[r] >= p.cfg.vocab) return fail(MC_ERR_INVALID_ARGUMENT, row + "token id outside the vocabulary");
             active++;
         }
@@ -467,6 +491,26 @@ export_kv(mc_batch* b, const char* what, int32_t row, int32_t layer, const step_
     return s;
 }
 
+// mc_ragged_export_kv (and mc_batch_export_kv for a row that has rolled): row `row`'s own logical view, min(length, max_seq_len)
+// positions -- the sink rows, then the ring unrolled.  The export kernel reads kv_len and the ring from a state of its own, made
+// from the row's length: the row last wrote position length - 1, which fixes its ring (mc_b_rows_begin_rolling)
+mc_status
+export_row(mc_batch* b, const char* what, int32_t row, int32_t layer, void* keys, void* values, int32_t* n_valid)
+{
+    const int32_t len = b->lengths[row], S = b->p.cfg.max_seq_len, n = std::min(len, S);
+    if (n_valid) *n_valid = n;
+    if (n == 0) return MC_OK;
+    MC_HIP(hipSetDevice(b->p.ordinal));
+    step_state st{};
+    st.kv_len = n;
+    st.ring_base = len > S ? (len - S) % (S - b->p.pre_len) : 0;
+    device_tmp stv;
+    hipError_t e = stv.alloc(sizeof st);
+    if (e == hipSuccess) e = hipMemcpyAsync(stv.ptr, &st, sizeof st, hipMemcpyHostToDevice, b->p.stream);
+    if (e != hipSuccess) return hip_fail(e, what);
+    return export_kv(b, what, row, layer, static_cast<const step_state*>(stv.ptr), n, n, nullptr, keys, values);
+}
+
 } // namespace
 
 extern "C" {
@@ -512,6 +556,8 @@ batch_create(const std::string& who, int cap, bool wide, mc_decoder* d, int32_t 
         (s = b->alloc(&b->psum, sizeof(float) * batch * H * b->nsplit)) != MC_OK ||
         (s = b->alloc(&b->fcos, sizeof(float) * c.max_seq_len * (hd / 2))) != MC_OK ||
         (s = b->alloc(&b->fsin, sizeof(float) * c.max_seq_len * (hd / 2))) != MC_OK ||
+        (s = b->alloc(&b->rcos, sizeof(float) * batch * (hd / 2))) != MC_OK ||
+        (s = b->alloc(&b->rsin, sizeof(float) * batch * (hd / 2))) != MC_OK ||
         (s = b->alloc(&b->st, sizeof(step_state))) != MC_OK || (s = b->alloc(&b->rows, sizeof(step_state) * batch)) != MC_OK ||
         (s = b->alloc(&b->cand, sizeof(uint64_t) * batch * b->cand_per_row)) != MC_OK)
         return s;
@@ -614,6 +660,8 @@ mc_batch_export_kv(mc_batch* b, int32_t row, int32_t layer, void* keys, void* va
 {
     mc_status s = find_row(b, row, layer, "mc_batch_export_kv");
     if (s != MC_OK) return s;
+    // a row that has rolled has no lockstep view: its own (Part 2j)
+    if (b->lengths[row] > b->p.cfg.max_seq_len) return export_row(b, "mc_batch_export_kv", row, layer, keys, values, n_valid);
     MC_HIP(hipSetDevice(b->p.ordinal));
     // kv_len of the batch's shared state: the position of the last lockstep step, fork or import, whichever row that was for
     return export_kv(b, "mc_batch_export_kv", row, layer, b->st, b->p.cfg.max_seq_len, -1, n_valid, keys, values);
@@ -727,6 +775,7 @@ rows_check(const mc_batch* b, const std::string& who, const int32_t* tokens, con
         if ((int64_t)pos + len > c.max_seq_len)
             return fail(MC_ERR_INVALID_ARGUMENT, row + "position + length " + std::to_string((int64_t)pos + len) +
                                                      " exceeds max_seq_len (a batch's cache does not roll)");
+        if (const std::string why = b->rolled_rewind(r, pos); !why.empty()) return fail(MC_ERR_INVALID_ARGUMENT, row + why);
         for (int32_t i = 0; i < len; i++)
             if (tokens[total + i] < 0 || tokens[total + i] >= c.vocab)
                 return fail(MC_ERR_INVALID_ARGUMENT, row + "token id outside the vocabulary");
@@ -981,7 +1030,7 @@ mc_status
 mc_ragged_step(mc_batch* b, const int32_t* tokens, const int32_t* positions, int32_t* next_tokens)
 {
     if (!b || !tokens || !positions) return fail(MC_ERR_INVALID_ARGUMENT, "mc_ragged_step: null argument");
-    mc_status s = b->check_ragged("mc_ragged_step", tokens, positions);
+    mc_status s = b->check_ragged("mc_ragged_step", tokens, positions, 1);
     if (s != MC_OK) return s;
     MC_HIP(hipSetDevice(b->p.ordinal));
     if ((s = b->ensure_tokens(1)) != MC_OK || (s = b->start_ragged(tokens, positions, nullptr, 0, 1)) != MC_OK ||
@@ -1002,7 +1051,7 @@ mc_ragged_generate(mc_batch* b, const int32_t* first_tokens, const int32_t* posi
         return fail(MC_ERR_INVALID_ARGUMENT, "mc_ragged_generate: null argument");
     if (n < 1) return fail(MC_ERR_INVALID_ARGUMENT, "mc_ragged_generate: n must be positive");
     if (n_stop < 0) return fail(MC_ERR_INVALID_ARGUMENT, "mc_ragged_generate: n_stop must not be negative");
-    mc_status s = b->check_ragged("mc_ragged_generate", first_tokens, positions);
+    mc_status s = b->check_ragged("mc_ragged_generate", first_tokens, positions, n);
     if (s != MC_OK) return s;
     MC_HIP(hipSetDevice(b->p.ordinal));
     if ((s = b->ensure_tokens(n)) != MC_OK || (s = b->start_ragged(first_tokens, positions, stop_ids, n_stop, n)) != MC_OK) return s;
@@ -1034,18 +1083,47 @@ mc_ragged_export_kv(mc_batch* b, int32_t row, int32_t layer, void* keys, void* v
 {
     mc_status s = find_row(b, row, layer, "mc_ragged_export_kv");
     if (s != MC_OK) return s;
-    const int32_t n = b->lengths[row];
-    if (n_valid) *n_valid = n;
-    if (n == 0) return MC_OK;
+    return export_row(b, "mc_ragged_export_kv", row, layer, keys, values, n_valid);
+}
+
+// ---- Part 2j: rolling rows ----
+
+mc_status
+mc_rolling_set(mc_batch* b, int32_t enable)
+{
+    if (!b) return fail(MC_ERR_INVALID_ARGUMENT, "mc_rolling_set: null argument");
+    if (enable != 0 && enable != 1) return fail(MC_ERR_INVALID_ARGUMENT, "mc_rolling_set: enable must be 0 or 1");
+    b->rolling = enable == 1;
+    return MC_OK;
+}
+
+int32_t
+mc_rolling_enabled(const mc_batch* b)
+{
+    return b && b->rolling ? 1 : 0;
+}
+
+mc_status
+mc_rolling_fork_row(mc_batch* b, int32_t dst, int32_t src)
+{
+    if (!b) return fail(MC_ERR_INVALID_ARGUMENT, "mc_rolling_fork_row: null argument");
+    if (dst < 0 || dst >= b->B || src < 0 || src >= b->B) return fail(MC_ERR_INVALID_ARGUMENT, "mc_rolling_fork_row: row out of range");
+    if (dst == src) return fail(MC_ERR_INVALID_ARGUMENT, "mc_rolling_fork_row: dst and src are the same row");
+    const mc_decoder_config& c = b->p.cfg;
+    const int KV = c.n_kv_heads, hd = c.head_dim, S = c.max_seq_len;
+    // the physical slots as they lie: a rolled row's ring follows from its length, which the copy takes along
+    const int n = std::min(b->lengths[src], S);
     MC_HIP(hipSetDevice(b->p.ordinal));
-    // the export kernel reads kv_len (and a ring of 0) from a state of its own: row `row`'s length
-    step_state st{};
-    st.kv_len = n;
-    device_tmp stv;
-    hipError_t e = stv.alloc(sizeof st);
-    if (e == hipSuccess) e = hipMemcpyAsync(stv.ptr, &st, sizeof st, hipMemcpyHostToDevice, b->p.stream);
-    if (e != hipSuccess) return hip_fail(e, "mc_ragged_export_kv");
-    return export_kv(b, "mc_ragged_export_kv", row, layer, static_cast<const step_state*>(stv.ptr), n, n, nullptr, keys, values);
+    for (int l = 0; n > 0 && l < (int)b->p.layers.size(); l++) {
+        // K [kv][slot][hd]: n * hd elements per kv head; Vt [kv * hd][slot]: n elements per row
+        MC_HIP(hipMemcpy2DAsync(b->kc_of(l, dst), (size_t)S * hd * 2, b->kc_of(l, src), (size_t)S * hd * 2, (size_t)n * hd * 2, KV,
+                                hipMemcpyDeviceToDevice, b->p.stream));
+        MC_HIP(hipMemcpy2DAsync(b->vt_of(l, dst), (size_t)S * 2, b->vt_of(l, src), (size_t)S * 2, (size_t)n * 2, (size_t)KV * hd,
+                                hipMemcpyDeviceToDevice, b->p.stream));
+    }
+    MC_HIP(hipStreamSynchronize(b->p.stream));
+    b->lengths[dst] = b->lengths[src];
+    return MC_OK;
 }
 
 } // extern "C"

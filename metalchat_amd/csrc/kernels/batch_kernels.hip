@@ -380,6 +380,8 @@ mc_b_sample_bfloat(const uint64_t* cand, sampler_params p, const uint64_t* seeds
 // tokens_out for it.  The launches are thin wrappers over the lockstep kernels' bodies given rows + r for the shared state, so
 // a row at position p computes the bits a lockstep batch computes at p.  The grids are the lockstep grids; an idle row's
 // workgroups exit at once, and scores workgroups past a row's kv_len exit as they always do, so a row costs its own length.
+// A rolling batch (Part 2j) starts its steps with mc_b_rows_begin_rolling instead, which gives a row past the end the ring's
+// write_slot and a rope row of its own; the launches behind it are these.
 // ------------------------------------------------------------------------------------------
 __device__ __forceinline__ bool
 row_idle(const step_state* rows, uint32_t r)
@@ -412,6 +414,52 @@ mc_b_rows_begin(step_state* rows, const int32_t* stop_ids, int32_t n_stop, int32
     rows[r].kv_len = pos + 1;
     rows[r].write_slot = pos;
     rows[r].rope_row = pos;
+}
+
+// Rolling rows (mc_rolling_set, Part 2j): mc_b_rows_begin for a batch whose rows decode past max_seq on nn::sink_cache's
+// ring (nn/cache.h:187-204), one 64-thread workgroup per row (grid x = B).  Two differences:
+//   * a row never stops for the end of its cache -- on its stop ids only -- and at pos >= max_seq it takes the state derive_state
+//     (decode_kernels.hip) reaches after pos - max_seq + 1 single-step rolls from a linear cache: ring_base = (pos - max_seq + 1)
+//     % post, write_slot = pre_len + (post - 1 + ring_base) % post, kv_len = max_seq.  Rows get past the end by single steps only,
+//     so this is a function of pos alone and nothing is kept between calls; below max_seq the state is mc_b_rows_begin's.
+//   * the rope row.  The batch's table ends at max_seq and the rows of one call can be any distance apart, so thread j < hd / 2
+//     writes cos / sin of pair j at the row's absolute position into row r of rcos / rsin [B][hd / 2] -- rope_entry, the bits of
+//     mc_rope_table's row for that position -- and rope_row = r: mc_b_rope_kv_rows_bfloat is given rcos / rsin for the table.
+//     EVERY active row of a rolling batch takes this path, below max_seq as well: one path, and the same bits as the table's.
+// Every thread reads the row's state before thread 0 rewrites it (the barrier); a chained step needs no host round trip.
+extern "C" __global__ void __launch_bounds__(64)
+mc_b_rows_begin_rolling(step_state* rows, const int32_t* stop_ids, int32_t n_stop, int32_t max_seq, int32_t pre_len, int32_t advance,
+                        float* rcos, float* rsin, uint32_t hd, float theta)
+{
+    const uint32_t r = blockIdx.x, j = threadIdx.x, half = hd / 2;
+    if (row_idle(rows, r)) return; // (uniform)
+    int32_t pos = rows[r].pos;
+    const int32_t token = rows[r].token, step_index = rows[r].step_index;
+    bool stop = false;
+    if (advance) {
+        for (int32_t i = 0; i < n_stop && !stop; i++) stop = token == stop_ids[i];
+        pos += 1;
+    }
+    __syncthreads();
+    if (stop) {
+        if (j == 0) rows[r].pos = -1;
+        return;
+    }
+    if (j < half) rope_entry((uint32_t)pos, j, hd, theta, &rcos[(size_t)r * half + j], &rsin[(size_t)r * half + j]);
+    if (j != 0) return;
+    const int32_t post = max_seq - pre_len;
+    int32_t ring_base = 0, write_slot = pos, kv_len = pos + 1;
+    if (pos >= max_seq) {
+        ring_base = (pos - max_seq + 1) % post;
+        write_slot = pre_len + (post - 1 + ring_base) % post;
+        kv_len = max_seq;
+    }
+    rows[r].pos = pos;
+    if (advance) rows[r].step_index = step_index + (int32_t)gridDim.x;
+    rows[r].kv_len = kv_len;
+    rows[r].write_slot = write_slot;
+    rows[r].ring_base = ring_base;
+    rows[r].rope_row = (int32_t)r;
 }
 
 // mc_b_embed_bfloat without the advance (mc_b_rows_begin did it); an idle row gets zeros and its token is never read

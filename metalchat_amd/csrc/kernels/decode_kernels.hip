@@ -231,19 +231,27 @@ mc_rope_kv_float(const float* qkv, float* q_out, float* kc, float* vt, const flo
     rope_kv_body<F32>(qkv, q_out, kc, vt, fcos, fsin, q_norm, k_norm, st, H, KV, hd, max_seq, eps, mu);
 }
 
-// rope table (nn::rope::update, include/metalchat/nn/embedding.h:159-165): rows [start, start+rows)
+// one entry of nn::rope's table (nn::rope::update, include/metalchat/nn/embedding.h:159-165): cos / sin of pair j at absolute
+// position pos.  It depends on (pos, j, dim, theta) only -- whoever writes a table row writes these bits (mc_rope_table below,
+// mc_b_rows_begin_rolling of batch_kernels.hip)
+__device__ __forceinline__ void
+rope_entry(uint32_t pos, uint32_t j, uint32_t dim, float theta, float* c, float* s)
+{
+    const float e = 2.0f * (float)j / (float)dim;
+    const float freq = 1.0f / (float)pow((double)theta, (double)e);
+    const float angle = (float)pos * freq;
+    *c = (float)cos((double)angle);
+    *s = (float)sin((double)angle);
+}
+
+// rope table: rows [start, start+rows)
 extern "C" __global__ void
 mc_rope_table(float* fcos, float* fsin, uint32_t rows, uint32_t dim, uint32_t start_pos,
               float theta)
 {
     const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x, i = blockIdx.y;
-    if (i < rows && j < dim / 2) {
-        const float e = 2.0f * (float)j / (float)dim;
-        const float freq = 1.0f / (float)pow((double)theta, (double)e);
-        const float angle = (float)(start_pos + i) * freq;
-        fcos[(size_t)i * (dim / 2) + j] = (float)cos((double)angle);
-        fsin[(size_t)i * (dim / 2) + j] = (float)sin((double)angle);
-    }
+    if (i < rows && j < dim / 2)
+        rope_entry(start_pos + i, j, dim, theta, &fcos[(size_t)i * (dim / 2) + j], &fsin[(size_t)i * (dim / 2) + j]);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -205,6 +205,9 @@ def capi() -> C.CDLL:
                                      C.POINTER(i32)]),
         "mc_ragged_lengths": (i32, [vp, C.POINTER(i32)]),
         "mc_ragged_export_kv": (i32, [vp, i32, i32, vp, vp, C.POINTER(i32)]),
+        "mc_rolling_set": (i32, [vp, i32]),
+        "mc_rolling_enabled": (i32, [vp]),
+        "mc_rolling_fork_row": (i32, [vp, i32, i32]),
         "mc_rows_prefill": (i32, [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
         "mc_extend_rows": (i32, [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
         "mc_verify_rows": (i32, [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
@@ -874,8 +877,20 @@ class Batch:
         _check(capi().mc_ragged_lengths(self._h, out.ctypes.data_as(C.POINTER(C.c_int32))))
         return out
 
+    def set_rolling(self, enable: bool = True):
+        """Part 2j: ragged rows decode past max_seq_len on the sink ring (default off: they stop at the end of their cache)"""
+        _check(capi().mc_rolling_set(self._h, 1 if enable else 0))
+
+    def rolling(self) -> bool:
+        return bool(capi().mc_rolling_enabled(self._h))
+
+    def fork_row(self, dst: int, src: int):
+        """row `src`'s valid cache of every layer and its length onto row `dst`; works on a rolled row"""
+        _check(capi().mc_rolling_fork_row(self._h, dst, src))
+
     def export_row_kv(self, row: int, layer: int):
-        """row `row`'s own valid positions of `layer`: (K, V) of [length, n_kv_heads, head_dim]"""
+        """row `row`'s own valid positions of `layer`: (K, V) of [min(length, max_seq_len), n_kv_heads, head_dim] -- for a row
+        that has rolled the logical view: the sink rows, then the ring unrolled"""
         c = self.cfg
         shape = (c["max_seq_len"], c["n_kv_heads"], c["head_dim"])
         k = np.zeros(shape, dtype=self.np_T)
