@@ -21,8 +21,10 @@ SO = os.path.join(LIB, "libmetalchat_hip.so")
 KERNEL_SOURCES = [os.path.join(CSRC, "kernels", f) for f in (
     "metalchat_kernels.hip", "ref_kernels.hip", "gemv_kernels.hip", "decode_kernels.hip", "attn_block_kernels.hip",
     "synth_kernels.hip", "sampler_kernels.hip", "prefill_kernels.hip", "batch_kernels.hip", "packed_kernels.hip", "extend_kernels.hip", "verify_kernels.hip", "wide_kernels.hip", "tree_kernels.hip", "common.h", "abi.h", "handoff.h", "gemv.h", "gemv_ksplit.h", "synth.h", "pf_gemm8.h")]
-HOST_SOURCES = [os.path.join(CSRC, f) for f in ("backend.cc", "decoder.cc", "batch.cc", "model_io.cc", "text.cc", "json_min.h", "backend_impl.h",
-                                                 "decoder_batch.h", "decoder_options.h", "gemv_plan.h")] + [
+# the host library: every unit goes into the one hipcc command, units and headers together are what makes it stale
+HOST_UNITS = [os.path.join(CSRC, f) for f in ("backend.cc", "decoder.cc", "weights.cc", "prefill.cc", "prefill_blaslt.cc", "pipeline.cc", "batch.cc",
+                                               "model_io.cc", "text.cc")]
+HOST_HEADERS = [os.path.join(CSRC, f) for f in ("json_min.h", "backend_impl.h", "decoder_impl.h", "decoder_batch.h", "decoder_options.h", "gemv_plan.h")] + [
     os.path.join(CSRC, "kernels", "synth.h"), os.path.join(CSRC, "kernels", "abi.h"),
     os.path.join(os.path.dirname(HERE), "include", "metalchat_hip.h")]
 
@@ -55,10 +57,9 @@ def build_kernels(force: bool = False) -> str:
 
 def build_host(force: bool = False) -> str:
     os.makedirs(LIB, exist_ok=True)
-    if force or _stale(SO, HOST_SOURCES):
+    if force or _stale(SO, HOST_UNITS + HOST_HEADERS):
         cmd = [hipcc(), "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unused-function",
-               os.path.join(CSRC, "backend.cc"), os.path.join(CSRC, "decoder.cc"), os.path.join(CSRC, "batch.cc"),
-               os.path.join(CSRC, "model_io.cc"), os.path.join(CSRC, "text.cc"), "-ldl", "-o", SO]
+               *HOST_UNITS, "-ldl", "-o", SO]
         subprocess.check_call(cmd, cwd=CSRC)
     return SO
 

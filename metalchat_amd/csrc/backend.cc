@@ -2,8 +2,9 @@
 // queue+encoder) on the HIP module API.  Counterpart of the reference's src/metal.cc,
 // src/metal_impl.h and src/kernel_thread.cc; see the header for the per-function citations.
 //
-// This translation unit and decoder.cc are the ONLY places that include hip_runtime.h on the
-// host side (the reference confines metal-cpp to src/metal_impl.h the same way).
+// hip_runtime.h reaches the host side through backend_impl.h alone: this translation unit, the decoder's five (decoder.cc,
+// weights.cc, prefill.cc, prefill_blaslt.cc, pipeline.cc) and batch.cc include it, model_io.cc and text.cc do not (the reference
+// confines metal-cpp to src/metal_impl.h the same way).
 #include "backend_impl.h"
 
 #include <cstdio>

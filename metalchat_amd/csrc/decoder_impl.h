@@ -1,0 +1,521 @@
+// The decoder behind Part 2 of include/metalchat_hip.h, as its five translation units see it: the fused weights (linear_w, layer_w), the
+// greedy pick's descriptors (pick_block) and struct mc_decoder -- its state, the small helpers every unit calls inline, and the
+// declarations of everything else.  Which unit defines what:
+//   decoder.cc         the decode block plan (plan_block), the per-token decode, the hand-off fall-back, the C ABI of a step
+//   weights.cc         allocation and upload of the fused matrices, the synthetic model
+//   prefill.cc         the prompt pass (plan_gemm, run_prefill)
+//   prefill_blaslt.cc  the library GEMM of long prompts -- the only unit that sees hipBLASLt's header
+//   pipeline.cc        the layer pipeline (RCCL / local); it holds decoders, it is not part of one
+// batch.cc does not include this header: it reads a decoder through decoder_batch.h.
+#pragma once
+
+#include "backend_impl.h"
+#include "decoder_batch.h"
+#include "gemv_plan.h" // decoder_options / read_options (decoder_options.h) and plan_gemv
+
+#include <algorithm>
+#include <climits>
+#include <cmath>
+#include <cstddef>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <initializer_list>
+#include <map>
+#include <memory>
+#include <string>
+#include <unordered_map>
+#include <vector>
+
+struct blaslt_state; // prefill_blaslt.cc
+
+namespace mcimpl {
+
+// more kernel arguments behind a pack() whose head depends on the form of a launch
+template <typename... A> inline void
+push_all(arg_pack& p, const A&... a)
+{
+    (p.push(a), ...);
+}
+
+struct linear_w {
+    int fmt = MC_WFMT_T;
+    int out = 0, in = 0, group = 0; // group 0 = one scale per row
+    void* w = nullptr;
+    void* scales = nullptr;
+    size_t w_bytes = 0, s_bytes = 0;
+    size_t row_bytes = 0;
+    int ngroups = 1;
+    bool allocated = false;
+    std::vector<uint8_t> scales_host; // shadow of the quad-interleaved scale buffer (load path only)
+    void* wq2 = nullptr;      // int4: the quad-interleaved copy short prompts multiply from (prefill_kernels.hip mc_pf2_*), built on demand
+    uint64_t wq2_gen = 0;     // ... from the weights of this generation (mc_decoder::weights_gen)
+    void* wd = nullptr;       // int4 / int8: the dequantised bfloat16 copy [out][in] long prompts multiply by in the library GEMM (gemm_lib), built on demand
+    uint64_t wd_gen = 0;
+    // quantization::lora_adaptor(s) of the matrices fused here (quantization/lora.h:17-53): the A
+    // matrices stacked [nseg*rank][in] (a T-format GEMV of its own), B in fused row order
+    // [out][nseg*rank] with zeros outside each row's own adaptor columns, a = T(A x) in lora_vec
+    std::unique_ptr<linear_w> lora_a;
+    void* lora_b = nullptr;
+    std::vector<uint8_t> lora_b_host; // load path only
+    void* lora_vec = nullptr;
+    int lora_rank = 0;      // rank of one adaptor
+    int lora_cols = 0;      // nseg * rank
+    float lora_scale = 0.0f;
+};
+
+// EPI_STORE_PICK's two descriptors (kernels/gemv.h) and the words the first points at, as they lie in mc_decoder::pick_desc
+struct pick_block {
+    pick_epilogue atomic;   // key + ticket: the last workgroup of the head's launch finishes the pick
+    pick_epilogue per_wg;   // one key per workgroup (pick_keys), no ticket: folded by mc_argmax_keys behind the launch
+    unsigned long long key; // 0 between launches
+    uint32_t ticket;
+};
+
+struct layer_w {
+    linear_w qkv, wo, w13, w2;
+    void* qkv_epi = nullptr; // device qkv_epilogue
+    void* pn_attn = nullptr; // device postnorm_args: attention post-norm, residual = layer input, h_out = hidden_b
+    void* pn_ffn = nullptr;  // device postnorm_args: ffn post-norm, residual = hidden_b, h_out = hidden
+    void* attention_norm = nullptr;
+    void* ffn_norm = nullptr;
+    void* q_norm = nullptr;
+    void* k_norm = nullptr;
+    void* attention_post_norm = nullptr;
+    void* ffn_post_norm = nullptr;
+    void* kc = nullptr;
+    void* vt = nullptr;
+    int rope_table = 0;
+};
+
+inline uint16_t
+f2bf_host(float f)
+{
+    uint32_t u;
+    memcpy(&u, &f, 4);
+    if ((u & 0x7f800000u) == 0x7f800000u && (u & 0x007fffffu)) return (uint16_t)((u >> 16) | 0x40u);
+    u += 0x7fffu + ((u >> 16) & 1u);
+    return (uint16_t)(u >> 16);
+}
+
+inline float
+bf2f_host(uint16_t b)
+{
+    uint32_t u = (uint32_t)b << 16;
+    float f;
+    memcpy(&f, &u, 4);
+    return f;
+}
+
+inline int
+bit_width(uint32_t v)
+{
+    int n = 0;
+    while (v) {
+        n++;
+        v >>= 1;
+    }
+    return n;
+}
+
+// (weights.cc)
+size_t linear_bytes(const linear_w& L);
+// (decoder.cc) the owned layer of a global layer index; is every weight of the stage loaded (and gemma3's post-norm descriptors made)?
+mc_status find_layer(mc_decoder* d, int32_t layer, layer_w** out);
+mc_status check_ready(mc_decoder* d);
+// (prefill_blaslt.cc) the end of mc_decoder::blas
+void blaslt_release(blaslt_state* st);
+
+} // namespace mcimpl
+
+using namespace mcimpl;
+
+struct mc_decoder {
+    mc_decoder_config cfg;
+    decoder_options opt; // the MC_* switches, read once (read_options)
+    mc_device* dev = nullptr;
+    mc_library* lib = nullptr;
+    mc_queue* q = nullptr;
+    hipStream_t stream = nullptr;
+    int tb = 2; // sizeof(T)
+    int pre_len = 0;
+    int nsplit = 1;
+    int n_own = 0;
+    bool first_stage = true, last_stage = true;
+    std::string tname; // "bfloat" / "float"
+
+    std::map<std::string, hipFunction_t> fns;
+    std::vector<layer_w> layers;
+    // embedding
+    int emb_fmt = MC_WFMT_T;
+    void* emb_table = nullptr;
+    float* emb_scales = nullptr;
+    linear_w output;
+    void* final_norm = nullptr;
+
+    // arena
+    void* hidden = nullptr;     // T[dim]   running hidden row (h)
+    void* hidden_in = nullptr;  // T[dim]   inbound row for non-first stages
+    void* hidden_b = nullptr;   // T[dim]   gemma3: the row between the attention and the ffn half of a block
+    const void* pending_pn = nullptr; // gemma3: postnorm_args the next pre-norm GEMV has to apply to `proj`
+    uint64_t weights_gen = 1;  // bumped whenever weight rows change: the derived copies (linear_w::wq2) are rebuilt
+    bool pf_plain_on = false;  // ... resolved when the first long prompt arrives (plain_copy_ok)
+    bool pf_plain_known = false;
+    bool pf_lib_on = false;    // opt.pf_lib until the library fails (gemm_lib)
+    struct blaslt_state* blas = nullptr; // the library's handle, workspace and per-shape plans: made by gemm_lib on first use (prefill_blaslt.cc)
+    int lt_calls = 0; // library multiplications issued (mc_decoder_launch_log names them "hipblasLtMatmul")
+    bool lazy_pick = false;    // inside mc_decoder_generate: the pick of a token is folded by the NEXT token's embedding launch
+    bool graph_lazy = false;   // the captured token was recorded with lazy_pick
+    std::unordered_map<const void*, postnorm_args> pn_host; // the same descriptors on the host (the linear-order kernels take the three pointers as arguments)
+    void* qkv = nullptr;        // T[(H+2KV)*hd]
+    void* q_rot = nullptr;      // T[H*hd]
+    void* attn_out = nullptr;   // T[H*hd]
+    void* proj = nullptr;       // T[dim]   (gemma: pre-post-norm outputs)
+    void* gate = nullptr;       // T[ffn]
+    void* logits = nullptr;     // T[vocab]
+    float* expv = nullptr;      // [H][max_seq]
+    float* psum = nullptr;      // [H][nsplit]
+    float* pv_parts = nullptr;  // [pv_ranges][H*hd] fp32 partial P.V sums (long contexts)
+    int pv_ranges = 1;
+    // decode attention in one launch (mc_attn_fused_bfloat): {value, tag} granules of its two in-launch hand-offs
+    unsigned long long* attn_psum_g = nullptr; // [H][nsplit]            partial softmax denominators
+    unsigned long long* attn_slab_g = nullptr; // [KV][nsplit][n_rep][hd] fp32 partial P.V sums
+    unsigned long long* attn_row_g = nullptr;  // [H * hd / 2]          the finished attention row, two bf16 per granule (mc_attn_wo_*)
+    unsigned long long* attn_hid_g = nullptr;  // [dim / 2]             the hidden row behind Wo, for the w1|w3 phase of mc_attn_qkv_wo_w13_w_* (hand-off D)
+    int occ_w13 = -1;
+    unsigned long long* attn_qkv_g = nullptr;  // [KV][(n_rep + 2) hd / 2] the step's rotated queries and K / V row, two bf16 per granule (mc_attn_qkv_wo_*)
+    // ---- what happens when an in-launch hand-off gives up (its workgroups were not resident together: another stream or process
+    // holds part of the chip).  The launch sets state.err and completes; the host then LATCHES the decoder onto the launches
+    // that need no co-residency (attn_fused_on = false: scores, P.V and the GEMVs as launches of their own), drops the captured
+    // graph and -- where the step can be repeated exactly -- runs it again (mc_decoder_step; mc_decoder_generate while the
+    // ring has not turned inside the call).  handoff_fallbacks counts those events (mc_decoder_handoff_fallbacks).
+    step_state* state_bak = nullptr; // the step state in front of the call that may have to be repeated
+    uint32_t* err_host = nullptr;      // pinned: state.err of a step nobody waited for (a non-last stage, next_token == NULL)
+    hipEvent_t err_evt = nullptr;
+    bool err_pending = false;
+    int handoff_fallbacks = 0;
+    // ... and the fall-back is TEMPORARY (round 6): one transient stall (another stream holding CUs for 50 ms, a profiler pass) must not cost every
+    // later token the one-launch blocks.  After `rearm_after` tokens without a hand-off launch the decoder takes them again (mc_decoder_handoff_rearms counts);
+    // every further fall-back doubles the distance (a chip that is shared for good settles on the launches that need no co-residency), MC_HANDOFF_REARM=0: never
+    int rearm_after = 256, clean_tokens = 0, handoff_rearms = 0;
+    void
+    note_clean_tokens(int n)
+    {
+        if (attn_fused_on || !opt.attn_fused || rearm_after <= 0) return;
+        clean_tokens += n;
+        if (clean_tokens < rearm_after) return;
+        attn_fused_on = true;
+        clean_tokens = 0;
+        handoff_rearms++;
+        drop_graph(); // (captured with the launches that need no co-residency)
+    }
+    int occ_fused = -1, occ_wo = -1, occ_wo_w = -1, occ_wo_i8 = -1, occ_wo_qkn = -1, occ_qkv_qkn = -1, occ_qkv_only = -1, occ_wo_i4_wide = -1;   // co-resident workgroups per CU of the hand-off launches (the occupancy API's answer; -1: not asked yet)
+    bool attn_fused_on = true;   // opt.attn_fused, until a hand-off gives up (handoff_failed) and again after rearm_after clean tokens (note_clean_tokens)
+    void* taps = nullptr;       // T[(n_own+1)*dim]
+    step_state* state = nullptr;
+    int32_t* tokens_dev = nullptr;
+    // the greedy pick inside the output head's launch (gemv.h EPI_STORE_PICK): two descriptors {key*, ticket*, state*, tokens_out*}
+    // -- [0, 32) with the atomic key at [64, 72) and the ticket at [72, 76), both zero between launches; [32, 64) with pick_keys
+    // and no ticket
+    char* pick_desc = nullptr;
+    unsigned long long* pick_keys = nullptr; // MC_HEAD_PICK=2: one key per workgroup of the head's launch, folded by mc_argmax_keys
+    static constexpr unsigned pick_slots = 1024;
+    int tokens_cap = 0;
+    // sampler (nn/sampling.h:303-313); kind 0 = greedy argmax, 1 = topk -> nucleus -> multinomial
+    int sampler_kind = MC_SAMPLER_GREEDY;
+    int top_k = 50;
+    float inv_temp_T = 0.0f, top_p_T = 0.0f;
+    uint64_t* cand = nullptr;      // [chunks][kpad] candidate keys
+    uint64_t* seeds = nullptr;     // [n_seed_pairs][2]
+    int n_seed_pairs = 0, seed_cap = 0;
+    float* sampler_taps = nullptr; // [7][128]
+    // prompt pass (prefill_kernels.hip): row buffers for up to pf_cap rows
+    int pf_cap = 0;
+    size_t pf_probs_elems = 0;
+    void *pf_x = nullptr, *pf_xn = nullptr, *pf_h = nullptr, *pf_proj = nullptr, *pf_qkv = nullptr,
+         *pf_q = nullptr, *pf_att = nullptr, *pf_g2 = nullptr, *pf_g = nullptr, *pf_probs = nullptr;
+    int32_t* pf_tokens = nullptr;
+    float* pf_etab = nullptr; // exp_precise of every bfloat16 value (prefill_kernels.hip mc_exp_table_bfloat), 256 KiB
+    float* pf_gtab = nullptr; // gemma: T(gelu) of every bfloat16 value (mc_gelu_table_bfloat), 256 KiB; MC_PF_GELU_TABLE=0: none (the fp64 tanh per element)
+    void* pf_lora = nullptr;
+    size_t pf_lora_elems = 0;
+    float* pf_part = nullptr; // split-K partial sums [splits][M][N]
+    size_t pf_part_elems = 0;
+    bool ring_turned = false;
+    void *rot_k = nullptr, *rot_v = nullptr; // scratch of mc_kv_rotate (one layer's K and Vt)
+    hipEvent_t pf_e0 = nullptr, pf_e1 = nullptr;
+    std::map<std::string, double> pf_ms;
+
+    template <typename F> mc_status
+    timed(const char* cat, F&& f)
+    {
+        if (!opt.pf_timing) return f();
+        if (!pf_e0) {
+            MC_HIP(hipEventCreate(&pf_e0));
+            MC_HIP(hipEventCreate(&pf_e1));
+        }
+        MC_HIP(hipEventRecord(pf_e0, stream));
+        mc_status s = f();
+        if (s != MC_OK) return s;
+        MC_HIP(hipEventRecord(pf_e1, stream));
+        MC_HIP(hipEventSynchronize(pf_e1));
+        float ms = 0.0f;
+        MC_HIP(hipEventElapsedTime(&ms, pf_e0, pf_e1));
+        pf_ms[cat] += ms;
+        return MC_OK;
+    }
+    float* rope_cos[2] = {nullptr, nullptr};
+    float* rope_sin[2] = {nullptr, nullptr};
+    int rope_rows = 0;
+    int rope_start = 0;
+    bool rope_valid = false;
+    int last_pos = -1;
+    bool want_taps = false;
+
+    hipGraph_t graph = nullptr;
+    hipGraphExec_t graph_exec = nullptr;
+
+    std::vector<void*> allocs;
+    bool pn_ready = false;
+    // test / measurement aids: the names of the kernels launched eagerly since the log was switched on (a replayed graph
+    // launches what was logged when it was captured)
+    bool log_on = false;
+    std::vector<std::string> launch_log;
+
+    ~mc_decoder();
+
+    mc_status
+    alloc(void** p, size_t bytes, bool zero = true)
+    {
+        hipError_t e = hipMalloc(p, bytes ? bytes : 16);
+        if (e != hipSuccess)
+            return fail(MC_ERR_ALLOC, std::string("hardware_memory_allocator: failed to allocate ") +
+                                          std::to_string(bytes) + " bytes: " + hipGetErrorString(e));
+        allocs.push_back(*p);
+        if (zero) {
+            // complete before alloc returns: callers fill some of these buffers with synchronous copies on the null
+            // stream, which is not ordered against this (non-blocking, or adopted) stream
+            MC_HIP(hipMemsetAsync(*p, 0, bytes ? bytes : 16, stream));
+            MC_HIP(hipStreamSynchronize(stream));
+        }
+        return MC_OK;
+    }
+
+    // give a buffer of the arena back (the caller has synchronised the stream)
+    void
+    release(void** p)
+    {
+        if (!*p) return;
+        auto it = std::find(allocs.begin(), allocs.end(), *p);
+        if (it != allocs.end()) allocs.erase(it);
+        (void)hipFree(*p);
+        *p = nullptr;
+    }
+
+    void
+    drop_graph()
+    {
+        if (graph_exec) (void)hipGraphExecDestroy(graph_exec);
+        if (graph) (void)hipGraphDestroy(graph);
+        graph_exec = nullptr;
+        graph = nullptr;
+    }
+
+    mc_status
+    fn(const std::string& name, hipFunction_t* out)
+    {
+        auto it = fns.find(name);
+        if (it != fns.end()) {
+            *out = it->second;
+            return MC_OK;
+        }
+        hipFunction_t f = nullptr;
+        hipError_t e = hipModuleGetFunction(&f, lib->module, name.c_str());
+        if (e != hipSuccess || !f)
+            return fail(MC_ERR_INVALID_ARGUMENT, "hardware_accelerator: function " + name +
+                                                     " not found in a shader library");
+        fns[name] = f;
+        *out = f;
+        return MC_OK;
+    }
+
+    mc_status
+    launch(const std::string& name, unsigned gx, unsigned gy, unsigned gz, unsigned bx, unsigned lds,
+           arg_pack&& a)
+    {
+        hipFunction_t f;
+        mc_status s = fn(name, &f);
+        if (s != MC_OK) return s;
+        size_t n = a.buf.size();
+        void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, a.buf.data(), HIP_LAUNCH_PARAM_BUFFER_SIZE,
+                         &n, HIP_LAUNCH_PARAM_END};
+        mcimpl::launch_range range(name.c_str(), gx, gy, gz, bx, 1, 1);
+        if (log_on) launch_log.push_back(name);
+        hipError_t e = hipModuleLaunchKernel(f, gx, gy, gz, bx, 1, 1, lds, stream, nullptr, extra);
+        if (e != hipSuccess) return hip_fail(e, name.c_str());
+        return MC_OK;
+    }
+
+    // ---------------------------------------------------------------- weights (weights.cc)
+    size_t row_bytes(int fmt, int in) const;
+    mc_status alloc_linear(linear_w& L, int fmt, int out, int in, int group);
+    mc_status upload_rows(linear_w& L, int dst_row0, int dst_stride, int rows, const void* weight, const float* scales, int perm_hd = 0);
+
+    // ---------------------------------------------------------------- launches
+    // which kernel a decode GEMV takes is decided in gemv_plan.h (plan_gemv); these three gates of it are also what the launches around a GEMV ask
+    gemv_env genv{}; // fixed at create time
+    static gemv_shape
+    shape_of(const linear_w& L) { return {L.fmt, L.out, L.in, L.group, L.lora_cols}; }
+    bool
+    lin_ok(const linear_w& L) const { return ::lin_ok(shape_of(L), genv); }
+    bool
+    lin_split_ok(const linear_w& L) const { return ::lin_split_ok(shape_of(L), genv); }
+    int
+    ling_kib(const linear_w& L) const { return ::ling_kib(shape_of(L), genv); }
+    // P.V over four ranges of cache slots (256 workgroups instead of 64: a CU takes in ~ 25 GB/s, and 64 of them need
+    // ~ 4 us for the V cache of one layer at S = 2048) with the range sums added by the Wo GEMV's prologue (gemv.h
+    // PRO_PARTS) instead of a reduce launch
+    bool
+    pv_fold(const linear_w& wo) const
+    {
+        return opt.pv_fold_on && (lin_ok(wo) || ling_kib(wo)) && !wo.lora_cols && cfg.max_seq_len <= 16384;
+    }
+
+    // ---------------------------------------------------------------- the decode attention block: which launches (plan_block)
+    // The gates every launch with an in-launch hand-off shares: the switch (MC_ATTN_FUSED, and the latch of handoff_failed), bfloat rows -- the granule
+    // buffers attn_psum_g / attn_slab_g / attn_row_g / attn_qkv_g / attn_hid_g exist for them only, all or none (mc_decoder_create) -- and layer tags of one byte
+    bool
+    handoffs_ok() const { return attn_fused_on && attn_psum_g && tb == 2 && n_own <= 254; }
+    // 256-thread attention workgroups per CU that may wait for one another.
+    // Co-residency from what a CU can HOLD of the real kernel (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor, asked once:
+    // query_occupancy), capped by what was measured to pay (opt.attn_fused_max_wgs_per_cu).  The API is advisory (ROCm 7.2 reads
+    // one block per CU high for SGPR-heavy 256-thread kernels, MI355X_MICROARCH.md), and another stream can take CUs away
+    // at any time: a launch that is not resident after all gives up and the host falls back (handoff_failed).
+    unsigned
+    fused_wgs_per_cu() const { return std::min(opt.attn_fused_max_wgs_per_cu, occ_fused < 0 ? opt.attn_fused_max_wgs_per_cu : (unsigned)occ_fused); }
+    // scores + softmax + P.V in one launch: bfloat rows, layer tags of one byte, and a grid that is certainly co-resident (its
+    // workgroups wait for one another) and gathers from few producers: at most opt.attn_fused_max_wgs_per_cu 256-thread workgroups
+    // of 64 cache slots per CU
+    bool
+    attn_fused() const
+    {
+        return handoffs_ok() && (unsigned)(nsplit * cfg.n_kv_heads) <= fused_wgs_per_cu() * (unsigned)dev->prop.multiProcessorCount;
+    }
+    // ... with 128-slot ranges (mc_attn_fused_t2_bfloat: two score tiles per wave) where the 64-slot ranges are too many workgroups to
+    // be resident together -- Llama-3-8B at S = 8192: 1024 -> 512.  Round 3 measured that form at 14.8 us against 6.3 + 8.5 for
+    // the two launches; with the XCD-local hand-offs of round 4 it is re-measured (MC_ATTN_T2)
+    bool
+    attn_fused_t2() const
+    {
+        return opt.attn_t2_on && handoffs_ok() && !attn_fused() && nsplit % 2 == 0 &&
+               (cfg.head_dim == 128 || cfg.head_dim == 64) && cfg.n_kv_heads % 8 == 0 &&
+               (unsigned)(nsplit / 2 * cfg.n_kv_heads) <= fused_wgs_per_cu() * (unsigned)dev->prop.multiProcessorCount;
+    }
+    // (decoder.cc, like every member declared from here to run_head)
+    void query_occupancy();
+    void handoff_failed();
+    bool attn_wo_fused(const linear_w& wo) const;
+
+    // The XCD-local fast path of hand-offs A / B / Q (handoff.h) pays where the workgroups of one kv head CAN share an XCD: they
+    // are the blocks b with equal b % n_kv, blocks with equal b % 8 share an XCD, so n_kv must be a multiple of 8.  With
+    // TinyLlama's 4 kv heads half of every head's ranges sit on another XCD and are found only by the occasional look at the
+    // fabric copy: mc_attn_fused_bfloat 24.1 us against 7.0 without the fast path (profiles/r04_kernel_stats_tinyllama_fastpath_regression.csv)
+    bool
+    handoff_fast_here() const { return opt.handoff_fast && cfg.n_kv_heads % 8 == 0; }
+    uint32_t handoff_mode_alone() const;
+    int kv_virtual_shift() const;
+
+    // The row-pair deal of the launches with wq|wk|wv inside: a kv head's (n_rep + 2) hd / 2 row pairs of wq|wk|wv (its query heads' rows, its K and
+    // its V row) go evenly over the head's `ns` workgroups, at most `cap` to each
+    static bool
+    deal_ok(int pg, int ns, int cap) { return pg % ns == 0 && pg / ns <= cap; }
+    template <typename F> int whole_range_tiles(std::initializer_list<int> cands, int heads, F&& ok) const; // (defined in front of plan_block, its one caller)
+    int chain_w13_fetch(const layer_w& L, unsigned grid) const;
+
+    // What run_layers() launches for the first half of one block -- from the row handed to the block to the finished attention row, or past Wo
+    // where the form holds it.  Computed per layer per eager step: the fall-back latch (handoff_failed), the re-arm (note_clean_tokens), taps and a
+    // late occupancy answer all change it between tokens.
+    enum class block_form { // (by the numbers of plan_block's list)
+        qkv_wo_w13_w, qkv_wo_w, qkv_wo_i8, qkv_wo_i4 /* 4, 5 */, qkv_only, qkv_wo_qkn /* 8 */,
+        wo_qkn, wo_i4, fused, fused_qkn, fused_t2, scores_pv // 7, 9 -- wq|wk|wv as a GEMV -- by their attention tail a - e
+    };
+    struct block_plan {
+        block_form form = block_form::scores_pv;
+        std::string name;     // the kernel of the form's attention launch
+        int tiles = 1, vsh = 0, ns = 1; // 64-slot tiles per range; log2 of the virtual kv heads per cache head (kv_virtual_shift); ranges per kv head: nsplit / tiles
+        unsigned grid = 0;    // workgroups of that launch
+        uint32_t fast = 0;    // its `fastpath` argument (handoff.h)
+        int chain_f = 0, chain_p = 0; // qkv_wo_w13_w: pairs per fetcher wave, most pairs of a poller wave
+        bool qkv_gemv = false, rope_kv = false; // wq|wk|wv is a GEMV in front of the launch (7, 9); ... and gemma3's q/k-norm + rope + cache write a launch of their own (mc_rope_kv_T) behind it
+        bool wo_gemv = false, pv_fold = false;  // Wo is a GEMV behind the launch; ... whose prologue adds the range sums of P.V (pv_fold)
+    };
+    block_plan plan_block(const layer_w& L) const;
+
+    // ---------------------------------------------------------------- the hand-off reporting and the per-token decode (decoder.cc)
+    mc_status check_handoffs(const step_state& st);
+    mc_status report_handoff(uint32_t code);
+    mc_status check_err_synced();
+    mc_status poll_pending_err();
+    void note_err_async();
+    mc_status gemv(const linear_w& L, int pro, int epi, const void* x, void* y, const void* res, const void* norm_w, float mu);
+    mc_status ensure_rope(int pos, int len = 1);
+    mc_status post_norm_row(const void* norm_w, const void* res);
+    mc_status run_layers(const void* x_in);
+    mc_status run_embed(bool advance = false);
+    mc_status fold_pick();
+    // chained greedy generation on one stage: can the fold wait for the next token's embedding launch?
+    bool
+    lazy_pick_ok() const
+    {
+        return opt.lazy_pick_on && first_stage && last_stage && head_pick() && opt.head_pick_mode == 2 && emb_fmt == MC_WFMT_T && !want_taps;
+    }
+    bool head_pick() const;
+    mc_status run_head();
+    mc_status run_token(const void* hidden_src, bool advance = false);
+
+    // ---------------------------------------------------------------- prompt pass (prefill.cc; lib_ok and gemm_lib: prefill_blaslt.cc)
+    mc_status grow(void** p, size_t* have, size_t need, size_t elem_bytes);
+    mc_status ensure_prefill(int M, int S);
+    unsigned gemm_row_tile(int M) const;
+    unsigned gemm_splits(const linear_w& L, int M) const;
+    bool pf2_ok(const linear_w& L, int M) const;
+    mc_status ensure_pf2(const linear_w& Lc);
+    void pf2_split(const linear_w& L, unsigned& splits, unsigned& ktper) const;
+    bool g8_ok(const linear_w& L, int M) const;
+    unsigned g8_splits(const linear_w& L, int M) const;
+    bool plain_copy_ok();
+    bool lib_ok(const linear_w& L, int M) const;
+    mc_status ensure_wd(const linear_w& Lc, const void** wd);
+    bool gemm_lib(const linear_w& L, const void* X, void* Y, int M, bool f32_out);
+    // ---- the prompt GEMM plan: which kernel family multiplies X[M][L.in] by this matrix, with what tiles and K ranges.  The one place that
+    // chooses: gemm_run() launches what it says, run_prefill() asks it about w1|w3.  epi: 0 store, 1 + residual, 2 stop at the fp32
+    // partial sums (gemm_to_parts), 3 / 4 silu / gelu * mul.  No launch, no allocation, no kernel name (names are built where they are launched).
+    enum class gemm_family { lib, stream, g8, tiled, tile64 };
+    struct gemm_plan {
+        gemm_family fam = gemm_family::tile64;
+        unsigned bm = 64;                      // rows of X per workgroup
+        unsigned splits = 1, ktper = 0;        // K ranges (grid z; lib: the one partial); stream: K steps of 128 per range
+        unsigned gx = 0, gy = 0, block = 256;  // the family's launch
+    };
+    gemm_plan plan_gemm(const linear_w& L, int M, int epi) const;
+    // One plan, one launch per family, one reduce.  epi 2 stops at the partial sums in pf_part ([splits][M][out]); the answer's `splits`
+    // is then how many the consumer adds up, 0 when this matrix at this M leaves none (nothing was launched: the caller takes gemm()).
+    struct gemm_done {
+        mc_status st;
+        unsigned splits;
+    };
+    gemm_done gemm_run(const linear_w& L, int epi, const void* X, void* Y, const void* res, int M);
+    gemm_done gemm_to_parts(const linear_w& L, const void* X, int M);
+    mc_status gemm(const linear_w& L, int epi, const void* X, void* Y, const void* res, int M);
+    mc_status norm_rows(const void* x, const void* w, const void* res, void* y, int M, float mu);
+    mc_status qkv_rope_cache(const layer_w& L, void* kc, void* vt, int M, int start_pos, int rope_pos, float mu, const packed_prefill* pk);
+
+    // the fused attention launch of ONE prompt of M rows (the probabilities stay on chip): which kernel, its grid and block
+    struct attn_plan {
+        std::string name;
+        unsigned gx, gy, block;
+    };
+    attn_plan plan_attention(int M) const;
+    mc_status gemm_residual(const linear_w& W, const void* X, const void* res, void* out, const void* post_w, const void* next_w, const char* label, int M, float mu, bool* xn_done);
+    mc_status run_prefill(int M, int cache_pos, int rope_pos, int window, const void* rows_in, const packed_prefill* pk = nullptr);
+};

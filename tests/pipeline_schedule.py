@@ -8,7 +8,7 @@ brings the greedy token back to the first stage.  No all-reduce, no all-gather.
 This module is TEST INFRASTRUCTURE -- the schedule only (round 4: moved out of the product package): tests/test_pipeline_cpu.py drives it over gloo
 (world 2 and 3) with the CPU oracle as the stage, so the hop protocol -- who sends what to whom, in which
 order, past max_seq_len -- is covered without a GPU.  The product path does not use it: bench.py and the
-C++ shim go through mc_pipeline_* (metalchat_amd/csrc/decoder.cc: ncclSend / ncclRecv on the decoder's
+C++ shim go through mc_pipeline_* (metalchat_amd/csrc/pipeline.cc: ncclSend / ncclRecv on the decoder's
 stream, or device-to-device copies behind events), which implement the same schedule and are checked on the
 GPU by tests/test_pipeline_gpu.py (local transport == single stage bit for bit; RCCL with 2 and 4 ranks
 where that many devices are visible).

@@ -1,6 +1,6 @@
 """Kernel-level parity of the round-5 prompt GEMM (`mc_pf_gemm8_{i4,i8,w}_bfloat_e{0,1,2,3}`, kernels/pf_gemm8.h: 256 x 256 tiles, two
 wave groups alternating between LDS and the matrix pipe, quantised W dequantised inside the loop) -- the kernels `mc_decoder_prefill`
-launches for prompts of 384 rows and more (decoder.cc g8_ok), launched BY NAME through the Part-1 seam on weights packed by the decoder, against the
+launches for prompts of 384 rows and more (prefill.cc g8_ok), launched BY NAME through the Part-1 seam on weights packed by the decoder, against the
 oracle's restatement of the reference's linear on len > 1 rows: hadamard_broadcast (Wd = T(T(q) T(s)), kernel/mul.metal:51-85) + bmm
 (kernel/bmm.metal:25-82, nn/linear.h:70-81), residual add in T (kernel/arithmetic.metal:13-46), silu and hadamard in T
 (kernel/activation.metal:13-78, kernel/mul.metal:13-48) as nn/transformer.h:53-59 composes them.

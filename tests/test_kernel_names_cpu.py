@@ -79,7 +79,7 @@ def test_decode_and_reference_kernels_present(symbols):
               "mc_exp_table_bfloat", "mc_pf_exp_window_bfloat", "mc_pf_attn2_bfloat_hd128", "mc_pf_attn4_bfloat_hd128", "mc_pf_attn8_bfloat_hd128", "mc_pf_attn8_bfloat_hd256", "mc_pf_attn8_bfloat_hd64_h8", "mc_pf_attn8_bfloat_hd64_h4",  # exp of a bfloat16 by table (prompt attention, silu)
               "mc_pf_dequant_rows_i4_bfloat", "mc_pf_dequant_rows_i8_bfloat"):  # the dequantised copy the opt-in library GEMM multiplies by
         assert k in symbols, k
-    # the 256 x 256 ping-pong GEMM of long prompts (kernels/pf_gemm8.h, decoder.cc g8_launch)
+    # the 256 x 256 ping-pong GEMM of long prompts (kernels/pf_gemm8.h, prefill.cc gemm_run)
     assert "mc_gelu_table_bfloat" in symbols
     for f in ("i4", "i8", "w"):
         for e in range(5):   # (e4, round 6: gemma's gelu(w1 x) * (w3 x) from the table)

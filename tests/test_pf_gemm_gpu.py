@@ -178,7 +178,7 @@ def read_guarded(buf, n, dtype, what):
 
 
 def gemm(acc, fam, mat, xb, M, N, epi, z=1, res=None, lora=None):
-    """one launch of a tile GEMM as decoder.cc gemm() forms it; returns [M][N] (e0 / e1: T bits or floats), [z][M][N] fp32 (e2),
+    """one launch of a tile GEMM as prefill.cc gemm() forms it; returns [M][N] (e0 / e1: T bits or floats), [z][M][N] fp32 (e2),
     [M][N / 2] (e3)"""
     import metalchat_amd as mc
 

@@ -96,12 +96,12 @@ def test_pipelined_tokens_equal_single_process(world):
 
 def test_the_native_pipeline_ships_the_hidden_row_as_bytes_and_bench_needs_no_torch():
     # RCCL has no 16-bit unsigned element type (its process group rejects UInt16 tensors, tools/dtype_probe.py on the
-    # MI355X box): the bf16 hidden row travels as bytes through ncclSend / ncclRecv (csrc/decoder.cc, mc_pipeline_generate);
+    # MI355X box): the bf16 hidden row travels as bytes through ncclSend / ncclRecv (csrc/pipeline.cc, mc_pipeline_generate);
     # bench.py drives that C ABI and must not import torch at any N
     import os
     import re
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    host = open(os.path.join(root, "metalchat_amd", "csrc", "decoder.cc")).read()
+    host = open(os.path.join(root, "metalchat_amd", "csrc", "pipeline.cc")).read()
     assert re.search(r"api\.Send\(d->hidden, row, ncclUint8", host) and re.search(r"api\.Recv\(d->hidden_in, row, ncclUint8", host)
     bench = open(os.path.join(root, "bench.py")).read()
     assert not re.search(r"^\s*(import|from)\s+torch", bench, re.M)

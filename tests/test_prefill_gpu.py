@@ -549,7 +549,7 @@ def test_two_head_prompt_attention_sliding_window_and_second_chunk(acc, monkeypa
     check_against_oracle(acc, cfg, weights, dict(weight_format=2, group_size=32), tokens, start_pos=21, warm=warm, expect_kernel="mc_pf_attn2_bfloat_hd32")
 
 
-# ---- the 256 x 256 ping-pong GEMM of long prompts (kernels/pf_gemm8.h, decoder.cc g8_ok: from 257 rows on, two row tiles; MC_PF_GEMM8_ROWS lowers the
+# ---- the 256 x 256 ping-pong GEMM of long prompts (kernels/pf_gemm8.h, prefill.cc g8_ok: from 257 rows on, two row tiles; MC_PF_GEMM8_ROWS lowers the
 # gate so that shorter prompts of the models the oracle can follow reach it too).  Kernel-level parity: tests/test_gemm8_gpu.py.
 @pytest.mark.parametrize("quant,fmt,group,copy", [("i4", 2, 32, "0"), ("i4", 2, 128, "0"), ("i8", 1, 32, "0"), (None, 0, 0, None),
                                                   ("i4", 2, 128, None), ("i8", 1, 32, None)])
@@ -557,7 +557,7 @@ def test_two_head_prompt_attention_sliding_window_and_second_chunk(acc, monkeypa
 def test_long_prompts_take_the_ping_pong_gemm_and_match_the_oracle(acc, n, gate, quant, fmt, group, copy, monkeypatch):
     """Every linear of the block through mc_pf_gemm8_*: wq|wk|wv / wo / w2 with a plain store or residual (these models are too
     narrow to split K), w1|w3 with silu * mul in its epilogue; the library is never called.  Quantised matrices multiply from their
-    dequantised bfloat16 copies (round 6, decoder.cc plain_copy_ok: the default where the copies fit an eighth of the device's memory --
+    dequantised bfloat16 copies (round 6, prefill.cc plain_copy_ok: the default where the copies fit an eighth of the device's memory --
     mc_pf_gemm8_w_* on linear_w::wd) or, with MC_PF_PLAIN_COPY=0, from the quantised rows (no copy: mc_decoder_derived_weight_bytes stays 0)."""
     import metalchat_amd as mc
 
@@ -868,7 +868,7 @@ def test_wide_long_prompt_splits_k_in_the_ping_pong_gemm(acc, copy, monkeypatch)
 
 
 @pytest.mark.slow   # (hipBLASLt is opt-in since round 5, MC_PF_BLASLT=1: a comparison aid, not the product path)
-# ---- the library GEMM of long prompts (decoder.cc gemm_lib: hipBLASLt on the dequantised bfloat16 copy of a matrix).  The decoder
+# ---- the library GEMM of long prompts (prefill_blaslt.cc gemm_lib: hipBLASLt on the dequantised bfloat16 copy of a matrix).  The decoder
 # takes it -- ONLY when asked to, MC_PF_BLASLT=1: an opt-in comparison since round 5, the default path builds no dequantised copy --
 # where a launch has >= 48 tiles of 256 x 256 (w1|w3 of Llama-3-8B from 256 rows on, every matrix from 768); MC_PF_BLASLT=2 takes it for every
 # prompt GEMM that can, which is how the models the oracle can follow reach it.

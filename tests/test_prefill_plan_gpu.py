@@ -1,5 +1,5 @@
 """The ordered launch log of the prompt pass, pinned for the smallest shapes at which each arm of the prompt GEMM plan
-(decoder.cc plan_gemm) and each form of a run_prefill step is taken: an edit of the ladder shows up as a diff of kernel names,
+(prefill.cc plan_gemm) and each form of a run_prefill step is taken: an edit of the ladder shows up as a diff of kernel names,
 not as a timing.  The expected sequences are data (tests/golden/prompt_launch_logs.json), recorded on the MI355X from the build
 of the commit the file names -- the one in front of plan_gemm -- with this module's `record` entry point:
 

@@ -156,7 +156,7 @@ class Call:
 
 
 def px_launch(acc, etab, c, tab, grps, nh, slots=None):
-    """mc_px_sums, mc_px_pv and (a group with a split tile) mc_px_reduce as decoder.cc run_prefill launches them, group by group
+    """mc_px_sums, mc_px_pv and (a group with a split tile) mc_px_reduce as prefill.cc run_prefill launches them, group by group
     with ebase = the group's first range.  The scratch of a group is `slots` slots (the largest group), refilled with NaN between
     groups; the sums buffer continues as a NaN guard up to the whole table's size, so that an index that forgets ebase reads NaN
     inside the buffer.  Returns the output rows and the sums of every range [ranges][H][16]"""
@@ -189,7 +189,7 @@ def px_launch(acc, etab, c, tab, grps, nh, slots=None):
         assert np.all(np.isnan(got[count:])), f"group {gi}: mc_px_sums wrote behind its {count} slots"
         mc.KernelTask(k_pv, grid, (256, 1, 1), [c.qb, c.segb, tabb, u32(first), c.kb, c.vb, np.uint64(c.cstride), sumsb, partb, outb, u32(H),
                                                 u32(c.n_rep), u32(c.max_seq), c.scale, etab])()
-        if split:   # (decoder.cc: only a group that holds a split tile)
+        if split:   # (prefill.cc: only a group that holds a split tile)
             mc.KernelTask(k_red, (H * 256, count, 1), (256, 1, 1), [c.segb, tabb, u32(first), partb, outb, u32(H)])()
         acc.wait()
         part = partb.download(np.float32, nan_part.size).reshape(slots + 1, -1)
@@ -404,7 +404,7 @@ def test_px_placement_does_not_matter(acc, etab, hd, H, KV, nh):
 
 # ------------------------------------------------------------------------------------------ A2: the packed prompt pass's attention
 def pp_launch(acc, etab, c, nh):
-    """mc_pp_attn{,2}_bfloat_hd*: grid (tiles, H / NH), as decoder.cc run_prefill launches it"""
+    """mc_pp_attn{,2}_bfloat_hd*: grid (tiles, H / NH), as prefill.cc run_prefill launches it"""
     import metalchat_amd as mc
 
     H, hd = c.H, c.hd
@@ -499,7 +499,7 @@ class RopeCase:
         self.vt0 = bf(rng.normal(0, 30, (B, KV, hd, ROPE_S)))
         self.cstride = KV * ROPE_S * hd + GUARD
         self.segb = acc.to_device(rt.words(self.segs, 4).reshape(-1))
-        self.gx = ((H + KV) * self.M + per - 1) // per + KV * ((self.M + 15) // 16)    # decoder.cc pk_gx
+        self.gx = ((H + KV) * self.M + per - 1) // per + KV * ((self.M + 15) // 16)    # prefill.cc pk_gx
 
     def slot(self, r):
         """packed row r -> (batch row, slot)"""

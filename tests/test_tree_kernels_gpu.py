@@ -44,7 +44,7 @@ def node_table(c, trees):
 
 
 def tv_launch(acc, etab, c, tab, nh, nodes):
-    """mc_tv_sums, mc_tv_pv and (a split tile) mc_px_reduce as decoder.cc run_prefill launches them for a tree call: one group"""
+    """mc_tv_sums, mc_tv_pv and (a split tile) mc_px_reduce as prefill.cc run_prefill launches them for a tree call: one group"""
     import metalchat_amd as mc
 
     H, hd = c.H, c.hd

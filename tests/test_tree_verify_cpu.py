@@ -49,7 +49,7 @@ def test_the_tree_kernels_are_exactly_the_set_in_the_code_object():
     host = open(os.path.join(ROOT, "metalchat_amd", "csrc", "batch.cc")).read()
     for stem in ('"mc_tv_accept"', '"mc_tv_compact_bfloat"'):
         assert stem in host, stem
-    dec = open(os.path.join(ROOT, "metalchat_amd", "csrc", "decoder.cc")).read()
+    dec = open(os.path.join(ROOT, "metalchat_amd", "csrc", "prefill.cc")).read()
     for stem in ('"mc_tv_sums"', '"mc_tv_pv"', '"mc_tv_rope_cache_bfloat"', '"mc_tv_rope_cache_parts_bfloat"'):
         assert stem in dec, stem
     out = readelf("--symbols", "--wide")

@@ -396,7 +396,7 @@ def test_placement_and_company(acc, small, llama1b, shape):
     """A chunk's picks, accepted, next token, logits of every chunk row and K / V do not depend on its batch row, on B or on which
     other rows are in the call -- "as in Part 2e", whose pass this is.  Part 2e's pass has ONE place where the call as a whole reaches
     a row's bits: with int4 g128 weights the decoder multiplies a prompt pass of at most 64 rows by its weight-streaming GEMM
-    (mc_pf2_gemm_i4_*, decoder.cc pf2_ok) and a longer one by the tiled GEMM, which add the K ranges in another order.  Both sides of
+    (mc_pf2_gemm_i4_*, prefill.cc pf2_ok) and a longer one by the tiled GEMM, which add the K ranges in another order.  Both sides of
     that line lie inside a verify call's 2 .. 128 rows, so with int4 weights the calls are compared among those on the same side
     (and the launch log must show that the sides are what this test takes them for); with plain bfloat16 weights there is no such
     line below 128 rows and every call is compared with every other."""

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Tuning aid: the prompt pass of the BASELINE model shape, alternating on one box, under the environments given (default: with / without the
-# dequantised bfloat16 copy of the quantised matrices, decoder.cc plain_copy_ok).   usage: tools/pf_copy_ab.sh [rounds=2] ["ENV=.. ENV=.." ...]
+# dequantised bfloat16 copy of the quantised matrices, prefill.cc plain_copy_ok).   usage: tools/pf_copy_ab.sh [rounds=2] ["ENV=.. ENV=.." ...]
 cd "${GRAFT_REPO_ROOT:-.}"
 R=${1:-2}; shift
 [ $# -eq 0 ] && set -- "MC_PF_PLAIN_COPY=1" "MC_PF_PLAIN_COPY=0"
