@@ -608,6 +608,42 @@ int32_t mc_rolling_enabled(const mc_batch* b); /* 0 for a null batch */
  * batch, a row out of range, dst == src. */
 mc_status mc_rolling_fork_row(mc_batch* b, int32_t dst, int32_t src);
 
+/* ================================================================================================
+ * Part 2k -- row samplers: each row of a batch picks with settings of its own.  A serving loop holds requests of different callers
+ * -- one greedy, one at temperature 0.6 / top-p 0.9, one at temperature 1.0 / top-k 20 -- and one batch serves them all over one
+ * pass of the weights.  A row slot is MC_SAMPLER_INHERIT (the default: it follows mc_decoder_set_sampler, read at every call, as
+ * before), MC_SAMPLER_GREEDY or MC_SAMPLER_DEFAULT with its own top_k, temperature and top_p.
+ *   settings   belong to the row SLOT and hold until set again or reset; they are read at every call, as the decoder's sampler is.
+ *              mc_batch_fork, mc_rolling_fork_row, imports and prompt passes leave them alone: a loop that refills a slot sets the
+ *              slot's sampler with it.  MC_SAMPLER_DEFAULT takes mc_decoder_set_sampler's checks, texts and rounding.
+ *   seeds      unchanged: token i of row r uses pair (i * B + r) % n_pairs (mc_batch_set_seeds).  A greedy row draws nothing; the
+ *              pair index of a row does not depend on the other rows' kinds.
+ *   the rows   the row contract extends to the sampler: a row's tokens, logits and K / V do not depend on B, on its index, or on
+ *              the other rows OR THEIR SAMPLERS, bit for bit.  Row r with settings X computes exactly what it computes in a batch
+ *              whose decoder-wide sampler is X.  Every pick of every batch call (Parts 2b - 2e, 2h - 2j) goes through it.
+ *   launches   no row samples: mc_b_argmax_*; all rows sample with equal settings: mc_b_topk_candidates_bfloat + mc_b_sample_*,
+ *              both as before -- a batch on which no row sampler is set (or after mc_row_sampler_reset) launches exactly what it
+ *              launched before this part.  Anything else: mc_b_topk_candidates_mixed_bfloat + mc_b_pick_mixed_*, which read a
+ *              [B] table of the effective settings and branch per row (DESIGN.md s.4 "Row samplers").
+ *   verify     mc_verify_rows and mc_tree_verify look at the EFFECTIVE sampler of the rows in the call (lens[r] > 0): a sampling
+ *              row outside the call no longer blocks the others, and a row set to MC_SAMPLER_GREEDY verifies under a sampling
+ *              decoder.  A row in the call that is not greedy is refused, nothing enqueued:
+ *                "mc_verify_rows: row r: the row's sampler is not greedy (accepting sampled drafts needs the draft's probabilities)"
+ *              (mc_tree_verify: its own prefix).  With no row sampler set the decoder-wide refusal keeps its text.
+ * Not covered: accepting sampled drafts, log-probabilities, samplers other than these two, top_k above 128, the batch-1 decoder.
+ * ------------------------------------------------------------------------------------------ */
+enum { MC_SAMPLER_INHERIT = -1 }; /* a row that follows mc_decoder_set_sampler: the default of every row */
+/* kind: MC_SAMPLER_INHERIT, MC_SAMPLER_GREEDY or MC_SAMPLER_DEFAULT; top_k, temperature and top_p are checked for MC_SAMPLER_DEFAULT
+ * only ("nucleus_sampler: temperature must be positive", "nucleus_sampler: probability must be in [0.0, 1.0]", "topk_sampler: the
+ * fused sampler keeps 1..128 candidates").  An unknown kind, a row outside [0, B) and a null batch are refused with texts prefixed
+ * "mc_row_sampler_set: ".  All MC_ERR_INVALID_ARGUMENT; a refused call launches nothing and changes nothing. */
+mc_status mc_row_sampler_set(mc_batch* b, int32_t row, int32_t kind, int32_t top_k, float temperature, float top_p);
+/* what was set: the caller's values, not the rounded ones.  An inheriting row: *kind = MC_SAMPLER_INHERIT and the other outputs
+ * untouched.  top_k, temperature and top_p may be null. */
+mc_status mc_row_sampler_get(const mc_batch* b, int32_t row, int32_t* kind, int32_t* top_k, float* temperature, float* top_p);
+/* every row back to MC_SAMPLER_INHERIT */
+mc_status mc_row_sampler_reset(mc_batch* b);
+
 /* Host-side helpers shared by tests and the synthetic initialiser. */
 /* value in [-7,7] (bits = 4) or [-127,127] (bits = 8), zero mean, of element (row, col) of matrix `matrix_id` */
 int32_t mc_synth_weight(uint64_t seed, uint32_t matrix_id, uint32_t row, uint32_t col, int32_t bits);

@@ -17,6 +17,8 @@
 // Part 2j (mc_rolling_set): the ragged rows of a batch decode past max_seq_len on nn::sink_cache's ring (nn/cache.h:187-204).
 // A row's ring state is a function of its position -- rows get past the end by single steps only -- so the batch keeps its lengths
 // and nothing else: mc_b_rows_begin_rolling derives the state and writes the row's rope row, every other launch is the ragged one.
+// Part 2k (mc_row_sampler_*): a row slot may pick with settings of its own in place of the decoder's; head() resolves every row's
+// effective sampler and keeps the uniform launches wherever the rows agree.
 #include "decoder_batch.h"
 
 #include <algorithm>
@@ -25,6 +27,8 @@
 #include <memory>
 
 using namespace mcimpl;
+
+static_assert(ROW_SAMPLER_GREEDY == MC_SAMPLER_GREEDY && ROW_SAMPLER_DEFAULT == MC_SAMPLER_DEFAULT, "row_sampler::kind carries the public kinds");
 
 struct mc_batch {
     mc_decoder* d = nullptr;
@@ -78,6 +82,16 @@ struct mc_batch {
     int v_xn_cap = 0, v_logits_cap = 0, v_out_cap = 0;
     int v_rows = 0;                       // packed rows of the last mc_verify_rows / mc_tree_verify call (0: none yet)
     std::vector<int32_t> v_host;
+    // Part 2k: the sampler of each row slot as mc_row_sampler_set took it (the caller's values, and rounded as the decoder rounds its
+    // own); the table of effective settings the mixed launches read, and what of it the device holds
+    struct row_setting {
+        int32_t kind = MC_SAMPLER_INHERIT, top_k = 0;
+        float temperature = 0.0f, top_p = 0.0f;
+        float inv_temp_T = 0.0f, top_p_T = 0.0f;
+    };
+    std::vector<row_setting> row_samplers; // [B]
+    row_sampler* samplers_dev = nullptr;   // [B]
+    std::vector<row_sampler> samplers_host, samplers_sent;
 
     ~mc_batch()
     {
@@ -264,8 +278,27 @@ struct mc_batch {
         return head(sfx);
     }
 
-    // the final norm of x, the head and the pick per row (greedy, or the decoder's default sampler); sfx "_rows_bfloat": rows
-    // whose rows[r].pos is -1 get no pick
+    // row r's effective sampler: its own (mc_row_sampler_set), or the decoder's while it inherits
+    decoder_sampler
+    sampler_of_row(int r, const decoder_sampler& dec) const
+    {
+        const row_setting& rs = row_samplers[r];
+        if (rs.kind == MC_SAMPLER_INHERIT) return dec;
+        decoder_sampler e;
+        e.kind = rs.kind;
+        e.top_k = rs.top_k;
+        e.inv_temp_T = rs.inv_temp_T;
+        e.top_p_T = rs.top_p_T;
+        return e;
+    }
+
+    // the final norm of x, the head and the pick per row, each row with its effective sampler; sfx "_rows_bfloat": rows whose
+    // rows[r].pos is -1 get no pick.  The pick takes the cheapest of three forms, chosen from the settings of ALL B rows (which
+    // rows go idle inside a chained call is not known here):
+    //   1  no row samples               mc_b_argmax
+    //   2  all sample, settings equal   mc_b_topk_candidates_bfloat + mc_b_sample with the plan of those settings
+    //   3  anything else                the two mixed launches over the table of effective settings
+    // 1 and 2 are what a batch without row samplers launches for the decoder's sampler, argument for argument
     mc_status
     head(const std::string& sfx)
     {
@@ -273,19 +306,68 @@ struct mc_batch {
         mc_status s;
         if ((s = rmsnorm(x, p.final_norm, xn)) != MC_OK) return s;
         if ((s = gemv(p.output, 0, xn, logits, (uint32_t)c.vocab)) != MC_OK) return s;
-        const decoder_sampler sm = decoder_sampler_of(d);
-        if (sm.kind == MC_SAMPLER_GREEDY)
-            return launch("mc_b_argmax" + sfx, 1, B, 1, 1024, 0, pack(logits, (uint32_t)c.vocab, rows, tokens_dev));
+        const decoder_sampler dec = decoder_sampler_of(d);
+        const decoder_sampler sm = sampler_of_row(0, dec);
+        int sampling = 0, top_k_max = 0;
+        bool alike = true;
+        samplers_host.resize(B);
+        for (int r = 0; r < B; r++) {
+            const decoder_sampler e = sampler_of_row(r, dec);
+            const bool samples = e.kind != MC_SAMPLER_GREEDY;
+            samplers_host[r] = samples ? row_sampler{ROW_SAMPLER_DEFAULT, (uint32_t)std::min(e.top_k, c.vocab), e.inv_temp_T, e.top_p_T}
+                                       : row_sampler{ROW_SAMPLER_GREEDY, 0u, 0.0f, 0.0f};
+            if (r > 0 && memcmp(&samplers_host[r], &samplers_host[0], sizeof(row_sampler)) != 0) alike = false;
+            if (!samples) continue;
+            sampling++;
+            top_k_max = std::max(top_k_max, e.top_k);
+        }
+        if (!sampling) return launch("mc_b_argmax" + sfx, 1, B, 1, 1024, 0, pack(logits, (uint32_t)c.vocab, rows, tokens_dev));
         // make_default_sampler per row (sampler_kernels.hip): per-chunk candidates, then one workgroup per row
+        const bool mixed = !alike;
         sampler_params sp;
         uint32_t chunk;
-        if ((s = sampler_plan(sm.top_k, c.vocab, sm.inv_temp_T, sm.top_p_T, &sp, &chunk)) != MC_OK) return s;
+        if ((s = sampler_plan(mixed ? top_k_max : sm.top_k, c.vocab, sm.inv_temp_T, sm.top_p_T, &sp, &chunk)) != MC_OK) return s;
         if ((size_t)sp.nlists * sp.kpad > cand_per_row)
             return fail(MC_ERR_RUNTIME, "sampler: the fused sampler handles rows of up to 2048 * 1024 logits");
-        s = launch("mc_b_topk_candidates_bfloat", sp.nlists, B, 1, 64, 0, pack(logits, (uint32_t)c.vocab, sp.kpad, cand, chunk));
+        if (!mixed) {
+            s = launch("mc_b_topk_candidates_bfloat", sp.nlists, B, 1, 64, 0, pack(logits, (uint32_t)c.vocab, sp.kpad, cand, chunk));
+            if (s != MC_OK) return s;
+            return launch("mc_b_sample" + sfx, 1, B, 1, 128, sp.cap * 8,
+                          pack(cand, sp, seeds, (uint32_t)n_seed_pairs, rows, tokens_dev));
+        }
+        // the table goes up when it differs from what the device holds: once per call (the settings cannot change inside one), and
+        // every call drains the stream before it returns, so samplers_sent is not touched while a copy reads it
+        if (samplers_sent.size() != samplers_host.size() ||
+            memcmp(samplers_sent.data(), samplers_host.data(), sizeof(row_sampler) * B) != 0) {
+            samplers_sent = samplers_host;
+            MC_HIP(hipMemcpyAsync(samplers_dev, samplers_sent.data(), sizeof(row_sampler) * B, hipMemcpyHostToDevice, p.stream));
+        }
+        const bool ragged = sfx == "_rows_bfloat";
+        s = launch("mc_b_topk_candidates_mixed_bfloat", sp.nlists, B, 1, 64, 0,
+                   pack(logits, (uint32_t)c.vocab, sp.kpad, cand, chunk, (const row_sampler*)samplers_dev, (const step_state*)rows,
+                        (int32_t)(ragged ? 1 : 0)));
         if (s != MC_OK) return s;
-        return launch("mc_b_sample" + sfx, 1, B, 1, 128, sp.cap * 8,
-                      pack(cand, sp, seeds, (uint32_t)n_seed_pairs, rows, tokens_dev));
+        return launch("mc_b_pick_mixed" + sfx, 1, B, 1, 1024, sp.cap * 8,
+                      pack(logits, (uint32_t)c.vocab, (const uint64_t*)cand, (const row_sampler*)samplers_dev, sp.nlists, sp.kpad, sp.cap,
+                           (const uint64_t*)seeds, (uint32_t)n_seed_pairs, rows, tokens_dev));
+    }
+
+    // mc_verify_rows / mc_tree_verify (`who`): every row in the call must pick greedily.  A batch without row samplers keeps the
+    // decoder-wide refusal and its text
+    mc_status
+    verify_samplers(const char* who, const int32_t* lens) const
+    {
+        const decoder_sampler dec = decoder_sampler_of(d);
+        const bool any_set = std::any_of(row_samplers.begin(), row_samplers.end(), [](const row_setting& r) { return r.kind != MC_SAMPLER_INHERIT; });
+        if (!any_set) {
+            if (dec.kind == MC_SAMPLER_GREEDY) return MC_OK;
+            return fail(MC_ERR_INVALID_ARGUMENT, std::string(who) + ": the decoder's sampler is not greedy (accepting sampled drafts needs the draft's probabilities)");
+        }
+        for (int r = 0; r < B; r++)
+            if (lens[r] > 0 && sampler_of_row(r, dec).kind != MC_SAMPLER_GREEDY)
+                return fail(MC_ERR_INVALID_ARGUMENT, std::string(who) + ": row " + std::to_string(r) +
+                                                         ": the row's sampler is not greedy (accepting sampled drafts needs the draft's probabilities)");
+        return MC_OK;
     }
 
     // mc_verify_rows: the final norm, the head and a greedy pick for each of the M packed rows `xrows` of a call, then per segment
@@ -538,6 +620,7 @@ batch_create(const std::string& who, int cap, bool wide, mc_decoder* d, int32_t 
     b->p = parts;
     b->B = batch;
     b->lengths.assign(batch, 0);
+    b->row_samplers.assign(batch, mc_batch::row_setting{});
     const mc_decoder_config& c = parts.cfg;
     const int H = c.n_heads, KV = c.n_kv_heads, hd = c.head_dim, L = (int)parts.layers.size();
     b->nsplit = (c.max_seq_len + PB - 1) / PB;
@@ -559,7 +642,8 @@ batch_create(const std::string& who, int cap, bool wide, mc_decoder* d, int32_t 
         (s = b->alloc(&b->rcos, sizeof(float) * batch * (hd / 2))) != MC_OK ||
         (s = b->alloc(&b->rsin, sizeof(float) * batch * (hd / 2))) != MC_OK ||
         (s = b->alloc(&b->st, sizeof(step_state))) != MC_OK || (s = b->alloc(&b->rows, sizeof(step_state) * batch)) != MC_OK ||
-        (s = b->alloc(&b->cand, sizeof(uint64_t) * batch * b->cand_per_row)) != MC_OK)
+        (s = b->alloc(&b->cand, sizeof(uint64_t) * batch * b->cand_per_row)) != MC_OK ||
+        (s = b->alloc(&b->samplers_dev, sizeof(row_sampler) * batch)) != MC_OK)
         return s;
     for (const batch_layer& l : parts.layers)
         for (const batch_linear* lin : {&l.qkv, &l.wo, &l.w13, &l.w2}) b->lora_ld = std::max(b->lora_ld, lin->lora_cols);
@@ -992,9 +1076,7 @@ mc_verify_rows(mc_batch* b, const int32_t* tokens, const int32_t* lens, const in
                int32_t* picks)
 {
     if (!b || !tokens || !lens || !positions || !accepted) return fail(MC_ERR_INVALID_ARGUMENT, "mc_verify_rows: null argument");
-    if (decoder_sampler_of(b->d).kind != MC_SAMPLER_GREEDY)
-        return fail(MC_ERR_INVALID_ARGUMENT,
-                    "mc_verify_rows: the decoder's sampler is not greedy (accepting sampled drafts needs the draft's probabilities)");
+    if (mc_status s = b->verify_samplers("mc_verify_rows", lens); s != MC_OK) return s;
     const verify_out v{accepted, picks};
     return rows_pass(b, "mc_verify_rows", true, tokens, lens, positions, next_tokens, &v);
 }
@@ -1006,9 +1088,7 @@ mc_tree_verify(mc_batch* b, const int32_t* tokens, const int32_t* parents, const
                int32_t* next_tokens, int32_t* paths, int32_t* picks)
 {
     if (!b || !tokens || !parents || !lens || !positions || !accepted) return fail(MC_ERR_INVALID_ARGUMENT, "mc_tree_verify: null argument");
-    if (decoder_sampler_of(b->d).kind != MC_SAMPLER_GREEDY)
-        return fail(MC_ERR_INVALID_ARGUMENT,
-                    "mc_tree_verify: the decoder's sampler is not greedy (accepting sampled drafts needs the draft's probabilities)");
+    if (mc_status s = b->verify_samplers("mc_tree_verify", lens); s != MC_OK) return s;
     const verify_out v{accepted, picks, parents, paths};
     return rows_pass(b, "mc_tree_verify", true, tokens, lens, positions, next_tokens, &v);
 }
@@ -1123,6 +1203,63 @@ mc_rolling_fork_row(mc_batch* b, int32_t dst, int32_t src)
     }
     MC_HIP(hipStreamSynchronize(b->p.stream));
     b->lengths[dst] = b->lengths[src];
+    return MC_OK;
+}
+
+// ---- Part 2k: row samplers ----
+
+mc_status
+mc_row_sampler_set(mc_batch* b, int32_t row, int32_t kind, int32_t top_k, float temperature, float top_p)
+{
+    if (!b) return fail(MC_ERR_INVALID_ARGUMENT, "mc_row_sampler_set: null argument");
+    if (row < 0 || row >= b->B) return fail(MC_ERR_INVALID_ARGUMENT, "mc_row_sampler_set: row out of range");
+    if (kind != MC_SAMPLER_INHERIT && kind != MC_SAMPLER_GREEDY && kind != MC_SAMPLER_DEFAULT)
+        return fail(MC_ERR_INVALID_ARGUMENT, "mc_row_sampler_set: unknown sampler");
+    mc_batch::row_setting rs;
+    if (kind == MC_SAMPLER_DEFAULT) {
+        // mc_decoder_set_sampler's checks and texts (nn/sampling.h:165-174), and its rounding (a batch is bfloat16)
+        if (!(temperature > 0.0f)) return fail(MC_ERR_INVALID_ARGUMENT, "nucleus_sampler: temperature must be positive");
+        if (top_p < 0.0f || top_p > 1.0f) return fail(MC_ERR_INVALID_ARGUMENT, "nucleus_sampler: probability must be in [0.0, 1.0]");
+        if (top_k < 1 || top_k > 128) return fail(MC_ERR_INVALID_ARGUMENT, "topk_sampler: the fused sampler keeps 1..128 candidates");
+        auto rt = [](float v) {
+            uint32_t u;
+            memcpy(&u, &v, 4);
+            if ((u & 0x7f800000u) == 0x7f800000u && (u & 0x007fffffu)) u |= 0x400000u; // (a NaN stays one)
+            else u += 0x7fffu + ((u >> 16) & 1u);
+            u &= 0xFFFF0000u;
+            memcpy(&v, &u, 4);
+            return v;
+        };
+        rs.inv_temp_T = rt(1.0f / rt(temperature)); // T temp = T(1) / _M_temperature  (sampling.h:190)
+        rs.top_p_T = rt(top_p);
+    }
+    rs.kind = kind;
+    rs.top_k = top_k;
+    rs.temperature = temperature;
+    rs.top_p = top_p;
+    b->row_samplers[row] = rs;
+    return MC_OK;
+}
+
+mc_status
+mc_row_sampler_get(const mc_batch* b, int32_t row, int32_t* kind, int32_t* top_k, float* temperature, float* top_p)
+{
+    if (!b || !kind) return fail(MC_ERR_INVALID_ARGUMENT, "mc_row_sampler_get: null argument");
+    if (row < 0 || row >= b->B) return fail(MC_ERR_INVALID_ARGUMENT, "mc_row_sampler_get: row out of range");
+    const mc_batch::row_setting& rs = b->row_samplers[row];
+    *kind = rs.kind;
+    if (rs.kind == MC_SAMPLER_INHERIT) return MC_OK;
+    if (top_k) *top_k = rs.top_k;
+    if (temperature) *temperature = rs.temperature;
+    if (top_p) *top_p = rs.top_p;
+    return MC_OK;
+}
+
+mc_status
+mc_row_sampler_reset(mc_batch* b)
+{
+    if (!b) return fail(MC_ERR_INVALID_ARGUMENT, "mc_row_sampler_reset: null argument");
+    b->row_samplers.assign(b->B, mc_batch::row_setting{});
     return MC_OK;
 }
 

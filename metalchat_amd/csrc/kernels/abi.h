@@ -59,6 +59,20 @@ struct sampler_params {
 };
 static_assert(sizeof(sampler_params) == 28 && alignof(sampler_params) == 4, "sampler_params is a by-value kernel argument");
 
+// ---- a batch row's own sampler (batch_kernels.hip mc_b_*_mixed_*; ABI Part 2k), one per row in a [B] device table ----
+// the EFFECTIVE settings, resolved on the host: a row that inherits carries the decoder's
+constexpr int32_t ROW_SAMPLER_GREEDY = 0;  // (= MC_SAMPLER_GREEDY) the first index of the maximum; the other words are not read
+constexpr int32_t ROW_SAMPLER_DEFAULT = 1; // (= MC_SAMPLER_DEFAULT) make_default_sampler with the three words below
+struct row_sampler {
+    int32_t kind;   // ROW_SAMPLER_*
+    uint32_t k;     // sampler_params::k
+    float inv_temp; // sampler_params::inv_temp
+    float top_p;    // sampler_params::top_p
+};
+static_assert(sizeof(row_sampler) == 16 && alignof(row_sampler) == 4 && offsetof(row_sampler, kind) == 0 && offsetof(row_sampler, k) == 4 &&
+                  offsetof(row_sampler, inv_temp) == 8 && offsetof(row_sampler, top_p) == 12,
+              "row_sampler: four words (read whole with one scalar load)");
+
 // ---- the descriptors a decode GEMV finds behind its `res` argument (gemv.h) ----
 // PRO_POSTNORM
 struct postnorm_args {

@@ -537,3 +537,59 @@ mc_b_sample_rows_bfloat(const uint64_t* cand, sampler_params p, const uint64_t* 
     sample_body<BF>(cand + (size_t)r * p.ncand, p, seeds, n_seed_pairs, rows + r, tokens_out,
                     nullptr);
 }
+
+// ------------------------------------------------------------------------------------------
+// Row samplers (mc_row_sampler_*, Part 2k): every row picks with settings of its own.  samplers[r] holds row r's EFFECTIVE
+// settings (abi.h row_sampler, resolved on the host: greedy or the default sampler, never "inherit").  The two launches are the
+// uniform ones with the branch on the row's kind in front -- uniform per workgroup, the row is a grid index -- so a greedy row
+// computes mc_b_argmax_*'s pick and a sampling row mc_b_sample_*'s:
+//   launch 1  the candidate lists of the sampling rows with the CALL's kpad, the largest among its sampling rows.  The lists are
+//             exact (list w = the kpad best keys of chunk w, best first), so a row's k best keys are among the first k of each
+//             list whatever kpad >= k is: a larger kpad only appends keys that launch 2 drops.  Workgroups of greedy rows
+//             (and, ragged, of idle rows) exit at once.
+//   launch 2  one workgroup of 1024 threads per row -- the argmax's block size.  sample_body guards every phase by tid (its
+//             strides take blockDim.x), and the k best of the keys it collects do not depend on how many threads collected them.
+// ------------------------------------------------------------------------------------------
+// ragged: rows[r].pos < 0 marks an idle row (the lockstep calls do not maintain .pos)
+extern "C" __global__ void __launch_bounds__(64)
+mc_b_topk_candidates_mixed_bfloat(const bf16_t* logits, uint32_t n, uint32_t kpad, uint64_t* cand, uint32_t chunk,
+                                  const row_sampler* samplers, const step_state* rows, int32_t ragged)
+{
+    const uint32_t r = blockIdx.y;
+    if (samplers[r].kind == ROW_SAMPLER_GREEDY || (ragged && row_idle(rows, r))) return;
+    const bf16_t* lr = logits + (size_t)r * n;
+    uint64_t* cr = cand + (size_t)r * gridDim.x * kpad;
+    if (chunk == 512) topk_candidates_body<BF, 8>(lr, n, kpad, cr);
+    else if (chunk == 1024) topk_candidates_body<BF, 16>(lr, n, kpad, cr);
+    else if (chunk == 2048) topk_candidates_body<BF, 32>(lr, n, kpad, cr);
+}
+
+// nlists, kpad, cap: of the call (sampler_params' words of the same names); dynamic LDS: cap keys
+__device__ __forceinline__ void
+pick_mixed_body(const bf16_t* logits, uint32_t n, const uint64_t* cand, const row_sampler* samplers, uint32_t nlists, uint32_t kpad,
+                uint32_t cap, const uint64_t* seeds, uint32_t n_seed_pairs, step_state* rows, int32_t* tokens_out)
+{
+    const uint32_t r = blockIdx.y;
+    const row_sampler s = samplers[r];
+    if (s.kind == ROW_SAMPLER_GREEDY) {
+        argmax_row_body(logits, n, rows, tokens_out);
+        return;
+    }
+    const sampler_params p{s.k, nlists * kpad, cap, s.inv_temp, s.top_p, nlists, kpad};
+    sample_body<BF>(cand + (size_t)r * p.ncand, p, seeds, n_seed_pairs, rows + r, tokens_out, nullptr);
+}
+extern "C" __global__ void __launch_bounds__(1024)
+mc_b_pick_mixed_bfloat(const bf16_t* logits, uint32_t n, const uint64_t* cand, const row_sampler* samplers, uint32_t nlists,
+                       uint32_t kpad, uint32_t cap, const uint64_t* seeds, uint32_t n_seed_pairs, step_state* rows, int32_t* tokens_out)
+{
+    pick_mixed_body(logits, n, cand, samplers, nlists, kpad, cap, seeds, n_seed_pairs, rows, tokens_out);
+}
+// an idle row gets no pick: nothing of rows[r] or tokens_out is written for it
+extern "C" __global__ void __launch_bounds__(1024)
+mc_b_pick_mixed_rows_bfloat(const bf16_t* logits, uint32_t n, const uint64_t* cand, const row_sampler* samplers, uint32_t nlists,
+                            uint32_t kpad, uint32_t cap, const uint64_t* seeds, uint32_t n_seed_pairs, step_state* rows,
+                            int32_t* tokens_out)
+{
+    if (row_idle(rows, blockIdx.y)) return;
+    pick_mixed_body(logits, n, cand, samplers, nlists, kpad, cap, seeds, n_seed_pairs, rows, tokens_out);
+}

@@ -631,8 +631,12 @@ sample_body(const uint64_t* cand, sampler_params p, const uint64_t* seeds, uint3
         pv x[2];
 #pragma unroll
         for (int r = 0; r < 2; r++) x[r] = pv{srt[2 * tid + r], sidx[2 * tid + r]};
-        // (kernel/sort.metal's strict compares: equal values stay where they are)
-        wave_bitonic<2>(x, tid, aligned, [](const pv& a, const pv& o, bool first) { return (first ? a.v < o.v : a.v > o.v) ? o : a; });
+        // (kernel/sort.metal's strict compares: equal values stay where they are.  The two words are selected one by one: `take ? o : a`
+        // on the structs selects an ADDRESS, and the slots then live in private memory -- 48 bytes of it in every kernel with this body)
+        wave_bitonic<2>(x, tid, aligned, [](const pv& a, const pv& o, bool first) {
+            const bool take = first ? a.v < o.v : a.v > o.v;
+            return pv{take ? o.v : a.v, take ? o.i : a.i};
+        });
 #pragma unroll
         for (int r = 0; r < 2; r++) {
             srt[2 * tid + r] = x[r].v;

@@ -51,6 +51,7 @@ class TensorInfo(C.Structure):
 
 CKPT_META_LLAMA3, CKPT_HF_LLAMA3, CKPT_META_LLAMA3_QLORA, CKPT_HF_GEMMA3 = 0, 1, 2, 3
 SAMPLER_GREEDY, SAMPLER_DEFAULT = 0, 1
+SAMPLER_INHERIT = -1  # a batch row that follows the decoder's sampler (Batch.set_row_sampler)
 
 _lib = None
 
@@ -208,6 +209,9 @@ def capi() -> C.CDLL:
         "mc_rolling_set": (i32, [vp, i32]),
         "mc_rolling_enabled": (i32, [vp]),
         "mc_rolling_fork_row": (i32, [vp, i32, i32]),
+        "mc_row_sampler_set": (i32, [vp, i32, i32, i32, C.c_float, C.c_float]),
+        "mc_row_sampler_get": (i32, [vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(f32), C.POINTER(f32)]),
+        "mc_row_sampler_reset": (i32, [vp]),
         "mc_rows_prefill": (i32, [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
         "mc_extend_rows": (i32, [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
         "mc_verify_rows": (i32, [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
@@ -976,6 +980,25 @@ class Batch:
         _check(capi().mc_verify_get_logits(self._h, _np_ptr(out)))
         off = np.concatenate([[0], np.cumsum(lens)])
         return [out[off[r]:off[r + 1]] if lens[r] else None for r in range(self.B)]
+
+    # ---- row samplers (Part 2k): each row slot picks with settings of its own
+
+    def set_row_sampler(self, row: int, kind: int, top_k: int = 50, temperature: float = 0.6, top_p: float = 0.9):
+        """kind: SAMPLER_INHERIT (follow the decoder's sampler, the default of every row), SAMPLER_GREEDY or SAMPLER_DEFAULT with
+        the row's own top_k / temperature / top_p.  Belongs to the row slot until set again or reset."""
+        _check(capi().mc_row_sampler_set(self._h, row, kind, top_k, temperature, top_p))
+
+    def row_sampler(self, row: int):
+        """(kind, top_k, temperature, top_p) as set -- the caller's values; (SAMPLER_INHERIT, None, None, None) for a row that inherits"""
+        kind, top_k, temperature, top_p = C.c_int32(), C.c_int32(), C.c_float(), C.c_float()
+        _check(capi().mc_row_sampler_get(self._h, row, C.byref(kind), C.byref(top_k), C.byref(temperature), C.byref(top_p)))
+        if kind.value == SAMPLER_INHERIT:
+            return SAMPLER_INHERIT, None, None, None
+        return kind.value, top_k.value, temperature.value, top_p.value
+
+    def reset_row_samplers(self):
+        """every row back to SAMPLER_INHERIT"""
+        _check(capi().mc_row_sampler_reset(self._h))
 
     def set_seeds(self, pairs):
         a = np.ascontiguousarray(np.asarray(pairs, dtype=np.uint64).reshape(-1, 2))
