@@ -24,7 +24,7 @@ KERNEL_SOURCES = [os.path.join(CSRC, "kernels", f) for f in (
 # the host library: every unit goes into the one hipcc command, units and headers together are what makes it stale
 HOST_UNITS = [os.path.join(CSRC, f) for f in ("backend.cc", "decoder.cc", "weights.cc", "prefill.cc", "prefill_blaslt.cc", "pipeline.cc", "batch.cc",
                                                "model_io.cc", "text.cc")]
-HOST_HEADERS = [os.path.join(CSRC, f) for f in ("json_min.h", "backend_impl.h", "decoder_impl.h", "decoder_batch.h", "decoder_options.h", "gemv_plan.h")] + [
+HOST_HEADERS = [os.path.join(CSRC, f) for f in ("json_min.h", "backend_impl.h", "decoder_impl.h", "decoder_batch.h", "decoder_options.h", "gemv_plan.h", "prefill_plan.h", "rows_plan.h")] + [
     os.path.join(CSRC, "kernels", "synth.h"), os.path.join(CSRC, "kernels", "abi.h"),
     os.path.join(os.path.dirname(HERE), "include", "metalchat_hip.h")]
 
@@ -64,60 +64,55 @@ def build_host(force: bool = False) -> str:
     return SO
 
 
-def build_shim_test(force: bool = False) -> str:
-    """tests/cpp/test_shim: a plain g++ program over include/metalchat_hip.hpp -- host code above
-    the C ABI needs no HIP headers."""
+def _build_cpp_test(name: str, headers, force: bool, link_host: bool) -> str:
+    """tests/cpp/<name>: a plain g++ program (no HIP headers), rebuilt when its source or one of `headers` is newer.  link_host: a program above
+    the C ABI, linked against the host library; otherwise it stands on device-free headers alone and is compiled with -Wall."""
     root = os.path.dirname(HERE)
-    src = os.path.join(root, "tests", "cpp", "test_shim.cc")
-    out = os.path.join(root, "tests", "cpp", "test_shim")
-    deps = [src, os.path.join(root, "include", "metalchat_hip.hpp"),
-            os.path.join(root, "include", "metalchat_hip.h"), SO]
-    if force or _stale(out, deps):
-        subprocess.check_call(["g++", "-std=c++17", "-O1", "-I" + os.path.join(root, "include"), src,
-                               "-o", out, "-L" + LIB, "-lmetalchat_hip",
-                               "-Wl,-rpath," + LIB, "-Wl,-rpath,/opt/rocm/lib", "-pthread"])
+    src = os.path.join(root, "tests", "cpp", name + ".cc")
+    out = os.path.join(root, "tests", "cpp", name)
+    if force or _stale(out, [src, *headers] + ([SO] if link_host else [])):
+        cmd = ["g++", "-std=c++17", "-O1"]
+        if link_host:
+            cmd += ["-I" + os.path.join(root, "include"), src, "-o", out, "-L" + LIB, "-lmetalchat_hip", "-Wl,-rpath," + LIB, "-Wl,-rpath,/opt/rocm/lib", "-pthread"]
+        else:
+            cmd += ["-Wall", src, "-o", out]
+        subprocess.check_call(cmd)
     return out
+
+
+_ABI_HEADERS = [os.path.join(os.path.dirname(HERE), "include", f) for f in ("metalchat_hip.hpp", "metalchat_hip.h")]
+_PLAN_HEADERS = [os.path.join(CSRC, "gemv_plan.h"), os.path.join(CSRC, "decoder_options.h"), _ABI_HEADERS[1]]
+
+
+def build_shim_test(force: bool = False) -> str:
+    """tests/cpp/test_shim: a plain g++ program over include/metalchat_hip.hpp -- host code above the C ABI needs no HIP headers."""
+    return _build_cpp_test("test_shim", _ABI_HEADERS, force, True)
 
 
 def build_model_io_test(force: bool = False) -> str:
     """tests/cpp/test_model_io: host-only C++ test of the document / options part of the ABI."""
-    root = os.path.dirname(HERE)
-    src = os.path.join(root, "tests", "cpp", "test_model_io.cc")
-    out = os.path.join(root, "tests", "cpp", "test_model_io")
-    deps = [src, os.path.join(root, "include", "metalchat_hip.hpp"),
-            os.path.join(root, "include", "metalchat_hip.h"), SO]
-    if force or _stale(out, deps):
-        subprocess.check_call(["g++", "-std=c++17", "-O1", "-I" + os.path.join(root, "include"), src,
-                               "-o", out, "-L" + LIB, "-lmetalchat_hip",
-                               "-Wl,-rpath," + LIB, "-Wl,-rpath,/opt/rocm/lib", "-pthread"])
-    return out
+    return _build_cpp_test("test_model_io", _ABI_HEADERS, force, True)
 
 
 def build_text_test(force: bool = False) -> str:
     """tests/cpp/test_text: host-only C++ test of the text / interpreter-framing classes of the shim."""
-    root = os.path.dirname(HERE)
-    src = os.path.join(root, "tests", "cpp", "test_text.cc")
-    out = os.path.join(root, "tests", "cpp", "test_text")
-    deps = [src, os.path.join(root, "include", "metalchat_hip.hpp"),
-            os.path.join(root, "include", "metalchat_hip.h"), SO]
-    if force or _stale(out, deps):
-        subprocess.check_call(["g++", "-std=c++17", "-O1", "-I" + os.path.join(root, "include"), src,
-                               "-o", out, "-L" + LIB, "-lmetalchat_hip",
-                               "-Wl,-rpath," + LIB, "-Wl,-rpath,/opt/rocm/lib", "-pthread"])
-    return out
+    return _build_cpp_test("test_text", _ABI_HEADERS, force, True)
 
 
+# The three plan programs are no part of build_all(): nothing of the package needs them, their CPU tests build them (a second or two) when they run.
 def build_gemv_plan_test(force: bool = False) -> str:
-    """tests/cpp/test_gemv_plan: plan_gemv() (csrc/gemv_plan.h) from the command line -- a plain g++ program, no HIP and no host library.
-    Not part of build_all(): nothing of the package needs it, tests/test_gemv_plan_cpu.py builds it (a second or two) when it runs."""
-    root = os.path.dirname(HERE)
-    src = os.path.join(root, "tests", "cpp", "test_gemv_plan.cc")
-    out = os.path.join(root, "tests", "cpp", "test_gemv_plan")
-    deps = [src, os.path.join(CSRC, "gemv_plan.h"), os.path.join(CSRC, "decoder_options.h"),
-            os.path.join(root, "include", "metalchat_hip.h")]
-    if force or _stale(out, deps):
-        subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", src, "-o", out])
-    return out
+    """tests/cpp/test_gemv_plan: plan_gemv() (csrc/gemv_plan.h) from the command line -- no HIP and no host library."""
+    return _build_cpp_test("test_gemv_plan", _PLAN_HEADERS, force, False)
+
+
+def build_prefill_plan_test(force: bool = False) -> str:
+    """tests/cpp/test_prefill_plan: the prompt plan (csrc/prefill_plan.h) from the command line -- no HIP and no host library."""
+    return _build_cpp_test("test_prefill_plan", [os.path.join(CSRC, "prefill_plan.h"), *_PLAN_HEADERS], force, False)
+
+
+def build_rows_plan_test(force: bool = False) -> str:
+    """tests/cpp/test_rows_plan: the tables of the rows passes (csrc/rows_plan.h) from the command line -- no HIP and no host library."""
+    return _build_cpp_test("test_rows_plan", [os.path.join(CSRC, "rows_plan.h"), os.path.join(CSRC, "kernels", "abi.h")], force, False)
 
 
 def build_all(force: bool = False):

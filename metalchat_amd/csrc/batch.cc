@@ -142,10 +142,6 @@ struct mc_batch {
         return decoder_launch(d, name, gx, gy, gz, bx, lds, std::move(a));
     }
 
-    // the two tables inside pp_tab / pp_host.data()
-    static pp_seg* pp_segs(char* tab) { return reinterpret_cast<pp_seg*>(tab); }
-    static pp_tile* pp_tiles(char* tab) { return reinterpret_cast<pp_tile*>(tab + sizeof(pp_seg) * MC_WIDE_BATCH_MAX); }
-    static tv_node* tv_nodes(char* tab, int ntiles) { return reinterpret_cast<tv_node*>(pp_tiles(tab) + ntiles); }
 
     char* kc_of(int layer, int row) const { return (char*)kc + ((size_t)layer * B + row) * cache_elems * 2; }
     char* vt_of(int layer, int row) const { return (char*)vt + ((size_t)layer * B + row) * cache_elems * 2; }
@@ -429,14 +425,9 @@ struct mc_batch {
         return MC_OK;
     }
 
-    // a row whose length exceeds max_seq_len has rolled: its evicted positions are gone, so it is continued at its length or
-    // restarted at 0 and nothing between ("" = fine, else the refusal behind the row's name)
+    // (rows_plan.h: a row that has rolled is continued at its length or restarted at 0)
     std::string
-    rolled_rewind(int r, int64_t pos) const
-    {
-        if (lengths[r] <= p.cfg.max_seq_len || pos == 0 || pos >= lengths[r]) return "";
-        return "position " + std::to_string(pos) + " lies below the row's length " + std::to_string(lengths[r]) + " and the row has rolled";
-    }
+    rolled_rewind(int r, int64_t pos) const { return mcimpl::rolled_rewind(lengths[r], p.cfg.max_seq_len, pos); }
 
     // a ragged call's positions and tokens: -1 = idle, else 0 <= pos <= the row's length and pos < max_seq_len (a rolling batch:
     // any pos, as long as the n steps of the call stay inside int32), with a token of the vocabulary; at least one row active
@@ -816,103 +807,6 @@ mc_batch_get_logits(mc_batch* b, void* logits_T)
 
 namespace {
 
-// How mc_extend_rows' attention deals the keys [0, S) of a 16-row tile over workgroups (kernels/extend_kernels.hip): the size of
-// a key range, a multiple of 128; S or more = one range.  The rule looks at the tile's own segment only -- never at what else is
-// in the call -- so that a row's bits depend on nothing but the row: a segment of at most two tiles (a short message) behind more
-// than 512 keys brings too few workgroups for its keys and takes two ranges; every other tile has one (measured: DESIGN.md
-// "Chunks that see their context").  MC_PX_KEYS is the experiment's handle: N = ranges of N keys for every tile, 0 = never split.
-int
-px_range_keys(int S, int len)
-{
-    if (const char* e = getenv("MC_PX_KEYS")) {
-        const int keys = atoi(e);
-        return keys <= 0 ? S : (keys + 127) / 128 * 128;
-    }
-    return len <= 32 && S > 512 ? ((S + 1) / 2 + 127) / 128 * 128 : S;
-}
-// the most ranges a tile can have in a cache of max_seq slots
-int
-px_ranges_max(int max_seq)
-{
-    const int keys = px_range_keys(max_seq, 2);
-    return (max_seq + keys - 1) / keys;
-}
-
-// step 1 of rows_pass: the call's lengths, positions and tokens against the rows' caches; counts its packed rows, segments and tiles
-mc_status
-rows_check(const mc_batch* b, const std::string& who, const int32_t* tokens, const int32_t* lens, const int32_t* positions, int* M, int* nseg,
-           int* ntiles)
-{
-    const mc_decoder_config& c = b->p.cfg;
-    int64_t total = 0;
-    *nseg = *ntiles = 0;
-    for (int r = 0; r < b->B; r++) {
-        const std::string row = who + ": row " + std::to_string(r) + ": ";
-        const int32_t len = lens[r], pos = positions[r];
-        if (len < 0) return fail(MC_ERR_INVALID_ARGUMENT, row + "length below 0 (0 = the row is not in the call)");
-        if (len == 0) continue;
-        if (len == 1) return fail(MC_ERR_INVALID_ARGUMENT, row + "a one-token chunk is a step: mc_ragged_step");
-        if (pos < 0) return fail(MC_ERR_INVALID_ARGUMENT, row + "position below 0");
-        if (pos > b->lengths[r])
-            return fail(MC_ERR_INVALID_ARGUMENT, row + "position " + std::to_string(pos) + " is past the row's length " +
-                                                     std::to_string(b->lengths[r]) + " (its cache has no slots written beyond it)");
-        if ((int64_t)pos + len > c.max_seq_len)
-            return fail(MC_ERR_INVALID_ARGUMENT, row + "position + length " + std::to_string((int64_t)pos + len) +
-                                                     " exceeds max_seq_len (a batch's cache does not roll)");
-        if (const std::string why = b->rolled_rewind(r, pos); !why.empty()) return fail(MC_ERR_INVALID_ARGUMENT, row + why);
-        for (int32_t i = 0; i < len; i++)
-            if (tokens[total + i] < 0 || tokens[total + i] >= c.vocab)
-                return fail(MC_ERR_INVALID_ARGUMENT, row + "token id outside the vocabulary");
-        total += len;
-        (*nseg)++;
-        *ntiles += (len + PP_TILE_ROWS - 1) / PP_TILE_ROWS;
-    }
-    if (*nseg == 0) return fail(MC_ERR_INVALID_ARGUMENT, who + ": no row in the call (every length is 0)");
-    if (total > c.max_seq_len)
-        return fail(MC_ERR_INVALID_ARGUMENT, who + ": the rows' lengths add up to " + std::to_string(total) +
-                                                 ", more than max_seq_len (" + std::to_string(c.max_seq_len) + "): split the call by rows");
-    *M = (int)total;
-    return MC_OK;
-}
-
-// step 2: the rows' states, the segment table (packed in row order) and the ntiles attention tiles of the segments
-void
-rows_tables(mc_batch* b, const int32_t* lens, const int32_t* positions, int ntiles)
-{
-    b->rows_host.assign(b->B, step_state{});
-    b->pp_host.assign(sizeof(pp_seg) * MC_WIDE_BATCH_MAX + sizeof(pp_tile) * ntiles, 0);
-    pp_seg* seg = mc_batch::pp_segs(b->pp_host.data());
-    pp_tile* tile = mc_batch::pp_tiles(b->pp_host.data());
-    for (int r = 0, off = 0, si = 0; r < b->B; r++) {
-        b->rows_host[r].pos = lens[r] > 0 ? positions[r] : -1;
-        b->rows_host[r].token = -1;
-        b->rows_host[r].step_index = r; // seed pair r % n_pairs, next_tokens[r]
-        if (lens[r] == 0) continue;
-        for (int t = 0; t < lens[r]; t += PP_TILE_ROWS) *tile++ = {si, t};
-        seg[si++] = {r, positions[r], off, lens[r]};
-        off += lens[r];
-    }
-}
-
-// step 3 (mc_extend_rows): the range table -- the keys [0, pos + last row of the tile] of every tile in ranges of px_range_keys --
-// and the launch groups: whole tiles, at most `slots` ranges each
-void
-rows_ranges(mc_batch* b, int ntiles, int slots)
-{
-    b->px_host.clear();
-    b->px_groups.clear();
-    for (int ti = 0; ti < ntiles; ti++) {
-        const pp_tile t = mc_batch::pp_tiles(b->pp_host.data())[ti];
-        const pp_seg g = mc_batch::pp_segs(b->pp_host.data())[t.seg];
-        const int S = g.pos + std::min(t.r0 + PP_TILE_ROWS, g.len), keys = px_range_keys(S, g.len), n = (S + keys - 1) / keys;
-        const int first = (int)b->px_host.size();
-        if (b->px_groups.empty() || b->px_groups.back().count + n > slots) b->px_groups.push_back({first, 0, false});
-        b->px_groups.back().count += n;
-        if (n > 1) b->px_groups.back().split = true;
-        for (int k = 0; k < n; k++) b->px_host.push_back({t.seg, t.r0, k * keys, std::min((k + 1) * keys, S), first, n, 0, 0});
-    }
-}
-
 // what mc_verify_rows adds to the pass: a pick after every chunk row and the acceptance (next_tokens is the pass's own argument)
 struct verify_out {
     int32_t* accepted; // [B]
@@ -922,33 +816,6 @@ struct verify_out {
     int32_t* paths = nullptr;         // [B][MC_VERIFY_MAX_LEN], may be null
 };
 
-// mc_tree_verify: every row's `parents` (root -1, then 0 <= parent < i), and the node table behind the tiles of pp_host
-mc_status
-tree_check(const mc_batch* b, const std::string& who, const int32_t* parents, const int32_t* lens)
-{
-    for (int r = 0, off = 0; r < b->B; off += lens[r], r++) {
-        const std::string row = who + ": row " + std::to_string(r) + ": ";
-        if (lens[r] == 0) continue;
-        if (parents[off] != -1) return fail(MC_ERR_INVALID_ARGUMENT, row + "the parent of node 0 (the root) must be -1, not " + std::to_string(parents[off]));
-        for (int32_t i = 1; i < lens[r]; i++)
-            if (parents[off + i] < 0 || parents[off + i] >= i)
-                return fail(MC_ERR_INVALID_ARGUMENT, row + "the parent of node " + std::to_string(i) + " is " + std::to_string(parents[off + i]) +
-                                                         ", outside [0, " + std::to_string(i) + ") (nodes come in topological order)");
-    }
-    return MC_OK;
-}
-void
-tree_nodes(mc_batch* b, const int32_t* parents, const int32_t* lens, int ntiles, int M)
-{
-    b->pp_host.resize(b->pp_host.size() + sizeof(tv_node) * M);
-    tv_node* node = mc_batch::tv_nodes(b->pp_host.data(), ntiles);
-    for (int r = 0, off = 0; r < b->B; off += lens[r], r++)
-        for (int32_t i = 0; i < lens[r]; i++) {
-            const int32_t par = parents[off + i];
-            node[off + i] = i == 0 ? tv_node{0, 1u} : tv_node{node[off + par].depth + 1, node[off + par].anc | (1u << i)};
-        }
-}
-
 // mc_rows_prefill, mc_extend_rows, mc_verify_rows and mc_tree_verify: one body, `extend` selects the attention (and `who` the
 // texts), `v` the head over every packed row in place of the head over each row's last, v->parents the tree form of that
 mc_status
@@ -957,34 +824,29 @@ rows_pass(mc_batch* b, const char* who, bool extend, const int32_t* tokens, cons
 {
     const mc_decoder_config& c = b->p.cfg;
     const int B = b->B;
-    int M = 0, nseg = 0, ntiles = 0;
-    mc_status s = rows_check(b, who, tokens, lens, positions, &M, &nseg, &ntiles);
-    if (s != MC_OK) return s;
-    if (v)
-        for (int r = 0; r < B; r++)
-            if (lens[r] > MC_VERIFY_MAX_LEN)
-                return fail(MC_ERR_INVALID_ARGUMENT, std::string(who) + ": row " + std::to_string(r) + ": a chunk of " + std::to_string(lens[r]) +
-                                                         " tokens is longer than MC_VERIFY_MAX_LEN (" + std::to_string(MC_VERIFY_MAX_LEN) + ")");
-    // (eight rows of at most 16 tokens never get here; a wide batch can: mc_v_head_* holds MC_VERIFY_MAX_ROWS rows)
-    if (v && M > MC_VERIFY_MAX_ROWS)
-        return fail(MC_ERR_INVALID_ARGUMENT, std::string(who) + ": the chunks add up to " + std::to_string(M) + " rows, more than MC_VERIFY_MAX_ROWS (" +
-                                                 std::to_string(MC_VERIFY_MAX_ROWS) + "): split the call by rows");
+    // check (rows_plan.h: the admission, the tables and the scratch sizes are plain arithmetic there), tables, upload, prompt pass, head
     const bool tree = v && v->parents;
-    if (tree && (s = tree_check(b, who, v->parents, lens)) != MC_OK) return s;
+    const rows_counts n = rows_check(who, tokens, lens, positions, b->lengths.data(), B, c.max_seq_len, c.vocab, v != nullptr);
+    if (!n.refusal.empty()) return fail(MC_ERR_INVALID_ARGUMENT, n.refusal);
+    if (tree)
+        if (const std::string why = tree_check(who, v->parents, lens, B); !why.empty()) return fail(MC_ERR_INVALID_ARGUMENT, why);
+    const int M = n.M, nseg = n.nseg, ntiles = n.ntiles;
+    // MC_PX_KEYS, the experiment's handle on the key ranges, is read at the call (the tests set it between calls on a live batch)
+    const char* keys_env = getenv("MC_PX_KEYS");
+    const int keys_override = keys_env ? std::max(atoi(keys_env), 0) : PX_KEYS_RULE;
+    const rows_scratch sc = rows_scratch_of(c.max_seq_len, c.n_heads, c.head_dim, keys_override);
+    mc_status s;
     MC_HIP(hipSetDevice(b->p.ordinal));
-    rows_tables(b, lens, positions, ntiles);
-    if (tree) tree_nodes(b, v->parents, lens, ntiles, M);
-    // (enough for any call: at most max_seq_len rows in at most MC_WIDE_BATCH_MAX segments, one per row of the batch)
-    const int tiles_max = c.max_seq_len / PP_TILE_ROWS + MC_WIDE_BATCH_MAX;
-    if ((s = b->reserve(b->pp_tab, b->pp_tab_cap, (int)b->pp_host.size(), (int)(sizeof(pp_seg) * MC_WIDE_BATCH_MAX + sizeof(pp_tile) * tiles_max + sizeof(tv_node) * MC_VERIFY_MAX_ROWS))) != MC_OK)
-        return s;
+    rows_tables(lens, positions, B, ntiles, b->rows_host, b->pp_host);
+    if (tree) tree_nodes(v->parents, lens, B, ntiles, M, b->pp_host);
+    if ((s = b->reserve(b->pp_tab, b->pp_tab_cap, (int)b->pp_host.size(), (int)sc.tab_bytes())) != MC_OK) return s;
     MC_HIP(hipMemcpyAsync(b->pp_tab, b->pp_host.data(), b->pp_host.size(), hipMemcpyHostToDevice, b->p.stream));
     packed_prefill pk;
-    pk.segs = mc_batch::pp_segs(b->pp_tab);
+    pk.segs = pp_segs(b->pp_tab);
     pk.nseg = nseg;
-    pk.tiles = mc_batch::pp_tiles(b->pp_tab);
+    pk.tiles = pp_tiles(b->pp_tab);
     pk.ntiles = ntiles;
-    if (tree) pk.nodes = mc_batch::tv_nodes(b->pp_tab, ntiles);
+    if (tree) pk.nodes = tv_nodes(b->pp_tab, ntiles);
     MC_HIP(hipMemcpyAsync(b->rows, b->rows_host.data(), sizeof(step_state) * B, hipMemcpyHostToDevice, b->p.stream));
     if ((s = b->ensure_tokens(1)) != MC_OK) return s;
     MC_HIP(hipMemsetAsync(b->tokens_dev, 0xFF, sizeof(int32_t) * B, b->p.stream));
@@ -996,17 +858,13 @@ rows_pass(mc_batch* b, const char* who, bool extend, const int32_t* tokens, cons
     pk.fsin = b->fsin;
     pk.x_out = b->x;
     if (extend) {
-        // scratch for one launch group, sized once: 64 MiB of partial outputs, and never less than one tile's ranges
-        const int per_tile = px_ranges_max(c.max_seq_len);
-        const size_t per_slot = (size_t)c.n_heads * PP_TILE_ROWS * c.head_dim * sizeof(float);
-        const int slots = (int)std::min<size_t>(32768, std::max<size_t>((size_t)per_tile, ((size_t)64 << 20) / per_slot));
+        // scratch for one launch group, sized once (rows_scratch_of)
         int sums_slots = b->px_slots;
-        if ((s = b->reserve(b->px_sums, sums_slots, per_tile, slots, sizeof(float) * c.n_heads * PP_TILE_ROWS)) != MC_OK ||
-            (s = b->reserve(b->px_part, b->px_slots, per_tile, slots, per_slot)) != MC_OK)
+        if ((s = b->reserve(b->px_sums, sums_slots, sc.per_tile, sc.slots, sizeof(float) * c.n_heads * PP_TILE_ROWS)) != MC_OK ||
+            (s = b->reserve(b->px_part, b->px_slots, sc.per_tile, sc.slots, sc.per_slot)) != MC_OK)
             return s;
-        rows_ranges(b, ntiles, b->px_slots);
-        // (enough for any call: every tile of the largest call with the most ranges a tile can have)
-        if ((s = b->reserve(b->px_tab, b->px_tab_cap, (int)b->px_host.size(), tiles_max * per_tile)) != MC_OK) return s;
+        rows_ranges(b->pp_host, ntiles, b->px_slots, keys_override, b->px_host, b->px_groups);
+        if ((s = b->reserve(b->px_tab, b->px_tab_cap, (int)b->px_host.size(), sc.tiles_max * sc.per_tile)) != MC_OK) return s;
         MC_HIP(hipMemcpyAsync(b->px_tab, b->px_host.data(), sizeof(px_range) * b->px_host.size(), hipMemcpyHostToDevice, b->p.stream));
         pk.extend = true;
         pk.ranges = b->px_tab;

@@ -5,6 +5,7 @@
 
 #include "backend_impl.h"
 #include "kernels/abi.h"
+#include "rows_plan.h" // the tables of the packed prompt pass as the host builds them
 
 namespace mcimpl {
 
@@ -65,11 +66,7 @@ mc_status sampler_plan(int top_k, int vocab, float inv_temp_T, float top_p_T, sa
 
 // The packed prompt pass (mc_rows_prefill and mc_extend_rows, kernels/packed_kernels.hip): the chunks of several sequences as one prompt pass of
 // M = sum of their lengths rows.  The tables are on the device already (uploaded on the decoder's stream).
-// a launch group of mc_extend_rows: whole tiles, at most as many ranges as the scratch has slots
-struct px_group {
-    int first = 0, count = 0; // its ranges: [first, first + count) of the range table
-    bool split = false;       // a tile of the group has several ranges (their partial outputs want mc_px_reduce)
-};
+// (px_group, a launch group of mc_extend_rows: rows_plan.h)
 struct packed_prefill {
     const pp_seg* segs = nullptr;   // [nseg]: the rows in the call, offsets ascending
     int nseg = 0;

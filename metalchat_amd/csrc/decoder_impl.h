@@ -3,15 +3,18 @@
 // declarations of everything else.  Which unit defines what:
 //   decoder.cc         the decode block plan (plan_block), the per-token decode, the hand-off fall-back, the C ABI of a step
 //   weights.cc         allocation and upload of the fused matrices, the synthetic model
-//   prefill.cc         the prompt pass (plan_gemm, run_prefill)
+//   prefill.cc         the prompt pass (run_prefill): it launches what prefill_plan.h plans -- GEMM family, attention, rope form, folds; no HIP there
 //   prefill_blaslt.cc  the library GEMM of long prompts -- the only unit that sees hipBLASLt's header
 //   pipeline.cc        the layer pipeline (RCCL / local); it holds decoders, it is not part of one
-// batch.cc does not include this header: it reads a decoder through decoder_batch.h.
+// batch.cc does not include this header: it reads a decoder through decoder_batch.h.  Three headers beside the units need no device and are pinned
+// on the CPU by plain g++ programs (tests/cpp): gemv_plan.h (the decode GEMV), prefill_plan.h (the prompt pass) and rows_plan.h (the admission
+// and the tables of batch.cc's rows passes).
 #pragma once
 
 #include "backend_impl.h"
 #include "decoder_batch.h"
 #include "gemv_plan.h" // decoder_options / read_options (decoder_options.h) and plan_gemv
+#include "prefill_plan.h" // plan_gemm, plan_attention, plan_rope and the fold predicates of the prompt pass
 
 #include <algorithm>
 #include <climits>
@@ -473,31 +476,22 @@ struct mc_decoder {
     mc_status run_head();
     mc_status run_token(const void* hidden_src, bool advance = false);
 
-    // ---------------------------------------------------------------- prompt pass (prefill.cc; lib_ok and gemm_lib: prefill_blaslt.cc)
+    // ---------------------------------------------------------------- prompt pass (prefill.cc; gemm_lib: prefill_blaslt.cc)
+    // what the prompt pass launches is decided in prefill_plan.h, over this view of the decoder; the members here touch the device
+    prefill_env
+    penv() const
+    {
+        return {tb, (int)cfg.qmode, (int)cfg.family, (unsigned)dev->prop.multiProcessorCount, cfg.dim, cfg.ffn_dim, cfg.n_heads, cfg.n_kv_heads, cfg.head_dim,
+                cfg.max_seq_len, pf_lib_on, &opt};
+    }
+    gemm_plan
+    plan_gemm(const linear_w& L, int M, int epi) const { return ::plan_gemm(shape_of(L), penv(), M, epi); }
     mc_status grow(void** p, size_t* have, size_t need, size_t elem_bytes);
     mc_status ensure_prefill(int M, int S);
-    unsigned gemm_row_tile(int M) const;
-    unsigned gemm_splits(const linear_w& L, int M) const;
-    bool pf2_ok(const linear_w& L, int M) const;
     mc_status ensure_pf2(const linear_w& Lc);
-    void pf2_split(const linear_w& L, unsigned& splits, unsigned& ktper) const;
-    bool g8_ok(const linear_w& L, int M) const;
-    unsigned g8_splits(const linear_w& L, int M) const;
     bool plain_copy_ok();
-    bool lib_ok(const linear_w& L, int M) const;
     mc_status ensure_wd(const linear_w& Lc, const void** wd);
     bool gemm_lib(const linear_w& L, const void* X, void* Y, int M, bool f32_out);
-    // ---- the prompt GEMM plan: which kernel family multiplies X[M][L.in] by this matrix, with what tiles and K ranges.  The one place that
-    // chooses: gemm_run() launches what it says, run_prefill() asks it about w1|w3.  epi: 0 store, 1 + residual, 2 stop at the fp32
-    // partial sums (gemm_to_parts), 3 / 4 silu / gelu * mul.  No launch, no allocation, no kernel name (names are built where they are launched).
-    enum class gemm_family { lib, stream, g8, tiled, tile64 };
-    struct gemm_plan {
-        gemm_family fam = gemm_family::tile64;
-        unsigned bm = 64;                      // rows of X per workgroup
-        unsigned splits = 1, ktper = 0;        // K ranges (grid z; lib: the one partial); stream: K steps of 128 per range
-        unsigned gx = 0, gy = 0, block = 256;  // the family's launch
-    };
-    gemm_plan plan_gemm(const linear_w& L, int M, int epi) const;
     // One plan, one launch per family, one reduce.  epi 2 stops at the partial sums in pf_part ([splits][M][out]); the answer's `splits`
     // is then how many the consumer adds up, 0 when this matrix at this M leaves none (nothing was launched: the caller takes gemm()).
     struct gemm_done {
@@ -509,13 +503,6 @@ struct mc_decoder {
     mc_status gemm(const linear_w& L, int epi, const void* X, void* Y, const void* res, int M);
     mc_status norm_rows(const void* x, const void* w, const void* res, void* y, int M, float mu);
     mc_status qkv_rope_cache(const layer_w& L, void* kc, void* vt, int M, int start_pos, int rope_pos, float mu, const packed_prefill* pk);
-
-    // the fused attention launch of ONE prompt of M rows (the probabilities stay on chip): which kernel, its grid and block
-    struct attn_plan {
-        std::string name;
-        unsigned gx, gy, block;
-    };
-    attn_plan plan_attention(int M) const;
     mc_status gemm_residual(const linear_w& W, const void* X, const void* res, void* out, const void* post_w, const void* next_w, const char* label, int M, float mu, bool* xn_done);
     mc_status run_prefill(int M, int cache_pos, int rope_pos, int window, const void* rows_in, const packed_prefill* pk = nullptr);
 };

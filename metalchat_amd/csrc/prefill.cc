@@ -1,6 +1,7 @@
 // The prompt pass of a decoder: M > 1 rows through every owned block with GEMMs instead of GEMVs (kernels/prefill_kernels.hip, pf_gemm8.h; the
-// packed, extend and tree forms of the batch: packed_kernels.hip, extend_kernels.hip, tree_kernels.hip).  plan_gemm chooses each GEMM, run_prefill is
-// the one launch sequence; the library GEMM it may choose is prefill_blaslt.cc.
+// packed, extend and tree forms of the batch: packed_kernels.hip, extend_kernels.hip, tree_kernels.hip).  What is launched -- each GEMM's family, tiles and
+// K ranges, the attention kernel, the rope form, the folds -- is decided in prefill_plan.h, without a device; run_prefill is the one launch sequence; the
+// library GEMM the plan may choose is prefill_blaslt.cc.
 #include "decoder_impl.h"
 
 using namespace mcimpl;
@@ -63,42 +64,9 @@ if (s != MC_OK) return s;
     return grow(&pf_probs, &pf_probs_elems, need, tb);
 }
 
-// Y[M, L.out] = T(X[M, L.in] Wd^T) (+ res): the fused matrices of the decode GEMV, same HBM layout
-// K splits the big prompt GEMM takes for this matrix at M rows (plan_gemm() below), and the row tile
-unsigned
-mc_decoder::gemm_row_tile(int M) const
-{
-    return tb == 2 && M >= 256 && !opt.pf_depth1 && !opt.pf_bm128 ? 256u : 128u;
-}
-
-unsigned
-mc_decoder::gemm_splits(const linear_w& L, int M) const
-{
-    const unsigned bm = gemm_row_tile(M);
-    const unsigned tiles = ((L.out + 127) / 128) * ((M + bm - 1) / bm);
-    const unsigned want = (bm == 256 ? 1u : 2u) * (unsigned)dev->prop.multiProcessorCount; // (256 rows: one 8-wave workgroup per CU)
-    unsigned splits = 1;
-    while (splits < 16 && tiles * splits < want && (unsigned)L.in / (splits * 2) >= 512) splits *= 2;
-    // (round 4) ... but not past the point where the extra workgroups only start another round: 96 tiles on 256 CUs take one
-    // round of K/2 at 2 splits and two rounds of K/4 at 4 -- the same time, with twice the partials written and read back
-    // (MC_PF_SPLITS_OLD=1: the plain doubling rule)
-    if (!opt.pf_splits_old && splits > 1) {
-        auto rounds = [&](unsigned sp) { return (tiles * sp + want - 1) / want; };
-        const unsigned half = splits / 2;
-        if (rounds(splits) * half >= rounds(half) * splits) splits = half; // rounds(s)/s >= rounds(s/2)/(s/2)
-    }
-    return opt.pf_no_splitk ? 1u : splits;
-}
-
-// Short prompts (<= 64 rows) on int4 weights: the weight-streaming GEMM over the quad-interleaved copy (prefill_kernels.hip
-// mc_pf2_gemm_i4_bfloat: matrix-pipe dequantisation straight into MFMA operands, no LDS image of W)
-bool
-mc_decoder::pf2_ok(const linear_w& L, int M) const
-{
-    return opt.pf2_on && tb == 2 && L.fmt == MC_WFMT_I4 && cfg.qmode == MC_QMODE_EXACT && M <= 64 && L.group == 128 && L.in % 128 == 0 &&
-           L.in >= 256;
-}
-
+// Y[M, L.out] = T(X[M, L.in] Wd^T) (+ res): the fused matrices of the decode GEMV, same HBM layout.  Which kernel multiplies, with what tiles and K
+// ranges, is decided in prefill_plan.h (plan_gemm); here are the derived copies of a matrix the plan may multiply from: the quad-interleaved int4
+// copy of short prompts ...
 mc_status
 mc_decoder::ensure_pf2(const linear_w& Lc)
 {
@@ -115,41 +83,7 @@ mc_decoder::ensure_pf2(const linear_w& Lc)
     return MC_OK;
 }
 
-// K ranges of the weight-streaming GEMM: enough workgroups for the chip, at least two steps of 128 each
-void
-mc_decoder::pf2_split(const linear_w& L, unsigned& splits, unsigned& ktper) const
-{
-    const unsigned nwg = ((unsigned)L.out + 127u) / 128u, KT = (unsigned)L.in / 128u;
-    const unsigned cus = (unsigned)dev->prop.multiProcessorCount;
-    const unsigned target = cus * (unsigned)opt.pf2_wgs_per_cu;
-    splits = std::max(1u, std::min(16u, (target + nwg - 1) / nwg));
-    ktper = std::max(2u, (KT + splits - 1) / splits);
-    splits = (KT + ktper - 1) / ktper;
-}
-
-// ---- the 256 x 256 ping-pong GEMM (round 5, kernels/pf_gemm8.h): bfloat16 rows, no adaptor, K in whole tiles of 64, scale groups
-// of whole 16-runs; from opt.pf_g8_rows rows on (below that the 128-row tiles keep more workgroups busy)
-bool
-mc_decoder::g8_ok(const linear_w& L, int M) const
-{
-    if (!opt.pf_g8_on || tb != 2 || L.lora_cols || M < opt.pf_g8_rows || opt.pf_small_gemm) return false;
-    if (L.in % 64 != 0 || L.out % 4 != 0) return false;
-    if (L.fmt != MC_WFMT_T && L.group && (L.group < 32 || (L.group & (L.group - 1)) != 0)) return false;
-    if ((size_t)L.out * L.in * 2 > 0xFFFFFFFFull || (size_t)M * L.in * 2 > 0xFFFFFFFFull) return false; // (32-bit buffer offsets)
-    return true;
-}
-
-// K ranges of a launch: one round of workgroups on the chip at most, eight K tiles per range at least
-unsigned
-mc_decoder::g8_splits(const linear_w& L, int M) const
-{
-    const unsigned tiles = ((L.out + 255) / 256) * ((M + 255) / 256), cus = (unsigned)dev->prop.multiProcessorCount;
-    unsigned splits = 1;
-    while (splits < (unsigned)opt.pf_g8_max_splits && tiles * splits * 2 <= cus && (unsigned)L.in / 64u / (splits * 2) >= (unsigned)opt.pf_g8_min_ktiles) splits *= 2;
-    return opt.pf_no_splitk ? 1u : splits;
-}
-
-// the quantised matrices of long prompts as dequantised bfloat16 copies (opt.pf_plain_mode above)
+// ... and the quantised matrices of long prompts as dequantised bfloat16 copies (opt.pf_plain_mode)
 bool
 mc_decoder::plain_copy_ok()
 {
@@ -197,51 +131,6 @@ mc_decoder::ensure_wd(const linear_w& Lc, const void** wd)
     return MC_OK;
 }
 
-mc_decoder::gemm_plan
-mc_decoder::plan_gemm(const linear_w& L, int M, int epi) const
-{
-    // The families in priority order: the first whose gate holds multiplies.
-    //   1. lib: hipBLASLt on the dequantised copy (lib_ok) -- a plain store (epi 0) or its fp32 sums as ONE partial (epi 2), nothing else
-    //   2. stream: mc_pf2_gemm_i4_* (pf2_ok: int4, <= 64 rows; K ranges by pf2_split) -- no epilogue of its own, always through the reduce
-    //   3. g8: the 256 x 256 ping-pong mc_pf_gemm8_* (g8_ok; K ranges by g8_splits) -- an activation epilogue (epi >= 3) does not split
-    //   4. tiled: mc_pf_gemm{128,256}_* (row tile by gemm_row_tile, K ranges by gemm_splits) -- every other bfloat16 prompt: a short one
-    //      is bound by the weight stream, and the unpipelined 64 x 64 tile needed 32-42 ms for 8-64 rows where this one needs 5
-    //   5. tile64: mc_pf_gemm_* -- T = float (the parity path) and MC_PF_SMALL_GEMM=1; never splits
-    gemm_plan P;
-    const unsigned out = (unsigned)L.out;
-    if ((epi == 0 || epi == 2) && lib_ok(L, M)) {
-        P.fam = gemm_family::lib;
-    } else if (pf2_ok(L, M)) {
-        P.fam = gemm_family::stream;
-        pf2_split(L, P.splits, P.ktper);
-        P.gx = (out + 127u) / 128u;
-        P.gy = 1;
-        P.block = 512;
-    } else if (g8_ok(L, M)) {
-        P.fam = gemm_family::g8;
-        P.bm = 256;
-        P.splits = epi >= 3 ? 1u : g8_splits(L, M);
-        P.gx = (out + 255u) / 256u;
-        P.gy = ((unsigned)M + 255u) / 256u;
-        P.block = 512;
-    } else if (tb == 2 && !opt.pf_small_gemm) {
-        // 256 rows of X per workgroup from 256 rows on (prefill_kernels.hip pf_gemm_big_body, BM): the W tile is dequantised once
-        // per workgroup, and at 128 rows that vector work is ~ 0.8 of the matrix pipe's time
-        // A 128 x 128 tile walks K serially (~1.5 us per 64-wide chunk), so a grid that does not
-        // oversubscribe the CUs several times is latency-bound: split K until it does.
-        P.fam = gemm_family::tiled;
-        P.bm = gemm_row_tile(M);
-        P.splits = gemm_splits(L, M);
-        P.gx = (out + 127u) / 128u;
-        P.gy = ((unsigned)M + P.bm - 1u) / P.bm;
-        P.block = 2 * P.bm;
-    } else {
-        P.gx = (out + 63u) / 64u;
-        P.gy = ((unsigned)M + 63u) / 64u;
-    }
-    return P;
-}
-
 mc_decoder::gemm_done
 mc_decoder::gemm_run(const linear_w& L, int epi, const void* X, void* Y, const void* res, int M)
 {
@@ -255,7 +144,7 @@ mc_decoder::gemm_run(const linear_w& L, int epi, const void* X, void* Y, const v
         P = plan_gemm(L, M, epi); // (pf_lib_on went false for good: the prompt kernels take over)
     }
     if (stop && P.splits < 2) return {MC_OK, 0};
-    const bool parts = stop || P.splits > 1 || P.fam == gemm_family::stream;
+    const bool parts = P.writes_partials();
     mc_status s = parts ? grow((void**)&pf_part, &pf_part_elems, (size_t)P.splits * M * L.out, 4) : MC_OK;
     if (s != MC_OK) return {s, P.splits};
     // the kernel writes T rows with the caller's epilogue, or fp32 partials (e2: no residual, no adaptor -- the reduce carries them)
@@ -267,13 +156,11 @@ mc_decoder::gemm_run(const linear_w& L, int epi, const void* X, void* Y, const v
     const void *kla = parts ? nullptr : la, *klb = parts ? nullptr : lb;
     const uint32_t kcols = parts ? 0u : (uint32_t)L.lora_cols;
     const float kscale = parts ? 0.0f : lscale;
-    const char* f = L.fmt == MC_WFMT_I4 ? "i4_" : (L.fmt == MC_WFMT_I8 ? "i8_" : "w_");
-    const std::string e = "_e" + std::to_string(parts ? 2 : epi);
     switch (P.fam) {
     case gemm_family::stream:
         s = ensure_pf2(L);
         if (s != MC_OK) break;
-        s = launch("mc_pf2_gemm_i4_" + tname, P.gx, P.gy, P.splits, P.block, 0,
+        s = launch(P.kernel(parts), P.gx, P.gy, P.splits, P.block, 0,
                    pack((const void*)L.wq2, (const void*)L.scales, X, dst, (uint32_t)M, (uint32_t)L.out, (uint32_t)L.in, P.ktper));
         break;
     case gemm_family::g8: {
@@ -285,26 +172,19 @@ mc_decoder::gemm_run(const linear_w& L, int epi, const void* X, void* Y, const v
                 w = wd;
                 sc = nullptr;
                 group = 0;
-                f = "w_";
             } else {
                 pf_plain_on = false; // (no memory for the copy: the quantised rows from here on)
                 (void)hipGetLastError(); // (the failed allocation's residue: RCCL reads it between its own calls)
             }
         }
-        s = launch(std::string("mc_pf_gemm8_") + f + "bfloat" + e, P.gx, P.gy, P.splits, P.block, 0,
+        s = launch(P.kernel(parts, wd != nullptr), P.gx, P.gy, P.splits, P.block, 0,
                    pack(w, sc, X, dst, kres, (uint32_t)M, (uint32_t)L.out, (uint32_t)L.in, group, (const void*)nullptr, (const void*)nullptr,
                         (uint32_t)0, 0.0f));
         break;
     }
-    default: {
-        // two K chunks in flight per workgroup (prefill_kernels.hip: measured best at every length);
-        // MC_PF_DEPTH=1 selects the one-chunk build for A/B runs
-        const bool big = P.fam == gemm_family::tiled;
-        const std::string deep = big && !opt.pf_depth1 ? "_d2" : "";
-        s = launch((big ? (P.bm == 256 ? "mc_pf_gemm256_" : "mc_pf_gemm128_") : "mc_pf_gemm_") + (f + tname) + deep + e, P.gx, P.gy, P.splits,
-                   P.block, 0,
+    default: // tiled, tile64
+        s = launch(P.kernel(parts), P.gx, P.gy, P.splits, P.block, 0,
                    pack(L.w, L.scales, X, dst, kres, (uint32_t)M, (uint32_t)L.out, (uint32_t)L.in, (uint32_t)L.group, kla, klb, kcols, kscale));
-    }
     }
     if (s != MC_OK || stop || !parts) return {s, P.splits};
     s = launch("mc_pf_splitk_reduce_" + tname, (L.out + 255) / 256, M, 1, 256, 0,
@@ -319,7 +199,7 @@ mc_decoder::gemm_run(const linear_w& L, int epi, const void* X, void* Y, const v
 mc_decoder::gemm_done
 mc_decoder::gemm_to_parts(const linear_w& L, const void* X, int M)
 {
-    if (!opt.pf_fold_on || tb != 2 || L.lora_cols || opt.pf_small_gemm) return {MC_OK, 0};
+    if (!fold_parts_ok(shape_of(L), penv())) return {MC_OK, 0};
     return gemm_run(L, 2, X, nullptr, nullptr, M);
 }
 
@@ -356,85 +236,27 @@ mc_decoder::qkv_rope_cache(const layer_w& L, void* kc, void* vt, int M, int star
         mc_status s = timed("gemm_qkv", [&] { return gemm(L.qkv, 0, pf_xn, pf_qkv, nullptr, M); });
         if (s != MC_OK) return s;
     }
-    // rope + cache write: four rotation pairs per thread (prefill_kernels.hip pf_rope_cache_v4_body: a quarter of the waves of the one-pair
-    // launch, which is bound by the rate waves start at, and the transposed V cache written 16 slots at a time); MC_PF_ROPE_PACK=0: the launch of rounds 1-5
-    const bool rope_v4 = opt.pf_rope_pack && tb == 2 && hd % 8 == 0 && hd <= 2048 && 2048 % hd == 0 &&
-                         ((!L.q_norm && !L.k_norm) || hd == 128 || hd == 256); // (q / k norms: the head sizes whose sum order the kernel reproduces)
-    std::string name;
-    unsigned gx = 0, gy = 1, block = 256;
+    // rope + cache write in the form and grid prefill_plan.h plan_rope gives
+    const rope_plan R = plan_rope(penv(), M, parts, pk ? (pk->nodes ? 2 : 1) : 0, L.q_norm || L.k_norm);
     arg_pack a = parts ? pack((const void*)pf_part, g.splits, (uint32_t)M, pf_q) : (pk ? pack((const void*)pf_qkv, (uint32_t)M, pf_q) : pack(pf_qkv, pf_q));
-    if (pk || rope_v4) {
-        const unsigned per = 2048u / (unsigned)hd; // heads of a row per workgroup of 256 threads
-        gx = ((unsigned)(H + KV) * (unsigned)M + per - 1) / per + (unsigned)KV * (((unsigned)M + 15u) / 16u); // q / k units, then v tiles of 16 rows
-    }
-    if (pk) {
-        // packed rows (kc, vt: this layer of every batch row): the four-pair arithmetic whatever MC_PF_ROPE_PACK says (bit for bit the one-pair launch's)
-        name = pk->nodes ? (parts ? "mc_tv_rope_cache_parts_bfloat" : "mc_tv_rope_cache_bfloat")
-                         : (parts ? "mc_pp_rope_cache_parts_bfloat" : "mc_pp_rope_cache_bfloat");
+    switch (R.form) {
+    case rope_form::packed:
+    case rope_form::tree: // (kc, vt: this layer of every batch row)
         push_all(a, pk->segs, (uint32_t)pk->nseg, kc, vt, pk->cache_stride, pk->fcos, pk->fsin, (uint32_t)H, (uint32_t)KV, (uint32_t)hd,
                  (uint32_t)cfg.max_seq_len);
         if (pk->nodes) a.push(pk->nodes);
-    } else if (rope_v4) {
-        name = parts ? "mc_pf_rope_cache_parts_v4_bfloat" : "mc_pf_rope_cache_v4_bfloat";
+        break;
+    case rope_form::v4:
         push_all(a, kc, vt, rope_cos[L.rope_table], rope_sin[L.rope_table], (uint32_t)H, (uint32_t)KV, (uint32_t)hd, (uint32_t)cfg.max_seq_len,
                  (uint32_t)start_pos, (uint32_t)(rope_pos - rope_start));
         if (!parts) a.push((uint32_t)M);
         push_all(a, L.q_norm, L.k_norm, cfg.norm_eps, mu);
-    } else {
-        name = (parts ? "mc_pf_rope_cache_parts_" : "mc_pf_rope_cache_") + tname;
-        gx = H + 2 * KV;
-        gy = M;
-        block = hd / 2;
+        break;
+    case rope_form::pair:
         push_all(a, kc, vt, rope_cos[L.rope_table], rope_sin[L.rope_table], L.q_norm, L.k_norm, (uint32_t)H, (uint32_t)KV, (uint32_t)hd,
                  (uint32_t)cfg.max_seq_len, (uint32_t)start_pos, (uint32_t)(rope_pos - rope_start), cfg.norm_eps, mu);
     }
-    return timed("rope_cache", [&] { return launch(name, gx, gy, 1, block, 0, std::move(a)); });
-}
-
-mc_decoder::attn_plan
-mc_decoder::plan_attention(int M) const
-{
-    const int H = cfg.n_heads, KV = cfg.n_kv_heads, hd = cfg.head_dim;
-    // two query heads of a kv head per workgroup where the grouping allows it: each K / V
-    // fragment is loaded once for both (MC_PF_ATTN_HEADS=1: one head per workgroup)
-    // (measured: 2048 rows 15.8 -> 14.0 ms, 512 rows 2.05 -> 1.56 ms per prompt; with too few
-    // workgroups to fill the chip -- 128 rows -- it loses, 0.46 -> 0.61 ms)
-    const bool heads_given = opt.pf_attn_heads >= 0;
-    const bool enough = (unsigned)((M + 15) / 16) * (unsigned)(H / 2) >= 2u * (unsigned)dev->prop.multiProcessorCount;
-    const bool two = (H / KV) % 2 == 0 && hd <= 128 && (heads_given ? opt.pf_attn_heads == 2 : enough);
-    // four query heads per workgroup (head_dim 128, 360 registers: one workgroup per CU): at 1024 rows and more
-    // the launch is bound by the K / V fragments its waves pull out of L2 (1.6 GB per layer at 2048 rows, ~ 6 TB/s),
-    // and four heads per fragment halve them again: 2048 rows 44.5 -> 42.6 ms, 1024: 22.75 -> 22.3, 512: 11.8 -> 11.7
-    const bool four = (H / KV) % 4 == 0 && hd == 128 &&
-                      (heads_given ? opt.pf_attn_heads == 4
-                                   : (unsigned)((M + 15) / 16) * (unsigned)(H / 4) >= (unsigned)dev->prop.multiProcessorCount);
-    // long prompts (round 5): K / V tiles through LDS, 32 rows x 4 heads per workgroup (prefill_kernels.hip pf_attn_lds_body)
-    const bool eight = (H / KV) % 4 == 0 && hd == 128 && cfg.max_seq_len % 8 == 0 &&
-                       (heads_given ? opt.pf_attn_heads == 8 : (opt.pf_attn8_on && M >= opt.pf_attn8_rows));
-    // (row tiles of 32 rows, dealt in pairs -- tile x with tile (last - x): equal work under the causal mask -- when the
-    //  pairs still cover the CUs; MC_PF_ATTN8_PAIR=0 / 1 forces either)
-    const unsigned ntl = (unsigned)(M + 31) / 32u;
-    const bool pair_given = opt.pf_attn8_pair >= 0;
-    const bool pair = pair_given ? opt.pf_attn8_pair != 0 : ((ntl + 1u) / 2u) * (unsigned)(H / 4) >= (unsigned)dev->prop.multiProcessorCount;
-    // head_dim 256 (round 6; Gemma-7B: a kv head per query head): the same K / V tiles through LDS for 64 rows of ONE head, four waves
-    // (MC_PF_ATTN8_ROWS256: from how many rows; MC_PF_ATTN_HEADS=1: never)
-    const bool eight256 = hd == 256 && cfg.max_seq_len % 8 == 0 && (heads_given ? opt.pf_attn_heads == 8 : (opt.pf_attn8_on && M >= opt.pf_attn8_rows256));
-    if (eight256) {
-        const unsigned ntl64 = (unsigned)(M + 63) / 64u;
-        const bool pair64 = pair_given ? opt.pf_attn8_pair != 0 : ((ntl64 + 1u) / 2u) * (unsigned)H >= (unsigned)dev->prop.multiProcessorCount;
-        return {"mc_pf_attn8_bfloat_hd256", pair64 ? (ntl64 + 1u) / 2u : ntl64, (unsigned)H, 256};
-    }
-    // head_dim 64 (round 6; TinyLlama-1.1B: 8 query heads per kv head, Llama-3.2-1B: 4): 8 heads x 16 rows or 4 heads x 32 rows per workgroup
-    const unsigned nh64 = (H / KV) % 8 == 0 ? 8u : ((H / KV) % 4 == 0 ? 4u : 0u);
-    const bool eight64 = hd == 64 && nh64 && cfg.max_seq_len % 8 == 0 && (heads_given ? opt.pf_attn_heads == 8 : (opt.pf_attn8_on && M >= opt.pf_attn8_rows64));
-    if (eight64) {
-        const unsigned rt64 = 128u / nh64, ntl = ((unsigned)M + rt64 - 1u) / rt64;
-        const bool pr = pair_given ? opt.pf_attn8_pair != 0 : ((ntl + 1u) / 2u) * ((unsigned)H / nh64) >= (unsigned)dev->prop.multiProcessorCount;
-        return {nh64 == 8 ? "mc_pf_attn8_bfloat_hd64_h8" : "mc_pf_attn8_bfloat_hd64_h4", pr ? (ntl + 1u) / 2u : ntl, (unsigned)H / nh64, 512};
-    }
-    if (eight) return {"mc_pf_attn8_bfloat_hd128", pair ? (ntl + 1u) / 2u : ntl, (unsigned)H / 4, 512};
-    if (four) return {"mc_pf_attn4_bfloat_hd128", ((unsigned)M + 15) / 16, (unsigned)H / 4, 256};
-    return {std::string(two ? "mc_pf_attn2_bfloat_hd" : "mc_pf_attn_bfloat_hd") + std::to_string(hd), ((unsigned)M + 15) / 16, (unsigned)(two ? H / 2 : H), 256};
+    return timed("rope_cache", [&] { return launch(R.name, R.gx, R.gy, 1, R.block, 0, std::move(a)); });
 }
 
 // Wo and w2: out = T(res + y), y = T(X W^T) or gemma3's post norm of it (post_w; null: llama) -- and where the GEMM splits K its
@@ -446,11 +268,9 @@ mc_decoder::gemm_residual(const linear_w& W, const void* X, const void* res, voi
 {
     const int dim = cfg.dim;
     *xn_done = false;
-    // gemma3's post norms: the reduce of a split Wo / w2, the post norm with the residual and the next norm in one launch
-    // (prefill_kernels.hip mc_pf_rmsnorm2_parts_bfloat, which takes no next norm too; MC_PF_NORM2=0: the three launches)
-    // llama: h = T(x + T(sum of the partials)) -> out, rmsnorm(h) -> pf_xn: the reduce, the residual and the next norm in one launch
-    const bool fold_norm = dim % 8 == 0 && dim / 8 <= 4 * 256;
-    const bool fold = post_w ? fold_norm && tb == 2 && opt.pf_norm2 : fold_norm && next_w;
+    // the reduce of a split Wo / w2, the residual and the norm(s) behind it in one launch where prefill_plan.h fold_norm_ok allows:
+    // llama: h = T(x + T(sum of the partials)) -> out, rmsnorm(h) -> pf_xn; gemma3: the post norm in front of the residual too
+    const bool fold = fold_norm_ok(penv(), post_w != nullptr, next_w != nullptr);
     const gemm_done g = fold ? gemm_to_parts(W, X, M) : gemm_done{MC_OK, 0};
     if (g.st != MC_OK) return g.st;
     if (g.splits) {
@@ -518,28 +338,26 @@ mc_decoder::run_prefill(int M, int cache_pos, int rope_pos, int window, const vo
         const uint32_t win = (gemma && L.rope_table == 1) ? (uint32_t)window : 0u;
         if (pk && pk->extend) {
             // chunks that see their context (mc_extend_rows, kernels/extend_kernels.hip): the exp sums of every key range, then
-            // p V over the ranges, then the ranges of a tile added in order; two query heads of a kv head per workgroup where
-            // the grouping allows it.  A group is as many whole tiles as the scratch holds (one group unless the call is huge).
+            // p V over the ranges, then the ranges of a tile added in order (names and heads per workgroup: prefill_plan.h
+            // plan_extend_attention).  A group is as many whole tiles as the scratch holds (one group unless the call is huge).
             // Chunks that are trees (mc_tree_verify, pk->nodes): the mc_tv_* forms of the first two, the node table behind their arguments.
             s = timed("attention", [&] {
-                const bool two = (H / KV) % 2 == 0;
-                const std::string sfx = std::string(two ? "2" : "") + "_bfloat_hd" + std::to_string(hd);
-                const unsigned gh = two ? H / 2 : H;
+                const extend_plan E = plan_extend_attention(penv(), pk->nodes != nullptr);
                 for (int g = 0; g < pk->ngroups; g++) {
                     const uint32_t e0 = (uint32_t)pk->groups[g].first, ne = (uint32_t)pk->groups[g].count;
                     arg_pack as = pack(pf_q, pk->segs, pk->ranges, e0, (const void*)pk_kc, pk->cache_stride, pk->sums, (uint32_t)H,
                                        (uint32_t)(H / KV), (uint32_t)cfg.max_seq_len, scale_T, (const void*)pf_etab);
                     if (pk->nodes) as.push(pk->nodes);
-                    mc_status ls = launch((pk->nodes ? "mc_tv_sums" : "mc_px_sums") + sfx, gh, ne, 1, 256, 0, std::move(as));
+                    mc_status ls = launch(E.sums, E.heads, ne, 1, 256, 0, std::move(as));
                     if (ls != MC_OK) return ls;
                     arg_pack ap = pack(pf_q, pk->segs, pk->ranges, e0, (const void*)pk_kc, (const void*)pk_vt, pk->cache_stride,
                                        (const void*)pk->sums, pk->part, pf_att, (uint32_t)H, (uint32_t)(H / KV), (uint32_t)cfg.max_seq_len, scale_T,
                                        (const void*)pf_etab);
                     if (pk->nodes) ap.push(pk->nodes);
-                    ls = launch((pk->nodes ? "mc_tv_pv" : "mc_px_pv") + sfx, gh, ne, 1, 256, 0, std::move(ap));
+                    ls = launch(E.pv, E.heads, ne, 1, 256, 0, std::move(ap));
                     if (ls != MC_OK) return ls;
                     if (!pk->groups[g].split) continue; // no tile of the group is split: mc_px_pv wrote the outputs
-                    ls = launch("mc_px_reduce_bfloat_hd" + std::to_string(hd), H, ne, 1, 256, 0,
+                    ls = launch(E.reduce, H, ne, 1, 256, 0,
                                 pack(pk->segs, pk->ranges, e0, (const void*)pk->part, pf_att, (uint32_t)H));
                     if (ls != MC_OK) return ls;
                 }
@@ -547,14 +365,10 @@ mc_decoder::run_prefill(int M, int cache_pos, int rope_pos, int window, const vo
             });
             if (s != MC_OK) return s;
         } else if (pk) {
-            // one or two query heads per workgroup by the rule of one prompt below, over the tiles of all segments; the LDS-tile and
-            // four-head forms have no packed counterpart (DESIGN.md "The packed prompt pass")
+            // (prefill_plan.h plan_packed_attention: the two-heads rule of one prompt over the tiles of all segments)
             s = timed("attention", [&] {
-                const bool heads_given = opt.pf_attn_heads >= 0;
-                const bool enough = (unsigned)pk->ntiles * (unsigned)(H / 2) >= 2u * (unsigned)dev->prop.multiProcessorCount;
-                const bool two = (H / KV) % 2 == 0 && (heads_given ? opt.pf_attn_heads == 2 : enough);
-                return launch(std::string(two ? "mc_pp_attn2_bfloat_hd" : "mc_pp_attn_bfloat_hd") + std::to_string(hd), (unsigned)pk->ntiles,
-                              two ? H / 2 : H, 1, 256, 0,
+                const attn_plan A = plan_packed_attention(penv(), pk->ntiles);
+                return launch(A.name, A.gx, A.gy, 1, A.block, 0,
                               pack(pf_q, pk->segs, pk->tiles, (const void*)pk_kc, (const void*)pk_vt, pk->cache_stride, pf_att, (uint32_t)H,
                                    (uint32_t)(H / KV), (uint32_t)cfg.max_seq_len, scale_T, (const void*)pf_etab));
             });
@@ -562,7 +376,7 @@ mc_decoder::run_prefill(int M, int cache_pos, int rope_pos, int window, const vo
         } else if (tb == 2 && !opt.pf_two_pass) {
             // fused: the probabilities stay on chip
             s = timed("attention", [&] {
-                const attn_plan A = plan_attention(M);
+                const attn_plan A = plan_attention(penv(), M);
                 return launch(A.name, A.gx, A.gy, 1, A.block, 0,
                               pack(pf_q, L.kc, L.vt, pf_att, (uint32_t)M, (uint32_t)S, (uint32_t)H, (uint32_t)(H / KV),
                                    (uint32_t)cfg.max_seq_len, scale_T, win, (const void*)pf_etab));
@@ -587,13 +401,9 @@ mc_decoder::run_prefill(int M, int cache_pos, int rope_pos, int window, const vo
         //  SLOWER: 13.60 against 13.26 ms per 512-row prompt, 52.0 against 50.6 at 2048 rows: half the lanes idle through the
         //  fp64 exponential, in the kernel that holds the matrix pipe)
         const unsigned act_pp = 8u / (unsigned)tb; // pairs per thread (one 16-byte packet)
-        // silu(w1 x) * (w3 x) in the epilogue of an unsplit 256-row GEMM (prefill_kernels.hip pf_gemm_big_body EPI 3; the
-        // table of exponentials rides in `res`).  MC_PF_ACT_EPI=0: the separate launch
-        // (gemma: gelu from the table of round 6 -- the 256 x 256 GEMM's e4 epilogue only; without the table the separate launch with its fp64 tanh)
+        // the activation in the epilogue of an unsplit w1|w3 GEMM where prefill_plan.h act_epi_ok allows (the table rides in `res`)
         const gemm_plan p13 = plan_gemm(L.w13, M, 0);
-        const bool act_epi = opt.pf_act_epi && !L.w13.lora_cols && p13.splits == 1 &&
-                             (p13.fam == gemm_family::g8 ? cfg.ffn_dim % 2 == 0 && (!gemma || pf_gtab)
-                                                         : p13.fam == gemm_family::tiled && !gemma && p13.bm == 256 && !opt.pf_depth1);
+        const bool act_epi = act_epi_ok(shape_of(L.w13), penv(), p13, pf_gtab != nullptr);
         const void* act_tab = gemma ? (const void*)pf_gtab : (const void*)pf_etab; // (gelu without a table: nullptr, the kernels evaluate it)
         // (the library GEMM writes bfloat16 rows for the separate activation launch: half the bytes of fp32 partials)
         const gemm_done g13 = !act_epi && cfg.ffn_dim % 4 == 0 && p13.fam != gemm_family::lib ? gemm_to_parts(L.w13, pf_xn, M) : gemm_done{MC_OK, 0};

@@ -104,26 +104,7 @@ mcimpl::blaslt_release(blaslt_state* st)
     delete st;
 }
 
-// ---- the library GEMM of long prompts
-// Measured on MI355X (tools/blaslt_probe.py, profiles/r04_blaslt_probe.log; WBITS=16 tools/prefill_bench.py): the hand-written
-// tiled GEMM reaches 600-725 TFLOP/s with AND without its dequantisation (plain bfloat weights: 180 us for w1|w3 at 512 rows
-// against 168 with int4) -- its ceiling is the tile loop, not the exact arithmetic -- while hipBLASLt multiplies the same shapes
-// at 1.1-1.36 PFLOP/s once a launch has >= 128 tiles of 256 x 256 and at 600-750 with 32-48 of them, where the split-K kernels
-// here are as fast or faster.  The threshold was then swept on whole prompts of 256-1536 rows (profiles/r04_prefill_blaslt.log):
-// 48 tiles is the best or equal at every length (w1|w3 from 256 rows on, wq|wk|wv from 512, every matrix of Llama-3-8B from 768).  The operand is Wd = T(T(q) T(s)), the very
-// values the prompt kernels hold in LDS, kept as a bfloat16 copy [out][in] (2 bytes per weight more HBM: 14 GB for Llama-3-8B
-// of 288); sums are fp32, rounded to T once (linear.h:70-81) -- only the order of the fp32 additions differs from the kernels'.
-// Any failure of the library (absent, no algorithm, an error status) switches the path off: the prompt kernels take over.
-bool
-mc_decoder::lib_ok(const linear_w& L, int M) const
-{
-    if (!pf_lib_on || tb != 2 || L.lora_cols || opt.pf_small_gemm) return false;
-    if (L.fmt != MC_WFMT_T && (L.in % 16 != 0 || (L.group && (L.group & (L.group - 1)) != 0))) return false;
-    if (L.in % 8 != 0 || L.out % 8 != 0) return false;
-    if (opt.pf_lib_force) return true; // (MC_PF_BLASLT=2: every prompt GEMM that can, whatever its size -- how the tests reach it on small models)
-    return M >= opt.pf_lib_rows && (size_t)((L.out + 255) / 256) * (size_t)((M + 255) / 256) >= (size_t)opt.pf_lib_tiles;
-}
-
+// ---- the library GEMM of long prompts (when it is taken, and what was measured: prefill_plan.h lib_ok)
 // Y[M][out] (bfloat16, or fp32 when f32_out) = X[M][in] Wd^T on the decoder's stream.  false: the library path is off now
 bool
 mc_decoder::gemm_lib(const linear_w& L, const void* X, void* Y, int M, bool f32_out)

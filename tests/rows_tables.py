@@ -1,10 +1,10 @@
 """The tables of the packed prompt pass and of mc_extend_rows, restated in Python for the kernel-level tests
 (test_rows_kernels_gpu.py): the segment, tile and key-range tables of kernels/abi.h (pp_seg, pp_tile, px_range) and the launch groups,
-built by the rules of metalchat_amd/csrc/batch.cc (rows_tables, rows_ranges, px_range_keys).
+built by the rules of metalchat_amd/csrc/rows_plan.h (rows_tables, rows_ranges, px_range_keys).
 
-This is a RESTATEMENT: nothing binds it to the C++ rules without a device (the host code builds its tables inside mc_extend_rows and
-hands them to the launches only).  test_rows_tables_cpu.py checks it against examples worked by hand from the C++ text;
-test_rows_extend_gpu.test_a_call_in_several_launch_groups binds the host's own tables and groups on the device."""
+This is a RESTATEMENT, bound to the C++ rules on the CPU: they live in a header without HIP (csrc/rows_plan.h), and test_rows_tables_cpu.py
+holds every function here to tests/cpp/test_rows_plan, a plain g++ program over that header, on the examples worked by hand and on 300
+random calls.  test_rows_extend_gpu.test_a_call_in_several_launch_groups binds the host's own tables and groups on the device."""
 import numpy as np
 
 TILE_ROWS = 16   # abi.h PP_TILE_ROWS

@@ -14,7 +14,7 @@ from metalchat_amd import build as b
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 READELF = ["/opt/rocm/lib/llvm/bin/llvm-readelf", "/usr/bin/readelf"]
 
-# prefill.cc run_prefill (the branch of a packed pass that extends) forms these names: the exp sums and p V of a key range with one
+# prefill.cc run_prefill (the branch of a packed pass that extends) launches these names, formed in prefill_plan.h plan_extend_attention: the exp sums and p V of a key range with one
 # or two query heads per workgroup, and the reduce over a split tile's ranges, at head_dim 64 / 128 (the batch's admitted sizes)
 EXTEND_KERNELS = [f"mc_px_{a}_bfloat_hd{hd}" for a in ("sums", "sums2", "pv", "pv2", "reduce") for hd in (64, 128)]
 
@@ -35,7 +35,7 @@ def test_the_entry_point_is_declared_once_exported_and_bound():
 
 
 def test_every_extend_kernel_is_in_the_code_object():
-    src = open(os.path.join(ROOT, "metalchat_amd", "csrc", "prefill.cc")).read()
+    src = open(os.path.join(ROOT, "metalchat_amd", "csrc", "prefill_plan.h")).read()
     for stem in ('"mc_px_sums"', '"mc_px_pv"', '"mc_px_reduce_bfloat_hd"'):
         assert stem in src, stem
     hsaco, _ = b.build_all()

@@ -13,7 +13,7 @@ from metalchat_amd import build as b
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 READELF = ["/opt/rocm/lib/llvm/bin/llvm-readelf", "/usr/bin/readelf"]
 
-# prefill.cc run_prefill (packed branches) forms these names: rope + cache write from the GEMM's rows or its split-K partials, one
+# prefill.cc run_prefill (packed branches) launches these names (formed in prefill_plan.h plan_rope / plan_packed_attention; the gather: prefill.cc): rope + cache write from the GEMM's rows or its split-K partials, one
 # or two query heads per attention workgroup at head_dim 64 / 128 (the batch's admitted sizes), and the gather of the last rows
 PACKED_KERNELS = ["mc_pp_rope_cache_bfloat", "mc_pp_rope_cache_parts_bfloat", "mc_pp_gather_last_bfloat"] + [
     f"mc_pp_{a}_bfloat_hd{hd}" for a in ("attn", "attn2") for hd in (64, 128)]
@@ -33,7 +33,7 @@ def test_the_entry_point_is_exported_and_bound():
 
 
 def test_every_packed_kernel_is_in_the_code_object():
-    src = open(os.path.join(ROOT, "metalchat_amd", "csrc", "prefill.cc")).read()
+    src = open(os.path.join(ROOT, "metalchat_amd", "csrc", "prefill.cc")).read() + open(os.path.join(ROOT, "metalchat_amd", "csrc", "prefill_plan.h")).read()
     for stem in ('"mc_pp_rope_cache_bfloat"', '"mc_pp_rope_cache_parts_bfloat"', '"mc_pp_attn2_bfloat_hd"', '"mc_pp_attn_bfloat_hd"',
                  '"mc_pp_gather_last_bfloat"'):
         assert stem in src, stem

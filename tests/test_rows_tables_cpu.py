@@ -1,13 +1,18 @@
-"""rows_tables.py (the Python restatement of batch.cc rows_tables / rows_ranges / px_range_keys that test_rows_kernels_gpu.py builds its
-tables with) against examples worked by hand from the C++ rule, and the properties the kernels rely on.  Nothing here can bind the
-restatement to the C++ code without a device: test_rows_extend_gpu.test_a_call_in_several_launch_groups does that."""
+"""rows_tables.py (the Python restatement of the C++ rules rows_tables / rows_ranges / px_range_keys that test_rows_kernels_gpu.py builds its
+tables with) against examples worked by hand from the C++ rule, the properties the kernels rely on -- and against the C++ rules themselves:
+they live in csrc/rows_plan.h, a header without HIP that batch.cc builds every call's tables with, and tests/cpp/test_rows_plan (a plain g++
+program over it, rows_plan_program.py) must print the restatement's segments, tiles, ranges and groups for every by-hand example here, the calls
+of test_rows_extend_gpu.py and 300 random calls.  A host rule that changes fails here, before a kernel test goes on testing the old one.
+test_rows_extend_gpu.test_a_call_in_several_launch_groups still binds the uploaded tables on the device."""
 import os
 import re
 import subprocess
 
 import numpy as np
 
+import rows_plan_program as rp
 import rows_tables as rt
+import tree_rule as tr
 from metalchat_amd import build as b
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -129,3 +134,113 @@ def test_every_packed_and_extend_kernel_is_launched_by_name_in_the_kernel_tests(
     named = set(re.findall(r'"(mc_p[px]_\w+)"', text))
     assert named == set(ROWS_KERNELS), sorted(set(ROWS_KERNELS) ^ named)
     assert "acc.load(" in text
+
+
+# ---- the binding: the restatement against csrc/rows_plan.h itself (tests/cpp/test_rows_plan)
+
+def restated(lens, positions, keys=rp.RULE, slots=1024):
+    segs = rt.segments(lens, positions)
+    tls = rt.tiles(segs)
+    tab = rt.ranges(segs, tls, rt.default_keys if keys == rp.RULE else rt.keys_of(keys))
+    return segs, tls, tab, rt.groups(tab, slots)
+
+
+def test_the_cpp_rules_give_the_restatement_on_every_example_worked_by_hand():
+    by_hand = [([0, 5, 0, 0, 33, 0, 16, 0], [9, 7, 0, 0, 64, 0, 3, 0], 128, rp.RULE),    # test_segments_and_tiles_by_hand
+               (LONG_LENS, LONG_POS, 1024, rp.RULE), (LONG_LENS, LONG_POS, 1024, 128),    # test_rows_extend_gpu's long contexts
+               (LONG_LENS, LONG_POS, 1024, 100), (LONG_LENS, LONG_POS, 1024, 129), (LONG_LENS, LONG_POS, 1024, 0),
+               ([200] * 8, [1800] * 8, 2048, 128), ([200], [1800], 2048, 128)]            # test_a_call_in_several_launch_groups
+    by_hand += [([n], [S - n], 2048, rp.RULE) for S, n in ((512, 2), (513, 2), (513, 32), (513, 33), (2048, 2), (1025, 17))]   # the rule's edges
+    answers = rp.ask([rp.call(lens, pos, S, keys=keys) for lens, pos, S, keys in by_hand])
+    for (lens, pos, S, keys), a in zip(by_hand, answers):
+        assert a["scratch"]["slots"] == 1024 and a["scratch"]["per_slot"] == 8 * 16 * 128 * 4     # 64 MiB / (8 heads * 16 rows * 128 * 4 bytes)
+        assert rp.tables(a) == restated(lens, pos, keys), (lens, pos, S, keys)
+        assert (a["M"], a["nseg"], a["ntiles"]) == (sum(lens), len(a["segs"]), len(a["tiles"]))
+        assert a["pos"] == [p if n else -1 for n, p in zip(lens, pos)]
+    # the literal tables of the by-hand tests, from the C++ side too
+    assert answers[0]["segs"] == [[1, 7, 0, 5], [4, 64, 5, 33], [6, 3, 38, 16]] and answers[0]["tiles"] == [[0, 0], [1, 0], [1, 16], [1, 32], [2, 0]]
+    assert [x for x in answers[1]["ranges"] if x[0] == 0] == [[0, 0, 0, 512, 0, 2, 0, 0], [0, 0, 512, 1005, 0, 2, 0, 0]]
+    assert len(answers[1]["ranges"]) == 20 and answers[1]["groups"] == [[0, 20, True]]
+    assert len(answers[6]["ranges"]) == 8 * 201 and len(answers[6]["groups"]) == 2 and len(answers[7]["groups"]) == 1
+    # the most ranges of a tile and the tables' reserve: two by the rule, ceil(max_seq_len / 128) under MC_PX_KEYS=128
+    assert answers[1]["scratch"]["per_tile"] == 2 and answers[2]["scratch"]["per_tile"] == 8 and answers[6]["scratch"]["per_tile"] == 16
+    assert answers[6]["scratch"]["tiles_max"] == 2048 // 16 + 64
+
+
+def random_call(rng):
+    """a call that is valid by construction: position <= length, position + len <= S, lengths summing to at most S"""
+    while True:
+        B, S = int(rng.integers(1, 65)), int(rng.integers(64, 2049))
+        tree = bool(rng.integers(0, 2))
+        lens, left = [], min(S, 128) if tree else S
+        for _ in range(B):
+            n = int(rng.integers(2, 17 if tree else 131)) if rng.integers(0, 3) else 0
+            n = n if n <= left else 0
+            lens.append(n)
+            left -= n
+        if any(lens):
+            break
+    pos = [int(rng.integers(0, S - n + 1)) if n else int(rng.integers(0, S)) for n in lens]
+    lengths = [p + int(rng.integers(0, 5)) for p in pos]
+    parents = None
+    if tree:
+        parents = [par for n in lens if n for par in [-1] + [int(rng.integers(0, i)) for i in range(1, n)]]
+    return dict(lens=lens, pos=pos, S=S, lengths=lengths, parents=parents, keys=int(rng.choice([rp.RULE, rp.RULE, 0, 128, 384])),
+                H=int(rng.choice([8, 32])), hd=int(rng.choice([64, 128])))
+
+
+def test_the_cpp_rules_give_the_restatement_on_300_random_calls():
+    rng = np.random.default_rng(20260101)
+    calls = [random_call(rng) for _ in range(300)]
+    for c in calls:   # a launch group holds whole tiles: never fewer slots than the most ranges of a tile
+        c["most"] = max(e[5] for e in restated(c["lens"], c["pos"], c["keys"], 1 << 20)[2])
+        c["slots"] = int(rng.choice([c["most"], c["most"] + 1, 2 * c["most"] + 3, 0]))
+    answers = rp.ask([rp.call(c["lens"], c["pos"], c["S"], lengths=c["lengths"], parents=c["parents"], keys=c["keys"], slots=c["slots"],
+                              who="mc_tree_verify" if c["parents"] else "mc_extend_rows", n_heads=c["H"], head_dim=c["hd"]) for c in calls])
+    assert sum(1 for c in calls if c["parents"]) > 100 and sum(1 for c in calls if not c["parents"]) > 100
+    for c, a in zip(calls, answers):
+        assert "refused" not in a, (c, a)   # none of them may be refused
+        slots = c["slots"] or a["scratch"]["slots"]
+        assert a["scratch"]["slots"] == min(32768, max(a["scratch"]["per_tile"], (64 << 20) // (c["H"] * 16 * c["hd"] * 4)))
+        assert a["scratch"]["per_tile"] >= c["most"]
+        assert rp.tables(a) == restated(c["lens"], c["pos"], c["keys"], slots), c
+        if c["parents"]:
+            nodes, off = [], 0
+            for n in c["lens"]:
+                par = c["parents"][off:off + n]
+                nodes += [list(x) for x in zip(tr.depths(par), tr.anc_masks(par))] if n else []
+                off += n
+            assert a["nodes"] == nodes, c
+        else:
+            assert a["nodes"] == []
+
+
+def test_every_refusal_of_a_rows_call_by_its_words():
+    S = 64
+    refusals = [
+        (dict(lens=[-1, 2], positions=[0, 0]), "mc_extend_rows: row 0: length below 0 (0 = the row is not in the call)"),
+        (dict(lens=[0, 1], positions=[0, 0]), "mc_extend_rows: row 1: a one-token chunk is a step: mc_ragged_step"),
+        (dict(lens=[2], positions=[-3], lengths=[0]), "mc_extend_rows: row 0: position below 0"),
+        (dict(lens=[2], positions=[9], lengths=[8]), "mc_extend_rows: row 0: position 9 is past the row's length 8 (its cache has no slots written beyond it)"),
+        (dict(lens=[5], positions=[60]), "mc_extend_rows: row 0: position + length 65 exceeds max_seq_len (a batch's cache does not roll)"),
+        (dict(lens=[2], positions=[10], lengths=[70]), "mc_extend_rows: row 0: position 10 lies below the row's length 70 and the row has rolled"),
+        (dict(lens=[3], positions=[0], tokens=[1, 512, 2]), "mc_extend_rows: row 0: token id outside the vocabulary"),
+        (dict(lens=[3], positions=[0], tokens=[1, -1, 2]), "mc_extend_rows: row 0: token id outside the vocabulary"),
+        (dict(lens=[0, 0], positions=[0, 0]), "mc_extend_rows: no row in the call (every length is 0)"),
+        (dict(lens=[40, 40], positions=[0, 0]), "mc_extend_rows: the rows' lengths add up to 80, more than max_seq_len (64): split the call by rows"),
+        (dict(lens=[2, 17], positions=[0, 0], verify=True, who="mc_verify_rows"),
+         "mc_verify_rows: row 1: a chunk of 17 tokens is longer than MC_VERIFY_MAX_LEN (16)"),
+        (dict(lens=[16] * 9, positions=[0] * 9, verify=True, who="mc_verify_rows", max_seq_len=256),
+         "mc_verify_rows: the chunks add up to 144 rows, more than MC_VERIFY_MAX_ROWS (128): split the call by rows"),
+        (dict(lens=[3], positions=[0], parents=[0, 0, 1], who="mc_tree_verify"),
+         "mc_tree_verify: row 0: the parent of node 0 (the root) must be -1, not 0"),
+        (dict(lens=[0, 3], positions=[0, 0], parents=[-1, 0, 2], who="mc_tree_verify"),
+         "mc_tree_verify: row 1: the parent of node 2 is 2, outside [0, 2) (nodes come in topological order)"),
+        (dict(lens=[3], positions=[0], parents=[-1, -1, 0], who="mc_tree_verify"),
+         "mc_tree_verify: row 0: the parent of node 1 is -1, outside [0, 1) (nodes come in topological order)"),
+    ]
+    lines = [rp.call(k.pop("lens"), k.pop("positions"), k.pop("max_seq_len", S), **k) for k, _ in refusals]
+    assert [a.get("refused") for a in rp.ask(lines)] == [text for _, text in refusals]
+    # a rolled row restarted at 0 is admitted (a chunk at its length would leave the cache); the chunks of the verify limit without `verify` are too
+    ok = rp.ask([rp.call([2], [0], S, lengths=[70]), rp.call([2, 17], [0, 0], S)])
+    assert ["refused" in a for a in ok] == [False, False]

@@ -1,7 +1,8 @@
 """Speculative verify over a draft tree (mc_tree_verify, include/metalchat_hip.h Part 2g) without a GPU: the entry point is declared
 once, exported and bound; the twelve mc_tv_* kernels are exactly the set in the code object and keep nothing in private memory; null
 arguments are refused before a batch is looked at; and the rules (tree_rule.py, which the GPU tests hold the device to) on cases
-worked by hand."""
+worked by hand -- its depths and ancestor masks also against the host's own tree_nodes (csrc/rows_plan.h through tests/cpp/test_rows_plan;
+random trees: test_rows_tables_cpu.py)."""
 import ctypes as C
 import os
 import re
@@ -10,6 +11,7 @@ import subprocess
 import numpy as np
 
 import metalchat_amd as mc
+import rows_plan_program as rp
 import tree_rule as tr
 from metalchat_amd import build as b
 
@@ -49,7 +51,7 @@ def test_the_tree_kernels_are_exactly_the_set_in_the_code_object():
     host = open(os.path.join(ROOT, "metalchat_amd", "csrc", "batch.cc")).read()
     for stem in ('"mc_tv_accept"', '"mc_tv_compact_bfloat"'):
         assert stem in host, stem
-    dec = open(os.path.join(ROOT, "metalchat_amd", "csrc", "prefill.cc")).read()
+    dec = open(os.path.join(ROOT, "metalchat_amd", "csrc", "prefill_plan.h")).read()   # (the names prefill.cc launches are formed there)
     for stem in ('"mc_tv_sums"', '"mc_tv_pv"', '"mc_tv_rope_cache_bfloat"', '"mc_tv_rope_cache_parts_bfloat"'):
         assert stem in dec, stem
     out = readelf("--symbols", "--wide")
@@ -103,6 +105,10 @@ def test_depths_and_ancestor_masks_by_hand():
     assert list(tr.chain(5)) == [-1, 0, 1, 2, 3]
     assert tr.depths(tr.chain(16)) == list(range(16))
     assert tr.anc_masks(tr.chain(16)) == [(2 << i) - 1 for i in range(16)]
+    # the host's node table (rows_plan.h tree_nodes) for the same trees, two rows of one call: the tree above and the chain
+    a = rp.ask([rp.call([8, 0, 16], [5, 0, 40], 64, parents=par + list(tr.chain(16)), who="mc_tree_verify")])[0]
+    assert a["nodes"] == [list(x) for x in zip(tr.depths(par), tr.anc_masks(par))] + [[i, (2 << i) - 1] for i in range(16)]
+    assert a["M"] == 24 and a["ntiles"] == 2 and a["segs"] == [[0, 5, 0, 8], [2, 40, 8, 16]]
 
 
 def test_the_walk_on_cases_worked_by_hand():

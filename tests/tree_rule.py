@@ -11,8 +11,9 @@ nodes 1 .. n - 1 are drafts and parents[i] < i names node i's parent.  pick[i] i
                             path[d] for d <= accepted -- a permutation-like move of slots, every other slot untouched
   trie                      candidate continuations of one last token merged into (tokens, parents)
 
-This is a RESTATEMENT of kernels/tree_kernels.hip (mc_tv_accept, mc_tv_compact_bfloat) and of batch.cc tree_nodes;
-test_tree_kernels_gpu.py binds the kernels to it on the device."""
+This is a RESTATEMENT of kernels/tree_kernels.hip (mc_tv_accept, mc_tv_compact_bfloat) and of csrc/rows_plan.h tree_nodes;
+test_tree_kernels_gpu.py binds the kernels to it on the device, test_rows_tables_cpu.py and test_tree_verify_cpu.py bind depths / anc_masks to
+the host's tree_nodes on the CPU (tests/cpp/test_rows_plan, a plain g++ program over that header)."""
 import numpy as np
 
 MAX_NODES = 16
