@@ -30,7 +30,8 @@ mc_decoder::~mc_decoder()
 void
 mc_decoder::query_occupancy()
 {
-    if (tb != 2 || occ_fused >= 0) return;
+    block_occupancy& occ = benv.occ;
+    if (tb != 2 || occ.fused >= 0) return;
     auto ask = [&](const std::string& name, int block) {
         hipFunction_t f;
         if (fn(name, &f) != MC_OK) return 0;
@@ -38,16 +39,16 @@ mc_decoder::query_occupancy()
         if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&n, f, block, 0) != hipSuccess) return 0;
         return n;
     };
-    occ_fused = ask("mc_attn_fused_bfloat", 256);
+    occ.fused = ask("mc_attn_fused_bfloat", 256);
     const int hd = cfg.head_dim, k = cfg.n_heads * hd / 2048;
-    occ_wo = ask("mc_attn_wo_i4_bfloat_hd" + std::to_string(hd) + "_k" + std::to_string(k), 512);
-    occ_wo_w = hd == 64 ? ask("mc_attn_qkv_wo_w_bfloat_hd64_k4_q4", 512) : 0;
-    occ_wo_i8 = hd == 128 ? ask("mc_attn_qkv_wo_i8_bfloat_hd128_k4_q4_t4", 512) : 0;
-    occ_wo_qkn = hd == 256 ? ask("mc_attn_wo_qkn_i4_bfloat_hd256_k2_t2", 512) : 0;
-    occ_qkv_qkn = hd == 256 ? ask("mc_attn_qkv_wo_qkn_i4_bfloat_hd256_k2_p2_t2", 512) : 0;
-    occ_qkv_only = hd == 128 ? ask("mc_attn_qkv_i4_bfloat_hd128_q4", 512) : 0;
-    occ_wo_i4_wide = hd == 128 ? ask("mc_attn_qkv_wo_i4_bfloat_hd128_k2_q2_t4", 512) : 0;
-    occ_w13 = hd == 64 ? ask("mc_attn_qkv_wo_w13_w_bfloat_hd64_k4_q4_f4p4", 512) : 0;
+    occ.wo = ask("mc_attn_wo_i4_bfloat_hd" + std::to_string(hd) + "_k" + std::to_string(k), 512);
+    occ.wo_w = hd == 64 ? ask("mc_attn_qkv_wo_w_bfloat_hd64_k4_q4", 512) : 0;
+    occ.wo_i8 = hd == 128 ? ask("mc_attn_qkv_wo_i8_bfloat_hd128_k4_q4_t4", 512) : 0;
+    occ.wo_qkn = hd == 256 ? ask("mc_attn_wo_qkn_i4_bfloat_hd256_k2_t2", 512) : 0;
+    occ.qkv_qkn = hd == 256 ? ask("mc_attn_qkv_wo_qkn_i4_bfloat_hd256_k2_p2_t2", 512) : 0;
+    occ.qkv_only = hd == 128 ? ask("mc_attn_qkv_i4_bfloat_hd128_q4", 512) : 0;
+    occ.wo_i4_wide = hd == 128 ? ask("mc_attn_qkv_wo_i4_bfloat_hd128_k2_q2_t4", 512) : 0;
+    occ.w13 = hd == 64 ? ask("mc_attn_qkv_wo_w13_w_bfloat_hd64_k4_q4_f4p4", 512) : 0;
     // (one kernel per family is asked: the widest-range / most-register instantiation, which bounds the others -- every form is ONE 512-thread
     //  workgroup per CU, so the answer that matters is "at least one")
     (void)hipGetLastError();
@@ -59,224 +60,11 @@ mc_decoder::handoff_failed()
 {
     (void)hipMemsetAsync(&state->err, 0, 4, stream);
     (void)hipStreamSynchronize(stream);
-    attn_fused_on = false; // (handoffs_ok: every form of plan_block with a hand-off needs it)
+    attn_fused_on = false; // (block_plan.h handoffs_ok: every form of plan_block with a hand-off needs it)
     drop_graph();
     handoff_fallbacks++;
     clean_tokens = 0;
     if (handoff_fallbacks > 1 && rearm_after > 0 && rearm_after < (1 << 24)) rearm_after *= 2;
-}
-
-// ... with the Wo GEMV and its residual in the same launch (attn_block_kernels.hip): int4 weights on bfloat rows with scale
-// groups of whole lane blocks, K = H * hd of 1 or 2 KiB per row in one of the built (head_dim, K) pairs, no adaptor, at
-// most two row pairs per wave of the launch
-bool
-mc_decoder::attn_wo_fused(const linear_w& wo) const
-{
-    if (!opt.attn_wo_on || !attn_fused() || occ_wo == 0 || !lin_ok(wo) || wo.lora_cols || wo.out % 2 != 0) return false;
-    const int hd = cfg.head_dim, k = wo.in / 2048;
-    // (K = 8192, Llama-3-70B: measured slower than the two launches -- attn_block_kernels.hip)
-    const bool built = (hd == 128 && k == 2) || (hd == 64 && k == 1) || (hd == 256 && k == 2) || (hd == 128 && k == 4 && opt.attn_wo_k4);
-    // (one 512-thread workgroup per CU: the kernels hold up to 132 VGPRs, two such workgroups would not be resident together)
-    return built && wo.in == cfg.n_heads * hd && (unsigned)wo.out / 2 <= 2u * 8u * (unsigned)(nsplit * cfg.n_kv_heads) &&
-           (unsigned)(nsplit * cfg.n_kv_heads) <= (unsigned)dev->prop.multiProcessorCount;
-}
-
-// ... and for the launches that are the attention ALONE (mc_attn_fused_T: no GEMV phase that needs every workgroup of the
-// grid) any other head count is dealt with a stride of the next multiple of 8 -- bit 1 of the kernel's `fastpath` argument; the
-// grid is nsplit x that stride and the workgroups without a head leave at once -- when the heads that then share an XCD
-// still fit its CUs
-uint32_t
-mc_decoder::handoff_mode_alone() const
-{
-    if (!opt.handoff_fast) return 0u;
-    const unsigned KV = (unsigned)cfg.n_kv_heads;
-    if (KV % 8u == 0u) return 1u;
-    const bool fits = (unsigned)nsplit * ((KV + 7u) / 8u) <= fused_wgs_per_cu() * (unsigned)dev->prop.multiProcessorCount / 8u;
-    return fits ? 3u : 0u;
-}
-
-// VIRTUAL kv heads of the launches with wq|wk|wv inside (decode_kernels.hip attn_fused_bf, kv_shift): a model with 1, 2 or 4 kv heads is
-// launched as 8 heads of n_rep / (8 / KV) query heads each, 8 / KV of them on one cache head -- a workgroup on every CU, a virtual
-// head's ranges on one XCD.  Returns log2 of the heads per cache head (0: the real heads).
-int
-mc_decoder::kv_virtual_shift() const
-{
-    const int KV = cfg.n_kv_heads, n_rep = cfg.n_heads / KV;
-    if (!opt.kv_virtual_on || KV >= 8 || 8 % KV != 0 || n_rep % (8 / KV) != 0) return 0;
-    return KV == 4 ? 1 : (KV == 2 ? 2 : 3);
-}
-
-// The fewest 64-slot tiles per range among `cands` with WHOLE ranges (nsplit / t of them per head, `heads` heads) on at most one workgroup per
-// CU that `ok(t, ns, grid)` takes; 0 = none.
-// (wide ranges of a cache that is not whole ranges long -- S = 4040 -- would leave a ragged last range: refused here; the form such a
-//  context takes instead is pinned by tests/test_context_gpu.py::test_contexts_of_partial_ranges_against_the_oracle_and_the_form_they_take.
-//  64-slot ranges with a short last one are taken: tests/test_attn_kernels_gpu.py runs them at S = 2040)
-template <typename F> int
-mc_decoder::whole_range_tiles(std::initializer_list<int> cands, int heads, F&& ok) const
-{
-    for (int t : cands) {
-        if (nsplit % t || (t > 1 && cfg.max_seq_len % (64 * t))) continue;
-        const int ns = nsplit / t;
-        const unsigned grid = (unsigned)(ns * heads);
-        if (grid <= (unsigned)dev->prop.multiProcessorCount && ok(t, ns, grid)) return t;
-    }
-    return 0;
-}
-
-// ffn_norm + w1|w3 + act*mul as the next phase of the plain-weight block's launch (round 6, mc_attn_qkv_wo_w13_w_bfloat_hd64_k4_q4_f{3p3,4p4}, attn_block_kernels.hip):
-// behind the Wo phase half the waves of every workgroup fetch w1|w3 row pairs into registers while the other half waits for the hidden row.
-// For that block with 64-slot ranges on `grid` workgroups: exactly one workgroup per CU, w1|w3 plain bfloat with K = 2048, no adaptor.
-// Returns 10 F + P (pairs per fetcher wave, most pairs of a poller wave), 0 = no.
-int
-mc_decoder::chain_w13_fetch(const layer_w& L, unsigned grid) const
-{
-    if (!opt.chain_w13_on || occ_w13 <= 0 || L.w13.fmt != MC_WFMT_T || L.w13.lora_cols) return 0;
-    if (cfg.dim != 2048 || L.w13.in != 2048 || L.w13.out % 2 || grid != (unsigned)dev->prop.multiProcessorCount || opt.lin_waves != 8) return 0;
-    const unsigned nb = ((unsigned)L.w13.out / 2 + grid - 1) / grid; // pairs of the fullest workgroup
-    // (the fetchers F each, the pollers the rest, at most P each.  Returns 10 F + P.)
-    unsigned f = nb <= 24u ? 3u : 4u;
-    if (opt.chain_f >= 0) f = (unsigned)opt.chain_f; // (MC_CHAIN_F)
-    if (f < 1u || 4u * f > nb) return 0;
-    const unsigned p_ = (nb - 4u * f + 3u) / 4u; // the fullest poller
-    // built: f3p3 (22 pairs per workgroup: TinyLlama) and f4p4 (32: Llama-3.2-1B) -- the even deals, the measured best (attn_block_kernels.hip)
-    const unsigned pcap = f == 3u ? 3u : (f == 4u ? 4u : 0u);
-    return pcap && p_ <= pcap ? (int)(10u * f + pcap) : 0;
-}
-
-mc_decoder::block_plan
-mc_decoder::plan_block(const layer_w& L) const
-{
-    // The forms in priority order: the first whose conditions hold is the block's.
-    //   1. plain weights, the whole chain: mc_attn_qkv_wo_w13_w_* (only where form 2 has 64-slot ranges)
-    //   2. mc_attn_qkv_wo_w_* (_t2 / _t4)
-    //   3. mc_attn_qkv_wo_i8_*_t{1,2,4}
-    //   4. mc_attn_qkv_wo_i4_*
-    //   5. ... with wide ranges, _t{2,4}
-    //   6. llama only: mc_attn_qkv_i4_*_hd128_q4, then Wo as a GEMV
-    //   7. llama: the wq|wk|wv GEMV with the rope epilogue (p1_e4), then an attention tail
-    //   8. gemma3: mc_attn_qkv_wo_qkn_*_p{1,2}_t*
-    //   9. gemma3: the wq|wk|wv GEMV (p2_e0 while a post-norm is pending, else p1_e0), then an attention tail
-    // The attention tails of 7 and 9:
-    //   a. mc_attn_wo_qkn_* (gemma3, head_dim 256)
-    //   b. mc_attn_wo_i4_*
-    //   c. mc_attn_fused (_qkn where gemma3's norms go inside, otherwise behind mc_rope_kv)
-    //   d. mc_attn_fused_t2
-    //   e. scores + P.V, the range sums folded into Wo's prologue or reduced by their own launch
-    // 1 - 5 and 8 end behind Wo (llama: + residual, in `hidden`; gemma3: in `proj`), so do a and b; the others leave the attention row to a Wo GEMV.
-    const bool gemma = cfg.family == MC_FAMILY_GEMMA3;
-    const int H = cfg.n_heads, KV = cfg.n_kv_heads, hd = cfg.head_dim, n_rep = H / KV;
-    const int pg = (n_rep + 2) * hd / 2; // row pairs of wq|wk|wv per kv head (deal_ok)
-    const linear_w &qkv = L.qkv, &wo = L.wo;
-    // ---- the shared gates
-    const bool fused = attn_fused(); // (implies handoffs_ok)
-    const bool qkv_rows_ok = qkv.out == (H + 2 * KV) * hd, wo_rows_ok = wo.in == H * hd && wo.out % 2 == 0;
-    // wq|wk|wv AND Wo inside the attention launch (1 - 5): both switches, no adaptor on either matrix, llama
-    const bool qkv_wo_in = handoffs_ok() && opt.attn_qkv_on && opt.attn_wo_on && !gemma && !qkv.lora_cols && !wo.lora_cols && qkv_rows_ok && wo_rows_ok;
-    // ... int4, the built shape (Llama-3-8B: rows of 2 KiB, mc_attn_qkv_wo_i4_bfloat_hd128_k2_q2*)
-    const bool i4_shape = lin_ok(wo) && lin_ok(qkv) && hd == 128 && wo.in == 4096 && qkv.in == 4096 && qkv.group == wo.group && n_rep <= 16;
-    block_plan P;
-    // (the name is built by the arm that returns, and moved: no string is made for a form that is not taken)
-    auto one_launch = [&](block_form form, int tiles, int vsh, std::string name) -> block_plan&& {
-        P.form = form;
-        P.name = std::move(name);
-        P.tiles = tiles;
-        P.vsh = vsh;
-        P.ns = nsplit / tiles;
-        P.grid = (unsigned)(P.ns * (KV << vsh));
-        P.fast = (vsh ? opt.handoff_fast : handoff_fast_here()) ? 1u : 0u;
-        return std::move(P);
-    };
-
-    // 1, 2: PLAIN bfloat weights (mc_attn_qkv_wo_w_bfloat_hd64_k4_q4: Llama-3.2-1B, the reference's default model): rows of 4 KiB (K = 2048), at most
-    // ONE row pair per wave in either GEMV phase; fewer than 8 kv heads are launched as 8 virtual ones.  64-slot ranges (S <= 2048) or, round 5, 128- / 256-slot
-    // ranges at S = 4096 / 8192 (_t{2,4}; they share MC_ATTN_I4_WIDE with the int4 form)
-    if (qkv_wo_in && qkv.fmt == MC_WFMT_T && wo.fmt == MC_WFMT_T && occ_wo_w != 0 && hd == 64 && wo.in == 2048 && qkv.in == 2048) {
-        const int vsh = kv_virtual_shift(), pgv = ((n_rep >> vsh) + 2) * hd / 2;
-        const int t = (n_rep >> vsh) > 16 || pgv < 64 || pgv > 512 ? 0 : whole_range_tiles({1, 2, 4}, KV << vsh, [&](int t_, int ns, unsigned grid) {
-            return (t_ == 1 ? fused : opt.attn_i4_wide_on) && deal_ok(pgv, ns, 8) && (unsigned)wo.out / 2 <= 8u * grid;
-        });
-        const int chain = t == 1 ? chain_w13_fetch(L, (unsigned)(nsplit * (KV << vsh))) : 0;
-        if (chain) {
-            P.chain_f = chain / 10;
-            P.chain_p = chain % 10;
-            return one_launch(block_form::qkv_wo_w13_w, 1, vsh, "mc_attn_qkv_wo_w13_w_bfloat_hd64_k4_q4_f" + std::to_string(P.chain_f) + "p" + std::to_string(P.chain_p));
-        }
-        if (t) return one_launch(block_form::qkv_wo_w, t, vsh, std::string("mc_attn_qkv_wo_w_bfloat_hd64_k4_q4") + (t > 1 ? "_t" + std::to_string(t) : std::string()));
-    }
-    // 3: INT8 weights (round 5, mc_attn_qkv_wo_i8_bfloat_hd128_k4_q4_t{1,4}: Llama-3-8B int8): rows of 4 KiB (K = 4096),
-    // one 512-thread workgroup per CU -- 64-slot ranges up to S = 2048 (t1), 256-slot ranges at S = 8192 (t4: 32 ranges x 8 kv heads)
-    if (qkv_wo_in && opt.attn_i8_on && qkv.fmt == MC_WFMT_I8 && wo.fmt == MC_WFMT_I8 && occ_wo_i8 != 0) {
-        auto group_ok = [](const linear_w& W) { return W.group == 0 || (W.group >= 16 && (W.group & (W.group - 1)) == 0); };
-        const bool built = group_ok(qkv) && group_ok(wo) && qkv.group == wo.group && hd == 128 && wo.in == 4096 && qkv.in == 4096 && KV % 8 == 0 && n_rep <= 16;
-        const int t = !built ? 0 : whole_range_tiles({1, 2, 4}, KV, [&](int, int ns, unsigned grid) {
-            return deal_ok(pg, ns, 16) && (unsigned)wo.out / 2 <= 8u * grid;
-        });
-        if (t) return one_launch(block_form::qkv_wo_i8, t, 0, "mc_attn_qkv_wo_i8_bfloat_hd128_k4_q4_t" + std::to_string(t));
-    }
-    if (qkv_wo_in && i4_shape) {
-        auto name = [&] { return "mc_attn_qkv_wo_i4_" + tname + "_hd128_k" + std::to_string(wo.in / 2048) + "_q" + std::to_string(qkv.in / 2048); };
-        // 4: INT4 (attn_block_kernels.hip qkv_in_launch): where Wo goes into the launch of 64-slot ranges (attn_wo_fused), the kv head's row pairs
-        // dealt over its nsplit workgroups, at most two per wave
-        if (attn_wo_fused(wo) && deal_ok(pg, nsplit, 16) && pg >= 64 && pg <= 512) return one_launch(block_form::qkv_wo_i4, 1, 0, name());
-        // 5: ... with WIDE ranges (round 5, mc_attn_qkv_wo_i4_bfloat_hd128_k2_q2_t{2,4}): contexts whose 64-slot ranges are more workgroups
-        // than CUs -- Llama-3-8B at S = 4096 / 8192 -- as 128- / 256-slot ranges, one 512-thread workgroup per CU
-        const int t = !opt.attn_i4_wide_on || occ_wo_i4_wide == 0 || KV % 8 != 0 ? 0 : whole_range_tiles({2, 4}, KV, [&](int, int ns, unsigned grid) {
-            return deal_ok(pg, ns, 16) && pg >= 64 && (unsigned)wo.out / 2 <= 16u * grid;
-        });
-        if (t) return one_launch(block_form::qkv_wo_i4, t, 0, name() + "_t" + std::to_string(t));
-    }
-    // 6: wq|wk|wv in the launch WITHOUT Wo (round 5, mc_attn_qkv_i4_bfloat_hd128_q4: Llama-3-70B -- its Wo rows of 4 KiB stay a GEMV, attn_wo_fused): rows of
-    // 4 KiB for wq|wk|wv too (K = 8192), up to three pairs per wave, the kv head's pairs gathered in two passes of 512.  MC_ATTN_QKV_ONLY=1 only.
-    if (!gemma && fused && opt.attn_qkv_on && opt.attn_qkv_only_on && occ_qkv_only != 0 && lin_ok(qkv) && !qkv.lora_cols && qkv_rows_ok && qkv.in == 8192 &&
-        cfg.dim == 8192 && hd == 128 && KV % 8 == 0 && (unsigned)(nsplit * KV) <= (unsigned)dev->prop.multiProcessorCount && n_rep <= 16 && pg <= 1024 &&
-        deal_ok(pg, nsplit, 24) && pg / nsplit >= 8) {
-        P.wo_gemv = true;
-        return one_launch(block_form::qkv_only, 1, 0, "mc_attn_qkv_i4_" + tname + "_hd128_q4");
-    }
-    // gemma3 (round 5): q_norm / k_norm + rotation + cache write + attention + Wo in ONE launch from the raw wq|wk|wv rows
-    // (mc_attn_wo_qkn_i4_bfloat_hd256_k2_t{1,2,4}: one 512-thread workgroup per CU, whole ranges of 64, 128 or 256 slots -- S = 1024, 2048, 4096 at
-    // Gemma-7B's 16 kv heads, 16 x 16 workgroups at S = 2048)
-    int qkn_tiles = 0;
-    if (gemma && handoffs_ok() && opt.attn_wo_qkn_on && opt.attn_wo_on && opt.attn_qkn_on && hd == 256 && occ_wo_qkn != 0 && lin_ok(wo) && !wo.lora_cols &&
-        wo_rows_ok && wo.in == 4096 && n_rep <= 16)
-        qkn_tiles = whole_range_tiles({1, 2, 4}, KV, [&](int t_, int, unsigned grid) {
-            return (t_ > 1 || cfg.max_seq_len % 64 == 0) && (unsigned)wo.out / 2 <= 2u * 8u * grid;
-        });
-    // 8: ... with wq|wk|wv and the block's norms in the launch too (mc_attn_qkv_wo_qkn_i4_bfloat_hd256_k2_p{1,2}_t*, attn_block_kernels.hip
-    // qkv_qkn_in_launch): rows of 1.5 KiB (K = 3072), the kv head's rotation pairs dealt evenly over its ranges, at most three per wave, one thread
-    // per pair in the hand-off.  _p2: the previous block's ffn post-norm + residual is its prologue.
-    if (qkn_tiles && opt.attn_qkv_qkn_on && opt.attn_qkv_on && occ_qkv_qkn != 0 && lin_split_ok(qkv) && !qkv.lora_cols && qkv.in == 3072 && cfg.dim == 3072 &&
-        qkv.group == wo.group && qkv_rows_ok && pg <= 512 && deal_ok(pg, nsplit / qkn_tiles, 24))
-        return one_launch(block_form::qkv_wo_qkn, qkn_tiles, 0,
-                          "mc_attn_qkv_wo_qkn_i4_" + tname + "_hd256_k2_p" + (pending_pn ? "2" : "1") + "_t" + std::to_string(qkn_tiles));
-
-    // 7, 9: wq|wk|wv as a GEMV, then the tail
-    P.qkv_gemv = true;
-    if (qkn_tiles) return one_launch(block_form::wo_qkn, qkn_tiles, 0, "mc_attn_wo_qkn_i4_" + tname + "_hd256_k2_t" + std::to_string(qkn_tiles)); // a
-    // (gemma3 normalises q and k per head before the rotation, attention.h:174-175: that needs whole heads, so rope + cache write are a launch of
-    //  their own -- except inside the one-launch attention where that is what follows: mc_attn_fused_qkn_bfloat, decode_kernels.hip q_from_qkv_rows)
-    P.rope_kv = gemma;
-    if (attn_wo_fused(wo)) return one_launch(block_form::wo_i4, 1, 0, "mc_attn_wo_i4_" + tname + "_hd" + std::to_string(hd) + "_k" + std::to_string(wo.in / 2048)); // b
-    P.wo_gemv = true;
-    if (fused) { // c
-        if (gemma && opt.attn_qkn_on && (hd == 128 || hd == 256)) {
-            P.rope_kv = false;
-            return one_launch(block_form::fused_qkn, 1, 0, "mc_attn_fused_qkn_" + tname);
-        }
-        one_launch(block_form::fused, 1, 0, "mc_attn_fused_" + tname);
-        P.fast = handoff_mode_alone();
-        P.grid = (unsigned)nsplit * ((P.fast & 2u) ? ((unsigned)KV + 7u) & ~7u : (unsigned)KV);
-        return P;
-    }
-    if (attn_fused_t2()) { // d
-        one_launch(block_form::fused_t2, 2, 0, "mc_attn_fused_t2_" + tname);
-        P.fast = opt.handoff_fast ? 1u : 0u;
-        return P;
-    }
-    P.form = block_form::scores_pv; // e
-    P.name = "mc_attn_scores_" + tname;
-    P.pv_fold = pv_fold(wo);
-    return P;
 }
 
 // a hand-off inside a launch that gave up (bounded waits, decode_kernels.hip): reported once, then cleared
@@ -335,7 +123,7 @@ mc_status
 mc_decoder::gemv(const linear_w& L, int pro, int epi, const void* x, void* y, const void* res,
      const void* norm_w, float mu)
 {
-    const gemv_plan P = plan_gemv(shape_of(L), genv, pro, epi);
+    const gemv_plan P = plan_gemv(shape_of(L), benv.g, pro, epi);
     if (P.error) return fail(MC_ERR_RUNTIME, P.error);
     if (L.lora_cols) {
         // a = T(A x): the stacked adaptor inputs through the same kernel family (same prologue,
@@ -532,16 +320,14 @@ mc_decoder::run_layers(const void* x_in)
                        pack(q_rot, L.kc, expv, psum, (void*)nullptr, state, (uint32_t)n_rep,
                             (uint32_t)hd, (uint32_t)cfg.max_seq_len, scale_T, (uint32_t)nsplit));
             if (s != MC_OK) return s;
-            // softmax normalisation + P.V          (attention.h:200-203)
-            const int ranges = P.pv_fold ? 4 : pv_ranges;
-            // folded: one round of loads per wave (four k-steps of 32 slots each)
-            const int fold_waves = std::max(4, std::min(16, ((cfg.max_seq_len + 31) / 32 / 4 + 3) / 4));
-            s = launch("mc_attn_pv_" + tname, hd / 16, KV, ranges, P.pv_fold ? 64 * fold_waves : opt.pv_block, 0,
+            // softmax normalisation + P.V          (attention.h:200-203): over P.pv_ranges ranges of cache slots, their sums folded into Wo's prologue
+            // or added by a launch of their own (block_plan.h)
+            s = launch("mc_attn_pv_" + tname, hd / 16, KV, P.pv_ranges, P.pv_block, 0,
                        pack(expv, psum, L.vt, attn_out, state, (uint32_t)n_rep, (uint32_t)hd,
                             (uint32_t)cfg.max_seq_len, (uint32_t)nsplit, pv_parts, (uint32_t)H));
-            if (s == MC_OK && ranges > 1 && !P.pv_fold)
+            if (s == MC_OK && P.pv_reduce)
                 s = launch("mc_attn_pv_reduce_" + tname, (H * hd + 255) / 256, 1, 1, 256, 0,
-                           pack((const void*)pv_parts, attn_out, (uint32_t)(H * hd), (uint32_t)ranges));
+                           pack((const void*)pv_parts, attn_out, (uint32_t)(H * hd), (uint32_t)P.pv_ranges));
             break;
         }
         }
@@ -765,7 +551,6 @@ mc_decoder_create(mc_device* dev, mc_library* lib, mc_queue* q, const mc_decoder
     d->first_stage = c.layer_begin == 0;
     d->last_stage = c.layer_end == c.n_layers;
     d->opt = read_options();
-    d->genv = gemv_env{d->tb, (int)c.qmode, (unsigned)dev->prop.multiProcessorCount, mc_decoder::pick_slots, &d->opt};
     d->attn_fused_on = d->opt.attn_fused;
     d->rearm_after = d->opt.rearm_after;
     d->pf_lib_on = d->opt.pf_lib;
@@ -801,6 +586,9 @@ mc_decoder_create(mc_device* dev, mc_library* lib, mc_queue* q, const mc_decoder
         A(d->attn_hid_g, (size_t)dim / 2 * 8);
         A(d->attn_qkv_g, (size_t)(H + 2 * std::max(KV, 8)) * hd / 2 * 8 * 2); // (virtual kv heads: a K and a V row per virtual head)
     }
+    // what the plans of the decode launches see of this decoder (gemv_plan.h, block_plan.h); the occupancy answers follow with the first step
+    d->benv = block_env{gemv_env{d->tb, (int)c.qmode, (unsigned)dev->prop.multiProcessorCount, mc_decoder::pick_slots, &d->opt}, d->nsplit, d->n_own,
+                        d->attn_psum_g != nullptr, d->pv_ranges, d->tname, block_occupancy{}};
     A(d->taps, (size_t)(d->n_own + 1) * dim * tb);
     A(d->state, sizeof(step_state));
     A(d->state_bak, sizeof(step_state));
@@ -954,7 +742,7 @@ mc_decoder_step(mc_decoder* d, int32_t token, int32_t start_pos, const void* hid
     if (s != MC_OK) return s;
     d->query_occupancy();
     for (int attempt = 0;; attempt++) {
-        const bool handoffs = d->attn_fused() || d->attn_fused_t2();
+        const bool handoffs = d->uses_handoffs();
         // (a step whose hand-offs give up is repeated on the launches that need no co-residency: the state in front of it)
         if (handoffs) MC_HIP(hipMemcpyAsync(d->state_bak, d->state, sizeof(step_state), hipMemcpyDeviceToDevice, d->stream));
         s = d->ensure_rope(start_pos);
@@ -1006,7 +794,7 @@ mc_decoder_generate(mc_decoder* d, int32_t first_token, int32_t start_pos, int32
     s = d->poll_pending_err();
     if (s != MC_OK) return s;
     d->query_occupancy();
-    const bool handoffs = d->attn_fused() || d->attn_fused_t2();
+    const bool handoffs = d->uses_handoffs();
     if (handoffs) MC_HIP(hipMemcpyAsync(d->state_bak, d->state, sizeof(step_state), hipMemcpyDeviceToDevice, d->stream));
     s = d->ensure_rope(start_pos);
     if (s != MC_OK) return s;
@@ -1261,7 +1049,7 @@ timed_gemvs(mc_decoder* d, const std::string& w)
     std::vector<timed_gemv> all;
     for (size_t li = 0; li < d->layers.size(); li++) {
         const layer_w& L = d->layers[li % lim];
-        const bool fold = !d->attn_fused() && !d->attn_fused_t2() && d->pv_fold(L.wo);
+        const bool fold = !d->uses_handoffs() && pv_fold(mc_decoder::shape_of(L.wo), d->model(), d->benv);
         all.push_back({"qkv", &L.qkv, 1, gemma ? 0 : 4, d->hidden, d->qkv, gemma ? nullptr : L.qkv_epi, L.attention_norm});
         all.push_back({"wo", &L.wo, fold ? 3 : 0, gemma ? 0 : 1, fold ? (const void*)d->pv_parts : (const void*)d->attn_out, d->proj, gemma ? nullptr : d->hidden, nullptr});
         all.push_back({"w13", &L.w13, 1, gemma ? 3 : 2, d->hidden, d->gate, nullptr, L.ffn_norm});
@@ -1288,8 +1076,8 @@ mc_decoder_gemv_kernel_name(mc_decoder* d, const char* which, char* buf, size_t 
         if (s0 != MC_OK) return s0;
         if (d->layers.empty()) return fail(MC_ERR_INVALID_ARGUMENT, "mc_decoder_gemv_kernel_name: this stage owns no block");
         d->query_occupancy();
-        const mc_decoder::block_plan P = d->plan_block(d->layers[0]);
-        name = P.form == mc_decoder::block_form::scores_pv ? P.name + " + mc_attn_pv_" + d->tname : P.name;
+        const block_plan P = d->plan_block(d->layers[0]);
+        name = P.form == block_form::scores_pv ? P.name + " + mc_attn_pv_" + d->tname : P.name;
         const size_t n0 = std::min(cap - 1, name.size());
         memcpy(buf, name.data(), n0);
         buf[n0] = 0;
@@ -1300,7 +1088,7 @@ mc_decoder_gemv_kernel_name(mc_decoder* d, const char* which, char* buf, size_t 
     const std::vector<timed_gemv> table = timed_gemvs(d, which);
     if (table.empty()) return fail(MC_ERR_INVALID_ARGUMENT, std::string("mc_decoder_gemv_kernel_name: no such GEMV '") + which + "'");
     const timed_gemv& g = table.front();
-    const gemv_plan P = plan_gemv(mc_decoder::shape_of(*g.L), d->genv, g.pro, g.epi);
+    const gemv_plan P = plan_gemv(mc_decoder::shape_of(*g.L), d->benv.g, g.pro, g.epi);
     if (P.error) return fail(MC_ERR_RUNTIME, P.error);
     const size_t n = std::min(cap - 1, P.name.size());
     memcpy(buf, P.name.data(), n);

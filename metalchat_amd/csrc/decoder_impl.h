@@ -1,19 +1,20 @@
 // The decoder behind Part 2 of include/metalchat_hip.h, as its five translation units see it: the fused weights (linear_w, layer_w), the
 // greedy pick's descriptors (pick_block) and struct mc_decoder -- its state, the small helpers every unit calls inline, and the
 // declarations of everything else.  Which unit defines what:
-//   decoder.cc         the decode block plan (plan_block), the per-token decode, the hand-off fall-back, the C ABI of a step
+//   decoder.cc         the per-token decode -- it launches what block_plan.h plans for the attention block -- the hand-off fall-back, the C ABI of a step
 //   weights.cc         allocation and upload of the fused matrices, the synthetic model
 //   prefill.cc         the prompt pass (run_prefill): it launches what prefill_plan.h plans -- GEMM family, attention, rope form, folds; no HIP there
 //   prefill_blaslt.cc  the library GEMM of long prompts -- the only unit that sees hipBLASLt's header
 //   pipeline.cc        the layer pipeline (RCCL / local); it holds decoders, it is not part of one
-// batch.cc does not include this header: it reads a decoder through decoder_batch.h.  Three headers beside the units need no device and are pinned
-// on the CPU by plain g++ programs (tests/cpp): gemv_plan.h (the decode GEMV), prefill_plan.h (the prompt pass) and rows_plan.h (the admission
-// and the tables of batch.cc's rows passes).
+// batch.cc does not include this header: it reads a decoder through decoder_batch.h.  Four headers beside the units need no device and are pinned
+// on the CPU by plain g++ programs (tests/cpp): gemv_plan.h (the decode GEMV), block_plan.h (the decode attention block), prefill_plan.h (the prompt
+// pass) and rows_plan.h (the admission and the tables of batch.cc's rows passes).
 #pragma once
 
 #include "backend_impl.h"
 #include "decoder_batch.h"
 #include "gemv_plan.h" // decoder_options / read_options (decoder_options.h) and plan_gemv
+#include "block_plan.h" // plan_block: form, kernel and grid of the decode attention block
 #include "prefill_plan.h" // plan_gemm, plan_attention, plan_rope and the fold predicates of the prompt pass
 
 #include <algorithm>
@@ -23,7 +24,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <initializer_list>
 #include <map>
 #include <memory>
 #include <string>
@@ -185,7 +185,6 @@ struct mc_decoder {
     unsigned long long* attn_slab_g = nullptr; // [KV][nsplit][n_rep][hd] fp32 partial P.V sums
     unsigned long long* attn_row_g = nullptr;  // [H * hd / 2]          the finished attention row, two bf16 per granule (mc_attn_wo_*)
     unsigned long long* attn_hid_g = nullptr;  // [dim / 2]             the hidden row behind Wo, for the w1|w3 phase of mc_attn_qkv_wo_w13_w_* (hand-off D)
-    int occ_w13 = -1;
     unsigned long long* attn_qkv_g = nullptr;  // [KV][(n_rep + 2) hd / 2] the step's rotated queries and K / V row, two bf16 per granule (mc_attn_qkv_wo_*)
     // ---- what happens when an in-launch hand-off gives up (its workgroups were not resident together: another stream or process
     // holds part of the chip).  The launch sets state.err and completes; the host then LATCHES the decoder onto the launches
@@ -212,7 +211,6 @@ struct mc_decoder {
         handoff_rearms++;
         drop_graph(); // (captured with the launches that need no co-residency)
     }
-    int occ_fused = -1, occ_wo = -1, occ_wo_w = -1, occ_wo_i8 = -1, occ_wo_qkn = -1, occ_qkv_qkn = -1, occ_qkv_only = -1, occ_wo_i4_wide = -1;   // co-resident workgroups per CU of the hand-off launches (the occupancy API's answer; -1: not asked yet)
     bool attn_fused_on = true;   // opt.attn_fused, until a hand-off gives up (handoff_failed) and again after rearm_after clean tokens (note_clean_tokens)
     void* taps = nullptr;       // T[(n_own+1)*dim]
     step_state* state = nullptr;
@@ -365,94 +363,28 @@ struct mc_decoder {
     mc_status upload_rows(linear_w& L, int dst_row0, int dst_stride, int rows, const void* weight, const float* scales, int perm_hd = 0);
 
     // ---------------------------------------------------------------- launches
-    // which kernel a decode GEMV takes is decided in gemv_plan.h (plan_gemv); these three gates of it are also what the launches around a GEMV ask
-    gemv_env genv{}; // fixed at create time
+    // Which kernel a decode GEMV takes is decided in gemv_plan.h (plan_gemv), what the attention block launches in block_plan.h (plan_block): both
+    // over this view of the decoder -- benv.g is the GEMV's part of it -- fixed at create time but for the occupancy answers (query_occupancy).
+    block_env benv{};
     static gemv_shape
     shape_of(const linear_w& L) { return {L.fmt, L.out, L.in, L.group, L.lora_cols}; }
+    // (these gates of plan_gemv are also what the launches around a GEMV ask)
     bool
-    lin_ok(const linear_w& L) const { return ::lin_ok(shape_of(L), genv); }
-    bool
-    lin_split_ok(const linear_w& L) const { return ::lin_split_ok(shape_of(L), genv); }
+    lin_ok(const linear_w& L) const { return ::lin_ok(shape_of(L), benv.g); }
     int
-    ling_kib(const linear_w& L) const { return ::ling_kib(shape_of(L), genv); }
-    // P.V over four ranges of cache slots (256 workgroups instead of 64: a CU takes in ~ 25 GB/s, and 64 of them need
-    // ~ 4 us for the V cache of one layer at S = 2048) with the range sums added by the Wo GEMV's prologue (gemv.h
-    // PRO_PARTS) instead of a reduce launch
+    ling_kib(const linear_w& L) const { return ::ling_kib(shape_of(L), benv.g); }
+    block_model
+    model() const { return {(int)cfg.family, cfg.n_heads, cfg.n_kv_heads, cfg.head_dim, cfg.dim, cfg.max_seq_len}; }
+    block_state
+    block_now() const { return {attn_fused_on, pending_pn != nullptr}; }
+    block_plan
+    plan_block(const layer_w& L) const { return ::plan_block({shape_of(L.qkv), shape_of(L.wo), shape_of(L.w13)}, model(), benv, block_now()); }
+    // may a hand-off of the next launches give up?  (the step in front of them is then kept for the retry)
     bool
-    pv_fold(const linear_w& wo) const
-    {
-        return opt.pv_fold_on && (lin_ok(wo) || ling_kib(wo)) && !wo.lora_cols && cfg.max_seq_len <= 16384;
-    }
-
-    // ---------------------------------------------------------------- the decode attention block: which launches (plan_block)
-    // The gates every launch with an in-launch hand-off shares: the switch (MC_ATTN_FUSED, and the latch of handoff_failed), bfloat rows -- the granule
-    // buffers attn_psum_g / attn_slab_g / attn_row_g / attn_qkv_g / attn_hid_g exist for them only, all or none (mc_decoder_create) -- and layer tags of one byte
-    bool
-    handoffs_ok() const { return attn_fused_on && attn_psum_g && tb == 2 && n_own <= 254; }
-    // 256-thread attention workgroups per CU that may wait for one another.
-    // Co-residency from what a CU can HOLD of the real kernel (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor, asked once:
-    // query_occupancy), capped by what was measured to pay (opt.attn_fused_max_wgs_per_cu).  The API is advisory (ROCm 7.2 reads
-    // one block per CU high for SGPR-heavy 256-thread kernels, MI355X_MICROARCH.md), and another stream can take CUs away
-    // at any time: a launch that is not resident after all gives up and the host falls back (handoff_failed).
-    unsigned
-    fused_wgs_per_cu() const { return std::min(opt.attn_fused_max_wgs_per_cu, occ_fused < 0 ? opt.attn_fused_max_wgs_per_cu : (unsigned)occ_fused); }
-    // scores + softmax + P.V in one launch: bfloat rows, layer tags of one byte, and a grid that is certainly co-resident (its
-    // workgroups wait for one another) and gathers from few producers: at most opt.attn_fused_max_wgs_per_cu 256-thread workgroups
-    // of 64 cache slots per CU
-    bool
-    attn_fused() const
-    {
-        return handoffs_ok() && (unsigned)(nsplit * cfg.n_kv_heads) <= fused_wgs_per_cu() * (unsigned)dev->prop.multiProcessorCount;
-    }
-    // ... with 128-slot ranges (mc_attn_fused_t2_bfloat: two score tiles per wave) where the 64-slot ranges are too many workgroups to
-    // be resident together -- Llama-3-8B at S = 8192: 1024 -> 512.  Round 3 measured that form at 14.8 us against 6.3 + 8.5 for
-    // the two launches; with the XCD-local hand-offs of round 4 it is re-measured (MC_ATTN_T2)
-    bool
-    attn_fused_t2() const
-    {
-        return opt.attn_t2_on && handoffs_ok() && !attn_fused() && nsplit % 2 == 0 &&
-               (cfg.head_dim == 128 || cfg.head_dim == 64) && cfg.n_kv_heads % 8 == 0 &&
-               (unsigned)(nsplit / 2 * cfg.n_kv_heads) <= fused_wgs_per_cu() * (unsigned)dev->prop.multiProcessorCount;
-    }
+    uses_handoffs() const { return block_uses_handoffs(model(), benv, block_now()); }
     // (decoder.cc, like every member declared from here to run_head)
     void query_occupancy();
     void handoff_failed();
-    bool attn_wo_fused(const linear_w& wo) const;
-
-    // The XCD-local fast path of hand-offs A / B / Q (handoff.h) pays where the workgroups of one kv head CAN share an XCD: they
-    // are the blocks b with equal b % n_kv, blocks with equal b % 8 share an XCD, so n_kv must be a multiple of 8.  With
-    // TinyLlama's 4 kv heads half of every head's ranges sit on another XCD and are found only by the occasional look at the
-    // fabric copy: mc_attn_fused_bfloat 24.1 us against 7.0 without the fast path (profiles/r04_kernel_stats_tinyllama_fastpath_regression.csv)
-    bool
-    handoff_fast_here() const { return opt.handoff_fast && cfg.n_kv_heads % 8 == 0; }
-    uint32_t handoff_mode_alone() const;
-    int kv_virtual_shift() const;
-
-    // The row-pair deal of the launches with wq|wk|wv inside: a kv head's (n_rep + 2) hd / 2 row pairs of wq|wk|wv (its query heads' rows, its K and
-    // its V row) go evenly over the head's `ns` workgroups, at most `cap` to each
-    static bool
-    deal_ok(int pg, int ns, int cap) { return pg % ns == 0 && pg / ns <= cap; }
-    template <typename F> int whole_range_tiles(std::initializer_list<int> cands, int heads, F&& ok) const; // (defined in front of plan_block, its one caller)
-    int chain_w13_fetch(const layer_w& L, unsigned grid) const;
-
-    // What run_layers() launches for the first half of one block -- from the row handed to the block to the finished attention row, or past Wo
-    // where the form holds it.  Computed per layer per eager step: the fall-back latch (handoff_failed), the re-arm (note_clean_tokens), taps and a
-    // late occupancy answer all change it between tokens.
-    enum class block_form { // (by the numbers of plan_block's list)
-        qkv_wo_w13_w, qkv_wo_w, qkv_wo_i8, qkv_wo_i4 /* 4, 5 */, qkv_only, qkv_wo_qkn /* 8 */,
-        wo_qkn, wo_i4, fused, fused_qkn, fused_t2, scores_pv // 7, 9 -- wq|wk|wv as a GEMV -- by their attention tail a - e
-    };
-    struct block_plan {
-        block_form form = block_form::scores_pv;
-        std::string name;     // the kernel of the form's attention launch
-        int tiles = 1, vsh = 0, ns = 1; // 64-slot tiles per range; log2 of the virtual kv heads per cache head (kv_virtual_shift); ranges per kv head: nsplit / tiles
-        unsigned grid = 0;    // workgroups of that launch
-        uint32_t fast = 0;    // its `fastpath` argument (handoff.h)
-        int chain_f = 0, chain_p = 0; // qkv_wo_w13_w: pairs per fetcher wave, most pairs of a poller wave
-        bool qkv_gemv = false, rope_kv = false; // wq|wk|wv is a GEMV in front of the launch (7, 9); ... and gemma3's q/k-norm + rope + cache write a launch of their own (mc_rope_kv_T) behind it
-        bool wo_gemv = false, pv_fold = false;  // Wo is a GEMV behind the launch; ... whose prologue adds the range sums of P.V (pv_fold)
-    };
-    block_plan plan_block(const layer_w& L) const;
 
     // ---------------------------------------------------------------- the hand-off reporting and the per-token decode (decoder.cc)
     mc_status check_handoffs(const step_state& st);

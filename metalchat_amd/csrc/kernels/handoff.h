@@ -6,7 +6,7 @@
 // an earlier launch is never mistaken for this one's and nothing has to be cleared between launches.  Every wait is bounded
 // (50 ms of s_memrealtime -- a launch is ~ 15 us, so 3000 x its length; round 4: 2 s): on expiry the launch sets state.err and carries on with what it has; later waits see the flag and do
 // not wait at all, and the host reports it (mc_decoder_generate / _step return MC_ERR_RUNTIME).  A launch whose workgroups wait
-// for one another must be co-resident: the host guarantees it (decoder.cc attn_fused(), attn_wo_fused(), chain_ok()).
+// for one another must be co-resident: the host guarantees it (block_plan.h attn_fused(), attn_wo_fused(), chain_w13_fetch()).
 #pragma once
 
 #include "abi.h"

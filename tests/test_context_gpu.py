@@ -528,7 +528,7 @@ def test_gemma_7b_widths_at_the_benchmark_context(acc, taps):
 
 @pytest.mark.parametrize("taps", [True, False])
 def test_gemma_with_128_slot_ranges_takes_the_gemma_epilogue_behind_the_attention(acc, taps, monkeypatch):
-    # gemma3 blocks whose attention is mc_attn_fused_t2_bfloat (decoder.cc plan_block, tail d): head_dim 128 and 16 kv heads at S = 4096 are
+    # gemma3 blocks whose attention is mc_attn_fused_t2_bfloat (block_plan.h plan_block, tail d): head_dim 128 and 16 kv heads at S = 4096 are
     # 64 x 16 workgroups of 64 slots -- more than two per CU -- and 32 x 16 = 512 of 128 slots, which fit (Gemma3-27B's widths have this shape).
     # Behind that launch Wo goes to `proj` and attention_post_norm (weights in [0.5, 1.5), not ones) + the residual follow: as a launch of their own
     # with taps, as the w1|w3 GEMV's prologue without.
@@ -1009,7 +1009,7 @@ PARTIAL_RANGE_FORMS = {
     # S = 2040: 32 ranges per kv head as at 2048 -- the one-launch blocks of the benchmark context, the last range 56 slots
     ("llama3-8b-int4", 2040): ({"mc_attn_qkv_wo_i4_bfloat_hd128_k2_q2"}, {"mc_attn_fused_bfloat", "mc_gemv_i4_bfloat_lin2_p1_e4"}),
     ("llama3-8b-int8", 2040): ({"mc_attn_qkv_wo_i8_bfloat_hd128_k4_q4_t1"}, {"mc_attn_fused_bfloat", "mc_gemv_i8_bfloat_ling4_p1_e4"}),
-    # (gemma3: decoder.cc plan_block, tail a, takes whole ranges only -- the attention with q_norm / k_norm inside, between the two GEMVs)
+    # (gemma3: block_plan.h plan_block, tail a, takes whole ranges only -- the attention with q_norm / k_norm inside, between the two GEMVs)
     ("gemma-7b", 2040): ({"mc_attn_fused_qkn_bfloat"}, set(QKV_WO)),
     # S = 1000: 16 ranges per kv head, as at 1024, and the same form as there -- so the steps up to the end of the cache are held BIT FOR BIT to a
     # decoder with S = 1024 on the same rows (kv_len 996 .. 1000: the last range 40 slots long) instead of the oracle: measured at 4.7e-3 (int4),
@@ -1025,7 +1025,7 @@ PARTIAL_RANGE_FORMS = {
     ("tinyllama", 1000): ({"mc_gemv_w_bfloat_ling4_p1_e4", "mc_attn_fused_bfloat"}, set(QKV_WO)),
     # (gemma3: 16 x 16 workgroups, one per CU -- the rope launch, then attention + Wo in one launch: round 4's form)
     ("gemma-7b", 1000): ({"mc_attn_wo_i4_bfloat_hd256_k2", "mc_rope_kv_bfloat"}, set(QKV_WO)),
-    # Where the wide ranges are refused (decoder.cc plan_block: forms 2, 3 and 5 take S % (64 t) == 0 only, whole_range_tiles;
+    # Where the wide ranges are refused (block_plan.h plan_block: forms 2, 3 and 5 take S % (64 t) == 0 only, whole_range_tiles;
     # attn_fused_t2 an even nsplit).  What the decoder takes today:
     #   S = 4040 (63 ranges and 8 slots: nsplit 64) and 4032 (63 whole ranges, odd): 64 / 63 x 8 workgroups of the one-launch attention between
     #   the wq|wk|wv and Wo GEMVs -- five launches per layer, where 4096 takes the three of `_t2`

@@ -57,14 +57,14 @@ def test_decode_and_reference_kernels_present(symbols):
             assert f"{k}_{t}" in symbols, f"{k}_{t}"
     for k in ("mc_step_set", "mc_step_advance", "mc_step_rope", "mc_rope_table", "mc_argmax_keys",
               "mc_attn_fused_bfloat",  # decode attention in one launch
-              # ... with the Wo GEMV behind it (decoder.cc attn_wo_fused: head_dim x KiB per Wo row)
+              # ... with the Wo GEMV behind it (block_plan.h attn_wo_fused: head_dim x KiB per Wo row)
               "mc_attn_wo_i4_bfloat_hd128_k2", "mc_attn_wo_i4_bfloat_hd64_k1", "mc_attn_wo_i4_bfloat_hd256_k2",
               "mc_attn_qkv_wo_i4_bfloat_hd128_k2_q2",  # wq|wk|wv, attention and Wo in one launch (round 4)
-              "mc_attn_qkv_wo_i4_bfloat_hd128_k2_q2_t2", "mc_attn_qkv_wo_i4_bfloat_hd128_k2_q2_t4",  # ... 128- / 256-slot ranges (decoder.cc plan_block, form 5)
-              "mc_attn_qkv_wo_w_bfloat_hd64_k4_q4",    # ... for plain bfloat weights (decoder.cc plan_block, form 2)
-              "mc_attn_qkv_wo_w13_w_bfloat_hd64_k4_q4_f3p3", "mc_attn_qkv_wo_w13_w_bfloat_hd64_k4_q4_f4p4",  # ... + ffn_norm + w1|w3 + act*mul (round 6: decoder.cc plan_block form 1, chain_w13_fetch)
+              "mc_attn_qkv_wo_i4_bfloat_hd128_k2_q2_t2", "mc_attn_qkv_wo_i4_bfloat_hd128_k2_q2_t4",  # ... 128- / 256-slot ranges (block_plan.h plan_block, form 5)
+              "mc_attn_qkv_wo_w_bfloat_hd64_k4_q4",    # ... for plain bfloat weights (block_plan.h plan_block, form 2)
+              "mc_attn_qkv_wo_w13_w_bfloat_hd64_k4_q4_f3p3", "mc_attn_qkv_wo_w13_w_bfloat_hd64_k4_q4_f4p4",  # ... + ffn_norm + w1|w3 + act*mul (round 6: block_plan.h plan_block form 1, chain_w13_fetch)
               "mc_gemv_i4_bfloat_lin12k4_p0_e0", "mc_gemv_i4_bfloat_lin12k4_p0_e1",  # Gemma-7B's w2: the K range of a pair over four waves (gemv_ksplit.h)
-              "mc_attn_qkv_i4_bfloat_hd128_q4",        # ... without Wo, rows of 4 KiB (Llama-3-70B; decoder.cc plan_block, form 6)
+              "mc_attn_qkv_i4_bfloat_hd128_q4",        # ... without Wo, rows of 4 KiB (Llama-3-70B; block_plan.h plan_block, form 6)
               "mc_attn_qkv_wo_i8_bfloat_hd128_k4_q4_t1", "mc_attn_qkv_wo_i8_bfloat_hd128_k4_q4_t2", "mc_attn_qkv_wo_i8_bfloat_hd128_k4_q4_t4",
               "mc_attn_qkv_wo_w_bfloat_hd64_k4_q4_t2", "mc_attn_qkv_wo_w_bfloat_hd64_k4_q4_t4",   # wide ranges of the plain-bfloat launch (plan_block, form 2)  # ... for int8 weights (plan_block, form 3)
               "mc_attn_fused_qkn_bfloat",              # gemma3: q/k-norm + rope + cache write inside the one-launch attention
@@ -72,7 +72,7 @@ def test_decode_and_reference_kernels_present(symbols):
               "mc_attn_qkv_wo_qkn_i4_bfloat_hd256_k2_p1_t2", "mc_attn_qkv_wo_qkn_i4_bfloat_hd256_k2_p2_t2",
               "mc_attn_qkv_wo_qkn_i4_bfloat_hd256_k2_p1_t1", "mc_attn_qkv_wo_qkn_i4_bfloat_hd256_k2_p2_t1",
               "mc_attn_qkv_wo_qkn_i4_bfloat_hd256_k2_p1_t4", "mc_attn_qkv_wo_qkn_i4_bfloat_hd256_k2_p2_t4", "mc_attn_wo_qkn_i4_bfloat_hd256_k2_t4",  # ... and wq|wk|wv + the norms (plan_block, form 8)
-              "mc_attn_fused_t2_bfloat",               # 128-slot ranges (decoder.cc attn_fused_t2: S = 8192)
+              "mc_attn_fused_t2_bfloat",               # 128-slot ranges (block_plan.h attn_fused_t2: S = 8192)
               # the prompt pass on the quad-interleaved weight copy and its consumers with the split-K reduce inside (round 4)
               "mc_pf2_repack_i4", "mc_pf2_gemm_i4_bfloat", "mc_pf_rope_cache_parts_bfloat", "mc_pf_rope_cache_v4_bfloat", "mc_pf_rope_cache_parts_v4_bfloat", "mc_pf_act_mul_parts_bfloat",
               "mc_pf_rmsnorm_parts_bfloat", "mc_pf_rmsnorm2_parts_bfloat", "mc_pf_splitk_reduce_bfloat",
@@ -89,6 +89,19 @@ def test_decode_and_reference_kernels_present(symbols):
     # the reference's own kernel names (ABI part 1, kernel/kernel.h:30-90)
     for k in ("rmsnorm_bfloat", "softmax_bfloat", "bmm_8_float", "hadamard_broadcast_bfloat_int8_t_float"):
         assert k in symbols, k
+
+
+def test_every_attention_block_kernel_the_plan_names_exists(symbols):
+    """plan_block() (csrc/block_plan.h) builds the name of the block's attention kernel from the form, the type, head_dim, the row lengths, the ranges
+    and the chain's deal: every name recorded in tests/golden/decode_block_plans.json, every name the header forms over the same sweep
+    (tests/cpp/test_block_plan) and every launch a real decoder made of them is in the code object."""
+    from block_plan_program import G, answers
+
+    names = {a.split()[1] for a in G["answers"]} | {a.split()[1] for a in answers()}
+    names |= {launch[0] for c in G["device_cases"].values() for launch in c["attn_launches"]}
+    assert len(names) > 12, names   # (at least one per form: test_block_plan_cpu.py holds the recording to every form)
+    missing = sorted(n for n in names if n not in symbols)
+    assert not missing, missing
 
 
 def test_no_hot_kernel_keeps_private_memory():
