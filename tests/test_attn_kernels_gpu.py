@@ -24,21 +24,22 @@ BF16 = 0
 PB = 64
 
 
-def oracle_attention(q, k, v, n_rep, scale):
-    """q [H, hd], k / v [n, KV, hd] (bf16 bits) -> [H, hd] bf16 bits"""
+def oracle_attention(q, k, v, n_rep, scale, dt=BF16):
+    """q [H, hd], k / v [n, KV, hd] (storage of type dt: bf16 bits or float32) -> [H, hd] of the same"""
     L = mo.layout
     H, hd = q.shape
     n = k.shape[0]
+    st = mo.np_dtype(dt)
     krep = np.ascontiguousarray(np.repeat(k.transpose(1, 0, 2), n_rep, axis=0))   # [H, n, hd]  (functional/transform.h:20-90)
     vrep = np.ascontiguousarray(np.repeat(v.transpose(1, 0, 2), n_rep, axis=0))
-    s = np.zeros((H, 1, n), np.uint16)
-    mo.bmm(BF16, L(s.shape), s, L((H, 1, hd)), q.reshape(H, 1, hd), L((H, hd, n), strides=(n * hd, 1, hd)), krep)
+    s = np.zeros((H, 1, n), st)
+    mo.bmm(dt, L(s.shape), s, L((H, 1, hd)), q.reshape(H, 1, hd), L((H, hd, n), strides=(n * hd, 1, hd)), krep)
     s2 = np.zeros_like(s)
-    mo.scalar_mul(BF16, L((H, n)), s2, L((H, n)), s.reshape(H, n), scale)
-    p = np.zeros((H, n), np.uint16)
-    mo.softmax(BF16, L((H, n)), p, L((H, n)), s2.reshape(H, n))
-    o = np.zeros((H, 1, hd), np.uint16)
-    mo.bmm(BF16, L(o.shape), o, L((H, 1, n)), p.reshape(H, 1, n), L((H, n, hd)), vrep)
+    mo.scalar_mul(dt, L((H, n)), s2, L((H, n)), s.reshape(H, n), scale)
+    p = np.zeros((H, n), st)
+    mo.softmax(dt, L((H, n)), p, L((H, n)), s2.reshape(H, n))
+    o = np.zeros((H, 1, hd), st)
+    mo.bmm(dt, L(o.shape), o, L((H, 1, n)), p.reshape(H, 1, n), L((H, n, hd)), vrep)
     return o.reshape(H, hd)
 
 
