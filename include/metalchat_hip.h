@@ -644,6 +644,67 @@ mc_status mc_row_sampler_get(const mc_batch* b, int32_t row, int32_t* kind, int3
 /* every row back to MC_SAMPLER_INHERIT */
 mc_status mc_row_sampler_reset(mc_batch* b);
 
+/* ================================================================================================
+ * Part 2l -- row logit processors: per-row token masks and penalties.  A serving loop must be able to shape what a row may pick: hold it
+ * to a set of tokens (JSON or grammar output, a choice among N answers, a ban list, "no EOS before n tokens") and apply the
+ * repetition, frequency and presence penalties that every public API exposes next to temperature and top_p -- without giving up
+ * mc_ragged_generate's chained steps.  A row slot holds an optional mask (`allowed` bits, one per token), penalties (rep, freq, pres),
+ * neutral at (1, 0, 0), and a count c[t] per token.
+ *   the rule   T is bfloat16, x the float value of a logit, every operation one float32 operation in the order written.  For a row
+ *              with anything set, every element t of its logits row becomes
+ *                c  = c[t]                                   (after this step's input token has been counted, below)
+ *                x1 = c > 0 ? (x > 0 ? x * inv_rep : x * rep) : x        inv_rep = float(1.0f / rep), formed once on the host
+ *                x2 = c > 0 ? x1 - (freq * float(c) + pres) : x
+ *                y  = allowed(t) ? T(x2) : -inf              (T: round to nearest even; an untouched x keeps its bits)
+ *              y is written in place into the batch's logits, and the unchanged pick launches run on them: a processed row's pick is
+ *              what its effective sampler (Part 2k) picks from y with the row's own seed pair, and mc_batch_get_logits returns y.
+ *              There is no division on the device.  Neutral penalties with no mask are the identity, bit for bit, -0.0 included.
+ *   counts     c[t] = how often token t was fed to the row as a step input since its counts were last cleared: mc_batch_step /
+ *              _generate and mc_ragged_step / _generate, every chained step included.  The process launch of a step first counts that
+ *              step's input token for each active row with (non-neutral) penalties, then penalises; the thread that owns element t
+ *              increments and uses the new value (no atomics), so in a chained call every pick is counted before the next pick, with
+ *              no host round trip.  Idle rows and rows that stopped count nothing.  The packed passes (mc_rows_prefill,
+ *              mc_extend_rows) are processed with the counts as they stand and count nothing of their chunks: a caller that wants
+ *              the prompt in the history adds it with mc_row_penalty_count.  Counts are int32 [B][vocab] on the device, allocated at
+ *              the first mc_row_penalty_set or _count, as the mask words [B][(vocab + 31) / 32] are at the first mask: a batch that
+ *              uses neither holds what it held.  Rewinds do not rewind counts: the caller clears and recounts.
+ *   state      mask, penalties and counts belong to the row SLOT, as samplers do: mc_batch_fork, mc_rolling_fork_row, imports and
+ *              prompt passes leave them alone.
+ *   the rows   the row contract extends: a row's tokens, logits and K / V do not depend on B, on its index, or on the other rows,
+ *              their samplers OR THEIR PROCESSORS, bit for bit (narrow, wide, QLoRA and rolling batches).  A row with nothing set
+ *              computes exactly what it computed before.
+ *   launches   a batch on which no row has anything set launches exactly what it launched before this part -- also after
+ *              mc_row_logits_reset, or with every mask removed and every penalty neutral.  Otherwise one more launch per head,
+ *              mc_b_logits_process_*, between the head GEMV and the pick (DESIGN.md s.4 "Row logit processors").
+ *   verify     mc_verify_rows and mc_tree_verify refuse a row in the call (lens[r] > 0) that has a mask or non-neutral penalties,
+ *              nothing enqueued:
+ *                "mc_verify_rows: row r: the row has a token mask or penalties (a verify call would need them per chunk row)"
+ *              (mc_tree_verify: its own prefix).  Rows outside the call do not matter.
+ * Refusals: all MC_ERR_INVALID_ARGUMENT, prefixed with the call's name; nothing is launched and nothing changes.  A null batch, a row
+ * outside [0, B), and what each call names below.  Uploads are synchronous (every batch call drains the stream before it returns).
+ * Not covered: the batch-1 decoder, additive logit bias lists, masks per chunk row in verify calls, log-probabilities, samplers other
+ * than the two the project has.
+ * ------------------------------------------------------------------------------------------ */
+/* bit t % 32 of word t / 32 set = token t may be picked; n_words == (vocab + 31) / 32; bits at and above vocab are ignored;
+ * allowed == NULL (n_words ignored) removes the mask.  Refused: another n_words, a mask that allows no token below vocab
+ * ("mc_row_mask_set: the mask allows no token"). */
+mc_status mc_row_mask_set(mc_batch* b, int32_t row, const uint32_t* allowed, int32_t n_words);
+/* *is_set = 0 / 1; with a mask set and allowed != NULL (then n_words as above) its words, zeros at and above vocab */
+mc_status mc_row_mask_get(const mc_batch* b, int32_t row, int32_t* is_set, uint32_t* allowed, int32_t n_words);
+/* Refused: repetition not finite or <= 0, frequency or presence not finite.  (1, 0, 0) is neutral. */
+mc_status mc_row_penalty_set(mc_batch* b, int32_t row, float repetition, float frequency, float presence);
+/* the caller's values; each output may be null */
+mc_status mc_row_penalty_get(const mc_batch* b, int32_t row, float* repetition, float* frequency, float* presence);
+/* adds n tokens to the row's history.  Refused: n < 0, a null `tokens` with n > 0, a token outside the vocabulary (the text names
+ * its index). */
+mc_status mc_row_penalty_count(mc_batch* b, int32_t row, const int32_t* tokens, int32_t n);
+/* the row's counts [vocab], read back */
+mc_status mc_row_penalty_counts(mc_batch* b, int32_t row, int32_t* counts);
+/* the row's counts to zero */
+mc_status mc_row_penalty_clear(mc_batch* b, int32_t row);
+/* every row: no mask, neutral penalties, zero counts */
+mc_status mc_row_logits_reset(mc_batch* b);
+
 /* Host-side helpers shared by tests and the synthetic initialiser. */
 /* value in [-7,7] (bits = 4) or [-127,127] (bits = 8), zero mean, of element (row, col) of matrix `matrix_id` */
 int32_t mc_synth_weight(uint64_t seed, uint32_t matrix_id, uint32_t row, uint32_t col, int32_t bits);

@@ -19,10 +19,14 @@
 // and nothing else: mc_b_rows_begin_rolling derives the state and writes the row's rope row, every other launch is the ragged one.
 // Part 2k (mc_row_sampler_*): a row slot may pick with settings of its own in place of the decoder's; head() resolves every row's
 // effective sampler and keeps the uniform launches wherever the rows agree.
+// Part 2l (mc_row_mask_*, mc_row_penalty_*, mc_row_logits_reset): a row slot may carry a token mask and repetition / frequency /
+// presence penalties; head() then puts ONE launch (logit_kernels.hip) between the head GEMV and the pick, which rewrites the logits
+// of those rows in place.  A batch on which no row has either launches what it launched before.
 #include "decoder_batch.h"
 
 #include <algorithm>
 #include <climits>
+#include <cmath>
 #include <cstring>
 #include <memory>
 
@@ -92,6 +96,20 @@ struct mc_batch {
     std::vector<row_setting> row_samplers; // [B]
     row_sampler* samplers_dev = nullptr;   // [B]
     std::vector<row_sampler> samplers_host, samplers_sent;
+    // Part 2l: the logit processor of each row slot as the caller set it, the table head() resolves from it and what of that the
+    // device holds.  The mask words [B][mask_words()] (and their copy on the host), the counts [B][vocab] and the table are
+    // allocated at the first call that needs them: a batch that uses neither holds what it held
+    struct row_logit_setting {
+        bool masked = false;
+        float rep = 1.0f, freq = 0.0f, pres = 0.0f;
+        bool penalised() const { return !(rep == 1.0f && freq == 0.0f && pres == 0.0f); }
+    };
+    std::vector<row_logit_setting> row_logit_set; // [B]
+    uint32_t* masks_dev = nullptr;
+    std::vector<uint32_t> masks_host;
+    int32_t* counts_dev = nullptr;
+    row_logits* logits_tab_dev = nullptr;
+    std::vector<row_logits> logits_tab_host, logits_tab_sent;
 
     ~mc_batch()
     {
@@ -142,6 +160,25 @@ struct mc_batch {
         return decoder_launch(d, name, gx, gy, gz, bx, lds, std::move(a));
     }
 
+
+    int mask_words() const { return (p.cfg.vocab + 31) / 32; }
+    // (the stream drains behind the allocation: the synchronous copies of the mc_row_* calls must find its zeros in place)
+    template <typename P> mc_status
+    ensure(P*& ptr, size_t bytes)
+    {
+        if (ptr) return MC_OK;
+        MC_HIP(hipSetDevice(p.ordinal));
+        mc_status s = alloc(&ptr, bytes);
+        if (s != MC_OK) return s;
+        MC_HIP(hipStreamSynchronize(p.stream));
+        return MC_OK;
+    }
+    mc_status ensure_masks()
+    {
+        masks_host.resize((size_t)B * mask_words(), 0u);
+        return ensure(masks_dev, sizeof(uint32_t) * B * mask_words());
+    }
+    mc_status ensure_counts() { return ensure(counts_dev, sizeof(int32_t) * (size_t)B * p.cfg.vocab); }
 
     char* kc_of(int layer, int row) const { return (char*)kc + ((size_t)layer * B + row) * cache_elems * 2; }
     char* vt_of(int layer, int row) const { return (char*)vt + ((size_t)layer * B + row) * cache_elems * 2; }
@@ -271,7 +308,7 @@ struct mc_batch {
             if ((s = gemv(L.w13, 2, xn, gate, (uint32_t)(L.w13.out / 2))) != MC_OK) return s;
             if ((s = gemv(L.w2, 1, gate, x, (uint32_t)c.dim)) != MC_OK) return s;
         }
-        return head(sfx);
+        return head(sfx, true);
     }
 
     // row r's effective sampler: its own (mc_row_sampler_set), or the decoder's while it inherits
@@ -294,14 +331,17 @@ struct mc_batch {
     //   1  no row samples               mc_b_argmax
     //   2  all sample, settings equal   mc_b_topk_candidates_bfloat + mc_b_sample with the plan of those settings
     //   3  anything else                the two mixed launches over the table of effective settings
-    // 1 and 2 are what a batch without row samplers launches for the decoder's sampler, argument for argument
+    // 1 and 2 are what a batch without row samplers launches for the decoder's sampler, argument for argument.
+    // Part 2l: with a mask or penalties on any row, mc_b_logits_process_* rewrites those rows' logits between the head and the pick;
+    // count: the rows with penalties count their input token first (a step; the packed passes count nothing)
     mc_status
-    head(const std::string& sfx)
+    head(const std::string& sfx, bool count)
     {
         const mc_decoder_config& c = p.cfg;
         mc_status s;
         if ((s = rmsnorm(x, p.final_norm, xn)) != MC_OK) return s;
         if ((s = gemv(p.output, 0, xn, logits, (uint32_t)c.vocab)) != MC_OK) return s;
+        if ((s = process_logits(sfx, count)) != MC_OK) return s;
         const decoder_sampler dec = decoder_sampler_of(d);
         const decoder_sampler sm = sampler_of_row(0, dec);
         int sampling = 0, top_k_max = 0;
@@ -346,6 +386,52 @@ struct mc_batch {
         return launch("mc_b_pick_mixed" + sfx, 1, B, 1, 1024, sp.cap * 8,
                       pack(logits, (uint32_t)c.vocab, (const uint64_t*)cand, (const row_sampler*)samplers_dev, sp.nlists, sp.kpad, sp.cap,
                            (const uint64_t*)seeds, (uint32_t)n_seed_pairs, rows, tokens_dev));
+    }
+
+    // the table of the rows' logit processors, resolved as the samplers' is and sent when it differs from what the device holds;
+    // no launch (and no table) while no row has anything set
+    mc_status
+    process_logits(const std::string& sfx, bool count)
+    {
+        const mc_decoder_config& c = p.cfg;
+        bool any = false;
+        logits_tab_host.assign(B, row_logits{});
+        for (int r = 0; r < B; r++) {
+            const row_logit_setting& rs = row_logit_set[r];
+            row_logits& t = logits_tab_host[r];
+            t.flags = (rs.masked ? ROW_LOGITS_MASK : 0u) | (rs.penalised() ? ROW_LOGITS_PENALTY : 0u);
+            if (!t.flags) continue;
+            any = true;
+            if (!rs.penalised()) continue;
+            t.rep = rs.rep;
+            t.inv_rep = 1.0f / rs.rep;
+            t.freq = rs.freq;
+            t.pres = rs.pres;
+        }
+        if (!any) return MC_OK;
+        mc_status s;
+        if ((s = ensure(logits_tab_dev, sizeof(row_logits) * B)) != MC_OK) return s;
+        if (logits_tab_sent.size() != logits_tab_host.size() ||
+            memcmp(logits_tab_sent.data(), logits_tab_host.data(), sizeof(row_logits) * B) != 0) {
+            logits_tab_sent = logits_tab_host;
+            MC_HIP(hipMemcpyAsync(logits_tab_dev, logits_tab_sent.data(), sizeof(row_logits) * B, hipMemcpyHostToDevice, p.stream));
+        }
+        const unsigned gx = ((unsigned)c.vocab + LP_CHUNK - 1) / LP_CHUNK;
+        arg_pack a = pack(logits, (uint32_t)c.vocab, (const row_logits*)logits_tab_dev, (const uint32_t*)masks_dev, counts_dev, (const step_state*)rows);
+        if (sfx == "_rows_bfloat") a.push((int32_t)(count ? 1 : 0));
+        return launch("mc_b_logits_process" + sfx, gx, B, 1, LP_THREADS, 0, std::move(a));
+    }
+
+    // mc_verify_rows / mc_tree_verify (`who`): a row in the call with a mask or penalties is refused (its chunk rows would each
+    // need them)
+    mc_status
+    verify_logit_rows(const char* who, const int32_t* lens) const
+    {
+        for (int r = 0; r < B; r++)
+            if (lens[r] > 0 && (row_logit_set[r].masked || row_logit_set[r].penalised()))
+                return fail(MC_ERR_INVALID_ARGUMENT, std::string(who) + ": row " + std::to_string(r) +
+                                                         ": the row has a token mask or penalties (a verify call would need them per chunk row)");
+        return MC_OK;
     }
 
     // mc_verify_rows / mc_tree_verify (`who`): every row in the call must pick greedily.  A batch without row samplers keeps the
@@ -612,6 +698,7 @@ batch_create(const std::string& who, int cap, bool wide, mc_decoder* d, int32_t 
     b->B = batch;
     b->lengths.assign(batch, 0);
     b->row_samplers.assign(batch, mc_batch::row_setting{});
+    b->row_logit_set.assign(batch, mc_batch::row_logit_setting{});
     const mc_decoder_config& c = parts.cfg;
     const int H = c.n_heads, KV = c.n_kv_heads, hd = c.head_dim, L = (int)parts.layers.size();
     b->nsplit = (c.max_seq_len + PB - 1) / PB;
@@ -888,7 +975,7 @@ rows_pass(mc_batch* b, const char* who, bool extend, const int32_t* tokens, cons
         pk.tokens_dev = &ids;
     }
     if ((s = decoder_prefill_packed(b->d, tokens, M, pk)) != MC_OK) return s;
-    if ((s = v ? b->verify_head(rows_all, ids, M, nseg, pk.nodes) : b->head("_rows_bfloat")) != MC_OK) return s;
+    if ((s = v ? b->verify_head(rows_all, ids, M, nseg, pk.nodes) : b->head("_rows_bfloat", false)) != MC_OK) return s;
     MC_HIP(hipStreamSynchronize(b->p.stream)); // (`tokens` is the caller's buffer; the tables are read by the launches)
     if (v) {
         b->v_rows = M;
@@ -935,6 +1022,7 @@ mc_verify_rows(mc_batch* b, const int32_t* tokens, const int32_t* lens, const in
 {
     if (!b || !tokens || !lens || !positions || !accepted) return fail(MC_ERR_INVALID_ARGUMENT, "mc_verify_rows: null argument");
     if (mc_status s = b->verify_samplers("mc_verify_rows", lens); s != MC_OK) return s;
+    if (mc_status s = b->verify_logit_rows("mc_verify_rows", lens); s != MC_OK) return s;
     const verify_out v{accepted, picks};
     return rows_pass(b, "mc_verify_rows", true, tokens, lens, positions, next_tokens, &v);
 }
@@ -947,6 +1035,7 @@ mc_tree_verify(mc_batch* b, const int32_t* tokens, const int32_t* parents, const
 {
     if (!b || !tokens || !parents || !lens || !positions || !accepted) return fail(MC_ERR_INVALID_ARGUMENT, "mc_tree_verify: null argument");
     if (mc_status s = b->verify_samplers("mc_tree_verify", lens); s != MC_OK) return s;
+    if (mc_status s = b->verify_logit_rows("mc_tree_verify", lens); s != MC_OK) return s;
     const verify_out v{accepted, picks, parents, paths};
     return rows_pass(b, "mc_tree_verify", true, tokens, lens, positions, next_tokens, &v);
 }
@@ -1118,6 +1207,141 @@ mc_row_sampler_reset(mc_batch* b)
 {
     if (!b) return fail(MC_ERR_INVALID_ARGUMENT, "mc_row_sampler_reset: null argument");
     b->row_samplers.assign(b->B, mc_batch::row_setting{});
+    return MC_OK;
+}
+
+// ---- Part 2l: row logit processors ----
+// Every batch call drains the stream before it returns, so the synchronous copies below meet an idle stream.
+
+static mc_status
+logit_row(const mc_batch* b, int32_t row, const char* who)
+{
+    if (!b) return fail(MC_ERR_INVALID_ARGUMENT, std::string(who) + ": null argument");
+    if (row < 0 || row >= b->B) return fail(MC_ERR_INVALID_ARGUMENT, std::string(who) + ": row out of range");
+    return MC_OK;
+}
+
+mc_status
+mc_row_mask_set(mc_batch* b, int32_t row, const uint32_t* allowed, int32_t n_words)
+{
+    if (mc_status s = logit_row(b, row, "mc_row_mask_set"); s != MC_OK) return s;
+    if (!allowed) {
+        b->row_logit_set[row].masked = false;
+        return MC_OK;
+    }
+    const int nw = b->mask_words(), vocab = b->p.cfg.vocab;
+    if (n_words != nw) return fail(MC_ERR_INVALID_ARGUMENT, "mc_row_mask_set: n_words must be (vocab + 31) / 32 = " + std::to_string(nw));
+    // bits at and above vocab are ignored: the device's words hold zeros there
+    std::vector<uint32_t> words(allowed, allowed + nw);
+    if (vocab % 32) words[nw - 1] &= (1u << (vocab % 32)) - 1u;
+    if (std::all_of(words.begin(), words.end(), [](uint32_t w) { return w == 0; }))
+        return fail(MC_ERR_INVALID_ARGUMENT, "mc_row_mask_set: the mask allows no token");
+    if (mc_status s = b->ensure_masks(); s != MC_OK) return s;
+    MC_HIP(hipSetDevice(b->p.ordinal));
+    MC_HIP(hipMemcpyAsync(b->masks_dev + (size_t)row * nw, words.data(), sizeof(uint32_t) * nw, hipMemcpyHostToDevice, b->p.stream));
+    MC_HIP(hipStreamSynchronize(b->p.stream));
+    std::copy(words.begin(), words.end(), b->masks_host.begin() + (size_t)row * nw);
+    b->row_logit_set[row].masked = true;
+    return MC_OK;
+}
+
+mc_status
+mc_row_mask_get(const mc_batch* b, int32_t row, int32_t* is_set, uint32_t* allowed, int32_t n_words)
+{
+    if (mc_status s = logit_row(b, row, "mc_row_mask_get"); s != MC_OK) return s;
+    if (!is_set) return fail(MC_ERR_INVALID_ARGUMENT, "mc_row_mask_get: null argument");
+    const int nw = b->mask_words();
+    if (allowed && n_words != nw) return fail(MC_ERR_INVALID_ARGUMENT, "mc_row_mask_get: n_words must be (vocab + 31) / 32 = " + std::to_string(nw));
+    *is_set = b->row_logit_set[row].masked ? 1 : 0;
+    if (*is_set && allowed) std::copy_n(b->masks_host.begin() + (size_t)row * nw, nw, allowed);
+    return MC_OK;
+}
+
+mc_status
+mc_row_penalty_set(mc_batch* b, int32_t row, float repetition, float frequency, float presence)
+{
+    if (mc_status s = logit_row(b, row, "mc_row_penalty_set"); s != MC_OK) return s;
+    if (!std::isfinite(repetition) || !(repetition > 0.0f))
+        return fail(MC_ERR_INVALID_ARGUMENT, "mc_row_penalty_set: repetition must be finite and positive");
+    if (!std::isfinite(frequency)) return fail(MC_ERR_INVALID_ARGUMENT, "mc_row_penalty_set: frequency must be finite");
+    if (!std::isfinite(presence)) return fail(MC_ERR_INVALID_ARGUMENT, "mc_row_penalty_set: presence must be finite");
+    if (mc_status s = b->ensure_counts(); s != MC_OK) return s;
+    mc_batch::row_logit_setting& rs = b->row_logit_set[row];
+    rs.rep = repetition;
+    rs.freq = frequency;
+    rs.pres = presence;
+    return MC_OK;
+}
+
+mc_status
+mc_row_penalty_get(const mc_batch* b, int32_t row, float* repetition, float* frequency, float* presence)
+{
+    if (mc_status s = logit_row(b, row, "mc_row_penalty_get"); s != MC_OK) return s;
+    const mc_batch::row_logit_setting& rs = b->row_logit_set[row];
+    if (repetition) *repetition = rs.rep;
+    if (frequency) *frequency = rs.freq;
+    if (presence) *presence = rs.pres;
+    return MC_OK;
+}
+
+mc_status
+mc_row_penalty_count(mc_batch* b, int32_t row, const int32_t* tokens, int32_t n)
+{
+    if (mc_status s = logit_row(b, row, "mc_row_penalty_count"); s != MC_OK) return s;
+    if (n < 0) return fail(MC_ERR_INVALID_ARGUMENT, "mc_row_penalty_count: n must not be negative");
+    if (n > 0 && !tokens) return fail(MC_ERR_INVALID_ARGUMENT, "mc_row_penalty_count: null argument");
+    const int vocab = b->p.cfg.vocab;
+    for (int32_t i = 0; i < n; i++)
+        if (tokens[i] < 0 || tokens[i] >= vocab)
+            return fail(MC_ERR_INVALID_ARGUMENT, "mc_row_penalty_count: token " + std::to_string(i) + " (id " + std::to_string(tokens[i]) +
+                                                     ") is outside the vocabulary");
+    if (mc_status s = b->ensure_counts(); s != MC_OK) return s;
+    if (n == 0) return MC_OK;
+    MC_HIP(hipSetDevice(b->p.ordinal));
+    std::vector<int32_t> counts(vocab);
+    int32_t* dev = b->counts_dev + (size_t)row * vocab;
+    MC_HIP(hipMemcpy(counts.data(), dev, sizeof(int32_t) * vocab, hipMemcpyDeviceToHost));
+    for (int32_t i = 0; i < n; i++) counts[tokens[i]]++;
+    MC_HIP(hipMemcpyAsync(dev, counts.data(), sizeof(int32_t) * vocab, hipMemcpyHostToDevice, b->p.stream));
+    MC_HIP(hipStreamSynchronize(b->p.stream));
+    return MC_OK;
+}
+
+mc_status
+mc_row_penalty_counts(mc_batch* b, int32_t row, int32_t* counts)
+{
+    if (mc_status s = logit_row(b, row, "mc_row_penalty_counts"); s != MC_OK) return s;
+    if (!counts) return fail(MC_ERR_INVALID_ARGUMENT, "mc_row_penalty_counts: null argument");
+    const int vocab = b->p.cfg.vocab;
+    if (!b->counts_dev) {
+        std::fill_n(counts, vocab, 0);
+        return MC_OK;
+    }
+    MC_HIP(hipSetDevice(b->p.ordinal));
+    MC_HIP(hipMemcpy(counts, b->counts_dev + (size_t)row * vocab, sizeof(int32_t) * vocab, hipMemcpyDeviceToHost));
+    return MC_OK;
+}
+
+mc_status
+mc_row_penalty_clear(mc_batch* b, int32_t row)
+{
+    if (mc_status s = logit_row(b, row, "mc_row_penalty_clear"); s != MC_OK) return s;
+    if (!b->counts_dev) return MC_OK;
+    MC_HIP(hipSetDevice(b->p.ordinal));
+    MC_HIP(hipMemsetAsync(b->counts_dev + (size_t)row * b->p.cfg.vocab, 0, sizeof(int32_t) * b->p.cfg.vocab, b->p.stream));
+    MC_HIP(hipStreamSynchronize(b->p.stream));
+    return MC_OK;
+}
+
+mc_status
+mc_row_logits_reset(mc_batch* b)
+{
+    if (!b) return fail(MC_ERR_INVALID_ARGUMENT, "mc_row_logits_reset: null argument");
+    b->row_logit_set.assign(b->B, mc_batch::row_logit_setting{});
+    if (!b->counts_dev) return MC_OK;
+    MC_HIP(hipSetDevice(b->p.ordinal));
+    MC_HIP(hipMemsetAsync(b->counts_dev, 0, sizeof(int32_t) * (size_t)b->B * b->p.cfg.vocab, b->p.stream));
+    MC_HIP(hipStreamSynchronize(b->p.stream));
     return MC_OK;
 }
 

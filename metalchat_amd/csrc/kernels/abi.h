@@ -73,6 +73,25 @@ static_assert(sizeof(row_sampler) == 16 && alignof(row_sampler) == 4 && offsetof
                   offsetof(row_sampler, inv_temp) == 8 && offsetof(row_sampler, top_p) == 12,
               "row_sampler: four words (read whole with one scalar load)");
 
+// ---- a batch row's logit processor (logit_kernels.hip mc_b_logits_process_*; ABI Part 2l), one per row in a [B] device table ----
+// resolved on the host: flags 0 = nothing set, the row's workgroups exit.  The row's mask words and counts are found from the row
+// index: masks + r * ((vocab + 31) / 32), counts + r * vocab
+constexpr uint32_t ROW_LOGITS_MASK = 1u;    // the row has a token mask: a cleared bit makes the logit -inf
+constexpr uint32_t ROW_LOGITS_PENALTY = 2u; // the row's penalties are not (1, 0, 0): its counts are read, and its input token counted
+constexpr uint32_t LP_THREADS = 256;        // mc_b_logits_process_*: threads of a workgroup ...
+constexpr uint32_t LP_CHUNK = 8 * LP_THREADS; // ... and the logits of one row it streams: one 16-byte piece per thread
+struct alignas(16) row_logits {
+    uint32_t flags; // ROW_LOGITS_*
+    float rep;      // the repetition penalty ...
+    float inv_rep;  // ... and float(1.0f / rep), formed on the host: no division on the device
+    float freq;     // the frequency penalty
+    float pres;     // the presence penalty
+    uint32_t pad[3];
+};
+static_assert(sizeof(row_logits) == 32 && alignof(row_logits) == 16 && offsetof(row_logits, flags) == 0 && offsetof(row_logits, rep) == 4 &&
+                  offsetof(row_logits, inv_rep) == 8 && offsetof(row_logits, freq) == 12 && offsetof(row_logits, pres) == 16,
+              "row_logits: eight words (read whole with one scalar load)");
+
 // ---- the descriptors a decode GEMV finds behind its `res` argument (gemv.h) ----
 // PRO_POSTNORM
 struct postnorm_args {

@@ -14,3 +14,4 @@
 #include "verify_kernels.hip"
 #include "wide_kernels.hip"
 #include "tree_kernels.hip"
+#include "logit_kernels.hip"

@@ -212,6 +212,14 @@ def capi() -> C.CDLL:
         "mc_row_sampler_set": (i32, [vp, i32, i32, i32, C.c_float, C.c_float]),
         "mc_row_sampler_get": (i32, [vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(f32), C.POINTER(f32)]),
         "mc_row_sampler_reset": (i32, [vp]),
+        "mc_row_mask_set": (i32, [vp, i32, C.POINTER(u32), i32]),
+        "mc_row_mask_get": (i32, [vp, i32, C.POINTER(i32), C.POINTER(u32), i32]),
+        "mc_row_penalty_set": (i32, [vp, i32, C.c_float, C.c_float, C.c_float]),
+        "mc_row_penalty_get": (i32, [vp, i32, C.POINTER(f32), C.POINTER(f32), C.POINTER(f32)]),
+        "mc_row_penalty_count": (i32, [vp, i32, C.POINTER(i32), i32]),
+        "mc_row_penalty_counts": (i32, [vp, i32, C.POINTER(i32)]),
+        "mc_row_penalty_clear": (i32, [vp, i32]),
+        "mc_row_logits_reset": (i32, [vp]),
         "mc_rows_prefill": (i32, [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
         "mc_extend_rows": (i32, [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
         "mc_verify_rows": (i32, [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
@@ -999,6 +1007,70 @@ class Batch:
     def reset_row_samplers(self):
         """every row back to SAMPLER_INHERIT"""
         _check(capi().mc_row_sampler_reset(self._h))
+
+    # ---- row logit processors (Part 2l): a token mask and repetition / frequency / presence penalties per row slot
+
+    def _mask_words(self) -> int:
+        return (self.cfg["vocab"] + 31) // 32
+
+    def set_row_mask(self, row: int, allowed):
+        """allowed: a bool array [vocab] (True = the token may be picked), an iterable of token ids, or None to remove the mask"""
+        if allowed is None:
+            _check(capi().mc_row_mask_set(self._h, row, None, 0))
+            return
+        vocab, nw = self.cfg["vocab"], self._mask_words()
+        a = np.asarray(allowed)
+        if a.dtype == np.bool_:
+            assert a.shape == (vocab,), "set_row_mask: a bool mask has one entry per token"
+            bits = a
+        else:
+            ids = np.asarray(list(allowed) if not isinstance(allowed, np.ndarray) else allowed, dtype=np.int64).reshape(-1)
+            if ids.size and (ids.min() < 0 or ids.max() >= vocab):
+                raise ValueError("set_row_mask: token id outside the vocabulary")
+            bits = np.zeros(vocab, np.bool_)
+            bits[ids] = True
+        padded = np.zeros(nw * 32, np.uint8)
+        padded[:vocab] = bits
+        words = np.ascontiguousarray(np.packbits(padded, bitorder="little").view("<u4").astype(np.uint32))
+        _check(capi().mc_row_mask_set(self._h, row, words.ctypes.data_as(C.POINTER(C.c_uint32)), nw))
+
+    def row_mask(self, row: int):
+        """the row's mask as a bool array [vocab], or None for a row without one"""
+        nw = self._mask_words()
+        is_set, words = C.c_int32(), np.zeros(nw, np.uint32)
+        _check(capi().mc_row_mask_get(self._h, row, C.byref(is_set), words.ctypes.data_as(C.POINTER(C.c_uint32)), nw))
+        if not is_set.value:
+            return None
+        return np.unpackbits(words.astype("<u4").view(np.uint8), bitorder="little")[: self.cfg["vocab"]].astype(np.bool_)
+
+    def set_row_penalties(self, row: int, repetition: float = 1.0, frequency: float = 0.0, presence: float = 0.0):
+        """a counted token's logit x becomes (x > 0 ? x / repetition : x * repetition) - (frequency * count + presence);
+        (1, 0, 0) is neutral.  The counts are the row's step inputs since they were cleared, plus count_row_tokens."""
+        _check(capi().mc_row_penalty_set(self._h, row, repetition, frequency, presence))
+
+    def row_penalties(self, row: int):
+        """(repetition, frequency, presence) as set"""
+        rep, freq, pres = C.c_float(), C.c_float(), C.c_float()
+        _check(capi().mc_row_penalty_get(self._h, row, C.byref(rep), C.byref(freq), C.byref(pres)))
+        return rep.value, freq.value, pres.value
+
+    def count_row_tokens(self, row: int, tokens):
+        """adds tokens (a prompt, say) to the row's history"""
+        t = np.ascontiguousarray(np.asarray(tokens, dtype=np.int32).reshape(-1))
+        _check(capi().mc_row_penalty_count(self._h, row, t.ctypes.data_as(C.POINTER(C.c_int32)), t.shape[0]))
+
+    def row_token_counts(self, row: int) -> np.ndarray:
+        """the row's counts [vocab]"""
+        out = np.zeros(self.cfg["vocab"], dtype=np.int32)
+        _check(capi().mc_row_penalty_counts(self._h, row, out.ctypes.data_as(C.POINTER(C.c_int32))))
+        return out
+
+    def clear_row_counts(self, row: int):
+        _check(capi().mc_row_penalty_clear(self._h, row))
+
+    def reset_row_logits(self):
+        """every row: no mask, neutral penalties, zero counts"""
+        _check(capi().mc_row_logits_reset(self._h))
 
     def set_seeds(self, pairs):
         a = np.ascontiguousarray(np.asarray(pairs, dtype=np.uint64).reshape(-1, 2))
