@@ -23,8 +23,9 @@ KERNEL_SOURCES = [os.path.join(CSRC, "kernels", f) for f in (
     "synth_kernels.hip", "sampler_kernels.hip", "prefill_kernels.hip", "batch_kernels.hip", "packed_kernels.hip", "extend_kernels.hip", "verify_kernels.hip", "wide_kernels.hip", "tree_kernels.hip", "logit_kernels.hip", "common.h", "abi.h", "handoff.h", "gemv.h", "gemv_ksplit.h", "synth.h", "pf_gemm8.h")]
 # the host library: every unit goes into the one hipcc command, units and headers together are what makes it stale
 HOST_UNITS = [os.path.join(CSRC, f) for f in ("backend.cc", "decoder.cc", "weights.cc", "prefill.cc", "prefill_blaslt.cc", "pipeline.cc", "batch.cc",
-                                               "model_io.cc", "text.cc")]
-HOST_HEADERS = [os.path.join(CSRC, f) for f in ("json_min.h", "backend_impl.h", "decoder_impl.h", "decoder_batch.h", "decoder_options.h", "gemv_plan.h", "block_plan.h", "prefill_plan.h", "rows_plan.h")] + [
+                                               "batch_rows.cc", "batch_cache.cc", "batch_settings.cc", "model_io.cc", "text.cc")]
+HOST_HEADERS = [os.path.join(CSRC, f) for f in ("json_min.h", "backend_impl.h", "decoder_impl.h", "decoder_batch.h", "decoder_options.h", "gemv_plan.h", "block_plan.h", "prefill_plan.h", "rows_plan.h",
+                                                 "batch_plan.h", "batch_impl.h", "bf16_host.h", "sampler_plan.h")] + [
     os.path.join(CSRC, "kernels", "synth.h"), os.path.join(CSRC, "kernels", "abi.h"),
     os.path.join(os.path.dirname(HERE), "include", "metalchat_hip.h")]
 
@@ -99,7 +100,7 @@ def build_text_test(force: bool = False) -> str:
     return _build_cpp_test("test_text", _ABI_HEADERS, force, True)
 
 
-# The four plan programs are no part of build_all(): nothing of the package needs them, their CPU tests build them (a second or two) when they run.
+# The five plan programs are no part of build_all(): nothing of the package needs them, their CPU tests build them (a second or two) when they run.
 def build_gemv_plan_test(force: bool = False) -> str:
     """tests/cpp/test_gemv_plan: plan_gemv() (csrc/gemv_plan.h) from the command line -- no HIP and no host library."""
     return _build_cpp_test("test_gemv_plan", _PLAN_HEADERS, force, False)
@@ -118,6 +119,12 @@ def build_prefill_plan_test(force: bool = False) -> str:
 def build_rows_plan_test(force: bool = False) -> str:
     """tests/cpp/test_rows_plan: the tables of the rows passes (csrc/rows_plan.h) from the command line -- no HIP and no host library."""
     return _build_cpp_test("test_rows_plan", [os.path.join(CSRC, "rows_plan.h"), os.path.join(CSRC, "kernels", "abi.h")], force, False)
+
+
+def build_batch_plan_test(force: bool = False) -> str:
+    """tests/cpp/test_batch_plan: what a batch launches (csrc/batch_plan.h) from the command line -- no HIP and no host library."""
+    headers = [os.path.join(CSRC, f) for f in ("batch_plan.h", "rows_plan.h", "bf16_host.h", "sampler_plan.h")] + [os.path.join(CSRC, "kernels", "abi.h"), _ABI_HEADERS[1]]
+    return _build_cpp_test("test_batch_plan", headers, force, False)
 
 
 def build_all(force: bool = False):

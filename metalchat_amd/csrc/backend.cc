@@ -3,7 +3,7 @@
 // src/metal_impl.h and src/kernel_thread.cc; see the header for the per-function citations.
 //
 // hip_runtime.h reaches the host side through backend_impl.h alone: this translation unit, the decoder's five (decoder.cc,
-// weights.cc, prefill.cc, prefill_blaslt.cc, pipeline.cc) and batch.cc include it, model_io.cc and text.cc do not (the reference
+// weights.cc, prefill.cc, prefill_blaslt.cc, pipeline.cc) and the batch's four units include it, model_io.cc and text.cc do not (the reference
 // confines metal-cpp to src/metal_impl.h the same way).
 #include "backend_impl.h"
 

@@ -1,0 +1,238 @@
+// Part 2b of include/metalchat_hip.h: batched decode -- B sequences in lockstep over one decoder's weights (B <= 8 from
+// mc_batch_create, B <= 64 from Part 2h's mc_wide_batch_create, which since Part 2i also admits QLoRA decoders: int4 / int8 linears in
+// groups of 32, each linear in a format of its own, LoRA adaptors on the layer linears).
+//
+// The reference's layers carry the batch dimension already: nn::attention::operator() takes input[bs, len, dim]
+// (include/metalchat/nn/attention.h:163-206) and nn::sink_cache holds [max_batch_size, max_seq_len, n_kv_heads, head_dim],
+// writing cache[0:bs, start_pos:start_pos+len] at ONE start_pos for the whole batch (nn/cache.h:154-215); only nn::llama3 pins
+// max_batch_size = 1 (nn/llama.h:86).  A batch here shares the decoder's weights (read through decoder_batch.h, never copied)
+// and owns B caches per layer.  Per token and layer it enqueues a fixed sequence of launches (batch_kernels.hip), none of which
+// waits for another workgroup:
+//   rmsnorm, wq|wk|wv, rope + cache write, scores, softmax + P.V, Wo + residual, rmsnorm, w1|w3 + SiLU.mul, w2 + residual
+// then the final norm, the head and the pick (greedy, or the decoder's default sampler) per row.  Every GEMV streams each
+// weight once for all B rows: plan_batch_gemv() (batch_plan.h) picks the launch by B, and nothing else knows where that line runs.
+// Part 2c (mc_ragged_*) runs the same sequence with every row at a position of its own: the per-row launches read rows[r]
+// instead of the shared state, one small launch (mc_b_rows_begin) starts each step in place of mc_step_set, and a row whose
+// position is -1, or which stopped on a stop id or at the end of its cache, is idle.
+// Part 2j (mc_rolling_set): the ragged rows of a batch decode past max_seq_len on nn::sink_cache's ring (nn/cache.h:187-204).
+// A row's ring state is a function of its position -- rows get past the end by single steps only -- so the batch keeps its lengths
+// and nothing else: mc_b_rows_begin_rolling derives the state and writes the row's rope row, every other launch is the ragged one.
+// Part 2k (mc_row_sampler_*): a row slot may pick with settings of its own in place of the decoder's; plan_head() resolves every row's
+// effective sampler and keeps the uniform launches wherever the rows agree.
+// Part 2l (mc_row_mask_*, mc_row_penalty_*, mc_row_logits_reset): a row slot may carry a token mask and repetition / frequency /
+// presence penalties; head() then puts ONE launch (logit_kernels.hip) between the head GEMV and the pick, which rewrites the logits
+// of those rows in place.  A batch on which no row has either launches what it launched before.
+//
+// WHAT is launched -- names, grids, blocks, LDS bytes, the admission and every check of a call that needs no device -- is decided in
+// batch_plan.h, without HIP.  This header is struct mc_batch as its four units see it: the state, the allocator, the launch path and the
+// small helpers every unit calls inline.  Which unit defines what:
+//   batch.cc           creation and release, one token (gemv, enqueue_token, head), the lockstep and ragged entry points
+//   batch_rows.cc      the rows passes: rows_pass, verify_head, mc_rows_prefill / mc_extend_rows / mc_verify_rows / mc_tree_verify
+//   batch_cache.cc     a row's cache: fork, import, the exports, mc_rolling_*
+//   batch_settings.cc  what a row slot carries between calls: seeds, row samplers, row logit processors
+#pragma once
+
+#include "bf16_host.h"
+#include "decoder_batch.h"
+
+#include <algorithm>
+#include <climits>
+#include <cmath>
+#include <cstring>
+#include <memory>
+
+struct mc_batch {
+    mcimpl::decoder_parts p;
+    mc_decoder* d = nullptr;
+    int B = 0;
+    int nsplit = 0;
+    size_t cache_elems = 0; // one row's cache of one layer: n_kv * max_seq * hd
+    std::vector<void*> allocs;
+    void *kc = nullptr, *vt = nullptr;    // [layer][B][n_kv][max_seq][hd], [layer][B][n_kv][hd][max_seq]
+    void *x = nullptr, *xn = nullptr;     // [B][dim]
+    void *qkv = nullptr;                  // [B][(H + 2 KV) hd]
+    void *q = nullptr, *att = nullptr;    // [B][H hd]
+    void *gate = nullptr;                 // [B][ffn]
+    void *lora_vec = nullptr;             // [B][lora_ld]: a = T(A x) of the linear in flight; only when some linear has an adaptor.  ONE
+                                          // scratch for all linears: every launch goes to the decoder's one stream, in order
+    int lora_ld = 0;                      // the most lora_cols of any linear
+    void *logits = nullptr;               // [B][vocab]
+    float *expv = nullptr, *psum = nullptr; // [B][H][max_seq], [B][H][nsplit]
+    float *fcos = nullptr, *fsin = nullptr; // rope table rows [0, max_seq)
+    float *rcos = nullptr, *rsin = nullptr; // [B][hd / 2]: a rolling batch's rope row of each row, written by every step's first launch
+    bool rolling = false;                   // mc_rolling_set
+    mcimpl::step_state* st = nullptr;     // the shared position
+    mcimpl::step_state* rows = nullptr;   // [B]: token and step_index of each row (ragged calls: the whole state of each row)
+    uint64_t* cand = nullptr;             // [B][lists * kpad]
+    size_t cand_per_row = 0;
+    uint64_t* seeds = nullptr;
+    int n_seed_pairs = 0, seed_cap = 0;   // (capacity in pairs)
+    int32_t* tokens_dev = nullptr;
+    int tokens_cap = 0;
+    std::vector<mcimpl::step_state> rows_host;
+    std::vector<int32_t> lengths;         // [B]: valid cache positions of each row
+    int32_t* stop_dev = nullptr;          // the stop ids of a ragged call
+    int stop_cap = 0;
+    std::vector<int32_t> stop_host;
+    char* pp_tab = nullptr;               // a packed prompt pass (mc_rows_prefill): pp_seg[MC_WIDE_BATCH_MAX], then the pp_tile table,
+                                          // then (mc_tree_verify) one tv_node per packed row
+    int pp_tab_cap = 0;                   // (bytes)
+    std::vector<char> pp_host;            // the same bytes on the host: one upload
+    mcimpl::px_range* px_tab = nullptr;   // mc_extend_rows: the range table
+    int px_tab_cap = 0;
+    std::vector<mcimpl::px_range> px_host;
+    std::vector<mcimpl::px_group> px_groups;
+    float *px_sums = nullptr, *px_part = nullptr; // scratch of one launch group: [px_slots][H][16], [px_slots][H][16][hd]
+    int px_slots = 0;
+    // mc_verify_rows and mc_tree_verify, reserved at the first call: the normed rows [128][dim], their logits [128][vocab], and the
+    // call's results on the device: accepted[B], next_tokens[B], picks[M], then (mc_tree_verify) paths[B][MC_VERIFY_MAX_LEN]
+    void *v_xn = nullptr, *v_logits = nullptr;
+    int32_t* v_out = nullptr;
+    int v_xn_cap = 0, v_logits_cap = 0, v_out_cap = 0;
+    int v_rows = 0;                       // packed rows of the last mc_verify_rows / mc_tree_verify call (0: none yet)
+    std::vector<int32_t> v_host;
+    // Part 2k: the sampler of each row slot as mc_row_sampler_set took it, the table of effective settings the mixed launches read
+    // (plan_head resolves it), and what of it the device holds
+    std::vector<mcimpl::row_setting> row_samplers; // [B]
+    mcimpl::row_sampler* samplers_dev = nullptr;   // [B]
+    std::vector<mcimpl::row_sampler> samplers_sent;
+    // Part 2l: the logit processor of each row slot as the caller set it, and what of the table plan_logits resolves from it the
+    // device holds.  The mask words [B][mask_words()] (and their copy on the host), the counts [B][vocab] and the table are
+    // allocated at the first call that needs them: a batch that uses neither holds what it held
+    std::vector<mcimpl::row_logit_setting> row_logit_set; // [B]
+    uint32_t* masks_dev = nullptr;
+    std::vector<uint32_t> masks_host;
+    int32_t* counts_dev = nullptr;
+    mcimpl::row_logits* logits_tab_dev = nullptr;
+    std::vector<mcimpl::row_logits> logits_tab_sent;
+    // The plans (batch_plan.h).  Fixed at creation: B, the device's compute units and MC_WB_TILES, both read once there (genv); the GEMV of
+    // every matrix; the launches of a step, lockstep / ragged / ragged on a rolling batch.  Of the call in flight (plan_call, plan_pick):
+    // its step, the rows' logit processors and the pick -- the settings cannot change inside a call
+    mcimpl::batch_env genv;
+    struct layer_gemvs {
+        mcimpl::batch_gemv_plan qkv, wo, w13, w2;
+    };
+    std::vector<layer_gemvs> gemvs;
+    mcimpl::batch_gemv_plan head_gemv;
+    mcimpl::step_plan steps[3];
+    const mcimpl::step_plan* step = nullptr;
+    mcimpl::logits_plan lp;
+    mcimpl::head_plan pick;
+
+    ~mc_batch()
+    {
+        (void)hipSetDevice(p.ordinal);
+        (void)hipStreamSynchronize(p.stream);
+        for (void* a : allocs) (void)hipFree(a);
+    }
+
+    template <typename P> mc_status
+    alloc(P** ptr, size_t bytes)
+    {
+        void* v = nullptr;
+        hipError_t e = hipMalloc(&v, bytes ? bytes : 16);
+        if (e != hipSuccess)
+            return mcimpl::fail(MC_ERR_ALLOC, std::string("hardware_memory_allocator: failed to allocate ") + std::to_string(bytes) +
+                                                  " bytes: " + hipGetErrorString(e));
+        allocs.push_back(v);
+        MC_HIP(hipMemsetAsync(v, 0, bytes ? bytes : 16, p.stream));
+        *ptr = static_cast<P*>(v);
+        return MC_OK;
+    }
+    void
+    free_one(void* v)
+    {
+        auto it = std::find(allocs.begin(), allocs.end(), v);
+        if (it != allocs.end()) allocs.erase(it);
+        (void)hipFree(v);
+    }
+    // a buffer that only grows: `need` elements of `elem` bytes fit in `have`, or the stream drains and a zeroed buffer of `cap`
+    // elements takes its place (nothing in flight reads the old one then)
+    template <typename P> mc_status
+    reserve(P*& ptr, int& have, int need, int cap, size_t elem = sizeof(P))
+    {
+        if (need <= have) return MC_OK;
+        MC_HIP(hipStreamSynchronize(p.stream));
+        if (ptr) free_one(ptr);
+        ptr = nullptr;
+        have = 0;
+        mc_status s = alloc(&ptr, elem * (size_t)cap);
+        if (s != MC_OK) return s;
+        have = cap;
+        return MC_OK;
+    }
+    // a buffer made at the first call that needs it (the stream drains behind the allocation: the synchronous copies of the mc_row_*
+    // calls must find its zeros in place)
+    template <typename P> mc_status
+    ensure(P*& ptr, size_t bytes)
+    {
+        if (ptr) return MC_OK;
+        MC_HIP(hipSetDevice(p.ordinal));
+        mc_status s = alloc(&ptr, bytes);
+        if (s != MC_OK) return s;
+        MC_HIP(hipStreamSynchronize(p.stream));
+        return MC_OK;
+    }
+    // a per-row table goes up when it differs from what the device holds: once per call, and every call drains the stream before it
+    // returns, so `sent` is not touched while a copy reads it
+    template <typename T> mc_status
+    send_if_changed(T* dev, std::vector<T>& sent, const std::vector<T>& now)
+    {
+        if (sent.size() == now.size() && memcmp(sent.data(), now.data(), sizeof(T) * now.size()) == 0) return MC_OK;
+        sent = now;
+        MC_HIP(hipMemcpyAsync(dev, sent.data(), sizeof(T) * sent.size(), hipMemcpyHostToDevice, p.stream));
+        return MC_OK;
+    }
+
+    mc_status
+    launch(const std::string& name, unsigned gx, unsigned gy, unsigned gz, unsigned bx, unsigned lds, mcimpl::arg_pack&& a)
+    {
+        return mcimpl::decoder_launch(d, name, gx, gy, gz, bx, lds, std::move(a));
+    }
+    mc_status
+    launch(const mcimpl::launch_plan& l, mcimpl::arg_pack&& a)
+    {
+        return mcimpl::decoder_launch(d, l.name, l.gx, l.gy, l.gz, l.block, l.lds, std::move(a));
+    }
+
+    int mask_words() const { return (p.cfg.vocab + 31) / 32; }
+    char* kc_of(int layer, int row) const { return (char*)kc + ((size_t)layer * B + row) * cache_elems * 2; }
+    char* vt_of(int layer, int row) const { return (char*)vt + ((size_t)layer * B + row) * cache_elems * 2; }
+    mc_status ensure_tokens(int n) { return reserve(tokens_dev, tokens_cap, n * B, n * B); }
+
+    // the shared step state at position `pos` (slot = pos: a batch's cache never turns)
+    mc_status
+    set_pos(int pos)
+    {
+        return launch(steps[0].begin, mcimpl::pack(st, (int32_t)-1, (int32_t)pos, (int32_t)p.cfg.max_seq_len, (int32_t)p.pre_len, (int32_t)0, (int32_t)1));
+    }
+
+    // ---------------------------------------------------------------- one token (batch.cc)
+    mc_status gemv(const mcimpl::batch_linear& L, const mcimpl::batch_gemv_plan& g, const void* xin, void* y, uint32_t ldy);
+    // the plans of a call: its step (plan_call), and the rows' logit processors and pick, with their tables sent (plan_pick: a rows pass)
+    mc_status plan_call(bool ragged);
+    mc_status plan_pick(bool ragged);
+    mc_status enqueue_token(int pos, bool advance);
+    mc_status head(bool ragged, bool count);
+    mc_status process_logits(bool ragged, bool count);
+    // ---------------------------------------------------------------- the rows passes (batch_rows.cc)
+    mc_status verify_head(const void* xrows, const int32_t* tokens, int M, int nseg, const mcimpl::tv_node* nodes = nullptr);
+};
+
+namespace mcimpl {
+
+// fail() for a refusal of batch_plan.h ("" = none)
+inline mc_status
+refuse(const std::string& why, mc_status code = MC_ERR_INVALID_ARGUMENT)
+{
+    return why.empty() ? MC_OK : fail(code, why);
+}
+
+// the batch, row and (with_layer) layer of the call `who`: one check, the caller's name in front of its text
+inline mc_status
+find_row(const mc_batch* b, const char* who, int32_t row, bool with_layer = false, int32_t layer = 0)
+{
+    return refuse(check_row(who, b ? b->B : -1, row, b && with_layer ? (int)b->p.layers.size() : -1, layer));
+}
+
+} // namespace mcimpl

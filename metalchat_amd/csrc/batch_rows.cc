@@ -1,0 +1,207 @@
+// The batch's rows passes (Parts 2d to 2g; the map of the whole: batch_impl.h): mc_rows_prefill, mc_extend_rows, mc_verify_rows and
+// mc_tree_verify through one body, rows_pass -- the admission and the tables are rows_plan.h's, the prompt pass the decoder's, the head behind it
+// the batch's own (head(), or verify_head() with what plan_verify_head plans) -- and mc_verify_get_logits.
+#include "batch_impl.h"
+
+using namespace mcimpl;
+
+// mc_verify_rows: the final norm, the head and a greedy pick for each of the M packed rows `xrows` of a call, then per segment
+// the acceptance of its drafts (`tokens`: the call's ids on the device) and the accepted row's logits into logits[row].
+// nodes (mc_tree_verify): the chunks are trees -- the walk in place of the prefix rule, then the accepted path's K / V
+// moved into place in every layer, both reading the device's own results
+mc_status
+mc_batch::verify_head(const void* xrows, const int32_t* tokens, int M, int nseg, const tv_node* nodes)
+{
+    const mc_decoder_config& c = p.cfg;
+    const batch_linear& L = p.output;
+    const verify_plan v = plan_verify_head(L, c, (int)p.layers.size(), M, nseg, nodes != nullptr);
+    mc_status s = launch(v.norm, pack(xrows, p.final_norm, v_xn, (uint32_t)c.dim, c.norm_eps));
+    if (s != MC_OK) return s;
+    s = launch(v.head, pack(L.w, L.scales, (const void*)v_xn, v_logits, (uint32_t)L.in, (uint32_t)L.ngroups, (uint32_t)L.group, (uint32_t)M,
+                            (uint32_t)L.out, (uint32_t)c.vocab));
+    if (s != MC_OK) return s;
+    int32_t* picks = v_out + 2 * B;
+    if ((s = launch(v.argmax, pack((const void*)v_logits, (uint32_t)c.vocab, picks))) != MC_OK) return s;
+    if (!v.tree)
+        return launch(v.accept, pack((const pp_seg*)pp_segs(pp_tab), tokens, (const int32_t*)picks, (const void*)v_logits, (uint32_t)c.vocab, v_out,
+                                     v_out + B, logits));
+    int32_t* paths = picks + M;
+    s = launch(v.accept, pack((const pp_seg*)pp_segs(pp_tab), tokens, nodes, (const int32_t*)picks, (const void*)v_logits, (uint32_t)c.vocab, v_out,
+                              v_out + B, paths, logits));
+    if (s != MC_OK) return s;
+    return launch(v.compact, pack((const pp_seg*)pp_segs(pp_tab), (const int32_t*)v_out, (const int32_t*)paths, kc, vt, (uint64_t)cache_elems,
+                                  (uint32_t)B, (uint32_t)c.n_kv_heads, (uint32_t)c.head_dim, (uint32_t)c.max_seq_len));
+}
+
+namespace {
+
+// what mc_verify_rows adds to the pass: a pick after every chunk row and the acceptance (next_tokens is the pass's own argument)
+struct verify_out {
+    int32_t* accepted; // [B]
+    int32_t* picks;    // [M], may be null
+    // mc_tree_verify: the chunks are trees
+    const int32_t* parents = nullptr; // [M], packed like the tokens
+    int32_t* paths = nullptr;         // [B][MC_VERIFY_MAX_LEN], may be null
+};
+
+// mc_rows_prefill, mc_extend_rows, mc_verify_rows and mc_tree_verify: one body, `extend` selects the attention (and `who` the
+// texts), `v` the head over every packed row in place of the head over each row's last, v->parents the tree form of that
+mc_status
+rows_pass(mc_batch* b, const char* who, bool extend, const int32_t* tokens, const int32_t* lens, const int32_t* positions, int32_t* next_tokens,
+          const verify_out* v = nullptr)
+{
+    const mc_decoder_config& c = b->p.cfg;
+    const int B = b->B;
+    // check (rows_plan.h: the admission, the tables and the scratch sizes are plain arithmetic there), tables, upload, prompt pass, head
+    const bool tree = v && v->parents;
+    const rows_counts n = rows_check(who, tokens, lens, positions, b->lengths.data(), B, c.max_seq_len, c.vocab, v != nullptr);
+    if (!n.refusal.empty()) return fail(MC_ERR_INVALID_ARGUMENT, n.refusal);
+    if (tree)
+        if (const std::string why = tree_check(who, v->parents, lens, B); !why.empty()) return fail(MC_ERR_INVALID_ARGUMENT, why);
+    const int M = n.M, nseg = n.nseg, ntiles = n.ntiles;
+    // MC_PX_KEYS, the experiment's handle on the key ranges, is read at the call (the tests set it between calls on a live batch)
+    const char* keys_env = getenv("MC_PX_KEYS");
+    const int keys_override = keys_env ? std::max(atoi(keys_env), 0) : PX_KEYS_RULE;
+    const rows_scratch sc = rows_scratch_of(c.max_seq_len, c.n_heads, c.head_dim, keys_override);
+    mc_status s;
+    MC_HIP(hipSetDevice(b->p.ordinal));
+    rows_tables(lens, positions, B, ntiles, b->rows_host, b->pp_host);
+    if (tree) tree_nodes(v->parents, lens, B, ntiles, M, b->pp_host);
+    if ((s = b->reserve(b->pp_tab, b->pp_tab_cap, (int)b->pp_host.size(), (int)sc.tab_bytes())) != MC_OK) return s;
+    MC_HIP(hipMemcpyAsync(b->pp_tab, b->pp_host.data(), b->pp_host.size(), hipMemcpyHostToDevice, b->p.stream));
+    packed_prefill pk;
+    pk.segs = pp_segs(b->pp_tab);
+    pk.nseg = nseg;
+    pk.tiles = pp_tiles(b->pp_tab);
+    pk.ntiles = ntiles;
+    if (tree) pk.nodes = tv_nodes(b->pp_tab, ntiles);
+    MC_HIP(hipMemcpyAsync(b->rows, b->rows_host.data(), sizeof(step_state) * B, hipMemcpyHostToDevice, b->p.stream));
+    if ((s = b->ensure_tokens(1)) != MC_OK) return s;
+    MC_HIP(hipMemsetAsync(b->tokens_dev, 0xFF, sizeof(int32_t) * B, b->p.stream));
+    pk.kc = b->kc;
+    pk.vt = b->vt;
+    pk.B = B;
+    pk.cache_stride = b->cache_elems;
+    pk.fcos = b->fcos;
+    pk.fsin = b->fsin;
+    pk.x_out = b->x;
+    if (extend) {
+        // scratch for one launch group, sized once (rows_scratch_of)
+        int sums_slots = b->px_slots;
+        if ((s = b->reserve(b->px_sums, sums_slots, sc.per_tile, sc.slots, sizeof(float) * c.n_heads * PP_TILE_ROWS)) != MC_OK ||
+            (s = b->reserve(b->px_part, b->px_slots, sc.per_tile, sc.slots, sc.per_slot)) != MC_OK)
+            return s;
+        rows_ranges(b->pp_host, ntiles, b->px_slots, keys_override, b->px_host, b->px_groups);
+        if ((s = b->reserve(b->px_tab, b->px_tab_cap, (int)b->px_host.size(), sc.tiles_max * sc.per_tile)) != MC_OK) return s;
+        MC_HIP(hipMemcpyAsync(b->px_tab, b->px_host.data(), sizeof(px_range) * b->px_host.size(), hipMemcpyHostToDevice, b->p.stream));
+        pk.extend = true;
+        pk.ranges = b->px_tab;
+        pk.groups = b->px_groups.data();
+        pk.ngroups = (int)b->px_groups.size();
+        pk.sums = b->px_sums;
+        pk.part = b->px_part;
+    }
+    const void* rows_all = nullptr;
+    const int32_t* ids = nullptr;
+    if (v) {
+        // (M <= 128 here; the scratch is sized for any call)
+        if ((s = b->reserve(b->v_xn, b->v_xn_cap, M, MC_VERIFY_MAX_ROWS, (size_t)c.dim * 2)) != MC_OK ||
+            (s = b->reserve(b->v_logits, b->v_logits_cap, M, MC_VERIFY_MAX_ROWS, (size_t)c.vocab * 2)) != MC_OK ||
+            (s = b->reserve(b->v_out, b->v_out_cap, 2 * B + M + MC_VERIFY_MAX_LEN * B, 2 * MC_WIDE_BATCH_MAX + MC_VERIFY_MAX_ROWS + MC_VERIFY_MAX_LEN * MC_WIDE_BATCH_MAX)) !=
+                MC_OK)
+            return s;
+        MC_HIP(hipMemsetAsync(b->v_out, 0xFF, sizeof(int32_t) * 2 * B, b->p.stream)); // -1: a row not in the call
+        if (tree) MC_HIP(hipMemsetAsync(b->v_out + 2 * B + M, 0xFF, sizeof(int32_t) * MC_VERIFY_MAX_LEN * B, b->p.stream)); // ... its path
+        pk.rows_all = &rows_all;
+        pk.tokens_dev = &ids;
+    }
+    if ((s = decoder_prefill_packed(b->d, tokens, M, pk)) != MC_OK) return s;
+    if (v) s = b->verify_head(rows_all, ids, M, nseg, pk.nodes);
+    else if ((s = b->plan_pick(true)) == MC_OK) s = b->head(true, false);
+    if (s != MC_OK) return s;
+    MC_HIP(hipStreamSynchronize(b->p.stream)); // (`tokens` is the caller's buffer; the tables are read by the launches)
+    if (v) {
+        b->v_rows = M;
+        b->v_host.resize(2 * B + M + (tree ? MC_VERIFY_MAX_LEN * B : 0));
+        MC_HIP(hipMemcpy(b->v_host.data(), b->v_out, sizeof(int32_t) * b->v_host.size(), hipMemcpyDeviceToHost));
+        std::copy_n(b->v_host.begin(), B, v->accepted);
+        if (next_tokens) std::copy_n(b->v_host.begin() + B, B, next_tokens);
+        if (v->picks) std::copy_n(b->v_host.begin() + 2 * B, M, v->picks);
+        if (v->paths) std::copy_n(b->v_host.begin() + 2 * B + M, MC_VERIFY_MAX_LEN * B, v->paths);
+        // the rejected drafts' slots stay written past the length: the rewound state every rows call handles
+        for (int r = 0; r < B; r++)
+            if (lens[r] > 0) b->lengths[r] = positions[r] + v->accepted[r] + 1;
+        return MC_OK;
+    }
+    for (int r = 0; r < B; r++)
+        if (lens[r] > 0) b->lengths[r] = positions[r] + lens[r];
+    if (next_tokens) MC_HIP(hipMemcpy(next_tokens, b->tokens_dev, sizeof(int32_t) * B, hipMemcpyDeviceToHost));
+    return MC_OK;
+}
+
+// mc_verify_rows / mc_tree_verify (`who`): every row in the call picks greedily, and none carries a mask or penalties
+mc_status
+verify_settings(const mc_batch* b, const char* who, const int32_t* lens)
+{
+    if (mc_status s = refuse(verify_samplers(who, lens, b->row_samplers, decoder_sampler_of(b->d))); s != MC_OK) return s;
+    return refuse(verify_logit_rows(who, lens, b->row_logit_set));
+}
+
+} // namespace
+
+extern "C" {
+
+// ---- Part 2d: the packed prompt pass ----
+
+mc_status
+mc_rows_prefill(mc_batch* b, const int32_t* tokens, const int32_t* lens, const int32_t* positions, int32_t* next_tokens)
+{
+    if (!b || !tokens || !lens || !positions) return fail(MC_ERR_INVALID_ARGUMENT, "mc_rows_prefill: null argument");
+    return rows_pass(b, "mc_rows_prefill", false, tokens, lens, positions, next_tokens);
+}
+
+// ---- Part 2e: chunks that see their row's context ----
+
+mc_status
+mc_extend_rows(mc_batch* b, const int32_t* tokens, const int32_t* lens, const int32_t* positions, int32_t* next_tokens)
+{
+    if (!b || !tokens || !lens || !positions) return fail(MC_ERR_INVALID_ARGUMENT, "mc_extend_rows: null argument");
+    return rows_pass(b, "mc_extend_rows", true, tokens, lens, positions, next_tokens);
+}
+
+// ---- Part 2f: speculative verify ----
+
+mc_status
+mc_verify_rows(mc_batch* b, const int32_t* tokens, const int32_t* lens, const int32_t* positions, int32_t* accepted, int32_t* next_tokens,
+               int32_t* picks)
+{
+    if (!b || !tokens || !lens || !positions || !accepted) return fail(MC_ERR_INVALID_ARGUMENT, "mc_verify_rows: null argument");
+    if (mc_status s = verify_settings(b, "mc_verify_rows", lens); s != MC_OK) return s;
+    const verify_out v{accepted, picks};
+    return rows_pass(b, "mc_verify_rows", true, tokens, lens, positions, next_tokens, &v);
+}
+
+// ---- Part 2g: speculative verify over a draft tree per row ----
+
+mc_status
+mc_tree_verify(mc_batch* b, const int32_t* tokens, const int32_t* parents, const int32_t* lens, const int32_t* positions, int32_t* accepted,
+               int32_t* next_tokens, int32_t* paths, int32_t* picks)
+{
+    if (!b || !tokens || !parents || !lens || !positions || !accepted) return fail(MC_ERR_INVALID_ARGUMENT, "mc_tree_verify: null argument");
+    if (mc_status s = verify_settings(b, "mc_tree_verify", lens); s != MC_OK) return s;
+    const verify_out v{accepted, picks, parents, paths};
+    return rows_pass(b, "mc_tree_verify", true, tokens, lens, positions, next_tokens, &v);
+}
+
+mc_status
+mc_verify_get_logits(mc_batch* b, void* logits_T)
+{
+    if (!b || !logits_T) return fail(MC_ERR_INVALID_ARGUMENT, "mc_verify_get_logits: null argument");
+    if (!b->v_rows) return fail(MC_ERR_INVALID_ARGUMENT, "mc_verify_get_logits: no mc_verify_rows call on this batch yet");
+    MC_HIP(hipSetDevice(b->p.ordinal));
+    MC_HIP(hipStreamSynchronize(b->p.stream));
+    MC_HIP(hipMemcpy(logits_T, b->v_logits, (size_t)b->v_rows * b->p.cfg.vocab * 2, hipMemcpyDeviceToHost));
+    return MC_OK;
+}
+
+} // extern "C"

@@ -444,7 +444,7 @@ mc_decoder::run_head()
     // make_default_sampler: per-chunk candidates, then one workgroup finishes the chain
     sampler_params p;
     uint32_t chunk;
-    if ((s = sampler_plan(top_k, cfg.vocab, inv_temp_T, top_p_T, &p, &chunk)) != MC_OK) return s;
+    if (const std::string why = sampler_plan(top_k, cfg.vocab, inv_temp_T, top_p_T, &p, &chunk); !why.empty()) return fail(MC_ERR_RUNTIME, why);
     s = launch("mc_topk_candidates_" + tname, p.nlists, 1, 1, 64, 0, pack(logits, (uint32_t)cfg.vocab, p.kpad, cand, chunk));
     if (s != MC_OK) return s;
     return launch("mc_sample_" + tname, 1, 1, 1, 128, p.cap * 8,
@@ -1134,7 +1134,7 @@ mc_decoder_time_gemv(mc_decoder* d, const char* which, int32_t repeats, float* t
 } // extern "C"
 
 // ------------------------------------------------------------------------------------------------
-// What the batched decode (batch.cc) reads of a decoder: decoder_batch.h
+// What the batched decode (batch_impl.h and its units) reads of a decoder: decoder_batch.h
 // ------------------------------------------------------------------------------------------------
 namespace mcimpl {
 
@@ -1216,20 +1216,6 @@ mc_status
 decoder_launch(mc_decoder* d, const std::string& name, unsigned gx, unsigned gy, unsigned gz, unsigned bx, unsigned lds, arg_pack&& args)
 {
     return d->launch(name, gx, gy, gz, bx, lds, std::move(args));
-}
-
-mc_status
-sampler_plan(int top_k, int vocab, float inv_temp_T, float top_p_T, sampler_params* p, uint32_t* chunk)
-{
-    uint32_t kpad = 1;
-    while (kpad < (uint32_t)top_k) kpad *= 2;
-    const uint32_t k = (uint32_t)std::min(top_k, vocab);
-    *chunk = std::max(512u, kpad);
-    while (*chunk < 2048u && ((uint32_t)vocab + *chunk - 1) / *chunk > MC_SAMPLE_LISTS_MAX) *chunk *= 2;
-    const uint32_t lists = ((uint32_t)vocab + *chunk - 1) / *chunk;
-    if (lists > MC_SAMPLE_LISTS_MAX) return fail(MC_ERR_RUNTIME, "sampler: the fused sampler handles rows of up to 2048 * 1024 logits");
-    *p = sampler_params{k, lists * kpad, SAMPLE_CAP, inv_temp_T, top_p_T, lists, kpad};
-    return MC_OK;
 }
 
 } // namespace mcimpl

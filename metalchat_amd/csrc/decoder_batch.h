@@ -1,27 +1,26 @@
-// What the batched decode (batch.cc, mc_batch_*) needs from a decoder (decoder.cc): the device addresses of its weights, norms,
+// What the batched decode (batch_impl.h and its units, mc_batch_*) needs from a decoder (decoder.cc): the device addresses of its weights, norms,
 // embedding, head and caches as they lie in HBM, its sampler settings, and its launch path (the launch log included).  Nothing
 // here changes the decoder.
 #pragma once
 
 #include "backend_impl.h"
 #include "kernels/abi.h"
+#include "batch_plan.h" // linear_shape, decoder_sampler: what a batch launches, decided without a device
 #include "rows_plan.h" // the tables of the packed prompt pass as the host builds them
 
 namespace mcimpl {
 
 using namespace mc::abi;
 
-// one fused matrix as decoder.cc holds it: rows [out][in] in MC_WFMT_* format, bfloat scales in row quads
-struct batch_linear {
-    int fmt = MC_WFMT_T, out = 0, in = 0, group = 0, ngroups = 0;
+// one fused matrix as decoder.cc holds it: its shape (batch_plan.h linear_shape: all that the admission and the launch plans
+// read) and where it lies -- rows [out][in] in MC_WFMT_* format, bfloat scales in row quads
+struct batch_linear : linear_shape {
     const void* w = nullptr;
     const void* scales = nullptr;
-    bool lora = false;
     // its LoRA adaptor(s), when lora (mc_decoder_load_lora): the stacked A matrices, plain T [lora_cols][in]; B [out][lora_cols] of T in
     // fused row order, zeros outside a row's own adaptor columns; lora_cols = adaptors x rank
     const void* lora_a = nullptr;
     const void* lora_b = nullptr;
-    int lora_cols = 0;
     float lora_scale = 0.0f;
 };
 
@@ -46,11 +45,6 @@ struct decoder_parts {
     std::vector<batch_layer> layers;
 };
 
-struct decoder_sampler {
-    int kind = MC_SAMPLER_GREEDY, top_k = 50;
-    float inv_temp_T = 0.0f, top_p_T = 0.0f;
-};
-
 // fails with MC_ERR_RUNTIME when the decoder's weights are not all loaded
 mc_status decoder_parts_of(mc_decoder* d, decoder_parts* out);
 decoder_sampler decoder_sampler_of(const mc_decoder* d);
@@ -58,11 +52,6 @@ decoder_sampler decoder_sampler_of(const mc_decoder* d);
 mc_status decoder_cache_state(mc_decoder* d, int* kv_len, bool* rolled);
 // a launch on the decoder's stream through its launch path (named ranges, mc_decoder_launch_log); args: the packed kernel arguments
 mc_status decoder_launch(mc_decoder* d, const std::string& name, unsigned gx, unsigned gy, unsigned gz, unsigned bx, unsigned lds, arg_pack&& args);
-// make_default_sampler's two launches over a row of `vocab` logits (sampler_kernels.hip): the candidate lists come from chunks of
-// 512 logits (1024 / 2048 where that would be more than MC_SAMPLE_LISTS_MAX lists), each sorted by ONE wave in registers, kpad =
-// top_k rounded up to a power of two keys per list; the second launch finds the k best of the sorted lists.  Fills the second
-// launch's parameters and the chunk of the first (its grid is p->nlists); fails where the row is too long for the second.
-mc_status sampler_plan(int top_k, int vocab, float inv_temp_T, float top_p_T, sampler_params* p, uint32_t* chunk);
 
 // The packed prompt pass (mc_rows_prefill and mc_extend_rows, kernels/packed_kernels.hip): the chunks of several sequences as one prompt pass of
 // M = sum of their lengths rows.  The tables are on the device already (uploaded on the decoder's stream).
@@ -72,7 +61,7 @@ struct packed_prefill {
     int nseg = 0;
     const pp_tile* tiles = nullptr; // [ntiles]: the 16-row attention tiles of every segment
     int ntiles = 0;
-    void* kc = nullptr;             // caches of layer l, batch row r at kc / vt + (l * B + r) * cache_stride elements (batch.cc kc_of / vt_of)
+    void* kc = nullptr;             // caches of layer l, batch row r at kc / vt + (l * B + r) * cache_stride elements (batch_impl.h kc_of / vt_of)
     void* vt = nullptr;
     int B = 0;
     uint64_t cache_stride = 0;

@@ -6,13 +6,16 @@
 //   prefill.cc         the prompt pass (run_prefill): it launches what prefill_plan.h plans -- GEMM family, attention, rope form, folds; no HIP there
 //   prefill_blaslt.cc  the library GEMM of long prompts -- the only unit that sees hipBLASLt's header
 //   pipeline.cc        the layer pipeline (RCCL / local); it holds decoders, it is not part of one
-// batch.cc does not include this header: it reads a decoder through decoder_batch.h.  Four headers beside the units need no device and are pinned
-// on the CPU by plain g++ programs (tests/cpp): gemv_plan.h (the decode GEMV), block_plan.h (the decode attention block), prefill_plan.h (the prompt
-// pass) and rows_plan.h (the admission and the tables of batch.cc's rows passes).
+// The batch's units (batch_impl.h) do not include this header: they read a decoder through decoder_batch.h.  Five headers beside the units need no
+// device and are pinned on the CPU by plain g++ programs (tests/cpp): gemv_plan.h (the decode GEMV), block_plan.h (the decode attention block),
+// prefill_plan.h (the prompt pass), rows_plan.h (the admission and the tables of the batch's rows passes) and batch_plan.h (what a batch launches);
+// sampler_plan.h plans the default sampler's two launches for the decoder and the batch alike.
 #pragma once
 
 #include "backend_impl.h"
+#include "bf16_host.h" // f2bf_host / bf2f_host
 #include "decoder_batch.h"
+#include "sampler_plan.h" // the two launches of the default sampler
 #include "gemv_plan.h" // decoder_options / read_options (decoder_options.h) and plan_gemv
 #include "block_plan.h" // plan_block: form, kernel and grid of the decode attention block
 #include "prefill_plan.h" // plan_gemm, plan_attention, plan_rope and the fold predicates of the prompt pass
@@ -90,25 +93,6 @@ struct layer_w {
     void* vt = nullptr;
     int rope_table = 0;
 };
-
-inline uint16_t
-f2bf_host(float f)
-{
-    uint32_t u;
-    memcpy(&u, &f, 4);
-    if ((u & 0x7f800000u) == 0x7f800000u && (u & 0x007fffffu)) return (uint16_t)((u >> 16) | 0x40u);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
-}
-
-inline float
-bf2f_host(uint16_t b)
-{
-    uint32_t u = (uint32_t)b << 16;
-    float f;
-    memcpy(&f, &u, 4);
-    return f;
-}
 
 inline int
 bit_width(uint32_t v)

@@ -4,7 +4,7 @@
 // pass's own launches; only the attention is here.
 //
 // The shape that matters is few chunk rows over many keys (a 20-token message behind 1900 tokens), so the KEYS of a 16-row tile are
-// dealt over workgroups in key ranges where the tile's segment is short (batch.cc px_range_keys).  The softmax has no max shift and p is rounded to T with the FULL row
+// dealt over workgroups in key ranges where the tile's segment is short (rows_plan.h px_range_keys).  The softmax has no max shift and p is rounded to T with the FULL row
 // sum, so the sums must be complete before any p exists -- three launches per layer, all over the range table:
 //
 //   mc_px_sums   (heads, ranges)  exp row sums of one key range                         -> sums[range][head][16]       fp32

@@ -15,7 +15,7 @@
 // The shape of the work is mc_v_head_*'s with WB_GROUPS = 4 column groups: a workgroup owns TILES 16-row weight tiles and all
 // column groups, so a weight is dequantised once per call and a B fragment (16 activation rows x 8 k per lane group) is used for
 // TILES weight tiles.  TILES is 1, 2, 4 or 8, taken from the grid: the launch that brings ceil(N / 16 / tiles) workgroups gets
-// `tiles` per workgroup.  The host picks it per matrix (batch.cc wb_tiles): a matrix of few rows needs its workgroups to reach every
+// `tiles` per workgroup.  The host picks it per matrix (batch_plan.h wb_tiles): a matrix of few rows needs its workgroups to reach every
 // compute unit, a matrix of many can spend them on fewer fetches of x.  The tile count does not reach the bits: the accumulators
 // of two tiles never meet.  Column groups at or past M are skipped (wave-uniform), rows past M inside the last group are zero
 // operands and are not stored.

@@ -430,7 +430,7 @@ mc_decoder::run_prefill(int M, int cache_pos, int rope_pos, int window, const vo
                                   hipMemcpyDeviceToDevice, stream));
     }
     if (pk) {
-        // the batch's head follows (batch.cc): the last row of each chunk into its batch row
+        // the batch's head follows (batch_rows.cc): the last row of each chunk into its batch row
         s = launch("mc_pp_gather_last_bfloat", gd, (unsigned)pk->nseg, 1, 256, 0, pack((const void*)pf_x, pk->segs, pk->x_out, (uint32_t)dim));
         if (pk->rows_all) *pk->rows_all = pf_x;
         if (pk->tokens_dev) *pk->tokens_dev = pf_tokens;

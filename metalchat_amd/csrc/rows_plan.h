@@ -1,8 +1,8 @@
-// The host side of the rows passes (mc_rows_prefill, mc_extend_rows, mc_verify_rows, mc_tree_verify; batch.cc rows_pass) without a device: the
+// The host side of the rows passes (mc_rows_prefill, mc_extend_rows, mc_verify_rows, mc_tree_verify; batch_rows.cc rows_pass) without a device: the
 // admission of a call (rows_check, tree_check), the tables its kernels index memory by -- pp_seg / pp_tile / tv_node (rows_tables, tree_nodes),
 // px_range and the launch groups (rows_ranges) -- and the scratch sizes derived from them (rows_scratch_of).  Plain C++ over kernels/abi.h, no
 // HIP, so tests/cpp/test_rows_plan.cc prints exactly what a call uploads and tests/rows_tables.py / tree_rule.py, which the kernel-level tests
-// build their tables with, are held to it on the CPU.  batch.cc keeps fail(), the reserves, the copies and the launches.
+// build their tables with, are held to it on the CPU.  batch_rows.cc keeps fail(), the reserves, the copies and the launches.
 #pragma once
 
 #include <algorithm>

@@ -1,4 +1,4 @@
-"""tests/cpp/test_rows_plan -- a plain g++ program over metalchat_amd/csrc/rows_plan.h, the header batch.cc builds the tables of a rows pass
+"""tests/cpp/test_rows_plan -- a plain g++ program over metalchat_amd/csrc/rows_plan.h, the header batch_rows.cc builds the tables of a rows pass
 with -- asked from Python: what the C++ rules make of a call, for the tests that hold rows_tables.py and tree_rule.py to them."""
 import json
 import subprocess

@@ -13,7 +13,7 @@ from metalchat_amd import build as b
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 READELF = ["/opt/rocm/lib/llvm/bin/llvm-readelf", "/usr/bin/readelf"]
 
-# every name batch.cc can form: mc_b_gemv_{i4|w}_bfloat_e{0,1,2} and the per-row launches, plus the existing kernels it reuses
+# every name the batch plan (batch_plan.h) can form: mc_b_gemv_{i4|w}_bfloat_e{0,1,2} and the per-row launches, plus the existing kernels it reuses
 BATCH_KERNELS = [f"mc_b_gemv_{f}_bfloat_e{e}" for f in ("i4", "w") for e in (0, 1, 2)] + [
     "mc_b_embed_bfloat", "mc_b_rmsnorm_bfloat", "mc_b_rope_kv_bfloat", "mc_b_attn_scores_bfloat", "mc_b_attn_pv_bfloat",
     "mc_b_argmax_bfloat", "mc_b_topk_candidates_bfloat", "mc_b_sample_bfloat",

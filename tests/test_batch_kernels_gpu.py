@@ -144,7 +144,7 @@ class Packed:
         return y, a
 
     def launch(self, acc, x, epi=0, ldy=None, y_init=None, y_rows=None):
-        """mc_b_gemv_* as batch.cc launches it: out / 16 workgroups of 512 threads; B = rows of x; y rows at stride ldy"""
+        """mc_b_gemv_* as batch.cc launches it (batch_plan.h plan_batch_gemv): out / 16 workgroups of 512 threads; B = rows of x; y rows at stride ldy"""
         import metalchat_amd as mc
 
         B = x.shape[0]

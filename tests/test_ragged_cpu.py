@@ -1,5 +1,5 @@
 """Ragged rows (mc_ragged_*, include/metalchat_hip.h Part 2c) without a GPU: every entry point is exported and bound, every
-per-row kernel name batch.cc can form is in the code object, and the arguments that need no device are refused."""
+per-row kernel name the batch plan (batch_plan.h) can form is in the code object, and the arguments that need no device are refused."""
 import ctypes as C
 import os
 import re
@@ -7,13 +7,14 @@ import subprocess
 
 import pytest
 
+import batch_plan_program as bp
 import metalchat_amd as mc
 from metalchat_amd import build as b
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 READELF = ["/opt/rocm/lib/llvm/bin/llvm-readelf", "/usr/bin/readelf"]
 
-# what a ragged step launches besides the lockstep kernels it shares (the GEMVs, rmsnorm, top-k candidates): batch.cc forms
+# what a ragged step launches besides the lockstep kernels it shares (the GEMVs, rmsnorm, top-k candidates): batch_plan.h forms
 # the per-row names as "mc_b_<kernel>" + "_rows_bfloat"
 RAGGED_KERNELS = ["mc_b_rows_begin", "mc_b_embed_rows_bfloat"] + [
     f"mc_b_{k}_rows_bfloat" for k in ("rope_kv", "attn_scores", "attn_pv", "argmax", "sample")] + [
@@ -39,8 +40,8 @@ def test_every_ragged_entry_point_is_exported_and_bound():
 
 
 def test_every_ragged_kernel_is_in_the_code_object():
-    src = open(os.path.join(ROOT, "metalchat_amd", "csrc", "batch.cc")).read()
-    assert '"_rows_bfloat"' in src and '"mc_b_rows_begin"' in src
+    formed = bp.formed_names()   # (the host forms these names: batch_plan.h through tests/cpp/test_batch_plan)
+    assert "mc_b_rows_begin" in formed and not [n for n in RAGGED_KERNELS if n.endswith("_rows_bfloat") and n not in formed]
     hsaco, _ = b.build_all()
     tool = next((t for t in READELF if os.path.exists(t)), None)
     if tool is None:

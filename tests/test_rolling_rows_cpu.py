@@ -7,6 +7,7 @@ import os
 import re
 import subprocess
 
+import batch_plan_program as bp
 import metalchat_amd as mc
 import rolling_rule as rr
 from metalchat_amd import build as b
@@ -42,8 +43,8 @@ def test_the_entry_points_are_declared_exported_and_bound():
 
 
 def test_the_rolling_kernel_is_in_the_code_object_and_the_host_names_it():
-    host = open(os.path.join(ROOT, "metalchat_amd", "csrc", "batch.cc")).read()
-    assert '"mc_b_rows_begin_rolling"' in host and '"mc_b_rows_begin"' in host   # the default launch stays
+    formed = bp.formed_names()   # (batch_plan.h through tests/cpp/test_batch_plan)
+    assert "mc_b_rows_begin_rolling" in formed and "mc_b_rows_begin" in formed   # the default launch stays
     out = readelf("--symbols", "--wide")
     symbols = {line.split()[-1] for line in out.splitlines() if " FUNC " in line}
     assert not [n for n in ROLLING_KERNELS if n not in symbols]

@@ -60,7 +60,7 @@ def table(settings):
 
 
 def run_mixed(acc, lb, settings, ragged):
-    """the two launches as batch.cc head() makes them; returns (the rows' states before, after, tokens_out)"""
+    """the two launches as batch.cc head() makes them from batch_plan.h plan_head(); returns (the rows' states before, after, tokens_out)"""
     import metalchat_amd as mc
 
     kpad = 1

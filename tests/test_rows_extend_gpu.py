@@ -179,7 +179,7 @@ def test_the_launch_log(acc, small):
 
 
 def test_a_call_in_several_launch_groups(acc, monkeypatch):
-    """a call whose ranges exceed the scratch of one launch group (batch.cc rows_ranges: groups of whole tiles, the kernels' `ebase`):
+    """a call whose ranges exceed the scratch of one launch group (rows_plan.h rows_ranges: groups of whole tiles, the kernels' `ebase`):
     eight rows of 200 tokens behind 1800 keys with ranges of 128 keys -- 13 tiles of 15 or 16 ranges per row, 1608 ranges, and a
     scratch of 64 MiB / (8 heads * 16 rows * 128 * 4 bytes) = 1024 slots: two groups.  A row's bits depend on its own segment only,
     so every row must come out bit for bit as it does extended alone, in a call of its own that fits one group (201 ranges)"""

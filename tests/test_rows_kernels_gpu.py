@@ -1,6 +1,6 @@
 """Kernel-level parity of the packed prompt pass (kernels/packed_kernels.hip, mc_pp_*) and of the chunks that see their row's context
 (kernels/extend_kernels.hip, mc_px_*): every kernel launched BY NAME through the Part-1 seam on buffers the test owns, with tables
-built by rows_tables.py (the restatement of batch.cc's rules), against a plain reference of the same operation:
+built by rows_tables.py (the restatement of rows_plan.h's rules), against a plain reference of the same operation:
 
   * mc_px_sums{,2} + mc_px_pv{,2} + mc_px_reduce: chunk row i at position p = pos + i against the oracle's attention over the keys
     [0, p] of its row, with the bound of the decode attention (test_batch_kernels_gpu.test_b_attention_per_row); the one-head and

@@ -1,6 +1,6 @@
 """rows_tables.py (the Python restatement of the C++ rules rows_tables / rows_ranges / px_range_keys that test_rows_kernels_gpu.py builds its
 tables with) against examples worked by hand from the C++ rule, the properties the kernels rely on -- and against the C++ rules themselves:
-they live in csrc/rows_plan.h, a header without HIP that batch.cc builds every call's tables with, and tests/cpp/test_rows_plan (a plain g++
+they live in csrc/rows_plan.h, a header without HIP that batch_rows.cc builds every call's tables with, and tests/cpp/test_rows_plan (a plain g++
 program over it, rows_plan_program.py) must print the restatement's segments, tiles, ranges and groups for every by-hand example here, the calls
 of test_rows_extend_gpu.py and 300 random calls.  A host rule that changes fails here, before a kernel test goes on testing the old one.
 test_rows_extend_gpu.test_a_call_in_several_launch_groups still binds the uploaded tables on the device."""

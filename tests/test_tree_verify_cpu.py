@@ -10,6 +10,7 @@ import subprocess
 
 import numpy as np
 
+import batch_plan_program as bp
 import metalchat_amd as mc
 import rows_plan_program as rp
 import tree_rule as tr
@@ -48,9 +49,9 @@ def test_the_entry_point_is_declared_once_exported_and_bound():
 
 def test_the_tree_kernels_are_exactly_the_set_in_the_code_object():
     assert len(TREE_KERNELS) == 12
-    host = open(os.path.join(ROOT, "metalchat_amd", "csrc", "batch.cc")).read()
-    for stem in ('"mc_tv_accept"', '"mc_tv_compact_bfloat"'):
-        assert stem in host, stem
+    formed = bp.formed_names()   # (the host forms these names: batch_plan.h through tests/cpp/test_batch_plan)
+    for name in ("mc_tv_accept", "mc_tv_compact_bfloat"):
+        assert name in formed, name
     dec = open(os.path.join(ROOT, "metalchat_amd", "csrc", "prefill_plan.h")).read()   # (the names prefill.cc launches are formed there)
     for stem in ('"mc_tv_sums"', '"mc_tv_pv"', '"mc_tv_rope_cache_bfloat"', '"mc_tv_rope_cache_parts_bfloat"'):
         assert stem in dec, stem

@@ -5,7 +5,7 @@ every row.  Per B in 8, 16, 17, 32, 64 two variants: `wide`, one mc_batch_genera
 and `narrow`, the same on each of the ceil(B / 8) mc_batch_create batches one after another -- what the rows cost without the wide
 batch.  All variants alternate in one process: a warm-up round, then 5 timed rounds, each timed region ending in the call's own host
 synchronisation; median, min and max per variant.  B = 16 runs on mc_b_gemv_*, B = 17 on mc_wb_gemv_*: what the 16-row line costs.
---tiles: also B = 64 with MC_WB_TILES = 1, 2, 4, 8 (weight tiles per workgroup for every matrix, in place of batch.cc's rule).
+--tiles: also B = 64 with MC_WB_TILES = 1, 2, 4, 8 (weight tiles per workgroup for every matrix, in place of batch_plan.h's rule (wb_tiles)).
 Prints one JSON line.
 
 usage: python tools/wide_batch_bench.py [--out FILE] [--tiles] [--only B]      (--only: the wide variant of B alone, e.g. under a trace)
