@@ -288,15 +288,39 @@ void mc_pipeline_release(mc_pipeline* p);
  *                       partial_sorts the vocabulary on the CPU).  Errors as nucleus_sampler's
  *                       constructor ("temperature must be positive", "probability must be in
  *                       [0.0, 1.0]").  top_k <= 128.  Equal logits are ordered by index
- *                       (std::partial_sort leaves them unspecified).
+ *                       (std::partial_sort leaves them unspecified).  The reference's multinomial reads
+ *                       the lower end of its draw interval at column sample_size - 1 = 0, so the
+ *                       interval is empty and the pick is the head of the sorted nucleus WHATEVER the
+ *                       seeds are; reproduced bit for bit.
+ *   MC_SAMPLER_DRAW   : the sampler whose pick depends on its seeds (opt-in; ours, not the reference's).
+ *                       MC_SAMPLER_DEFAULT's chain unchanged up to the nucleus cut -- the seven taps are
+ *                       the same bits -- with its checks, texts, rounding and top_k <= 128; only the
+ *                       last phase differs.  In float32, not rounded to T, one operation per step, with
+ *                       m[j] = masked[j] (tap 5; sorted order, the zeros are a suffix), j = 0 .. k-1:
+ *                         total = ((0 + m[0]) + m[1]) + .. + m[k-1]     sequential, ascending j
+ *                         u     = the first uniform() of pcg32(seed0, seed1)
+ *                         t     = u * total
+ *                         c_j   = c_{j-1} + m[j] (c_{-1} = 0);  pos = the smallest j with c_j > t
+ *                         none (t rounded up to total; total is 0 or NaN): pos = the largest j with
+ *                               m[j] > 0, else 0
+ *                         token = ids[sidx[pos]]
+ *                       So: a masked entry is never picked (c does not grow there); k = 1 or top_p = 0
+ *                       gives position 0, MC_SAMPLER_DEFAULT's pick; P(pos = j) = m[j] / total to within
+ *                       the generator's 2^-23 step; there is no division on the device.
+ *                       NOTHING IS KEPT BETWEEN CALLS: a caller who uploads no pairs, or reuses the same
+ *                       pairs, gets the same u again.  A loop that samples uploads fresh pairs from the
+ *                       host's generator in front of each call -- n for n tokens of a decoder call,
+ *                       n * B for a batch call -- as the reference draws a new pair from its
+ *                       std::mt19937 for every call.
  * mc_decoder_set_seeds: the (init_state, init_seq) pairs kernel::multinomial draws from its
  * std::mt19937 per call (include/metalchat/kernel/multinomial.h:46-55); token i of one
  * mc_decoder_generate call uses pair i % n_pairs (mc_decoder_step: pair 0); no pairs = (0, 0). */
-enum { MC_SAMPLER_GREEDY = 0, MC_SAMPLER_DEFAULT = 1 };
+enum { MC_SAMPLER_GREEDY = 0, MC_SAMPLER_DEFAULT = 1, MC_SAMPLER_DRAW = 2 };
 mc_status mc_decoder_set_sampler(mc_decoder* d, int32_t kind, int32_t top_k, float temperature, float top_p);
 mc_status mc_decoder_set_seeds(mc_decoder* d, const uint64_t* seeds, int32_t n_pairs);
 /* After a step with taps enabled: [7][k] floats -- scaled logits, probabilities, sorted, cumsum,
- * cumsum - sorted, masked, vocabulary ids -- of the sampler chain. */
+ * cumsum - sorted, masked, vocabulary ids -- of the sampler chain, under MC_SAMPLER_DEFAULT and
+ * MC_SAMPLER_DRAW alike (the chain is one); refused under greedy. */
 mc_status mc_decoder_get_sampler_taps(mc_decoder* d, float* out_7xk);
 /* Debug / parity taps (synchronise the queue).  mc_decoder_set_taps(1) makes every step also
  * copy the hidden row after the embedding and after each owned layer into a tap buffer. */
@@ -612,10 +636,11 @@ mc_status mc_rolling_fork_row(mc_batch* b, int32_t dst, int32_t src);
  * Part 2k -- row samplers: each row of a batch picks with settings of its own.  A serving loop holds requests of different callers
  * -- one greedy, one at temperature 0.6 / top-p 0.9, one at temperature 1.0 / top-k 20 -- and one batch serves them all over one
  * pass of the weights.  A row slot is MC_SAMPLER_INHERIT (the default: it follows mc_decoder_set_sampler, read at every call, as
- * before), MC_SAMPLER_GREEDY or MC_SAMPLER_DEFAULT with its own top_k, temperature and top_p.
+ * before), MC_SAMPLER_GREEDY, or MC_SAMPLER_DEFAULT or MC_SAMPLER_DRAW with its own top_k, temperature and top_p.  Only a
+ * MC_SAMPLER_DRAW row's pick depends on its seed pair (Part 2: the rule, and why a loop uploads n * B fresh pairs per call).
  *   settings   belong to the row SLOT and hold until set again or reset; they are read at every call, as the decoder's sampler is.
  *              mc_batch_fork, mc_rolling_fork_row, imports and prompt passes leave them alone: a loop that refills a slot sets the
- *              slot's sampler with it.  MC_SAMPLER_DEFAULT takes mc_decoder_set_sampler's checks, texts and rounding.
+ *              slot's sampler with it.  MC_SAMPLER_DEFAULT and MC_SAMPLER_DRAW take mc_decoder_set_sampler's checks, texts and rounding.
  *   seeds      unchanged: token i of row r uses pair (i * B + r) % n_pairs (mc_batch_set_seeds).  A greedy row draws nothing; the
  *              pair index of a row does not depend on the other rows' kinds.
  *   the rows   the row contract extends to the sampler: a row's tokens, logits and K / V do not depend on B, on its index, or on
@@ -623,18 +648,20 @@ mc_status mc_rolling_fork_row(mc_batch* b, int32_t dst, int32_t src);
  *              whose decoder-wide sampler is X.  Every pick of every batch call (Parts 2b - 2e, 2h - 2j) goes through it.
  *   launches   no row samples: mc_b_argmax_*; all rows sample with equal settings: mc_b_topk_candidates_bfloat + mc_b_sample_*,
  *              both as before -- a batch on which no row sampler is set (or after mc_row_sampler_reset) launches exactly what it
- *              launched before this part.  Anything else: mc_b_topk_candidates_mixed_bfloat + mc_b_pick_mixed_*, which read a
+ *              launched before this part; all rows MC_SAMPLER_DRAW with equal settings: mc_b_topk_candidates_bfloat +
+ *              mc_draw_b_*.  Anything else (any mixture with a drawing row included): mc_b_topk_candidates_mixed_bfloat + mc_b_pick_mixed_*, which read a
  *              [B] table of the effective settings and branch per row (DESIGN.md s.4 "Row samplers").
  *   verify     mc_verify_rows and mc_tree_verify look at the EFFECTIVE sampler of the rows in the call (lens[r] > 0): a sampling
  *              row outside the call no longer blocks the others, and a row set to MC_SAMPLER_GREEDY verifies under a sampling
  *              decoder.  A row in the call that is not greedy is refused, nothing enqueued:
  *                "mc_verify_rows: row r: the row's sampler is not greedy (accepting sampled drafts needs the draft's probabilities)"
  *              (mc_tree_verify: its own prefix).  With no row sampler set the decoder-wide refusal keeps its text.
- * Not covered: accepting sampled drafts, log-probabilities, samplers other than these two, top_k above 128, the batch-1 decoder.
+ * Not covered: accepting sampled drafts, log-probabilities, samplers other than these three, top_k above 128, seed state kept on the device
+ * between calls, the batch-1 decoder.
  * ------------------------------------------------------------------------------------------ */
 enum { MC_SAMPLER_INHERIT = -1 }; /* a row that follows mc_decoder_set_sampler: the default of every row */
-/* kind: MC_SAMPLER_INHERIT, MC_SAMPLER_GREEDY or MC_SAMPLER_DEFAULT; top_k, temperature and top_p are checked for MC_SAMPLER_DEFAULT
- * only ("nucleus_sampler: temperature must be positive", "nucleus_sampler: probability must be in [0.0, 1.0]", "topk_sampler: the
+/* kind: MC_SAMPLER_INHERIT, MC_SAMPLER_GREEDY, MC_SAMPLER_DEFAULT or MC_SAMPLER_DRAW; top_k, temperature and top_p are checked for the
+ * last two only ("nucleus_sampler: temperature must be positive", "nucleus_sampler: probability must be in [0.0, 1.0]", "topk_sampler: the
  * fused sampler keeps 1..128 candidates").  An unknown kind, a row outside [0, B) and a null batch are refused with texts prefixed
  * "mc_row_sampler_set: ".  All MC_ERR_INVALID_ARGUMENT; a refused call launches nothing and changes nothing. */
 mc_status mc_row_sampler_set(mc_batch* b, int32_t row, int32_t kind, int32_t top_k, float temperature, float top_p);

@@ -100,7 +100,7 @@ def build_text_test(force: bool = False) -> str:
     return _build_cpp_test("test_text", _ABI_HEADERS, force, True)
 
 
-# The five plan programs are no part of build_all(): nothing of the package needs them, their CPU tests build them (a second or two) when they run.
+# The six plan programs are no part of build_all(): nothing of the package needs them, their CPU tests build them (a second or two) when they run.
 def build_gemv_plan_test(force: bool = False) -> str:
     """tests/cpp/test_gemv_plan: plan_gemv() (csrc/gemv_plan.h) from the command line -- no HIP and no host library."""
     return _build_cpp_test("test_gemv_plan", _PLAN_HEADERS, force, False)
@@ -125,6 +125,12 @@ def build_batch_plan_test(force: bool = False) -> str:
     """tests/cpp/test_batch_plan: what a batch launches (csrc/batch_plan.h) from the command line -- no HIP and no host library."""
     headers = [os.path.join(CSRC, f) for f in ("batch_plan.h", "rows_plan.h", "bf16_host.h", "sampler_plan.h")] + [os.path.join(CSRC, "kernels", "abi.h"), _ABI_HEADERS[1]]
     return _build_cpp_test("test_batch_plan", headers, force, False)
+
+
+def build_draw_plan_test(force: bool = False) -> str:
+    """tests/cpp/test_draw_plan: the pick of a batch with MC_SAMPLER_DRAW rows (csrc/batch_plan.h plan_head) -- no HIP and no host library."""
+    headers = [os.path.join(CSRC, f) for f in ("batch_plan.h", "rows_plan.h", "bf16_host.h", "sampler_plan.h")] + [os.path.join(CSRC, "kernels", "abi.h"), _ABI_HEADERS[1]]
+    return _build_cpp_test("test_draw_plan", headers, force, False)
 
 
 def build_all(force: bool = False):

@@ -26,7 +26,8 @@ namespace mcimpl {
 
 using namespace mc::abi;
 
-static_assert(ROW_SAMPLER_GREEDY == MC_SAMPLER_GREEDY && ROW_SAMPLER_DEFAULT == MC_SAMPLER_DEFAULT, "row_sampler::kind carries the public kinds");
+static_assert(ROW_SAMPLER_GREEDY == MC_SAMPLER_GREEDY && ROW_SAMPLER_DEFAULT == MC_SAMPLER_DEFAULT && ROW_SAMPLER_DRAW == MC_SAMPLER_DRAW,
+              "row_sampler::kind carries the public kinds");
 
 struct launch_plan {
     std::string name;
@@ -216,6 +217,7 @@ sampler_of_row(const row_setting& rs, const decoder_sampler& dec)
 // not known on the host):
 //   PICK_GREEDY   no row samples               mc_b_argmax
 //   PICK_UNIFORM  all sample, settings equal   mc_b_topk_candidates_bfloat + mc_b_sample with the plan of those settings
+//                 (all MC_SAMPLER_DRAW: + mc_draw_b, the same shape; the kind is one of the settings, so default and draw rows mix)
 //   PICK_MIXED    anything else                the two mixed launches over the table of effective settings
 // The first two are what a batch without row samplers launches for the decoder's sampler, argument for argument.  ragged: the _rows forms,
 // where rows whose pos is -1 get no pick.  cand_per_row: the candidate keys the batch holds for each row.
@@ -241,7 +243,7 @@ plan_head(const std::vector<row_setting>& rows, const decoder_sampler& dec, int 
     for (unsigned r = 0; r < B; r++) {
         const decoder_sampler e = sampler_of_row(rows[r], dec);
         const bool samples = e.kind != MC_SAMPLER_GREEDY;
-        h.table[r] = samples ? row_sampler{ROW_SAMPLER_DEFAULT, (uint32_t)std::min(e.top_k, vocab), e.inv_temp_T, e.top_p_T}
+        h.table[r] = samples ? row_sampler{e.kind == MC_SAMPLER_DRAW ? ROW_SAMPLER_DRAW : ROW_SAMPLER_DEFAULT, (uint32_t)std::min(e.top_k, vocab), e.inv_temp_T, e.top_p_T}
                              : row_sampler{ROW_SAMPLER_GREEDY, 0u, 0.0f, 0.0f};
         if (r > 0 && memcmp(&h.table[r], &h.table[0], sizeof(row_sampler)) != 0) alike = false;
         if (!samples) continue;
@@ -259,7 +261,7 @@ plan_head(const std::vector<row_setting>& rows, const decoder_sampler& dec, int 
     if (!h.refusal.empty()) return h;
     if (alike) {
         h.first = {"mc_b_topk_candidates_bfloat", h.sp.nlists, B, 1, 64, 0};
-        h.second = {"mc_b_sample" + sfx, 1, B, 1, 128, h.sp.cap * 8};
+        h.second = {(sm.kind == MC_SAMPLER_DRAW ? "mc_draw_b" : "mc_b_sample") + sfx, 1, B, 1, 128, h.sp.cap * 8};
     } else {
         h.first = {"mc_b_topk_candidates_mixed_bfloat", h.sp.nlists, B, 1, 64, 0};
         h.second = {"mc_b_pick_mixed" + sfx, 1, B, 1, 1024, h.sp.cap * 8};

@@ -45,10 +45,10 @@ mc_status
 mc_row_sampler_set(mc_batch* b, int32_t row, int32_t kind, int32_t top_k, float temperature, float top_p)
 {
     if (mc_status s = find_row(b, "mc_row_sampler_set", row); s != MC_OK) return s;
-    if (kind != MC_SAMPLER_INHERIT && kind != MC_SAMPLER_GREEDY && kind != MC_SAMPLER_DEFAULT)
+    if (kind != MC_SAMPLER_INHERIT && kind != MC_SAMPLER_GREEDY && kind != MC_SAMPLER_DEFAULT && kind != MC_SAMPLER_DRAW)
         return fail(MC_ERR_INVALID_ARGUMENT, "mc_row_sampler_set: unknown sampler");
     row_setting rs;
-    if (kind == MC_SAMPLER_DEFAULT) {
+    if (kind == MC_SAMPLER_DEFAULT || kind == MC_SAMPLER_DRAW) {
         // mc_decoder_set_sampler's checks and texts (nn/sampling.h:165-174), and its rounding (a batch is bfloat16)
         if (!(temperature > 0.0f)) return fail(MC_ERR_INVALID_ARGUMENT, "nucleus_sampler: temperature must be positive");
         if (top_p < 0.0f || top_p > 1.0f) return fail(MC_ERR_INVALID_ARGUMENT, "nucleus_sampler: probability must be in [0.0, 1.0]");

@@ -441,13 +441,14 @@ mc_decoder::run_head()
     if (sampler_kind == MC_SAMPLER_GREEDY)
         return launch("mc_argmax_" + tname, 1, 1, 1, 1024, 0,
                       pack(logits, (uint32_t)cfg.vocab, state, tokens_dev));
-    // make_default_sampler: per-chunk candidates, then one workgroup finishes the chain
+    // make_default_sampler: per-chunk candidates, then one workgroup finishes the chain (MC_SAMPLER_DRAW: the same chain, its last
+    // phase draws -- mc_draw_T)
     sampler_params p;
     uint32_t chunk;
     if (const std::string why = sampler_plan(top_k, cfg.vocab, inv_temp_T, top_p_T, &p, &chunk); !why.empty()) return fail(MC_ERR_RUNTIME, why);
     s = launch("mc_topk_candidates_" + tname, p.nlists, 1, 1, 64, 0, pack(logits, (uint32_t)cfg.vocab, p.kpad, cand, chunk));
     if (s != MC_OK) return s;
-    return launch("mc_sample_" + tname, 1, 1, 1, 128, p.cap * 8,
+    return launch((sampler_kind == MC_SAMPLER_DRAW ? "mc_draw_" : "mc_sample_") + tname, 1, 1, 1, 128, p.cap * 8,
                   pack(cand, p, seeds, (uint32_t)n_seed_pairs, state, tokens_dev,
                        want_taps ? sampler_taps : (float*)nullptr));
 }
@@ -654,9 +655,9 @@ mc_status
 mc_decoder_set_sampler(mc_decoder* d, int32_t kind, int32_t top_k, float temperature, float top_p)
 {
     if (!d) return fail(MC_ERR_INVALID_ARGUMENT, "mc_decoder_set_sampler: null argument");
-    if (kind != MC_SAMPLER_GREEDY && kind != MC_SAMPLER_DEFAULT)
+    if (kind != MC_SAMPLER_GREEDY && kind != MC_SAMPLER_DEFAULT && kind != MC_SAMPLER_DRAW)
         return fail(MC_ERR_INVALID_ARGUMENT, "mc_decoder_set_sampler: unknown sampler");
-    if (kind == MC_SAMPLER_DEFAULT) {
+    if (kind != MC_SAMPLER_GREEDY) { // MC_SAMPLER_DRAW shares the chain: the same checks, texts, rounding and allocations
         // the argument checks of nucleus_sampler (nn/sampling.h:165-174)
         if (!(temperature > 0.0f)) return fail(MC_ERR_INVALID_ARGUMENT, "nucleus_sampler: temperature must be positive");
         if (top_p < 0.0f || top_p > 1.0f)
@@ -707,7 +708,7 @@ mc_status
 mc_decoder_get_sampler_taps(mc_decoder* d, float* out_7xk)
 {
     if (!d || !out_7xk) return fail(MC_ERR_INVALID_ARGUMENT, "mc_decoder_get_sampler_taps: null argument");
-    if (d->sampler_kind != MC_SAMPLER_DEFAULT || !d->sampler_taps)
+    if (d->sampler_kind == MC_SAMPLER_GREEDY || !d->sampler_taps)
         return fail(MC_ERR_INVALID_ARGUMENT, "decoder: the default sampler is not active");
     MC_HIP(hipSetDevice(d->dev->ordinal));
     MC_HIP(hipStreamSynchronize(d->stream));

@@ -63,6 +63,7 @@ static_assert(sizeof(sampler_params) == 28 && alignof(sampler_params) == 4, "sam
 // the EFFECTIVE settings, resolved on the host: a row that inherits carries the decoder's
 constexpr int32_t ROW_SAMPLER_GREEDY = 0;  // (= MC_SAMPLER_GREEDY) the first index of the maximum; the other words are not read
 constexpr int32_t ROW_SAMPLER_DEFAULT = 1; // (= MC_SAMPLER_DEFAULT) make_default_sampler with the three words below
+constexpr int32_t ROW_SAMPLER_DRAW = 2;    // (= MC_SAMPLER_DRAW) the same chain, the last phase draws with the row's seed pair
 struct row_sampler {
     int32_t kind;   // ROW_SAMPLER_*
     uint32_t k;     // sampler_params::k

@@ -372,6 +372,15 @@ mc_b_sample_bfloat(const uint64_t* cand, sampler_params p, const uint64_t* seeds
     sample_body<BF>(cand + (size_t)r * p.ncand, p, seeds, n_seed_pairs, rows + r, tokens_out,
                     nullptr);
 }
+// MC_SAMPLER_DRAW per row: mc_b_sample_bfloat with the drawing last phase (sampler_kernels.hip draw_position); named outside
+// mc_b_* like its batch-1 form mc_draw_bfloat
+extern "C" __global__ void
+mc_draw_b_bfloat(const uint64_t* cand, sampler_params p, const uint64_t* seeds, uint32_t n_seed_pairs, step_state* rows,
+                 int32_t* tokens_out)
+{
+    const uint32_t r = blockIdx.y;
+    sample_body<BF, SAMPLE_LAST_DRAW>(cand + (size_t)r * p.ncand, p, seeds, n_seed_pairs, rows + r, tokens_out, nullptr);
+}
 
 // ------------------------------------------------------------------------------------------
 // Ragged rows (mc_ragged_*, Part 2c): every row at a position of its own.  rows[r] is then row r's whole step state -- pos,
@@ -537,12 +546,20 @@ mc_b_sample_rows_bfloat(const uint64_t* cand, sampler_params p, const uint64_t* 
     sample_body<BF>(cand + (size_t)r * p.ncand, p, seeds, n_seed_pairs, rows + r, tokens_out,
                     nullptr);
 }
+extern "C" __global__ void
+mc_draw_b_rows_bfloat(const uint64_t* cand, sampler_params p, const uint64_t* seeds, uint32_t n_seed_pairs, step_state* rows,
+                      int32_t* tokens_out)
+{
+    const uint32_t r = blockIdx.y;
+    if (row_idle(rows, r)) return;
+    sample_body<BF, SAMPLE_LAST_DRAW>(cand + (size_t)r * p.ncand, p, seeds, n_seed_pairs, rows + r, tokens_out, nullptr);
+}
 
 // ------------------------------------------------------------------------------------------
 // Row samplers (mc_row_sampler_*, Part 2k): every row picks with settings of its own.  samplers[r] holds row r's EFFECTIVE
-// settings (abi.h row_sampler, resolved on the host: greedy or the default sampler, never "inherit").  The two launches are the
+// settings (abi.h row_sampler, resolved on the host: greedy, the default sampler or the drawing one, never "inherit").  The two launches are the
 // uniform ones with the branch on the row's kind in front -- uniform per workgroup, the row is a grid index -- so a greedy row
-// computes mc_b_argmax_*'s pick and a sampling row mc_b_sample_*'s:
+// computes mc_b_argmax_*'s pick, a default row mc_b_sample_*'s and a drawing row mc_draw_b_*'s (the chain is one, the last phase the row's):
 //   launch 1  the candidate lists of the sampling rows with the CALL's kpad, the largest among its sampling rows.  The lists are
 //             exact (list w = the kpad best keys of chunk w, best first), so a row's k best keys are among the first k of each
 //             list whatever kpad >= k is: a larger kpad only appends keys that launch 2 drops.  Workgroups of greedy rows
@@ -576,7 +593,7 @@ pick_mixed_body(const bf16_t* logits, uint32_t n, const uint64_t* cand, const ro
         return;
     }
     const sampler_params p{s.k, nlists * kpad, cap, s.inv_temp, s.top_p, nlists, kpad};
-    sample_body<BF>(cand + (size_t)r * p.ncand, p, seeds, n_seed_pairs, rows + r, tokens_out, nullptr);
+    sample_body<BF, SAMPLE_LAST_ROW>(cand + (size_t)r * p.ncand, p, seeds, n_seed_pairs, rows + r, tokens_out, nullptr, s.kind == ROW_SAMPLER_DRAW);
 }
 extern "C" __global__ void __launch_bounds__(1024)
 mc_b_pick_mixed_bfloat(const bf16_t* logits, uint32_t n, const uint64_t* cand, const row_sampler* samplers, uint32_t nlists,

@@ -473,10 +473,47 @@ using namespace mc::abi;
 
 // launch 2: one workgroup.  Dynamic LDS: ncand_pad keys.  taps (optional): 7*k floats, the
 // intermediates in the order of mco_sample_default.
-template <typename T>
+//
+// LAST, the compile-time switch of the last phase -- everything up to it (the seven taps) is one chain for every sampler:
+//   SAMPLE_LAST_DEFAULT  MC_SAMPLER_DEFAULT: the reference's multinomial(sample_size 1), whose draw interval is empty (below)
+//   SAMPLE_LAST_DRAW     MC_SAMPLER_DRAW: the pick depends on the seed pair (draw_position)
+//   SAMPLE_LAST_ROW      one of the two by `draw_row` (uniform over the workgroup): the mixed batch kernels, whose rows differ
+//
+// MC_SAMPLER_DRAW's rule is OURS, not the reference's, so it is float32 and not rounded to T; one operation per
+// step, in this order, with m[j] = masked[j] (tap 5: sorted order, the zeros are a suffix):
+//   total = ((0 + m[0]) + m[1]) + .. + m[k-1]         sequential, ascending j
+//   u     = the first uniform() of pcg32(seed0, seed1)  the generator and the pair choice of MC_SAMPLER_DEFAULT
+//   t     = u * total
+//   c_j   = c_{j-1} + m[j] (c_{-1} = 0);  pos = the smallest j with c_j > t
+//   none (t rounded up to total; total is 0 or NaN): pos = the largest j with m[j] > 0, else 0
+//   token = ids[sidx[pos]]
+// What follows: a masked entry is never picked (c does not grow there); k = 1 or top_p = 0 gives position 0, MC_SAMPLER_DEFAULT's
+// pick; P(pos = j) = m[j] / total to within the generator's 2^-23 step; no division on the device.  One thread's serial sums over
+// at most 128 LDS values.  Nothing is kept between calls: the same pair gives the same u again, so a caller uploads fresh pairs
+// in front of each call (include/metalchat_hip.h Part 2).
+enum { SAMPLE_LAST_DEFAULT = 0, SAMPLE_LAST_DRAW = 1, SAMPLE_LAST_ROW = 2 };
+
+__device__ __forceinline__ int32_t
+draw_position(const float* m, uint32_t k, float u)
+{
+    float total = 0.0f;
+    for (uint32_t j = 0; j < k; j++) total = total + m[j];
+    const float t = u * total;
+    float c = 0.0f;
+    int32_t pos = -1, last = 0;
+    for (uint32_t j = 0; j < k; j++) {
+        const float mj = m[j];
+        c = c + mj;
+        if (pos < 0 && c > t) pos = (int32_t)j;
+        if (mj > 0.0f) last = (int32_t)j;
+    }
+    return pos < 0 ? last : pos;
+}
+
+template <typename T, int LAST = SAMPLE_LAST_DEFAULT>
 __device__ __forceinline__ void
 sample_body(const uint64_t* cand, sampler_params p, const uint64_t* seeds, uint32_t n_seed_pairs,
-            step_state* st, int32_t* tokens_out, float* taps)
+            step_state* st, int32_t* tokens_out, float* taps, bool draw_row = false)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     uint64_t* keys = reinterpret_cast<uint64_t*>(smem);
@@ -681,10 +718,16 @@ sample_body(const uint64_t* cand, sampler_params p, const uint64_t* seeds, uint3
     // multinomial(sample_size 1) + gather: see multinomial_body for the interval quirk
     if (tid == 0) {
         const uint64_t s0 = n_seed_pairs ? seed0 : 0ull, s1 = n_seed_pairs ? seed1 : 0ull;
-        const float a = val[0], b = val[0]; // column output.size(1) - 1 == 0
         pcg32 g(s0, s1);
-        const float random = T::rt(g.uniform() * (b - a) + a);
-        const int32_t pos = descending_search<T>([&](uint32_t m) { return val[m]; }, k, random);
+        const bool draw = LAST == SAMPLE_LAST_ROW ? draw_row : LAST == SAMPLE_LAST_DRAW;
+        int32_t pos;
+        if (draw) {
+            pos = draw_position(val, k, g.uniform());
+        } else {
+            const float a = val[0], b = val[0]; // column output.size(1) - 1 == 0
+            const float random = T::rt(g.uniform() * (b - a) + a);
+            pos = descending_search<T>([&](uint32_t m) { return val[m]; }, k, random);
+        }
         const int32_t token = ids[sidx[pos]];
         st->token = token;
         if (tokens_out) tokens_out[st->step_index] = token;
@@ -702,4 +745,17 @@ mc_sample_float(const uint64_t* cand, sampler_params p, const uint64_t* seeds, u
                 step_state* st, int32_t* tokens_out, float* taps)
 {
     sample_body<F32>(cand, p, seeds, n_seed_pairs, st, tokens_out, taps);
+}
+// MC_SAMPLER_DRAW's launch 2: mc_sample_T's arguments, the last phase draws
+extern "C" __global__ void
+mc_draw_bfloat(const uint64_t* cand, sampler_params p, const uint64_t* seeds, uint32_t n_seed_pairs,
+               step_state* st, int32_t* tokens_out, float* taps)
+{
+    sample_body<BF, SAMPLE_LAST_DRAW>(cand, p, seeds, n_seed_pairs, st, tokens_out, taps);
+}
+extern "C" __global__ void
+mc_draw_float(const uint64_t* cand, sampler_params p, const uint64_t* seeds, uint32_t n_seed_pairs,
+              step_state* st, int32_t* tokens_out, float* taps)
+{
+    sample_body<F32, SAMPLE_LAST_DRAW>(cand, p, seeds, n_seed_pairs, st, tokens_out, taps);
 }

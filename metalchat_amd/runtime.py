@@ -51,7 +51,15 @@ class TensorInfo(C.Structure):
 
 CKPT_META_LLAMA3, CKPT_HF_LLAMA3, CKPT_META_LLAMA3_QLORA, CKPT_HF_GEMMA3 = 0, 1, 2, 3
 SAMPLER_GREEDY, SAMPLER_DEFAULT = 0, 1
+SAMPLER_DRAW = 2      # the sampler whose pick depends on its seed pairs (include/metalchat_hip.h Part 2)
 SAMPLER_INHERIT = -1  # a batch row that follows the decoder's sampler (Batch.set_row_sampler)
+
+
+def seed_pairs(rng, count: int) -> np.ndarray:
+    """`count` (init_state, init_seq) pairs, uint64 [count][2], from the numpy Generator `rng`.  Nothing is kept on the device between
+    calls, so a loop that samples with SAMPLER_DRAW uploads fresh pairs in front of EVERY call -- n for the n tokens of a decoder
+    call, n * B for a batch call (token i of row r uses pair i * B + r) -- or it gets the same draws again."""
+    return rng.integers(0, 2**64, size=(int(count), 2), dtype=np.uint64)
 
 _lib = None
 
@@ -630,7 +638,9 @@ class Decoder:
 
     # -- sampler ------------------------------------------------------------------------------
     def set_sampler(self, kind: int, top_k: int = 50, temperature: float = 0.6, top_p: float = 0.9):
-        """kind: SAMPLER_GREEDY / SAMPLER_DEFAULT (make_default_sampler, nn/sampling.h:303-313)."""
+        """kind: SAMPLER_GREEDY / SAMPLER_DEFAULT (make_default_sampler, nn/sampling.h:303-313; like the reference's, its pick
+        does not depend on the seeds) / SAMPLER_DRAW (the same chain, the last phase draws with the token's seed pair: set_seeds
+        with fresh pairs -- seed_pairs(rng, n) -- in front of every call)."""
         _check(capi().mc_decoder_set_sampler(self._h, kind, top_k, temperature, top_p))
         self._top_k = min(top_k, self.cfg["vocab"])
 
@@ -992,8 +1002,9 @@ class Batch:
     # ---- row samplers (Part 2k): each row slot picks with settings of its own
 
     def set_row_sampler(self, row: int, kind: int, top_k: int = 50, temperature: float = 0.6, top_p: float = 0.9):
-        """kind: SAMPLER_INHERIT (follow the decoder's sampler, the default of every row), SAMPLER_GREEDY or SAMPLER_DEFAULT with
-        the row's own top_k / temperature / top_p.  Belongs to the row slot until set again or reset."""
+        """kind: SAMPLER_INHERIT (follow the decoder's sampler, the default of every row), SAMPLER_GREEDY, or SAMPLER_DEFAULT or
+        SAMPLER_DRAW with the row's own top_k / temperature / top_p.  Belongs to the row slot until set again or reset.  Only a
+        SAMPLER_DRAW row's pick depends on its seed pair: set_seeds(seed_pairs(rng, n * B)) in front of every call."""
         _check(capi().mc_row_sampler_set(self._h, row, kind, top_k, temperature, top_p))
 
     def row_sampler(self, row: int):
