@@ -20,7 +20,7 @@ SO = os.path.join(LIB, "libmetalchat_hip.so")
 
 KERNEL_SOURCES = [os.path.join(CSRC, "kernels", f) for f in (
     "metalchat_kernels.hip", "ref_kernels.hip", "gemv_kernels.hip", "decode_kernels.hip", "attn_block_kernels.hip",
-    "synth_kernels.hip", "sampler_kernels.hip", "prefill_kernels.hip", "batch_kernels.hip", "packed_kernels.hip", "extend_kernels.hip", "verify_kernels.hip", "wide_kernels.hip", "tree_kernels.hip", "logit_kernels.hip", "common.h", "abi.h", "handoff.h", "gemv.h", "gemv_ksplit.h", "synth.h", "pf_gemm8.h")]
+    "synth_kernels.hip", "sampler_kernels.hip", "prefill_kernels.hip", "batch_kernels.hip", "packed_kernels.hip", "extend_kernels.hip", "verify_kernels.hip", "wide_kernels.hip", "tree_kernels.hip", "logit_kernels.hip", "common.h", "abi.h", "handoff.h", "gemv.h", "gemv_norm.h", "gemv_ksplit.h", "synth.h", "pf_gemm8.h")]
 # the host library: every unit goes into the one hipcc command, units and headers together are what makes it stale
 HOST_UNITS = [os.path.join(CSRC, f) for f in ("backend.cc", "decoder.cc", "weights.cc", "prefill.cc", "prefill_blaslt.cc", "pipeline.cc", "batch.cc",
                                                "batch_rows.cc", "batch_cache.cc", "batch_settings.cc", "model_io.cc", "text.cc")]

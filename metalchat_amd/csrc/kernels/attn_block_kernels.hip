@@ -221,23 +221,13 @@ struct qkv_in_launch {
         const uint32_t tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
         // ---- rmsnorm on the way into LDS (kernel/rmsnorm.metal:52-95; the additions in the stand-alone kernel's order)
         {
-            // (gemv.h, the build-time prologue: a sum per packet, the packets' sums added in order)
+            // (gemv_norm.h: a sum per packet, the packets' sums added in order)
             float ss = 0.0f;
 #pragma unroll
-            for (int i = 0; i < NXP; i++) {
-                const uint32_t vv[4] = {xr[i].x, xr[i].y, xr[i].z, xr[i].w};
-                float s1 = 0.0f;
-#pragma unroll
-                for (int e = 0; e < 4; e++) {
-                    const float a = asf(vv[e] << 16), b = asf(vv[e] & 0xFFFF0000u);
-                    s1 += a * a;
-                    s1 += b * b;
-                }
-                ss += s1;
-            }
+            for (int i = 0; i < NXP; i++) ss += packet_sumsq<BF>(xr[i]);
             const float wsum_ = wave_sum_dpp(WB == 1 && tid >= NPK ? 0.0f : ss);
 #if MC_ABL_NORM_NOXWAVE
-            float tot = wsum_ * 8.0f; // (ablation build, gemv.h: timing only)
+            float tot = wsum_ * 8.0f; // (ablation build, MC_ABL_NORM_NOXWAVE: gemv_norm.h, the int4 linear-order prologue of gemv.h; timing only)
 #else
             if (lane == 0) red[wave] = wsum_;
             asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); // (LDS only: the first pairs stay in flight)
@@ -248,17 +238,10 @@ struct qkv_in_launch {
             const float inv = 1.0f / sqrtf(tot / (float)KQ + eps);
 #pragma unroll
             for (int i = 0; i < NXP; i++) {
-                const uint32_t vv[4] = {xr[i].x, xr[i].y, xr[i].z, xr[i].w}, wv[4] = {nr[i].x, nr[i].y, nr[i].z, nr[i].w};
-                uint32_t o[4];
-#pragma unroll
-                for (int e = 0; e < 4; e++) {
-                    const float a = (mu + asf(wv[e] << 16)) * asf(vv[e] << 16) * inv;
-                    const float b = (mu + asf(wv[e] & 0xFFFF0000u)) * asf(vv[e] & 0xFFFF0000u) * inv;
-                    o[e] = pack_bf16x2(a, b);
-                }
+                const rowv4 row = packet_normalise<BF>(xr[i], nr[i], mu, inv);
                 const uint32_t p = tid + 512u * i;
-                if constexpr (WB == 0) reinterpret_cast<rowv4*>(xs)[p + (p >> 4)] = rowv4{o[0], o[1], o[2], o[3]}; // (packet p sits in slot p + p / 16)
-                else if (tid < NPK) reinterpret_cast<rowv4*>(xs)[tid] = rowv4{o[0], o[1], o[2], o[3]};              // (natural order)
+                if constexpr (WB == 0) reinterpret_cast<rowv4*>(xs)[p + (p >> 4)] = row; // (packet p sits in slot p + p / 16)
+                else if (tid < NPK) reinterpret_cast<rowv4*>(xs)[tid] = row;              // (natural order)
             }
         }
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
@@ -571,27 +554,10 @@ struct qkv_qkn_in_launch {
         const bool live = tid < NPK;
         // ---- the prologue of mc_gemv_i4_bfloat_lin3s_p{1,2}_* (gemv.h, the build-time prologue): the same sums in the same order
         auto sumsq = [&](const rowv4& v) {
-            const uint32_t vv[4] = {v.x, v.y, v.z, v.w};
-            float s1 = 0.0f;
-#pragma unroll
-            for (int e = 0; e < 4; e++) {
-                const float a = asf(vv[e] << 16), b = asf(vv[e] & 0xFFFF0000u);
-                s1 += a * a;
-                s1 += b * b;
-            }
+            const float s1 = packet_sumsq<BF>(v);
             return live ? s1 : 0.0f;
         };
-        auto normalise = [&](const rowv4& v, const rowv4& w, float inv) {
-            const uint32_t vv[4] = {v.x, v.y, v.z, v.w}, wv[4] = {w.x, w.y, w.z, w.w};
-            uint32_t o[4];
-#pragma unroll
-            for (int e = 0; e < 4; e++) {
-                const float a = (mu + asf(wv[e] << 16)) * asf(vv[e] << 16) * inv;
-                const float b = (mu + asf(wv[e] & 0xFFFF0000u)) * asf(vv[e] & 0xFFFF0000u) * inv;
-                o[e] = pack_bf16x2(a, b);
-            }
-            return rowv4{o[0], o[1], o[2], o[3]};
-        };
+        auto normalise = [&](const rowv4& v, const rowv4& w, float inv) { return packet_normalise<BF>(v, w, mu, inv); };
         rowv4 row;
         {
             const float w1 = wave_sum_dpp(sumsq(xr));
@@ -603,12 +569,8 @@ struct qkv_qkn_in_launch {
             const float inv1 = 1.0f / sqrtf(tot / (float)KQ + eps);
             if constexpr (P2 != 0) {
                 const rowv4 y = normalise(xr, pwr, inv1);
-                const uint32_t aa[4] = {rrr.x, rrr.y, rrr.z, rrr.w}, bb[4] = {y.x, y.y, y.z, y.w};
-                uint32_t o[4];
-#pragma unroll
-                for (int e = 0; e < 4; e++)
-                    o[e] = pack_bf16x2(asf(aa[e] << 16) + asf(bb[e] << 16), asf(aa[e] & 0xFFFF0000u) + asf(bb[e] & 0xFFFF0000u));
-                const rowv4 h = live ? rowv4{o[0], o[1], o[2], o[3]} : rowv4{0, 0, 0, 0};
+                const rowv4 hv = packet_add_T<BF>(rrr, y);
+                const rowv4 h = live ? hv : rowv4{0, 0, 0, 0};
                 if (blockIdx.x == 0 && live) ((__attribute__((address_space(1))) rowv4*)h_out)[tid] = h;
                 const float w2 = wave_sum_dpp(sumsq(h));
                 if (lane == 0) red[16 + wave] = w2;
@@ -1301,14 +1263,7 @@ attn_qkv_wo_w13_w_body(const bf16_t* kc, const bf16_t* vt, bf16_t* attn_out, uns
     constexpr int NW = PM * 2 * PK; // weight loads, the youngest
     // ---- ffn_norm on the way into LDS (kernel/rmsnorm.metal:52-95; gemv.h LGEN, the build-time prologue: the same additions in the same order)
     {
-        const uint32_t vv[4] = {xr.x, xr.y, xr.z, xr.w};
-        float s1 = 0.0f;
-#pragma unroll
-        for (int e = 0; e < 4; e++) {
-            const float a = asf(vv[e] << 16), b = asf(vv[e] & 0xFFFF0000u);
-            s1 += a * a;
-            s1 += b * b;
-        }
+        const float s1 = packet_sumsq<BF>(xr);
         float ss = 0.0f;
         ss += poller ? s1 : 0.0f; // (the stand-alone kernel's threads 256 .. 511 add nothing)
         const float wsum_ = wave_sum_dpp(ss);
@@ -1319,15 +1274,7 @@ attn_qkv_wo_w13_w_body(const bf16_t* kc, const bf16_t* vt, bf16_t* attn_out, uns
         for (uint32_t i = 0; i < 8u; i++) tot += red13[i];
         const float inv = 1.0f / sqrtf(tot / (float)KF + eps);
         if (poller) {
-            const uint32_t wv[4] = {nr.x, nr.y, nr.z, nr.w};
-            uint32_t o[4];
-#pragma unroll
-            for (int e = 0; e < 4; e++) {
-                const float a = (mu + asf(wv[e] << 16)) * asf(vv[e] << 16) * inv;
-                const float b = (mu + asf(wv[e] & 0xFFFF0000u)) * asf(vv[e] & 0xFFFF0000u) * inv;
-                o[e] = pack_bf16x2(a, b);
-            }
-            reinterpret_cast<w13_v4*>(xs13)[tid] = w13_v4{o[0], o[1], o[2], o[3]}; // (natural order)
+            reinterpret_cast<w13_v4*>(xs13)[tid] = packet_normalise<BF>(xr, nr, mu, inv); // (natural order)
         }
     }
     lds_barrier();

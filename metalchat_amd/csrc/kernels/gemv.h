@@ -24,13 +24,30 @@
 // weights go straight from HBM to VGPRs (no LDS round trip), tiles are double-buffered in
 // registers so the next tile's loads are in flight while the current one is dequantised.
 // HBM-bound: algorithmic bytes per output row = in*bits/8 + (in/group)*scale_bytes.
+//
+// THE MAP.  Every per-token GEMV kernel of gemv_kernels.hip is body<...> below, and body<...> holds three main loops behind
+// `if constexpr`; what stands in front of them (load, finish_pair, finish, cursor / advance, stage_x) is shared as noted:
+//   generic linear order  `if constexpr (LGEN > 0)`   mc_gemv_{i8|w}_bfloat_ling{KiB}_*: int8 / plain bfloat weights on bfloat rows.  Own
+//                                                     prologue (build-time geometry), ring, scales, pair_g and the one-row-per-wave path
+//                                                     (which repeats pair_g's multiply ladder).  Uses finish_pair, pick_finish, the eo_* operands.
+//   int4 linear order     `if constexpr (LNCH > 0)`   mc_gemv_i4_bfloat_lin{1,2,4,7,12,14}_* and _lin3s_* (LSPLIT): Q_M4D.  The lean
+//                                                     prologue (stage_x only when LWAVES == 0), ltile, lscales, lscales_quad, do_pair.
+//                                                     Uses finish_pair, pick_finish, the eo_* operands.
+//   classic               the rest of body            mc_gemv_{i4|i8|w}_{bfloat|float}[_fast|_m4|_m4d]_p*_e* and the _dbg* ablations: any
+//                                                     workgroup size.  stage_x, load, a register ring of three tiles, compute, finish,
+//                                                     cursor / advance.  Uses finish_pair without the eo_* operands.
+//   (K cut over four waves  gemv_ksplit.h             mc_gemv_i4_bfloat_lin12k4_*: body_ksplit4, one loop in one function.)
+// In front of body: formats (fmt, xregs), the per-packet dequantise-and-multiply helpers (mac, mac4, mac4b_n, mac8b_n, m4b_*),
+// own_element, wave_sum_dpp, pick_key / pick_finish, tile, lin_deal.  gemv_norm.h: the packet arithmetic of the rmsnorm prologues
+// and the order of additions they all keep.  The attention-block kernels (attn_block_kernels.hip) borrow these helpers.
+// A change here that is meant to leave the device code alone is checked with tools/code_object_diff.py against the parent's build:
+// this compiler's output depends on how a value reaches its use (a lambda's reference capture against a copy in an argument or a
+// member, a helper call against the same expression written out), so "the same arithmetic" is not yet "the same code".
 #pragma once
-#ifndef MC_ABL_NORM_NOXWAVE
-#define MC_ABL_NORM_NOXWAVE 0
-#endif
 
 #include "abi.h"
 #include "common.h"
+#include "gemv_norm.h"
 
 #include <type_traits>
 
@@ -73,6 +90,45 @@ pick_key(float v, uint32_t index)
     if (u == 0x80000000u) u = 0u;
     u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
     return ((unsigned long long)u << 32) | (unsigned long long)(0xFFFFFFFFu - index);
+}
+
+// the tail of EPI_STORE_PICK, run by every wave of the launch exactly once, after its last flush: pick_best = the best key this lane
+// has finished, resp = the launch's pick_epilogue* (the kernel's `res`), red_ = the workgroup's reduction scratch (its floats 24..26 hold the workgroup's
+// key and arrival count, zeroed before the prologue's barrier)
+__device__ __forceinline__ void
+pick_finish(unsigned long long pick_best, uint32_t lane, const void* resp, float* red_, uint32_t nwaves_)
+{
+    unsigned long long k = pick_best;
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const unsigned long long o = __shfl_xor(k, off, 64);
+        k = max(k, o);
+    }
+    if (lane == 0) {
+        unsigned long long* wg_key = reinterpret_cast<unsigned long long*>(red_ + 24);
+        uint32_t* wg_count = reinterpret_cast<uint32_t*>(red_ + 26);
+        (void)__hip_atomic_fetch_max(wg_key, k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        const uint32_t arrived = __hip_atomic_fetch_add(wg_count, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        if (arrived == nwaves_ - 1) { // a wave's LDS operations complete in order: every wave's key is in
+            const pick_epilogue pe_ = *static_cast<const pick_epilogue*>(resp);
+            const unsigned long long wk = __hip_atomic_load(wg_key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            if (pe_.ticket == nullptr) { // no ticket: `key` is an array, one slot per workgroup, folded by mc_argmax_keys behind this launch
+                ((__attribute__((address_space(1))) unsigned long long*)pe_.key)[blockIdx.x] = wk;
+                return;
+            }
+            const unsigned long long before = __hip_atomic_fetch_max(pe_.key, wk, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            asm volatile("" ::"v"(before)); // the ticket is taken only when the maximum has been applied
+            const uint32_t t = __hip_atomic_fetch_add(pe_.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (t == gridDim.x - 1) {
+                const unsigned long long fin = __hip_atomic_fetch_max(pe_.key, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                const int32_t token = (int32_t)(0xFFFFFFFFu - (uint32_t)fin);
+                pe_.state->token = token;
+                if (pe_.tokens_out) pe_.tokens_out[pe_.state->step_index] = token;
+                __hip_atomic_store(pe_.key, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(pe_.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        }
+    }
 }
 
 // EPI_QKV_ROPE: the fused wq|wk|wv GEMV finishes RoPE and the sink-cache write itself
@@ -272,6 +328,16 @@ sbyte(uint32_t v, int i)
 // MI355X_MICROARCH.md), and the work stays on the lane that dequantised it.
 typedef short mf_s4 __attribute__((ext_vector_type(4)));
 typedef float mf_f4 __attribute__((ext_vector_type(4)));
+// ... and that element, where a row's accumulator is read out: element lane % 4 of the lane's four results.
+// (The classic loop and the split rows read it through this helper.  The int4 linear-order loop's plain rows, the int8 linear-order
+//  loop, gemv_ksplit.h and the attention-block kernels still write the select out: with the helper in them -- by reference or by
+//  value -- hipcc emits different code for those kernels.)
+__device__ __forceinline__ float
+own_element(const mf_f4& v, uint32_t lane)
+{
+    const uint32_t e = lane & 3;
+    return e == 0 ? v[0] : (e == 1 ? v[1] : (e == 2 ? v[2] : v[3]));
+}
 __device__ __forceinline__ void
 mac4(mf_f4& acc, const uint4& w, float s, const xregs<BF, 32>& x)
 {
@@ -728,41 +794,7 @@ body(const void* __restrict__ wp, const void* __restrict__ sp, const void* __res
     uint32_t eo_res = 0, eo_slot = 0, eo_rrow = 0;
     float eo_c = 0.0f, eo_s = 0.0f;
     qkv_epilogue eo_q = {};
-    unsigned long long pick_best = 0ull; // EPI_STORE_PICK: the best key this lane has finished
-    // the tail of EPI_STORE_PICK, run by every wave of the launch exactly once, after its last flush
-    auto pick_finish = [&](float* red_, uint32_t nwaves_) {
-        unsigned long long k = pick_best;
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {
-            const unsigned long long o = __shfl_xor(k, off, 64);
-            k = max(k, o);
-        }
-        if (lane == 0) {
-            unsigned long long* wg_key = reinterpret_cast<unsigned long long*>(red_ + 24);
-            uint32_t* wg_count = reinterpret_cast<uint32_t*>(red_ + 26);
-            (void)__hip_atomic_fetch_max(wg_key, k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            const uint32_t arrived = __hip_atomic_fetch_add(wg_count, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            if (arrived == nwaves_ - 1) { // a wave's LDS operations complete in order: every wave's key is in
-                const pick_epilogue pe_ = *static_cast<const pick_epilogue*>(resp);
-                const unsigned long long wk = __hip_atomic_load(wg_key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                if (pe_.ticket == nullptr) { // no ticket: `key` is an array, one slot per workgroup, folded by mc_argmax_keys behind this launch
-                    ((__attribute__((address_space(1))) unsigned long long*)pe_.key)[blockIdx.x] = wk;
-                    return;
-                }
-                const unsigned long long before = __hip_atomic_fetch_max(pe_.key, wk, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                asm volatile("" ::"v"(before)); // the ticket is taken only when the maximum has been applied
-                const uint32_t t = __hip_atomic_fetch_add(pe_.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (t == gridDim.x - 1) {
-                    const unsigned long long fin = __hip_atomic_fetch_max(pe_.key, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    const int32_t token = (int32_t)(0xFFFFFFFFu - (uint32_t)fin);
-                    pe_.state->token = token;
-                    if (pe_.tokens_out) pe_.tokens_out[pe_.state->step_index] = token;
-                    __hip_atomic_store(pe_.key, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    __hip_atomic_store(pe_.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-            }
-        }
-    };
+    unsigned long long pick_best = 0ull; // EPI_STORE_PICK: the best key this lane has finished (pick_finish above ends the launch with it)
     auto finish_pair = [&](uint32_t pair, float a, float b, bool early = false) {
         const uint32_t row = 2 * pair;
         if (row >= out_rows) return;
@@ -903,53 +935,13 @@ body(const void* __restrict__ wp, const void* __restrict__ sp, const void* __res
         // zero padding behind the row
         for (uint32_t p = npk + tid; p < npk_pad; p += bd) xl[xpk(p)] = make_uint4(0, 0, 0, 0);
 
-        auto sumsq = [&](const uint4& v) {
-            const uint32_t vv[4] = {v.x, v.y, v.z, v.w};
-            float ss = 0.0f;
-#pragma unroll
-            for (int i = 0; i < 4; i++) {
-                if (T::bytes == 2) {
-                    const float a = asf(vv[i] << 16), b = asf(vv[i] & 0xFFFF0000u);
-                    ss += a * a;
-                    ss += b * b;
-                } else {
-                    const float a = asf(vv[i]);
-                    ss += a * a;
-                }
-            }
-            return ss;
-        };
-        auto normalise = [&](const uint4& v, const uint4& wv, float inv) {
-            const uint32_t vv[4] = {v.x, v.y, v.z, v.w};
-            const uint32_t ww[4] = {wv.x, wv.y, wv.z, wv.w};
-            uint32_t o[4];
-#pragma unroll
-            for (int i = 0; i < 4; i++) {
-                if (T::bytes == 2) {
-                    const float a = (mu + asf(ww[i] << 16)) * asf(vv[i] << 16) * inv;
-                    const float b = (mu + asf(ww[i] & 0xFFFF0000u)) * asf(vv[i] & 0xFFFF0000u) * inv;
-                    o[i] = pack_bf16x2(a, b);
-                } else {
-                    o[i] = __float_as_uint((mu + asf(ww[i])) * asf(vv[i]) * inv);
-                }
-            }
-            return make_uint4(o[0], o[1], o[2], o[3]);
-        };
+        // (the packet arithmetic and the order of additions: gemv_norm.h)
+        auto sumsq = [&](const uint4& v) { return packet_sumsq<T>(v); };
+        auto normalise = [&](const uint4& v, const uint4& wv, float inv) { return packet_normalise<T>(v, wv, mu, inv); };
 
         if (fits && PRO == PRO_POSTNORM) {
             // elementwise T(a + b) on packets (the residual add of the block, evaluated in T)
-            auto add_T = [&](const uint4& a, const uint4& b) {
-                const uint32_t aa[4] = {a.x, a.y, a.z, a.w}, bb[4] = {b.x, b.y, b.z, b.w};
-                uint32_t o[4];
-#pragma unroll
-                for (int i = 0; i < 4; i++) {
-                    if (T::bytes == 2)
-                        o[i] = pack_bf16x2(asf(aa[i] << 16) + asf(bb[i] << 16), asf(aa[i] & 0xFFFF0000u) + asf(bb[i] & 0xFFFF0000u));
-                    else
-                        o[i] = __float_as_uint(asf(aa[i]) + asf(bb[i]));
-                }
-                return make_uint4(o[0], o[1], o[2], o[3]);
-            };
+            auto add_T = [&](const uint4& a, const uint4& b) { return packet_add_T<T>(a, b); };
             float ss = 0.0f;
 #pragma unroll
             for (int i = 0; i < MAXP; i++) ss += sumsq(xr[i]);
@@ -1186,6 +1178,7 @@ body(const void* __restrict__ wp, const void* __restrict__ sp, const void* __res
                 float ss = 0.0f;
 #pragma unroll
                 for (int i = 0; i < NXP; i++) {
+                    // (gemv_norm.h packet_sumsq, written out: called here, the helper changes the code hipcc emits)
                     const uint32_t vv[4] = {gxr[i].x, gxr[i].y, gxr[i].z, gxr[i].w};
                     float s1 = 0.0f;
 #pragma unroll
@@ -1287,6 +1280,7 @@ body(const void* __restrict__ wp, const void* __restrict__ sp, const void* __res
                 if (c == LGEN - 1) {
                     if constexpr (I8M) {
                         // element lane % 4 of the lane's four results is its own dot product, formed at 2^-M4B_Q
+                        // (own_element() written out, here and in the one-row path below: see there)
                         const uint32_t e = lane & 3;
                         accf = (e == 0 ? acc4[0][0] : (e == 1 ? acc4[0][1] : (e == 2 ? acc4[0][2] : acc4[0][3]))) * 0x1p37f;
                         acc4[0] = mf_f4{0, 0, 0, 0};
@@ -1315,6 +1309,7 @@ body(const void* __restrict__ wp, const void* __restrict__ sp, const void* __res
                     const int slot = c % RS;
                     float sc = 1.0f;
                     if constexpr (SCALED) sc = hrow ? asf(gsa[c] & 0xFFFF0000u) : asf(gsa[c] << 16);
+                    // (the pair loop's ladder a second time: one helper for both changes the code hipcc emits for two of the plain-bfloat kernels)
                     if constexpr (I8M) {
                         if constexpr (XREG) {
                             mac8b_n<1>(acc4, gring[slot], m4b_prepare(__float_as_uint(sc), i8k), gx[c]);
@@ -1350,7 +1345,7 @@ body(const void* __restrict__ wp, const void* __restrict__ sp, const void* __res
         }
         for (uint32_t pr = pb; pr < pe; pr++) pair_g(pr);
         flush();
-        if (EPI == EPI_STORE_PICK) pick_finish(red, nwaves);
+        if (EPI == EPI_STORE_PICK) pick_finish(pick_best, lane, resp, red, nwaves);
         return;
     }
     if constexpr (LNCH > 0) {
@@ -1574,11 +1569,12 @@ body(const void* __restrict__ wp, const void* __restrict__ sp, const void* __res
                     xr[i] = rowv4{pack_bf16x2(a[0], a[1]), pack_bf16x2(a[2], a[3]), pack_bf16x2(a[4], a[5]), pack_bf16x2(a[6], a[7])};
                 }
             }
-            // sum of squares of the thread's packets / the normalised packet: stage_x's arithmetic, addition for addition
+            // sum of squares of the thread's packets / the normalised packet (gemv_norm.h: the arithmetic and the order of additions)
             auto sumsq_l = [&](const rowv4 (&v)[NXP]) {
                 float ss = 0.0f;
 #pragma unroll
                 for (int i = 0; i < NXP; i++) {
+                    // (gemv_norm.h packet_sumsq, written out: called here, the helper changes the code hipcc emits for the ragged rows)
                     const uint32_t vv[4] = {v[i].x, v[i].y, v[i].z, v[i].w};
                     float s1 = 0.0f;
 #pragma unroll
@@ -1591,17 +1587,7 @@ body(const void* __restrict__ wp, const void* __restrict__ sp, const void* __res
                 }
                 return ss;
             };
-            auto normalise_l = [&](const rowv4& v, const rowv4& w, float inv) {
-                const uint32_t vv[4] = {v.x, v.y, v.z, v.w}, ww[4] = {w.x, w.y, w.z, w.w};
-                uint32_t o[4];
-#pragma unroll
-                for (int e = 0; e < 4; e++) {
-                    const float a = (mu + asf(ww[e] << 16)) * asf(vv[e] << 16) * inv;
-                    const float b = (mu + asf(ww[e] & 0xFFFF0000u)) * asf(vv[e] & 0xFFFF0000u) * inv;
-                    o[e] = pack_bf16x2(a, b);
-                }
-                return rowv4{o[0], o[1], o[2], o[3]};
-            };
+            auto normalise_l = [&](const rowv4& v, const rowv4& w, float inv) { return packet_normalise<T>(v, w, mu, inv); };
             // the staged row; split rows keep it twice, [x, x] (LSPLIT above), written here instead of copied behind a barrier
             auto put = [&](int i, const rowv4& v) {
                 if (!live(i)) return;
@@ -1622,6 +1608,7 @@ body(const void* __restrict__ wp, const void* __restrict__ sp, const void* __res
 #pragma unroll
                 for (int i = 0; i < NXP; i++) {
                     const rowv4 y = normalise_l(xr[i], lpw[i], inv1);
+                    // (gemv_norm.h packet_add_T, written out: called here, the helper changes the code hipcc emits)
                     const uint32_t aa[4] = {lrr[i].x, lrr[i].y, lrr[i].z, lrr[i].w}, bb[4] = {y.x, y.y, y.z, y.w};
                     uint32_t o[4];
 #pragma unroll
@@ -1774,9 +1761,7 @@ body(const void* __restrict__ wp, const void* __restrict__ sp, const void* __res
                 if (LSPLIT != 0 && sidx == SUB - 1) {
                     // the super row is complete: packets 0 and 2 are whole rows' worth, the middle one is the first row's in
                     // lanes 0..31 and the second row's in lanes 32..63
-                    const uint32_t e = lane & 3;
-                    auto diag = [&](const mf_f4& v) { return e == 0 ? v[0] : (e == 1 ? v[1] : (e == 2 ? v[2] : v[3])); };
-                    const float m0 = diag(laccs3[0]), m1 = diag(laccs3[1]), m2 = diag(laccs3[2]);
+                    const float m0 = own_element(laccs3[0], lane), m1 = own_element(laccs3[1], lane), m2 = own_element(laccs3[2], lane);
                     const float fa = wave_sum_dpp((m0 + (lane < 32 ? m1 : 0.0f)) * 0x1p37f);
                     const float fb = wave_sum_dpp((m2 + (lane < 32 ? 0.0f : m1)) * 0x1p37f);
                     if (r == 0) { ra = fa; rb = fb; }
@@ -1785,6 +1770,7 @@ body(const void* __restrict__ wp, const void* __restrict__ sp, const void* __res
                     for (int a = 0; a < 3; a++) laccs3[a] = mf_f4{0, 0, 0, 0};
                 } else if (sidx == SUB - 1) {
                     // the row is complete: element lane % 4 of the lane's four results is its own dot product
+                    // (own_element() written out: see there)
                     const uint32_t e = lane & 3;
                     const mf_f4 lacc = laccs[0];
                     const float mine = e == 0 ? lacc[0] : (e == 1 ? lacc[1] : (e == 2 ? lacc[2] : lacc[3]));
@@ -1824,7 +1810,7 @@ body(const void* __restrict__ wp, const void* __restrict__ sp, const void* __res
         }
         if (PRIO_MASK != 0) __builtin_amdgcn_s_setprio(0);
         flush();
-        if (EPI == EPI_STORE_PICK) pick_finish(red, nwaves);
+        if (EPI == EPI_STORE_PICK) pick_finish(pick_best, lane, resp, red, nwaves);
         return;
     }
 
@@ -1889,8 +1875,7 @@ body(const void* __restrict__ wp, const void* __restrict__ sp, const void* __res
             for (int r = 0; r < R; r++) {
                 if constexpr (M4) {
                     // element lane % 4 of the lane's four results is its own dot product
-                    const uint32_t e = lane & 3;
-                    float mine = e == 0 ? accv[r][0] : (e == 1 ? accv[r][1] : (e == 2 ? accv[r][2] : accv[r][3]));
+                    float mine = own_element(accv[r], lane);
                     if (M4D) mine *= 0x1p37f; // the sums were formed at 2^-M4B_Q (mac4b_n)
                     tot[r] = wave_sum_dpp(mine);
                     accv[r] = mf_f4{0, 0, 0, 0};
