@@ -24,7 +24,7 @@ KERNEL_SOURCES = [os.path.join(CSRC, "kernels", f) for f in (
 # the host library: every unit goes into the one hipcc command, units and headers together are what makes it stale
 HOST_UNITS = [os.path.join(CSRC, f) for f in ("backend.cc", "decoder.cc", "weights.cc", "prefill.cc", "prefill_blaslt.cc", "pipeline.cc", "batch.cc",
                                                "batch_rows.cc", "batch_cache.cc", "batch_settings.cc", "model_io.cc", "text.cc")]
-HOST_HEADERS = [os.path.join(CSRC, f) for f in ("json_min.h", "backend_impl.h", "decoder_impl.h", "decoder_batch.h", "decoder_options.h", "gemv_plan.h", "block_plan.h", "prefill_plan.h", "rows_plan.h",
+HOST_HEADERS = [os.path.join(CSRC, f) for f in ("json_min.h", "backend_impl.h", "decoder_impl.h", "decoder_batch.h", "decoder_options.h", "gemv_plan.h", "block_plan.h", "token_plan.h", "prefill_plan.h", "rows_plan.h",
                                                  "batch_plan.h", "batch_impl.h", "bf16_host.h", "sampler_plan.h")] + [
     os.path.join(CSRC, "kernels", "synth.h"), os.path.join(CSRC, "kernels", "abi.h"),
     os.path.join(os.path.dirname(HERE), "include", "metalchat_hip.h")]
@@ -100,7 +100,7 @@ def build_text_test(force: bool = False) -> str:
     return _build_cpp_test("test_text", _ABI_HEADERS, force, True)
 
 
-# The six plan programs are no part of build_all(): nothing of the package needs them, their CPU tests build them (a second or two) when they run.
+# The seven plan programs are no part of build_all(): nothing of the package needs them, their CPU tests build them (a second or two) when they run.
 def build_gemv_plan_test(force: bool = False) -> str:
     """tests/cpp/test_gemv_plan: plan_gemv() (csrc/gemv_plan.h) from the command line -- no HIP and no host library."""
     return _build_cpp_test("test_gemv_plan", _PLAN_HEADERS, force, False)
@@ -109,6 +109,12 @@ def build_gemv_plan_test(force: bool = False) -> str:
 def build_block_plan_test(force: bool = False) -> str:
     """tests/cpp/test_block_plan: plan_block() (csrc/block_plan.h) from the command line -- no HIP and no host library."""
     return _build_cpp_test("test_block_plan", [os.path.join(CSRC, "block_plan.h"), *_PLAN_HEADERS], force, False)
+
+
+def build_token_plan_test(force: bool = False) -> str:
+    """tests/cpp/test_token_plan: plan_token() (csrc/token_plan.h) from the command line -- no HIP and no host library."""
+    headers = [os.path.join(CSRC, f) for f in ("token_plan.h", "block_plan.h", "sampler_plan.h")] + [os.path.join(CSRC, "kernels", "abi.h"), *_PLAN_HEADERS]
+    return _build_cpp_test("test_token_plan", headers, force, False)
 
 
 def build_prefill_plan_test(force: bool = False) -> str:

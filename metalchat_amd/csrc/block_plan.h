@@ -2,7 +2,8 @@
 // form holds it: plan_block().  Nine forms and five attention tails, chosen by integer arithmetic and string building on the layer's three linears, six
 // fields of the model, what a decoder fixes when it is created (block_env: the GEMV environment, the range count, the occupancy answers), and two pieces
 // of run-time state (block_state) -- no HIP, no mc_decoder, so the choice is pinned on the CPU, name, grid and flags included
-// (tests/cpp/test_block_plan.cc against tests/golden/decode_block_plans.json).  mc_decoder::run_layers() launches what the plan says and decides nothing.
+// (tests/cpp/test_block_plan.cc against tests/golden/decode_block_plans.json).  plan_token() (token_plan.h) asks it once per block, with the pending
+// post-norm it carries from block to block; mc_decoder::attn_launch() packs the arguments of the form it names.
 #pragma once
 
 #include <algorithm>

@@ -8,7 +8,7 @@
 //   nn::sink_cache / nn::rope     include/metalchat/nn/cache.h:96-232, nn/embedding.h:107-200
 //   transformer<Layer>::transform include/metalchat/transformer.h:357-364
 // Instead of ~1000 one-op launches and as many allocations per token it issues 4 to 6 launches per
-// layer (llama3: wq|wk|wv, attention + Wo, w1|w3, w2 for the headline shapes -- run_layers) on one in-order stream over a pre-allocated arena, keeps the token / position state in
+// layer (llama3: wq|wk|wv, attention + Wo, w1|w3, w2 for the headline shapes -- token_plan.h plan_token) on one in-order stream over a pre-allocated arena, keeps the token / position state in
 // HBM so successive steps chain without a host round trip, and (optionally) replays one captured
 // hipGraph per token.
 // struct mc_decoder itself, and which unit defines the rest of it (weights, prompt pass, library GEMM): decoder_impl.h.
@@ -131,15 +131,23 @@ mc_decoder::gemv(const linear_w& L, int pro, int epi, const void* x, void* y, co
         mc_status s = gemv(*L.lora_a, pro, 0, x, L.lora_vec, pro == 2 ? res : nullptr, norm_w, mu);
         if (s != MC_OK) return s;
     }
-    if (P.postnorm_by_value) {
+    return gemv_launch(L, P.name, P.wgs, P.block, P.lds, P.postnorm_by_value, x, y, res, norm_w, mu);
+}
+
+// ... the launch itself, as planned: a step of a token's plan comes here directly (its adaptor is a step of its own)
+mc_status
+mc_decoder::gemv_launch(const linear_w& L, const std::string& name, unsigned wgs, unsigned block, unsigned lds, bool pn_by_value, const void* x, void* y,
+                        const void* res, const void* norm_w, float mu)
+{
+    if (pn_by_value) {
         const auto it = pn_host.find(res);
         if (it == pn_host.end()) return fail(MC_ERR_RUNTIME, "gemv: unknown post-norm descriptor");
         const postnorm_args& h = it->second;
-        return launch(P.name, P.wgs, 1, 1, P.block, P.lds,
+        return launch(name, wgs, 1, 1, block, lds,
                       pack(L.w, L.scales, x, y, (const void*)h.res, norm_w, (uint32_t)L.out, (uint32_t)L.in, (uint32_t)L.group,
                            cfg.norm_eps, mu, (const void*)h.post_w, (const void*)h.h_out, (uint32_t)0, 0.0f));
     }
-    return launch(P.name, P.wgs, 1, 1, P.block, P.lds,
+    return launch(name, wgs, 1, 1, block, lds,
                   pack(L.w, L.scales, x, y, res, norm_w, (uint32_t)L.out, (uint32_t)L.in,
                        (uint32_t)L.group, cfg.norm_eps, mu, (const void*)L.lora_vec,
                        (const void*)L.lora_b, (uint32_t)L.lora_cols, L.lora_scale));
@@ -168,243 +176,17 @@ mc_decoder::ensure_rope(int pos, int len)
     return launch("mc_step_rope", 1, 1, 1, 64, 0, pack(state, (int32_t)rope_start));
 }
 
-// gemma3's post-norm of `proj` as a launch of its own: hidden = res + norm(proj) w
-mc_status
-mc_decoder::post_norm_row(const void* norm_w, const void* res)
+// ------------------------------------------------------------------------------------------------
+// One token: plan_token() (token_plan.h) says which launches, in which order, on which symbolic operands; everything from here to run_token() binds
+// device pointers to those symbols and packs each kernel's arguments.
+// ------------------------------------------------------------------------------------------------
+token_fixed
+mc_decoder::token_fixed_now() const
 {
-    const float mu = cfg.family == MC_FAMILY_GEMMA3 ? 1.0f : 0.0f;
-    return launch("mc_rmsnorm_row_" + tname, 1, 1, 1, 1024, 0, pack(proj, norm_w, res, hidden, (uint32_t)cfg.dim, cfg.norm_eps, mu));
-}
-
-mc_status
-mc_decoder::run_layers(const void* x_in)
-{
-    const int dim = cfg.dim, H = cfg.n_heads, KV = cfg.n_kv_heads, hd = cfg.head_dim;
-    const int n_rep = H / KV;
-    const float mu = cfg.family == MC_FAMILY_GEMMA3 ? 1.0f : 0.0f;
-    const bool gemma = cfg.family == MC_FAMILY_GEMMA3;
-    const float scale_T = tb == 2 ? bf2f_host(f2bf_host(cfg.attn_scale)) : cfg.attn_scale;
-    mc_status s;
-    const void* x = x_in; // current hidden row
-    // gemma3: post-norms folded into the prologue of the GEMV that consumes them (gemv.h PRO 2) --
-    // 7 launches per block instead of 9.  Not with parity taps (they want every block output in
-    // HBM) and only while the row fits the prologue's register path.
-    const bool fuse_pn = gemma && !want_taps && opt.gemma_fuse && (size_t)dim * tb / 16 <= (size_t)4 * opt.gemv_block;
-    pending_pn = nullptr;
-    if (fuse_pn && x != hidden && n_own > 0) {
-        // the residual pointers of the fused prologues are fixed at `hidden`: a later pipeline
-        // stage first parks its inbound row there
-        MC_HIP(hipMemcpyAsync(hidden, x, (size_t)dim * tb, hipMemcpyDeviceToDevice, stream));
-        x = hidden;
-    }
-    for (int li = 0; li < n_own; li++) {
-        layer_w& L = layers[li];
-        const block_plan P = plan_block(L);
-        const float* rcos = rope_cos[L.rope_table];
-        const float* rsin = rope_sin[L.rope_table];
-        if (P.qkv_gemv && !gemma) {
-            // attention_norm + wq|wk|wv + rope + cache write in ONE launch
-            // (transformer.h:130, attention.h:170-177)
-            s = gemv(L.qkv, 1, 4, x, qkv, L.qkv_epi, L.attention_norm, mu);
-            if (s != MC_OK) return s;
-        } else if (P.qkv_gemv) {
-            // gemma3: attention_norm + wq|wk|wv; q_norm / k_norm, rope and the cache write follow, in the attention launch or as mc_rope_kv
-            // (fused flow: the previous block's ffn post-norm + residual is applied by this
-            // kernel's prologue, PRO 2, and its workgroup 0 leaves the block input in `hidden`)
-            if (pending_pn) {
-                s = gemv(L.qkv, 2, 0, proj, qkv, pending_pn, L.attention_norm, mu);
-                pending_pn = nullptr;
-                x = hidden;
-            } else {
-                s = gemv(L.qkv, 1, 0, x, qkv, nullptr, L.attention_norm, mu);
-            }
-            if (s != MC_OK) return s;
-            if (P.rope_kv) {
-                s = launch("mc_rope_kv_" + tname, H + 2 * KV, 1, 1, hd / 2, 0,
-                           pack(qkv, q_rot, L.kc, L.vt, rope_cos[L.rope_table], rope_sin[L.rope_table],
-                                L.q_norm, L.k_norm, state, (uint32_t)H, (uint32_t)KV, (uint32_t)hd,
-                                (uint32_t)cfg.max_seq_len, cfg.norm_eps, mu));
-                if (s != MC_OK) return s;
-            }
-        }
-        switch (P.form) {
-        case block_form::qkv_wo_w13_w:
-        case block_form::qkv_wo_w:
-        case block_form::qkv_wo_i8:
-        case block_form::qkv_wo_i4: {
-            // attention_norm, wq|wk|wv, rope, cache write, scores, softmax, P.V, wo + residual (transformer.h:130-133,
-            // attention.h:170-205) in ONE launch: every hand-off but the last stays inside one kv head
-            // (plain weights: fewer than 8 kv heads are launched as 8 virtual ones, kv_virtual_shift; P.ns ranges of 64 P.tiles slots per kv head)
-            arg_pack a = pack((const void*)L.kc, (const void*)L.vt, attn_out, attn_psum_g, attn_slab_g, attn_row_g, attn_qkv_g, state,
-                              (uint32_t)(n_rep >> P.vsh), (uint32_t)(KV << P.vsh), (uint32_t)cfg.max_seq_len, scale_T, (uint32_t)P.ns, (uint32_t)(li + 1),
-                              (const void*)L.wo.w, (const void*)L.wo.scales, x, hidden, (uint32_t)L.wo.out, (uint32_t)L.wo.group,
-                              (const void*)L.attention_norm, (const void*)L.qkv.w, (const void*)L.qkv.scales,
-                              rcos, rsin, cfg.norm_eps, mu,
-                              P.fast, (void*)nullptr, (uint32_t)P.vsh);
-            // ... and ffn_norm, w1|w3, act*mul (transformer.h:135-137, 53-59) too: the block up to the gate row in ONE launch
-            auto more = [&a](const auto&... v) { (a.push(v), ...); };
-            if (P.form == block_form::qkv_wo_w13_w) more(attn_hid_g, (const void*)L.w13.w, (const void*)L.ffn_norm, gate, (uint32_t)L.w13.out, (void*)nullptr);
-            s = launch(P.name, P.grid, 1, 1, 512, 0, std::move(a));
-            break;
-        }
-        case block_form::qkv_only:
-            // attention_norm, wq|wk|wv, rope, cache write, scores, softmax, P.V (transformer.h:130, attention.h:170-203) in ONE launch;
-            // Wo + residual from the finished row below
-            s = launch(P.name, P.grid, 1, 1, 512, 0,
-                       pack((const void*)L.kc, (const void*)L.vt, attn_out, attn_psum_g, attn_slab_g, attn_qkv_g, state, (uint32_t)n_rep,
-                            (uint32_t)KV, (uint32_t)cfg.max_seq_len, scale_T, (uint32_t)P.ns, (uint32_t)(li + 1), x, (uint32_t)L.qkv.group,
-                            (const void*)L.attention_norm, (const void*)L.qkv.w, (const void*)L.qkv.scales,
-                            rcos, rsin, cfg.norm_eps, mu,
-                            P.fast, (void*)nullptr));
-            break;
-        case block_form::qkv_wo_qkn: {
-            // gemma3, ONE launch from the row handed to the block to Wo's output: (the previous block's ffn post-norm + residual,)
-            // attention_norm, wq|wk|wv, q_norm / k_norm, rope, cache write, scores, softmax, P.V, wo (transformer.h:126-133,
-            // attention.h:170-205); the attention post-norm and its residual are the w1|w3 GEMV's prologue (or post_norm_row below)
-            postnorm_args h{};
-            if (pending_pn) {
-                const auto it = pn_host.find(pending_pn);
-                if (it == pn_host.end()) return fail(MC_ERR_RUNTIME, "attention block: unknown post-norm descriptor");
-                h = it->second;
-            }
-            s = launch(P.name, P.grid, 1, 1, 512, 0,
-                       pack((const void*)L.kc, (const void*)L.vt, attn_out, attn_psum_g, attn_slab_g, attn_row_g, attn_qkv_g, state,
-                            (uint32_t)n_rep, (uint32_t)KV, (uint32_t)cfg.max_seq_len, scale_T, (uint32_t)P.ns, (uint32_t)(li + 1),
-                            (const void*)L.wo.w, (const void*)L.wo.scales, pending_pn ? (const void*)proj : x, proj, (uint32_t)L.wo.out,
-                            (uint32_t)L.wo.group, (const void*)L.attention_norm, (const void*)L.qkv.w, (const void*)L.qkv.scales,
-                            rcos, rsin, cfg.norm_eps, mu,
-                            P.fast, (void*)nullptr, (const void*)L.q_norm, (const void*)L.k_norm,
-                            (const void*)h.post_w, (const void*)h.res, (void*)h.h_out));
-            if (pending_pn) {
-                pending_pn = nullptr;
-                x = hidden;
-            }
-            break;
-        }
-        case block_form::wo_qkn:
-            // q_norm / k_norm, rope, cache write, scores, softmax, P.V, wo (attention.h:170-205) in ONE launch; the post-norm and the
-            // residual are the next GEMV's prologue (or post_norm_row below)
-            s = launch(P.name, P.grid, 1, 1, 512, 0,
-                       pack((const void*)qkv, (const void*)L.kc, (const void*)L.vt, attn_out, attn_psum_g, attn_slab_g, attn_row_g, state,
-                            (uint32_t)n_rep, (uint32_t)KV, (uint32_t)cfg.max_seq_len, scale_T, (uint32_t)P.ns, (uint32_t)(li + 1),
-                            (const void*)L.wo.w, (const void*)L.wo.scales, (const void*)nullptr, proj, (uint32_t)L.wo.out, (uint32_t)L.wo.group,
-                            (uint32_t)0, P.fast, (void*)nullptr, (const void*)L.q_norm, (const void*)L.k_norm,
-                            rcos, rsin, cfg.norm_eps, mu));
-            break;
-        case block_form::wo_i4:
-            // scores, softmax, P.V, wo + residual  (attention.h:191-205, transformer.h:132-133) in ONE launch
-            s = launch(P.name, P.grid, 1, 1, 512, 0,
-                       pack(q_rot, L.kc, L.vt, attn_out, attn_psum_g, attn_slab_g, attn_row_g, state, (uint32_t)n_rep, (uint32_t)KV,
-                            (uint32_t)cfg.max_seq_len, scale_T, (uint32_t)P.ns, (uint32_t)(li + 1), (const void*)L.wo.w,
-                            (const void*)L.wo.scales, gemma ? (const void*)nullptr : x, gemma ? proj : hidden, (uint32_t)L.wo.out,
-                            (uint32_t)L.wo.group, (uint32_t)(gemma ? 0 : 1), P.fast, (void*)nullptr));
-            break;
-        case block_form::fused_qkn:
-            // q_norm / k_norm, rope, cache write, scores, softmax, P.V (attention.h:170-203) in ONE launch, then Wo from the finished row
-            s = launch(P.name, P.grid, 1, 1, 256, 0,
-                       pack((const void*)qkv, L.kc, L.vt, attn_out, attn_psum_g, attn_slab_g, state, (uint32_t)n_rep, (uint32_t)KV,
-                            (uint32_t)hd, (uint32_t)cfg.max_seq_len, scale_T, (uint32_t)P.ns, (uint32_t)(li + 1),
-                            P.fast, (const void*)L.q_norm, (const void*)L.k_norm,
-                            rcos, rsin, cfg.norm_eps, mu));
-            break;
-        case block_form::fused:
-        case block_form::fused_t2:
-            // scores, softmax, P.V                 (attention.h:191-203) in ONE launch of 64- or 128-slot ranges, then Wo from the finished row
-            s = launch(P.name, P.grid, 1, 1, 256, 0,
-                       pack(q_rot, L.kc, L.vt, attn_out, attn_psum_g, attn_slab_g, state, (uint32_t)n_rep, (uint32_t)KV, (uint32_t)hd,
-                            (uint32_t)cfg.max_seq_len, scale_T, (uint32_t)P.ns, (uint32_t)(li + 1), (void*)nullptr, P.fast));
-            break;
-        case block_form::scores_pv: {
-            // scores, softmax denominators         (attention.h:195-200)
-            s = launch(P.name, nsplit, KV, 1, 256, 0,
-                       pack(q_rot, L.kc, expv, psum, (void*)nullptr, state, (uint32_t)n_rep,
-                            (uint32_t)hd, (uint32_t)cfg.max_seq_len, scale_T, (uint32_t)nsplit));
-            if (s != MC_OK) return s;
-            // softmax normalisation + P.V          (attention.h:200-203): over P.pv_ranges ranges of cache slots, their sums folded into Wo's prologue
-            // or added by a launch of their own (block_plan.h)
-            s = launch("mc_attn_pv_" + tname, hd / 16, KV, P.pv_ranges, P.pv_block, 0,
-                       pack(expv, psum, L.vt, attn_out, state, (uint32_t)n_rep, (uint32_t)hd,
-                            (uint32_t)cfg.max_seq_len, (uint32_t)nsplit, pv_parts, (uint32_t)H));
-            if (s == MC_OK && P.pv_reduce)
-                s = launch("mc_attn_pv_reduce_" + tname, (H * hd + 255) / 256, 1, 1, 256, 0,
-                           pack((const void*)pv_parts, attn_out, (uint32_t)(H * hd), (uint32_t)P.pv_ranges));
-            break;
-        }
-        }
-        if (s != MC_OK) return s;
-        // wo (+ post norm) + residual          (attention.h:205, transformer.h:132-133), where the launches above stopped at the attention row:
-        // llama with the residual into `hidden`, gemma3 into `proj` like the forms that hold Wo
-        if (P.wo_gemv) {
-            const void* wo_x = P.pv_fold ? (const void*)pv_parts : (const void*)attn_out;
-            const int wo_pro = P.pv_fold ? 3 : 0;
-            s = gemma ? gemv(L.wo, wo_pro, 0, wo_x, proj, nullptr, nullptr, mu) : gemv(L.wo, wo_pro, 1, wo_x, hidden, x, nullptr, mu);
-            if (s != MC_OK) return s;
-        }
-        // gemma3: the attention post-norm + residual, unless it is the w1|w3 GEMV's prologue
-        if (gemma && !fuse_pn) {
-            s = post_norm_row(L.attention_post_norm, x);
-            if (s != MC_OK) return s;
-        }
-        // ffn_norm + w1|w3 + act*mul           (transformer.h:135-137, 53-59)
-        // (qkv_wo_w13_w: a phase of the launch above; gemma3 with folded post-norms: attention post-norm + residual (-> hidden_b) + ffn_norm in the prologue)
-        if (P.form != block_form::qkv_wo_w13_w) {
-            s = gemma && fuse_pn ? gemv(L.w13, 2, 3, proj, gate, L.pn_attn, L.ffn_norm, mu) : gemv(L.w13, 1, gemma ? 3 : 2, hidden, gate, nullptr, L.ffn_norm, mu);
-            if (s != MC_OK) return s;
-        }
-        // w2 (+ post norm) + residual          (transformer.h:59, 138-139)
-        if (!gemma) {
-            s = gemv(L.w2, 0, 1, gate, hidden, hidden, nullptr, mu);
-            if (s != MC_OK) return s;
-        } else {
-            s = gemv(L.w2, 0, 0, gate, proj, nullptr, nullptr, mu);
-            if (s != MC_OK) return s;
-            if (!fuse_pn) {
-                s = post_norm_row(L.ffn_post_norm, hidden);
-                if (s != MC_OK) return s;
-            } else if (li + 1 < n_own || last_stage) {
-                // ffn post-norm + residual (hidden_b) is left to the next pre-norm GEMV: the next
-                // block's wq|wk|wv, or the output head
-                pending_pn = L.pn_ffn;
-            } else {
-                // the row leaves this pipeline stage: materialise it
-                s = post_norm_row(L.ffn_post_norm, hidden_b);
-                if (s != MC_OK) return s;
-            }
-        }
-        x = hidden;
-        if (want_taps)
-            MC_HIP(hipMemcpyAsync((char*)taps + (size_t)(li + 1) * dim * tb, hidden,
-                                  (size_t)dim * tb, hipMemcpyDeviceToDevice, stream));
-    }
-    return MC_OK;
-}
-
-// advance: the embedding launch also advances the step state (chained generation on a first stage)
-mc_status
-mc_decoder::run_embed(bool advance)
-{
-    const int32_t adv_seq = advance ? (int32_t)cfg.max_seq_len : 0;
-    const bool gemma = cfg.family == MC_FAMILY_GEMMA3;
-    float sc = std::sqrt((float)cfg.dim);
-    if (tb == 2) sc = bf2f_host(f2bf_host(sc));
-    const unsigned g = (cfg.dim + 255) / 256;
-    mc_status s;
-    if (emb_fmt == MC_WFMT_T) {
-        // (lazy_pick: the previous token's pick is folded HERE, by every workgroup of this launch, instead of by a
-        //  mc_argmax_keys launch behind its head -- mc_decoder_generate)
-        const bool fold = lazy_pick && advance;
-        s = launch("mc_embed_" + tname, g, 1, 1, 256, 0,
-                   pack(emb_table, hidden, state, (uint32_t)cfg.dim, sc, (int32_t)(gemma ? 1 : 0), adv_seq, (int32_t)pre_len,
-                        fold ? (const void*)pick_keys : (const void*)nullptr, (uint32_t)pick_slots, fold ? tokens_dev : (int32_t*)nullptr));
-    }
-    else
-        s = launch("mc_embed_q8_" + tname, g, 1, 1, 256, 0,
-                   pack(emb_table, emb_scales, hidden, state, (uint32_t)cfg.dim, sc,
-                        (int32_t)(gemma ? 1 : 0), adv_seq, (int32_t)pre_len));
-    if (s != MC_OK) return s;
-    if (want_taps)
-        MC_HIP(hipMemcpyAsync(taps, hidden, (size_t)cfg.dim * tb, hipMemcpyDeviceToDevice, stream));
-    return MC_OK;
+    token_fixed f{model(), &benv, {}, shape_of(output), emb_fmt, cfg.vocab, first_stage, last_stage, top_k, inv_temp_T, top_p_T};
+    f.layers.reserve(layers.size());
+    for (const layer_w& L : layers) f.layers.push_back({{shape_of(L.qkv), shape_of(L.wo), shape_of(L.w13)}, shape_of(L.w2)});
+    return f;
 }
 
 // the one-workgroup fold of the head's per-workgroup keys: the token into the step state and the token list
@@ -414,65 +196,202 @@ mc_decoder::fold_pick()
     return launch("mc_argmax_keys", 1, 1, 1, 256, 0, pack((const void*)pick_keys, (uint32_t)pick_slots, state, tokens_dev));
 }
 
-// does the greedy pick ride in the head's own launch (gemv.h EPI_STORE_PICK)?
-bool
-mc_decoder::head_pick() const
+// The attention launch of a block in the form `P` (block_plan.h): from `x` -- the row handed to the block, the raw wq|wk|wv row or the rotated queries --
+// to `y` -- behind Wo (+ the residual `res` where the form adds it) or the attention row.  pn: the post-norm descriptor the launch's prologue applies.
+mc_status
+mc_decoder::attn_launch(const layer_w& L, const block_plan& P, const void* x, void* y, const void* res, const void* pn)
 {
-    return sampler_kind == MC_SAMPLER_GREEDY && opt.head_pick_on && !pending_pn && opt.lin_waves == 8 && !output.lora_cols &&
-           (lin_ok(output) || ling_kib(output)) && cfg.vocab % 2 == 0;
+    const int H = cfg.n_heads, KV = cfg.n_kv_heads, hd = cfg.head_dim, n_rep = H / KV;
+    const float mu = cfg.family == MC_FAMILY_GEMMA3 ? 1.0f : 0.0f;
+    const float scale_T = tb == 2 ? bf2f_host(f2bf_host(cfg.attn_scale)) : cfg.attn_scale;
+    const uint32_t S = (uint32_t)cfg.max_seq_len, tag = (uint32_t)(&L - layers.data()) + 1, ns = (uint32_t)P.ns;
+    const float* rcos = rope_cos[L.rope_table];
+    const float* rsin = rope_sin[L.rope_table];
+    const void *kc = L.kc, *vt = L.vt, *wo_w = L.wo.w, *wo_s = L.wo.scales, *qkv_w = L.qkv.w, *qkv_s = L.qkv.scales, *an = L.attention_norm;
+    const void *qn = L.q_norm, *kn = L.k_norm;
+    void* const none = nullptr;
+    arg_pack a;
+    switch (P.form) {
+    case block_form::qkv_wo_w13_w:
+    case block_form::qkv_wo_w:
+    case block_form::qkv_wo_i8:
+    case block_form::qkv_wo_i4:
+        // attention_norm, wq|wk|wv, rope, cache write, scores, softmax, P.V, wo + residual (transformer.h:130-133, attention.h:170-205) in ONE launch: every
+        // hand-off but the last stays inside one kv head (plain weights: fewer than 8 kv heads are launched as 8 virtual ones, kv_virtual_shift; P.ns ranges
+        // of 64 P.tiles slots per kv head)
+        a = pack(kc, vt, attn_out, attn_psum_g, attn_slab_g, attn_row_g, attn_qkv_g, state, (uint32_t)(n_rep >> P.vsh), (uint32_t)(KV << P.vsh), S, scale_T, ns, tag,
+                 wo_w, wo_s, x, y, (uint32_t)L.wo.out, (uint32_t)L.wo.group, an, qkv_w, qkv_s, rcos, rsin, cfg.norm_eps, mu, P.fast, none, (uint32_t)P.vsh);
+        // ... and ffn_norm, w1|w3, act*mul (transformer.h:135-137, 53-59) too: the block up to the gate row in ONE launch
+        if (P.form == block_form::qkv_wo_w13_w) push_all(a, attn_hid_g, (const void*)L.w13.w, (const void*)L.ffn_norm, gate, (uint32_t)L.w13.out, none);
+        break;
+    case block_form::qkv_only:
+        // attention_norm, wq|wk|wv, rope, cache write, scores, softmax, P.V (transformer.h:130, attention.h:170-203) in ONE launch; Wo + residual from the finished row
+        a = pack(kc, vt, y, attn_psum_g, attn_slab_g, attn_qkv_g, state, (uint32_t)n_rep, (uint32_t)KV, S, scale_T, ns, tag, x, (uint32_t)L.qkv.group,
+                 an, qkv_w, qkv_s, rcos, rsin, cfg.norm_eps, mu, P.fast, none);
+        break;
+    case block_form::qkv_wo_qkn: {
+        // gemma3, ONE launch from the row handed to the block to Wo's output: (the previous block's ffn post-norm + residual,) attention_norm, wq|wk|wv,
+        // q_norm / k_norm, rope, cache write, scores, softmax, P.V, wo (transformer.h:126-133, attention.h:170-205); the attention post-norm and its
+        // residual are the w1|w3 GEMV's prologue (or a post_norm_attn step)
+        postnorm_args h{};
+        if (pn) {
+            const auto it = pn_host.find(pn);
+            if (it == pn_host.end()) return fail(MC_ERR_RUNTIME, "attention block: unknown post-norm descriptor");
+            h = it->second;
+        }
+        a = pack(kc, vt, attn_out, attn_psum_g, attn_slab_g, attn_row_g, attn_qkv_g, state, (uint32_t)n_rep, (uint32_t)KV, S, scale_T, ns, tag, wo_w, wo_s, x, y,
+                 (uint32_t)L.wo.out, (uint32_t)L.wo.group, an, qkv_w, qkv_s, rcos, rsin, cfg.norm_eps, mu, P.fast, none, qn, kn, (const void*)h.post_w,
+                 (const void*)h.res, (void*)h.h_out);
+        break;
+    }
+    case block_form::wo_qkn:
+        // q_norm / k_norm, rope, cache write, scores, softmax, P.V, wo (attention.h:170-205) in ONE launch; the post-norm and the residual are the next
+        // GEMV's prologue (or a post_norm_attn step)
+        a = pack(x, kc, vt, attn_out, attn_psum_g, attn_slab_g, attn_row_g, state, (uint32_t)n_rep, (uint32_t)KV, S, scale_T, ns, tag, wo_w, wo_s,
+                 (const void*)nullptr, y, (uint32_t)L.wo.out, (uint32_t)L.wo.group, (uint32_t)0, P.fast, none, qn, kn, rcos, rsin, cfg.norm_eps, mu);
+        break;
+    case block_form::wo_i4:
+        // scores, softmax, P.V, wo + residual  (attention.h:191-205, transformer.h:132-133) in ONE launch
+        a = pack(x, kc, vt, attn_out, attn_psum_g, attn_slab_g, attn_row_g, state, (uint32_t)n_rep, (uint32_t)KV, S, scale_T, ns, tag, wo_w, wo_s, res, y,
+                 (uint32_t)L.wo.out, (uint32_t)L.wo.group, (uint32_t)(res ? 1 : 0), P.fast, none);
+        break;
+    case block_form::fused_qkn:
+        // q_norm / k_norm, rope, cache write, scores, softmax, P.V (attention.h:170-203) in ONE launch, then Wo from the finished row
+        a = pack(x, kc, vt, y, attn_psum_g, attn_slab_g, state, (uint32_t)n_rep, (uint32_t)KV, (uint32_t)hd, S, scale_T, ns, tag, P.fast, qn, kn, rcos, rsin,
+                 cfg.norm_eps, mu);
+        break;
+    case block_form::fused:
+    case block_form::fused_t2:
+        // scores, softmax, P.V                 (attention.h:191-203) in ONE launch of 64- or 128-slot ranges, then Wo from the finished row
+        a = pack(x, kc, vt, y, attn_psum_g, attn_slab_g, state, (uint32_t)n_rep, (uint32_t)KV, (uint32_t)hd, S, scale_T, ns, tag, none, P.fast);
+        break;
+    case block_form::scores_pv:
+        // scores, softmax denominators         (attention.h:195-200); P.V follows as the `pv` step
+        return launch(P.name, nsplit, KV, 1, 256, 0, pack(x, kc, expv, psum, none, state, (uint32_t)n_rep, (uint32_t)hd, S, scale_T, (uint32_t)nsplit));
+    }
+    return launch(P.name, P.grid, 1, 1, P.form == block_form::fused_qkn || P.form == block_form::fused || P.form == block_form::fused_t2 ? 256 : 512, 0, std::move(a));
 }
 
 mc_status
-mc_decoder::run_head()
+mc_decoder::run_step(const token_plan& P, const token_step& s, const void* in)
 {
-    const float mu = cfg.family == MC_FAMILY_GEMMA3 ? 1.0f : 0.0f;
-    // final norm + output head (llama.h:128-133) + greedy pick
-    // greedy on a linear-order head kernel: the pick rides in the head's own launch (gemv.h EPI_STORE_PICK; the post-norm
-    // prologue passes its row through `res`, so that variant keeps the argmax launch)
-    const bool pick = head_pick();
-    mc_status s = pending_pn ? gemv(output, 2, 0, proj, logits, pending_pn, final_norm, mu)
-                             : gemv(output, 1, pick ? 5 : 0, hidden, logits,
-                                    pick ? (const void*)(pick_desc + (opt.head_pick_mode == 2 ? offsetof(pick_block, per_wg) : offsetof(pick_block, atomic))) : nullptr, final_norm, mu);
-    pending_pn = nullptr;
-    if (s != MC_OK) return s;
-    if (pick && opt.head_pick_mode == 2)
-        return lazy_pick ? MC_OK : fold_pick();
-    if (pick) return MC_OK;
-    if (sampler_kind == MC_SAMPLER_GREEDY)
-        return launch("mc_argmax_" + tname, 1, 1, 1, 1024, 0,
-                      pack(logits, (uint32_t)cfg.vocab, state, tokens_dev));
-    // make_default_sampler: per-chunk candidates, then one workgroup finishes the chain (MC_SAMPLER_DRAW: the same chain, its last
-    // phase draws -- mc_draw_T)
-    sampler_params p;
-    uint32_t chunk;
-    if (const std::string why = sampler_plan(top_k, cfg.vocab, inv_temp_T, top_p_T, &p, &chunk); !why.empty()) return fail(MC_ERR_RUNTIME, why);
-    s = launch("mc_topk_candidates_" + tname, p.nlists, 1, 1, 64, 0, pack(logits, (uint32_t)cfg.vocab, p.kpad, cand, chunk));
-    if (s != MC_OK) return s;
-    return launch((sampler_kind == MC_SAMPLER_DRAW ? "mc_draw_" : "mc_sample_") + tname, 1, 1, 1, 128, p.cap * 8,
-                  pack(cand, p, seeds, (uint32_t)n_seed_pairs, state, tokens_dev,
-                       want_taps ? sampler_taps : (float*)nullptr));
+    if (!P.error.empty()) return fail(MC_ERR_RUNTIME, P.error);
+    const int dim = cfg.dim, H = cfg.n_heads, KV = cfg.n_kv_heads, hd = cfg.head_dim;
+    const bool gemma = cfg.family == MC_FAMILY_GEMMA3;
+    const float mu = gemma ? 1.0f : 0.0f;
+    const size_t row_bytes = (size_t)dim * tb;
+    auto row = [&](token_row r) -> void* {
+        switch (r) {
+        case token_row::none: return nullptr;
+        case token_row::in: return const_cast<void*>(in);
+        case token_row::hidden: return hidden;
+        case token_row::hidden_b: return hidden_b;
+        case token_row::proj: return proj;
+        case token_row::qkv: return qkv;
+        case token_row::q_rot: return q_rot;
+        case token_row::gate: return gate;
+        case token_row::attn_out: return attn_out;
+        case token_row::pv_parts: return pv_parts;
+        case token_row::logits: return logits;
+        }
+        return nullptr;
+    };
+    layer_w* L = s.layer >= 0 ? &layers[s.layer] : nullptr;
+    const token_launch& K = s.L;
+    const void* res = nullptr;
+    switch (s.res) {
+    case token_res::none: break;
+    case token_res::row: res = row(s.res_row); break;
+    case token_res::qkv_epi: res = L->qkv_epi; break;
+    case token_res::pn_attn: res = layers[s.res_layer].pn_attn; break;
+    case token_res::pn_ffn: res = layers[s.res_layer].pn_ffn; break;
+    case token_res::pick_atomic: res = pick_desc + offsetof(pick_block, atomic); break;
+    case token_res::pick_per_wg: res = pick_desc + offsetof(pick_block, per_wg); break;
+    }
+    mc_status r = MC_OK;
+    switch (s.op) {
+    case token_op::park_row: MC_HIP(hipMemcpyAsync(hidden, row(s.x), row_bytes, hipMemcpyDeviceToDevice, stream)); break;
+    case token_op::tap: MC_HIP(hipMemcpyAsync((char*)taps + (size_t)(s.layer + 1) * row_bytes, hidden, row_bytes, hipMemcpyDeviceToDevice, stream)); break;
+    case token_op::embed: {
+        float sc = std::sqrt((float)dim);
+        if (tb == 2) sc = bf2f_host(f2bf_host(sc));
+        const int32_t adv_seq = s.advance ? (int32_t)cfg.max_seq_len : 0; // (chained generation on a first stage: the embed also advances the step state)
+        r = launch(K.name, K.gx, 1, 1, K.block, 0,
+                   emb_fmt == MC_WFMT_T
+                       ? pack(emb_table, hidden, state, (uint32_t)dim, sc, (int32_t)(gemma ? 1 : 0), adv_seq, (int32_t)pre_len,
+                              s.fold_keys ? (const void*)pick_keys : (const void*)nullptr, (uint32_t)pick_slots, s.fold_keys ? tokens_dev : (int32_t*)nullptr)
+                       : pack(emb_table, emb_scales, hidden, state, (uint32_t)dim, sc, (int32_t)(gemma ? 1 : 0), adv_seq, (int32_t)pre_len));
+        break;
+    }
+    case token_op::qkv_gemv:
+    case token_op::wo_gemv:
+    case token_op::w13_gemv:
+    case token_op::w2_gemv:
+    case token_op::head_gemv: {
+        const linear_w& W = s.op == token_op::head_gemv ? output : s.op == token_op::qkv_gemv ? L->qkv : s.op == token_op::wo_gemv ? L->wo
+                          : s.op == token_op::w13_gemv ? L->w13 : L->w2;
+        const void* norm_w = s.norm == token_norm::attention ? L->attention_norm : s.norm == token_norm::ffn ? L->ffn_norm
+                           : s.norm == token_norm::final ? final_norm : nullptr;
+        r = gemv_launch(s.adaptor ? *W.lora_a : W, K.name, K.gx, K.block, K.lds, s.pn_by_value, row(s.x), s.adaptor ? W.lora_vec : row(s.y), res, norm_w, mu);
+        break;
+    }
+    case token_op::rope_kv:
+        // gemma3: q_norm / k_norm per head, rope and the cache write as a launch of their own
+        r = launch(K.name, K.gx, 1, 1, K.block, 0,
+                   pack(qkv, q_rot, L->kc, L->vt, rope_cos[L->rope_table], rope_sin[L->rope_table], L->q_norm, L->k_norm, state, (uint32_t)H, (uint32_t)KV,
+                        (uint32_t)hd, (uint32_t)cfg.max_seq_len, cfg.norm_eps, mu));
+        break;
+    case token_op::attn:
+    case token_op::scores: r = attn_launch(*L, P.blocks[s.layer], row(s.x), row(s.y), res, s.res == token_res::pn_ffn ? res : nullptr); break;
+    case token_op::pv:
+        // softmax normalisation + P.V          (attention.h:200-203): over gz ranges of cache slots, their sums folded into Wo's prologue or added by pv_reduce
+        r = launch(K.name, K.gx, K.gy, K.gz, K.block, 0,
+                   pack(expv, psum, L->vt, attn_out, state, (uint32_t)(H / KV), (uint32_t)hd, (uint32_t)cfg.max_seq_len, (uint32_t)nsplit, pv_parts, (uint32_t)H));
+        break;
+    case token_op::pv_reduce:
+        r = launch(K.name, K.gx, 1, 1, K.block, 0, pack((const void*)pv_parts, attn_out, (uint32_t)(H * hd), (uint32_t)P.blocks[s.layer].pv_ranges));
+        break;
+    case token_op::post_norm_attn:
+    case token_op::post_norm_ffn: {
+        // gemma3's post-norm of `proj` as a launch of its own: hidden = res + norm(proj) w
+        const void* w = s.op == token_op::post_norm_attn ? L->attention_post_norm : L->ffn_post_norm;
+        r = launch(K.name, 1, 1, 1, K.block, 0, pack(proj, w, (const void*)row(s.x), hidden, (uint32_t)dim, cfg.norm_eps, mu));
+        break;
+    }
+    case token_op::fold_pick: r = fold_pick(); break;
+    case token_op::argmax: r = launch(K.name, 1, 1, 1, K.block, 0, pack(logits, (uint32_t)cfg.vocab, state, tokens_dev)); break;
+    case token_op::candidates: r = launch(K.name, K.gx, 1, 1, K.block, 0, pack(logits, (uint32_t)cfg.vocab, P.sampler.kpad, cand, P.sampler_chunk)); break;
+    case token_op::sample:
+        r = launch(K.name, 1, 1, 1, K.block, K.lds,
+                   pack(cand, P.sampler, seeds, (uint32_t)n_seed_pairs, state, tokens_dev, want_taps ? sampler_taps : (float*)nullptr));
+        break;
+    }
+    return r;
 }
 
-// everything one token needs after the state has been set
+// everything one token needs after the state has been set.  advance: the embedding launch also advances the step state.  Each step is launched as it is
+// planned (the planning of the later blocks runs while the device works); after a step that failed nothing more is launched.
 mc_status
 mc_decoder::run_token(const void* hidden_src, bool advance)
 {
-    mc_status s;
-    const void* x = hidden_src;
-    if (first_stage) {
-        s = run_embed(advance);
-        if (s != MC_OK) return s;
-        x = hidden;
-    }
-    s = run_layers(x);
-    if (s != MC_OK) return s;
-    if (last_stage) {
-        if (n_own == 0 && !first_stage)
-            MC_HIP(hipMemcpyAsync(hidden, x, (size_t)cfg.dim * tb, hipMemcpyDeviceToDevice, stream));
-        s = run_head();
-        if (s != MC_OK) return s;
-    }
-    return MC_OK;
+    token_plan P;
+    mc_status st = MC_OK;
+    plan_token(P, token_fixed_now(), token_now(advance, hidden_src == hidden), [&](const token_step& s) {
+        if (st == MC_OK) st = run_step(P, s, hidden_src);
+    });
+    return st == MC_OK && !P.error.empty() ? fail(MC_ERR_RUNTIME, P.error) : st;
+}
+
+// the head and the pick alone, nothing pending in front: where the prompt pass ends
+mc_status
+mc_decoder::run_head()
+{
+    token_plan P;
+    mc_status st = MC_OK;
+    plan_head(P, token_fixed_now(), token_now(false, true), -1, [&](const token_step& s) {
+        if (st == MC_OK) st = run_step(P, s, nullptr);
+    });
+    return st == MC_OK && !P.error.empty() ? fail(MC_ERR_RUNTIME, P.error) : st; // (a refusal that left no step: the sampler's)
 }
 
 namespace mcimpl {
@@ -814,7 +733,11 @@ mc_decoder_generate(mc_decoder* d, int32_t first_token, int32_t start_pos, int32
         mc_decoder* d;
         ~lazy_scope() { d->lazy_pick = false; }
     } lazy_guard{d};
-    d->lazy_pick = d->lazy_pick_ok();
+    {
+        const token_fixed f = d->token_fixed_now();
+        const token_state now = d->token_now(false, true);
+        d->lazy_pick = lazy_pick_ok(f, now, head_behind_post_norm(f, now)); // (one answer: the head's own plan asks the same question of the same inputs)
+    }
     s = d->run_token(nullptr);
     if (s != MC_OK) return s;
     for (int i = 1; i < n; i++) {
@@ -1030,9 +953,10 @@ mc_decoder_launch_log_read(mc_decoder* d, char* buf, size_t cap)
 }
 
 // The decode GEMVs of one pass of mc_decoder_time_gemv(which), in launch order: "qkv", "wo", "w13", "w2" of every owned block (MC_TIME_GEMV_LAYERS=n: with the
-// weights of block i % n), then "head" on the last stage; "all" = every one.  Each is the variant the token really launches: gemma3's plain stores; Wo with the
-// residual epilogue, and the partial-sum prologue when P.V is folded (its result goes to `proj`, so the hidden row stays what it was); the head with the greedy
-// pick inside (one key per workgroup into pick_keys; the step state is not touched) when run_head() would take it.
+// weights of block i % n), then "head" on the last stage; "all" = every one.  Each is the pair the token's table names (token_plan.h gemv_use_of) BEHIND THE
+// PLAIN NORM: no post-norm in front, the partial-sum prologue when P.V is folded, the head with the greedy pick inside where head_pick_ok() says so.  The
+// buffers are this table's own: Wo and w2 store into `proj`, so the hidden row stays what it was, and the pick leaves one key per workgroup in pick_keys
+// whatever MC_HEAD_PICK says (the step state is not touched).
 struct timed_gemv {
     const char* which;
     const linear_w* L;
@@ -1047,22 +971,27 @@ timed_gemvs(mc_decoder* d, const std::string& w)
 {
     const bool gemma = d->cfg.family == MC_FAMILY_GEMMA3;
     const size_t lim = d->opt.time_gemv_layers ? (size_t)d->opt.time_gemv_layers : d->layers.size(); // (MC_TIME_GEMV_LAYERS)
-    std::vector<timed_gemv> all;
+    std::vector<timed_gemv> out;
+    auto add = [&](const char* which, const linear_w& W, const layer_w* L, const gemv_use& u, const void* x, void* y) {
+        if (w != "all" && w != which) return;
+        const void* res = u.res == token_res::row ? d->hidden : u.res == token_res::qkv_epi ? L->qkv_epi
+                        : u.res == token_res::none ? nullptr : (const void*)(d->pick_desc + offsetof(pick_block, per_wg));
+        const void* norm_w = u.norm == token_norm::attention ? L->attention_norm : u.norm == token_norm::ffn ? L->ffn_norm
+                           : u.norm == token_norm::final ? d->final_norm : nullptr;
+        out.push_back({which, &W, u.pro, u.epi, x, y, res, norm_w});
+    };
     for (size_t li = 0; li < d->layers.size(); li++) {
         const layer_w& L = d->layers[li % lim];
         const bool fold = !d->uses_handoffs() && pv_fold(mc_decoder::shape_of(L.wo), d->model(), d->benv);
-        all.push_back({"qkv", &L.qkv, 1, gemma ? 0 : 4, d->hidden, d->qkv, gemma ? nullptr : L.qkv_epi, L.attention_norm});
-        all.push_back({"wo", &L.wo, fold ? 3 : 0, gemma ? 0 : 1, fold ? (const void*)d->pv_parts : (const void*)d->attn_out, d->proj, gemma ? nullptr : d->hidden, nullptr});
-        all.push_back({"w13", &L.w13, 1, gemma ? 3 : 2, d->hidden, d->gate, nullptr, L.ffn_norm});
-        all.push_back({"w2", &L.w2, 0, gemma ? 0 : 1, d->gate, d->proj, gemma ? nullptr : d->hidden, nullptr});
+        add("qkv", L.qkv, &L, gemv_use_of(gemv_role::qkv, gemma, false), d->hidden, d->qkv);
+        add("wo", L.wo, &L, gemv_use_of(gemv_role::wo, gemma, false, fold), fold ? (const void*)d->pv_parts : (const void*)d->attn_out, d->proj);
+        add("w13", L.w13, &L, gemv_use_of(gemv_role::w13, gemma, false), d->hidden, d->gate);
+        add("w2", L.w2, &L, gemv_use_of(gemv_role::w2, gemma, false), d->gate, d->proj);
     }
     if (d->last_stage) {
-        const bool pick = d->head_pick();
-        all.push_back({"head", &d->output, 1, pick ? 5 : 0, d->hidden, d->logits, pick ? (const void*)(d->pick_desc + offsetof(pick_block, per_wg)) : nullptr, d->final_norm});
+        const bool pick = head_pick_ok(d->token_fixed_now(), d->token_now(false, true), false);
+        add("head", d->output, nullptr, gemv_use_of(gemv_role::head, gemma, false, false, pick ? 2 : 0), d->hidden, d->logits);
     }
-    std::vector<timed_gemv> out;
-    for (const timed_gemv& g : all)
-        if (w == "all" || w == g.which) out.push_back(g);
     return out;
 }
 

@@ -1,14 +1,14 @@
 // The decoder behind Part 2 of include/metalchat_hip.h, as its five translation units see it: the fused weights (linear_w, layer_w), the
 // greedy pick's descriptors (pick_block) and struct mc_decoder -- its state, the small helpers every unit calls inline, and the
 // declarations of everything else.  Which unit defines what:
-//   decoder.cc         the per-token decode -- it launches what block_plan.h plans for the attention block -- the hand-off fall-back, the C ABI of a step
+//   decoder.cc         the per-token decode -- it launches what token_plan.h plans, step by step -- the hand-off fall-back, the C ABI of a step
 //   weights.cc         allocation and upload of the fused matrices, the synthetic model
 //   prefill.cc         the prompt pass (run_prefill): it launches what prefill_plan.h plans -- GEMM family, attention, rope form, folds; no HIP there
 //   prefill_blaslt.cc  the library GEMM of long prompts -- the only unit that sees hipBLASLt's header
 //   pipeline.cc        the layer pipeline (RCCL / local); it holds decoders, it is not part of one
-// The batch's units (batch_impl.h) do not include this header: they read a decoder through decoder_batch.h.  Five headers beside the units need no
+// The batch's units (batch_impl.h) do not include this header: they read a decoder through decoder_batch.h.  Six headers beside the units need no
 // device and are pinned on the CPU by plain g++ programs (tests/cpp): gemv_plan.h (the decode GEMV), block_plan.h (the decode attention block),
-// prefill_plan.h (the prompt pass), rows_plan.h (the admission and the tables of the batch's rows passes) and batch_plan.h (what a batch launches);
+// token_plan.h (the whole decode token), prefill_plan.h (the prompt pass), rows_plan.h (the admission and the tables of the batch's rows passes) and batch_plan.h (what a batch launches);
 // sampler_plan.h plans the default sampler's two launches for the decoder and the batch alike.
 #pragma once
 
@@ -18,6 +18,7 @@
 #include "sampler_plan.h" // the two launches of the default sampler
 #include "gemv_plan.h" // decoder_options / read_options (decoder_options.h) and plan_gemv
 #include "block_plan.h" // plan_block: form, kernel and grid of the decode attention block
+#include "token_plan.h" // plan_token: every launch of one decode token, in order, on symbolic operands
 #include "prefill_plan.h" // plan_gemm, plan_attention, plan_rope and the fold predicates of the prompt pass
 
 #include <algorithm>
@@ -144,7 +145,6 @@ struct mc_decoder {
     void* hidden = nullptr;     // T[dim]   running hidden row (h)
     void* hidden_in = nullptr;  // T[dim]   inbound row for non-first stages
     void* hidden_b = nullptr;   // T[dim]   gemma3: the row between the attention and the ffn half of a block
-    const void* pending_pn = nullptr; // gemma3: postnorm_args the next pre-norm GEMV has to apply to `proj`
     uint64_t weights_gen = 1;  // bumped whenever weight rows change: the derived copies (linear_w::wq2) are rebuilt
     bool pf_plain_on = false;  // ... resolved when the first long prompt arrives (plain_copy_ok)
     bool pf_plain_known = false;
@@ -347,26 +347,22 @@ struct mc_decoder {
     mc_status upload_rows(linear_w& L, int dst_row0, int dst_stride, int rows, const void* weight, const float* scales, int perm_hd = 0);
 
     // ---------------------------------------------------------------- launches
-    // Which kernel a decode GEMV takes is decided in gemv_plan.h (plan_gemv), what the attention block launches in block_plan.h (plan_block): both
-    // over this view of the decoder -- benv.g is the GEMV's part of it -- fixed at create time but for the occupancy answers (query_occupancy).
+    // Which kernel a decode GEMV takes is decided in gemv_plan.h (plan_gemv), what the attention block launches in block_plan.h (plan_block), the
+    // token's whole sequence in token_plan.h (plan_token): all over this view of the decoder -- benv.g is the GEMV's part of it -- fixed at create time but for the occupancy answers (query_occupancy).
     block_env benv{};
     static gemv_shape
     shape_of(const linear_w& L) { return {L.fmt, L.out, L.in, L.group, L.lora_cols}; }
-    // (these gates of plan_gemv are also what the launches around a GEMV ask)
-    bool
-    lin_ok(const linear_w& L) const { return ::lin_ok(shape_of(L), benv.g); }
-    int
-    ling_kib(const linear_w& L) const { return ::ling_kib(shape_of(L), benv.g); }
     block_model
     model() const { return {(int)cfg.family, cfg.n_heads, cfg.n_kv_heads, cfg.head_dim, cfg.dim, cfg.max_seq_len}; }
+    // (in front of a stage's first block no post-norm is pending; a later block's flag is a value of the token's plan -- token_plan.h)
     block_state
-    block_now() const { return {attn_fused_on, pending_pn != nullptr}; }
+    block_now() const { return {attn_fused_on, false}; }
     block_plan
     plan_block(const layer_w& L) const { return ::plan_block({shape_of(L.qkv), shape_of(L.wo), shape_of(L.w13)}, model(), benv, block_now()); }
     // may a hand-off of the next launches give up?  (the step in front of them is then kept for the retry)
     bool
     uses_handoffs() const { return block_uses_handoffs(model(), benv, block_now()); }
-    // (decoder.cc, like every member declared from here to run_head)
+    // (decoder.cc, like every member declared from here to run_token)
     void query_occupancy();
     void handoff_failed();
 
@@ -377,18 +373,16 @@ struct mc_decoder {
     mc_status poll_pending_err();
     void note_err_async();
     mc_status gemv(const linear_w& L, int pro, int epi, const void* x, void* y, const void* res, const void* norm_w, float mu);
+    mc_status gemv_launch(const linear_w& L, const std::string& name, unsigned wgs, unsigned block, unsigned lds, bool pn_by_value, const void* x, void* y,
+                          const void* res, const void* norm_w, float mu);
     mc_status ensure_rope(int pos, int len = 1);
-    mc_status post_norm_row(const void* norm_w, const void* res);
-    mc_status run_layers(const void* x_in);
-    mc_status run_embed(bool advance = false);
+    // what plan_token (token_plan.h) sees of this decoder, and of this moment
+    token_fixed token_fixed_now() const;
+    token_state
+    token_now(bool advance, bool in_hidden) const { return {attn_fused_on, want_taps, sampler_kind, lazy_pick, advance, in_hidden}; }
     mc_status fold_pick();
-    // chained greedy generation on one stage: can the fold wait for the next token's embedding launch?
-    bool
-    lazy_pick_ok() const
-    {
-        return opt.lazy_pick_on && first_stage && last_stage && head_pick() && opt.head_pick_mode == 2 && emb_fmt == MC_WFMT_T && !want_taps;
-    }
-    bool head_pick() const;
+    mc_status attn_launch(const layer_w& L, const block_plan& P, const void* x, void* y, const void* res, const void* pn);
+    mc_status run_step(const token_plan& P, const token_step& s, const void* in);
     mc_status run_head();
     mc_status run_token(const void* hidden_src, bool advance = false);
 

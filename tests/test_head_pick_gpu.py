@@ -48,6 +48,36 @@ def test_pick_in_the_head_launch_equals_the_argmax_launch(quant, wfmt, dim, voca
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("use_graph", [0, 1])
+def test_a_head_behind_a_folded_post_norm_defers_no_pick(use_graph):
+    """gemma3 with the post-norms folded in: the head's prologue is the last block's ffn post-norm, which takes the argument the pick's descriptor
+    would -- so that head makes no pick, and a chained call must not leave one to the next token's embed (csrc/token_plan.h lazy_pick_ok).  The
+    gemma3 decoder of test_gemv_plan_gpu.py, whose head lin_ok() takes, under the default switches: generate equals chained steps."""
+    acc = mc.HardwareAccelerator(ordinal=0)
+    cfg = mg.tiny_cfg(0, family=1, dim=2048, n_heads=8, n_kv_heads=2, head_dim=256, ffn_dim=4096, n_layers=2, vocab=512, max_seq_len=64,
+                      rope_sliding_theta=10000.0, sliding_stride=2)
+    kw = mg.decoder_kwargs(cfg, weight_format=mc.WFMT_I4, group_size=128)
+    a, b = mc.Decoder(acc, use_graph=use_graph, **kw), mc.Decoder(acc, **kw)
+    a.init_synthetic(7)
+    b.init_synthetic(7)
+    a.launch_log(True)
+    got = list(a.generate(3, 0, 8))
+    names = a.launched()
+    a.launch_log(False)
+    want, tok = [], 3
+    for pos in range(8):
+        tok = b.step(tok, pos)
+        want.append(tok)
+    assert got == want
+    assert np.array_equal(a.logits(), b.logits())
+    assert "mc_argmax_keys" not in names and any(n.endswith("_p2_e0") for n in names), names
+    if use_graph:  # (the log dropped the graph: once more, replayed)
+        assert list(a.generate(3, 0, 8)) == want
+    a.release()
+    b.release()
+
+
+@pytest.mark.gpu
 def test_equal_logits_pick_the_first_index():
     acc = mc.HardwareAccelerator(ordinal=0)
     cfg = mg.tiny_cfg(0, dim=2048, n_heads=16, n_kv_heads=4, head_dim=128, ffn_dim=2048, n_layers=1, vocab=8192, max_seq_len=32)

@@ -24,7 +24,7 @@ def symbols():
     return {line.split()[-1] for line in out.splitlines() if " FUNC " in line}
 
 
-# prologue / epilogue pairs run_layers(), run_head() and mc_decoder_time_gemv() launch (gemv_kernels.hip MC_GEMV_SET)
+# prologue / epilogue pairs the table of csrc/token_plan.h (gemv_use_of) names for a token and for mc_decoder_time_gemv() (gemv_kernels.hip MC_GEMV_SET)
 PE = ["p0_e0", "p1_e0", "p0_e1", "p1_e2", "p1_e3", "p1_e4", "p2_e0", "p2_e3"]
 PE_FOLD = ["p3_e0", "p3_e1"]  # P.V range sums added by the Wo prologue: linear-order kernels only
 PE_PICK = ["p1_e5", "p2_e5"]  # the greedy pick inside the output head's launch (gemv.h EPI_STORE_PICK): linear-order kernels only
@@ -100,6 +100,24 @@ def test_every_attention_block_kernel_the_plan_names_exists(symbols):
     names = {a.split()[1] for a in G["answers"]} | {a.split()[1] for a in answers()}
     names |= {launch[0] for c in G["device_cases"].values() for launch in c["attn_launches"]}
     assert len(names) > 12, names   # (at least one per form: test_block_plan_cpu.py holds the recording to every form)
+    missing = sorted(n for n in names if n not in symbols)
+    assert not missing, missing
+
+
+def test_every_kernel_a_token_plan_names_exists(symbols):
+    """plan_token() (csrc/token_plan.h) names every launch of a decode token: the GEMVs and the attention launch through plan_gemv and plan_block, the
+    rest itself from the type name.  Every name it forms over the cases of tests/golden/decode_token_plans.json (tests/cpp/test_token_plan), every
+    name recorded there, and every name it can build for either type is in the code object."""
+    from token_plan_program import G, launches, plans
+
+    names = {n for tokens in plans().values() for t in tokens for n in launches(t.steps)}
+    names |= {n for c in G["cases"].values() for call in ("step0", "step1", "generate") for n in c.get(call, ())}
+    assert {n.rsplit("_", 1)[0] for n in names} >= {"mc_embed", "mc_embed_q8", "mc_rope_kv", "mc_rmsnorm_row", "mc_attn_scores", "mc_attn_pv", "mc_argmax",
+                                                     "mc_topk_candidates", "mc_sample", "mc_draw"}, sorted(names)
+    assert "mc_argmax_keys" in names
+    for t in ("bfloat", "float"):
+        names |= {f"{k}_{t}" for k in ("mc_embed", "mc_embed_q8", "mc_rope_kv", "mc_rmsnorm_row", "mc_attn_scores", "mc_attn_pv", "mc_attn_pv_reduce",
+                                       "mc_argmax", "mc_topk_candidates", "mc_sample", "mc_draw")}
     missing = sorted(n for n in names if n not in symbols)
     assert not missing, missing
 
