@@ -656,7 +656,8 @@ mc_status mc_rolling_fork_row(mc_batch* b, int32_t dst, int32_t src);
  *              decoder.  A row in the call that is not greedy is refused, nothing enqueued:
  *                "mc_verify_rows: row r: the row's sampler is not greedy (accepting sampled drafts needs the draft's probabilities)"
  *              (mc_tree_verify: its own prefix).  With no row sampler set the decoder-wide refusal keeps its text.
- * Not covered: accepting sampled drafts, log-probabilities, samplers other than these three, top_k above 128, seed state kept on the device
+ *              Part 2m lifts this refusal per batch: the pick after every chunk row is then the row's own sampler's.
+ * Not covered: accepting drafts that were themselves sampled (Part 2m verifies sampling rows against drafts proposed without a draw), log-probabilities, samplers other than these three, top_k above 128, seed state kept on the device
  * between calls, the batch-1 decoder.
  * ------------------------------------------------------------------------------------------ */
 enum { MC_SAMPLER_INHERIT = -1 }; /* a row that follows mc_decoder_set_sampler: the default of every row */
@@ -709,7 +710,8 @@ mc_status mc_row_sampler_reset(mc_batch* b);
  *              (mc_tree_verify: its own prefix).  Rows outside the call do not matter.
  * Refusals: all MC_ERR_INVALID_ARGUMENT, prefixed with the call's name; nothing is launched and nothing changes.  A null batch, a row
  * outside [0, B), and what each call names below.  Uploads are synchronous (every batch call drains the stream before it returns).
- * Not covered: the batch-1 decoder, additive logit bias lists, masks per chunk row in verify calls, log-probabilities, samplers other
+ *              Part 2m lifts this refusal per batch: the slot's mask and its counts plus the chunk's tokens then apply to every chunk row.
+ * Not covered: the batch-1 decoder, additive logit bias lists, masks that change per chunk row in verify calls (grammar state), log-probabilities, samplers other
  * than the two the project has.
  * ------------------------------------------------------------------------------------------ */
 /* bit t % 32 of word t / 32 set = token t may be picked; n_words == (vocab + 31) / 32; bits at and above vocab are ignored;
@@ -731,6 +733,47 @@ mc_status mc_row_penalty_counts(mc_batch* b, int32_t row, int32_t* counts);
 mc_status mc_row_penalty_clear(mc_batch* b, int32_t row);
 /* every row: no mask, neutral penalties, zero counts */
 mc_status mc_row_logits_reset(mc_batch* b);
+
+/* ================================================================================================
+ * Part 2m -- verify calls for sampling, masked and penalised rows, opt-in per batch.  Parts 2k and 2l let one batch serve rows
+ * with different settings, and both verify calls (Parts 2f, 2g) refuse every such row.  MC_SAMPLER_DRAW is a pure function of the
+ * logits row, the row's settings and one seed pair, so the pick after any chunk row can be made on the device exactly as a ragged
+ * step makes it.  For a drafter that proposes a token WITHOUT drawing -- prompt lookup, a greedy draft model -- the proposal q is a
+ * point mass on the draft x, and "accept x where it equals the row's own draw" is exact speculative sampling: x is accepted with
+ * P(draw == x) = p(x) = min(1, p / q), and on rejection the row's own draw is emitted, which is p conditioned on != x, i.e.
+ * norm(max(0, p - q)).  The draft's probabilities are not needed, and the output is what lens[r] ragged steps with the same seed
+ * pairs pick from the same logits.  MC_SAMPLER_DEFAULT never draws and verifies the same way.
+ * With the switch off (the default) both verify calls refuse what they refused, with the same texts.  With it on the two refusals
+ * "the row's sampler is not greedy" / "the decoder's sampler is not greedy" and "the row has a token mask or penalties" are not
+ * raised; every other refusal keeps its text (lengths, positions, MC_VERIFY_MAX_ROWS, rolled rows, tree shape).  Then, r a batch
+ * row in the call, j a chunk row of its segment (a tree: node j at depth d):
+ *   processors  a row with a mask or non-neutral penalties has the logits of each of its packed rows rewritten in place before the
+ *               pick, by Part 2l's rule with allowed = the slot's mask and c[t] = the slot's count + the number of chunk tokens equal
+ *               to t among tokens[0 .. j] (a tree: on the path from the root to node j, both included) -- what the ragged steps
+ *               would have counted: a step counts its input, then penalises.  Nothing is written to the counts before the
+ *               acceptance; behind it the counts of a row with penalties gain the accepted[r] + 1 tokens that were fed (chunk rows
+ *               0 .. accepted[r], a tree's accepted path; a token fed twice counts twice).  mc_verify_get_logits and
+ *               mc_batch_get_logits return the processed rows, as after a step.
+ *   picks       picks[m] is what row r's effective sampler (Part 2k) picks from packed row m's processed logits with seed pair
+ *               (j * B + r) % n_pairs, a tree (d * B + r) % n_pairs (siblings share a pair: they are alternatives for one draw) --
+ *               the pair mc_ragged_generate uses for token j of row r.  A caller uploads MC_VERIFY_MAX_LEN * B fresh pairs in front
+ *               of each call.  A greedy row takes the first index of the maximum.
+ *   the rest    acceptance, the tree walk, the K / V compaction and the lengths are Parts 2f / 2g's, run on these picks.
+ *   launches    a call whose rows are all greedy and unprocessed launches exactly what it launches with the switch off.  Otherwise
+ *               mc_v_argmax_bfloat gives way to mc_vs_topk_candidates_mixed_bfloat + mc_vs_pick_mixed_bfloat over the packed rows
+ *               (when a row in the call samples), and at most one launch in front of the pick (mc_vs_logits_process_bfloat) and one
+ *               behind the acceptance (mc_vs_count_accepted) are added.  The per-packed-row table and the candidate keys are
+ *               reserved at the first call that needs them.
+ *   the rows    a row's picks, logits, K / V and counts do not depend on B, on its index, or on the other rows and their settings.
+ * The switch belongs to the batch: mc_batch_fork, imports and the resets of Parts 2k / 2l leave it alone.
+ * Not covered: drafts that were themselves sampled (a real q), masks that change per chunk row (grammar state), the batch-1
+ * decoder, rolled rows in verify calls.  The calls carry a prefix of their own, mc_settings_verify_ (Part 2f's test pins the set
+ * of names that begin with the verify calls' prefix).
+ * ------------------------------------------------------------------------------------------ */
+/* 0 (default): the verify calls refuse sampling, masked and penalised rows.  1: they take them.  A null batch and any other value
+ * are refused with MC_ERR_INVALID_ARGUMENT, texts prefixed "mc_settings_verify_set: "; nothing changes. */
+mc_status mc_settings_verify_set(mc_batch* b, int32_t enable);
+int32_t mc_settings_verify_enabled(const mc_batch* b); /* 0 for a null batch */
 
 /* Host-side helpers shared by tests and the synthetic initialiser. */
 /* value in [-7,7] (bits = 4) or [-127,127] (bits = 8), zero mean, of element (row, col) of matrix `matrix_id` */

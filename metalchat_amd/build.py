@@ -139,6 +139,13 @@ def build_draw_plan_test(force: bool = False) -> str:
     return _build_cpp_test("test_draw_plan", headers, force, False)
 
 
+def build_verify_settings_plan_test(force: bool = False) -> str:
+    """tests/cpp/test_verify_settings_plan: the head of a verify call whose rows carry settings (csrc/batch_plan.h plan_verify_pick /
+    plan_verify_logits) -- no HIP and no host library."""
+    headers = [os.path.join(CSRC, f) for f in ("batch_plan.h", "rows_plan.h", "bf16_host.h", "sampler_plan.h")] + [os.path.join(CSRC, "kernels", "abi.h"), _ABI_HEADERS[1]]
+    return _build_cpp_test("test_verify_settings_plan", headers, force, False)
+
+
 def build_all(force: bool = False):
     r = build_kernels(force), build_host(force)
     build_shim_test(force)

@@ -22,6 +22,8 @@
 // Part 2l (mc_row_mask_*, mc_row_penalty_*, mc_row_logits_reset): a row slot may carry a token mask and repetition / frequency /
 // presence penalties; head() then puts ONE launch (logit_kernels.hip) between the head GEMV and the pick, which rewrites the logits
 // of those rows in place.  A batch on which no row has either launches what it launched before.
+// Part 2m (mc_settings_verify_set): opt-in per batch, the two verify calls take rows that sample or carry a mask or penalties;
+// verify_head() then runs process -> pick -> accept -> count over the packed rows (plan_verify_pick, plan_verify_logits).
 //
 // WHAT is launched -- names, grids, blocks, LDS bytes, the admission and every check of a call that needs no device -- is decided in
 // batch_plan.h, without HIP.  This header is struct mc_batch as its four units see it: the state, the allocator, the launch path and the
@@ -91,6 +93,17 @@ struct mc_batch {
     int v_xn_cap = 0, v_logits_cap = 0, v_out_cap = 0;
     int v_rows = 0;                       // packed rows of the last mc_verify_rows / mc_tree_verify call (0: none yet)
     std::vector<int32_t> v_host;
+    // Part 2m (mc_settings_verify_set): with the switch on the verify calls take sampling, masked and penalised rows.  The plans of the call
+    // in flight (batch_plan.h plan_verify_pick / plan_verify_logits), the per-packed-row table on the device and the candidate keys
+    // [MC_VERIFY_MAX_ROWS][cand_per_row], both reserved at the first call that needs them: a batch that never verifies such a row holds
+    // what it held
+    bool verify_settings_on = false;
+    mcimpl::verify_pick_plan v_pick;
+    mcimpl::verify_logits_plan v_lp;
+    mcimpl::verify_row* v_tab = nullptr;
+    int v_tab_cap = 0;
+    uint64_t* v_cand = nullptr;
+    int v_cand_cap = 0; // (packed rows)
     // Part 2k: the sampler of each row slot as mc_row_sampler_set took it, the table of effective settings the mixed launches read
     // (plan_head resolves it), and what of it the device holds
     std::vector<mcimpl::row_setting> row_samplers; // [B]

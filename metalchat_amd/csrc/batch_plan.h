@@ -1,7 +1,8 @@
 // What a batch (mc_batch_*, mc_ragged_*, the rows passes' heads; batch_impl.h) launches, decided without a device: the admission of a decoder
 // (refusal), the GEMV of every matrix (plan_batch_gemv: family, tiles, grid, the adaptor's launch in front), the launches of a step whose name and
 // grid follow from the config alone (plan_step), the head's pick in its three forms with the rows' effective samplers (plan_head, sampler_plan),
-// the logit processors' table and launch (plan_logits), the head of a verify call (plan_verify_head), and the checks of a call that need no device
+// the logit processors' table and launch (plan_logits), the head of a verify call (plan_verify_head; with row settings: plan_verify_pick,
+// plan_verify_logits), and the checks of a call that need no device
 // (check_ragged, check_tokens, step_bounds / generate_bounds, verify_samplers, verify_logit_rows, check_row).  Plain integer arithmetic over config
 // words, a linear's shape and kernels/abi.h constants -- no HIP, no mc_decoder, no device pointers -- so tests/cpp/test_batch_plan.cc pins names,
 // grids, blocks and LDS bytes on the CPU against a recording of the launches (tests/golden/batch_plans.json).  The batch's units launch what these
@@ -327,6 +328,85 @@ plan_verify_head(const linear_shape& L, const mc_decoder_config& c, int n_layers
     v.accept = {tree ? "mc_tv_accept" : "mc_v_accept", gx, (unsigned)nseg, 1, 256, 0};
     if (tree) v.compact = {"mc_tv_compact_bfloat", ((unsigned)(c.n_kv_heads * c.head_dim) + 255) / 256, (unsigned)nseg, (unsigned)n_layers, 256, 0};
     return v;
+}
+
+// ---------------------------------------------------------------- a verify call whose rows carry settings (Part 2m)
+
+// The per-packed-row table of a verify call (abi.h verify_row) and its pick: chunk row j of batch row r draws with seed pair (j * B + r) %
+// n_pairs -- token j of row r in mc_ragged_generate -- a tree's node at depth d with (d * B + r) % n_pairs (siblings are alternatives for one
+// draw); a chain's anc word is (2 << j) - 1, a tree's the node's (nodes: the call's tv_node table in packed order, null = chains).  greedy: no
+// row IN THE CALL samples -- plan_verify_head's mc_v_argmax_bfloat stays and nothing here is launched.  Otherwise first / second take its place
+// over the M packed rows, with the kpad of the largest top_k among the call's sampling rows (rows outside the call do not count).
+struct verify_pick_plan {
+    std::string refusal; // (MC_ERR_RUNTIME)
+    bool greedy = true;
+    launch_plan first, second;
+    sampler_params sp{};
+    uint32_t chunk = 0;
+    std::vector<verify_row> table; // [M]
+};
+inline verify_pick_plan
+plan_verify_pick(const int32_t* lens, const std::vector<row_setting>& rows, const decoder_sampler& dec, int vocab, int n_pairs, const tv_node* nodes,
+                 size_t cand_per_row)
+{
+    const int B = (int)rows.size();
+    verify_pick_plan v;
+    int top_k_max = 0;
+    decoder_sampler first_sampling;
+    for (int r = 0, off = 0; r < B; off += lens[r], r++) {
+        if (lens[r] <= 0) continue;
+        const decoder_sampler e = sampler_of_row(rows[r], dec);
+        const bool samples = e.kind != MC_SAMPLER_GREEDY;
+        const row_sampler rs = samples ? row_sampler{e.kind == MC_SAMPLER_DRAW ? ROW_SAMPLER_DRAW : ROW_SAMPLER_DEFAULT, (uint32_t)std::min(e.top_k, vocab), e.inv_temp_T, e.top_p_T}
+                                       : row_sampler{ROW_SAMPLER_GREEDY, 0u, 0.0f, 0.0f};
+        if (samples && v.greedy) first_sampling = e;
+        if (samples) v.greedy = false, top_k_max = std::max(top_k_max, e.top_k);
+        for (int32_t j = 0; j < lens[r]; j++) {
+            const int32_t depth = nodes ? nodes[off + j].depth : j;
+            const uint32_t anc = nodes ? nodes[off + j].anc : (2u << j) - 1u;
+            const uint32_t seed = n_pairs > 0 ? (uint32_t)(((int64_t)depth * B + r) % n_pairs) : 0u;
+            v.table.push_back(verify_row{rs, seed, anc, r, off});
+        }
+    }
+    if (v.greedy) return v;
+    v.refusal = sampler_plan(top_k_max, vocab, first_sampling.inv_temp_T, first_sampling.top_p_T, &v.sp, &v.chunk);
+    if (v.refusal.empty() && (size_t)v.sp.nlists * v.sp.kpad > cand_per_row) v.refusal = SAMPLER_ROW_TOO_LONG;
+    if (!v.refusal.empty()) return v;
+    const unsigned M = (unsigned)v.table.size();
+    v.first = {"mc_vs_topk_candidates_mixed_bfloat", v.sp.nlists, M, 1, 64, 0};
+    v.second = {"mc_vs_pick_mixed_bfloat", 1, M, 1, 1024, v.sp.cap * 8};
+    return v;
+}
+
+// ... and its logit processors: the [B] table is the step's (plan_logits), what decides is whether a row IN THE CALL has anything set (any: ONE
+// process launch over the M packed rows between the head and the pick) and whether one has penalties (count: ONE launch behind the acceptance
+// that adds the accepted path to those rows' counts)
+struct verify_logits_plan {
+    bool any = false, count = false;
+    std::vector<row_logits> table; // [B]
+    launch_plan process, counting;
+};
+inline verify_logits_plan
+plan_verify_logits(const int32_t* lens, const std::vector<row_logit_setting>& rows, int vocab, int M, int nseg)
+{
+    verify_logits_plan p;
+    for (size_t r = 0; r < rows.size(); r++) {
+        if (lens[r] <= 0) continue;
+        p.any = p.any || rows[r].masked || rows[r].penalised();
+        p.count = p.count || rows[r].penalised();
+    }
+    if (!p.any) return p;
+    p.table = plan_logits(rows, vocab, true).table;
+    p.process = {"mc_vs_logits_process_bfloat", ((unsigned)vocab + LP_CHUNK - 1) / LP_CHUNK, (unsigned)M, 1, LP_THREADS, 0};
+    if (p.count) p.counting = {"mc_vs_count_accepted", (unsigned)nseg, 1, 1, 64, 0};
+    return p;
+}
+
+// mc_settings_verify_set's value
+inline std::string
+check_verify_switch(int32_t enable)
+{
+    return enable == 0 || enable == 1 ? "" : "mc_settings_verify_set: enable must be 0 or 1";
 }
 
 // ---------------------------------------------------------------- the checks of a call ("" = fine)

@@ -1,6 +1,7 @@
 // The batch's rows passes (Parts 2d to 2g; the map of the whole: batch_impl.h): mc_rows_prefill, mc_extend_rows, mc_verify_rows and
 // mc_tree_verify through one body, rows_pass -- the admission and the tables are rows_plan.h's, the prompt pass the decoder's, the head behind it
-// the batch's own (head(), or verify_head() with what plan_verify_head plans) -- and mc_verify_get_logits.
+// the batch's own (head(), or verify_head() with what plan_verify_head plans) -- and mc_verify_get_logits; Part 2m's switch
+// (mc_settings_verify_set), with which verify_head() also processes, samples and counts per packed row (plan_verify_pick, plan_verify_logits).
 #include "batch_impl.h"
 
 using namespace mcimpl;
@@ -21,14 +22,35 @@ mc_batch::verify_head(const void* xrows, const int32_t* tokens, int M, int nseg,
                             (uint32_t)L.out, (uint32_t)c.vocab));
     if (s != MC_OK) return s;
     int32_t* picks = v_out + 2 * B;
-    if ((s = launch(v.argmax, pack((const void*)v_logits, (uint32_t)c.vocab, picks))) != MC_OK) return s;
+    // Part 2m: the rows' processors rewrite the packed rows' logits in front of the pick; the pick of a call with a sampling row is the two
+    // launches over the per-packed-row table.  A call whose rows are all greedy and unprocessed launches what it launched before
+    if (v_lp.any)
+        if ((s = launch(v_lp.process, pack(v_logits, (uint32_t)c.vocab, (const verify_row*)v_tab, (const row_logits*)logits_tab_dev, (const uint32_t*)masks_dev,
+                                           (const int32_t*)counts_dev, tokens))) != MC_OK)
+            return s;
+    if (v_pick.greedy) {
+        if ((s = launch(v.argmax, pack((const void*)v_logits, (uint32_t)c.vocab, picks))) != MC_OK) return s;
+    } else {
+        const sampler_params& sp = v_pick.sp;
+        if ((s = launch(v_pick.first, pack((const void*)v_logits, (uint32_t)c.vocab, sp.kpad, v_cand, v_pick.chunk, (const verify_row*)v_tab))) != MC_OK) return s;
+        s = launch(v_pick.second, pack((const void*)v_logits, (uint32_t)c.vocab, (const uint64_t*)v_cand, (const verify_row*)v_tab, sp.nlists, sp.kpad, sp.cap,
+                                       (const uint64_t*)seeds, (uint32_t)n_seed_pairs, picks));
+        if (s != MC_OK) return s;
+    }
+    int32_t* paths = v.tree ? picks + M : nullptr;
     if (!v.tree)
-        return launch(v.accept, pack((const pp_seg*)pp_segs(pp_tab), tokens, (const int32_t*)picks, (const void*)v_logits, (uint32_t)c.vocab, v_out,
-                                     v_out + B, logits));
-    int32_t* paths = picks + M;
-    s = launch(v.accept, pack((const pp_seg*)pp_segs(pp_tab), tokens, nodes, (const int32_t*)picks, (const void*)v_logits, (uint32_t)c.vocab, v_out,
-                              v_out + B, paths, logits));
+        s = launch(v.accept, pack((const pp_seg*)pp_segs(pp_tab), tokens, (const int32_t*)picks, (const void*)v_logits, (uint32_t)c.vocab, v_out,
+                                  v_out + B, logits));
+    else
+        s = launch(v.accept, pack((const pp_seg*)pp_segs(pp_tab), tokens, nodes, (const int32_t*)picks, (const void*)v_logits, (uint32_t)c.vocab, v_out,
+                                  v_out + B, paths, logits));
     if (s != MC_OK) return s;
+    // ... and behind the acceptance the penalised rows count what was fed: the accepted path
+    if (v_lp.count)
+        if ((s = launch(v_lp.counting, pack((const pp_seg*)pp_segs(pp_tab), tokens, (const int32_t*)v_out, (const int32_t*)paths, (const row_logits*)logits_tab_dev,
+                                            counts_dev, (uint32_t)c.vocab))) != MC_OK)
+            return s;
+    if (!v.tree) return MC_OK;
     return launch(v.compact, pack((const pp_seg*)pp_segs(pp_tab), (const int32_t*)v_out, (const int32_t*)paths, kc, vt, (uint64_t)cache_elems,
                                   (uint32_t)B, (uint32_t)c.n_kv_heads, (uint32_t)c.head_dim, (uint32_t)c.max_seq_len));
 }
@@ -114,6 +136,24 @@ rows_pass(mc_batch* b, const char* who, bool extend, const int32_t* tokens, cons
         if (tree) MC_HIP(hipMemsetAsync(b->v_out + 2 * B + M, 0xFF, sizeof(int32_t) * MC_VERIFY_MAX_LEN * B, b->p.stream)); // ... its path
         pk.rows_all = &rows_all;
         pk.tokens_dev = &ids;
+        // Part 2m: the pick and the processors of the rows in the call (with the switch off verify_settings has refused every row that would
+        // need them); their tables go up with the call's other tables
+        b->v_pick = verify_pick_plan{};
+        b->v_lp = verify_logits_plan{};
+        if (b->verify_settings_on) {
+            const tv_node* host_nodes = tree ? tv_nodes(b->pp_host.data(), ntiles) : nullptr;
+            b->v_pick = plan_verify_pick(lens, b->row_samplers, decoder_sampler_of(b->d), c.vocab, b->n_seed_pairs, host_nodes, b->cand_per_row);
+            if (!b->v_pick.refusal.empty()) return fail(MC_ERR_RUNTIME, b->v_pick.refusal);
+            b->v_lp = plan_verify_logits(lens, b->row_logit_set, c.vocab, M, nseg);
+            if (!b->v_pick.greedy || b->v_lp.any) {
+                if ((s = b->reserve(b->v_tab, b->v_tab_cap, M, MC_VERIFY_MAX_ROWS)) != MC_OK) return s;
+                MC_HIP(hipMemcpyAsync(b->v_tab, b->v_pick.table.data(), sizeof(verify_row) * M, hipMemcpyHostToDevice, b->p.stream));
+            }
+            if (!b->v_pick.greedy && (s = b->reserve(b->v_cand, b->v_cand_cap, M, MC_VERIFY_MAX_ROWS, sizeof(uint64_t) * b->cand_per_row)) != MC_OK) return s;
+            if (b->v_lp.any && ((s = b->ensure(b->logits_tab_dev, sizeof(row_logits) * B)) != MC_OK ||
+                                (s = b->send_if_changed(b->logits_tab_dev, b->logits_tab_sent, b->v_lp.table)) != MC_OK))
+                return s;
+        }
     }
     if ((s = decoder_prefill_packed(b->d, tokens, M, pk)) != MC_OK) return s;
     if (v) s = b->verify_head(rows_all, ids, M, nseg, pk.nodes);
@@ -139,10 +179,12 @@ rows_pass(mc_batch* b, const char* who, bool extend, const int32_t* tokens, cons
     return MC_OK;
 }
 
-// mc_verify_rows / mc_tree_verify (`who`): every row in the call picks greedily, and none carries a mask or penalties
+// mc_verify_rows / mc_tree_verify (`who`): every row in the call picks greedily, and none carries a mask or penalties -- unless the batch's
+// switch is on (Part 2m), when rows_pass plans the pick and the processors of such rows instead
 mc_status
 verify_settings(const mc_batch* b, const char* who, const int32_t* lens)
 {
+    if (b->verify_settings_on) return MC_OK;
     if (mc_status s = refuse(verify_samplers(who, lens, b->row_samplers, decoder_sampler_of(b->d))); s != MC_OK) return s;
     return refuse(verify_logit_rows(who, lens, b->row_logit_set));
 }
@@ -191,6 +233,23 @@ mc_tree_verify(mc_batch* b, const int32_t* tokens, const int32_t* parents, const
     if (mc_status s = verify_settings(b, "mc_tree_verify", lens); s != MC_OK) return s;
     const verify_out v{accepted, picks, parents, paths};
     return rows_pass(b, "mc_tree_verify", true, tokens, lens, positions, next_tokens, &v);
+}
+
+// ---- Part 2m: verify calls for sampling, masked and penalised rows ----
+
+mc_status
+mc_settings_verify_set(mc_batch* b, int32_t enable)
+{
+    if (!b) return fail(MC_ERR_INVALID_ARGUMENT, "mc_settings_verify_set: null argument");
+    if (mc_status s = refuse(check_verify_switch(enable)); s != MC_OK) return s;
+    b->verify_settings_on = enable == 1;
+    return MC_OK;
+}
+
+int32_t
+mc_settings_verify_enabled(const mc_batch* b)
+{
+    return b && b->verify_settings_on ? 1 : 0;
 }
 
 mc_status

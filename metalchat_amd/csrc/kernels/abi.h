@@ -151,6 +151,18 @@ struct alignas(8) tv_node {
 static_assert(sizeof(tv_node) == 8 && alignof(tv_node) == 8 && offsetof(tv_node, depth) == 0 && offsetof(tv_node, anc) == 4,
               "tv_node: two words, one 8-byte load");
 static_assert(MC_VERIFY_MAX_LEN <= 32, "tv_node::anc holds one bit per node of a chunk");
+// one per packed row of a verify call whose rows carry settings (verify_kernels.hip mc_vs_*, logit_kernels.hip mc_vs_logits_process_bfloat;
+// ABI Part 2m), resolved on the host: chunk row j (tree: node j at depth d) of the segment of batch row `row`
+struct alignas(16) verify_row {
+    row_sampler sampler; // the batch row's EFFECTIVE sampler
+    uint32_t seed;       // its seed pair: (j * B + row) % n_pairs, a tree (d * B + row) % n_pairs -- token j of the row in mc_ragged_generate; 0 without pairs
+    uint32_t anc;        // bit i: chunk token i of the segment was fed up to and including this row -- a chain (2 << j) - 1, a tree tv_node::anc
+    int32_t row;         // the batch row: its processor is table[row], its mask words and counts lie where the step's launch finds them
+    int32_t off;         // the segment's first packed row: chunk token i is tokens[off + i]
+};
+static_assert(sizeof(verify_row) == 32 && alignof(verify_row) == 16 && offsetof(verify_row, sampler) == 0 && offsetof(verify_row, seed) == 16 &&
+                  offsetof(verify_row, anc) == 20 && offsetof(verify_row, row) == 24 && offsetof(verify_row, off) == 28,
+              "verify_row: eight words (read whole with one scalar load)");
 
 } // namespace abi
 } // namespace mc

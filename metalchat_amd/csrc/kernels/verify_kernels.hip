@@ -137,12 +137,11 @@ mc_v_head_w_bfloat(const uint8_t* w, const bf16_t* scales, const bf16_t* x, bf16
     vhead_body<BFMT_W>(w, scales, x, y, K, ngroups, group, M, N, ldy);
 }
 
-// grid (1, M), 1024 threads: picks[row] = the first index of the maximum of logits[row][0, n) (argmax_row_body's keys)
-extern "C" __global__ void __launch_bounds__(1024)
-mc_v_argmax_bfloat(const bf16_t* logits, uint32_t n, int32_t* picks)
+// the first index of the maximum of lr[0, n) into *pick, by the whole workgroup (argmax_row_body's keys and order)
+__device__ __forceinline__ void
+v_argmax_row(const bf16_t* lr, uint32_t n, int32_t* pick)
 {
     __shared__ unsigned long long wk[16];
-    const bf16_t* lr = logits + (size_t)blockIdx.y * n;
     unsigned long long best = 0ull;
     for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) best = max(best, (unsigned long long)make_key(bf2f(lr[i]), i));
     for (int off = 32; off >= 1; off >>= 1) best = max(best, (unsigned long long)__shfl_xor(best, off, 64));
@@ -150,8 +149,15 @@ mc_v_argmax_bfloat(const bf16_t* logits, uint32_t n, int32_t* picks)
     __syncthreads();
     if (threadIdx.x == 0) {
         for (uint32_t w = 1; w < (blockDim.x + 63) / 64; w++) best = max(best, wk[w]);
-        picks[blockIdx.y] = (int32_t)key_index(best);
+        *pick = (int32_t)key_index(best);
     }
+}
+
+// grid (1, M), 1024 threads: picks[row] = the first index of the maximum of logits[row][0, n) (argmax_row_body's keys)
+extern "C" __global__ void __launch_bounds__(1024)
+mc_v_argmax_bfloat(const bf16_t* logits, uint32_t n, int32_t* picks)
+{
+    v_argmax_row(logits + (size_t)blockIdx.y * n, n, picks + blockIdx.y);
 }
 
 // grid (any, nseg): segment g = segs[blockIdx.y] holds the chunk c[0, len) = tokens[off ..] and the picks after each of its rows.
@@ -172,4 +178,71 @@ mc_v_accept(const pp_seg* segs, const int32_t* tokens, const int32_t* picks, con
     const uint4* src = reinterpret_cast<const uint4*>(logits + (size_t)(g.off + a) * vocab);
     uint4* dst = reinterpret_cast<uint4*>(logits_out + (size_t)g.row * vocab);
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < vocab / 8; i += gridDim.x * blockDim.x) dst[i] = src[i];
+}
+
+// ------------------------------------------------------------------------------------------
+// Verify calls for sampling, masked and penalised rows (include/metalchat_hip.h Part 2m).  vrows[m] (abi.h verify_row, resolved on
+// the host) carries packed row m's effective sampler and seed pair.  The two pick launches are the packed-row forms of the mixed
+// launches of the row samplers (batch_kernels.hip): the branch on the row's kind is uniform per workgroup -- the packed row is a
+// grid index -- so a greedy row computes mc_v_argmax_bfloat's pick, a default or drawing row sample_body's from its own logits
+// row with pair vrows[m].seed, and the pick goes to picks[m].  (The names stand outside the mc_v_ prefix, whose symbols
+// tests/test_verify_rows_cpu.py lists.)
+//   mc_vs_topk_candidates_mixed_bfloat  grid (nlists, M), 64 threads: the candidate lists of the sampling packed rows with the
+//                                       CALL's kpad into cand[m][nlists * kpad]; workgroups of greedy rows exit at once
+//   mc_vs_pick_mixed_bfloat             grid (1, M), 1024 threads, dynamic LDS: cap keys
+//   mc_vs_count_accepted                grid (nseg), after the accept launch: the counts of a penalised row gain the tokens fed
+// ------------------------------------------------------------------------------------------
+extern "C" __global__ void __launch_bounds__(64)
+mc_vs_topk_candidates_mixed_bfloat(const bf16_t* logits, uint32_t n, uint32_t kpad, uint64_t* cand, uint32_t chunk, const verify_row* vrows)
+{
+    const uint32_t m = blockIdx.y;
+    if (vrows[m].sampler.kind == ROW_SAMPLER_GREEDY) return; // (uniform)
+    const bf16_t* lr = logits + (size_t)m * n;
+    uint64_t* cr = cand + (size_t)m * gridDim.x * kpad;
+    if (chunk == 512) topk_candidates_body<BF, 8>(lr, n, kpad, cr);
+    else if (chunk == 1024) topk_candidates_body<BF, 16>(lr, n, kpad, cr);
+    else if (chunk == 2048) topk_candidates_body<BF, 32>(lr, n, kpad, cr);
+}
+
+// sample_body finds its seed pair and its slot of tokens_out through a step state: the packed row's lives in LDS, step_index = m,
+// and is handed ONE pair, the row's own -- so pair m % 1 = 0 of seeds + 2 seed is drawn from and the pick lands in picks[m].
+// Nothing of the batch's rows[] is read or written.  n_seed_pairs == 0: no pair is read (sample_body's zero pair)
+extern "C" __global__ void __launch_bounds__(1024)
+mc_vs_pick_mixed_bfloat(const bf16_t* logits, uint32_t n, const uint64_t* cand, const verify_row* vrows, uint32_t nlists, uint32_t kpad,
+                        uint32_t cap, const uint64_t* seeds, uint32_t n_seed_pairs, int32_t* picks)
+{
+    __shared__ step_state st;
+    const uint32_t m = blockIdx.y;
+    const verify_row v = vrows[m];
+    if (v.sampler.kind == ROW_SAMPLER_GREEDY) { // (uniform)
+        v_argmax_row(logits + (size_t)m * n, n, picks + m);
+        return;
+    }
+    if (threadIdx.x == 0) st.step_index = (int32_t)m;
+    __syncthreads();
+    const sampler_params p{v.sampler.k, nlists * kpad, cap, v.sampler.inv_temp, v.sampler.top_p, nlists, kpad};
+    sample_body<BF, SAMPLE_LAST_ROW>(cand + (size_t)m * p.ncand, p, seeds + 2 * (size_t)v.seed, n_seed_pairs ? 1u : 0u, &st, picks, nullptr,
+                                     v.sampler.kind == ROW_SAMPLER_DRAW);
+}
+
+// grid (nseg), 64 threads: segment g = segs[blockIdx.x].  A row with penalties (table[row], the step's table) counts what was
+// fed: chunk rows 0 .. accepted[row], for a tree (paths != null) the nodes paths[row][0 .. accepted[row]].  ONE thread walks them
+// in order with plain loads and stores -- a token that occurs twice on the path is counted twice -- and no other word of counts is
+// written.  Rows without penalties neither read nor write counts.  accepted <= len - 1 and the path's nodes lie below len
+// (mc_v_accept / mc_tv_accept), the tokens inside the vocabulary (rows_check).
+extern "C" __global__ void __launch_bounds__(64)
+mc_vs_count_accepted(const pp_seg* segs, const int32_t* tokens, const int32_t* accepted, const int32_t* paths, const row_logits* table,
+                     int32_t* counts, uint32_t vocab)
+{
+    const pp_seg g = segs[blockIdx.x];
+    if (threadIdx.x != 0 || !(table[g.row].flags & ROW_LOGITS_PENALTY)) return;
+    const int32_t a = min(accepted[g.row], g.len - 1);
+    int32_t* cr = counts + (size_t)g.row * vocab;
+    const int32_t* path = paths ? paths + (size_t)g.row * MC_VERIFY_MAX_LEN : nullptr;
+    for (int32_t d = 0; d <= a; d++) {
+        const int32_t node = path ? path[d] : d;
+        if (node < 0 || node >= g.len) break;
+        const int32_t t = tokens[g.off + node];
+        cr[t] = cr[t] + 1;
+    }
 }

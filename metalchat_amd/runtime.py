@@ -233,6 +233,8 @@ def capi() -> C.CDLL:
         "mc_verify_rows": (i32, [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
         "mc_verify_get_logits": (i32, [vp, vp]),
         "mc_tree_verify": (i32, [vp] + [C.POINTER(i32)] * 8),
+        "mc_settings_verify_set": (i32, [vp, i32]),
+        "mc_settings_verify_enabled": (i32, [vp]),
         "mc_synth_weight": (i32, [u64, u32, u32, u32, i32]),
         "mc_synth_scale": (f32, [u64, u32, u32, u32, i32, i32]),
         "mc_synth_value": (f32, [u64, u32, u32, i32, u32]),
@@ -998,6 +1000,17 @@ class Batch:
         _check(capi().mc_verify_get_logits(self._h, _np_ptr(out)))
         off = np.concatenate([[0], np.cumsum(lens)])
         return [out[off[r]:off[r + 1]] if lens[r] else None for r in range(self.B)]
+
+    # ---- verify calls for sampling, masked and penalised rows (Part 2m), opt-in per batch
+
+    def set_verify_settings(self, enable: bool = True):
+        """on: verify_rows and verify_tree take rows that sample or carry a mask or penalties -- picks[r][j] is then the row's own
+        sampler's pick from chunk row j's processed logits with seed pair (j * B + r) % n_pairs (a tree: the node's depth for j):
+        set_seeds(seed_pairs(rng, 16 * B)) in front of every call.  Default off: such rows are refused."""
+        _check(capi().mc_settings_verify_set(self._h, 1 if enable else 0))
+
+    def verify_settings(self) -> bool:
+        return bool(capi().mc_settings_verify_enabled(self._h))
 
     # ---- row samplers (Part 2k): each row slot picks with settings of its own
 
