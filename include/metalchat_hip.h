@@ -657,7 +657,7 @@ mc_status mc_rolling_fork_row(mc_batch* b, int32_t dst, int32_t src);
  *                "mc_verify_rows: row r: the row's sampler is not greedy (accepting sampled drafts needs the draft's probabilities)"
  *              (mc_tree_verify: its own prefix).  With no row sampler set the decoder-wide refusal keeps its text.
  *              Part 2m lifts this refusal per batch: the pick after every chunk row is then the row's own sampler's.
- * Not covered: accepting drafts that were themselves sampled (Part 2m verifies sampling rows against drafts proposed without a draw), log-probabilities, samplers other than these three, top_k above 128, seed state kept on the device
+ * Not covered: accepting drafts that were themselves sampled (Part 2m verifies sampling rows against drafts proposed without a draw), log-probabilities (Part 2n has them), samplers other than these three, top_k above 128, seed state kept on the device
  * between calls, the batch-1 decoder.
  * ------------------------------------------------------------------------------------------ */
 enum { MC_SAMPLER_INHERIT = -1 }; /* a row that follows mc_decoder_set_sampler: the default of every row */
@@ -774,6 +774,51 @@ mc_status mc_row_logits_reset(mc_batch* b);
  * are refused with MC_ERR_INVALID_ARGUMENT, texts prefixed "mc_settings_verify_set: "; nothing changes. */
 mc_status mc_settings_verify_set(mc_batch* b, int32_t enable);
 int32_t mc_settings_verify_enabled(const mc_batch* b); /* 0 for a null batch */
+
+/* ================================================================================================
+ * Part 2n -- row log-probabilities: the pick's and the top n, opt-in per batch.  Best-of-n over forked rows is ranked by the sum of
+ * each row's token log-probabilities, a choice among N masked answers is scored by the answer's, and serving APIs report `logprobs`
+ * / `top_logprobs` next to the sampler settings of Parts 2k and 2l.  With the switch on, every pick of the batch leaves a record,
+ * made on the device behind the pick, so chained calls keep their chain.  For one row, y[0..V) the bfloat16 logits the pick read
+ * -- what mc_batch_get_logits returns: after the row's mask and penalties, before temperature and truncation:
+ *   M      = max y                                        (a mask that allows no token is refused, so M is finite)
+ *   S      = sum over t of exp(double(y[t]) - double(M))  in float64; exp(-inf) = 0
+ *   lse    = double(M) + log(S)                           float64
+ *   lp[t]  = float(double(y[t]) - lse)                    one rounding; a banned token's lp is -inf
+ *   top n  = the n largest y in the sampler's key order (value descending, -0 == +0, then LOWER index), each with its lp
+ * This is the model's distribution over the processed logits at temperature 1, what OpenAI-style `logprobs` report.  It is not
+ * the sampler's truncated nucleus.  The device evaluates exp, log, the sums and the last subtraction in double; only the order of
+ * its double sum differs from a whole-row evaluation, so a value is never more than 1 float ulp from the rule above and equals it
+ * bit for bit in at least 999 of 1000 cases.
+ *   records   a record is the picked token's lp and, for top_n > 0, top_n ids with their lp.  mc_batch_step / _generate,
+ *             mc_ragged_step / _generate: token i of row r has its record in slot [i][r], where its token is in tokens_out.  A row
+ *             that picks a stop id has that token's record; behind it, and for an idle row, the slots hold the fill: NaN bits
+ *             (0xFFFFFFFF) and id -1.  mc_rows_prefill / mc_extend_rows: n = 1, the one pick of each row in the call.
+ *             mc_verify_rows / mc_tree_verify: one record per packed row, for picks[m] -- every accepted token and the bonus token
+ *             is one of them -- under Part 2m's settings too.
+ *   launches  two per pick launch sequence, directly behind it: mc_logprob_parts_* over (chunks of 2048 logits, rows) and
+ *             mc_logprob_finish_* with one workgroup per row; no atomics and no in-launch hand-offs.  With the switch off (the
+ *             default) a batch launches, uploads and allocates exactly what it did before; the buffers are reserved at the first
+ *             call with the switch on.
+ *   the rows  a row's records do not depend on B, on its index, or on the other rows and their settings.
+ * The switch belongs to the batch: mc_batch_fork, imports and the resets of Parts 2k / 2l leave it alone.
+ * Not covered: the batch-1 decoder, prompt ("echo") log-probabilities of fed tokens, the sampler's truncated distribution, draft
+ * probabilities.  The verify calls' getter is mc_logprobs_get_verify: it carries this part's prefix (Part 2f's test pins the set
+ * of names that begin with the verify calls' prefix).
+ * ------------------------------------------------------------------------------------------ */
+#define MC_LOGPROBS_MAX_TOP 20 /* the largest `top_logprobs` any public API takes */
+/* enable 0 (default) / 1, and the top_n of the records from the next call on; setting it drops the records of earlier calls.
+ * Refused with MC_ERR_INVALID_ARGUMENT, texts prefixed "mc_logprobs_set: ": a null batch, "enable must be 0 or 1", "top_n must lie
+ * in [0, 20]", "top_n (N) is above the vocabulary (V)"; nothing changes then. */
+mc_status mc_logprobs_set(mc_batch* b, int32_t enable, int32_t top_n);
+int32_t mc_logprobs_enabled(const mc_batch* b, int32_t* top_n); /* 0 for a null batch; top_n may be null */
+/* the records of the last step, generate or packed call: token_logprobs [n][B], top_ids and top_logprobs [n][B][top_n].  n must
+ * be that call's n (1 for a step or a packed pass).  The top arrays may be null, and must be null when top_n == 0.  Refused
+ * (MC_ERR_INVALID_ARGUMENT, "mc_logprobs_get: ") while the switch is off, before any such call, and with another n. */
+mc_status mc_logprobs_get(mc_batch* b, int32_t n, float* token_logprobs, int32_t* top_ids, float* top_logprobs);
+/* the records of the last mc_verify_rows / mc_tree_verify call, packed like its tokens (as mc_verify_get_logits packs the logits):
+ * pick_logprobs [M], top_ids and top_logprobs [M][top_n].  The same refusals, prefixed "mc_logprobs_get_verify: ". */
+mc_status mc_logprobs_get_verify(mc_batch* b, float* pick_logprobs, int32_t* top_ids, float* top_logprobs);
 
 /* Host-side helpers shared by tests and the synthetic initialiser. */
 /* value in [-7,7] (bits = 4) or [-127,127] (bits = 8), zero mean, of element (row, col) of matrix `matrix_id` */

@@ -20,7 +20,7 @@ SO = os.path.join(LIB, "libmetalchat_hip.so")
 
 KERNEL_SOURCES = [os.path.join(CSRC, "kernels", f) for f in (
     "metalchat_kernels.hip", "ref_kernels.hip", "gemv_kernels.hip", "decode_kernels.hip", "attn_block_kernels.hip",
-    "synth_kernels.hip", "sampler_kernels.hip", "prefill_kernels.hip", "batch_kernels.hip", "packed_kernels.hip", "extend_kernels.hip", "verify_kernels.hip", "wide_kernels.hip", "tree_kernels.hip", "logit_kernels.hip", "common.h", "abi.h", "handoff.h", "gemv.h", "gemv_norm.h", "gemv_ksplit.h", "synth.h", "pf_gemm8.h")]
+    "synth_kernels.hip", "sampler_kernels.hip", "prefill_kernels.hip", "batch_kernels.hip", "packed_kernels.hip", "extend_kernels.hip", "verify_kernels.hip", "wide_kernels.hip", "tree_kernels.hip", "logit_kernels.hip", "logprob_kernels.hip", "common.h", "abi.h", "handoff.h", "gemv.h", "gemv_norm.h", "gemv_ksplit.h", "synth.h", "pf_gemm8.h")]
 # the host library: every unit goes into the one hipcc command, units and headers together are what makes it stale
 HOST_UNITS = [os.path.join(CSRC, f) for f in ("backend.cc", "decoder.cc", "weights.cc", "prefill.cc", "prefill_blaslt.cc", "pipeline.cc", "batch.cc",
                                                "batch_rows.cc", "batch_cache.cc", "batch_settings.cc", "model_io.cc", "text.cc")]
@@ -100,7 +100,7 @@ def build_text_test(force: bool = False) -> str:
     return _build_cpp_test("test_text", _ABI_HEADERS, force, True)
 
 
-# The seven plan programs are no part of build_all(): nothing of the package needs them, their CPU tests build them (a second or two) when they run.
+# The eight plan programs are no part of build_all(): nothing of the package needs them, their CPU tests build them (a second or two) when they run.
 def build_gemv_plan_test(force: bool = False) -> str:
     """tests/cpp/test_gemv_plan: plan_gemv() (csrc/gemv_plan.h) from the command line -- no HIP and no host library."""
     return _build_cpp_test("test_gemv_plan", _PLAN_HEADERS, force, False)
@@ -144,6 +144,13 @@ def build_verify_settings_plan_test(force: bool = False) -> str:
     plan_verify_logits) -- no HIP and no host library."""
     headers = [os.path.join(CSRC, f) for f in ("batch_plan.h", "rows_plan.h", "bf16_host.h", "sampler_plan.h")] + [os.path.join(CSRC, "kernels", "abi.h"), _ABI_HEADERS[1]]
     return _build_cpp_test("test_verify_settings_plan", headers, force, False)
+
+
+def build_logprob_plan_test(force: bool = False) -> str:
+    """tests/cpp/test_logprob_plan: the two launches behind a pick of a batch with log-probabilities on (csrc/batch_plan.h plan_logprobs) -- no HIP
+    and no host library."""
+    headers = [os.path.join(CSRC, f) for f in ("batch_plan.h", "rows_plan.h", "bf16_host.h", "sampler_plan.h")] + [os.path.join(CSRC, "kernels", "abi.h"), _ABI_HEADERS[1]]
+    return _build_cpp_test("test_logprob_plan", headers, force, False)
 
 
 def build_all(force: bool = False):

@@ -40,6 +40,9 @@ mc_status
 mc_batch::plan_pick(bool ragged)
 {
     mc_status s;
+    lpp = plan_logprobs(logprobs_on, logprobs_top, p.cfg.vocab, B, ragged);
+    if (!lpp.refusal.empty()) return fail(MC_ERR_RUNTIME, lpp.refusal);
+    if (lpp.any && (s = reserve_logprob_scratch(B)) != MC_OK) return s;
     lp = plan_logits(row_logit_set, p.cfg.vocab, ragged);
     if (lp.any && ((s = ensure(logits_tab_dev, sizeof(row_logits) * B)) != MC_OK || (s = send_if_changed(logits_tab_dev, logits_tab_sent, lp.table)) != MC_OK))
         return s;
@@ -104,7 +107,8 @@ mc_batch::enqueue_token(int pos, bool advance)
 // the final norm of x, the head and the pick per row as plan_pick planned them (the three forms: batch_plan.h plan_head), each row with its
 // effective sampler; ragged: rows whose rows[r].pos is -1 get no pick.  Part 2l: with a mask or penalties on any row,
 // mc_b_logits_process_* rewrites those rows' logits between the head and the pick; count: the rows with penalties count their input token
-// first (a step; the packed passes count nothing)
+// first (a step; the packed passes count nothing).  Part 2n: with the batch's switch on, the two log-probability launches run behind the pick
+// in all three forms, and the record lands in the slot the pick's token landed in
 mc_status
 mc_batch::head(bool ragged, bool count)
 {
@@ -115,17 +119,61 @@ mc_batch::head(bool ragged, bool count)
     if ((s = process_logits(ragged, count)) != MC_OK) return s;
     const sampler_params& sp = pick.sp;
     switch (pick.form) {
-    case PICK_GREEDY: return launch(pick.first, pack(logits, vocab, rows, tokens_dev));
+    case PICK_GREEDY: s = launch(pick.first, pack(logits, vocab, rows, tokens_dev)); break;
     case PICK_UNIFORM:
         if ((s = launch(pick.first, pack(logits, vocab, sp.kpad, cand, pick.chunk))) != MC_OK) return s;
-        return launch(pick.second, pack(cand, sp, seeds, (uint32_t)n_seed_pairs, rows, tokens_dev));
+        s = launch(pick.second, pack(cand, sp, seeds, (uint32_t)n_seed_pairs, rows, tokens_dev));
+        break;
     default:
         s = launch(pick.first, pack(logits, vocab, sp.kpad, cand, pick.chunk, (const row_sampler*)samplers_dev, (const step_state*)rows,
                                     (int32_t)(ragged ? 1 : 0)));
         if (s != MC_OK) return s;
-        return launch(pick.second, pack(logits, vocab, (const uint64_t*)cand, (const row_sampler*)samplers_dev, sp.nlists, sp.kpad, sp.cap,
-                                        (const uint64_t*)seeds, (uint32_t)n_seed_pairs, rows, tokens_dev));
+        s = launch(pick.second, pack(logits, vocab, (const uint64_t*)cand, (const row_sampler*)samplers_dev, sp.nlists, sp.kpad, sp.cap,
+                                     (const uint64_t*)seeds, (uint32_t)n_seed_pairs, rows, tokens_dev));
     }
+    if (s != MC_OK || !lpp.any) return s;
+    return enqueue_logprobs(lpp, logits, rows, nullptr, (uint32_t)(lp_n * B), lp_tok, lp_ids, lp_top);
+}
+
+// Part 2n: the records of a call of n tokens beside tokens_dev -- reserved, and every slot filled with 0xFF: a slot no pick reaches (an idle or
+// retired row, a row outside a packed call) reads as NaN bits and id -1
+mc_status
+mc_batch::begin_logprobs(int n)
+{
+    if (!logprobs_on) return MC_OK;
+    const int slots = n * B, top = logprobs_top;
+    mc_status s;
+    if ((s = reserve(lp_tok, lp_tok_cap, slots, slots)) != MC_OK) return s;
+    MC_HIP(hipMemsetAsync(lp_tok, 0xFF, sizeof(float) * (size_t)slots, p.stream));
+    if (top > 0) {
+        if ((s = reserve(lp_ids, lp_ids_cap, slots, slots, sizeof(int32_t) * top)) != MC_OK || (s = reserve(lp_top, lp_top_cap, slots, slots, sizeof(float) * top)) != MC_OK)
+            return s;
+        MC_HIP(hipMemsetAsync(lp_ids, 0xFF, sizeof(int32_t) * (size_t)slots * top, p.stream));
+        MC_HIP(hipMemsetAsync(lp_top, 0xFF, sizeof(float) * (size_t)slots * top, p.stream));
+    }
+    lp_n = n;
+    return MC_OK;
+}
+
+// a part per (row, chunk) and the chunks' keys at the most top_n, for R rows: sized by the bounds, so a change of top_n keeps them
+mc_status
+mc_batch::reserve_logprob_scratch(int R)
+{
+    const size_t nchunk = ((size_t)p.cfg.vocab + LOGPROB_CHUNK - 1) / LOGPROB_CHUNK;
+    mc_status s = reserve(lp_parts, lp_parts_cap, R, R, sizeof(logprob_part) * nchunk);
+    if (s != MC_OK) return s;
+    return reserve(lp_keys, lp_keys_cap, R, R, sizeof(uint64_t) * nchunk * MC_LOGPROBS_MAX_TOP);
+}
+
+mc_status
+mc_batch::enqueue_logprobs(const logprobs_plan& l, const void* rows_logits, const step_state* state, const int32_t* picks, uint32_t nslots, float* out_tok,
+                           int32_t* out_ids, float* out_top)
+{
+    const uint32_t vocab = (uint32_t)p.cfg.vocab, top = (uint32_t)logprobs_top;
+    mc_status s = launch(l.parts, pack(rows_logits, vocab, top, lp_parts, lp_keys, state));
+    if (s != MC_OK) return s;
+    return launch(l.finish, pack(rows_logits, vocab, top, l.nchunk, (const logprob_part*)lp_parts, (const uint64_t*)lp_keys, state, picks, nslots, out_tok,
+                                 out_ids, out_top));
 }
 
 mc_status
@@ -291,7 +339,7 @@ mc_batch_step(mc_batch* b, const int32_t* tokens, int32_t start_pos, int32_t* ne
     mc_status s;
     if ((s = refuse(step_bounds(start_pos, b->p.cfg.max_seq_len))) != MC_OK || (s = refuse(check_tokens(tokens, b->B, b->p.cfg.vocab))) != MC_OK) return s;
     MC_HIP(hipSetDevice(b->p.ordinal));
-    if ((s = b->plan_call(false)) != MC_OK || (s = b->ensure_tokens(1)) != MC_OK || (s = start_rows(b, tokens)) != MC_OK ||
+    if ((s = b->plan_call(false)) != MC_OK || (s = b->ensure_tokens(1)) != MC_OK || (s = b->begin_logprobs(1)) != MC_OK || (s = start_rows(b, tokens)) != MC_OK ||
         (s = b->enqueue_token(start_pos, false)) != MC_OK)
         return s;
     return finish(b, start_pos, nullptr, 1, next_tokens);
@@ -306,7 +354,7 @@ mc_batch_generate(mc_batch* b, const int32_t* first_tokens, int32_t start_pos, i
     if ((s = refuse(generate_bounds(start_pos, n, b->p.cfg.max_seq_len))) != MC_OK || (s = refuse(check_tokens(first_tokens, b->B, b->p.cfg.vocab))) != MC_OK)
         return s;
     MC_HIP(hipSetDevice(b->p.ordinal));
-    if ((s = b->plan_call(false)) != MC_OK || (s = b->ensure_tokens(n)) != MC_OK || (s = start_rows(b, first_tokens)) != MC_OK) return s;
+    if ((s = b->plan_call(false)) != MC_OK || (s = b->ensure_tokens(n)) != MC_OK || (s = b->begin_logprobs(n)) != MC_OK || (s = start_rows(b, first_tokens)) != MC_OK) return s;
     for (int i = 0; i < n; i++)
         if ((s = b->enqueue_token(start_pos + i, i > 0)) != MC_OK) return s;
     return finish(b, start_pos, nullptr, n, tokens_out);
@@ -332,7 +380,8 @@ mc_ragged_step(mc_batch* b, const int32_t* tokens, const int32_t* positions, int
     mc_status s = refuse(check_ragged("mc_ragged_step", tokens, positions, 1, b->lengths.data(), b->B, c.max_seq_len, c.vocab, b->rolling));
     if (s != MC_OK) return s;
     MC_HIP(hipSetDevice(b->p.ordinal));
-    if ((s = b->plan_call(true)) != MC_OK || (s = b->ensure_tokens(1)) != MC_OK || (s = start_ragged(b, tokens, positions, nullptr, 0, 1)) != MC_OK ||
+    if ((s = b->plan_call(true)) != MC_OK || (s = b->ensure_tokens(1)) != MC_OK || (s = b->begin_logprobs(1)) != MC_OK ||
+        (s = start_ragged(b, tokens, positions, nullptr, 0, 1)) != MC_OK ||
         (s = b->enqueue_token(0, false)) != MC_OK)
         return s;
     return finish(b, 0, positions, 1, next_tokens);
@@ -350,7 +399,7 @@ mc_ragged_generate(mc_batch* b, const int32_t* first_tokens, const int32_t* posi
     mc_status s = refuse(check_ragged("mc_ragged_generate", first_tokens, positions, n, b->lengths.data(), b->B, c.max_seq_len, c.vocab, b->rolling));
     if (s != MC_OK) return s;
     MC_HIP(hipSetDevice(b->p.ordinal));
-    if ((s = b->plan_call(true)) != MC_OK || (s = b->ensure_tokens(n)) != MC_OK ||
+    if ((s = b->plan_call(true)) != MC_OK || (s = b->ensure_tokens(n)) != MC_OK || (s = b->begin_logprobs(n)) != MC_OK ||
         (s = start_ragged(b, first_tokens, positions, stop_ids, n_stop, n)) != MC_OK)
         return s;
     for (int i = 0; i < n; i++)

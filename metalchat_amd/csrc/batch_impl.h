@@ -24,6 +24,8 @@
 // of those rows in place.  A batch on which no row has either launches what it launched before.
 // Part 2m (mc_settings_verify_set): opt-in per batch, the two verify calls take rows that sample or carry a mask or penalties;
 // verify_head() then runs process -> pick -> accept -> count over the packed rows (plan_verify_pick, plan_verify_logits).
+// Part 2n (mc_logprobs_set): opt-in per batch, two launches (logprob_kernels.hip) behind every pick -- head()'s three forms and verify_head()'s --
+// record the pick's log-probability and the top_n most likely tokens.  With the switch off a batch launches and holds what it did before.
 //
 // WHAT is launched -- names, grids, blocks, LDS bytes, the admission and every check of a call that needs no device -- is decided in
 // batch_plan.h, without HIP.  This header is struct mc_batch as its four units see it: the state, the allocator, the launch path and the
@@ -31,7 +33,7 @@
 //   batch.cc           creation and release, one token (gemv, enqueue_token, head), the lockstep and ragged entry points
 //   batch_rows.cc      the rows passes: rows_pass, verify_head, mc_rows_prefill / mc_extend_rows / mc_verify_rows / mc_tree_verify
 //   batch_cache.cc     a row's cache: fork, import, the exports, mc_rolling_*
-//   batch_settings.cc  what a row slot carries between calls: seeds, row samplers, row logit processors
+//   batch_settings.cc  what a row slot carries between calls: seeds, row samplers, row logit processors; the log-probability switch and mc_logprobs_get
 #pragma once
 
 #include "bf16_host.h"
@@ -118,6 +120,24 @@ struct mc_batch {
     int32_t* counts_dev = nullptr;
     mcimpl::row_logits* logits_tab_dev = nullptr;
     std::vector<mcimpl::row_logits> logits_tab_sent;
+    // Part 2n (mc_logprobs_set): with the switch on, two launches behind every pick record the pick's log-probability and the top_n most
+    // likely tokens (plan_logprobs).  Beside tokens_dev and indexed like it: lp_tok [n][B], lp_ids / lp_top [n][B][top_n], filled with 0xFF
+    // where tokens_dev is filled (a slot without a record: NaN bits, id -1); their [MC_VERIFY_MAX_ROWS] twins for the verify calls; the parts
+    // and chunk keys of the launches in flight.  All reserved at the first call that needs them: a batch that never asks holds what it held
+    bool logprobs_on = false;
+    int logprobs_top = 0;
+    mcimpl::logprobs_plan lpp, v_lpp;     // of the call in flight (plan_pick; a verify call: rows_pass)
+    float *lp_tok = nullptr, *lp_top = nullptr;
+    int32_t* lp_ids = nullptr;
+    int lp_tok_cap = 0, lp_top_cap = 0, lp_ids_cap = 0; // (slots)
+    int lp_n = 0;                         // n of the last step, generate or packed call with records (0: none yet)
+    float *v_lp_tok = nullptr, *v_lp_top = nullptr;
+    int32_t* v_lp_ids = nullptr;
+    int v_lp_tok_cap = 0, v_lp_top_cap = 0, v_lp_ids_cap = 0;
+    int v_lp_rows = 0;                    // packed rows of the last verify call with records (0: none yet)
+    mcimpl::logprob_part* lp_parts = nullptr;
+    uint64_t* lp_keys = nullptr;
+    int lp_parts_cap = 0, lp_keys_cap = 0; // (rows)
     // The plans (batch_plan.h).  Fixed at creation: B, the device's compute units and MC_WB_TILES, both read once there (genv); the GEMV of
     // every matrix; the launches of a step, lockstep / ragged / ragged on a rolling batch.  Of the call in flight (plan_call, plan_pick):
     // its step, the rows' logit processors and the pick -- the settings cannot change inside a call
@@ -228,6 +248,12 @@ struct mc_batch {
     mc_status enqueue_token(int pos, bool advance);
     mc_status head(bool ragged, bool count);
     mc_status process_logits(bool ragged, bool count);
+    // Part 2n: the records of a call of n tokens, reserved and filled (nothing while the switch is off); the scratch of the two launches for R
+    // rows; the launches themselves over the rows of `rows_logits`, token and slot from `state` or (state null) from picks[m] and m
+    mc_status begin_logprobs(int n);
+    mc_status reserve_logprob_scratch(int R);
+    mc_status enqueue_logprobs(const mcimpl::logprobs_plan& l, const void* rows_logits, const mcimpl::step_state* state, const int32_t* picks, uint32_t nslots,
+                               float* out_tok, int32_t* out_ids, float* out_top);
     // ---------------------------------------------------------------- the rows passes (batch_rows.cc)
     mc_status verify_head(const void* xrows, const int32_t* tokens, int M, int nseg, const mcimpl::tv_node* nodes = nullptr);
 };

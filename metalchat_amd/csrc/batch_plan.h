@@ -1,8 +1,8 @@
 // What a batch (mc_batch_*, mc_ragged_*, the rows passes' heads; batch_impl.h) launches, decided without a device: the admission of a decoder
 // (refusal), the GEMV of every matrix (plan_batch_gemv: family, tiles, grid, the adaptor's launch in front), the launches of a step whose name and
 // grid follow from the config alone (plan_step), the head's pick in its three forms with the rows' effective samplers (plan_head, sampler_plan),
-// the logit processors' table and launch (plan_logits), the head of a verify call (plan_verify_head; with row settings: plan_verify_pick,
-// plan_verify_logits), and the checks of a call that need no device
+// the logit processors' table and launch (plan_logits), the two log-probability launches behind a pick (plan_logprobs), the head of a verify
+// call (plan_verify_head; with row settings: plan_verify_pick, plan_verify_logits), and the checks of a call that need no device
 // (check_ragged, check_tokens, step_bounds / generate_bounds, verify_samplers, verify_logit_rows, check_row).  Plain integer arithmetic over config
 // words, a linear's shape and kernels/abi.h constants -- no HIP, no mc_decoder, no device pointers -- so tests/cpp/test_batch_plan.cc pins names,
 // grids, blocks and LDS bytes on the CPU against a recording of the launches (tests/golden/batch_plans.json).  The batch's units launch what these
@@ -304,6 +304,49 @@ plan_logits(const std::vector<row_logit_setting>& rows, int vocab, bool ragged)
         t.pres = rs.pres;
     }
     if (p.any) p.launch = {ragged ? "mc_b_logits_process_rows_bfloat" : "mc_b_logits_process_bfloat", ((unsigned)vocab + LP_CHUNK - 1) / LP_CHUNK, B, 1, LP_THREADS, 0};
+    return p;
+}
+
+// ---------------------------------------------------------------- row log-probabilities (Part 2n)
+
+static_assert(LOGPROBS_MAX_TOP == MC_LOGPROBS_MAX_TOP, "the kernels' bound is the public one");
+
+// mc_logprobs_set's values ("" = fine)
+inline std::string
+check_logprobs(int32_t enable, int32_t top_n, int vocab)
+{
+    if (enable != 0 && enable != 1) return "mc_logprobs_set: enable must be 0 or 1";
+    if (top_n < 0 || top_n > MC_LOGPROBS_MAX_TOP) return "mc_logprobs_set: top_n must lie in [0, " + std::to_string(MC_LOGPROBS_MAX_TOP) + "]";
+    if (top_n > vocab) return "mc_logprobs_set: top_n (" + std::to_string(top_n) + ") is above the vocabulary (" + std::to_string(vocab) + ")";
+    return "";
+}
+
+// The two launches behind the pick of R rows (logprob_kernels.hip): a part and top_n keys per (row, chunk), then one workgroup per row that folds
+// them.  any false (the switch is off): nothing is launched.  ragged: the _rows forms, in which idle rows' workgroups exit; a verify call takes the
+// plain forms over its M packed rows.  The finish launch holds a row's parts one to a thread and its nchunk * top_n keys in registers: a
+// vocabulary beyond that is refused (MC_ERR_RUNTIME)
+struct logprobs_plan {
+    std::string refusal;
+    bool any = false;
+    uint32_t nchunk = 0;
+    launch_plan parts, finish;
+};
+inline logprobs_plan
+plan_logprobs(bool enabled, int top_n, int vocab, int R, bool ragged)
+{
+    logprobs_plan p;
+    if (!enabled) return p;
+    p.any = true;
+    p.nchunk = ((uint32_t)vocab + LOGPROB_CHUNK - 1) / LOGPROB_CHUNK;
+    if (p.nchunk > LOGPROB_THREADS || p.nchunk * (uint32_t)top_n > LOGPROB_KEY_CAP) {
+        p.refusal = "mc_logprobs: the vocabulary has " + std::to_string(p.nchunk) + " chunks of " + std::to_string(LOGPROB_CHUNK) + ", with top_n " +
+                    std::to_string(top_n) + " more than the finish launch folds (" + std::to_string(LOGPROB_THREADS) + " chunks, " +
+                    std::to_string(LOGPROB_KEY_CAP) + " keys)";
+        return p;
+    }
+    const std::string sfx = ragged ? "_rows_bfloat" : "_bfloat";
+    p.parts = {"mc_logprob_parts" + sfx, p.nchunk, (unsigned)R, 1, LOGPROB_THREADS, 0};
+    p.finish = {"mc_logprob_finish" + sfx, 1, (unsigned)R, 1, LOGPROB_THREADS, 0};
     return p;
 }
 

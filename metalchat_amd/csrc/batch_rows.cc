@@ -37,6 +37,8 @@ mc_batch::verify_head(const void* xrows, const int32_t* tokens, int M, int nseg,
                                        (const uint64_t*)seeds, (uint32_t)n_seed_pairs, picks));
         if (s != MC_OK) return s;
     }
+    // Part 2n: every pick gets its record, in front of the acceptance: each accepted token and the bonus token is one of them
+    if (v_lpp.any && (s = enqueue_logprobs(v_lpp, v_logits, nullptr, picks, (uint32_t)M, v_lp_tok, v_lp_ids, v_lp_top)) != MC_OK) return s;
     int32_t* paths = v.tree ? picks + M : nullptr;
     if (!v.tree)
         s = launch(v.accept, pack((const pp_seg*)pp_segs(pp_tab), tokens, (const int32_t*)picks, (const void*)v_logits, (uint32_t)c.vocab, v_out,
@@ -100,6 +102,7 @@ rows_pass(mc_batch* b, const char* who, bool extend, const int32_t* tokens, cons
     MC_HIP(hipMemcpyAsync(b->rows, b->rows_host.data(), sizeof(step_state) * B, hipMemcpyHostToDevice, b->p.stream));
     if ((s = b->ensure_tokens(1)) != MC_OK) return s;
     MC_HIP(hipMemsetAsync(b->tokens_dev, 0xFF, sizeof(int32_t) * B, b->p.stream));
+    if (!v && (s = b->begin_logprobs(1)) != MC_OK) return s; // Part 2n: the one pick per row is a record in slot r
     pk.kc = b->kc;
     pk.vt = b->vt;
     pk.B = B;
@@ -136,6 +139,21 @@ rows_pass(mc_batch* b, const char* who, bool extend, const int32_t* tokens, cons
         if (tree) MC_HIP(hipMemsetAsync(b->v_out + 2 * B + M, 0xFF, sizeof(int32_t) * MC_VERIFY_MAX_LEN * B, b->p.stream)); // ... its path
         pk.rows_all = &rows_all;
         pk.tokens_dev = &ids;
+        // Part 2n: a record per packed row, in the [MC_VERIFY_MAX_ROWS] twins of the step's buffers
+        b->v_lpp = plan_logprobs(b->logprobs_on, b->logprobs_top, c.vocab, M, false);
+        if (!b->v_lpp.refusal.empty()) return fail(MC_ERR_RUNTIME, b->v_lpp.refusal);
+        if (b->v_lpp.any) {
+            const int top = b->logprobs_top;
+            if ((s = b->reserve_logprob_scratch(MC_VERIFY_MAX_ROWS)) != MC_OK || (s = b->reserve(b->v_lp_tok, b->v_lp_tok_cap, M, MC_VERIFY_MAX_ROWS)) != MC_OK) return s;
+            MC_HIP(hipMemsetAsync(b->v_lp_tok, 0xFF, sizeof(float) * MC_VERIFY_MAX_ROWS, b->p.stream));
+            if (top > 0) {
+                if ((s = b->reserve(b->v_lp_ids, b->v_lp_ids_cap, M, MC_VERIFY_MAX_ROWS, sizeof(int32_t) * top)) != MC_OK ||
+                    (s = b->reserve(b->v_lp_top, b->v_lp_top_cap, M, MC_VERIFY_MAX_ROWS, sizeof(float) * top)) != MC_OK)
+                    return s;
+                MC_HIP(hipMemsetAsync(b->v_lp_ids, 0xFF, sizeof(int32_t) * MC_VERIFY_MAX_ROWS * top, b->p.stream));
+                MC_HIP(hipMemsetAsync(b->v_lp_top, 0xFF, sizeof(float) * MC_VERIFY_MAX_ROWS * top, b->p.stream));
+            }
+        }
         // Part 2m: the pick and the processors of the rows in the call (with the switch off verify_settings has refused every row that would
         // need them); their tables go up with the call's other tables
         b->v_pick = verify_pick_plan{};
@@ -162,6 +180,7 @@ rows_pass(mc_batch* b, const char* who, bool extend, const int32_t* tokens, cons
     MC_HIP(hipStreamSynchronize(b->p.stream)); // (`tokens` is the caller's buffer; the tables are read by the launches)
     if (v) {
         b->v_rows = M;
+        b->v_lp_rows = b->v_lpp.any ? M : 0;
         b->v_host.resize(2 * B + M + (tree ? MC_VERIFY_MAX_LEN * B : 0));
         MC_HIP(hipMemcpy(b->v_host.data(), b->v_out, sizeof(int32_t) * b->v_host.size(), hipMemcpyDeviceToHost));
         std::copy_n(b->v_host.begin(), B, v->accepted);
@@ -260,6 +279,24 @@ mc_verify_get_logits(mc_batch* b, void* logits_T)
     MC_HIP(hipSetDevice(b->p.ordinal));
     MC_HIP(hipStreamSynchronize(b->p.stream));
     MC_HIP(hipMemcpy(logits_T, b->v_logits, (size_t)b->v_rows * b->p.cfg.vocab * 2, hipMemcpyDeviceToHost));
+    return MC_OK;
+}
+
+// ---- Part 2n: the records of the last verify call (the switch and mc_logprobs_get: batch_settings.cc) ----
+
+mc_status
+mc_logprobs_get_verify(mc_batch* b, float* pick_logprobs, int32_t* top_ids, float* top_logprobs)
+{
+    if (!b || !pick_logprobs) return fail(MC_ERR_INVALID_ARGUMENT, "mc_logprobs_get_verify: null argument");
+    if (!b->logprobs_on) return fail(MC_ERR_INVALID_ARGUMENT, "mc_logprobs_get_verify: log-probabilities are switched off (mc_logprobs_set)");
+    if (!b->v_lp_rows) return fail(MC_ERR_INVALID_ARGUMENT, "mc_logprobs_get_verify: no verify call with log-probabilities on this batch yet");
+    const size_t M = (size_t)b->v_lp_rows, top = (size_t)b->logprobs_top;
+    if (top == 0 && (top_ids || top_logprobs)) return fail(MC_ERR_INVALID_ARGUMENT, "mc_logprobs_get_verify: top_n is 0, the top arrays must be null");
+    MC_HIP(hipSetDevice(b->p.ordinal));
+    MC_HIP(hipStreamSynchronize(b->p.stream));
+    MC_HIP(hipMemcpy(pick_logprobs, b->v_lp_tok, sizeof(float) * M, hipMemcpyDeviceToHost));
+    if (top_ids) MC_HIP(hipMemcpy(top_ids, b->v_lp_ids, sizeof(int32_t) * M * top, hipMemcpyDeviceToHost));
+    if (top_logprobs) MC_HIP(hipMemcpy(top_logprobs, b->v_lp_top, sizeof(float) * M * top, hipMemcpyDeviceToHost));
     return MC_OK;
 }
 

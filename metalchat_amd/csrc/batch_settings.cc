@@ -1,5 +1,5 @@
-// What a batch's row slots carry between calls (the map of the whole: batch_impl.h): the seeds, the row samplers (Part 2k) and the row logit
-// processors (Part 2l).  The calls store what the caller set; plan_head / plan_logits (batch_plan.h) resolve it at the next step.
+// What a batch's row slots carry between calls (the map of the whole: batch_impl.h): the seeds, the row samplers (Part 2k), the row logit
+// processors (Part 2l) and the batch's log-probability switch with its records (Part 2n).  The calls store what the caller set; plan_head / plan_logits (batch_plan.h) resolve it at the next step.
 // Every batch call drains the stream before it returns, so the synchronous copies below meet an idle stream.
 #include "batch_impl.h"
 
@@ -209,6 +209,46 @@ mc_row_logits_reset(mc_batch* b)
     MC_HIP(hipSetDevice(b->p.ordinal));
     MC_HIP(hipMemsetAsync(b->counts_dev, 0, sizeof(int32_t) * (size_t)b->B * b->p.cfg.vocab, b->p.stream));
     MC_HIP(hipStreamSynchronize(b->p.stream));
+    return MC_OK;
+}
+
+// ---- Part 2n: row log-probabilities ----
+
+mc_status
+mc_logprobs_set(mc_batch* b, int32_t enable, int32_t top_n)
+{
+    if (!b) return fail(MC_ERR_INVALID_ARGUMENT, "mc_logprobs_set: null argument");
+    if (mc_status s = refuse(check_logprobs(enable, top_n, b->p.cfg.vocab)); s != MC_OK) return s;
+    if (top_n != b->logprobs_top) // the records are laid out by top_n: the next call reserves them anew
+        b->lp_ids_cap = b->lp_top_cap = b->v_lp_ids_cap = b->v_lp_top_cap = 0;
+    b->logprobs_on = enable == 1;
+    b->logprobs_top = top_n;
+    b->lp_n = b->v_lp_rows = 0; // what an earlier setting recorded is gone
+    return MC_OK;
+}
+
+int32_t
+mc_logprobs_enabled(const mc_batch* b, int32_t* top_n)
+{
+    if (!b) return 0;
+    if (top_n) *top_n = b->logprobs_top;
+    return b->logprobs_on ? 1 : 0;
+}
+
+mc_status
+mc_logprobs_get(mc_batch* b, int32_t n, float* token_logprobs, int32_t* top_ids, float* top_logprobs)
+{
+    if (!b || !token_logprobs) return fail(MC_ERR_INVALID_ARGUMENT, "mc_logprobs_get: null argument");
+    if (!b->logprobs_on) return fail(MC_ERR_INVALID_ARGUMENT, "mc_logprobs_get: log-probabilities are switched off (mc_logprobs_set)");
+    if (!b->lp_n) return fail(MC_ERR_INVALID_ARGUMENT, "mc_logprobs_get: no step, generate or packed call with log-probabilities on this batch yet");
+    if (n != b->lp_n) return fail(MC_ERR_INVALID_ARGUMENT, "mc_logprobs_get: n must be the last call's n = " + std::to_string(b->lp_n));
+    const size_t slots = (size_t)n * b->B, top = (size_t)b->logprobs_top;
+    if (top == 0 && (top_ids || top_logprobs)) return fail(MC_ERR_INVALID_ARGUMENT, "mc_logprobs_get: top_n is 0, the top arrays must be null");
+    MC_HIP(hipSetDevice(b->p.ordinal));
+    MC_HIP(hipStreamSynchronize(b->p.stream));
+    MC_HIP(hipMemcpy(token_logprobs, b->lp_tok, sizeof(float) * slots, hipMemcpyDeviceToHost));
+    if (top_ids) MC_HIP(hipMemcpy(top_ids, b->lp_ids, sizeof(int32_t) * slots * top, hipMemcpyDeviceToHost));
+    if (top_logprobs) MC_HIP(hipMemcpy(top_logprobs, b->lp_top, sizeof(float) * slots * top, hipMemcpyDeviceToHost));
     return MC_OK;
 }
 

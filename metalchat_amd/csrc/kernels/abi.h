@@ -93,6 +93,23 @@ static_assert(sizeof(row_logits) == 32 && alignof(row_logits) == 16 && offsetof(
                   offsetof(row_logits, inv_rep) == 8 && offsetof(row_logits, freq) == 12 && offsetof(row_logits, pres) == 16,
               "row_logits: eight words (read whole with one scalar load)");
 
+// ---- row log-probabilities (logprob_kernels.hip mc_logprob_parts_* / mc_logprob_finish_*; ABI Part 2n) ----
+// launch 1 writes one part per (row, chunk of LOGPROB_CHUNK logits) and the chunk's top_n best keys, launch 2 folds a row's parts
+constexpr int LOGPROBS_MAX_TOP = 20;                // (= MC_LOGPROBS_MAX_TOP) the most top_n: the largest `top_logprobs` any public API takes
+constexpr uint32_t LOGPROB_THREADS = 256;           // threads of a workgroup of either launch ...
+constexpr uint32_t LOGPROB_CHUNK = 8 * LOGPROB_THREADS; // ... and the logits of one row a parts workgroup streams: one 16-byte piece per thread
+constexpr uint32_t LOGPROB_FINISH_KEYS = 8;         // chunk keys a thread of the finish launch holds in registers
+constexpr uint32_t LOGPROB_KEY_CAP = LOGPROB_FINISH_KEYS * LOGPROB_THREADS; // nchunk * top_n it can fold; nchunk <= LOGPROB_THREADS as well
+struct alignas(16) logprob_part {
+    double s;  // sum over the chunk of exp(double(y) - double(m)), 0 where m is -inf
+    float m;   // the chunk's maximum (a bfloat16 value)
+    uint32_t pad;
+};
+static_assert(sizeof(logprob_part) == 16 && alignof(logprob_part) == 16 && offsetof(logprob_part, s) == 0 && offsetof(logprob_part, m) == 8,
+              "logprob_part: one 16-byte store and load");
+static_assert(LOGPROB_CHUNK == 2048 && LOGPROB_CHUNK == LP_CHUNK, "the parts launch has the shape of mc_b_logits_process_*");
+static_assert(LOGPROBS_MAX_TOP * ((128256 + LOGPROB_CHUNK - 1) / LOGPROB_CHUNK) <= LOGPROB_KEY_CAP, "Llama-3's vocabulary fits the finish launch at top_n = 20");
+
 // ---- the descriptors a decode GEMV finds behind its `res` argument (gemv.h) ----
 // PRO_POSTNORM
 struct postnorm_args {

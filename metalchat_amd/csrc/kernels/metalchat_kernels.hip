@@ -15,3 +15,4 @@
 #include "wide_kernels.hip"
 #include "tree_kernels.hip"
 #include "logit_kernels.hip"
+#include "logprob_kernels.hip"

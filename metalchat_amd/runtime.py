@@ -235,6 +235,10 @@ def capi() -> C.CDLL:
         "mc_tree_verify": (i32, [vp] + [C.POINTER(i32)] * 8),
         "mc_settings_verify_set": (i32, [vp, i32]),
         "mc_settings_verify_enabled": (i32, [vp]),
+        "mc_logprobs_set": (i32, [vp, i32, i32]),
+        "mc_logprobs_enabled": (i32, [vp, C.POINTER(i32)]),
+        "mc_logprobs_get": (i32, [vp, i32, C.POINTER(f32), C.POINTER(i32), C.POINTER(f32)]),
+        "mc_logprobs_get_verify": (i32, [vp, C.POINTER(f32), C.POINTER(i32), C.POINTER(f32)]),
         "mc_synth_weight": (i32, [u64, u32, u32, u32, i32]),
         "mc_synth_scale": (f32, [u64, u32, u32, u32, i32, i32]),
         "mc_synth_value": (f32, [u64, u32, u32, i32, u32]),
@@ -1011,6 +1015,42 @@ class Batch:
 
     def verify_settings(self) -> bool:
         return bool(capi().mc_settings_verify_enabled(self._h))
+
+    # ---- row log-probabilities (Part 2n), opt-in per batch
+
+    def set_logprobs(self, top_n: int = 0, enable: bool = True):
+        """on: every pick of the batch leaves a record on the device -- the picked token's log-probability under the model's
+        distribution over the row's processed logits at temperature 1 (not the sampler's truncated nucleus) and the top_n <= 20 most
+        likely tokens with theirs.  Default off: the batch launches and holds what it did before."""
+        _check(capi().mc_logprobs_set(self._h, 1 if enable else 0, top_n))
+
+    def logprobs_setting(self):
+        """(enabled, top_n)"""
+        top = C.c_int32()
+        on = capi().mc_logprobs_enabled(self._h, C.byref(top))
+        return bool(on), top.value
+
+    def _logprob_arrays(self, call, lead, shape):
+        top = self.logprobs_setting()[1]
+        tok = np.zeros(shape, dtype=np.float32)
+        ids = np.zeros(shape + (top,), dtype=np.int32)
+        lps = np.zeros(shape + (top,), dtype=np.float32)
+        fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int32)
+        _check(call(self._h, *lead, tok.ctypes.data_as(fp), ids.ctypes.data_as(ip) if top else None, lps.ctypes.data_as(fp) if top else None))
+        return tok, ids, lps
+
+    def logprobs(self, n: int = 1):
+        """the records of the last step, generate or packed call, n that call's n: (token_lp [n, B], top_ids [n, B, top_n],
+        top_lp [n, B, top_n]); a slot without a record (an idle or stopped row) holds NaN and id -1"""
+        return self._logprob_arrays(capi().mc_logprobs_get, (n,), (max(n, 0), self.B))
+
+    def verify_logprobs(self):
+        """the records of the last verify_rows or verify_tree call, one per packed row: per batch row (pick_lp [lens[r]],
+        top_ids [lens[r], top_n], top_lp [lens[r], top_n]), None for a row that was not in it"""
+        lens = getattr(self, "_verify_lens", np.zeros(self.B, np.int32))
+        tok, ids, lps = self._logprob_arrays(capi().mc_logprobs_get_verify, (), (max(int(lens.sum()), 1),))
+        off = np.concatenate([[0], np.cumsum(lens)])
+        return [(tok[off[r]:off[r + 1]], ids[off[r]:off[r + 1]], lps[off[r]:off[r + 1]]) if lens[r] else None for r in range(self.B)]
 
     # ---- row samplers (Part 2k): each row slot picks with settings of its own
 
