@@ -25,7 +25,7 @@ KERNEL_SOURCES = [os.path.join(CSRC, "kernels", f) for f in (
 HOST_UNITS = [os.path.join(CSRC, f) for f in ("backend.cc", "decoder.cc", "weights.cc", "prefill.cc", "prefill_blaslt.cc", "pipeline.cc", "batch.cc",
                                                "batch_rows.cc", "batch_cache.cc", "batch_settings.cc", "model_io.cc", "text.cc")]
 HOST_HEADERS = [os.path.join(CSRC, f) for f in ("json_min.h", "backend_impl.h", "decoder_impl.h", "decoder_batch.h", "decoder_options.h", "gemv_plan.h", "block_plan.h", "token_plan.h", "prefill_plan.h", "rows_plan.h",
-                                                 "batch_plan.h", "batch_impl.h", "bf16_host.h", "sampler_plan.h")] + [
+                                                 "batch_plan.h", "batch_call_plan.h", "batch_impl.h", "bf16_host.h", "sampler_plan.h")] + [
     os.path.join(CSRC, "kernels", "synth.h"), os.path.join(CSRC, "kernels", "abi.h"),
     os.path.join(os.path.dirname(HERE), "include", "metalchat_hip.h")]
 
@@ -128,28 +128,28 @@ def build_rows_plan_test(force: bool = False) -> str:
 
 
 def build_batch_plan_test(force: bool = False) -> str:
-    """tests/cpp/test_batch_plan: what a batch launches (csrc/batch_plan.h) from the command line -- no HIP and no host library."""
-    headers = [os.path.join(CSRC, f) for f in ("batch_plan.h", "rows_plan.h", "bf16_host.h", "sampler_plan.h")] + [os.path.join(CSRC, "kernels", "abi.h"), _ABI_HEADERS[1]]
+    """tests/cpp/test_batch_plan: what a batch launches (csrc/batch_plan.h, in order: batch_call_plan.h) from the command line -- no HIP and no host library."""
+    headers = [os.path.join(CSRC, f) for f in ("batch_plan.h", "batch_call_plan.h", "rows_plan.h", "bf16_host.h", "sampler_plan.h")] + [os.path.join(CSRC, "kernels", "abi.h"), _ABI_HEADERS[1]]
     return _build_cpp_test("test_batch_plan", headers, force, False)
 
 
 def build_draw_plan_test(force: bool = False) -> str:
     """tests/cpp/test_draw_plan: the pick of a batch with MC_SAMPLER_DRAW rows (csrc/batch_plan.h plan_head) -- no HIP and no host library."""
-    headers = [os.path.join(CSRC, f) for f in ("batch_plan.h", "rows_plan.h", "bf16_host.h", "sampler_plan.h")] + [os.path.join(CSRC, "kernels", "abi.h"), _ABI_HEADERS[1]]
+    headers = [os.path.join(CSRC, f) for f in ("batch_plan.h", "batch_call_plan.h", "rows_plan.h", "bf16_host.h", "sampler_plan.h")] + [os.path.join(CSRC, "kernels", "abi.h"), _ABI_HEADERS[1]]
     return _build_cpp_test("test_draw_plan", headers, force, False)
 
 
 def build_verify_settings_plan_test(force: bool = False) -> str:
     """tests/cpp/test_verify_settings_plan: the head of a verify call whose rows carry settings (csrc/batch_plan.h plan_verify_pick /
     plan_verify_logits) -- no HIP and no host library."""
-    headers = [os.path.join(CSRC, f) for f in ("batch_plan.h", "rows_plan.h", "bf16_host.h", "sampler_plan.h")] + [os.path.join(CSRC, "kernels", "abi.h"), _ABI_HEADERS[1]]
+    headers = [os.path.join(CSRC, f) for f in ("batch_plan.h", "batch_call_plan.h", "rows_plan.h", "bf16_host.h", "sampler_plan.h")] + [os.path.join(CSRC, "kernels", "abi.h"), _ABI_HEADERS[1]]
     return _build_cpp_test("test_verify_settings_plan", headers, force, False)
 
 
 def build_logprob_plan_test(force: bool = False) -> str:
     """tests/cpp/test_logprob_plan: the two launches behind a pick of a batch with log-probabilities on (csrc/batch_plan.h plan_logprobs) -- no HIP
     and no host library."""
-    headers = [os.path.join(CSRC, f) for f in ("batch_plan.h", "rows_plan.h", "bf16_host.h", "sampler_plan.h")] + [os.path.join(CSRC, "kernels", "abi.h"), _ABI_HEADERS[1]]
+    headers = [os.path.join(CSRC, f) for f in ("batch_plan.h", "batch_call_plan.h", "rows_plan.h", "bf16_host.h", "sampler_plan.h")] + [os.path.join(CSRC, "kernels", "abi.h"), _ABI_HEADERS[1]]
     return _build_cpp_test("test_logprob_plan", headers, force, False)
 
 

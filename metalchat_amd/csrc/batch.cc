@@ -1,188 +1,220 @@
-// The batch's step path (the map of the whole: batch_impl.h): creation and release, one token -- the launches batch_plan.h plans, with their
-// arguments bound here --, and the lockstep (mc_batch_step / _generate) and ragged (mc_ragged_step / _generate) entry points.
+// The batch's step path (the map of the whole: batch_impl.h): creation and release; prepare() and run(), which reserve for and execute the ordered
+// plan of any call on a batch (batch_call_plan.h) -- every launch's arguments are bound here --; the log-probability records; and the lockstep
+// (mc_batch_step / _generate) and ragged (mc_ragged_step / _generate) entry points.
 #include "batch_impl.h"
 
 using namespace mcimpl;
 
-// y[r] = epi(W x[r]) for the B rows as g says (plan_batch_gemv): a linear with an adaptor takes a = T(A x) for all rows into lora_vec first,
-// and its main launch the adaptor's five arguments behind its own
+// y[r] = epi(W x[r]) for the B rows, the launch plan_batch_gemv planned: the wide form (fx.wide, one answer for every linear of a batch) takes L.out
+// in front of ldy; adaptor: a = T(A x) for all rows into lora_vec, the launch the plan lists in front of a linear with an adaptor (L.lora, what
+// plan_batch_gemv read), whose main launch takes the adaptor's five arguments behind its own
 mc_status
-mc_batch::gemv(const batch_linear& L, const batch_gemv_plan& g, const void* xin, void* y, uint32_t ldy)
+mc_batch::gemv(const launch_plan& l, bool adaptor, const batch_linear& L, const void* xin, void* y, uint32_t ldy)
 {
     auto args = [&](const void* w, const void* scales, void* out, uint32_t ngroups, uint32_t group, uint32_t rows_out, uint32_t ld) {
-        return g.wide ? pack(w, scales, xin, out, (uint32_t)L.in, ngroups, group, (uint32_t)B, rows_out, ld)
-                      : pack(w, scales, xin, out, (uint32_t)L.in, ngroups, group, (uint32_t)B, ld);
+        return fx.wide ? pack(w, scales, xin, out, (uint32_t)L.in, ngroups, group, (uint32_t)B, rows_out, ld)
+                                 : pack(w, scales, xin, out, (uint32_t)L.in, ngroups, group, (uint32_t)B, ld);
     };
-    if (g.lora) {
-        mc_status s = launch(g.adaptor, args(L.lora_a, nullptr, lora_vec, 0, 0, (uint32_t)L.lora_cols, (uint32_t)lora_ld));
-        if (s != MC_OK) return s;
-    }
+    if (adaptor) return launch(l, args(L.lora_a, nullptr, lora_vec, 0, 0, (uint32_t)L.lora_cols, (uint32_t)lora_ld));
     arg_pack a = args(L.w, L.scales, y, (uint32_t)L.ngroups, (uint32_t)L.group, (uint32_t)L.out, ldy);
-    if (g.lora) {
+    if (L.lora) {
         a.push((const void*)lora_vec);
         a.push((uint32_t)lora_ld);
         a.push(L.lora_b);
         a.push((uint32_t)L.lora_cols);
         a.push(L.lora_scale);
     }
-    return launch(g.main, std::move(a));
+    return launch(l, std::move(a));
 }
 
+// Part 2n: `slots` records (of `cap` reserved), every slot filled with 0xFF: a slot no pick reaches (an idle or retired row, a row outside a
+// packed call) reads as NaN bits and id -1
 mc_status
-mc_batch::plan_call(bool ragged)
+mc_batch::begin_records(logprob_records& r, int slots, int cap)
 {
-    step = &steps[!ragged ? 0 : (rolling ? 2 : 1)];
-    return plan_pick(ragged);
-}
-
-// no table (and no launch) of the logit processors while no row has anything set; the samplers' table for the mixed form only
-mc_status
-mc_batch::plan_pick(bool ragged)
-{
+    const int top = logprobs_top;
     mc_status s;
-    lpp = plan_logprobs(logprobs_on, logprobs_top, p.cfg.vocab, B, ragged);
-    if (!lpp.refusal.empty()) return fail(MC_ERR_RUNTIME, lpp.refusal);
-    if (lpp.any && (s = reserve_logprob_scratch(B)) != MC_OK) return s;
-    lp = plan_logits(row_logit_set, p.cfg.vocab, ragged);
-    if (lp.any && ((s = ensure(logits_tab_dev, sizeof(row_logits) * B)) != MC_OK || (s = send_if_changed(logits_tab_dev, logits_tab_sent, lp.table)) != MC_OK))
-        return s;
-    pick = plan_head(row_samplers, decoder_sampler_of(d), p.cfg.vocab, ragged, cand_per_row);
-    if (!pick.refusal.empty()) return fail(MC_ERR_RUNTIME, pick.refusal);
-    return pick.form == PICK_MIXED ? send_if_changed(samplers_dev, samplers_sent, pick.table) : MC_OK;
-}
-
-// one token of the call plan_call planned.  Lockstep: at `pos` for every row; advance: a chained step (row r's step_index moves by B).
-// Ragged: every row at its own rows[r].pos instead, the same launches with the per-row kernels; `pos` is not used, and
-// mc_b_rows_begin starts the step (advance: retires the rows that stopped, moves the others on).
-mc_status
-mc_batch::enqueue_token(int pos, bool advance)
-{
-    const mc_decoder_config& c = p.cfg;
-    const step_plan& sp = *step;
-    const int H = c.n_heads, KV = c.n_kv_heads, hd = c.head_dim, n_rep = H / KV;
-    const float scale_T = round_bf_host(c.attn_scale); // T(attn_scale): the scalar_mul of attention.h:196 is evaluated in T
-    const uint64_t cstride = cache_elems;
-    const bool q8 = p.emb_fmt != MC_WFMT_T;
-    const void* emb = q8 ? nullptr : p.emb_table;
-    const void* emb_q8 = q8 ? p.emb_table : nullptr;
-    mc_status s;
-    if (sp.rolling)
-        s = launch(sp.begin, pack(rows, (const int32_t*)stop_dev, (int32_t)stop_host.size(), (int32_t)c.max_seq_len, (int32_t)p.pre_len,
-                                  (int32_t)(advance ? 1 : 0), rcos, rsin, (uint32_t)hd, c.rope_theta));
-    else if (sp.ragged)
-        s = launch(sp.begin, pack(rows, (const int32_t*)stop_dev, (int32_t)stop_host.size(), (int32_t)c.max_seq_len, (int32_t)B, (int32_t)(advance ? 1 : 0)));
-    else
-        s = set_pos(pos);
-    if (s != MC_OK) return s;
-    if (sp.ragged)
-        s = launch(sp.embed, pack(emb, p.emb_scales, emb_q8, x, rows, (uint32_t)c.dim));
-    else
-        s = launch(sp.embed, pack(emb, p.emb_scales, emb_q8, x, rows, (uint32_t)c.dim, (int32_t)(advance ? 1 : 0), (uint32_t)B));
-    if (s != MC_OK) return s;
-    // the per-row launches: the lockstep kernel reads the shared state, its _rows form row r's own
-    const step_state* state = sp.ragged ? rows : st;
-    for (size_t li = 0; li < p.layers.size(); li++) {
-        const batch_layer& L = p.layers[li];
-        const layer_gemvs& g = gemvs[li];
-        const int l = (int)li;
-        if ((s = launch(sp.rmsnorm, pack((const void*)x, L.attention_norm, xn, (uint32_t)c.dim, c.norm_eps))) != MC_OK) return s;
-        if ((s = gemv(L.qkv, g.qkv, xn, qkv, (uint32_t)L.qkv.out)) != MC_OK) return s;
-        s = launch(sp.rope, pack(qkv, q, (void*)kc_of(l, 0), (void*)vt_of(l, 0), sp.rolling ? rcos : fcos, sp.rolling ? rsin : fsin, state, (uint32_t)H,
-                                 (uint32_t)KV, (uint32_t)hd, (uint32_t)c.max_seq_len, cstride));
-        if (s != MC_OK) return s;
-        s = launch(sp.scores, pack(q, (void*)kc_of(l, 0), expv, psum, state, (uint32_t)n_rep, (uint32_t)hd, (uint32_t)c.max_seq_len, scale_T,
-                                   (uint32_t)nsplit, cstride));
-        if (s != MC_OK) return s;
-        s = launch(sp.pv, pack(expv, psum, (void*)vt_of(l, 0), att, state, (uint32_t)n_rep, (uint32_t)hd, (uint32_t)c.max_seq_len, (uint32_t)nsplit,
-                               cstride));
-        if (s != MC_OK) return s;
-        if ((s = gemv(L.wo, g.wo, att, x, (uint32_t)c.dim)) != MC_OK) return s;
-        if ((s = launch(sp.rmsnorm, pack((const void*)x, L.ffn_norm, xn, (uint32_t)c.dim, c.norm_eps))) != MC_OK) return s;
-        if ((s = gemv(L.w13, g.w13, xn, gate, (uint32_t)(L.w13.out / 2))) != MC_OK) return s;
-        if ((s = gemv(L.w2, g.w2, gate, x, (uint32_t)c.dim)) != MC_OK) return s;
-    }
-    return head(sp.ragged, true);
-}
-
-// the final norm of x, the head and the pick per row as plan_pick planned them (the three forms: batch_plan.h plan_head), each row with its
-// effective sampler; ragged: rows whose rows[r].pos is -1 get no pick.  Part 2l: with a mask or penalties on any row,
-// mc_b_logits_process_* rewrites those rows' logits between the head and the pick; count: the rows with penalties count their input token
-// first (a step; the packed passes count nothing).  Part 2n: with the batch's switch on, the two log-probability launches run behind the pick
-// in all three forms, and the record lands in the slot the pick's token landed in
-mc_status
-mc_batch::head(bool ragged, bool count)
-{
-    const uint32_t vocab = (uint32_t)p.cfg.vocab;
-    mc_status s;
-    if ((s = launch(steps[0].rmsnorm, pack((const void*)x, p.final_norm, xn, (uint32_t)p.cfg.dim, p.cfg.norm_eps))) != MC_OK) return s;
-    if ((s = gemv(p.output, head_gemv, xn, logits, vocab)) != MC_OK) return s;
-    if ((s = process_logits(ragged, count)) != MC_OK) return s;
-    const sampler_params& sp = pick.sp;
-    switch (pick.form) {
-    case PICK_GREEDY: s = launch(pick.first, pack(logits, vocab, rows, tokens_dev)); break;
-    case PICK_UNIFORM:
-        if ((s = launch(pick.first, pack(logits, vocab, sp.kpad, cand, pick.chunk))) != MC_OK) return s;
-        s = launch(pick.second, pack(cand, sp, seeds, (uint32_t)n_seed_pairs, rows, tokens_dev));
-        break;
-    default:
-        s = launch(pick.first, pack(logits, vocab, sp.kpad, cand, pick.chunk, (const row_sampler*)samplers_dev, (const step_state*)rows,
-                                    (int32_t)(ragged ? 1 : 0)));
-        if (s != MC_OK) return s;
-        s = launch(pick.second, pack(logits, vocab, (const uint64_t*)cand, (const row_sampler*)samplers_dev, sp.nlists, sp.kpad, sp.cap,
-                                     (const uint64_t*)seeds, (uint32_t)n_seed_pairs, rows, tokens_dev));
-    }
-    if (s != MC_OK || !lpp.any) return s;
-    return enqueue_logprobs(lpp, logits, rows, nullptr, (uint32_t)(lp_n * B), lp_tok, lp_ids, lp_top);
-}
-
-// Part 2n: the records of a call of n tokens beside tokens_dev -- reserved, and every slot filled with 0xFF: a slot no pick reaches (an idle or
-// retired row, a row outside a packed call) reads as NaN bits and id -1
-mc_status
-mc_batch::begin_logprobs(int n)
-{
-    if (!logprobs_on) return MC_OK;
-    const int slots = n * B, top = logprobs_top;
-    mc_status s;
-    if ((s = reserve(lp_tok, lp_tok_cap, slots, slots)) != MC_OK) return s;
-    MC_HIP(hipMemsetAsync(lp_tok, 0xFF, sizeof(float) * (size_t)slots, p.stream));
+    if ((s = reserve(r.tok, r.tok_cap, slots, cap)) != MC_OK) return s;
+    MC_HIP(hipMemsetAsync(r.tok, 0xFF, sizeof(float) * (size_t)slots, p.stream));
     if (top > 0) {
-        if ((s = reserve(lp_ids, lp_ids_cap, slots, slots, sizeof(int32_t) * top)) != MC_OK || (s = reserve(lp_top, lp_top_cap, slots, slots, sizeof(float) * top)) != MC_OK)
+        if ((s = reserve(r.ids, r.ids_cap, slots, cap, sizeof(int32_t) * top)) != MC_OK || (s = reserve(r.top, r.top_cap, slots, cap, sizeof(float) * top)) != MC_OK)
             return s;
-        MC_HIP(hipMemsetAsync(lp_ids, 0xFF, sizeof(int32_t) * (size_t)slots * top, p.stream));
-        MC_HIP(hipMemsetAsync(lp_top, 0xFF, sizeof(float) * (size_t)slots * top, p.stream));
+        MC_HIP(hipMemsetAsync(r.ids, 0xFF, sizeof(int32_t) * (size_t)slots * top, p.stream));
+        MC_HIP(hipMemsetAsync(r.top, 0xFF, sizeof(float) * (size_t)slots * top, p.stream));
     }
-    lp_n = n;
+    r.count = 0; // (until the call says whose they are: a step in front of its launches, a verify call behind them)
     return MC_OK;
 }
 
-// a part per (row, chunk) and the chunks' keys at the most top_n, for R rows: sized by the bounds, so a change of top_n keeps them
+// ... and copied out behind a getter's own checks (ids, top: may be null)
 mc_status
-mc_batch::reserve_logprob_scratch(int R)
+mc_batch::copy_records(const logprob_records& r, size_t slots, float* tok, int32_t* ids, float* top)
 {
-    const size_t nchunk = ((size_t)p.cfg.vocab + LOGPROB_CHUNK - 1) / LOGPROB_CHUNK;
-    mc_status s = reserve(lp_parts, lp_parts_cap, R, R, sizeof(logprob_part) * nchunk);
-    if (s != MC_OK) return s;
-    return reserve(lp_keys, lp_keys_cap, R, R, sizeof(uint64_t) * nchunk * MC_LOGPROBS_MAX_TOP);
+    const size_t n = (size_t)logprobs_top;
+    MC_HIP(hipSetDevice(p.ordinal));
+    MC_HIP(hipStreamSynchronize(p.stream));
+    MC_HIP(hipMemcpy(tok, r.tok, sizeof(float) * slots, hipMemcpyDeviceToHost));
+    if (ids) MC_HIP(hipMemcpy(ids, r.ids, sizeof(int32_t) * slots * n, hipMemcpyDeviceToHost));
+    if (top) MC_HIP(hipMemcpy(top, r.top, sizeof(float) * slots * n, hipMemcpyDeviceToHost));
+    return MC_OK;
 }
 
+// A planned call of n tokens in front of its first launch: the refusal; tokens_dev; with log-probabilities the scratch of the two launches -- a
+// part per (row, chunk) and the chunks' keys at the most top_n, sized by the bounds, so a change of top_n keeps them -- and the records; a verify
+// call's packed rows (M <= 128; sized for any call) with -1 in the results of the rows not in the call; the tables, each sent when it differs from
+// what the device holds (none while no launch of the plan reads it)
 mc_status
-mc_batch::enqueue_logprobs(const logprobs_plan& l, const void* rows_logits, const step_state* state, const int32_t* picks, uint32_t nslots, float* out_tok,
-                           int32_t* out_ids, float* out_top)
+mc_batch::prepare(const batch_call_plan& c, int n)
 {
-    const uint32_t vocab = (uint32_t)p.cfg.vocab, top = (uint32_t)logprobs_top;
-    mc_status s = launch(l.parts, pack(rows_logits, vocab, top, lp_parts, lp_keys, state));
+    if (!c.refusal.empty()) return fail(c.code, c.refusal);
+    const mc_decoder_config& cfg = p.cfg;
+    mc_status s = ensure_tokens(n);
     if (s != MC_OK) return s;
-    return launch(l.finish, pack(rows_logits, vocab, top, l.nchunk, (const logprob_part*)lp_parts, (const uint64_t*)lp_keys, state, picks, nslots, out_tok,
-                                 out_ids, out_top));
+    if (c.lp_slots) {
+        const int R = c.M ? MC_VERIFY_MAX_ROWS : B;
+        const size_t nchunk = ((size_t)cfg.vocab + LOGPROB_CHUNK - 1) / LOGPROB_CHUNK;
+        if ((s = reserve(lp_parts, lp_parts_cap, R, R, sizeof(logprob_part) * nchunk)) != MC_OK ||
+            (s = reserve(lp_keys, lp_keys_cap, R, R, sizeof(uint64_t) * nchunk * MC_LOGPROBS_MAX_TOP)) != MC_OK ||
+            (s = c.M ? begin_records(vs.records, c.M, MC_VERIFY_MAX_ROWS) : begin_records(records, n * B, n * B)) != MC_OK)
+            return s;
+        if (!c.M) records.count = n;
+    }
+    if (c.M) {
+        const int out_max = 2 * MC_WIDE_BATCH_MAX + MC_VERIFY_MAX_ROWS + MC_VERIFY_MAX_LEN * MC_WIDE_BATCH_MAX;
+        if ((s = reserve(vs.xn, vs.xn_cap, c.M, MC_VERIFY_MAX_ROWS, (size_t)cfg.dim * 2)) != MC_OK ||
+            (s = reserve(vs.logits, vs.logits_cap, c.M, MC_VERIFY_MAX_ROWS, (size_t)cfg.vocab * 2)) != MC_OK ||
+            (s = reserve(vs.out, vs.out_cap, 2 * B + c.M + MC_VERIFY_MAX_LEN * B, out_max)) != MC_OK)
+            return s;
+        MC_HIP(hipMemsetAsync(vs.out, 0xFF, sizeof(int32_t) * 2 * B, p.stream)); // -1: a row not in the call
+        if (c.tree) MC_HIP(hipMemsetAsync(vs.out + 2 * B + c.M, 0xFF, sizeof(int32_t) * MC_VERIFY_MAX_LEN * B, p.stream)); // ... its path
+        if (!c.verify.empty() && ((s = reserve(vs.tab, vs.tab_cap, c.M, MC_VERIFY_MAX_ROWS)) != MC_OK || (s = send_if_changed(vs.tab, vs.tab_sent, c.verify)) != MC_OK))
+            return s;
+        if (c.cand_rows && (s = reserve(vs.cand, vs.cand_cap, c.cand_rows, MC_VERIFY_MAX_ROWS, sizeof(uint64_t) * fx.cand_per_row)) != MC_OK) return s;
+    }
+    if (!c.logits.empty() && ((s = ensure(logits_tab_dev, sizeof(row_logits) * B)) != MC_OK || (s = send_if_changed(logits_tab_dev, logits_tab_sent, c.logits)) != MC_OK))
+        return s;
+    return c.samplers.empty() ? MC_OK : send_if_changed(samplers_dev, samplers_sent, c.samplers);
 }
 
+// ONE launch of a plan: its op's arguments, bound here and nowhere else.  A token -- lockstep: at a.pos for every row, the kernels read the
+// shared state; advance: a chained step (row r's step_index moves by B).  Ragged: every row at its own rows[r].pos, the per-row kernels; a.pos is
+// not used and the begin launch starts the step (advance: retires the rows that stopped, moves the others on); rows whose pos is -1 get no pick.
+// The log-probability launches put the record in the slot the pick's token landed in (a verify call: of picks[m] in slot m).  A verify call --
+// a.xrows: its M packed rows, a.ids: its ids on the device, a.nodes: a tree's table -- picks per packed row, then accepts per segment (the accepted
+// row's logits into logits[row]), counts the accepted path on the penalised rows and (a tree) moves its K / V into place in every layer
 mc_status
-mc_batch::process_logits(bool ragged, bool count)
+mc_batch::run(const batch_launch& l, const call_args& a)
 {
-    if (!lp.any) return MC_OK;
-    arg_pack a = pack(logits, (uint32_t)p.cfg.vocab, (const row_logits*)logits_tab_dev, (const uint32_t*)masks_dev, counts_dev, (const step_state*)rows);
-    if (ragged) a.push((int32_t)(count ? 1 : 0));
-    return launch(lp.launch, std::move(a));
+    using op = batch_op;
+    const batch_call_plan& c = a.plan;
+    const mc_decoder_config& cfg = p.cfg;
+    const int H = cfg.n_heads, KV = cfg.n_kv_heads, hd = cfg.head_dim, n_rep = H / KV, li = l.layer;
+    const uint32_t vocab = (uint32_t)cfg.vocab;
+    const uint64_t cstride = cache_elems;
+    const int32_t advance = a.advance ? 1 : 0;
+    const step_state* state = c.ragged ? rows : st; // the lockstep kernels read the shared state, their _rows forms row r's own
+    const sampler_params& sp = c.sp;
+    // a verify call's tables and results on the device: the segments, picks[M] and (a tree) paths[B][MC_VERIFY_MAX_LEN] behind accepted[B], next_tokens[B]
+    const pp_seg* segs = c.M ? (const pp_seg*)pp_segs(pp_tab) : nullptr;
+    int32_t* picks = c.M ? vs.out + 2 * B : nullptr;
+    const int32_t* paths = c.tree ? picks + c.M : nullptr;
+    switch (l.op) {
+    case op::begin_lockstep: return set_pos(a.pos);
+    case op::begin_rows:
+        return launch(l.L, pack(rows, (const int32_t*)stop_dev, (int32_t)stop_host.size(), (int32_t)cfg.max_seq_len, (int32_t)B, advance));
+    case op::begin_rolling:
+        return launch(l.L, pack(rows, (const int32_t*)stop_dev, (int32_t)stop_host.size(), (int32_t)cfg.max_seq_len, (int32_t)p.pre_len, advance, rcos, rsin,
+                                (uint32_t)hd, cfg.rope_theta));
+    case op::embed:
+    case op::embed_rows: {
+        const bool q8 = p.emb_fmt != MC_WFMT_T;
+        const void* emb = q8 ? nullptr : p.emb_table;
+        const void* emb_q8 = q8 ? p.emb_table : nullptr;
+        if (l.op == op::embed_rows) return launch(l.L, pack(emb, p.emb_scales, emb_q8, x, rows, (uint32_t)cfg.dim));
+        return launch(l.L, pack(emb, p.emb_scales, emb_q8, x, rows, (uint32_t)cfg.dim, advance, (uint32_t)B));
+    }
+    case op::attn_norm: return launch(l.L, pack((const void*)x, p.layers[li].attention_norm, xn, (uint32_t)cfg.dim, cfg.norm_eps));
+    case op::ffn_norm: return launch(l.L, pack((const void*)x, p.layers[li].ffn_norm, xn, (uint32_t)cfg.dim, cfg.norm_eps));
+    case op::final_norm: return launch(l.L, pack((const void*)x, p.final_norm, xn, (uint32_t)cfg.dim, cfg.norm_eps));
+    case op::qkv_adaptor:
+    case op::qkv_gemv: return gemv(l.L, l.op == op::qkv_adaptor, p.layers[li].qkv, xn, qkv, (uint32_t)p.layers[li].qkv.out);
+    case op::wo_adaptor:
+    case op::wo_gemv: return gemv(l.L, l.op == op::wo_adaptor, p.layers[li].wo, att, x, (uint32_t)cfg.dim);
+    case op::w13_adaptor:
+    case op::w13_gemv: return gemv(l.L, l.op == op::w13_adaptor, p.layers[li].w13, xn, gate, (uint32_t)(p.layers[li].w13.out / 2));
+    case op::w2_adaptor:
+    case op::w2_gemv: return gemv(l.L, l.op == op::w2_adaptor, p.layers[li].w2, gate, x, (uint32_t)cfg.dim);
+    case op::head_gemv: return gemv(l.L, false, p.output, xn, logits, vocab);
+    case op::rope:
+        return launch(l.L, pack(qkv, q, (void*)kc_of(li, 0), (void*)vt_of(li, 0), c.rolling ? rcos : fcos, c.rolling ? rsin : fsin, state, (uint32_t)H, (uint32_t)KV,
+                                (uint32_t)hd, (uint32_t)cfg.max_seq_len, cstride));
+    case op::scores: // T(attn_scale): the scalar_mul of attention.h:196 is evaluated in T
+        return launch(l.L, pack(q, (void*)kc_of(li, 0), expv, psum, state, (uint32_t)n_rep, (uint32_t)hd, (uint32_t)cfg.max_seq_len, round_bf_host(cfg.attn_scale),
+                                (uint32_t)fx.nsplit, cstride));
+    case op::pv:
+        return launch(l.L, pack(expv, psum, (void*)vt_of(li, 0), att, state, (uint32_t)n_rep, (uint32_t)hd, (uint32_t)cfg.max_seq_len, (uint32_t)fx.nsplit, cstride));
+    case op::process:
+    case op::process_rows:
+    case op::process_rows_count: { // count: the rows with penalties count their input token first (a step; the packed passes count nothing)
+        arg_pack args = pack(logits, vocab, (const row_logits*)logits_tab_dev, (const uint32_t*)masks_dev, counts_dev, (const step_state*)rows);
+        if (l.op != op::process) args.push((int32_t)(l.op == op::process_rows_count ? 1 : 0));
+        return launch(l.L, std::move(args));
+    }
+    case op::argmax: return launch(l.L, pack(logits, vocab, rows, tokens_dev));
+    case op::candidates: return launch(l.L, pack(logits, vocab, sp.kpad, cand, c.chunk));
+    case op::sample: return launch(l.L, pack(cand, sp, seeds, (uint32_t)n_seed_pairs, rows, tokens_dev));
+    case op::candidates_mixed:
+        return launch(l.L, pack(logits, vocab, sp.kpad, cand, c.chunk, (const row_sampler*)samplers_dev, (const step_state*)rows, (int32_t)(c.ragged ? 1 : 0)));
+    case op::pick_mixed:
+        return launch(l.L, pack(logits, vocab, (const uint64_t*)cand, (const row_sampler*)samplers_dev, sp.nlists, sp.kpad, sp.cap, (const uint64_t*)seeds,
+                                (uint32_t)n_seed_pairs, rows, tokens_dev));
+    case op::logprob_parts:
+    case op::logprob_finish: { // token and slot from the rows' state, or (a verify call) from picks[m] and m
+        const void* rows_logits = c.M ? vs.logits : logits;
+        const step_state* from = c.M ? nullptr : rows;
+        const int32_t* from_picks = c.M ? picks : nullptr;
+        const logprob_records& r = c.M ? vs.records : records;
+        const uint32_t top = (uint32_t)logprobs_top, nslots = c.M ? (uint32_t)c.M : (uint32_t)(records.count * B);
+        if (l.op == op::logprob_parts) return launch(l.L, pack(rows_logits, vocab, top, lp_parts, lp_keys, from));
+        return launch(l.L, pack(rows_logits, vocab, top, c.lp_nchunk, (const logprob_part*)lp_parts, (const uint64_t*)lp_keys, from, from_picks, nslots, r.tok, r.ids,
+                                r.top));
+    }
+    case op::v_norm: return launch(l.L, pack(a.xrows, p.final_norm, vs.xn, (uint32_t)cfg.dim, cfg.norm_eps));
+    case op::v_head: {
+        const batch_linear& L = p.output;
+        return launch(l.L, pack(L.w, L.scales, (const void*)vs.xn, vs.logits, (uint32_t)L.in, (uint32_t)L.ngroups, (uint32_t)L.group, (uint32_t)c.M, (uint32_t)L.out,
+                                vocab));
+    }
+    case op::v_process:
+        return launch(l.L, pack(vs.logits, vocab, (const verify_row*)vs.tab, (const row_logits*)logits_tab_dev, (const uint32_t*)masks_dev, (const int32_t*)counts_dev,
+                                a.ids));
+    case op::v_argmax: return launch(l.L, pack((const void*)vs.logits, vocab, picks));
+    case op::v_candidates: return launch(l.L, pack((const void*)vs.logits, vocab, sp.kpad, vs.cand, c.chunk, (const verify_row*)vs.tab));
+    case op::v_sample:
+        return launch(l.L, pack((const void*)vs.logits, vocab, (const uint64_t*)vs.cand, (const verify_row*)vs.tab, sp.nlists, sp.kpad, sp.cap, (const uint64_t*)seeds,
+                                (uint32_t)n_seed_pairs, picks));
+    case op::v_accept: return launch(l.L, pack(segs, a.ids, (const int32_t*)picks, (const void*)vs.logits, vocab, vs.out, vs.out + B, logits));
+    case op::v_tree_accept:
+        return launch(l.L, pack(segs, a.ids, a.nodes, (const int32_t*)picks, (const void*)vs.logits, vocab, vs.out, vs.out + B, (int32_t*)paths, logits));
+    case op::v_count:
+        return launch(l.L, pack(segs, a.ids, (const int32_t*)vs.out, paths, (const row_logits*)logits_tab_dev, counts_dev, vocab));
+    case op::v_compact:
+        return launch(l.L, pack(segs, (const int32_t*)vs.out, paths, kc, vt, (uint64_t)cache_elems, (uint32_t)B, (uint32_t)cfg.n_kv_heads, (uint32_t)cfg.head_dim,
+                                (uint32_t)cfg.max_seq_len));
+    }
+    return fail(MC_ERR_RUNTIME, "mc_batch: a launch without an executor");
+}
+
+// the list from front to back -- a token: the fixed body first --, up to the first launch that fails
+mc_status
+mc_batch::run_all(const call_args& a)
+{
+    if (a.plan.body)
+        for (const batch_launch& l : *a.plan.body)
+            if (mc_status s = run(l, a); s != MC_OK) return s;
+    for (const batch_launch& l : a.plan.launches)
+        if (mc_status s = run(l, a); s != MC_OK) return s;
+    return MC_OK;
 }
 
 namespace {
@@ -238,6 +270,20 @@ finish(mc_batch* b, int32_t start_pos, const int32_t* positions, int32_t n, int3
     return MC_OK;
 }
 
+// the four step / generate calls behind their checks: ONE token planned, once; everything reserved and sent; the rows (positions given: a ragged
+// call, with its stop ids); the same list for each of the n tokens -- the position and the advance word are arguments, not plan --; the tail
+mc_status
+run_tokens(mc_batch* b, const int32_t* tokens, int32_t start_pos, const int32_t* positions, int32_t n, const int32_t* stop_ids, int32_t n_stop, int32_t* tokens_out,
+           int32_t* produced = nullptr)
+{
+    MC_HIP(hipSetDevice(b->p.ordinal));
+    const batch_call_plan plan = plan_batch_token(b->fx, b->settings(), positions != nullptr);
+    mc_status s = b->prepare(plan, n);
+    if (s == MC_OK) s = positions ? start_ragged(b, tokens, positions, stop_ids, n_stop, n) : start_rows(b, tokens);
+    for (int i = 0; i < n && s == MC_OK; i++) s = b->run_all({plan, start_pos + i, i > 0});
+    return s != MC_OK ? s : finish(b, start_pos, positions, n, tokens_out, produced);
+}
+
 // mc_batch_create and mc_wide_batch_create: `who` names the caller in the texts, `cap` is its largest batch, `wide` its admission
 mc_status
 batch_create(const std::string& who, int cap, bool wide, mc_decoder* d, int32_t batch, mc_batch** out)
@@ -252,9 +298,11 @@ batch_create(const std::string& who, int cap, bool wide, mc_decoder* d, int32_t 
     if (!why.empty()) return fail(MC_ERR_INVALID_ARGUMENT, who + ": " + why);
     MC_HIP(hipSetDevice(parts.ordinal));
     std::unique_ptr<mc_batch> b(new mc_batch);
-    b->genv.B = batch;
-    MC_HIP(hipDeviceGetAttribute(&b->genv.cus, hipDeviceAttributeMultiprocessorCount, parts.ordinal));
-    b->genv.tiles_env = wb_tiles_env_of(getenv("MC_WB_TILES"));
+    batch_env env;
+    env.B = batch;
+    MC_HIP(hipDeviceGetAttribute(&env.cus, hipDeviceAttributeMultiprocessorCount, parts.ordinal));
+    env.tiles_env = wb_tiles_env_of(getenv("MC_WB_TILES"));
+    b->fx = fix_batch(parts, env);
     b->d = d;
     b->p = parts;
     b->B = batch;
@@ -263,17 +311,9 @@ batch_create(const std::string& who, int cap, bool wide, mc_decoder* d, int32_t 
     b->row_logit_set.assign(batch, row_logit_setting{});
     const mc_decoder_config& c = parts.cfg;
     const int H = c.n_heads, KV = c.n_kv_heads, hd = c.head_dim, L = (int)parts.layers.size();
-    b->nsplit = (c.max_seq_len + PB - 1) / PB;
-    for (const batch_layer& l : parts.layers)
-        b->gemvs.push_back({plan_batch_gemv(l.qkv, 0, b->genv), plan_batch_gemv(l.wo, 1, b->genv), plan_batch_gemv(l.w13, 2, b->genv),
-                            plan_batch_gemv(l.w2, 1, b->genv)});
-    b->head_gemv = plan_batch_gemv(parts.output, 0, b->genv);
-    for (int form = 0; form < 3; form++) b->steps[form] = plan_step(c, batch, b->nsplit, form > 0, form == 2);
     b->cache_elems = (size_t)KV * c.max_seq_len * hd;
     const size_t cache_bytes = (size_t)L * batch * b->cache_elems * 2;
     const int ffn = parts.layers.empty() ? 0 : parts.layers[0].w13.out / 2;
-    const uint32_t lists512 = ((uint32_t)c.vocab + 511) / 512;
-    b->cand_per_row = (size_t)std::max(lists512, 1u) * 128;
     if ((s = b->alloc(&b->kc, cache_bytes)) != MC_OK || (s = b->alloc(&b->vt, cache_bytes)) != MC_OK ||
         (s = b->alloc(&b->x, (size_t)batch * c.dim * 2)) != MC_OK || (s = b->alloc(&b->xn, (size_t)batch * c.dim * 2)) != MC_OK ||
         (s = b->alloc(&b->qkv, (size_t)batch * (H + 2 * KV) * hd * 2)) != MC_OK ||
@@ -281,13 +321,13 @@ batch_create(const std::string& who, int cap, bool wide, mc_decoder* d, int32_t 
         (s = b->alloc(&b->gate, (size_t)batch * ffn * 2)) != MC_OK ||
         (s = b->alloc(&b->logits, (size_t)batch * c.vocab * 2)) != MC_OK ||
         (s = b->alloc(&b->expv, sizeof(float) * batch * H * c.max_seq_len)) != MC_OK ||
-        (s = b->alloc(&b->psum, sizeof(float) * batch * H * b->nsplit)) != MC_OK ||
+        (s = b->alloc(&b->psum, sizeof(float) * batch * H * b->fx.nsplit)) != MC_OK ||
         (s = b->alloc(&b->fcos, sizeof(float) * c.max_seq_len * (hd / 2))) != MC_OK ||
         (s = b->alloc(&b->fsin, sizeof(float) * c.max_seq_len * (hd / 2))) != MC_OK ||
         (s = b->alloc(&b->rcos, sizeof(float) * batch * (hd / 2))) != MC_OK ||
         (s = b->alloc(&b->rsin, sizeof(float) * batch * (hd / 2))) != MC_OK ||
         (s = b->alloc(&b->st, sizeof(step_state))) != MC_OK || (s = b->alloc(&b->rows, sizeof(step_state) * batch)) != MC_OK ||
-        (s = b->alloc(&b->cand, sizeof(uint64_t) * batch * b->cand_per_row)) != MC_OK ||
+        (s = b->alloc(&b->cand, sizeof(uint64_t) * batch * b->fx.cand_per_row)) != MC_OK ||
         (s = b->alloc(&b->samplers_dev, sizeof(row_sampler) * batch)) != MC_OK)
         return s;
     for (const batch_layer& l : parts.layers)
@@ -338,11 +378,7 @@ mc_batch_step(mc_batch* b, const int32_t* tokens, int32_t start_pos, int32_t* ne
     if (!b || !tokens) return fail(MC_ERR_INVALID_ARGUMENT, "mc_batch_step: null argument");
     mc_status s;
     if ((s = refuse(step_bounds(start_pos, b->p.cfg.max_seq_len))) != MC_OK || (s = refuse(check_tokens(tokens, b->B, b->p.cfg.vocab))) != MC_OK) return s;
-    MC_HIP(hipSetDevice(b->p.ordinal));
-    if ((s = b->plan_call(false)) != MC_OK || (s = b->ensure_tokens(1)) != MC_OK || (s = b->begin_logprobs(1)) != MC_OK || (s = start_rows(b, tokens)) != MC_OK ||
-        (s = b->enqueue_token(start_pos, false)) != MC_OK)
-        return s;
-    return finish(b, start_pos, nullptr, 1, next_tokens);
+    return run_tokens(b, tokens, start_pos, nullptr, 1, nullptr, 0, next_tokens);
 }
 
 mc_status
@@ -353,11 +389,7 @@ mc_batch_generate(mc_batch* b, const int32_t* first_tokens, int32_t start_pos, i
     mc_status s;
     if ((s = refuse(generate_bounds(start_pos, n, b->p.cfg.max_seq_len))) != MC_OK || (s = refuse(check_tokens(first_tokens, b->B, b->p.cfg.vocab))) != MC_OK)
         return s;
-    MC_HIP(hipSetDevice(b->p.ordinal));
-    if ((s = b->plan_call(false)) != MC_OK || (s = b->ensure_tokens(n)) != MC_OK || (s = b->begin_logprobs(n)) != MC_OK || (s = start_rows(b, first_tokens)) != MC_OK) return s;
-    for (int i = 0; i < n; i++)
-        if ((s = b->enqueue_token(start_pos + i, i > 0)) != MC_OK) return s;
-    return finish(b, start_pos, nullptr, n, tokens_out);
+    return run_tokens(b, first_tokens, start_pos, nullptr, n, nullptr, 0, tokens_out);
 }
 
 mc_status
@@ -379,12 +411,7 @@ mc_ragged_step(mc_batch* b, const int32_t* tokens, const int32_t* positions, int
     const mc_decoder_config& c = b->p.cfg;
     mc_status s = refuse(check_ragged("mc_ragged_step", tokens, positions, 1, b->lengths.data(), b->B, c.max_seq_len, c.vocab, b->rolling));
     if (s != MC_OK) return s;
-    MC_HIP(hipSetDevice(b->p.ordinal));
-    if ((s = b->plan_call(true)) != MC_OK || (s = b->ensure_tokens(1)) != MC_OK || (s = b->begin_logprobs(1)) != MC_OK ||
-        (s = start_ragged(b, tokens, positions, nullptr, 0, 1)) != MC_OK ||
-        (s = b->enqueue_token(0, false)) != MC_OK)
-        return s;
-    return finish(b, 0, positions, 1, next_tokens);
+    return run_tokens(b, tokens, 0, positions, 1, nullptr, 0, next_tokens);
 }
 
 mc_status
@@ -398,13 +425,7 @@ mc_ragged_generate(mc_batch* b, const int32_t* first_tokens, const int32_t* posi
     const mc_decoder_config& c = b->p.cfg;
     mc_status s = refuse(check_ragged("mc_ragged_generate", first_tokens, positions, n, b->lengths.data(), b->B, c.max_seq_len, c.vocab, b->rolling));
     if (s != MC_OK) return s;
-    MC_HIP(hipSetDevice(b->p.ordinal));
-    if ((s = b->plan_call(true)) != MC_OK || (s = b->ensure_tokens(n)) != MC_OK || (s = b->begin_logprobs(n)) != MC_OK ||
-        (s = start_ragged(b, first_tokens, positions, stop_ids, n_stop, n)) != MC_OK)
-        return s;
-    for (int i = 0; i < n; i++)
-        if ((s = b->enqueue_token(0, i > 0)) != MC_OK) return s;
-    return finish(b, 0, positions, n, tokens_out, lengths);
+    return run_tokens(b, first_tokens, 0, positions, n, stop_ids, n_stop, tokens_out, lengths);
 }
 
 mc_status

@@ -20,23 +20,28 @@
 // Part 2k (mc_row_sampler_*): a row slot may pick with settings of its own in place of the decoder's; plan_head() resolves every row's
 // effective sampler and keeps the uniform launches wherever the rows agree.
 // Part 2l (mc_row_mask_*, mc_row_penalty_*, mc_row_logits_reset): a row slot may carry a token mask and repetition / frequency /
-// presence penalties; head() then puts ONE launch (logit_kernels.hip) between the head GEMV and the pick, which rewrites the logits
+// presence penalties; the plan then puts ONE launch (logit_kernels.hip) between the head GEMV and the pick, which rewrites the logits
 // of those rows in place.  A batch on which no row has either launches what it launched before.
 // Part 2m (mc_settings_verify_set): opt-in per batch, the two verify calls take rows that sample or carry a mask or penalties;
-// verify_head() then runs process -> pick -> accept -> count over the packed rows (plan_verify_pick, plan_verify_logits).
-// Part 2n (mc_logprobs_set): opt-in per batch, two launches (logprob_kernels.hip) behind every pick -- head()'s three forms and verify_head()'s --
+// the head of the call then runs process -> pick -> accept -> count over the packed rows (plan_verify_pick, plan_verify_logits).
+// Part 2n (mc_logprobs_set): opt-in per batch, two launches (logprob_kernels.hip) behind every pick -- a token's three forms and a verify call's --
 // record the pick's log-probability and the top_n most likely tokens.  With the switch off a batch launches and holds what it did before.
 //
 // WHAT is launched -- names, grids, blocks, LDS bytes, the admission and every check of a call that needs no device -- is decided in
-// batch_plan.h, without HIP.  This header is struct mc_batch as its four units see it: the state, the allocator, the launch path and the
-// small helpers every unit calls inline.  Which unit defines what:
-//   batch.cc           creation and release, one token (gemv, enqueue_token, head), the lockstep and ragged entry points
-//   batch_rows.cc      the rows passes: rows_pass, verify_head, mc_rows_prefill / mc_extend_rows / mc_verify_rows / mc_tree_verify
+// batch_plan.h, and IN WHICH ORDER in batch_call_plan.h: an entry point plans its whole call once (plan_batch_token, plan_rows_tail,
+// plan_verify_call), prepare() reserves and uploads what the plan names in front of the first launch, and run() -- one switch over the op tag, the
+// only place that packs a batch launch's arguments -- executes the list (the n tokens of a generate call: the same list n times).  Both headers are
+// without HIP.  This header is struct mc_batch as its four units see it: the state, the allocator, the launch path and the small helpers every
+// unit calls inline.  Which unit defines what:
+//   batch.cc           creation and release, prepare and run, the log-probability records, the lockstep and ragged entry points
+//   batch_rows.cc      the rows passes: rows_pass (check, tables, plan, prepare, prompt pass, run, read back) behind mc_rows_prefill /
+//                      mc_extend_rows / mc_verify_rows / mc_tree_verify
 //   batch_cache.cc     a row's cache: fork, import, the exports, mc_rolling_*
 //   batch_settings.cc  what a row slot carries between calls: seeds, row samplers, row logit processors; the log-probability switch and mc_logprobs_get
 #pragma once
 
 #include "bf16_host.h"
+#include "batch_call_plan.h"
 #include "decoder_batch.h"
 
 #include <algorithm>
@@ -45,11 +50,57 @@
 #include <cstring>
 #include <memory>
 
+namespace mcimpl {
+
+// Part 2n: the log-probability records of a call on the device -- tok [slots], ids / top [slots][top_n] -- with their capacities in slots
+struct logprob_records {
+    float *tok = nullptr, *top = nullptr;
+    int32_t* ids = nullptr;
+    int tok_cap = 0, top_cap = 0, ids_cap = 0;
+    int count = 0; // of the last call with records: its n (a step, generate or packed call) or its packed rows (a verify call); 0: none yet
+    // mc_logprobs_set: what an earlier setting recorded is gone; the records are laid out by top_n, so another one reserves them anew
+    void
+    forget(bool layout_changed)
+    {
+        if (layout_changed) ids_cap = top_cap = 0;
+        count = 0;
+    }
+};
+
+// mc_verify_rows and mc_tree_verify, all reserved at the first call that needs it: the normed rows [128][dim], their logits [128][vocab], and the
+// call's results on the device: accepted[B], next_tokens[B], picks[M], then (mc_tree_verify) paths[B][MC_VERIFY_MAX_LEN]; with row settings
+// (Part 2m) the per-packed-row table and the candidate keys [MC_VERIFY_MAX_ROWS][cand_per_row]; with log-probabilities a record per packed row
+struct verify_state {
+    void *xn = nullptr, *logits = nullptr;
+    int32_t* out = nullptr;
+    int xn_cap = 0, logits_cap = 0, out_cap = 0;
+    int rows = 0; // packed rows of the last mc_verify_rows / mc_tree_verify call (0: none yet)
+    std::vector<int32_t> host;
+    verify_row* tab = nullptr;
+    std::vector<verify_row> tab_sent;
+    int tab_cap = 0;
+    uint64_t* cand = nullptr;
+    int cand_cap = 0; // (packed rows)
+    logprob_records records;
+};
+
+// what changes between the launches of one plan: the lockstep position and the advance word of a token; of a verify call the packed rows behind
+// the last layer, the call's ids and (a tree) its node table, all on the device
+struct call_args {
+    const batch_call_plan& plan;
+    int pos = 0;
+    bool advance = false;
+    const void* xrows = nullptr;
+    const int32_t* ids = nullptr;
+    const tv_node* nodes = nullptr;
+};
+
+} // namespace mcimpl
+
 struct mc_batch {
     mcimpl::decoder_parts p;
     mc_decoder* d = nullptr;
     int B = 0;
-    int nsplit = 0;
     size_t cache_elems = 0; // one row's cache of one layer: n_kv * max_seq * hd
     std::vector<void*> allocs;
     void *kc = nullptr, *vt = nullptr;    // [layer][B][n_kv][max_seq][hd], [layer][B][n_kv][hd][max_seq]
@@ -61,14 +112,13 @@ struct mc_batch {
                                           // scratch for all linears: every launch goes to the decoder's one stream, in order
     int lora_ld = 0;                      // the most lora_cols of any linear
     void *logits = nullptr;               // [B][vocab]
-    float *expv = nullptr, *psum = nullptr; // [B][H][max_seq], [B][H][nsplit]
+    float *expv = nullptr, *psum = nullptr; // [B][H][max_seq], [B][H][fx.nsplit]
     float *fcos = nullptr, *fsin = nullptr; // rope table rows [0, max_seq)
     float *rcos = nullptr, *rsin = nullptr; // [B][hd / 2]: a rolling batch's rope row of each row, written by every step's first launch
     bool rolling = false;                   // mc_rolling_set
     mcimpl::step_state* st = nullptr;     // the shared position
     mcimpl::step_state* rows = nullptr;   // [B]: token and step_index of each row (ragged calls: the whole state of each row)
-    uint64_t* cand = nullptr;             // [B][lists * kpad]
-    size_t cand_per_row = 0;
+    uint64_t* cand = nullptr;             // [B][fx.cand_per_row]
     uint64_t* seeds = nullptr;
     int n_seed_pairs = 0, seed_cap = 0;   // (capacity in pairs)
     int32_t* tokens_dev = nullptr;
@@ -88,24 +138,10 @@ struct mc_batch {
     std::vector<mcimpl::px_group> px_groups;
     float *px_sums = nullptr, *px_part = nullptr; // scratch of one launch group: [px_slots][H][16], [px_slots][H][16][hd]
     int px_slots = 0;
-    // mc_verify_rows and mc_tree_verify, reserved at the first call: the normed rows [128][dim], their logits [128][vocab], and the
-    // call's results on the device: accepted[B], next_tokens[B], picks[M], then (mc_tree_verify) paths[B][MC_VERIFY_MAX_LEN]
-    void *v_xn = nullptr, *v_logits = nullptr;
-    int32_t* v_out = nullptr;
-    int v_xn_cap = 0, v_logits_cap = 0, v_out_cap = 0;
-    int v_rows = 0;                       // packed rows of the last mc_verify_rows / mc_tree_verify call (0: none yet)
-    std::vector<int32_t> v_host;
-    // Part 2m (mc_settings_verify_set): with the switch on the verify calls take sampling, masked and penalised rows.  The plans of the call
-    // in flight (batch_plan.h plan_verify_pick / plan_verify_logits), the per-packed-row table on the device and the candidate keys
-    // [MC_VERIFY_MAX_ROWS][cand_per_row], both reserved at the first call that needs them: a batch that never verifies such a row holds
-    // what it held
+    // mc_verify_rows and mc_tree_verify (verify_state above); Part 2m's switch (mc_settings_verify_set): the two calls take sampling, masked and
+    // penalised rows
+    mcimpl::verify_state vs;
     bool verify_settings_on = false;
-    mcimpl::verify_pick_plan v_pick;
-    mcimpl::verify_logits_plan v_lp;
-    mcimpl::verify_row* v_tab = nullptr;
-    int v_tab_cap = 0;
-    uint64_t* v_cand = nullptr;
-    int v_cand_cap = 0; // (packed rows)
     // Part 2k: the sampler of each row slot as mc_row_sampler_set took it, the table of effective settings the mixed launches read
     // (plan_head resolves it), and what of it the device holds
     std::vector<mcimpl::row_setting> row_samplers; // [B]
@@ -121,36 +157,18 @@ struct mc_batch {
     mcimpl::row_logits* logits_tab_dev = nullptr;
     std::vector<mcimpl::row_logits> logits_tab_sent;
     // Part 2n (mc_logprobs_set): with the switch on, two launches behind every pick record the pick's log-probability and the top_n most
-    // likely tokens (plan_logprobs).  Beside tokens_dev and indexed like it: lp_tok [n][B], lp_ids / lp_top [n][B][top_n], filled with 0xFF
-    // where tokens_dev is filled (a slot without a record: NaN bits, id -1); their [MC_VERIFY_MAX_ROWS] twins for the verify calls; the parts
-    // and chunk keys of the launches in flight.  All reserved at the first call that needs them: a batch that never asks holds what it held
+    // likely tokens (plan_logprobs): `records` beside tokens_dev and indexed like it, vs.records per packed row of a verify call; the parts and chunk keys
+    // of the launches in flight.  All reserved at the first call that needs them: a batch that never asks holds what it held
     bool logprobs_on = false;
     int logprobs_top = 0;
-    mcimpl::logprobs_plan lpp, v_lpp;     // of the call in flight (plan_pick; a verify call: rows_pass)
-    float *lp_tok = nullptr, *lp_top = nullptr;
-    int32_t* lp_ids = nullptr;
-    int lp_tok_cap = 0, lp_top_cap = 0, lp_ids_cap = 0; // (slots)
-    int lp_n = 0;                         // n of the last step, generate or packed call with records (0: none yet)
-    float *v_lp_tok = nullptr, *v_lp_top = nullptr;
-    int32_t* v_lp_ids = nullptr;
-    int v_lp_tok_cap = 0, v_lp_top_cap = 0, v_lp_ids_cap = 0;
-    int v_lp_rows = 0;                    // packed rows of the last verify call with records (0: none yet)
+    mcimpl::logprob_records records;         // count: n of the last step, generate or packed call with records
     mcimpl::logprob_part* lp_parts = nullptr;
     uint64_t* lp_keys = nullptr;
     int lp_parts_cap = 0, lp_keys_cap = 0; // (rows)
-    // The plans (batch_plan.h).  Fixed at creation: B, the device's compute units and MC_WB_TILES, both read once there (genv); the GEMV of
-    // every matrix; the launches of a step, lockstep / ragged / ragged on a rolling batch.  Of the call in flight (plan_call, plan_pick):
-    // its step, the rows' logit processors and the pick -- the settings cannot change inside a call
-    mcimpl::batch_env genv;
-    struct layer_gemvs {
-        mcimpl::batch_gemv_plan qkv, wo, w13, w2;
-    };
-    std::vector<layer_gemvs> gemvs;
-    mcimpl::batch_gemv_plan head_gemv;
-    mcimpl::step_plan steps[3];
-    const mcimpl::step_plan* step = nullptr;
-    mcimpl::logits_plan lp;
-    mcimpl::head_plan pick;
+    // The plans fixed at creation (batch_call_plan.h batch_fixed): B, the device's compute units and MC_WB_TILES, both read once there; the GEMV
+    // of every matrix; the launches of a step, lockstep / ragged / ragged on a rolling batch.  The plan of a call is the entry point's own
+    // (plan_batch_token, plan_rows_tail, plan_verify_call with settings()) and goes down by const&: the settings cannot change inside a call
+    mcimpl::batch_fixed fx;
 
     ~mc_batch()
     {
@@ -237,25 +255,26 @@ struct mc_batch {
     mc_status
     set_pos(int pos)
     {
-        return launch(steps[0].begin, mcimpl::pack(st, (int32_t)-1, (int32_t)pos, (int32_t)p.cfg.max_seq_len, (int32_t)p.pre_len, (int32_t)0, (int32_t)1));
+        return launch(fx.steps[0].begin, mcimpl::pack(st, (int32_t)-1, (int32_t)pos, (int32_t)p.cfg.max_seq_len, (int32_t)p.pre_len, (int32_t)0, (int32_t)1));
     }
 
-    // ---------------------------------------------------------------- one token (batch.cc)
-    mc_status gemv(const mcimpl::batch_linear& L, const mcimpl::batch_gemv_plan& g, const void* xin, void* y, uint32_t ldy);
-    // the plans of a call: its step (plan_call), and the rows' logit processors and pick, with their tables sent (plan_pick: a rows pass)
-    mc_status plan_call(bool ragged);
-    mc_status plan_pick(bool ragged);
-    mc_status enqueue_token(int pos, bool advance);
-    mc_status head(bool ragged, bool count);
-    mc_status process_logits(bool ragged, bool count);
-    // Part 2n: the records of a call of n tokens, reserved and filled (nothing while the switch is off); the scratch of the two launches for R
-    // rows; the launches themselves over the rows of `rows_logits`, token and slot from `state` or (state null) from picks[m] and m
-    mc_status begin_logprobs(int n);
-    mc_status reserve_logprob_scratch(int R);
-    mc_status enqueue_logprobs(const mcimpl::logprobs_plan& l, const void* rows_logits, const mcimpl::step_state* state, const int32_t* picks, uint32_t nslots,
-                               float* out_tok, int32_t* out_ids, float* out_top);
-    // ---------------------------------------------------------------- the rows passes (batch_rows.cc)
-    mc_status verify_head(const void* xrows, const int32_t* tokens, int M, int nseg, const mcimpl::tv_node* nodes = nullptr);
+    mcimpl::call_settings
+    settings() const
+    {
+        return {rolling, verify_settings_on, logprobs_on, logprobs_top, n_seed_pairs, mcimpl::decoder_sampler_of(d), row_samplers, row_logit_set};
+    }
+
+    // ---------------------------------------------------------------- one call (batch.cc)
+    // everything of a planned call in front of its first launch: its refusal, the n x B tokens, the log-probability records and scratch, the
+    // packed rows' buffers of a verify call, the tables sent
+    mc_status prepare(const mcimpl::batch_call_plan& c, int n);
+    // ONE launch of the plan: the op's arguments bound (the only place that packs them), and the list from front to back
+    mc_status run(const mcimpl::batch_launch& l, const mcimpl::call_args& a);
+    mc_status gemv(const mcimpl::launch_plan& l, bool adaptor, const mcimpl::batch_linear& L, const void* xin, void* y, uint32_t ldy);
+    mc_status run_all(const mcimpl::call_args& a);
+    // Part 2n: `slots` records, reserved and filled with 0xFF (a slot no pick reaches reads as NaN bits, id -1); the records copied out
+    mc_status begin_records(mcimpl::logprob_records& r, int slots, int cap);
+    mc_status copy_records(const mcimpl::logprob_records& r, size_t slots, float* tok, int32_t* ids, float* top);
 };
 
 namespace mcimpl {

@@ -5,8 +5,9 @@
 // call (plan_verify_head; with row settings: plan_verify_pick, plan_verify_logits), and the checks of a call that need no device
 // (check_ragged, check_tokens, step_bounds / generate_bounds, verify_samplers, verify_logit_rows, check_row).  Plain integer arithmetic over config
 // words, a linear's shape and kernels/abi.h constants -- no HIP, no mc_decoder, no device pointers -- so tests/cpp/test_batch_plan.cc pins names,
-// grids, blocks and LDS bytes on the CPU against a recording of the launches (tests/golden/batch_plans.json).  The batch's units launch what these
-// say and bind the arguments; fail(), the allocations, the uploads and the stream stay there.  A refusal is a text here, "" = none.
+// grids, blocks and LDS bytes on the CPU against a recording of the launches (tests/golden/batch_plans.json).  batch_call_plan.h composes these pieces
+// into the ordered list of a whole call; the batch's units run that list and bind the arguments; fail(), the allocations, the uploads and the
+// stream stay there.  A refusal is a text here, "" = none.
 #pragma once
 
 #include <algorithm>
@@ -211,6 +212,13 @@ sampler_of_row(const row_setting& rs, const decoder_sampler& dec)
     e.top_p_T = rs.top_p_T;
     return e;
 }
+// an effective sampler as the mixed launches read it (abi.h row_sampler): top_k capped at the vocabulary, a greedy row all zeros
+inline row_sampler
+row_sampler_of(const decoder_sampler& e, int vocab)
+{
+    if (e.kind == MC_SAMPLER_GREEDY) return row_sampler{ROW_SAMPLER_GREEDY, 0u, 0.0f, 0.0f};
+    return row_sampler{e.kind == MC_SAMPLER_DRAW ? ROW_SAMPLER_DRAW : ROW_SAMPLER_DEFAULT, (uint32_t)std::min(e.top_k, vocab), e.inv_temp_T, e.top_p_T};
+}
 
 // (sampler_plan, the two launches of make_default_sampler for given settings: sampler_plan.h)
 
@@ -244,8 +252,7 @@ plan_head(const std::vector<row_setting>& rows, const decoder_sampler& dec, int 
     for (unsigned r = 0; r < B; r++) {
         const decoder_sampler e = sampler_of_row(rows[r], dec);
         const bool samples = e.kind != MC_SAMPLER_GREEDY;
-        h.table[r] = samples ? row_sampler{e.kind == MC_SAMPLER_DRAW ? ROW_SAMPLER_DRAW : ROW_SAMPLER_DEFAULT, (uint32_t)std::min(e.top_k, vocab), e.inv_temp_T, e.top_p_T}
-                             : row_sampler{ROW_SAMPLER_GREEDY, 0u, 0.0f, 0.0f};
+        h.table[r] = row_sampler_of(e, vocab);
         if (r > 0 && memcmp(&h.table[r], &h.table[0], sizeof(row_sampler)) != 0) alike = false;
         if (!samples) continue;
         sampling++;
@@ -400,8 +407,7 @@ plan_verify_pick(const int32_t* lens, const std::vector<row_setting>& rows, cons
         if (lens[r] <= 0) continue;
         const decoder_sampler e = sampler_of_row(rows[r], dec);
         const bool samples = e.kind != MC_SAMPLER_GREEDY;
-        const row_sampler rs = samples ? row_sampler{e.kind == MC_SAMPLER_DRAW ? ROW_SAMPLER_DRAW : ROW_SAMPLER_DEFAULT, (uint32_t)std::min(e.top_k, vocab), e.inv_temp_T, e.top_p_T}
-                                       : row_sampler{ROW_SAMPLER_GREEDY, 0u, 0.0f, 0.0f};
+        const row_sampler rs = row_sampler_of(e, vocab);
         if (samples && v.greedy) first_sampling = e;
         if (samples) v.greedy = false, top_k_max = std::max(top_k_max, e.top_k);
         for (int32_t j = 0; j < lens[r]; j++) {

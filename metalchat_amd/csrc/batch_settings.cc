@@ -219,11 +219,9 @@ mc_logprobs_set(mc_batch* b, int32_t enable, int32_t top_n)
 {
     if (!b) return fail(MC_ERR_INVALID_ARGUMENT, "mc_logprobs_set: null argument");
     if (mc_status s = refuse(check_logprobs(enable, top_n, b->p.cfg.vocab)); s != MC_OK) return s;
-    if (top_n != b->logprobs_top) // the records are laid out by top_n: the next call reserves them anew
-        b->lp_ids_cap = b->lp_top_cap = b->v_lp_ids_cap = b->v_lp_top_cap = 0;
+    for (logprob_records* r : {&b->records, &b->vs.records}) r->forget(top_n != b->logprobs_top);
     b->logprobs_on = enable == 1;
     b->logprobs_top = top_n;
-    b->lp_n = b->v_lp_rows = 0; // what an earlier setting recorded is gone
     return MC_OK;
 }
 
@@ -240,16 +238,10 @@ mc_logprobs_get(mc_batch* b, int32_t n, float* token_logprobs, int32_t* top_ids,
 {
     if (!b || !token_logprobs) return fail(MC_ERR_INVALID_ARGUMENT, "mc_logprobs_get: null argument");
     if (!b->logprobs_on) return fail(MC_ERR_INVALID_ARGUMENT, "mc_logprobs_get: log-probabilities are switched off (mc_logprobs_set)");
-    if (!b->lp_n) return fail(MC_ERR_INVALID_ARGUMENT, "mc_logprobs_get: no step, generate or packed call with log-probabilities on this batch yet");
-    if (n != b->lp_n) return fail(MC_ERR_INVALID_ARGUMENT, "mc_logprobs_get: n must be the last call's n = " + std::to_string(b->lp_n));
-    const size_t slots = (size_t)n * b->B, top = (size_t)b->logprobs_top;
-    if (top == 0 && (top_ids || top_logprobs)) return fail(MC_ERR_INVALID_ARGUMENT, "mc_logprobs_get: top_n is 0, the top arrays must be null");
-    MC_HIP(hipSetDevice(b->p.ordinal));
-    MC_HIP(hipStreamSynchronize(b->p.stream));
-    MC_HIP(hipMemcpy(token_logprobs, b->lp_tok, sizeof(float) * slots, hipMemcpyDeviceToHost));
-    if (top_ids) MC_HIP(hipMemcpy(top_ids, b->lp_ids, sizeof(int32_t) * slots * top, hipMemcpyDeviceToHost));
-    if (top_logprobs) MC_HIP(hipMemcpy(top_logprobs, b->lp_top, sizeof(float) * slots * top, hipMemcpyDeviceToHost));
-    return MC_OK;
+    if (!b->records.count) return fail(MC_ERR_INVALID_ARGUMENT, "mc_logprobs_get: no step, generate or packed call with log-probabilities on this batch yet");
+    if (n != b->records.count) return fail(MC_ERR_INVALID_ARGUMENT, "mc_logprobs_get: n must be the last call's n = " + std::to_string(b->records.count));
+    if (b->logprobs_top == 0 && (top_ids || top_logprobs)) return fail(MC_ERR_INVALID_ARGUMENT, "mc_logprobs_get: top_n is 0, the top arrays must be null");
+    return b->copy_records(b->records, (size_t)n * b->B, token_logprobs, top_ids, top_logprobs);
 }
 
 } // extern "C"

@@ -95,32 +95,34 @@ def ask(lines):
     return answers
 
 
-def token_launches(cfg, linears, B, *, cus, tiles_env=0, ragged_call=False, rolling=False, dec_sampler=(0, 50, 0.6, 0.9), row_samplers=(), row_logits=()):
-    """the launches of ONE token of a step call, every one taken from the program's plans, put in the order of enqueue_token (batch.cc).
-    That order is RESTATED here, not produced by enqueue_token: a comparison with a recording pins what each plan holds (name, grid, block, LDS),
-    not the order in which batch.cc issues the launches nor which plan it binds to which launch (g.wo against g.w2, say) -- only the launch logs of
-    the GPU tests see that.
-    row_samplers: (row, kind, top_k, temperature, top_p) of the rows that do not inherit; row_logits: (row, masked, rep, freq, pres)"""
-    srows = [(-1, 0, 0.0, 0.0)] * B
+INHERITS, UNSET = (-1, 0, 0.0, 0.0), (0, 1.0, 0.0, 0.0)
+
+
+def token(cfg, linears, B, *, cus, tiles_env=0, ragged_call=False, rolling=False, dec_sampler=(0, 50, 0.6, 0.9), row_samplers=(), row_logits=(), logprobs=None,
+          tail=False):
+    """the request for the ordered launches of ONE token of a step call (tail: of the head behind a prompt pass).
+    row_samplers: (row, kind, top_k, temperature, top_p) of the rows that do not inherit; row_logits: (row, masked, rep, freq, pres); logprobs: top_n"""
+    srows, lrows = [INHERITS] * B, [UNSET] * B
     for r, *s in row_samplers:
         srows[r] = tuple(s)
-    lrows = [(0, 1.0, 0.0, 0.0)] * B
     for r, *s in row_logits:
         lrows[r] = tuple(s)
-    epi = dict(qkv=0, wo=1, w13=2, w2=1, output=0)
-    names = ("qkv", "wo", "w13", "w2", "output")
-    a = ask([step(cfg, B, ragged_call, rolling)] + [gemv(linears[n], epi[n], B, cus, tiles_env) for n in names] +
-            [logits(cfg["vocab"], ragged_call, lrows), head(cfg["vocab"], ragged_call, dec_sampler, srows)])
-    st, g, lp, hp = a[0], dict(zip(names, a[1:6])), a[6], a[7]
-    layer = [st["rmsnorm"]] + g["qkv"]["launches"] + [st["rope"], st["scores"], st["pv"]] + g["wo"]["launches"] + [st["rmsnorm"]] + \
-        g["w13"]["launches"] + g["w2"]["launches"]
-    return [st["begin"], st["embed"]] + layer * cfg["n_layers"] + [st["rmsnorm"]] + g["output"]["launches"] + lp["launches"] + hp["launches"]
+    floats = lambda t, first: [float(x) if i >= first else x for i, x in enumerate(t)]
+    return words("tail" if tail else "token", [cfg[k] for k in ("dim", "n_heads", "n_kv_heads", "head_dim", "n_layers", "vocab", "max_seq_len")], B, cus, tiles_env,
+                 int(ragged_call), int(rolling), *[linears[n] for n in ("qkv", "wo", "w13", "w2", "output")], floats(dec_sampler, 2),
+                 *[floats(r, 2) for r in srows], *[[int(r[0])] + floats(r[1:], 0) for r in lrows], int(logprobs is not None), logprobs or 0)
+
+
+def token_launches(cfg, linears, B, **kw):
+    """the launches of ONE token of a step call as plan_batch_token (batch_call_plan.h) orders them -- the list the batch's executor walks, so a
+    comparison with a recording pins what each launch holds (name, grid, block, LDS), the order, and which plan sits at which place (wo against w2)"""
+    return ask([token(cfg, linears, B, **kw)])[0]["launches"]
 
 
 def head_launches(cfg, linears, B, *, cus, tiles_env=0):
-    """the head of a rows pass (mc_rows_prefill, mc_extend_rows): the final norm, the head GEMV and the ragged pick, no row settings"""
-    a = ask([step(cfg, B, True), gemv(linears["output"], 0, B, cus, tiles_env), head(cfg["vocab"], True, (0, 50, 0.6, 0.9), [(-1, 0, 0.0, 0.0)] * B)])
-    return [a[0]["rmsnorm"]] + a[1]["launches"] + a[2]["launches"]
+    """the head of a rows pass (mc_rows_prefill, mc_extend_rows) as plan_rows_tail orders it: the final norm, the head GEMV and the ragged pick, no
+    row settings"""
+    return ask([token(cfg, linears, B, cus=cus, tiles_env=tiles_env, tail=True)])[0]["launches"]
 
 
 _FORMED = []

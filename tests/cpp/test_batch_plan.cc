@@ -1,4 +1,4 @@
-// What a batch launches (metalchat_amd/csrc/batch_plan.h) from the command line, without HIP: one request per line of standard input, one line of
+// What a batch launches (metalchat_amd/csrc/batch_plan.h, and in which order: batch_call_plan.h) from the command line, without HIP: one request per line of standard input, one line of
 // JSON per answer.  A linear is seven words, `fmt out in group ngroups lora lora_cols`; a launch is answered as [name, gx, gy, gz, block, lds];
 // a refusal as {"refused": "<text>"}.
 //
@@ -10,13 +10,17 @@
 //                                                                                                -> {"form", "launches", "sp", "chunk", "table"}
 //     logits   vocab ragged B {masked rep freq pres}[B]                                          -> {"any", "launches", "table"}
 //     verify   linear (the head) vocab n_kv_heads head_dim n_layers M nseg tree                  -> {"launches"}
+//     token    dim n_heads n_kv_heads head_dim n_layers vocab max_seq_len  B cus tiles_env ragged rolling  qkv wo w13 w2 output (linears, every layer
+//              alike)  kind top_k temperature top_p (the decoder's)  {kind top_k temperature top_p}[B]  {masked rep freq pres}[B]  logprobs top_n
+//                                                  -> {"launches": ONE token of the call in order (batch_call_plan.h plan_batch_token), "ops", "lp_slots"}
+//     tail     (the same words; ragged is not read)                                              -> the list behind a prompt pass (plan_rows_tail)
 //     ragged   what B max_seq_len vocab rolling n positions[B] tokens[B] lengths[B]              -> {"ok": true}
 //     bounds   step start_pos max_seq_len | generate start_pos n max_seq_len | tokens B vocab tokens[B]
 //     settings who B  kind (the decoder's)  lens[B] kind[B] {masked rep freq pres}[B]            (the two refusals of a verify call)
 //
 // The settings are rounded here as mc_decoder_set_sampler and mc_row_sampler_set round them.  tests/test_batch_plan_cpu.py holds the answers to
 // a recording of the launches (tests/golden/batch_plans.json), to the tile rule, and to the texts of every refusal.
-#include "../../metalchat_amd/csrc/batch_plan.h"
+#include "../../metalchat_amd/csrc/batch_call_plan.h"
 #include "../../metalchat_amd/csrc/bf16_host.h"
 
 #include <cstdio>
@@ -204,6 +208,47 @@ verify(std::istream& in)
 }
 
 static bool
+token(std::istream& in, bool tail)
+{
+    test_parts p;
+    mc_decoder_config& c = p.cfg;
+    batch_env e;
+    int n_layers = 0, is_ragged = 0, rolling = 0, logprobs = 0, top_n = 0;
+    test_layer L;
+    if (!(in >> c.dim >> c.n_heads >> c.n_kv_heads >> c.head_dim >> n_layers >> c.vocab >> c.max_seq_len >> e.B >> e.cus >> e.tiles_env >> is_ragged >> rolling) ||
+        n_layers < 0 || n_layers > 64 || e.B < 1 || e.B > MC_WIDE_BATCH_MAX || !read_linear(in, L.qkv) || !read_linear(in, L.wo) || !read_linear(in, L.w13) ||
+        !read_linear(in, L.w2) || !read_linear(in, p.output))
+        return false;
+    p.layers.assign(n_layers, L);
+    decoder_sampler dec;
+    if (!read_sampler(in, dec.kind, dec.top_k, dec.inv_temp_T, dec.top_p_T)) return false;
+    std::vector<row_setting> rows(e.B);
+    for (row_setting& r : rows) {
+        int kind = 0, top_k = 0;
+        if (!read_sampler(in, kind, top_k, r.inv_temp_T, r.top_p_T)) return false;
+        r.kind = kind;
+        r.top_k = top_k;
+    }
+    std::vector<row_logit_setting> lrows;
+    if (!read_logit_rows(in, lrows, e.B) || !(in >> logprobs >> top_n)) return false;
+    const batch_fixed f = fix_batch(p, e);
+    const call_settings s{rolling != 0, false, logprobs != 0, top_n, 0, dec, rows, lrows};
+    const batch_call_plan plan = tail ? plan_rows_tail(f, s) : plan_batch_token(f, s, is_ragged != 0);
+    if (!plan.refusal.empty()) {
+        answer_refusal(plan.refusal, "");
+        return true;
+    }
+    std::vector<launch_plan> ls;
+    std::string ops = "[";
+    for (const batch_launch& l : plan.listed()) {
+        ops += (ls.empty() ? "[" : ", [") + std::to_string((int)l.op) + ", " + std::to_string(l.layer) + "]";
+        ls.push_back(l.L);
+    }
+    printf("{\"launches\": %s, \"ops\": %s], \"lp_slots\": %d}\n", js(ls).c_str(), ops.c_str(), plan.lp_slots);
+    return true;
+}
+
+static bool
 ragged(std::istream& in)
 {
     std::string what;
@@ -266,6 +311,8 @@ main()
                         : kind == "head"     ? head(in)
                         : kind == "logits"   ? logits(in)
                         : kind == "verify"   ? verify(in)
+                        : kind == "token"    ? token(in, false)
+                        : kind == "tail"     ? token(in, true)
                         : kind == "ragged"   ? ragged(in)
                         : kind == "bounds"   ? bounds(in)
                         : kind == "settings" ? settings(in)

@@ -1,15 +1,15 @@
-// What a verify call with row settings launches (metalchat_amd/csrc/batch_plan.h plan_verify_pick / plan_verify_logits, Part 2m of the ABI) from the
-// command line, without HIP: one request per line of standard input, one line of JSON per answer.  A launch is answered as [name, gx, gy, gz, block,
-// lds], a refusal as {"refused": "<text>"}.
+// What a verify call with row settings launches (metalchat_amd/csrc/batch_plan.h plan_verify_pick / plan_verify_logits, Part 2m of the ABI; the whole
+// head of the call in order: batch_call_plan.h plan_verify_call) from the command line, without HIP: one request per line of standard input, one line of
+// JSON per answer.  A launch is answered as [name, gx, gy, gz, block, lds], a refusal as {"refused": "<text>"}.
 //
-//     call     vocab n_kv_heads head_dim n_layers n_pairs tree  kind top_k temperature top_p (the decoder's)  B  lens[B]
+//     call     vocab n_kv_heads head_dim n_layers n_pairs tree logprobs top_n head_fmt  kind top_k temperature top_p (the decoder's)  B  lens[B]
 //              {kind top_k temperature top_p}[B] (kind -1: inherits)  {masked rep freq pres}[B]  parents[sum of lens] (tree only)
-//                  -> {"greedy", "kpad", "nlists", "chunk", "cap", "any", "count", "head": plan_verify_head's launches over a plain head,
-//                      "launches": the whole head of the call in the order verify_head issues it, "table": [[kind, k, seed, anc, row, off] per packed row]}
+//                  -> {"greedy", "kpad", "nlists", "chunk", "cap", "any", "count", "head": plan_verify_head's launches over a head of format head_fmt,
+//                      "launches": the whole head of the call as plan_verify_call orders it, "table": [[kind, k, seed, anc, row, off] per packed row]}
 //     switch   enable                                                                       -> {"ok": true} or the refusal
 //
 // The settings are rounded here as mc_decoder_set_sampler and mc_row_sampler_set round them.  tests/test_verify_settings_cpu.py asks.
-#include "../../metalchat_amd/csrc/batch_plan.h"
+#include "../../metalchat_amd/csrc/batch_call_plan.h"
 #include "../../metalchat_amd/csrc/bf16_host.h"
 
 #include <cstdio>
@@ -47,9 +47,10 @@ static bool
 call(std::istream& in)
 {
     mc_decoder_config c{};
-    int n_layers = 0, n_pairs = 0, tree = 0, B = 0;
+    int n_layers = 0, n_pairs = 0, tree = 0, B = 0, logprobs = 0, top_n = 0;
+    linear_shape head;
     decoder_sampler dec;
-    if (!(in >> c.vocab >> c.n_kv_heads >> c.head_dim >> n_layers >> n_pairs >> tree) || !read_sampler(in, dec.kind, dec.top_k, dec.inv_temp_T, dec.top_p_T) ||
+    if (!(in >> c.vocab >> c.n_kv_heads >> c.head_dim >> n_layers >> n_pairs >> tree >> logprobs >> top_n >> head.fmt) || !read_sampler(in, dec.kind, dec.top_k, dec.inv_temp_T, dec.top_p_T) ||
         !(in >> B) || B < 1 || B > MC_WIDE_BATCH_MAX)
         return false;
     std::vector<int32_t> lens(B);
@@ -92,18 +93,23 @@ call(std::istream& in)
         return true;
     }
     const verify_logits_plan vl = plan_verify_logits(lens.data(), lrows, c.vocab, M, nseg);
-    linear_shape head;
     head.out = c.vocab;
     head.in = 1024;
     const verify_plan vh = plan_verify_head(head, c, n_layers, M, nseg, tree != 0);
-    std::vector<launch_plan> before = {vh.norm, vh.head, vh.argmax, vh.accept}, now = {vh.norm, vh.head};
+    std::vector<launch_plan> before = {vh.norm, vh.head, vh.argmax, vh.accept}, launches;
     if (tree) before.push_back(vh.compact);
-    if (vl.any) now.push_back(vl.process);
-    if (vp.greedy) now.push_back(vh.argmax);
-    else now.push_back(vp.first), now.push_back(vp.second);
-    now.push_back(vh.accept);
-    if (vl.count) now.push_back(vl.counting);
-    if (tree) now.push_back(vh.compact);
+    batch_fixed f;
+    f.cfg = c;
+    f.B = B;
+    f.n_layers = n_layers;
+    f.cand_per_row = cand_per_row;
+    f.head = head;
+    const batch_call_plan plan = plan_verify_call(f, call_settings{false, true, logprobs != 0, top_n, n_pairs, dec, rows, lrows}, lens.data(), M, nseg, nodes);
+    if (!plan.refusal.empty()) {
+        printf("{\"refused\": \"%s\"}\n", plan.refusal.c_str());
+        return true;
+    }
+    for (const batch_launch& l : plan.listed()) launches.push_back(l.L);
     std::string t = "[";
     for (size_t m = 0; m < vp.table.size(); m++) {
         const verify_row& v = vp.table[m];
@@ -113,7 +119,7 @@ call(std::istream& in)
     t += "]";
     printf("{\"greedy\": %s, \"kpad\": %u, \"nlists\": %u, \"chunk\": %u, \"cap\": %u, \"any\": %s, \"count\": %s, \"head\": %s, \"launches\": %s, \"table\": %s}\n",
            vp.greedy ? "true" : "false", vp.sp.kpad, vp.sp.nlists, vp.chunk, vp.sp.cap, vl.any ? "true" : "false", vl.count ? "true" : "false", js(before).c_str(),
-           js(now).c_str(), t.c_str());
+           js(launches).c_str(), t.c_str());
     return true;
 }
 

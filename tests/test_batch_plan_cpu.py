@@ -1,4 +1,4 @@
-"""What a batch launches (metalchat_amd/csrc/batch_plan.h) without a GPU, through tests/cpp/test_batch_plan (batch_plan_program.py):
+"""What a batch launches (metalchat_amd/csrc/batch_plan.h, in order: batch_call_plan.h) without a GPU, through tests/cpp/test_batch_plan (batch_plan_program.py):
 
   (a) every launch -- name, grid, block, LDS bytes -- of the cases recorded from the commit in front of the header
       (tests/golden/batch_plans.json: mc_decoder::launch wrote them down on an MI355X; the header is never recorded against itself);
@@ -6,8 +6,9 @@
   (c) every reason of the admission, reached from an admitted shape by one change, with its text; the shapes of the GPU tests admitted;
   (d) every refusal of a ragged call, the two of a verify call and the lockstep bounds, with their texts;
   (e) every kernel name any of these answers contains, or the plans form over a sweep of their inputs, is a FUNC symbol of the code object.
-(a) pins what each plan holds.  The order of a token's launches is restated in batch_plan_program.token_launches; that batch.cc issues them in
-this order, each with its own plan, is what the launch logs of the GPU tests see.
+(a) pins what each launch holds, the order of a call's launches and which plan sits at which place: the lists are batch_call_plan.h's
+(plan_batch_token, plan_rows_tail), the ones the batch's one executor walks; that it walks them is what tests/test_batch_call_plan_gpu.py sees.
+  (f) with log-probabilities on, the two launches are the last of a token in every pick form, and the process launch sits between the head and the pick.
 The texts below are the ones batch.cc carried before its checks moved into the header."""
 import json
 import os
@@ -253,6 +254,41 @@ def test_the_pick_forms_and_the_tables():
     assert some["table"] == [[0, 0, 0, 0, 0], [1, 0, 0, 0, 0], [2, 2.0, 0.5, 0.5, 0.25], [1, 0, 0, 0, 0]]
 
 
+# ------------------------------------------------------------------------------------------ (f) log-probabilities in the ordered list
+def test_the_log_probability_launches_are_the_last_of_a_token():
+    B, V = 4, SMALL["vocab"]
+    lin = bp.linears_of(SMALL)
+    sampling = (1, 50, 0.6, 0.9)
+    picks = {"greedy": (dict(), ["mc_b_argmax"]), "uniform": (dict(dec_sampler=sampling), ["mc_b_topk_candidates_bfloat", "mc_b_sample"]),
+             "mixed": (dict(dec_sampler=sampling, row_samplers=[(1, 1, 20, 0.7, 0.8)]), ["mc_b_topk_candidates_mixed_bfloat", "mc_b_pick_mixed"])}
+    masked = [(2, 1, 1.0, 0.0, 0.0)]
+    for ragged in (False, True):
+        sfx = "_rows_bfloat" if ragged else "_bfloat"
+        # vocab 2048: one chunk of 2048 logits per row (abi.h LOGPROB_CHUNK), 256 threads
+        lp = [["mc_logprob_parts" + sfx, 1, B, 1, 256, 0], ["mc_logprob_finish" + sfx, 1, B, 1, 256, 0]]
+        for form, (kw, pick) in picks.items():
+            pick = [n if n.endswith("_bfloat") else n + sfx for n in pick]
+            off, = ask([bp.token(SMALL, lin, B, cus=256, ragged_call=ragged, row_logits=masked, **kw)])
+            for top_n in (0, 3):
+                on, tail = ask([bp.token(SMALL, lin, B, cus=256, ragged_call=ragged, row_logits=masked, logprobs=top_n, **kw),
+                                bp.token(SMALL, lin, B, cus=256, row_logits=masked, logprobs=top_n, tail=True, **kw)])
+                assert on["launches"] == off["launches"] + lp and on["lp_slots"] == B and off["lp_slots"] == 0, (ragged, form, top_n)
+                names = [l[0] for l in on["launches"]]
+                process = "mc_b_logits_process" + sfx
+                assert names[-len(pick) - 4:] == ["mc_b_gemv_w_bfloat_e0", process] + pick + [l[0] for l in lp], (ragged, form, top_n, names)
+                assert names[-len(pick) - 5] == "mc_b_rmsnorm_bfloat" and names.count(process) == 1
+                # behind a prompt pass: the ragged list from the final norm on, whatever `ragged` of the request says
+                if ragged:
+                    assert tail["launches"] == on["launches"][-len(pick) - 5:], (form, top_n)
+    # the process launch of a step counts, the one behind a prompt pass does not: two op tags for one launch
+    on, tail = ask([bp.token(SMALL, lin, B, cus=256, ragged_call=True, row_logits=masked), bp.token(SMALL, lin, B, cus=256, row_logits=masked, tail=True)])
+    assert on["launches"][-2] == tail["launches"][-2] and on["ops"][-2] != tail["ops"][-2] and on["ops"][-1] == tail["ops"][-1]
+    # a vocabulary of more chunks than the finish launch folds is the call's refusal
+    big = dict(SMALL, vocab=2048 * 257)
+    a, = ask([bp.token(big, bp.linears_of(big), B, cus=256, logprobs=0)])
+    assert a["refused"].startswith("mc_logprobs: the vocabulary has 257 chunks of 2048"), a
+
+
 # ------------------------------------------------------------------------------------------ (e) the names exist
 def test_every_kernel_the_plans_name_exists():
     """the names of every answer of (a) to (d) -- asked again here, so that the check is the same whichever tests ran before it --, of the sweep
@@ -260,7 +296,8 @@ def test_every_kernel_the_plans_name_exists():
     SEEN.clear()
     for asks in (test_the_plans_are_the_recorded_launches_field_for_field, test_the_tile_rule_at_real_widths, test_the_shapes_of_the_gpu_tests_are_admitted,
                  test_every_reason_of_the_admission_is_reached_by_one_change, test_every_refusal_of_a_ragged_call,
-                 test_the_refusals_of_a_verify_call_and_the_lockstep_bounds, test_the_pick_forms_and_the_tables):
+                 test_the_refusals_of_a_verify_call_and_the_lockstep_bounds, test_the_pick_forms_and_the_tables,
+                 test_the_log_probability_launches_are_the_last_of_a_token):
         asks()
     assert len(SEEN) >= 40, sorted(SEEN)
     names = set(SEEN) | set(bp.formed_names())

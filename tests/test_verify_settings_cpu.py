@@ -1,9 +1,10 @@
 """Verify calls for sampling, masked and penalised rows (include/metalchat_hip.h Part 2m) without a GPU: the two calls are declared,
 exported and bound; a null batch and values other than 0 / 1 are refused with the call's prefix; the four kernels are in the code
-object and keep nothing in private memory; and the plan (csrc/batch_plan.h plan_verify_pick / plan_verify_logits through
-tests/cpp/test_verify_settings_plan, a plain g++ program): the per-packed-row table and the seed indices of segments on rows
+object and keep nothing in private memory; and the plan (csrc/batch_plan.h plan_verify_pick / plan_verify_logits, in order csrc/batch_call_plan.h
+plan_verify_call, through tests/cpp/test_verify_settings_plan, a plain g++ program): the per-packed-row table and the seed indices of segments on rows
 (5, 0, 2) of B = 8 with lens (2, 16, 5), the chain and tree `anc` words, a greedy-only call planning exactly plan_verify_head's
-launches, and the kpad of a call as the largest among the rows IN the call."""
+launches, the kpad of a call as the largest among the rows IN the call, and with log-probabilities on the two launches between the pick and the
+acceptance of a chain and of a tree."""
 import ctypes as C
 import json
 import os
@@ -33,8 +34,11 @@ def ask(lines):
     return answers
 
 
-def call(lens, samplers, logit_rows, *, dec=(GREEDY, 50, 0.6, 0.9), n_pairs=N_PAIRS, parents=None, cfg=CFG):
-    words = [cfg["vocab"], cfg["n_kv_heads"], cfg["head_dim"], cfg["n_layers"], n_pairs, int(parents is not None), *dec, len(lens), *lens]
+def call(lens, samplers, logit_rows, *, dec=(GREEDY, 50, 0.6, 0.9), n_pairs=N_PAIRS, parents=None, cfg=CFG, logprobs=None, head_fmt=0):
+    """logprobs: the top_n of a batch with log-probabilities on; head_fmt: the weight format of the head (0: plain)"""
+    words = [cfg["vocab"], cfg["n_kv_heads"], cfg["head_dim"], cfg["n_layers"], n_pairs, int(parents is not None), int(logprobs is not None), logprobs or 0, head_fmt,
+             *dec,
+             len(lens), *lens]
     for s in samplers:
         words += list(s)
     for r in logit_rows:
@@ -198,3 +202,26 @@ def test_a_tree_takes_depths_for_the_seed_and_the_nodes_anc_words():
     assert [t[2:] for t in a["table"][6:11]] == [[(j * B + 2) % N_PAIRS, (2 << j) - 1, 2, 6] for j in range(5)]
     assert [l[0] for l in a["launches"]] == ["mc_b_rmsnorm_bfloat", "mc_v_head_w_bfloat", "mc_vs_logits_process_bfloat", "mc_vs_topk_candidates_mixed_bfloat",
                                              "mc_vs_pick_mixed_bfloat", "mc_tv_accept", "mc_vs_count_accepted", "mc_tv_compact_bfloat"]
+
+
+def test_log_probabilities_sit_between_the_pick_and_the_accept():
+    """vocab 1312: one chunk of 2048 logits (abi.h LOGPROB_CHUNK), a part per (chunk, packed row), then one workgroup per packed row; 256 threads"""
+    parents = [[-1, 0, 0, 1, 2, 3], tr.chain(5), [-1, 0]]
+    lens = [6, 0, 5, 0, 0, 2, 0, 0]
+    samplers, logit_rows = mixed_rows()
+    lp = [["mc_logprob_parts_bfloat", 1, 13, 1, 256, 0], ["mc_logprob_finish_bfloat", 1, 13, 1, 256, 0]]
+    for top_n in (0, 3):
+        chain, tree, greedy, off = ask([call(lens, samplers, logit_rows, logprobs=top_n), call(lens, samplers, logit_rows, parents=parents, logprobs=top_n),
+                                        call(lens, [NOTHING] * B, [NEUTRAL] * B, logprobs=top_n), call(lens, samplers, logit_rows)])
+        names = [l[0] for l in chain["launches"]]
+        assert names == ["mc_b_rmsnorm_bfloat", "mc_v_head_w_bfloat", "mc_vs_logits_process_bfloat", "mc_vs_topk_candidates_mixed_bfloat", "mc_vs_pick_mixed_bfloat",
+                         "mc_logprob_parts_bfloat", "mc_logprob_finish_bfloat", "mc_v_accept", "mc_vs_count_accepted"]
+        assert chain["launches"][5:7] == lp
+        names = [l[0] for l in tree["launches"]]
+        assert names == ["mc_b_rmsnorm_bfloat", "mc_v_head_w_bfloat", "mc_vs_logits_process_bfloat", "mc_vs_topk_candidates_mixed_bfloat", "mc_vs_pick_mixed_bfloat",
+                         "mc_logprob_parts_bfloat", "mc_logprob_finish_bfloat", "mc_tv_accept", "mc_vs_count_accepted", "mc_tv_compact_bfloat"]
+        assert tree["launches"][5:7] == lp
+        # a greedy call: behind the argmax
+        assert greedy["launches"] == greedy["head"][:3] + lp + greedy["head"][3:]
+        # ... and every other launch is the one of the call without them
+        assert [l for l in chain["launches"] if l not in lp] == off["launches"]
