@@ -820,6 +820,37 @@ mc_status mc_logprobs_get(mc_batch* b, int32_t n, float* token_logprobs, int32_t
  * pick_logprobs [M], top_ids and top_logprobs [M][top_n].  The same refusals, prefixed "mc_logprobs_get_verify: ". */
 mc_status mc_logprobs_get_verify(mc_batch* b, float* pick_logprobs, int32_t* top_ids, float* top_logprobs);
 
+/* ================================================================================================
+ * Part 2o -- fp8 KV caches for batch rows.  What grows with the batch is each row's cache: 2 x head_dim bytes per kv head, K or V, layer
+ * and position in bfloat16.  An fp8 batch stores every cache vector (one kv head's K, or its V, at one slot) as head_dim OCP e4m3 bytes
+ * and ONE int8 exponent: head_dim + 1 bytes, (hd + 1) / (2 hd) of the bfloat16 figure.  It is a storage format: with x the vector as the
+ * bfloat16 batch would have stored it,
+ *   amax    = max |x|
+ *   e       = the smallest integer with amax 2^-e <= 448, clamped to [-100, 119]; -100 for amax = 0
+ *   byte[i] = e4m3(x[i] 2^-e), nearest, ties to even, saturating at +-448 (the scaling is exact in float32)
+ *   deq[i]  = e4m3(byte[i]) 2^e, exactly a normal bfloat16 or zero
+ * and every row computes bit for bit what a bfloat16 batch computes whose cache holds deq(quant(K)) and deq(quant(V)) -- the same
+ * MFMA operands, splits, sums and rounding points; tests/kv_fp8_rule.py states the rule in numpy.  Non-finite K / V are out of scope.
+ *   admitted  mc_batch_step / _generate, mc_ragged_step / _generate with idle rows and stop ids, mc_rolling_set, mc_batch_fork as a
+ *             quantising copy of the decoder's cache, mc_batch_import_kv, which quantises, mc_batch_export_kv / mc_ragged_export_kv,
+ *             which return bfloat16 deq values in the row's logical order, rolled rows included, mc_rolling_fork_row, which copies
+ *             the bytes and exponents as they lie, and everything that never touches a cache: Parts 2k, 2l, 2n, seeds,
+ *             mc_batch_get_logits.
+ *   refused   mc_rows_prefill, mc_extend_rows, mc_verify_rows, mc_tree_verify: MC_ERR_INVALID_ARGUMENT before anything is enqueued,
+ *             "<call>: the batch holds an fp8 cache, ..."; the rows' lengths stay.  A prompt reaches an fp8 batch through the decoder's
+ *             prompt pass and mc_batch_fork, or through mc_batch_import_kv.
+ *   the rows  the row contract holds: a row's tokens, logits and K / V do not depend on B, its index or the other rows.
+ * Not covered: the packed passes and both verify calls, the batch-1 decoder, float32 decoders, head_dim 256, formats other than e4m3.
+ * ------------------------------------------------------------------------------------------ */
+#define MC_KV_BF16 0
+#define MC_KV_FP8 1
+/* mc_wide_batch_create's admission, bound (1 <= batch <= 64) and texts, prefixed "mc_kv_batch_create: ".  MC_KV_BF16 makes exactly what
+ * mc_wide_batch_create makes.  Any other kv_format than the two: "kv_format must be MC_KV_BF16 (0) or MC_KV_FP8 (1)"; MC_KV_FP8 also
+ * needs max_seq_len % 8 == 0. */
+mc_status mc_kv_batch_create(mc_decoder* d, int32_t batch, int32_t kv_format, mc_batch** out);
+int32_t mc_kv_batch_format(const mc_batch* b); /* MC_KV_*; MC_KV_BF16 for a null batch and for every other create call's batch */
+uint64_t mc_kv_batch_bytes(const mc_batch* b); /* the bytes of the rows' caches, all layers and planes; 0 for a null batch */
+
 /* Host-side helpers shared by tests and the synthetic initialiser. */
 /* value in [-7,7] (bits = 4) or [-127,127] (bits = 8), zero mean, of element (row, col) of matrix `matrix_id` */
 int32_t mc_synth_weight(uint64_t seed, uint32_t matrix_id, uint32_t row, uint32_t col, int32_t bits);

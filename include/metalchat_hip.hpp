@@ -591,5 +591,18 @@ public:
     std::size_t start_pos() const { return mc_interpreter_start_pos(_M_it.get()); }
 };
 
+// ---- batches with a chosen cache format (Part 2o of the ABI) ---------------------------------
+/// A batch of `batch` rows over `decoder` whose caches hold `kv_format` (MC_KV_BF16 or MC_KV_FP8); released with the last copy.
+using shared_batch = std::shared_ptr<mc_batch>;
+inline shared_batch
+make_kv_batch(mc_decoder* decoder, std::int32_t batch, std::int32_t kv_format)
+{
+    mc_batch* b = nullptr;
+    check(mc_kv_batch_create(decoder, batch, kv_format, &b));
+    return shared_batch(b, mc_batch_release);
+}
+inline std::int32_t kv_format(const shared_batch& b) { return mc_kv_batch_format(b.get()); }
+inline std::uint64_t kv_bytes(const shared_batch& b) { return mc_kv_batch_bytes(b.get()); }
+
 } // namespace hip
 } // namespace metalchat

@@ -153,6 +153,15 @@ mc_batch::run(const batch_launch& l, const call_args& a)
                                 (uint32_t)fx.nsplit, cstride));
     case op::pv:
         return launch(l.L, pack(expv, psum, (void*)vt_of(li, 0), att, state, (uint32_t)n_rep, (uint32_t)hd, (uint32_t)cfg.max_seq_len, (uint32_t)fx.nsplit, cstride));
+    case op::rope_f8:
+        return launch(l.L, pack(qkv, q, (void*)kc_of(li, 0), (void*)vt_of(li, 0), kexp_of(li, 0), vexp_of(li, 0), c.rolling ? rcos : fcos, c.rolling ? rsin : fsin, state,
+                                (uint32_t)H, (uint32_t)KV, (uint32_t)hd, (uint32_t)cfg.max_seq_len, cstride, (uint64_t)exp_elems()));
+    case op::scores_f8:
+        return launch(l.L, pack(q, (void*)kc_of(li, 0), kexp_of(li, 0), expv, psum, state, (uint32_t)n_rep, (uint32_t)hd, (uint32_t)cfg.max_seq_len,
+                                round_bf_host(cfg.attn_scale), (uint32_t)fx.nsplit, cstride, (uint64_t)exp_elems()));
+    case op::pv_f8:
+        return launch(l.L, pack(expv, psum, (void*)vt_of(li, 0), vexp_of(li, 0), att, state, (uint32_t)n_rep, (uint32_t)hd, (uint32_t)cfg.max_seq_len, (uint32_t)fx.nsplit,
+                                cstride, (uint64_t)exp_elems()));
     case op::process:
     case op::process_rows:
     case op::process_rows_count: { // count: the rows with penalties count their input token first (a step; the packed passes count nothing)
@@ -284,9 +293,10 @@ run_tokens(mc_batch* b, const int32_t* tokens, int32_t start_pos, const int32_t*
     return s != MC_OK ? s : finish(b, start_pos, positions, n, tokens_out, produced);
 }
 
-// mc_batch_create and mc_wide_batch_create: `who` names the caller in the texts, `cap` is its largest batch, `wide` its admission
+// mc_batch_create, mc_wide_batch_create and mc_kv_batch_create: `who` names the caller in the texts, `cap` is its largest batch, `wide` its
+// admission, kv_format what the rows' caches hold
 mc_status
-batch_create(const std::string& who, int cap, bool wide, mc_decoder* d, int32_t batch, mc_batch** out)
+batch_create(const std::string& who, int cap, bool wide, mc_decoder* d, int32_t batch, mc_batch** out, int32_t kv_format = MC_KV_BF16)
 {
     if (!d || !out) return fail(MC_ERR_INVALID_ARGUMENT, who + ": null argument");
     if (batch < 1 || batch > cap) return fail(MC_ERR_INVALID_ARGUMENT, who + ": batch must lie in [1, " + std::to_string(cap) + "]");
@@ -296,12 +306,15 @@ batch_create(const std::string& who, int cap, bool wide, mc_decoder* d, int32_t 
     if (s != MC_OK) return s;
     const std::string why = refusal(parts, wide);
     if (!why.empty()) return fail(MC_ERR_INVALID_ARGUMENT, who + ": " + why);
+    if (const std::string bad = kv_format_refusal(parts.cfg, kv_format); !bad.empty()) return fail(MC_ERR_INVALID_ARGUMENT, who + ": " + bad);
     MC_HIP(hipSetDevice(parts.ordinal));
     std::unique_ptr<mc_batch> b(new mc_batch);
     batch_env env;
     env.B = batch;
     MC_HIP(hipDeviceGetAttribute(&env.cus, hipDeviceAttributeMultiprocessorCount, parts.ordinal));
     env.tiles_env = wb_tiles_env_of(getenv("MC_WB_TILES"));
+    env.kv_format = kv_format;
+    b->kv_format = kv_format;
     b->fx = fix_batch(parts, env);
     b->d = d;
     b->p = parts;
@@ -312,7 +325,10 @@ batch_create(const std::string& who, int cap, bool wide, mc_decoder* d, int32_t 
     const mc_decoder_config& c = parts.cfg;
     const int H = c.n_heads, KV = c.n_kv_heads, hd = c.head_dim, L = (int)parts.layers.size();
     b->cache_elems = (size_t)KV * c.max_seq_len * hd;
-    const size_t cache_bytes = (size_t)L * batch * b->cache_elems * 2;
+    const size_t cache_bytes = (size_t)L * batch * b->cache_elems * b->kv_elem();
+    const size_t exp_bytes = b->fp8() ? (size_t)L * batch * b->exp_elems() : 0;
+    b->kv_bytes = 2 * (cache_bytes + exp_bytes);
+    if (b->fp8() && ((s = b->alloc(&b->kexp, exp_bytes)) != MC_OK || (s = b->alloc(&b->vexp, exp_bytes)) != MC_OK)) return s;
     const int ffn = parts.layers.empty() ? 0 : parts.layers[0].w13.out / 2;
     if ((s = b->alloc(&b->kc, cache_bytes)) != MC_OK || (s = b->alloc(&b->vt, cache_bytes)) != MC_OK ||
         (s = b->alloc(&b->x, (size_t)batch * c.dim * 2)) != MC_OK || (s = b->alloc(&b->xn, (size_t)batch * c.dim * 2)) != MC_OK ||
@@ -358,6 +374,26 @@ mc_status
 mc_wide_batch_create(mc_decoder* d, int32_t batch, mc_batch** out)
 {
     return batch_create("mc_wide_batch_create", MC_WIDE_BATCH_MAX, true, d, batch, out);
+}
+
+// ---- Part 2o: fp8 caches ----
+
+mc_status
+mc_kv_batch_create(mc_decoder* d, int32_t batch, int32_t kv_format, mc_batch** out)
+{
+    return batch_create("mc_kv_batch_create", MC_WIDE_BATCH_MAX, true, d, batch, out, kv_format);
+}
+
+int32_t
+mc_kv_batch_format(const mc_batch* b)
+{
+    return b ? b->kv_format : MC_KV_BF16;
+}
+
+uint64_t
+mc_kv_batch_bytes(const mc_batch* b)
+{
+    return b ? (uint64_t)b->kv_bytes : 0;
 }
 
 void

@@ -17,9 +17,33 @@ copy_cache_rows(mc_batch* b, void* k_dst, void* vt_dst, const void* k_src, const
     return MC_OK;
 }
 
+// Part 2o: the first n positions of row `row`'s four planes from row `src`'s, byte for byte
+mc_status
+copy_cache_rows_f8(mc_batch* b, int layer, int row, int src, int n)
+{
+    const mc_decoder_config& c = b->p.cfg;
+    const size_t KV = c.n_kv_heads, hd = c.head_dim, S = c.max_seq_len;
+    MC_HIP(hipMemcpy2DAsync(b->kc_of(layer, row), S * hd, b->kc_of(layer, src), S * hd, (size_t)n * hd, KV, hipMemcpyDeviceToDevice, b->p.stream));
+    MC_HIP(hipMemcpy2DAsync(b->vt_of(layer, row), S, b->vt_of(layer, src), S, (size_t)n, KV * hd, hipMemcpyDeviceToDevice, b->p.stream));
+    MC_HIP(hipMemcpy2DAsync(b->kexp_of(layer, row), S, b->kexp_of(layer, src), S, (size_t)n, KV, hipMemcpyDeviceToDevice, b->p.stream));
+    MC_HIP(hipMemcpy2DAsync(b->vexp_of(layer, row), S, b->vexp_of(layer, src), S, (size_t)n, KV, hipMemcpyDeviceToDevice, b->p.stream));
+    return MC_OK;
+}
+
+// Part 2o: bfloat16 K [kv][src_seq][hd] and Vt [kv * hd][src_seq], positions [0, n), quantised into row `row`'s planes of `layer` (mc_kv_quant_f8)
+mc_status
+quant_cache_rows(mc_batch* b, int layer, int row, const void* k_src, const void* vt_src, int src_seq, int n)
+{
+    const mc_decoder_config& c = b->p.cfg;
+    return b->launch("mc_kv_quant_f8", (unsigned)(n + 63) / 64, (unsigned)c.n_kv_heads, 1, 256, 0,
+                     pack(k_src, vt_src, (uint32_t)src_seq, (void*)b->kc_of(layer, row), (void*)b->vt_of(layer, row), b->kexp_of(layer, row), b->vexp_of(layer, row),
+                          (uint32_t)n, (uint32_t)c.head_dim, (uint32_t)c.max_seq_len));
+}
+
 // mc_batch_export_kv and mc_ragged_export_kv: row `row`'s cache of `layer` through mc_kv_export_bfloat, which takes kv_len (and
 // the ring) from the device step state `state`, into staging buffers of `cap` positions; then n positions to the host.
-// n < 0: n = that kv_len, read back behind the launch and reported in *n_out.
+// n < 0: n = that kv_len, read back behind the launch and reported in *n_out.  An fp8 cache (Part 2o) goes through mc_kv_dequant_f8: the same
+// view, the values deq of the row's bytes.
 mc_status
 export_kv(mc_batch* b, const char* what, int32_t row, int32_t layer, const step_state* state, int32_t cap, int32_t n, int32_t* n_out,
           void* keys, void* values)
@@ -30,9 +54,14 @@ export_kv(mc_batch* b, const char* what, int32_t row, int32_t layer, const step_
     hipError_t e = kt.alloc(cap * per_pos);
     if (e == hipSuccess) e = vtmp.alloc(cap * per_pos);
     if (e != hipSuccess) return hip_fail(e, what);
-    mc_status s = b->launch("mc_kv_export_bfloat", 512, 1, 1, 256, 0,
-                            pack((const void*)b->kc_of(layer, row), (const void*)b->vt_of(layer, row), kt.ptr, vtmp.ptr, (const void*)state,
-                                 (uint32_t)c.n_kv_heads, (uint32_t)c.head_dim, (uint32_t)c.max_seq_len, (uint32_t)b->p.pre_len));
+    arg_pack args = pack((const void*)b->kc_of(layer, row), (const void*)b->vt_of(layer, row));
+    if (b->fp8()) {
+        args.push((const void*)b->kexp_of(layer, row));
+        args.push((const void*)b->vexp_of(layer, row));
+    }
+    for (const void* a : {(const void*)kt.ptr, (const void*)vtmp.ptr, (const void*)state}) args.push(a);
+    for (uint32_t w : {(uint32_t)c.n_kv_heads, (uint32_t)c.head_dim, (uint32_t)c.max_seq_len, (uint32_t)b->p.pre_len}) args.push(w);
+    mc_status s = b->launch(b->fp8() ? "mc_kv_dequant_f8" : "mc_kv_export_bfloat", 512, 1, 1, 256, 0, std::move(args));
     e = hipStreamSynchronize(b->p.stream);
     if (s == MC_OK && e == hipSuccess && n < 0) {
         step_state st{};
@@ -83,8 +112,11 @@ mc_batch_fork(mc_batch* b, int32_t row, int32_t n_valid)
     if (rolled) return fail(MC_ERR_INVALID_ARGUMENT, "mc_batch_fork: the decoder's cache has rolled (sink ring turned)");
     if (n_valid > kv_len) return fail(MC_ERR_INVALID_ARGUMENT, "mc_batch_fork: the decoder's cache holds fewer than n_valid positions");
     MC_HIP(hipSetDevice(b->p.ordinal));
-    for (size_t l = 0; l < b->p.layers.size(); l++)
-        if ((s = copy_cache_rows(b, b->kc_of((int)l, row), b->vt_of((int)l, row), b->p.layers[l].kc, b->p.layers[l].vt, n_valid)) != MC_OK) return s;
+    for (size_t l = 0; l < b->p.layers.size(); l++) { // (an fp8 cache: a quantising copy)
+        s = b->fp8() ? quant_cache_rows(b, (int)l, row, b->p.layers[l].kc, b->p.layers[l].vt, c.max_seq_len, n_valid)
+                     : copy_cache_rows(b, b->kc_of((int)l, row), b->vt_of((int)l, row), b->p.layers[l].kc, b->p.layers[l].vt, n_valid);
+        if (s != MC_OK) return s;
+    }
     if ((s = b->set_pos(n_valid - 1)) != MC_OK) return s;
     MC_HIP(hipStreamSynchronize(b->p.stream));
     b->lengths[row] = n_valid;
@@ -102,15 +134,21 @@ mc_batch_import_kv(mc_batch* b, int32_t row, int32_t layer, const void* keys, co
         return fail(MC_ERR_INVALID_ARGUMENT, "mc_batch_import_kv: n_valid must lie in [1, max_seq_len]");
     MC_HIP(hipSetDevice(b->p.ordinal));
     const size_t nb = (size_t)n_valid * c.n_kv_heads * c.head_dim * 2;
-    device_tmp kt, vtmp;
+    // an fp8 cache: the import kernel fills a bfloat16 cache of exactly n_valid slots (K [kv][n][hd], Vt [kv * hd][n]), which is then quantised
+    device_tmp kt, vtmp, kstage, vstage;
     MC_HIP(kt.alloc(nb));
     hipError_t e = vtmp.alloc(nb);
+    if (e == hipSuccess && b->fp8()) e = kstage.alloc(nb);
+    if (e == hipSuccess && b->fp8()) e = vstage.alloc(nb);
     if (e == hipSuccess) e = hipMemcpy(kt.ptr, keys, nb, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(vtmp.ptr, values, nb, hipMemcpyHostToDevice);
     if (e == hipSuccess) {
+        void* k_dst = b->fp8() ? kstage.ptr : (void*)b->kc_of(layer, row);
+        void* vt_dst = b->fp8() ? vstage.ptr : (void*)b->vt_of(layer, row);
         s = b->launch("mc_kv_import_bfloat", 512, 1, 1, 256, 0,
-                      pack((void*)b->kc_of(layer, row), (void*)b->vt_of(layer, row), (const void*)kt.ptr, (const void*)vtmp.ptr,
-                           (uint32_t)n_valid, (uint32_t)c.n_kv_heads, (uint32_t)c.head_dim, (uint32_t)c.max_seq_len));
+                      pack(k_dst, vt_dst, (const void*)kt.ptr, (const void*)vtmp.ptr, (uint32_t)n_valid, (uint32_t)c.n_kv_heads, (uint32_t)c.head_dim,
+                           (uint32_t)(b->fp8() ? n_valid : c.max_seq_len)));
+        if (s == MC_OK && b->fp8()) s = quant_cache_rows(b, layer, row, kstage.ptr, vstage.ptr, n_valid, n_valid);
         if (s == MC_OK) s = b->set_pos(n_valid - 1);
         e = hipStreamSynchronize(b->p.stream);
     }
@@ -165,8 +203,10 @@ mc_rolling_fork_row(mc_batch* b, int32_t dst, int32_t src)
     // the physical slots as they lie: a rolled row's ring follows from its length, which the copy takes along
     const int n = std::min(b->lengths[src], b->p.cfg.max_seq_len);
     MC_HIP(hipSetDevice(b->p.ordinal));
-    for (int l = 0; n > 0 && l < (int)b->p.layers.size(); l++)
-        if (mc_status s = copy_cache_rows(b, b->kc_of(l, dst), b->vt_of(l, dst), b->kc_of(l, src), b->vt_of(l, src), n); s != MC_OK) return s;
+    for (int l = 0; n > 0 && l < (int)b->p.layers.size(); l++) {
+        const mc_status s = b->fp8() ? copy_cache_rows_f8(b, l, dst, src, n) : copy_cache_rows(b, b->kc_of(l, dst), b->vt_of(l, dst), b->kc_of(l, src), b->vt_of(l, src), n);
+        if (s != MC_OK) return s;
+    }
     MC_HIP(hipStreamSynchronize(b->p.stream));
     b->lengths[dst] = b->lengths[src];
     return MC_OK;

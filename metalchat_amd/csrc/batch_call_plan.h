@@ -18,6 +18,7 @@ enum class batch_op {
     begin_lockstep, begin_rows, begin_rolling, embed, embed_rows, attn_norm, ffn_norm, final_norm,
     qkv_adaptor, qkv_gemv, wo_adaptor, wo_gemv, w13_adaptor, w13_gemv, w2_adaptor, w2_gemv, head_gemv, // adaptor: a = T(A x) in front of its linear
     rope, scores, pv,
+    rope_f8, scores_f8, pv_f8, // Part 2o: the byte and exponent planes in place of the bfloat16 caches
     process, process_rows, process_rows_count, // the ragged form takes the count flag: off behind a prompt pass
     argmax, candidates, sample, candidates_mixed, pick_mixed,
     logprob_parts, logprob_finish,
@@ -34,7 +35,7 @@ struct batch_launch {
 // launch to the last layer's w2: no setting of a call changes it, so a call's plan points at it and no call builds it again
 struct batch_fixed {
     mc_decoder_config cfg{};
-    int B = 0, nsplit = 0, n_layers = 0;
+    int B = 0, nsplit = 0, n_layers = 0, kv_format = MC_KV_BF16;
     bool wide = false; // B > 16: every GEMV of the batch is the wide kernel, whose argument list has the rows of the matrix in front of ldy
     size_t cand_per_row = 0;
     linear_shape head;
@@ -49,6 +50,7 @@ fix_batch(const Parts& p, const batch_env& e)
     batch_fixed f;
     f.cfg = p.cfg;
     f.B = e.B;
+    f.kv_format = e.kv_format;
     f.nsplit = (p.cfg.max_seq_len + PB - 1) / PB;
     f.n_layers = (int)p.layers.size();
     f.cand_per_row = (size_t)std::max(((uint32_t)p.cfg.vocab + 511) / 512, 1u) * 128;
@@ -58,7 +60,7 @@ fix_batch(const Parts& p, const batch_env& e)
     assert(!f.head_gemv.lora && "the admission refuses an adaptor on the head: a token's plan lists no adaptor launch in front of it");
     using op = batch_op;
     for (int form = 0; form < 3; form++) {
-        const step_plan& st = f.steps[form] = plan_step(p.cfg, e.B, f.nsplit, form > 0, form == 2);
+        const step_plan& st = f.steps[form] = plan_step(p.cfg, e.B, f.nsplit, form > 0, form == 2, e.kv_format);
         std::vector<batch_launch>& body = f.body[form];
         auto gemv = [&](op adaptor, op main, const batch_gemv_plan& g, int layer) { // (a linear with an adaptor: a = T(A x) in front)
             assert(g.wide == f.wide);
@@ -71,9 +73,9 @@ fix_batch(const Parts& p, const batch_env& e)
             const auto& L = p.layers[l];
             body.push_back({op::attn_norm, l, st.rmsnorm});
             gemv(op::qkv_adaptor, op::qkv_gemv, plan_batch_gemv(L.qkv, 0, e), l);
-            body.push_back({op::rope, l, st.rope});
-            body.push_back({op::scores, l, st.scores});
-            body.push_back({op::pv, l, st.pv});
+            body.push_back({st.fp8 ? op::rope_f8 : op::rope, l, st.rope});
+            body.push_back({st.fp8 ? op::scores_f8 : op::scores, l, st.scores});
+            body.push_back({st.fp8 ? op::pv_f8 : op::pv, l, st.pv});
             gemv(op::wo_adaptor, op::wo_gemv, plan_batch_gemv(L.wo, 1, e), l);
             body.push_back({op::ffn_norm, l, st.rmsnorm});
             gemv(op::w13_adaptor, op::w13_gemv, plan_batch_gemv(L.w13, 2, e), l);

@@ -24,6 +24,8 @@
 // of those rows in place.  A batch on which no row has either launches what it launched before.
 // Part 2m (mc_settings_verify_set): opt-in per batch, the two verify calls take rows that sample or carry a mask or penalties;
 // the head of the call then runs process -> pick -> accept -> count over the packed rows (plan_verify_pick, plan_verify_logits).
+// Part 2o (mc_kv_batch_create): the rows' caches hold e4m3 bytes and one exponent per cache vector (kv8_kernels.hip); the step's three cache
+// launches are their _f8 forms, fork and import quantise, the exports dequantise, and the four packed calls are refused.
 // Part 2n (mc_logprobs_set): opt-in per batch, two launches (logprob_kernels.hip) behind every pick -- a token's three forms and a verify call's --
 // record the pick's log-probability and the top_n most likely tokens.  With the switch off a batch launches and holds what it did before.
 //
@@ -103,7 +105,10 @@ struct mc_batch {
     int B = 0;
     size_t cache_elems = 0; // one row's cache of one layer: n_kv * max_seq * hd
     std::vector<void*> allocs;
-    void *kc = nullptr, *vt = nullptr;    // [layer][B][n_kv][max_seq][hd], [layer][B][n_kv][hd][max_seq]
+    void *kc = nullptr, *vt = nullptr;    // [layer][B][n_kv][max_seq][hd], [layer][B][n_kv][hd][max_seq]: bfloat16, or (Part 2o) e4m3 bytes
+    int kv_format = MC_KV_BF16;           // mc_kv_batch_create: MC_KV_FP8 = the caches hold bytes and, per cache vector, an exponent
+    int8_t *kexp = nullptr, *vexp = nullptr; // [layer][B][n_kv][max_seq]: the exponents of an fp8 cache's K and V vectors
+    size_t kv_bytes = 0;                  // what the caches took: all planes of all layers and rows
     void *x = nullptr, *xn = nullptr;     // [B][dim]
     void *qkv = nullptr;                  // [B][(H + 2 KV) hd]
     void *q = nullptr, *att = nullptr;    // [B][H hd]
@@ -247,8 +252,13 @@ struct mc_batch {
     }
 
     int mask_words() const { return (p.cfg.vocab + 31) / 32; }
-    char* kc_of(int layer, int row) const { return (char*)kc + ((size_t)layer * B + row) * cache_elems * 2; }
-    char* vt_of(int layer, int row) const { return (char*)vt + ((size_t)layer * B + row) * cache_elems * 2; }
+    bool fp8() const { return kv_format == MC_KV_FP8; }
+    size_t kv_elem() const { return fp8() ? 1 : 2; }                                      // bytes of one cache element
+    size_t exp_elems() const { return (size_t)p.cfg.n_kv_heads * p.cfg.max_seq_len; }     // one row's exponents of one layer, K or V
+    char* kc_of(int layer, int row) const { return (char*)kc + ((size_t)layer * B + row) * cache_elems * kv_elem(); }
+    char* vt_of(int layer, int row) const { return (char*)vt + ((size_t)layer * B + row) * cache_elems * kv_elem(); }
+    int8_t* kexp_of(int layer, int row) const { return kexp + ((size_t)layer * B + row) * exp_elems(); }
+    int8_t* vexp_of(int layer, int row) const { return vexp + ((size_t)layer * B + row) * exp_elems(); }
     mc_status ensure_tokens(int n) { return reserve(tokens_dev, tokens_cap, n * B, n * B); }
 
     // the shared step state at position `pos` (slot = pos: a batch's cache never turns)

@@ -105,7 +105,24 @@ refusal(const Parts& p, bool wide)
 // of a batch, fixed at its creation: its rows, the device's compute units and MC_WB_TILES (0: by wb_tiles' rule)
 struct batch_env {
     int B = 0, cus = 0, tiles_env = 0;
+    int kv_format = MC_KV_BF16; // Part 2o: what the rows' caches hold
 };
+
+// mc_kv_batch_create's format, and what an fp8 cache asks of the config beyond the admission (its P.V kernel loads a Vt row's exponents 8 slots a lane)
+inline std::string
+kv_format_refusal(const mc_decoder_config& c, int32_t kv_format)
+{
+    if (kv_format != MC_KV_BF16 && kv_format != MC_KV_FP8) return "kv_format must be MC_KV_BF16 (0) or MC_KV_FP8 (1)";
+    if (kv_format == MC_KV_FP8 && c.max_seq_len % 8 != 0) return "an fp8 cache needs max_seq_len % 8 == 0";
+    return "";
+}
+// the four packed calls on a batch whose cache is fp8: refused before anything is enqueued ("" = a bfloat16 cache)
+inline std::string
+kv_packed_refusal(const char* who, int kv_format)
+{
+    if (kv_format == MC_KV_BF16) return "";
+    return std::string(who) + ": the batch holds an fp8 cache, which the packed passes do not read or write (prompts reach it through mc_batch_fork or mc_batch_import_kv)";
+}
 
 // MC_WB_TILES as mc_batch_create reads it: 1, 2, 4 or 8, anything else (or unset) = 0
 inline int
@@ -164,21 +181,24 @@ plan_batch_gemv(const linear_shape& L, int epi, const batch_env& e)
 // ---------------------------------------------------------------- one token of a call
 
 // The launches of a step whose name and grid follow from the config, B and (ragged, rolling): the lockstep kernels read the shared state
-// (mc_step_set starts the step), their _rows forms row r's own (mc_b_rows_begin; a rolling batch: mc_b_rows_begin_rolling, a workgroup per row)
+// (mc_step_set starts the step), their _rows forms row r's own (mc_b_rows_begin; a rolling batch: mc_b_rows_begin_rolling, a workgroup per row).
+// kv_format MC_KV_FP8 (Part 2o): the three launches that touch the cache are their _f8 forms (kv8_kernels.hip), with the same grids
 struct step_plan {
     bool ragged = false, rolling = false; // rolling: ragged on a rolling batch
+    bool fp8 = false;                     // rope, scores and pv are the _f8 forms, which take the exponent planes as well
     launch_plan begin, embed, rmsnorm, rope, scores, pv;
 };
 inline step_plan
-plan_step(const mc_decoder_config& c, int B, int nsplit, bool ragged, bool rolling)
+plan_step(const mc_decoder_config& c, int B, int nsplit, bool ragged, bool rolling, int kv_format = MC_KV_BF16)
 {
     const unsigned H = c.n_heads, KV = c.n_kv_heads, hd = c.head_dim, b = B;
-    const std::string sfx = ragged ? "_rows_bfloat" : "_bfloat";
+    const std::string sfx = std::string(kv_format == MC_KV_FP8 ? "_f8" : "") + (ragged ? "_rows_bfloat" : "_bfloat");
     step_plan s;
     s.ragged = ragged;
     s.rolling = ragged && rolling;
     s.begin = !ragged ? launch_plan{"mc_step_set", 1, 1, 1, 64, 0}
                       : (s.rolling ? launch_plan{"mc_b_rows_begin_rolling", b, 1, 1, 64, 0} : launch_plan{"mc_b_rows_begin", 1, 1, 1, 64, 0});
+    s.fp8 = kv_format == MC_KV_FP8;
     s.embed = {ragged ? "mc_b_embed_rows_bfloat" : "mc_b_embed_bfloat", ((unsigned)c.dim + 255) / 256, b, 1, 256, 0};
     s.rmsnorm = {"mc_b_rmsnorm_bfloat", 1, b, 1, 1024, 0};
     s.rope = {"mc_b_rope_kv" + sfx, H + 2 * KV, b, 1, hd / 2, 0};

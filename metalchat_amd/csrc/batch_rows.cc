@@ -25,6 +25,7 @@ rows_pass(mc_batch* b, const char* who, bool extend, const int32_t* tokens, cons
 {
     const mc_decoder_config& c = b->p.cfg;
     const int B = b->B;
+    if (mc_status s = refuse(kv_packed_refusal(who, b->kv_format)); s != MC_OK) return s; // (Part 2o: nothing enqueued, the lengths as they were)
     // check (rows_plan.h: the admission, the tables and the scratch sizes are plain arithmetic there)
     const bool tree = v && v->parents;
     const rows_counts n = rows_check(who, tokens, lens, positions, b->lengths.data(), B, c.max_seq_len, c.vocab, v != nullptr);

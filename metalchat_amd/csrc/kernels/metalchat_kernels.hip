@@ -16,3 +16,4 @@
 #include "tree_kernels.hip"
 #include "logit_kernels.hip"
 #include "logprob_kernels.hip"
+#include "kv8_kernels.hip"

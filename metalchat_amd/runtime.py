@@ -200,6 +200,9 @@ def capi() -> C.CDLL:
         "mc_interpreter_pending": (i32, [vp, C.POINTER(i32), sz, C.POINTER(sz)]),
         "mc_batch_create": (i32, [vp, i32, pvp]),
         "mc_wide_batch_create": (i32, [vp, i32, pvp]),
+        "mc_kv_batch_create": (i32, [vp, i32, i32, pvp]),
+        "mc_kv_batch_format": (i32, [vp]),
+        "mc_kv_batch_bytes": (u64, [vp]),
         "mc_batch_release": (None, [vp]),
         "mc_batch_size": (i32, [vp]),
         "mc_batch_fork": (i32, [vp, i32, i32]),
@@ -819,16 +822,35 @@ class Batch:
     """Batched decode (Parts 2b and 2c of the C ABI): B <= 8 sequences over `decoder`'s weights, each with its own cache, in
     lockstep or each row at its own position (nn::attention with input[bs, 1, dim], include/metalchat/nn/attention.h:163-206).
     wide=True (Part 2h): B <= 64, the same rows bit for bit; that entry also admits QLoRA decoders (Part 2i): int4 / int8 linears
-    in groups of 32, each linear in a format of its own, LoRA adaptors of rank % 16 == 0 on the layer linears.  Keeps the decoder alive."""
+    in groups of 32, each linear in a format of its own, LoRA adaptors of rank % 16 == 0 on the layer linears.  Keeps the decoder alive.
+    kv="fp8" (Part 2o, with wide=True): the rows' caches hold e4m3 bytes and one exponent per cache vector, (hd + 1) / (2 hd) of the
+    bfloat16 bytes; the packed passes and the verify calls are refused on such a batch."""
 
-    def __init__(self, decoder: Decoder, batch: int, wide: bool = False):
+    KV_FORMATS = {"bf16": 0, "fp8": 1}   # MC_KV_*
+
+    def __init__(self, decoder: Decoder, batch: int, wide: bool = False, kv=None):
         self.decoder = decoder
         self.B = batch
         self.cfg = decoder.cfg
         self.np_T = decoder.np_T
         self._h = C.c_void_p()
+        if kv is not None:
+            if not wide:
+                raise ValueError("Batch(kv=...) goes through mc_kv_batch_create: pass wide=True")
+            _check(capi().mc_kv_batch_create(decoder._h, batch, self.KV_FORMATS.get(kv, kv), C.byref(self._h)))
+            return
         create = capi().mc_wide_batch_create if wide else capi().mc_batch_create
         _check(create(decoder._h, batch, C.byref(self._h)))
+
+    @property
+    def kv_format(self) -> str:
+        """what the rows' caches hold: "bf16" or "fp8" (Part 2o)"""
+        return {v: k for k, v in self.KV_FORMATS.items()}[capi().mc_kv_batch_format(self._h)]
+
+    @property
+    def kv_bytes(self) -> int:
+        """the bytes of the rows' caches, all layers and planes"""
+        return int(capi().mc_kv_batch_bytes(self._h))
 
     def size(self) -> int:
         return capi().mc_batch_size(self._h)
