@@ -836,11 +836,12 @@ mc_status mc_logprobs_get_verify(mc_batch* b, float* pick_logprobs, int32_t* top
  *             which return bfloat16 deq values in the row's logical order, rolled rows included, mc_rolling_fork_row, which copies
  *             the bytes and exponents as they lie, and everything that never touches a cache: Parts 2k, 2l, 2n, seeds,
  *             mc_batch_get_logits.
- *   refused   mc_rows_prefill, mc_extend_rows, mc_verify_rows, mc_tree_verify: MC_ERR_INVALID_ARGUMENT before anything is enqueued,
+ *   refused   (by default) mc_rows_prefill, mc_extend_rows, mc_verify_rows, mc_tree_verify: MC_ERR_INVALID_ARGUMENT before anything is enqueued,
  *             "<call>: the batch holds an fp8 cache, ..."; the rows' lengths stay.  A prompt reaches an fp8 batch through the decoder's
- *             prompt pass and mc_batch_fork, or through mc_batch_import_kv.
+ *             prompt pass and mc_batch_fork, or through mc_batch_import_kv.  (Part 2p: a switch per batch admits the first three.)
  *   the rows  the row contract holds: a row's tokens, logits and K / V do not depend on B, its index or the other rows.
- * Not covered: the packed passes and both verify calls, the batch-1 decoder, float32 decoders, head_dim 256, formats other than e4m3.
+ * Not covered: the packed passes and both verify calls by default (Part 2p admits three of them behind a switch), the batch-1 decoder, float32
+ * decoders, head_dim 256, formats other than e4m3.
  * ------------------------------------------------------------------------------------------ */
 #define MC_KV_BF16 0
 #define MC_KV_FP8 1
@@ -850,6 +851,23 @@ mc_status mc_logprobs_get_verify(mc_batch* b, float* pick_logprobs, int32_t* top
 mc_status mc_kv_batch_create(mc_decoder* d, int32_t batch, int32_t kv_format, mc_batch** out);
 int32_t mc_kv_batch_format(const mc_batch* b); /* MC_KV_*; MC_KV_BF16 for a null batch and for every other create call's batch */
 uint64_t mc_kv_batch_bytes(const mc_batch* b); /* the bytes of the rows' caches, all layers and planes; 0 for a null batch */
+
+/* ================================================================================================
+ * Part 2p -- the packed passes on an fp8 batch, opt-in per batch.  Part 2o refuses mc_rows_prefill, mc_extend_rows, mc_verify_rows and
+ * mc_tree_verify on an fp8 batch; with this switch on, the first three run on it: the rope + cache write stores quant of what the bfloat16
+ * batch would have stored, and the packed and the extend attention read the byte and exponent planes (kernels/kv8_rows_kernels.hip).  Part 2o's
+ * rule holds for them unchanged -- every packed row computes bit for bit what a bfloat16 batch computes whose caches hold deq(quant(K)),
+ * deq(quant(V)) -- and each call keeps its own admission, refusals, texts and row contract: a row's tokens, picks, logits and K / V do not
+ * depend on B, its index or the other rows in the call.  mc_verify_rows works with Part 2m's settings and Part 2n's records as on a bfloat16
+ * batch: the head, the picks and the acceptance never touch a cache.
+ *   off (the default)  every text and behaviour is Part 2o's.
+ *   on                 mc_tree_verify is still refused, with Part 2o's text: a tree needs a byte form of its rope + cache write, of the tree
+ *                      attention and of the compaction of the accepted path.
+ * The switch has no effect on a bfloat16 batch.  on other than 0 or 1: MC_ERR_INVALID_ARGUMENT, "mc_kv_packed_set: on must be 0 or 1".
+ * Not covered: mc_tree_verify, the batch-1 decoder, head_dim 256, float32 decoders.
+ * ------------------------------------------------------------------------------------------ */
+mc_status mc_kv_packed_set(mc_batch* b, int32_t on);
+int32_t mc_kv_packed_enabled(const mc_batch* b); /* 0 for a null batch */
 
 /* Host-side helpers shared by tests and the synthetic initialiser. */
 /* value in [-7,7] (bits = 4) or [-127,127] (bits = 8), zero mean, of element (row, col) of matrix `matrix_id` */

@@ -603,6 +603,9 @@ make_kv_batch(mc_decoder* decoder, std::int32_t batch, std::int32_t kv_format)
 }
 inline std::int32_t kv_format(const shared_batch& b) { return mc_kv_batch_format(b.get()); }
 inline std::uint64_t kv_bytes(const shared_batch& b) { return mc_kv_batch_bytes(b.get()); }
+/// Part 2p: an fp8 batch takes mc_rows_prefill, mc_extend_rows and mc_verify_rows while the switch is on (no effect on a bfloat16 batch).
+inline void set_kv_packed(const shared_batch& b, bool on) { check(mc_kv_packed_set(b.get(), on ? 1 : 0)); }
+inline bool kv_packed(const shared_batch& b) { return mc_kv_packed_enabled(b.get()) != 0; }
 
 } // namespace hip
 } // namespace metalchat

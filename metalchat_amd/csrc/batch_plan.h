@@ -116,11 +116,13 @@ kv_format_refusal(const mc_decoder_config& c, int32_t kv_format)
     if (kv_format == MC_KV_FP8 && c.max_seq_len % 8 != 0) return "an fp8 cache needs max_seq_len % 8 == 0";
     return "";
 }
-// the four packed calls on a batch whose cache is fp8: refused before anything is enqueued ("" = a bfloat16 cache)
+// the four packed calls on a batch whose cache is fp8: refused before anything is enqueued ("" = a bfloat16 cache).  packed_on (Part 2p,
+// mc_kv_packed_set): the three calls over plain chunks are admitted; a tree (mc_tree_verify) stays refused -- it would need a byte form of
+// mc_tv_rope_cache*, the TREE attention and mc_tv_compact_bfloat
 inline std::string
-kv_packed_refusal(const char* who, int kv_format)
+kv_packed_refusal(const char* who, int kv_format, bool packed_on = false, bool tree = false)
 {
-    if (kv_format == MC_KV_BF16) return "";
+    if (kv_format == MC_KV_BF16 || (packed_on && !tree)) return "";
     return std::string(who) + ": the batch holds an fp8 cache, which the packed passes do not read or write (prompts reach it through mc_batch_fork or mc_batch_import_kv)";
 }
 

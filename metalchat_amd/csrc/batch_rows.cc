@@ -25,7 +25,8 @@ rows_pass(mc_batch* b, const char* who, bool extend, const int32_t* tokens, cons
 {
     const mc_decoder_config& c = b->p.cfg;
     const int B = b->B;
-    if (mc_status s = refuse(kv_packed_refusal(who, b->kv_format)); s != MC_OK) return s; // (Part 2o: nothing enqueued, the lengths as they were)
+    // (Part 2o: nothing enqueued, the lengths as they were; Part 2p: the batch's switch admits the three calls over plain chunks)
+    if (mc_status s = refuse(kv_packed_refusal(who, b->kv_format, b->kv_packed_on, v && v->parents)); s != MC_OK) return s;
     // check (rows_plan.h: the admission, the tables and the scratch sizes are plain arithmetic there)
     const bool tree = v && v->parents;
     const rows_counts n = rows_check(who, tokens, lens, positions, b->lengths.data(), B, c.max_seq_len, c.vocab, v != nullptr);
@@ -79,6 +80,10 @@ rows_pass(mc_batch* b, const char* who, bool extend, const int32_t* tokens, cons
     pk.vt = b->vt;
     pk.B = B;
     pk.cache_stride = b->cache_elems;
+    pk.kv_format = b->kv_format; // (an fp8 cache: the same element counts in bytes, and the exponent planes)
+    pk.kexp = b->kexp;
+    pk.vexp = b->vexp;
+    pk.exp_stride = b->exp_elems();
     pk.fcos = b->fcos;
     pk.fsin = b->fsin;
     pk.x_out = b->x;
@@ -195,6 +200,23 @@ mc_verify_get_logits(mc_batch* b, void* logits_T)
     MC_HIP(hipStreamSynchronize(b->p.stream));
     MC_HIP(hipMemcpy(logits_T, b->vs.logits, (size_t)b->vs.rows * b->p.cfg.vocab * 2, hipMemcpyDeviceToHost));
     return MC_OK;
+}
+
+// ---- Part 2p: the packed passes on an fp8 batch ----
+
+mc_status
+mc_kv_packed_set(mc_batch* b, int32_t on)
+{
+    if (!b) return fail(MC_ERR_INVALID_ARGUMENT, "mc_kv_packed_set: null argument");
+    if (on != 0 && on != 1) return fail(MC_ERR_INVALID_ARGUMENT, "mc_kv_packed_set: on must be 0 or 1");
+    b->kv_packed_on = on == 1;
+    return MC_OK;
+}
+
+int32_t
+mc_kv_packed_enabled(const mc_batch* b)
+{
+    return b && b->kv_packed_on ? 1 : 0;
 }
 
 // ---- Part 2n: the records of the last verify call (the switch and mc_logprobs_get: batch_settings.cc) ----

@@ -65,6 +65,12 @@ struct packed_prefill {
     void* vt = nullptr;
     int B = 0;
     uint64_t cache_stride = 0;
+    // an fp8 cache (Part 2p): kc / vt hold bytes -- the same element counts, one byte each -- and every cache vector has an exponent, layer l, batch
+    // row r at kexp / vexp + (l * B + r) * exp_stride; the rope + cache write and the attention then take their mc_pp8_* / mc_px8_* names (kernels/kv8_rows_kernels.hip)
+    int kv_format = MC_KV_BF16;
+    int8_t* kexp = nullptr;
+    int8_t* vexp = nullptr;
+    uint64_t exp_stride = 0;
     const float* fcos = nullptr;    // the batch's rope table, rows = positions [0, max_seq_len)
     const float* fsin = nullptr;
     void* x_out = nullptr;          // [B][dim]: the last row of each segment lands in its batch row

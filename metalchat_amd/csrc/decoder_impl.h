@@ -412,7 +412,8 @@ struct mc_decoder {
     gemm_done gemm_to_parts(const linear_w& L, const void* X, int M);
     mc_status gemm(const linear_w& L, int epi, const void* X, void* Y, const void* res, int M);
     mc_status norm_rows(const void* x, const void* w, const void* res, void* y, int M, float mu);
-    mc_status qkv_rope_cache(const layer_w& L, void* kc, void* vt, int M, int start_pos, int rope_pos, float mu, const packed_prefill* pk);
+    mc_status qkv_rope_cache(const layer_w& L, void* kc, void* vt, int M, int start_pos, int rope_pos, float mu, const packed_prefill* pk, int8_t* kexp = nullptr,
+                             int8_t* vexp = nullptr);
     mc_status gemm_residual(const linear_w& W, const void* X, const void* res, void* out, const void* post_w, const void* next_w, const char* label, int M, float mu, bool* xn_done);
     mc_status run_prefill(int M, int cache_pos, int rope_pos, int window, const void* rows_in, const packed_prefill* pk = nullptr);
 };

@@ -226,7 +226,8 @@ mc_decoder::norm_rows(const void* x, const void* w, const void* res, void* y, in
 // wq|wk|wv of the M rows in pf_xn, then rope + cache write (q rows into pf_q, k and v into kc / vt) in the one form that fits -- packed / tree (pk), four
 // pairs per thread, one pair -- reading the GEMM's rows (pf_qkv) or, where it split K, its partial sums
 mc_status
-mc_decoder::qkv_rope_cache(const layer_w& L, void* kc, void* vt, int M, int start_pos, int rope_pos, float mu, const packed_prefill* pk)
+mc_decoder::qkv_rope_cache(const layer_w& L, void* kc, void* vt, int M, int start_pos, int rope_pos, float mu, const packed_prefill* pk, int8_t* kexp,
+                           int8_t* vexp)
 {
     const int H = cfg.n_heads, KV = cfg.n_kv_heads, hd = cfg.head_dim;
     const gemm_done g = gemm_to_parts(L.qkv, pf_xn, M);
@@ -237,13 +238,17 @@ mc_decoder::qkv_rope_cache(const layer_w& L, void* kc, void* vt, int M, int star
         if (s != MC_OK) return s;
     }
     // rope + cache write in the form and grid prefill_plan.h plan_rope gives
-    const rope_plan R = plan_rope(penv(), M, parts, pk ? (pk->nodes ? 2 : 1) : 0, L.q_norm || L.k_norm);
+    const bool f8 = pk && pk->kv_format == MC_KV_FP8; // (kexp, vexp: this layer of every batch row)
+    const rope_plan R = plan_rope(penv(), M, parts, pk ? (pk->nodes ? 2 : 1) : 0, L.q_norm || L.k_norm, pk ? pk->kv_format : MC_KV_BF16);
     arg_pack a = parts ? pack((const void*)pf_part, g.splits, (uint32_t)M, pf_q) : (pk ? pack((const void*)pf_qkv, (uint32_t)M, pf_q) : pack(pf_qkv, pf_q));
     switch (R.form) {
     case rope_form::packed:
     case rope_form::tree: // (kc, vt: this layer of every batch row)
-        push_all(a, pk->segs, (uint32_t)pk->nseg, kc, vt, pk->cache_stride, pk->fcos, pk->fsin, (uint32_t)H, (uint32_t)KV, (uint32_t)hd,
-                 (uint32_t)cfg.max_seq_len);
+        push_all(a, pk->segs, (uint32_t)pk->nseg, kc, vt);
+        if (f8) push_all(a, kexp, vexp);
+        a.push(pk->cache_stride);
+        if (f8) a.push(pk->exp_stride);
+        push_all(a, pk->fcos, pk->fsin, (uint32_t)H, (uint32_t)KV, (uint32_t)hd, (uint32_t)cfg.max_seq_len);
         if (pk->nodes) a.push(pk->nodes);
         break;
     case rope_form::v4:
@@ -331,9 +336,14 @@ mc_decoder::run_prefill(int M, int cache_pos, int rope_pos, int window, const vo
         }
         xn_ready = false;
         // packed rows: layer li of every batch row's caches
-        void* pk_kc = pk ? (char*)pk->kc + (size_t)li * pk->B * pk->cache_stride * tb : nullptr;
-        void* pk_vt = pk ? (char*)pk->vt + (size_t)li * pk->B * pk->cache_stride * tb : nullptr;
-        s = qkv_rope_cache(L, pk ? pk_kc : L.kc, pk ? pk_vt : L.vt, M, start_pos, rope_pos, mu, pk);
+        // (an fp8 cache: one byte per element, and the two exponent planes beside them)
+        const bool f8 = pk && pk->kv_format == MC_KV_FP8;
+        const size_t kvb = f8 ? 1 : (size_t)tb;
+        void* pk_kc = pk ? (char*)pk->kc + (size_t)li * pk->B * pk->cache_stride * kvb : nullptr;
+        void* pk_vt = pk ? (char*)pk->vt + (size_t)li * pk->B * pk->cache_stride * kvb : nullptr;
+        int8_t* pk_kx = f8 ? pk->kexp + (size_t)li * pk->B * pk->exp_stride : nullptr;
+        int8_t* pk_vx = f8 ? pk->vexp + (size_t)li * pk->B * pk->exp_stride : nullptr;
+        s = qkv_rope_cache(L, pk ? pk_kc : L.kc, pk ? pk_vt : L.vt, M, start_pos, rope_pos, mu, pk, pk_kx, pk_vx);
         if (s != MC_OK) return s;
         const uint32_t win = (gemma && L.rope_table == 1) ? (uint32_t)window : 0u;
         if (pk && pk->extend) {
@@ -342,17 +352,23 @@ mc_decoder::run_prefill(int M, int cache_pos, int rope_pos, int window, const vo
             // plan_extend_attention).  A group is as many whole tiles as the scratch holds (one group unless the call is huge).
             // Chunks that are trees (mc_tree_verify, pk->nodes): the mc_tv_* forms of the first two, the node table behind their arguments.
             s = timed("attention", [&] {
-                const extend_plan E = plan_extend_attention(penv(), pk->nodes != nullptr);
+                const extend_plan E = plan_extend_attention(penv(), pk->nodes != nullptr, pk->kv_format);
                 for (int g = 0; g < pk->ngroups; g++) {
                     const uint32_t e0 = (uint32_t)pk->groups[g].first, ne = (uint32_t)pk->groups[g].count;
-                    arg_pack as = pack(pf_q, pk->segs, pk->ranges, e0, (const void*)pk_kc, pk->cache_stride, pk->sums, (uint32_t)H,
-                                       (uint32_t)(H / KV), (uint32_t)cfg.max_seq_len, scale_T, (const void*)pf_etab);
+                    arg_pack as = pack(pf_q, pk->segs, pk->ranges, e0, (const void*)pk_kc);
+                    if (f8) as.push((const void*)pk_kx);
+                    as.push(pk->cache_stride);
+                    if (f8) as.push(pk->exp_stride);
+                    push_all(as, pk->sums, (uint32_t)H, (uint32_t)(H / KV), (uint32_t)cfg.max_seq_len, scale_T, (const void*)pf_etab);
                     if (pk->nodes) as.push(pk->nodes);
                     mc_status ls = launch(E.sums, E.heads, ne, 1, 256, 0, std::move(as));
                     if (ls != MC_OK) return ls;
-                    arg_pack ap = pack(pf_q, pk->segs, pk->ranges, e0, (const void*)pk_kc, (const void*)pk_vt, pk->cache_stride,
-                                       (const void*)pk->sums, pk->part, pf_att, (uint32_t)H, (uint32_t)(H / KV), (uint32_t)cfg.max_seq_len, scale_T,
-                                       (const void*)pf_etab);
+                    arg_pack ap = pack(pf_q, pk->segs, pk->ranges, e0, (const void*)pk_kc, (const void*)pk_vt);
+                    if (f8) push_all(ap, (const void*)pk_kx, (const void*)pk_vx);
+                    ap.push(pk->cache_stride);
+                    if (f8) ap.push(pk->exp_stride);
+                    push_all(ap, (const void*)pk->sums, pk->part, pf_att, (uint32_t)H, (uint32_t)(H / KV), (uint32_t)cfg.max_seq_len, scale_T,
+                             (const void*)pf_etab);
                     if (pk->nodes) ap.push(pk->nodes);
                     ls = launch(E.pv, E.heads, ne, 1, 256, 0, std::move(ap));
                     if (ls != MC_OK) return ls;
@@ -367,10 +383,13 @@ mc_decoder::run_prefill(int M, int cache_pos, int rope_pos, int window, const vo
         } else if (pk) {
             // (prefill_plan.h plan_packed_attention: the two-heads rule of one prompt over the tiles of all segments)
             s = timed("attention", [&] {
-                const attn_plan A = plan_packed_attention(penv(), pk->ntiles);
-                return launch(A.name, A.gx, A.gy, 1, A.block, 0,
-                              pack(pf_q, pk->segs, pk->tiles, (const void*)pk_kc, (const void*)pk_vt, pk->cache_stride, pf_att, (uint32_t)H,
-                                   (uint32_t)(H / KV), (uint32_t)cfg.max_seq_len, scale_T, (const void*)pf_etab));
+                const attn_plan A = plan_packed_attention(penv(), pk->ntiles, pk->kv_format);
+                arg_pack a = pack(pf_q, pk->segs, pk->tiles, (const void*)pk_kc, (const void*)pk_vt);
+                if (f8) push_all(a, (const void*)pk_kx, (const void*)pk_vx);
+                a.push(pk->cache_stride);
+                if (f8) a.push(pk->exp_stride);
+                push_all(a, pf_att, (uint32_t)H, (uint32_t)(H / KV), (uint32_t)cfg.max_seq_len, scale_T, (const void*)pf_etab);
+                return launch(A.name, A.gx, A.gy, 1, A.block, 0, std::move(a));
             });
             if (s != MC_OK) return s;
         } else if (tb == 2 && !opt.pf_two_pass) {

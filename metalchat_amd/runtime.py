@@ -203,6 +203,8 @@ def capi() -> C.CDLL:
         "mc_kv_batch_create": (i32, [vp, i32, i32, pvp]),
         "mc_kv_batch_format": (i32, [vp]),
         "mc_kv_batch_bytes": (u64, [vp]),
+        "mc_kv_packed_set": (i32, [vp, i32]),
+        "mc_kv_packed_enabled": (i32, [vp]),
         "mc_batch_release": (None, [vp]),
         "mc_batch_size": (i32, [vp]),
         "mc_batch_fork": (i32, [vp, i32, i32]),
@@ -824,7 +826,8 @@ class Batch:
     wide=True (Part 2h): B <= 64, the same rows bit for bit; that entry also admits QLoRA decoders (Part 2i): int4 / int8 linears
     in groups of 32, each linear in a format of its own, LoRA adaptors of rank % 16 == 0 on the layer linears.  Keeps the decoder alive.
     kv="fp8" (Part 2o, with wide=True): the rows' caches hold e4m3 bytes and one exponent per cache vector, (hd + 1) / (2 hd) of the
-    bfloat16 bytes; the packed passes and the verify calls are refused on such a batch."""
+    bfloat16 bytes; the packed passes and the verify calls are refused on such a batch by default; set_kv_packed(True) (Part 2p) admits
+    prefill_rows, extend_rows and verify_rows."""
 
     KV_FORMATS = {"bf16": 0, "fp8": 1}   # MC_KV_*
 
@@ -851,6 +854,14 @@ class Batch:
     def kv_bytes(self) -> int:
         """the bytes of the rows' caches, all layers and planes"""
         return int(capi().mc_kv_batch_bytes(self._h))
+
+    def set_kv_packed(self, on: bool):
+        """Part 2p: an fp8 batch takes prefill_rows, extend_rows and verify_rows while the switch is on; no effect on a bfloat16 batch"""
+        _check(capi().mc_kv_packed_set(self._h, 1 if on else 0))
+
+    @property
+    def kv_packed(self) -> bool:
+        return capi().mc_kv_packed_enabled(self._h) == 1
 
     def size(self) -> int:
         return capi().mc_batch_size(self._h)
