@@ -838,9 +838,10 @@ mc_status mc_logprobs_get_verify(mc_batch* b, float* pick_logprobs, int32_t* top
  *             mc_batch_get_logits.
  *   refused   (by default) mc_rows_prefill, mc_extend_rows, mc_verify_rows, mc_tree_verify: MC_ERR_INVALID_ARGUMENT before anything is enqueued,
  *             "<call>: the batch holds an fp8 cache, ..."; the rows' lengths stay.  A prompt reaches an fp8 batch through the decoder's
- *             prompt pass and mc_batch_fork, or through mc_batch_import_kv.  (Part 2p: a switch per batch admits the first three.)
+ *             prompt pass and mc_batch_fork, or through mc_batch_import_kv.  (Part 2p: a switch per batch admits the first three; Part 2q:
+ *             another admits mc_tree_verify.)
  *   the rows  the row contract holds: a row's tokens, logits and K / V do not depend on B, its index or the other rows.
- * Not covered: the packed passes and both verify calls by default (Part 2p admits three of them behind a switch), the batch-1 decoder, float32
+ * Not covered: the packed passes and both verify calls by default (Parts 2p and 2q admit them behind two switches), the batch-1 decoder, float32
  * decoders, head_dim 256, formats other than e4m3.
  * ------------------------------------------------------------------------------------------ */
 #define MC_KV_BF16 0
@@ -861,13 +862,31 @@ uint64_t mc_kv_batch_bytes(const mc_batch* b); /* the bytes of the rows' caches,
  * depend on B, its index or the other rows in the call.  mc_verify_rows works with Part 2m's settings and Part 2n's records as on a bfloat16
  * batch: the head, the picks and the acceptance never touch a cache.
  *   off (the default)  every text and behaviour is Part 2o's.
- *   on                 mc_tree_verify is still refused, with Part 2o's text: a tree needs a byte form of its rope + cache write, of the tree
- *                      attention and of the compaction of the accepted path.
+ *   on                 mc_tree_verify is still refused, with Part 2o's text: this switch never admits the tree, which has a switch of its own
+ *                      (Part 2q).
  * The switch has no effect on a bfloat16 batch.  on other than 0 or 1: MC_ERR_INVALID_ARGUMENT, "mc_kv_packed_set: on must be 0 or 1".
- * Not covered: mc_tree_verify, the batch-1 decoder, head_dim 256, float32 decoders.
+ * Not covered: mc_tree_verify, which Part 2q admits, the batch-1 decoder, head_dim 256, float32 decoders.
  * ------------------------------------------------------------------------------------------ */
 mc_status mc_kv_packed_set(mc_batch* b, int32_t on);
 int32_t mc_kv_packed_enabled(const mc_batch* b); /* 0 for a null batch */
+
+/* ================================================================================================
+ * Part 2q -- mc_tree_verify on an fp8 batch, opt-in per batch.  A switch of its own, off by default and independent of mc_kv_packed_set: it
+ * governs mc_tree_verify only, and mc_kv_packed_set never admits the tree.  With it on, the call runs on the byte and exponent planes
+ * (kernels/kv8_tree_kernels.hip): node i of a row's tree is quantised into slot pos + i, rotated for position pos + depth(i); the tree attention
+ * builds its operands from bytes; and the accepted path's vectors -- the head_dim bytes and the exponent of each, copied unchanged, nothing
+ * quantised again -- move from slot pos + path[d] to slot pos + d in every layer.  Part 2o's rule holds unchanged: every node computes bit for bit
+ * what a bfloat16 batch computes whose caches hold deq(quant(K)), deq(quant(V)), and after the call deq of slot pos + d is deq of what was written
+ * for node path[d].  The call keeps all of its own checks, refusals, texts and its row contract; greedy rows and Part 2m's settings are taken as on
+ * a bfloat16 batch, and Part 2n's records ride along: the head, the picks and the walk never touch a cache.
+ *   off (the default)  mc_tree_verify on an fp8 batch is refused with Part 2o's text, before anything is enqueued; the rows' lengths stay.
+ *   on                 admitted.  mc_rows_prefill, mc_extend_rows and mc_verify_rows stay under mc_kv_packed_set.
+ * The switch is accepted and changes nothing on a bfloat16 batch.  on other than 0 or 1: MC_ERR_INVALID_ARGUMENT, "mc_kv_tree_set: on must be 0
+ * or 1"; a null batch: "mc_kv_tree_set: null argument".
+ * Not covered: the batch-1 decoder, head_dim 256, float32 decoders, formats other than e4m3.
+ * ------------------------------------------------------------------------------------------ */
+mc_status mc_kv_tree_set(mc_batch* b, int32_t on);
+int32_t mc_kv_tree_enabled(const mc_batch* b); /* 0 for a null batch */
 
 /* Host-side helpers shared by tests and the synthetic initialiser. */
 /* value in [-7,7] (bits = 4) or [-127,127] (bits = 8), zero mean, of element (row, col) of matrix `matrix_id` */

@@ -606,6 +606,9 @@ inline std::uint64_t kv_bytes(const shared_batch& b) { return mc_kv_batch_bytes(
 /// Part 2p: an fp8 batch takes mc_rows_prefill, mc_extend_rows and mc_verify_rows while the switch is on (no effect on a bfloat16 batch).
 inline void set_kv_packed(const shared_batch& b, bool on) { check(mc_kv_packed_set(b.get(), on ? 1 : 0)); }
 inline bool kv_packed(const shared_batch& b) { return mc_kv_packed_enabled(b.get()) != 0; }
+/// Part 2q: an fp8 batch takes mc_tree_verify while the switch is on -- a switch of its own (no effect on a bfloat16 batch).
+inline void set_kv_tree(const shared_batch& b, bool on) { check(mc_kv_tree_set(b.get(), on ? 1 : 0)); }
+inline bool kv_tree(const shared_batch& b) { return mc_kv_tree_enabled(b.get()) != 0; }
 
 } // namespace hip
 } // namespace metalchat

@@ -20,7 +20,7 @@ SO = os.path.join(LIB, "libmetalchat_hip.so")
 
 KERNEL_SOURCES = [os.path.join(CSRC, "kernels", f) for f in (
     "metalchat_kernels.hip", "ref_kernels.hip", "gemv_kernels.hip", "decode_kernels.hip", "attn_block_kernels.hip",
-    "synth_kernels.hip", "sampler_kernels.hip", "prefill_kernels.hip", "batch_kernels.hip", "packed_kernels.hip", "extend_kernels.hip", "verify_kernels.hip", "wide_kernels.hip", "tree_kernels.hip", "logit_kernels.hip", "logprob_kernels.hip", "kv8_kernels.hip", "kv8_rows_kernels.hip", "common.h", "abi.h", "handoff.h", "gemv.h", "gemv_norm.h", "gemv_ksplit.h", "synth.h", "pf_gemm8.h")]
+    "synth_kernels.hip", "sampler_kernels.hip", "prefill_kernels.hip", "batch_kernels.hip", "packed_kernels.hip", "extend_kernels.hip", "verify_kernels.hip", "wide_kernels.hip", "tree_kernels.hip", "logit_kernels.hip", "logprob_kernels.hip", "kv8_kernels.hip", "kv8_rows_kernels.hip", "kv8_tree_kernels.hip", "common.h", "abi.h", "handoff.h", "gemv.h", "gemv_norm.h", "gemv_ksplit.h", "synth.h", "pf_gemm8.h")]
 # the host library: every unit goes into the one hipcc command, units and headers together are what makes it stale
 HOST_UNITS = [os.path.join(CSRC, f) for f in ("backend.cc", "decoder.cc", "weights.cc", "prefill.cc", "prefill_blaslt.cc", "pipeline.cc", "batch.cc",
                                                "batch_rows.cc", "batch_cache.cc", "batch_settings.cc", "model_io.cc", "text.cc")]
@@ -125,6 +125,13 @@ def build_prefill_plan_test(force: bool = False) -> str:
 def build_kv8_rows_plan_test(force: bool = False) -> str:
     """tests/cpp/test_kv8_rows_plan: the names the packed passes launch on an fp8 batch (csrc/prefill_plan.h) -- no HIP and no host library."""
     return _build_cpp_test("test_kv8_rows_plan", [os.path.join(CSRC, "prefill_plan.h"), *_PLAN_HEADERS], force, False)
+
+
+def build_kv8_tree_plan_test(force: bool = False) -> str:
+    """tests/cpp/test_kv8_tree_plan: the names mc_tree_verify launches on an fp8 batch (csrc/prefill_plan.h, csrc/batch_plan.h) and the tree
+    switch's refusal -- no HIP and no host library."""
+    headers = [os.path.join(CSRC, f) for f in ("prefill_plan.h", "batch_plan.h", "rows_plan.h", "sampler_plan.h")] + [os.path.join(CSRC, "kernels", "abi.h")]
+    return _build_cpp_test("test_kv8_tree_plan", [*headers, *_PLAN_HEADERS], force, False)
 
 
 def build_rows_plan_test(force: bool = False) -> str:

@@ -208,6 +208,9 @@ mc_batch::run(const batch_launch& l, const call_args& a)
     case op::v_count:
         return launch(l.L, pack(segs, a.ids, (const int32_t*)vs.out, paths, (const row_logits*)logits_tab_dev, counts_dev, vocab));
     case op::v_compact:
+        if (fp8()) // (mc_tv8_compact: layer 0's four planes and both strides)
+            return launch(l.L, pack(segs, (const int32_t*)vs.out, paths, kc, vt, kexp, vexp, (uint64_t)cache_elems, (uint64_t)exp_elems(), (uint32_t)B,
+                                    (uint32_t)cfg.n_kv_heads, (uint32_t)cfg.head_dim, (uint32_t)cfg.max_seq_len));
         return launch(l.L, pack(segs, (const int32_t*)vs.out, paths, kc, vt, (uint64_t)cache_elems, (uint32_t)B, (uint32_t)cfg.n_kv_heads, (uint32_t)cfg.head_dim,
                                 (uint32_t)cfg.max_seq_len));
     }

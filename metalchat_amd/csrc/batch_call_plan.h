@@ -198,7 +198,7 @@ plan_verify_call(const batch_fixed& f, const call_settings& s, const int32_t* le
         if (!vp.refusal.empty()) return c.refuse(vp.refusal);
         vl = plan_verify_logits(lens, s.logit_rows, vocab, M, nseg);
     }
-    const verify_plan v = plan_verify_head(f.head, f.cfg, f.n_layers, M, nseg, c.tree);
+    const verify_plan v = plan_verify_head(f.head, f.cfg, f.n_layers, M, nseg, c.tree, f.kv_format);
     c.add(op::v_norm, v.norm);
     c.add(op::v_head, v.head);
     if (vl.any) c.add(op::v_process, vl.process);

@@ -109,6 +109,7 @@ struct mc_batch {
     int kv_format = MC_KV_BF16;           // mc_kv_batch_create: MC_KV_FP8 = the caches hold bytes and, per cache vector, an exponent
     int8_t *kexp = nullptr, *vexp = nullptr; // [layer][B][n_kv][max_seq]: the exponents of an fp8 cache's K and V vectors
     bool kv_packed_on = false;            // mc_kv_packed_set (Part 2p): an fp8 batch takes mc_rows_prefill, mc_extend_rows and mc_verify_rows
+    bool kv_tree_on = false;              // mc_kv_tree_set (Part 2q): an fp8 batch takes mc_tree_verify
     size_t kv_bytes = 0;                  // what the caches took: all planes of all layers and rows
     void *x = nullptr, *xn = nullptr;     // [B][dim]
     void *qkv = nullptr;                  // [B][(H + 2 KV) hd]

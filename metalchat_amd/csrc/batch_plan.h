@@ -117,12 +117,12 @@ kv_format_refusal(const mc_decoder_config& c, int32_t kv_format)
     return "";
 }
 // the four packed calls on a batch whose cache is fp8: refused before anything is enqueued ("" = a bfloat16 cache).  packed_on (Part 2p,
-// mc_kv_packed_set): the three calls over plain chunks are admitted; a tree (mc_tree_verify) stays refused -- it would need a byte form of
-// mc_tv_rope_cache*, the TREE attention and mc_tv_compact_bfloat
+// mc_kv_packed_set): the three calls over plain chunks are admitted, and never a tree (mc_tree_verify) -- that call has a switch of its own, tree_on
+// (Part 2q, mc_kv_tree_set; kernels/kv8_tree_kernels.hip), which admits nothing else
 inline std::string
-kv_packed_refusal(const char* who, int kv_format, bool packed_on = false, bool tree = false)
+kv_packed_refusal(const char* who, int kv_format, bool packed_on = false, bool tree = false, bool tree_on = false)
 {
-    if (kv_format == MC_KV_BF16 || (packed_on && !tree)) return "";
+    if (kv_format == MC_KV_BF16 || (tree ? tree_on : packed_on)) return "";
     return std::string(who) + ": the batch holds an fp8 cache, which the packed passes do not read or write (prompts reach it through mc_batch_fork or mc_batch_import_kv)";
 }
 
@@ -382,13 +382,19 @@ plan_logprobs(bool enabled, int top_n, int vocab, int R, bool ragged)
 // ---------------------------------------------------------------- the head of a verify call
 
 // mc_verify_rows: the final norm, the head and a greedy pick for each of the M packed rows, then per segment the acceptance of its drafts.
-// tree (mc_tree_verify): the walk in place of the prefix rule, then the accepted path's K / V moved into place in every layer (compact)
+// tree (mc_tree_verify): the walk in place of the prefix rule, then the accepted path's K / V moved into place in every layer (compact); on an fp8
+// batch (kv_format) mc_tv8_compact, whose grid follows its owners: 16-byte words of K, bytes of V, the two exponent planes (kv8_tree_kernels.hip)
+inline unsigned
+tv8_compact_owners(const mc_decoder_config& c)
+{
+    return (unsigned)(c.n_kv_heads * (c.head_dim / 16) + c.n_kv_heads * c.head_dim + 2 * c.n_kv_heads);
+}
 struct verify_plan {
     bool tree = false;
     launch_plan norm, head, argmax, accept, compact;
 };
 inline verify_plan
-plan_verify_head(const linear_shape& L, const mc_decoder_config& c, int n_layers, int M, int nseg, bool tree)
+plan_verify_head(const linear_shape& L, const mc_decoder_config& c, int n_layers, int M, int nseg, bool tree, int kv_format = MC_KV_BF16)
 {
     verify_plan v;
     v.tree = tree;
@@ -398,7 +404,8 @@ plan_verify_head(const linear_shape& L, const mc_decoder_config& c, int n_layers
     v.argmax = {"mc_v_argmax_bfloat", 1, (unsigned)M, 1, 1024, 0};
     const unsigned gx = std::min(64u, ((unsigned)c.vocab / 8 + 255) / 256);
     v.accept = {tree ? "mc_tv_accept" : "mc_v_accept", gx, (unsigned)nseg, 1, 256, 0};
-    if (tree) v.compact = {"mc_tv_compact_bfloat", ((unsigned)(c.n_kv_heads * c.head_dim) + 255) / 256, (unsigned)nseg, (unsigned)n_layers, 256, 0};
+    if (tree && kv_format == MC_KV_FP8) v.compact = {"mc_tv8_compact", (tv8_compact_owners(c) + 255) / 256, (unsigned)nseg, (unsigned)n_layers, 256, 0};
+    else if (tree) v.compact = {"mc_tv_compact_bfloat", ((unsigned)(c.n_kv_heads * c.head_dim) + 255) / 256, (unsigned)nseg, (unsigned)n_layers, 256, 0};
     return v;
 }
 

@@ -25,8 +25,9 @@ rows_pass(mc_batch* b, const char* who, bool extend, const int32_t* tokens, cons
 {
     const mc_decoder_config& c = b->p.cfg;
     const int B = b->B;
-    // (Part 2o: nothing enqueued, the lengths as they were; Part 2p: the batch's switch admits the three calls over plain chunks)
-    if (mc_status s = refuse(kv_packed_refusal(who, b->kv_format, b->kv_packed_on, v && v->parents)); s != MC_OK) return s;
+    // (Part 2o: nothing enqueued, the lengths as they were; Part 2p: the batch's switch admits the three calls over plain chunks; Part 2q: a
+    // switch of its own admits the tree)
+    if (mc_status s = refuse(kv_packed_refusal(who, b->kv_format, b->kv_packed_on, v && v->parents, b->kv_tree_on)); s != MC_OK) return s;
     // check (rows_plan.h: the admission, the tables and the scratch sizes are plain arithmetic there)
     const bool tree = v && v->parents;
     const rows_counts n = rows_check(who, tokens, lens, positions, b->lengths.data(), B, c.max_seq_len, c.vocab, v != nullptr);
@@ -217,6 +218,23 @@ int32_t
 mc_kv_packed_enabled(const mc_batch* b)
 {
     return b && b->kv_packed_on ? 1 : 0;
+}
+
+// ---- Part 2q: mc_tree_verify on an fp8 batch ----
+
+mc_status
+mc_kv_tree_set(mc_batch* b, int32_t on)
+{
+    if (!b) return fail(MC_ERR_INVALID_ARGUMENT, "mc_kv_tree_set: null argument");
+    if (on != 0 && on != 1) return fail(MC_ERR_INVALID_ARGUMENT, "mc_kv_tree_set: on must be 0 or 1");
+    b->kv_tree_on = on == 1;
+    return MC_OK;
+}
+
+int32_t
+mc_kv_tree_enabled(const mc_batch* b)
+{
+    return b && b->kv_tree_on ? 1 : 0;
 }
 
 // ---- Part 2n: the records of the last verify call (the switch and mc_logprobs_get: batch_settings.cc) ----

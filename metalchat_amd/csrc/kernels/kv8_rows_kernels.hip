@@ -86,11 +86,13 @@ kv8_deq8s(uint2 b, const float (&s)[8])
 // Rope + cache write over the segment table: pf_rope_cache_v4_body's grid, units and values (no q / k norm: a batch's decoder has none), q rows as
 // bfloat16; grid and block as mc_pp_rope_cache{,_parts}_bfloat
 // ------------------------------------------------------------------------------------------
-template <bool SPLITS>
+// TREE (kv8_tree_kernels.hip, mc_tree_verify on an fp8 batch): packed row r is node i of its segment's tree -- written to slot pos + i, rotated with rope
+// row pos + depth(i) (tree_kernels.hip tv_rows::at); the one difference
+template <bool SPLITS, bool TREE = false>
 __device__ __forceinline__ void
 pp8_rope_cache_body(const void* rows, uint32_t splits, uint32_t M, bf16_t* q_out, const pp_seg* segs, uint32_t nseg, uint8_t* kq, uint8_t* vq, int8_t* kexp,
                     int8_t* vexp, uint64_t cache_stride, uint64_t exp_stride, const float* fcos, const float* fsin, uint32_t H, uint32_t KV, uint32_t hd,
-                    uint32_t max_seq)
+                    uint32_t max_seq, const tv_node* nodes = nullptr)
 {
     __shared__ uint32_t pmax[16][16]; // [g][i]: a V tile's partial maxima
     const uint32_t half = hd / 2, lpu = hd / 8, nb = H + KV, NQ = (H + 2 * KV) * hd, per = blockDim.x / lpu;
@@ -107,13 +109,14 @@ pp8_rope_cache_body(const void* rows, uint32_t splits, uint32_t M, bf16_t* q_out
             for (int i = 0; i < 8; i++) x[i] = __uint_as_float((i & 1) ? (d[i >> 1] & 0xFFFF0000u) : (d[i >> 1] << 16));
         }
     };
-    // pp_rows::at: packed row r -> (batch row, slot = rope row)
-    auto at = [&](uint32_t r, uint32_t& row, uint32_t& slot) {
+    // pp_rows::at: packed row r -> (batch row, slot = rope row); TREE: tv_rows::at, rope row = pos + depth
+    auto at = [&](uint32_t r, uint32_t& row, uint32_t& slot, uint32_t& rope_row) {
         uint32_t s = 0;
         while (s + 1 < nseg && r >= (uint32_t)segs[s + 1].off) s++;
         const pp_seg g = segs[s];
         row = (uint32_t)g.row;
         slot = (uint32_t)g.pos + (r - (uint32_t)g.off);
+        rope_row = TREE ? (uint32_t)g.pos + (uint32_t)nodes[r].depth : slot;
     };
     auto mag = [](float v) { return __float_as_uint(v) >> 16 & 0x7FFFu; }; // (v is a bfloat16 value)
     if (blockIdx.x >= gq) { // (uniform)
@@ -131,8 +134,8 @@ pp8_rope_cache_body(const void* rows, uint32_t splits, uint32_t M, bf16_t* q_out
         __syncthreads();
         if (!live) return;
         for (uint32_t gg = 0; gg < lpu; gg++) amax = max(amax, pmax[gg][i]);
-        uint32_t row, slot;
-        at(r, row, slot);
+        uint32_t row, slot, rope_row;
+        at(r, row, slot, rope_row);
         const int32_t e = kv8_exponent(amax);
         const float inv = kv8_pow2(-e);
         uint8_t* dst = vq + row * cache_stride + ((size_t)kv * hd + 8 * g) * max_seq + slot;
@@ -148,11 +151,11 @@ pp8_rope_cache_body(const void* rows, uint32_t splits, uint32_t M, bf16_t* q_out
     const uint32_t unit = blockIdx.x * per + threadIdx.x / lpu, l = threadIdx.x % lpu;
     if (unit >= nb * M) return;
     const uint32_t b = unit % nb, r = unit / nb;
-    uint32_t row, slot;
-    at(r, row, slot);
+    uint32_t row, slot, rope_row;
+    at(r, row, slot, rope_row);
     float x[8];
     load8((size_t)r * NQ + (size_t)b * hd + 8 * l, x);
-    const size_t tr = (size_t)slot * half + 4 * l;
+    const size_t tr = (size_t)rope_row * half + 4 * l;
     const float4 c4 = *reinterpret_cast<const float4*>(fcos + tr), s4 = *reinterpret_cast<const float4*>(fsin + tr);
     const float c[4] = {c4.x, c4.y, c4.z, c4.w}, s[4] = {s4.x, s4.y, s4.z, s4.w};
     float o1[4], o2[4];
@@ -209,6 +212,8 @@ mc_pp8_rope_cache_parts_bfloat(const float* part, uint32_t splits, uint32_t M, b
 //                           wsum / inv_sum, pa's packing order, the MFMA order over t and j, the osum reduction
 //   px8_sums_body, _pv_body extend_kernels.hip px_sums_body / px_pv_body: the same list; px_tile::score itself is called
 // What is NOT mirrored, on purpose: the loads (bytes, exponents, all V tiles before the scores) and the V masks (kv8_slot_masks).
+// kv8_tree_kernels.hip instantiates pp8_rope_cache_body, px8_sums_body and px8_pv_body with TREE = true (mc_tv8_*): nothing is restated there, and the
+// template parameter leaves the code of the kernels of this file as it was.
 // ------------------------------------------------------------------------------------------
 template <uint32_t HD>
 __device__ __forceinline__ void
@@ -521,9 +526,10 @@ MC_PP_ATTN_F8(128)
 // The extend attention over the range table: px_sums_body / px_pv_body with the operands made from bytes.  The rows, the mask, the Q fragments and
 // the scores are px_tile's own (its kbase is not used); mc_px_reduce_* follows unchanged
 // ------------------------------------------------------------------------------------------
-template <uint32_t HD, int NH>
+// TREE: px_tile's tree select over the node table (kv8_tree_kernels.hip) -- the one difference, as in extend_kernels.hip
+template <uint32_t HD, int NH, bool TREE = false>
 struct px8_tile {
-    px_tile<HD, NH> t;
+    px_tile<HD, NH, TREE> t;
     const uint8_t* kbase;
     const int8_t* kx;
     __device__ __forceinline__ void
@@ -541,23 +547,24 @@ struct px8_tile {
     }
 };
 
-template <uint32_t HD, int NH>
-__device__ __forceinline__ px8_tile<HD, NH>
+template <uint32_t HD, int NH, bool TREE = false>
+__device__ __forceinline__ px8_tile<HD, NH, TREE>
 px8_tile_of(const bf16_t* Q, const pp_seg& g, const px_range& e, const uint8_t* kq, const int8_t* kexp, uint64_t cache_stride, uint64_t exp_stride,
-            uint32_t H, uint32_t n_rep, uint32_t max_seq, float scale, uint32_t h0)
+            uint32_t H, uint32_t n_rep, uint32_t max_seq, float scale, uint32_t h0, const tv_node* nodes = nullptr)
 {
-    px8_tile<HD, NH> t;
-    t.t = px_tile_of<HD, NH, false>(Q, g, e, reinterpret_cast<const bf16_t*>(kq), 0, H, n_rep, max_seq, scale, h0);
+    px8_tile<HD, NH, TREE> t;
+    t.t = px_tile_of<HD, NH, TREE>(Q, g, e, reinterpret_cast<const bf16_t*>(kq), 0, H, n_rep, max_seq, scale, h0, nodes);
     t.kbase = kq + (size_t)g.row * cache_stride + (size_t)(h0 / n_rep) * max_seq * HD;
     t.kx = kexp + (size_t)g.row * exp_stride + (size_t)(h0 / n_rep) * max_seq;
     return t;
 }
 
 // grid (H / NH, ranges of the launch), 256 threads
-template <uint32_t HD, int NH>
+template <uint32_t HD, int NH, bool TREE = false>
 __device__ __forceinline__ void
 px8_sums_body(const bf16_t* Q, const pp_seg* segs, const px_range* tab, uint32_t ebase, const uint8_t* kq, const int8_t* kexp, uint64_t cache_stride,
-              uint64_t exp_stride, float* sums, uint32_t H, uint32_t n_rep, uint32_t max_seq, float scale, const float* etab)
+              uint64_t exp_stride, float* sums, uint32_t H, uint32_t n_rep, uint32_t max_seq, float scale, const float* etab,
+              const tv_node* nodes = nullptr)
 {
     __shared__ float wsum[NH][4][16];
     __shared__ __attribute__((aligned(16))) float ewin[2 * pf_exp_window::N];
@@ -566,7 +573,7 @@ px8_sums_body(const bf16_t* Q, const pp_seg* segs, const px_range* tab, uint32_t
     const px_range e = tab[ebase + blockIdx.y];
     const pp_seg g = segs[e.seg];
     const uint32_t wave = threadIdx.x >> 6, h0 = blockIdx.x * NH;
-    const px8_tile<HD, NH> t = px8_tile_of<HD, NH>(Q, g, e, kq, kexp, cache_stride, exp_stride, H, n_rep, max_seq, scale, h0);
+    const px8_tile<HD, NH, TREE> t = px8_tile_of<HD, NH, TREE>(Q, g, e, kq, kexp, cache_stride, exp_stride, H, n_rep, max_seq, scale, h0, nodes);
     const uint32_t b_lo = (uint32_t)e.k_lo / 32, b_end = ((uint32_t)e.k_hi + 31) / 32;
     float rsum[NH];
 #pragma unroll
@@ -600,11 +607,11 @@ px8_sums_body(const bf16_t* Q, const pp_seg* segs, const px_range* tab, uint32_t
 }
 
 // grid (H / NH, ranges of the launch), 256 threads
-template <uint32_t HD, int NH>
+template <uint32_t HD, int NH, bool TREE = false>
 __device__ __forceinline__ void
 px8_pv_body(const bf16_t* Q, const pp_seg* segs, const px_range* tab, uint32_t ebase, const uint8_t* kq, const uint8_t* vq, const int8_t* kexp,
             const int8_t* vexp, uint64_t cache_stride, uint64_t exp_stride, const float* sums, float* part, bf16_t* out, uint32_t H, uint32_t n_rep,
-            uint32_t max_seq, float scale, const float* etab)
+            uint32_t max_seq, float scale, const float* etab, const tv_node* nodes = nullptr)
 {
     constexpr uint32_t DT = HD / 16;
     __shared__ float inv_sum[NH][16];
@@ -617,7 +624,7 @@ px8_pv_body(const bf16_t* Q, const pp_seg* segs, const px_range* tab, uint32_t e
     const px_range e = tab[ebase + blockIdx.y];
     const pp_seg g = segs[e.seg];
     const uint32_t wave = threadIdx.x >> 6, h0 = blockIdx.x * NH;
-    const px8_tile<HD, NH> t = px8_tile_of<HD, NH>(Q, g, e, kq, kexp, cache_stride, exp_stride, H, n_rep, max_seq, scale, h0);
+    const px8_tile<HD, NH, TREE> t = px8_tile_of<HD, NH, TREE>(Q, g, e, kq, kexp, cache_stride, exp_stride, H, n_rep, max_seq, scale, h0, nodes);
     const uint32_t l15 = t.t.l15, lg = t.t.lg, kg = t.t.kg;
     const uint8_t* vbase = vq + (size_t)g.row * cache_stride + (size_t)(h0 / n_rep) * HD * max_seq;
     const int8_t* vx = vexp + (size_t)g.row * exp_stride + (size_t)(h0 / n_rep) * max_seq;

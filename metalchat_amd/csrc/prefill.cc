@@ -243,7 +243,7 @@ mc_decoder::qkv_rope_cache(const layer_w& L, void* kc, void* vt, int M, int star
     arg_pack a = parts ? pack((const void*)pf_part, g.splits, (uint32_t)M, pf_q) : (pk ? pack((const void*)pf_qkv, (uint32_t)M, pf_q) : pack(pf_qkv, pf_q));
     switch (R.form) {
     case rope_form::packed:
-    case rope_form::tree: // (kc, vt: this layer of every batch row)
+    case rope_form::tree: // (kc, vt: this layer of every batch row; a tree on an fp8 batch: the fp8 list with the node table behind it)
         push_all(a, pk->segs, (uint32_t)pk->nseg, kc, vt);
         if (f8) push_all(a, kexp, vexp);
         a.push(pk->cache_stride);
@@ -350,7 +350,8 @@ mc_decoder::run_prefill(int M, int cache_pos, int rope_pos, int window, const vo
             // chunks that see their context (mc_extend_rows, kernels/extend_kernels.hip): the exp sums of every key range, then
             // p V over the ranges, then the ranges of a tile added in order (names and heads per workgroup: prefill_plan.h
             // plan_extend_attention).  A group is as many whole tiles as the scratch holds (one group unless the call is huge).
-            // Chunks that are trees (mc_tree_verify, pk->nodes): the mc_tv_* forms of the first two, the node table behind their arguments.
+            // Chunks that are trees (mc_tree_verify, pk->nodes): the mc_tv_* forms of the first two (an fp8 batch: mc_tv8_*, over the fp8 argument
+            // lists), the node table behind their arguments.
             s = timed("attention", [&] {
                 const extend_plan E = plan_extend_attention(penv(), pk->nodes != nullptr, pk->kv_format);
                 for (int g = 0; g < pk->ngroups; g++) {

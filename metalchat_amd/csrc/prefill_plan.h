@@ -258,8 +258,9 @@ rope_v4_ok(const prefill_env& e, bool qk_norm)
     return e.opt->pf_rope_pack && e.tb == 2 && hd % 8 == 0 && hd <= 2048 && 2048 % hd == 0 &&
            (!qk_norm || hd == 128 || hd == 256); // (q / k norms: the head sizes whose sum order the kernel reproduces)
 }
-// batch: 0 one prompt, 1 packed rows, 2 packed trees; qk_norm: the layer has a q or a k norm; kv_format (packed rows only): MC_KV_FP8 names the
-// byte forms of kv8_rows_kernels.hip (mc_pp8_* for mc_pp_*, mc_px8_* for mc_px_*), which take the exponent planes and their stride as well -- same grid
+// batch: 0 one prompt, 1 packed rows, 2 packed trees; qk_norm: the layer has a q or a k norm; kv_format (packed rows and trees): MC_KV_FP8 names the
+// byte forms of kv8_rows_kernels.hip (mc_pp8_* for mc_pp_*, mc_px8_* for mc_px_*) and kv8_tree_kernels.hip (mc_tv8_* for mc_tv_*), which take the
+// exponent planes and their stride as well -- same grid
 inline rope_plan
 plan_rope(const prefill_env& e, int M, bool parts, int batch, bool qk_norm, int kv_format = MC_KV_BF16)
 {
@@ -268,6 +269,7 @@ plan_rope(const prefill_env& e, int M, bool parts, int batch, bool qk_norm, int 
         return {rope_form::pair, std::string(parts ? "mc_pf_rope_cache_parts_" : "mc_pf_rope_cache_") + pf_tname(e), H + 2 * KV, (unsigned)M, hd / 2};
     const unsigned per = 2048u / hd; // heads of a row per workgroup of 256 threads
     const unsigned gx = ((H + KV) * (unsigned)M + per - 1) / per + KV * (((unsigned)M + 15u) / 16u); // q / k units, then v tiles of 16 rows
+    if (batch == 2 && kv_format == MC_KV_FP8) return {rope_form::tree, parts ? "mc_tv8_rope_cache_parts_bfloat" : "mc_tv8_rope_cache_bfloat", gx, 1, 256};
     if (batch == 2) return {rope_form::tree, parts ? "mc_tv_rope_cache_parts_bfloat" : "mc_tv_rope_cache_bfloat", gx, 1, 256};
     if (batch && kv_format == MC_KV_FP8) return {rope_form::packed, parts ? "mc_pp8_rope_cache_parts_bfloat" : "mc_pp8_rope_cache_bfloat", gx, 1, 256};
     if (batch) return {rope_form::packed, parts ? "mc_pp_rope_cache_parts_bfloat" : "mc_pp_rope_cache_bfloat", gx, 1, 256};
@@ -353,7 +355,7 @@ plan_packed_attention(const prefill_env& e, int ntiles, int kv_format = MC_KV_BF
 // chunks that see their context (mc_extend_rows, kernels/extend_kernels.hip): the exp sums of every key range, then p V over the ranges, then the
 // ranges of a split tile added in order; two query heads of a kv head per workgroup wherever the grouping allows it (the ranges, not the row
 // tiles, fill the chip).  Chunks that are trees (mc_tree_verify): the mc_tv_* forms of the first two.  Grids: (heads, ranges of the group) for
-// sums and pv, (n_heads, ranges) for the reduce; 256 threads each.  kv_format MC_KV_FP8 (never with tree): the mc_px8_* forms of sums and pv, the reduce as it is.
+// sums and pv, (n_heads, ranges) for the reduce; 256 threads each.  kv_format MC_KV_FP8: the mc_px8_* forms of sums and pv (trees: mc_tv8_*), the reduce as it is.
 struct extend_plan {
     std::string sums, pv, reduce;
     unsigned heads; // grid x of sums and pv
@@ -363,7 +365,7 @@ plan_extend_attention(const prefill_env& e, bool tree, int kv_format = MC_KV_BF1
 {
     const bool two = attn_two_heads_fit(e);
     const std::string sfx = std::string(two ? "2" : "") + "_bfloat_hd" + std::to_string(e.head_dim);
-    if (kv_format == MC_KV_FP8 && !tree) return {"mc_px8_sums" + sfx, "mc_px8_pv" + sfx, "mc_px_reduce_bfloat_hd" + std::to_string(e.head_dim), (unsigned)(two ? e.n_heads / 2 : e.n_heads)};
+    if (kv_format == MC_KV_FP8) return {(tree ? "mc_tv8_sums" : "mc_px8_sums") + sfx, (tree ? "mc_tv8_pv" : "mc_px8_pv") + sfx, "mc_px_reduce_bfloat_hd" + std::to_string(e.head_dim), (unsigned)(two ? e.n_heads / 2 : e.n_heads)};
     return {(tree ? "mc_tv_sums" : "mc_px_sums") + sfx, (tree ? "mc_tv_pv" : "mc_px_pv") + sfx, "mc_px_reduce_bfloat_hd" + std::to_string(e.head_dim),
             (unsigned)(two ? e.n_heads / 2 : e.n_heads)};
 }

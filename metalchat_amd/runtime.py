@@ -205,6 +205,8 @@ def capi() -> C.CDLL:
         "mc_kv_batch_bytes": (u64, [vp]),
         "mc_kv_packed_set": (i32, [vp, i32]),
         "mc_kv_packed_enabled": (i32, [vp]),
+        "mc_kv_tree_set": (i32, [vp, i32]),
+        "mc_kv_tree_enabled": (i32, [vp]),
         "mc_batch_release": (None, [vp]),
         "mc_batch_size": (i32, [vp]),
         "mc_batch_fork": (i32, [vp, i32, i32]),
@@ -827,7 +829,7 @@ class Batch:
     in groups of 32, each linear in a format of its own, LoRA adaptors of rank % 16 == 0 on the layer linears.  Keeps the decoder alive.
     kv="fp8" (Part 2o, with wide=True): the rows' caches hold e4m3 bytes and one exponent per cache vector, (hd + 1) / (2 hd) of the
     bfloat16 bytes; the packed passes and the verify calls are refused on such a batch by default; set_kv_packed(True) (Part 2p) admits
-    prefill_rows, extend_rows and verify_rows."""
+    prefill_rows, extend_rows and verify_rows, set_kv_tree(True) (Part 2q) verify_tree."""
 
     KV_FORMATS = {"bf16": 0, "fp8": 1}   # MC_KV_*
 
@@ -862,6 +864,15 @@ class Batch:
     @property
     def kv_packed(self) -> bool:
         return capi().mc_kv_packed_enabled(self._h) == 1
+
+    def set_kv_tree(self, on: bool):
+        """Part 2q: an fp8 batch takes verify_tree while the switch is on (a switch of its own: set_kv_packed never admits the tree); no effect
+        on a bfloat16 batch"""
+        _check(capi().mc_kv_tree_set(self._h, 1 if on else 0))
+
+    @property
+    def kv_tree(self) -> bool:
+        return capi().mc_kv_tree_enabled(self._h) == 1
 
     def size(self) -> int:
         return capi().mc_batch_size(self._h)
