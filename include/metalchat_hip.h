@@ -888,6 +888,48 @@ int32_t mc_kv_packed_enabled(const mc_batch* b); /* 0 for a null batch */
 mc_status mc_kv_tree_set(mc_batch* b, int32_t on);
 int32_t mc_kv_tree_enabled(const mc_batch* b); /* 0 for a null batch */
 
+/* ================================================================================================
+ * Part 2r -- shared-prefix rows: attached rows attend ONE copy of a prompt.  After best-of-n behind one prompt pass, or several chats behind
+ * one system prompt, every row attends the same keys; a batch may therefore hold one shared prefix -- one more set of K / Vt planes per layer
+ * in a row's layout, allocated by the first call that fills them -- and rows ATTACHED to it read its slots [0, shared) from that one copy,
+ * shared = n_valid & ~63 (whole 64-slot score splits).  The attention of a ragged step then runs the mc_sp_* kernels
+ * (kernels/prefix_kernels.hip): 16 / n_rep batch rows sit on the MFMA rows the per-row kernels pad with zeros, against one K or V fragment.
+ * A batch that never fills a prefix allocates, uploads and launches exactly what it did; a ragged step with no attached row launches the
+ * per-row list.
+ *   mc_prefix_fork       the decoder's cache positions [0, n_valid) of every layer become the prefix (conditions of mc_batch_fork)
+ *   mc_prefix_import_kv  test aid, as mc_batch_import_kv: one layer's prefix from the host, n_valid positions [pos][kv][hd]
+ *   mc_prefix_attach     the row becomes a continuation of the prefix: its length is n_valid, slots [shared, n_valid) are copied into its own
+ *                        planes at the same slots, and its own slots [0, shared) are neither read nor written while it stays attached.  The row
+ *                        keeps absolute slot numbers: its steps write slot pos of its own planes.
+ *   mc_prefix_detach     materialise = 1: [0, shared) is copied into the row, which keeps its length and is an ordinary row again;
+ *                        materialise = 0: the attachment is dropped and the length is 0.
+ *   mc_prefix_info       n_valid (0: no prefix) and shared; either pointer may be null
+ *   mc_prefix_attached   1 if the row is attached; 0 otherwise, for a null batch and for a row out of range
+ * Attached rows are served by mc_ragged_step and mc_ragged_generate -- beside ordinary and idle rows, with stop ids, on narrow and wide batches
+ * and QLoRA decoders, with every sampler, mask, penalty and log-probability setting --, mc_ragged_lengths, and mc_ragged_export_kv, which returns
+ * the row's logical view: the prefix's [0, shared), then the row's own slots.
+ * Contract: an attached row computes bit for bit what the same row computes on a batch whose row holds a full copy of the prefix -- tokens,
+ * logits, log-probability records, its own K / V, its export after a detach -- whatever B is, whatever its index, whoever shares its group.
+ * Refusals, all MC_ERR_INVALID_ARGUMENT behind the call's own name, nothing enqueued, no length changed:
+ *   mc_prefix_fork, mc_prefix_import_kv   on an fp8 batch, on a rolling batch, while any row is attached
+ *   mc_rolling_set, enable 1              while a prefix is held
+ *   mc_prefix_attach                      no prefix, a bad row index, a row that is already attached
+ *   mc_prefix_detach                      a bad row index, a row that is not attached, materialise other than 0 or 1
+ *   a ragged call                         an attached row at positions[r] < shared
+ *   any other call on a batch with an attached row (mc_batch_step / _generate), or one that names an attached row (mc_batch_fork,
+ *   mc_batch_import_kv, mc_batch_export_kv, mc_rolling_fork_row as src or dst; mc_rows_prefill, mc_extend_rows, mc_verify_rows and
+ *   mc_tree_verify with lens[r] > 0): "row r is attached to the shared prefix (mc_prefix_detach it first)"
+ * Not covered: fp8 batches, rolling batches, more than one prefix per batch, the packed passes and verify calls on attached rows, the lockstep
+ * calls, and giving back the attached rows' unused [0, shared) slots: every row still owns max_seq_len slots.  This part buys step time and
+ * HBM traffic, not cache bytes.
+ * ------------------------------------------------------------------------------------------ */
+mc_status mc_prefix_fork(mc_batch* b, int32_t n_valid);
+mc_status mc_prefix_import_kv(mc_batch* b, int32_t layer, const void* keys, const void* values, int32_t n_valid);
+mc_status mc_prefix_attach(mc_batch* b, int32_t row);
+mc_status mc_prefix_detach(mc_batch* b, int32_t row, int32_t materialise);
+mc_status mc_prefix_info(const mc_batch* b, int32_t* n_valid, int32_t* shared);
+int32_t mc_prefix_attached(const mc_batch* b, int32_t row); /* 0 for a null batch */
+
 /* Host-side helpers shared by tests and the synthetic initialiser. */
 /* value in [-7,7] (bits = 4) or [-127,127] (bits = 8), zero mean, of element (row, col) of matrix `matrix_id` */
 int32_t mc_synth_weight(uint64_t seed, uint32_t matrix_id, uint32_t row, uint32_t col, int32_t bits);

@@ -93,6 +93,11 @@ mc_batch::prepare(const batch_call_plan& c, int n)
     }
     if (!c.logits.empty() && ((s = ensure(logits_tab_dev, sizeof(row_logits) * B)) != MC_OK || (s = send_if_changed(logits_tab_dev, logits_tab_sent, c.logits)) != MC_OK))
         return s;
+    if (c.prefix) { // Part 2r: sp_len goes up only when the attachments changed
+        std::vector<int32_t> sp(B, 0);
+        for (int r = 0; r < B; r++) sp[r] = attached[r] ? prefix_shared() : 0;
+        if ((s = send_if_changed(sp_dev, sp_sent, sp)) != MC_OK) return s;
+    }
     return c.samplers.empty() ? MC_OK : send_if_changed(samplers_dev, samplers_sent, c.samplers);
 }
 
@@ -153,6 +158,13 @@ mc_batch::run(const batch_launch& l, const call_args& a)
                                 (uint32_t)fx.nsplit, cstride));
     case op::pv:
         return launch(l.L, pack(expv, psum, (void*)vt_of(li, 0), att, state, (uint32_t)n_rep, (uint32_t)hd, (uint32_t)cfg.max_seq_len, (uint32_t)fx.nsplit, cstride));
+    case op::sp_scores:
+        return launch(l.L, pack(q, (void*)kc_of(li, 0), (void*)pkc_of(li), expv, psum, state, (const int32_t*)sp_dev, (uint32_t)n_rep, (uint32_t)hd,
+                                (uint32_t)cfg.max_seq_len, round_bf_host(cfg.attn_scale), (uint32_t)fx.nsplit, cstride, (uint32_t)B, (uint32_t)prefix_group(cfg),
+                                (uint32_t)prefix_shared()));
+    case op::sp_pv:
+        return launch(l.L, pack(expv, psum, (void*)vt_of(li, 0), (void*)pvt_of(li), att, state, (const int32_t*)sp_dev, (uint32_t)n_rep, (uint32_t)hd,
+                                (uint32_t)cfg.max_seq_len, (uint32_t)fx.nsplit, cstride, (uint32_t)B, (uint32_t)prefix_group(cfg)));
     case op::rope_f8:
         return launch(l.L, pack(qkv, q, (void*)kc_of(li, 0), (void*)vt_of(li, 0), kexp_of(li, 0), vexp_of(li, 0), c.rolling ? rcos : fcos, c.rolling ? rsin : fsin, state,
                                 (uint32_t)H, (uint32_t)KV, (uint32_t)hd, (uint32_t)cfg.max_seq_len, cstride, (uint64_t)exp_elems()));
@@ -323,6 +335,7 @@ batch_create(const std::string& who, int cap, bool wide, mc_decoder* d, int32_t 
     b->p = parts;
     b->B = batch;
     b->lengths.assign(batch, 0);
+    b->attached.assign(batch, 0);
     b->row_samplers.assign(batch, row_setting{});
     b->row_logit_set.assign(batch, row_logit_setting{});
     const mc_decoder_config& c = parts.cfg;
@@ -416,6 +429,7 @@ mc_batch_step(mc_batch* b, const int32_t* tokens, int32_t start_pos, int32_t* ne
 {
     if (!b || !tokens) return fail(MC_ERR_INVALID_ARGUMENT, "mc_batch_step: null argument");
     mc_status s;
+    if ((s = refuse(attached_any_refusal("mc_batch_step", b->attached))) != MC_OK) return s;
     if ((s = refuse(step_bounds(start_pos, b->p.cfg.max_seq_len))) != MC_OK || (s = refuse(check_tokens(tokens, b->B, b->p.cfg.vocab))) != MC_OK) return s;
     return run_tokens(b, tokens, start_pos, nullptr, 1, nullptr, 0, next_tokens);
 }
@@ -426,6 +440,7 @@ mc_batch_generate(mc_batch* b, const int32_t* first_tokens, int32_t start_pos, i
     if (!b || !first_tokens || !tokens_out) return fail(MC_ERR_INVALID_ARGUMENT, "mc_batch_generate: null argument");
     if (n < 1) return fail(MC_ERR_INVALID_ARGUMENT, "mc_batch_generate: n must be positive");
     mc_status s;
+    if ((s = refuse(attached_any_refusal("mc_batch_generate", b->attached))) != MC_OK) return s;
     if ((s = refuse(generate_bounds(start_pos, n, b->p.cfg.max_seq_len))) != MC_OK || (s = refuse(check_tokens(first_tokens, b->B, b->p.cfg.vocab))) != MC_OK)
         return s;
     return run_tokens(b, first_tokens, start_pos, nullptr, n, nullptr, 0, tokens_out);
@@ -449,6 +464,7 @@ mc_ragged_step(mc_batch* b, const int32_t* tokens, const int32_t* positions, int
     if (!b || !tokens || !positions) return fail(MC_ERR_INVALID_ARGUMENT, "mc_ragged_step: null argument");
     const mc_decoder_config& c = b->p.cfg;
     mc_status s = refuse(check_ragged("mc_ragged_step", tokens, positions, 1, b->lengths.data(), b->B, c.max_seq_len, c.vocab, b->rolling));
+    if (s == MC_OK) s = refuse(check_ragged_attached("mc_ragged_step", positions, b->attached, b->prefix_shared()));
     if (s != MC_OK) return s;
     return run_tokens(b, tokens, 0, positions, 1, nullptr, 0, next_tokens);
 }
@@ -463,6 +479,7 @@ mc_ragged_generate(mc_batch* b, const int32_t* first_tokens, const int32_t* posi
     if (n_stop < 0) return fail(MC_ERR_INVALID_ARGUMENT, "mc_ragged_generate: n_stop must not be negative");
     const mc_decoder_config& c = b->p.cfg;
     mc_status s = refuse(check_ragged("mc_ragged_generate", first_tokens, positions, n, b->lengths.data(), b->B, c.max_seq_len, c.vocab, b->rolling));
+    if (s == MC_OK) s = refuse(check_ragged_attached("mc_ragged_generate", positions, b->attached, b->prefix_shared()));
     if (s != MC_OK) return s;
     return run_tokens(b, first_tokens, 0, positions, n, stop_ids, n_stop, tokens_out, lengths);
 }

@@ -6,14 +6,16 @@ using namespace mcimpl;
 
 namespace {
 
-// the first n cache positions of every kv head, one layer: K [kv][pos][hd] is n * hd elements per kv head, Vt [kv * hd][pos] n elements per row
+// the cache positions [first, n) of every kv head, one layer: K [kv][pos][hd] is hd elements a position per kv head, Vt [kv * hd][pos] one per row
 mc_status
-copy_cache_rows(mc_batch* b, void* k_dst, void* vt_dst, const void* k_src, const void* vt_src, int n)
+copy_cache_rows(mc_batch* b, void* k_dst, void* vt_dst, const void* k_src, const void* vt_src, int n, int first = 0)
 {
     const mc_decoder_config& c = b->p.cfg;
     const int KV = c.n_kv_heads, hd = c.head_dim, S = c.max_seq_len;
-    MC_HIP(hipMemcpy2DAsync(k_dst, (size_t)S * hd * 2, k_src, (size_t)S * hd * 2, (size_t)n * hd * 2, KV, hipMemcpyDeviceToDevice, b->p.stream));
-    MC_HIP(hipMemcpy2DAsync(vt_dst, (size_t)S * 2, vt_src, (size_t)S * 2, (size_t)n * 2, (size_t)KV * hd, hipMemcpyDeviceToDevice, b->p.stream));
+    if (n <= first) return MC_OK;
+    const size_t ko = (size_t)first * hd * 2, vo = (size_t)first * 2, w = (size_t)(n - first);
+    MC_HIP(hipMemcpy2DAsync((char*)k_dst + ko, (size_t)S * hd * 2, (const char*)k_src + ko, (size_t)S * hd * 2, w * hd * 2, KV, hipMemcpyDeviceToDevice, b->p.stream));
+    MC_HIP(hipMemcpy2DAsync((char*)vt_dst + vo, (size_t)S * 2, (const char*)vt_src + vo, (size_t)S * 2, w * 2, (size_t)KV * hd, hipMemcpyDeviceToDevice, b->p.stream));
     return MC_OK;
 }
 
@@ -43,10 +45,11 @@ quant_cache_rows(mc_batch* b, int layer, int row, const void* k_src, const void*
 // mc_batch_export_kv and mc_ragged_export_kv: row `row`'s cache of `layer` through mc_kv_export_bfloat, which takes kv_len (and
 // the ring) from the device step state `state`, into staging buffers of `cap` positions; then n positions to the host.
 // n < 0: n = that kv_len, read back behind the launch and reported in *n_out.  An fp8 cache (Part 2o) goes through mc_kv_dequant_f8: the same
-// view, the values deq of the row's bytes.
+// view, the values deq of the row's bytes.  prefix (Part 2r): the shared prefix's planes in place of the row's; skip: only positions [skip, n) reach
+// the host, at their place in keys / values.
 mc_status
 export_kv(mc_batch* b, const char* what, int32_t row, int32_t layer, const step_state* state, int32_t cap, int32_t n, int32_t* n_out,
-          void* keys, void* values)
+          void* keys, void* values, bool prefix = false, int32_t skip = 0)
 {
     const mc_decoder_config& c = b->p.cfg;
     const size_t per_pos = (size_t)c.n_kv_heads * c.head_dim * 2;
@@ -54,7 +57,7 @@ export_kv(mc_batch* b, const char* what, int32_t row, int32_t layer, const step_
     hipError_t e = kt.alloc(cap * per_pos);
     if (e == hipSuccess) e = vtmp.alloc(cap * per_pos);
     if (e != hipSuccess) return hip_fail(e, what);
-    arg_pack args = pack((const void*)b->kc_of(layer, row), (const void*)b->vt_of(layer, row));
+    arg_pack args = prefix ? pack((const void*)b->pkc_of(layer), (const void*)b->pvt_of(layer)) : pack((const void*)b->kc_of(layer, row), (const void*)b->vt_of(layer, row));
     if (b->fp8()) {
         args.push((const void*)b->kexp_of(layer, row));
         args.push((const void*)b->vexp_of(layer, row));
@@ -69,15 +72,17 @@ export_kv(mc_batch* b, const char* what, int32_t row, int32_t layer, const step_
         n = st.kv_len;
         if (n_out) *n_out = n;
     }
-    if (s == MC_OK && e == hipSuccess && keys) e = hipMemcpy(keys, kt.ptr, n * per_pos, hipMemcpyDeviceToHost);
-    if (s == MC_OK && e == hipSuccess && values) e = hipMemcpy(values, vtmp.ptr, n * per_pos, hipMemcpyDeviceToHost);
+    const size_t so = skip * per_pos;
+    if (s == MC_OK && e == hipSuccess && keys) e = hipMemcpy((char*)keys + so, (const char*)kt.ptr + so, (n - skip) * per_pos, hipMemcpyDeviceToHost);
+    if (s == MC_OK && e == hipSuccess && values) e = hipMemcpy((char*)values + so, (const char*)vtmp.ptr + so, (n - skip) * per_pos, hipMemcpyDeviceToHost);
     if (e != hipSuccess) return hip_fail(e, what);
     return s;
 }
 
 // mc_ragged_export_kv (and mc_batch_export_kv for a row that has rolled): row `row`'s own logical view, min(length, max_seq_len)
 // positions -- the sink rows, then the ring unrolled.  The export kernel reads kv_len and the ring from a state of its own, made
-// from the row's length: the row last wrote position length - 1, which fixes its ring (mc_b_rows_begin_rolling)
+// from the row's length: the row last wrote position length - 1, which fixes its ring (mc_b_rows_begin_rolling).  An attached row (Part 2r):
+// the prefix's [0, shared), then the row's own slots
 mc_status
 export_row(mc_batch* b, const char* what, int32_t row, int32_t layer, void* keys, void* values, int32_t* n_valid)
 {
@@ -92,7 +97,23 @@ export_row(mc_batch* b, const char* what, int32_t row, int32_t layer, void* keys
     hipError_t e = stv.alloc(sizeof st);
     if (e == hipSuccess) e = hipMemcpyAsync(stv.ptr, &st, sizeof st, hipMemcpyHostToDevice, b->p.stream);
     if (e != hipSuccess) return hip_fail(e, what);
-    return export_kv(b, what, row, layer, static_cast<const step_state*>(stv.ptr), n, n, nullptr, keys, values);
+    const step_state* state = static_cast<const step_state*>(stv.ptr);
+    if (!b->attached[row]) return export_kv(b, what, row, layer, state, n, n, nullptr, keys, values);
+    const int32_t shared = b->prefix_shared(); // (n >= shared; the export kernel writes n positions of staging either way)
+    const mc_status s = shared ? export_kv(b, what, row, layer, state, n, shared, nullptr, keys, values, true) : MC_OK;
+    return s != MC_OK ? s : export_kv(b, what, row, layer, state, n, n, nullptr, keys, values, false, shared);
+}
+
+// mc_prefix_fork / mc_prefix_import_kv in front of their copies: the refusals, then the planes (zeroed, so finite behind n_valid)
+mc_status
+prefix_begin(mc_batch* b, const char* who, int32_t n_valid)
+{
+    mc_status s = refuse(prefix_fill_refusal(who, b->kv_format, b->rolling, b->attached));
+    if (s != MC_OK) return s;
+    if (n_valid < 1 || n_valid > b->p.cfg.max_seq_len) return fail(MC_ERR_INVALID_ARGUMENT, std::string(who) + ": n_valid must lie in [1, max_seq_len]");
+    const size_t bytes = b->p.layers.size() * b->cache_elems * 2;
+    if ((s = b->ensure(b->pkc, bytes)) != MC_OK || (s = b->ensure(b->pvt, bytes)) != MC_OK) return s;
+    return b->ensure(b->sp_dev, sizeof(int32_t) * b->B);
 }
 
 } // namespace
@@ -103,6 +124,7 @@ mc_status
 mc_batch_fork(mc_batch* b, int32_t row, int32_t n_valid)
 {
     mc_status s = find_row(b, "mc_batch_fork", row, true, 0);
+    if (s == MC_OK) s = refuse(attached_row_refusal("mc_batch_fork", b->attached, row));
     if (s != MC_OK) return s;
     const mc_decoder_config& c = b->p.cfg;
     if (n_valid < 1 || n_valid > c.max_seq_len) return fail(MC_ERR_INVALID_ARGUMENT, "mc_batch_fork: n_valid must lie in [1, max_seq_len]");
@@ -127,6 +149,7 @@ mc_status
 mc_batch_import_kv(mc_batch* b, int32_t row, int32_t layer, const void* keys, const void* values, int32_t n_valid)
 {
     mc_status s = find_row(b, "mc_batch_import_kv", row, true, layer);
+    if (s == MC_OK) s = refuse(attached_row_refusal("mc_batch_import_kv", b->attached, row));
     if (s != MC_OK) return s;
     if (!keys || !values) return fail(MC_ERR_INVALID_ARGUMENT, "mc_batch_import_kv: null argument");
     const mc_decoder_config& c = b->p.cfg;
@@ -161,6 +184,7 @@ mc_status
 mc_batch_export_kv(mc_batch* b, int32_t row, int32_t layer, void* keys, void* values, int32_t* n_valid)
 {
     mc_status s = find_row(b, "mc_batch_export_kv", row, true, layer);
+    if (s == MC_OK) s = refuse(attached_row_refusal("mc_batch_export_kv", b->attached, row));
     if (s != MC_OK) return s;
     // a row that has rolled has no lockstep view: its own (Part 2j)
     if (b->lengths[row] > b->p.cfg.max_seq_len) return export_row(b, "mc_batch_export_kv", row, layer, keys, values, n_valid);
@@ -184,6 +208,7 @@ mc_rolling_set(mc_batch* b, int32_t enable)
 {
     if (!b) return fail(MC_ERR_INVALID_ARGUMENT, "mc_rolling_set: null argument");
     if (enable != 0 && enable != 1) return fail(MC_ERR_INVALID_ARGUMENT, "mc_rolling_set: enable must be 0 or 1");
+    if (enable == 1 && b->prefix_n > 0) return fail(MC_ERR_INVALID_ARGUMENT, "mc_rolling_set: the batch holds a shared prefix (a shared prefix does not roll)");
     b->rolling = enable == 1;
     return MC_OK;
 }
@@ -200,6 +225,8 @@ mc_rolling_fork_row(mc_batch* b, int32_t dst, int32_t src)
     if (!b) return fail(MC_ERR_INVALID_ARGUMENT, "mc_rolling_fork_row: null argument");
     if (dst < 0 || dst >= b->B || src < 0 || src >= b->B) return fail(MC_ERR_INVALID_ARGUMENT, "mc_rolling_fork_row: row out of range");
     if (dst == src) return fail(MC_ERR_INVALID_ARGUMENT, "mc_rolling_fork_row: dst and src are the same row");
+    for (int32_t r : {dst, src})
+        if (const mc_status s = refuse(attached_row_refusal("mc_rolling_fork_row", b->attached, r)); s != MC_OK) return s;
     // the physical slots as they lie: a rolled row's ring follows from its length, which the copy takes along
     const int n = std::min(b->lengths[src], b->p.cfg.max_seq_len);
     MC_HIP(hipSetDevice(b->p.ordinal));
@@ -210,6 +237,101 @@ mc_rolling_fork_row(mc_batch* b, int32_t dst, int32_t src)
     MC_HIP(hipStreamSynchronize(b->p.stream));
     b->lengths[dst] = b->lengths[src];
     return MC_OK;
+}
+
+// ---- Part 2r: shared-prefix rows ----
+
+mc_status
+mc_prefix_fork(mc_batch* b, int32_t n_valid)
+{
+    if (!b) return fail(MC_ERR_INVALID_ARGUMENT, "mc_prefix_fork: null argument");
+    mc_status s = prefix_begin(b, "mc_prefix_fork", n_valid);
+    if (s != MC_OK) return s;
+    int kv_len = 0;
+    bool rolled = false;
+    if ((s = decoder_cache_state(b->d, &kv_len, &rolled)) != MC_OK) return s;
+    if (rolled) return fail(MC_ERR_INVALID_ARGUMENT, "mc_prefix_fork: the decoder's cache has rolled (sink ring turned)");
+    if (n_valid > kv_len) return fail(MC_ERR_INVALID_ARGUMENT, "mc_prefix_fork: the decoder's cache holds fewer than n_valid positions");
+    MC_HIP(hipSetDevice(b->p.ordinal));
+    for (size_t l = 0; l < b->p.layers.size(); l++)
+        if ((s = copy_cache_rows(b, b->pkc_of((int)l), b->pvt_of((int)l), b->p.layers[l].kc, b->p.layers[l].vt, n_valid)) != MC_OK) return s;
+    MC_HIP(hipStreamSynchronize(b->p.stream));
+    b->prefix_n = n_valid;
+    return MC_OK;
+}
+
+mc_status
+mc_prefix_import_kv(mc_batch* b, int32_t layer, const void* keys, const void* values, int32_t n_valid)
+{
+    if (!b || !keys || !values) return fail(MC_ERR_INVALID_ARGUMENT, "mc_prefix_import_kv: null argument");
+    if (layer < 0 || layer >= (int32_t)b->p.layers.size()) return fail(MC_ERR_INVALID_ARGUMENT, "mc_prefix_import_kv: layer out of range");
+    mc_status s = prefix_begin(b, "mc_prefix_import_kv", n_valid);
+    if (s != MC_OK) return s;
+    const mc_decoder_config& c = b->p.cfg;
+    MC_HIP(hipSetDevice(b->p.ordinal));
+    const size_t nb = (size_t)n_valid * c.n_kv_heads * c.head_dim * 2;
+    device_tmp kt, vtmp;
+    MC_HIP(kt.alloc(nb));
+    hipError_t e = vtmp.alloc(nb);
+    if (e == hipSuccess) e = hipMemcpy(kt.ptr, keys, nb, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(vtmp.ptr, values, nb, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        s = b->launch("mc_kv_import_bfloat", 512, 1, 1, 256, 0,
+                      pack((void*)b->pkc_of(layer), (void*)b->pvt_of(layer), (const void*)kt.ptr, (const void*)vtmp.ptr, (uint32_t)n_valid, (uint32_t)c.n_kv_heads,
+                           (uint32_t)c.head_dim, (uint32_t)c.max_seq_len));
+        e = hipStreamSynchronize(b->p.stream);
+    }
+    if (e != hipSuccess) return hip_fail(e, "mc_prefix_import_kv");
+    if (s == MC_OK) b->prefix_n = n_valid;
+    return s;
+}
+
+mc_status
+mc_prefix_attach(mc_batch* b, int32_t row)
+{
+    mc_status s = find_row(b, "mc_prefix_attach", row);
+    if (s != MC_OK) return s;
+    if (b->prefix_n == 0) return fail(MC_ERR_INVALID_ARGUMENT, "mc_prefix_attach: the batch holds no shared prefix (mc_prefix_fork or mc_prefix_import_kv first)");
+    if (b->attached[row]) return fail(MC_ERR_INVALID_ARGUMENT, "mc_prefix_attach: row " + std::to_string(row) + " is already attached");
+    MC_HIP(hipSetDevice(b->p.ordinal));
+    // the prefix's tail [shared, n_valid) becomes the row's own, at the same slots; [0, shared) of the row is not touched
+    for (int l = 0; l < (int)b->p.layers.size(); l++)
+        if ((s = copy_cache_rows(b, b->kc_of(l, row), b->vt_of(l, row), b->pkc_of(l), b->pvt_of(l), b->prefix_n, b->prefix_shared())) != MC_OK) return s;
+    MC_HIP(hipStreamSynchronize(b->p.stream));
+    b->attached[row] = 1;
+    b->lengths[row] = b->prefix_n;
+    return MC_OK;
+}
+
+mc_status
+mc_prefix_detach(mc_batch* b, int32_t row, int32_t materialise)
+{
+    mc_status s = find_row(b, "mc_prefix_detach", row);
+    if (s != MC_OK) return s;
+    if (materialise != 0 && materialise != 1) return fail(MC_ERR_INVALID_ARGUMENT, "mc_prefix_detach: materialise must be 0 or 1");
+    if (!b->attached[row]) return fail(MC_ERR_INVALID_ARGUMENT, "mc_prefix_detach: row " + std::to_string(row) + " is not attached");
+    MC_HIP(hipSetDevice(b->p.ordinal));
+    for (int l = 0; materialise && l < (int)b->p.layers.size(); l++)
+        if ((s = copy_cache_rows(b, b->kc_of(l, row), b->vt_of(l, row), b->pkc_of(l), b->pvt_of(l), b->prefix_shared())) != MC_OK) return s;
+    MC_HIP(hipStreamSynchronize(b->p.stream));
+    b->attached[row] = 0;
+    if (!materialise) b->lengths[row] = 0;
+    return MC_OK;
+}
+
+mc_status
+mc_prefix_info(const mc_batch* b, int32_t* n_valid, int32_t* shared)
+{
+    if (!b) return fail(MC_ERR_INVALID_ARGUMENT, "mc_prefix_info: null argument");
+    if (n_valid) *n_valid = b->prefix_n;
+    if (shared) *shared = b->prefix_shared();
+    return MC_OK;
+}
+
+int32_t
+mc_prefix_attached(const mc_batch* b, int32_t row)
+{
+    return b && row >= 0 && row < b->B && b->attached[row] ? 1 : 0;
 }
 
 } // extern "C"

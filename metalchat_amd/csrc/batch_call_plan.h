@@ -19,6 +19,7 @@ enum class batch_op {
     qkv_adaptor, qkv_gemv, wo_adaptor, wo_gemv, w13_adaptor, w13_gemv, w2_adaptor, w2_gemv, head_gemv, // adaptor: a = T(A x) in front of its linear
     rope, scores, pv,
     rope_f8, scores_f8, pv_f8, // Part 2o: the byte and exponent planes in place of the bfloat16 caches
+    sp_scores, sp_pv,          // Part 2r: a ragged step with rows attached to the shared prefix (the prefix planes and sp_len beside the rows')
     process, process_rows, process_rows_count, // the ragged form takes the count flag: off behind a prompt pass
     argmax, candidates, sample, candidates_mixed, pick_mixed,
     logprob_parts, logprob_finish,
@@ -31,7 +32,7 @@ struct batch_launch {
 };
 
 // what a batch fixes at its creation: B, the split of the attention scores, the candidate keys it holds per row, the launches of a step in its
-// three forms (lockstep, ragged, ragged on a rolling batch) and the head's GEMV -- and with them the BODY of a token in each form, from the begin
+// forms (lockstep, ragged, ragged on a rolling batch, ragged with rows attached to the shared prefix: Part 2r) and the head's GEMV -- and with them the BODY of a token in each form, from the begin
 // launch to the last layer's w2: no setting of a call changes it, so a call's plan points at it and no call builds it again
 struct batch_fixed {
     mc_decoder_config cfg{};
@@ -40,8 +41,8 @@ struct batch_fixed {
     size_t cand_per_row = 0;
     linear_shape head;
     batch_gemv_plan head_gemv;
-    step_plan steps[3];
-    std::vector<batch_launch> body[3];
+    step_plan steps[4];
+    std::vector<batch_launch> body[4];
 };
 // Parts: as refusal() reads them
 template <typename Parts> batch_fixed
@@ -59,8 +60,14 @@ fix_batch(const Parts& p, const batch_env& e)
     f.wide = f.head_gemv.wide;
     assert(!f.head_gemv.lora && "the admission refuses an adaptor on the head: a token's plan lists no adaptor launch in front of it");
     using op = batch_op;
-    for (int form = 0; form < 3; form++) {
-        const step_plan& st = f.steps[form] = plan_step(p.cfg, e.B, f.nsplit, form > 0, form == 2, e.kv_format);
+    for (int form = 0; form < 4; form++) {
+        const bool sp = form == 3; // (refused on an fp8 and on a rolling batch: the list is then never run)
+        step_plan& st = f.steps[form] = plan_step(p.cfg, e.B, f.nsplit, form > 0, form == 2, e.kv_format);
+        if (sp) {
+            const prefix_attention_plan a = plan_prefix_attention(p.cfg, e.B, f.nsplit, true);
+            st.scores = a.scores;
+            st.pv = a.pv;
+        }
         std::vector<batch_launch>& body = f.body[form];
         auto gemv = [&](op adaptor, op main, const batch_gemv_plan& g, int layer) { // (a linear with an adaptor: a = T(A x) in front)
             assert(g.wide == f.wide);
@@ -74,8 +81,8 @@ fix_batch(const Parts& p, const batch_env& e)
             body.push_back({op::attn_norm, l, st.rmsnorm});
             gemv(op::qkv_adaptor, op::qkv_gemv, plan_batch_gemv(L.qkv, 0, e), l);
             body.push_back({st.fp8 ? op::rope_f8 : op::rope, l, st.rope});
-            body.push_back({st.fp8 ? op::scores_f8 : op::scores, l, st.scores});
-            body.push_back({st.fp8 ? op::pv_f8 : op::pv, l, st.pv});
+            body.push_back({sp ? op::sp_scores : (st.fp8 ? op::scores_f8 : op::scores), l, st.scores});
+            body.push_back({sp ? op::sp_pv : (st.fp8 ? op::pv_f8 : op::pv), l, st.pv});
             gemv(op::wo_adaptor, op::wo_gemv, plan_batch_gemv(L.wo, 1, e), l);
             body.push_back({op::ffn_norm, l, st.rmsnorm});
             gemv(op::w13_adaptor, op::w13_gemv, plan_batch_gemv(L.w13, 2, e), l);
@@ -92,12 +99,14 @@ struct call_settings {
     decoder_sampler dec;
     const std::vector<row_setting>& samplers;         // [B]
     const std::vector<row_logit_setting>& logit_rows; // [B]
+    bool prefix_rows = false;                         // Part 2r: some row is attached to the shared prefix
 };
 
 struct batch_call_plan {
     std::string refusal; // "" = none, else the call fails with `code`
     mc_status code = MC_OK;
     bool ragged = false, rolling = false, tree = false;
+    bool prefix = false; // Part 2r: the body is the one with the mc_sp_* attention, which reads the sp_len table
     const std::vector<batch_launch>* body = nullptr; // a token: the batch's fixed list in front of `launches` (batch_fixed::body)
     std::vector<batch_launch> launches;              // what the call's settings decide: from the final norm on; a verify call: its whole head
     // the tables the call uploads (empty: none, the launches that read it are not in the list)
@@ -140,7 +149,8 @@ plan_token_from(const batch_fixed& f, const call_settings& s, bool ragged, bool 
     const logits_plan lg = plan_logits(s.logit_rows, vocab, ragged);
     const head_plan h = plan_head(s.samplers, s.dec, vocab, ragged, f.cand_per_row);
     if (!h.refusal.empty()) return c.refuse(h.refusal);
-    if (!tail) c.body = &f.body[!ragged ? 0 : (s.rolling ? 2 : 1)];
+    c.prefix = !tail && ragged && !s.rolling && s.prefix_rows;
+    if (!tail) c.body = &f.body[!ragged ? 0 : (s.rolling ? 2 : (c.prefix ? 3 : 1))];
     c.add(op::final_norm, f.steps[0].rmsnorm);
     c.add(op::head_gemv, f.head_gemv.main); // (no adaptor: the admission refuses one on the head)
     if (lg.any) c.add(!ragged ? op::process : (count ? op::process_rows_count : op::process_rows), lg.launch);

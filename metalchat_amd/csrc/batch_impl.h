@@ -28,6 +28,8 @@
 // launches are their _f8 forms, fork and import quantise, the exports dequantise, and the four packed calls are refused.
 // Part 2n (mc_logprobs_set): opt-in per batch, two launches (logprob_kernels.hip) behind every pick -- a token's three forms and a verify call's --
 // record the pick's log-probability and the top_n most likely tokens.  With the switch off a batch launches and holds what it did before.
+// Part 2r (mc_prefix_*): one shared prefix per batch; a ragged step with rows attached to it runs the mc_sp_* attention (prefix_kernels.hip), in
+// which 16 / n_rep rows share one K or V fragment.  A batch that never fills a prefix allocates, uploads and launches what it did before.
 //
 // WHAT is launched -- names, grids, blocks, LDS bytes, the admission and every check of a call that needs no device -- is decided in
 // batch_plan.h, and IN WHICH ORDER in batch_call_plan.h: an entry point plans its whole call once (plan_batch_token, plan_rows_tail,
@@ -172,6 +174,18 @@ struct mc_batch {
     mcimpl::logprob_part* lp_parts = nullptr;
     uint64_t* lp_keys = nullptr;
     int lp_parts_cap = 0, lp_keys_cap = 0; // (rows)
+    // Part 2r (mc_prefix_*): one shared prefix -- K / Vt planes [layer][n_kv][max_seq][hd], [layer][n_kv][hd][max_seq], allocated by the first
+    // call that fills them -- of prefix_n valid positions; which rows are attached; and sp_len[B] (shared for an attached row, else 0) as the
+    // device holds it.  A batch that never fills a prefix allocates, uploads and launches what it did
+    void *pkc = nullptr, *pvt = nullptr;
+    int prefix_n = 0;
+    std::vector<char> attached; // [B]
+    int32_t* sp_dev = nullptr;
+    std::vector<int32_t> sp_sent;
+    int prefix_shared() const { return mcimpl::prefix_shared(prefix_n); }
+    bool any_attached() const { return std::find(attached.begin(), attached.end(), (char)1) != attached.end(); }
+    char* pkc_of(int layer) const { return (char*)pkc + (size_t)layer * cache_elems * 2; }
+    char* pvt_of(int layer) const { return (char*)pvt + (size_t)layer * cache_elems * 2; }
     // The plans fixed at creation (batch_call_plan.h batch_fixed): B, the device's compute units and MC_WB_TILES, both read once there; the GEMV
     // of every matrix; the launches of a step, lockstep / ragged / ragged on a rolling batch.  The plan of a call is the entry point's own
     // (plan_batch_token, plan_rows_tail, plan_verify_call with settings()) and goes down by const&: the settings cannot change inside a call
@@ -273,7 +287,7 @@ struct mc_batch {
     mcimpl::call_settings
     settings() const
     {
-        return {rolling, verify_settings_on, logprobs_on, logprobs_top, n_seed_pairs, mcimpl::decoder_sampler_of(d), row_samplers, row_logit_set};
+        return {rolling, verify_settings_on, logprobs_on, logprobs_top, n_seed_pairs, mcimpl::decoder_sampler_of(d), row_samplers, row_logit_set, any_attached()};
     }
 
     // ---------------------------------------------------------------- one call (batch.cc)

@@ -209,6 +209,85 @@ plan_step(const mc_decoder_config& c, int B, int nsplit, bool ragged, bool rolli
     return s;
 }
 
+// ---------------------------------------------------------------- shared-prefix rows (Part 2r)
+
+// rows of a batch that share one K or V fragment in the mc_sp_* kernels (prefix_kernels.hip): 16 MFMA rows, n_rep of them per batch row
+inline int
+prefix_group(const mc_decoder_config& c)
+{
+    return 16 / (c.n_heads / c.n_kv_heads);
+}
+// whole PB-slot score splits of a prefix of n_valid positions: what attached rows read from the prefix planes
+inline int
+prefix_shared(int n_valid)
+{
+    return n_valid & ~((int)PB - 1);
+}
+
+// The two attention launches of a ragged step.  No row attached: plan_step's.  Otherwise mc_sp_attn_scores_bfloat -- z = 0 the prefix's
+// workgroups, z = 1 + r row r's own splits -- and mc_sp_attn_pv_bfloat, a workgroup per group of rows: as many launches as without
+struct prefix_attention_plan {
+    bool attached = false;
+    launch_plan scores, pv;
+};
+inline prefix_attention_plan
+plan_prefix_attention(const mc_decoder_config& c, int B, int nsplit, bool attached)
+{
+    prefix_attention_plan a;
+    a.attached = attached;
+    if (!attached) {
+        const step_plan s = plan_step(c, B, nsplit, true, false);
+        a.scores = s.scores;
+        a.pv = s.pv;
+        return a;
+    }
+    const unsigned KV = c.n_kv_heads, hd = c.head_dim, G = (unsigned)prefix_group(c);
+    a.scores = {"mc_sp_attn_scores_bfloat", (unsigned)nsplit, KV, (unsigned)B + 1, 256, 0};
+    a.pv = {"mc_sp_attn_pv_bfloat", hd / 16, KV, ((unsigned)B + G - 1) / G, 1024, 0};
+    return a;
+}
+
+// the refusals of Part 2r ("" = fine).  attached: [B], whether row r is attached
+inline std::string
+attached_text(const char* who, int r)
+{
+    return std::string(who) + ": row " + std::to_string(r) + " is attached to the shared prefix (mc_prefix_detach it first)";
+}
+// a call that names one row
+inline std::string
+attached_row_refusal(const char* who, const std::vector<char>& attached, int row)
+{
+    return row >= 0 && row < (int)attached.size() && attached[row] ? attached_text(who, row) : "";
+}
+// a call over the whole batch (lens null), or over the rows with lens[r] > 0
+inline std::string
+attached_any_refusal(const char* who, const std::vector<char>& attached, const int32_t* lens = nullptr)
+{
+    for (size_t r = 0; r < attached.size(); r++)
+        if (attached[r] && (!lens || lens[r] > 0)) return attached_text(who, (int)r);
+    return "";
+}
+// mc_prefix_fork and mc_prefix_import_kv
+inline std::string
+prefix_fill_refusal(const char* who, int kv_format, bool rolling, const std::vector<char>& attached)
+{
+    if (kv_format != MC_KV_BF16) return std::string(who) + ": the batch holds an fp8 cache (a shared prefix is bfloat16)";
+    if (rolling) return std::string(who) + ": the batch is rolling (a shared prefix does not roll)";
+    for (size_t r = 0; r < attached.size(); r++)
+        if (attached[r]) return std::string(who) + ": row " + std::to_string(r) + " is attached to the prefix this call would overwrite";
+    return "";
+}
+// a ragged call: an attached row steps in its own slots only
+inline std::string
+check_ragged_attached(const char* what, const int32_t* positions, const std::vector<char>& attached, int shared)
+{
+    for (size_t r = 0; r < attached.size(); r++)
+        if (attached[r] && positions[r] >= 0 && positions[r] < shared)
+            return std::string(what) + ": row " + std::to_string(r) + ": position " + std::to_string(positions[r]) + " lies inside the shared prefix (its first " +
+                   std::to_string(shared) + " slots)";
+    return "";
+}
+
 // ---------------------------------------------------------------- the pick
 
 // the decoder's sampler as a batch reads it (decoder_sampler_of), and a row's effective one

@@ -28,6 +28,9 @@ rows_pass(mc_batch* b, const char* who, bool extend, const int32_t* tokens, cons
     // (Part 2o: nothing enqueued, the lengths as they were; Part 2p: the batch's switch admits the three calls over plain chunks; Part 2q: a
     // switch of its own admits the tree)
     if (mc_status s = refuse(kv_packed_refusal(who, b->kv_format, b->kv_packed_on, v && v->parents, b->kv_tree_on)); s != MC_OK) return s;
+    // (Part 2r: the packed passes do not serve a row attached to the shared prefix)
+    if (lens)
+        if (mc_status s = refuse(attached_any_refusal(who, b->attached, lens)); s != MC_OK) return s;
     // check (rows_plan.h: the admission, the tables and the scratch sizes are plain arithmetic there)
     const bool tree = v && v->parents;
     const rows_counts n = rows_check(who, tokens, lens, positions, b->lengths.data(), B, c.max_seq_len, c.vocab, v != nullptr);

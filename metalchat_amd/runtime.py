@@ -224,6 +224,12 @@ def capi() -> C.CDLL:
         "mc_rolling_set": (i32, [vp, i32]),
         "mc_rolling_enabled": (i32, [vp]),
         "mc_rolling_fork_row": (i32, [vp, i32, i32]),
+        "mc_prefix_fork": (i32, [vp, i32]),
+        "mc_prefix_import_kv": (i32, [vp, i32, vp, vp, i32]),
+        "mc_prefix_attach": (i32, [vp, i32]),
+        "mc_prefix_detach": (i32, [vp, i32, i32]),
+        "mc_prefix_info": (i32, [vp, C.POINTER(i32), C.POINTER(i32)]),
+        "mc_prefix_attached": (i32, [vp, i32]),
         "mc_row_sampler_set": (i32, [vp, i32, i32, i32, C.c_float, C.c_float]),
         "mc_row_sampler_get": (i32, [vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(f32), C.POINTER(f32)]),
         "mc_row_sampler_reset": (i32, [vp]),
@@ -970,6 +976,36 @@ class Batch:
         n = C.c_int32()
         _check(capi().mc_ragged_export_kv(self._h, row, layer, _np_ptr(k), _np_ptr(v), C.byref(n)))
         return k[: n.value], v[: n.value]
+
+    # ---- shared-prefix rows (Part 2r): attached rows attend one copy of a prompt in their ragged steps
+
+    def prefix_fork(self, n_valid: int):
+        """the decoder's cache positions [0, n_valid) of every layer become the batch's shared prefix"""
+        _check(capi().mc_prefix_fork(self._h, n_valid))
+
+    def prefix_import_kv(self, layer: int, keys: np.ndarray, values: np.ndarray):
+        """test aid, as import_kv: one layer of the shared prefix from [n_valid, n_kv_heads, head_dim] arrays"""
+        k = np.ascontiguousarray(keys, dtype=self.np_T)
+        v = np.ascontiguousarray(values, dtype=self.np_T)
+        assert k.shape == v.shape and k.shape[1:] == (self.cfg["n_kv_heads"], self.cfg["head_dim"])
+        _check(capi().mc_prefix_import_kv(self._h, layer, _np_ptr(k), _np_ptr(v), k.shape[0]))
+
+    def attach_row(self, row: int):
+        """row `row` becomes a continuation of the prefix: length n_valid, its slots below `shared` read from the one copy"""
+        _check(capi().mc_prefix_attach(self._h, row))
+
+    def detach_row(self, row: int, materialise: bool = True):
+        """ends the attachment: the row takes a copy of the shared slots and keeps its length, or (materialise=False) is emptied"""
+        _check(capi().mc_prefix_detach(self._h, row, 1 if materialise else 0))
+
+    def prefix_info(self):
+        """(n_valid, shared) of the batch's prefix; (0, 0) without one"""
+        n, s = C.c_int32(), C.c_int32()
+        _check(capi().mc_prefix_info(self._h, C.byref(n), C.byref(s)))
+        return n.value, s.value
+
+    def attached(self, row: int) -> bool:
+        return capi().mc_prefix_attached(self._h, row) == 1
 
     # ---- the packed prompt pass (Part 2d): the prompts of several rows in one pass over the weights
 
