@@ -911,7 +911,8 @@ int32_t mc_kv_tree_enabled(const mc_batch* b); /* 0 for a null batch */
  * Contract: an attached row computes bit for bit what the same row computes on a batch whose row holds a full copy of the prefix -- tokens,
  * logits, log-probability records, its own K / V, its export after a detach -- whatever B is, whatever its index, whoever shares its group.
  * Refusals, all MC_ERR_INVALID_ARGUMENT behind the call's own name, nothing enqueued, no length changed:
- *   mc_prefix_fork, mc_prefix_import_kv   on an fp8 batch, on a rolling batch, while any row is attached
+ *   mc_prefix_fork, mc_prefix_import_kv   on an fp8 batch whose mc_kv_prefix_set switch is off (Part 2s), on a rolling batch, while any row
+ *                                         is attached
  *   mc_rolling_set, enable 1              while a prefix is held
  *   mc_prefix_attach                      no prefix, a bad row index, a row that is already attached
  *   mc_prefix_detach                      a bad row index, a row that is not attached, materialise other than 0 or 1
@@ -919,7 +920,7 @@ int32_t mc_kv_tree_enabled(const mc_batch* b); /* 0 for a null batch */
  *   any other call on a batch with an attached row (mc_batch_step / _generate), or one that names an attached row (mc_batch_fork,
  *   mc_batch_import_kv, mc_batch_export_kv, mc_rolling_fork_row as src or dst; mc_rows_prefill, mc_extend_rows, mc_verify_rows and
  *   mc_tree_verify with lens[r] > 0): "row r is attached to the shared prefix (mc_prefix_detach it first)"
- * Not covered: fp8 batches, rolling batches, more than one prefix per batch, the packed passes and verify calls on attached rows, the lockstep
+ * Not covered: fp8 batches (Part 2s admits them), rolling batches, more than one prefix per batch, the packed passes and verify calls on attached rows, the lockstep
  * calls, and giving back the attached rows' unused [0, shared) slots: every row still owns max_seq_len slots.  This part buys step time and
  * HBM traffic, not cache bytes.
  * ------------------------------------------------------------------------------------------ */
@@ -929,6 +930,30 @@ mc_status mc_prefix_attach(mc_batch* b, int32_t row);
 mc_status mc_prefix_detach(mc_batch* b, int32_t row, int32_t materialise);
 mc_status mc_prefix_info(const mc_batch* b, int32_t* n_valid, int32_t* shared);
 int32_t mc_prefix_attached(const mc_batch* b, int32_t row); /* 0 for a null batch */
+
+/* ================================================================================================
+ * Part 2s -- shared-prefix rows on an fp8 batch, opt-in per batch.  A switch of its own, off by default.  With it on, all six mc_prefix_* calls
+ * work on a batch from mc_kv_batch_create(.., MC_KV_FP8, ..): the prefix is one more set of a row's four planes per layer (K bytes, V bytes, the
+ * two exponent planes), allocated zeroed by the first call that fills them, and a ragged step with attached rows runs the mc_sp8_* attention
+ * (kernels/kv8_prefix_kernels.hip), which turns a prefix fragment into the bfloat16 MFMA operand ONCE for all rows that share it -- the per-row
+ * fp8 kernels pay that conversion once per row.
+ *   mc_prefix_fork       quantises the decoder's cache into the prefix planes, as mc_batch_fork quantises into a row
+ *   mc_prefix_import_kv  stages and quantises as mc_batch_import_kv does
+ *   mc_prefix_attach     copies slots [shared, n_valid) of all four planes into the row byte for byte; nothing is quantised again
+ *   mc_prefix_detach     materialise = 1: copies slots [0, shared) of all four planes into the row, byte for byte
+ *   mc_ragged_export_kv  of an attached row: deq of the prefix's planes for [0, shared), of the row's own for the rest
+ * Part 2o's rule holds unchanged, and Part 2r's contract with it: an attached row computes bit for bit what the same row computes on an fp8 batch
+ * whose row holds a byte copy of the prefix.  Every other refusal of Part 2r holds as it is.
+ *   off (the default)  mc_prefix_fork and mc_prefix_import_kv on an fp8 batch are refused with Part 2r's text.
+ *   on                 admitted.  The switch cannot be turned off while the fp8 batch holds a prefix: "mc_kv_prefix_set: the batch holds a shared
+ *                      prefix (the switch stays on while it does)".
+ * The switch is accepted and changes nothing on a bfloat16 batch.  on other than 0 or 1: MC_ERR_INVALID_ARGUMENT, "mc_kv_prefix_set: on must be 0
+ * or 1"; a null batch: "mc_kv_prefix_set: null argument".
+ * Not covered: more than one prefix per batch, the packed passes and verify calls on attached rows, rolling batches, giving back an attached
+ * row's unused [0, shared) slots, the batch-1 decoder, head_dim 256.
+ * ------------------------------------------------------------------------------------------ */
+mc_status mc_kv_prefix_set(mc_batch* b, int32_t on);
+int32_t mc_kv_prefix_enabled(const mc_batch* b); /* 0 for a null batch */
 
 /* Host-side helpers shared by tests and the synthetic initialiser. */
 /* value in [-7,7] (bits = 4) or [-127,127] (bits = 8), zero mean, of element (row, col) of matrix `matrix_id` */

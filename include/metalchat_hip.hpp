@@ -609,6 +609,9 @@ inline bool kv_packed(const shared_batch& b) { return mc_kv_packed_enabled(b.get
 /// Part 2q: an fp8 batch takes mc_tree_verify while the switch is on -- a switch of its own (no effect on a bfloat16 batch).
 inline void set_kv_tree(const shared_batch& b, bool on) { check(mc_kv_tree_set(b.get(), on ? 1 : 0)); }
 inline bool kv_tree(const shared_batch& b) { return mc_kv_tree_enabled(b.get()) != 0; }
+/// Part 2s: an fp8 batch takes the mc_prefix_* calls while the switch is on and holds its shared prefix as fp8 planes (no effect on a bfloat16 batch).
+inline void set_kv_prefix(const shared_batch& b, bool on) { check(mc_kv_prefix_set(b.get(), on ? 1 : 0)); }
+inline bool kv_prefix(const shared_batch& b) { return mc_kv_prefix_enabled(b.get()) != 0; }
 
 } // namespace hip
 } // namespace metalchat

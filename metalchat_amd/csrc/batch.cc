@@ -165,6 +165,14 @@ mc_batch::run(const batch_launch& l, const call_args& a)
     case op::sp_pv:
         return launch(l.L, pack(expv, psum, (void*)vt_of(li, 0), (void*)pvt_of(li), att, state, (const int32_t*)sp_dev, (uint32_t)n_rep, (uint32_t)hd,
                                 (uint32_t)cfg.max_seq_len, (uint32_t)fx.nsplit, cstride, (uint32_t)B, (uint32_t)prefix_group(cfg)));
+    case op::sp8_scores:
+        return launch(l.L, pack(q, (void*)kc_of(li, 0), kexp_of(li, 0), (void*)pkc_of(li), pkexp_of(li), expv, psum, state, (const int32_t*)sp_dev, (uint32_t)n_rep,
+                                (uint32_t)hd, (uint32_t)cfg.max_seq_len, round_bf_host(cfg.attn_scale), (uint32_t)fx.nsplit, cstride, (uint64_t)exp_elems(), (uint32_t)B,
+                                (uint32_t)prefix_group(cfg), (uint32_t)prefix_shared()));
+    case op::sp8_pv:
+        return launch(l.L, pack(expv, psum, (void*)vt_of(li, 0), vexp_of(li, 0), (void*)pvt_of(li), pvexp_of(li), att, state, (const int32_t*)sp_dev, (uint32_t)n_rep,
+                                (uint32_t)hd, (uint32_t)cfg.max_seq_len, (uint32_t)fx.nsplit, cstride, (uint64_t)exp_elems(), (uint32_t)B, (uint32_t)prefix_group(cfg),
+                                (uint32_t)fx.sp8_gw, (uint32_t)prefix_shared()));
     case op::rope_f8:
         return launch(l.L, pack(qkv, q, (void*)kc_of(li, 0), (void*)vt_of(li, 0), kexp_of(li, 0), vexp_of(li, 0), c.rolling ? rcos : fcos, c.rolling ? rsin : fsin, state,
                                 (uint32_t)H, (uint32_t)KV, (uint32_t)hd, (uint32_t)cfg.max_seq_len, cstride, (uint64_t)exp_elems()));
@@ -328,6 +336,7 @@ batch_create(const std::string& who, int cap, bool wide, mc_decoder* d, int32_t 
     env.B = batch;
     MC_HIP(hipDeviceGetAttribute(&env.cus, hipDeviceAttributeMultiprocessorCount, parts.ordinal));
     env.tiles_env = wb_tiles_env_of(getenv("MC_WB_TILES"));
+    env.sp8_groups_env = sp8_groups_env_of(getenv("MC_SP8_GROUPS"));
     env.kv_format = kv_format;
     b->kv_format = kv_format;
     b->fx = fix_batch(parts, env);

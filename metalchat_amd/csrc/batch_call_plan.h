@@ -20,6 +20,7 @@ enum class batch_op {
     rope, scores, pv,
     rope_f8, scores_f8, pv_f8, // Part 2o: the byte and exponent planes in place of the bfloat16 caches
     sp_scores, sp_pv,          // Part 2r: a ragged step with rows attached to the shared prefix (the prefix planes and sp_len beside the rows')
+    sp8_scores, sp8_pv,        // Part 2s: ... on an fp8 batch (the rows' and the prefix's byte and exponent planes, both strides, sp_len)
     process, process_rows, process_rows_count, // the ragged form takes the count flag: off behind a prompt pass
     argmax, candidates, sample, candidates_mixed, pick_mixed,
     logprob_parts, logprob_finish,
@@ -37,6 +38,7 @@ struct batch_launch {
 struct batch_fixed {
     mc_decoder_config cfg{};
     int B = 0, nsplit = 0, n_layers = 0, kv_format = MC_KV_BF16;
+    int sp8_gw = 1; // Part 2s: groups per workgroup of mc_sp8_attn_pv_bfloat, an argument of that launch
     bool wide = false; // B > 16: every GEMV of the batch is the wide kernel, whose argument list has the rows of the matrix in front of ldy
     size_t cand_per_row = 0;
     linear_shape head;
@@ -61,12 +63,13 @@ fix_batch(const Parts& p, const batch_env& e)
     assert(!f.head_gemv.lora && "the admission refuses an adaptor on the head: a token's plan lists no adaptor launch in front of it");
     using op = batch_op;
     for (int form = 0; form < 4; form++) {
-        const bool sp = form == 3; // (refused on an fp8 and on a rolling batch: the list is then never run)
+        const bool sp = form == 3; // (refused on a rolling batch and, without mc_kv_prefix_set, on an fp8 batch: the list is then never run)
         step_plan& st = f.steps[form] = plan_step(p.cfg, e.B, f.nsplit, form > 0, form == 2, e.kv_format);
         if (sp) {
-            const prefix_attention_plan a = plan_prefix_attention(p.cfg, e.B, f.nsplit, true);
+            const prefix_attention_plan a = plan_prefix_attention(p.cfg, e.B, f.nsplit, true, e.kv_format, e.sp8_groups_env, e.cus);
             st.scores = a.scores;
             st.pv = a.pv;
+            f.sp8_gw = a.gw;
         }
         std::vector<batch_launch>& body = f.body[form];
         auto gemv = [&](op adaptor, op main, const batch_gemv_plan& g, int layer) { // (a linear with an adaptor: a = T(A x) in front)
@@ -81,8 +84,8 @@ fix_batch(const Parts& p, const batch_env& e)
             body.push_back({op::attn_norm, l, st.rmsnorm});
             gemv(op::qkv_adaptor, op::qkv_gemv, plan_batch_gemv(L.qkv, 0, e), l);
             body.push_back({st.fp8 ? op::rope_f8 : op::rope, l, st.rope});
-            body.push_back({sp ? op::sp_scores : (st.fp8 ? op::scores_f8 : op::scores), l, st.scores});
-            body.push_back({sp ? op::sp_pv : (st.fp8 ? op::pv_f8 : op::pv), l, st.pv});
+            body.push_back({sp ? (st.fp8 ? op::sp8_scores : op::sp_scores) : (st.fp8 ? op::scores_f8 : op::scores), l, st.scores});
+            body.push_back({sp ? (st.fp8 ? op::sp8_pv : op::sp_pv) : (st.fp8 ? op::pv_f8 : op::pv), l, st.pv});
             gemv(op::wo_adaptor, op::wo_gemv, plan_batch_gemv(L.wo, 1, e), l);
             body.push_back({op::ffn_norm, l, st.rmsnorm});
             gemv(op::w13_adaptor, op::w13_gemv, plan_batch_gemv(L.w13, 2, e), l);

@@ -30,6 +30,8 @@
 // record the pick's log-probability and the top_n most likely tokens.  With the switch off a batch launches and holds what it did before.
 // Part 2r (mc_prefix_*): one shared prefix per batch; a ragged step with rows attached to it runs the mc_sp_* attention (prefix_kernels.hip), in
 // which 16 / n_rep rows share one K or V fragment.  A batch that never fills a prefix allocates, uploads and launches what it did before.
+// Part 2s (mc_kv_prefix_set): opt-in per batch, an fp8 batch holds its prefix as fp8 planes and its attached rows run the mc_sp8_* attention
+// (kv8_prefix_kernels.hip), which converts a prefix fragment to the bfloat16 operand once for all rows that share it.
 //
 // WHAT is launched -- names, grids, blocks, LDS bytes, the admission and every check of a call that needs no device -- is decided in
 // batch_plan.h, and IN WHICH ORDER in batch_call_plan.h: an entry point plans its whole call once (plan_batch_token, plan_rows_tail,
@@ -177,15 +179,21 @@ struct mc_batch {
     // Part 2r (mc_prefix_*): one shared prefix -- K / Vt planes [layer][n_kv][max_seq][hd], [layer][n_kv][hd][max_seq], allocated by the first
     // call that fills them -- of prefix_n valid positions; which rows are attached; and sp_len[B] (shared for an attached row, else 0) as the
     // device holds it.  A batch that never fills a prefix allocates, uploads and launches what it did
+    // Part 2s (mc_kv_prefix_set): on an fp8 batch the prefix is one more set of a row's four planes per layer -- pkc / pvt hold bytes, pkexp / pvexp
+    // [layer][n_kv][max_seq] the exponents -- and the step runs the mc_sp8_* attention (kv8_prefix_kernels.hip)
     void *pkc = nullptr, *pvt = nullptr;
+    int8_t *pkexp = nullptr, *pvexp = nullptr;
+    bool kv_prefix_on = false;
     int prefix_n = 0;
     std::vector<char> attached; // [B]
     int32_t* sp_dev = nullptr;
     std::vector<int32_t> sp_sent;
     int prefix_shared() const { return mcimpl::prefix_shared(prefix_n); }
     bool any_attached() const { return std::find(attached.begin(), attached.end(), (char)1) != attached.end(); }
-    char* pkc_of(int layer) const { return (char*)pkc + (size_t)layer * cache_elems * 2; }
-    char* pvt_of(int layer) const { return (char*)pvt + (size_t)layer * cache_elems * 2; }
+    char* pkc_of(int layer) const { return (char*)pkc + (size_t)layer * cache_elems * kv_elem(); }
+    char* pvt_of(int layer) const { return (char*)pvt + (size_t)layer * cache_elems * kv_elem(); }
+    int8_t* pkexp_of(int layer) const { return pkexp + (size_t)layer * exp_elems(); }
+    int8_t* pvexp_of(int layer) const { return pvexp + (size_t)layer * exp_elems(); }
     // The plans fixed at creation (batch_call_plan.h batch_fixed): B, the device's compute units and MC_WB_TILES, both read once there; the GEMV
     // of every matrix; the launches of a step, lockstep / ragged / ragged on a rolling batch.  The plan of a call is the entry point's own
     // (plan_batch_token, plan_rows_tail, plan_verify_call with settings()) and goes down by const&: the settings cannot change inside a call

@@ -106,6 +106,7 @@ refusal(const Parts& p, bool wide)
 struct batch_env {
     int B = 0, cus = 0, tiles_env = 0;
     int kv_format = MC_KV_BF16; // Part 2o: what the rows' caches hold
+    int sp8_groups_env = 0;     // Part 2s: MC_SP8_GROUPS (0: by sp8_groups' rule)
 };
 
 // mc_kv_batch_create's format, and what an fp8 cache asks of the config beyond the admission (its P.V kernel loads a Vt row's exponents 8 slots a lane)
@@ -226,22 +227,50 @@ prefix_shared(int n_valid)
 
 // The two attention launches of a ragged step.  No row attached: plan_step's.  Otherwise mc_sp_attn_scores_bfloat -- z = 0 the prefix's
 // workgroups, z = 1 + r row r's own splits -- and mc_sp_attn_pv_bfloat, a workgroup per group of rows: as many launches as without
+// On an fp8 batch (Part 2s, kv_format MC_KV_FP8) the per-row launches are the _f8_rows forms and the attached ones mc_sp8_attn_scores_bfloat and
+// mc_sp8_attn_pv_bfloat (kv8_prefix_kernels.hip), whose P.V workgroup serves gw consecutive groups: grid z = ceil(ceil(B / G) / gw)
 struct prefix_attention_plan {
     bool attached = false;
+    int gw = 1; // groups per P.V workgroup (1 for the bfloat16 kernels)
     launch_plan scores, pv;
 };
+// MC_SP8_GROUPS as mc_batch_create reads it: 1, 2 or 4, anything else (or unset) = 0, "by the rule"
+inline int
+sp8_groups_env_of(const char* value)
+{
+    const int g = value ? atoi(value) : 0;
+    return g == 1 || g == 2 || g == 4 ? g : 0;
+}
+// groups per workgroup of mc_sp8_attn_pv_bfloat: each extra group reuses a converted V operand, and takes a workgroup from the grid.  The most
+// of 4, 2 that still brings a workgroup to every compute unit, else 1 (measured: DESIGN.md "Shared-prefix rows on an fp8 batch" -- 4 is the
+// fastest at B = 64, where it leaves 256 workgroups, and 1 at B = 8); cus 0: not known, 1.  MC_SP8_GROUPS is the experiment's handle
+inline int
+sp8_groups(int groups_env, int cus, unsigned wgs_per_z, unsigned groups)
+{
+    if (groups_env) return groups_env;
+    for (unsigned g = 4; cus > 0 && g > 1; g /= 2)
+        if (wgs_per_z * ((groups + g - 1) / g) >= (unsigned)cus) return (int)g;
+    return 1;
+}
 inline prefix_attention_plan
-plan_prefix_attention(const mc_decoder_config& c, int B, int nsplit, bool attached)
+plan_prefix_attention(const mc_decoder_config& c, int B, int nsplit, bool attached, int kv_format = MC_KV_BF16, int groups_env = 0, int cus = 0)
 {
     prefix_attention_plan a;
     a.attached = attached;
     if (!attached) {
-        const step_plan s = plan_step(c, B, nsplit, true, false);
+        const step_plan s = plan_step(c, B, nsplit, true, false, kv_format);
         a.scores = s.scores;
         a.pv = s.pv;
         return a;
     }
     const unsigned KV = c.n_kv_heads, hd = c.head_dim, G = (unsigned)prefix_group(c);
+    if (kv_format == MC_KV_FP8) {
+        const unsigned groups = ((unsigned)B + G - 1) / G;
+        a.gw = sp8_groups(groups_env, cus, hd / 16 * KV, groups);
+        a.scores = {"mc_sp8_attn_scores_bfloat", (unsigned)nsplit, KV, (unsigned)B + 1, 256, 0};
+        a.pv = {"mc_sp8_attn_pv_bfloat", hd / 16, KV, (groups + a.gw - 1) / a.gw, 1024, 0};
+        return a;
+    }
     a.scores = {"mc_sp_attn_scores_bfloat", (unsigned)nsplit, KV, (unsigned)B + 1, 256, 0};
     a.pv = {"mc_sp_attn_pv_bfloat", hd / 16, KV, ((unsigned)B + G - 1) / G, 1024, 0};
     return a;
@@ -267,11 +296,11 @@ attached_any_refusal(const char* who, const std::vector<char>& attached, const i
         if (attached[r] && (!lens || lens[r] > 0)) return attached_text(who, (int)r);
     return "";
 }
-// mc_prefix_fork and mc_prefix_import_kv
+// mc_prefix_fork and mc_prefix_import_kv.  prefix_on (Part 2s, mc_kv_prefix_set): an fp8 batch holds its prefix as fp8 planes
 inline std::string
-prefix_fill_refusal(const char* who, int kv_format, bool rolling, const std::vector<char>& attached)
+prefix_fill_refusal(const char* who, int kv_format, bool rolling, const std::vector<char>& attached, bool prefix_on = false)
 {
-    if (kv_format != MC_KV_BF16) return std::string(who) + ": the batch holds an fp8 cache (a shared prefix is bfloat16)";
+    if (kv_format != MC_KV_BF16 && !prefix_on) return std::string(who) + ": the batch holds an fp8 cache (a shared prefix is bfloat16)";
     if (rolling) return std::string(who) + ": the batch is rolling (a shared prefix does not roll)";
     for (size_t r = 0; r < attached.size(); r++)
         if (attached[r]) return std::string(who) + ": row " + std::to_string(r) + " is attached to the prefix this call would overwrite";

@@ -230,6 +230,8 @@ def capi() -> C.CDLL:
         "mc_prefix_detach": (i32, [vp, i32, i32]),
         "mc_prefix_info": (i32, [vp, C.POINTER(i32), C.POINTER(i32)]),
         "mc_prefix_attached": (i32, [vp, i32]),
+        "mc_kv_prefix_set": (i32, [vp, i32]),
+        "mc_kv_prefix_enabled": (i32, [vp]),
         "mc_row_sampler_set": (i32, [vp, i32, i32, i32, C.c_float, C.c_float]),
         "mc_row_sampler_get": (i32, [vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(f32), C.POINTER(f32)]),
         "mc_row_sampler_reset": (i32, [vp]),
@@ -879,6 +881,14 @@ class Batch:
     @property
     def kv_tree(self) -> bool:
         return capi().mc_kv_tree_enabled(self._h) == 1
+
+    def set_kv_prefix(self, on: bool):
+        """Part 2s: an fp8 batch takes the shared-prefix calls (prefix_fork, attach_row, ..) while the switch is on and holds its prefix as fp8
+        planes; it cannot be turned off while the batch holds a prefix; no effect on a bfloat16 batch"""
+        _check(capi().mc_kv_prefix_set(self._h, 1 if on else 0))
+
+    def kv_prefix(self) -> bool:
+        return capi().mc_kv_prefix_enabled(self._h) == 1
 
     def size(self) -> int:
         return capi().mc_batch_size(self._h)
