@@ -920,7 +920,7 @@ int32_t mc_kv_tree_enabled(const mc_batch* b); /* 0 for a null batch */
  *   any other call on a batch with an attached row (mc_batch_step / _generate), or one that names an attached row (mc_batch_fork,
  *   mc_batch_import_kv, mc_batch_export_kv, mc_rolling_fork_row as src or dst; mc_rows_prefill, mc_extend_rows, mc_verify_rows and
  *   mc_tree_verify with lens[r] > 0): "row r is attached to the shared prefix (mc_prefix_detach it first)"
- * Not covered: fp8 batches (Part 2s admits them), rolling batches, more than one prefix per batch, the packed passes and verify calls on attached rows, the lockstep
+ * Not covered: fp8 batches (Part 2s admits them), rolling batches, more than one prefix per batch, the packed passes and verify calls on attached rows (Part 2t admits two of them), the lockstep
  * calls, and giving back the attached rows' unused [0, shared) slots: every row still owns max_seq_len slots.  This part buys step time and
  * HBM traffic, not cache bytes.
  * ------------------------------------------------------------------------------------------ */
@@ -954,6 +954,30 @@ int32_t mc_prefix_attached(const mc_batch* b, int32_t row); /* 0 for a null batc
  * ------------------------------------------------------------------------------------------ */
 mc_status mc_kv_prefix_set(mc_batch* b, int32_t on);
 int32_t mc_kv_prefix_enabled(const mc_batch* b); /* 0 for a null batch */
+
+/* ================================================================================================
+ * Part 2t -- packed chunks and speculative verify on attached rows, opt-in per batch, bfloat16 batches.  A switch of its own, off by default:
+ * with it off every text, launch, upload and allocation is what it was.  With it on, mc_extend_rows and mc_verify_rows admit rows attached to
+ * the shared prefix (Part 2r) with lens[r] > 0, beside ordinary rows and rows not in the call, on narrow and wide batches and QLoRA decoders;
+ * Part 2m's settings and Part 2n's records work as on any row.  The chunk's K / V are written to the row's OWN planes at slots pos + i (the
+ * packed rope + cache write as it is), a verify call leaves the row at its accepted length, and the attention of the attached rows' tiles runs
+ * mc_ax_sums / mc_ax_pv (kernels/attached_kernels.hip): a workgroup serves the query heads of one kv head for a unit of several tiles, loads
+ * each K / V fragment of the prefix ONCE for all of them, and keeps one accumulator per (tile, head, wave) that receives exactly the 32-key
+ * blocks mc_px_sums / mc_px_pv would give it, in the same order.  Ordinary rows of the same call keep the mc_px_* launches; a call that names
+ * no attached row launches what it launched.
+ * Contract (Part 2r's): an attached row computes bit for bit what the same row computes on a batch whose row holds a full copy of the prefix
+ * -- the chunk's K / V, the logits, the picks, the accepted counts, the records, mc_ragged_export_kv afterwards and the ragged steps that
+ * follow -- whatever B is, whatever the row's index, whoever else is in the call.
+ * Refusals, all MC_ERR_INVALID_ARGUMENT, nothing enqueued, no length changed:
+ *   mc_extend_rows, mc_verify_rows   positions[r] < shared for an attached row in the call: "<call>: row r: position p lies inside the shared
+ *                                    prefix (its first <shared> slots)"
+ *   mc_attached_packed_set           on = 1 on an fp8 batch: "mc_attached_packed_set: the batch holds an fp8 cache"; on other than 0 or 1:
+ *                                    "mc_attached_packed_set: on must be 0 or 1"; a null batch: "mc_attached_packed_set: null argument"
+ * mc_rows_prefill, whose mask never sees the context, and mc_tree_verify stay refused on an attached row with Part 2r's text, whatever the switch says.
+ * Not covered: fp8 batches, the tree, rolling batches, more than one prefix per batch.
+ * ------------------------------------------------------------------------------------------ */
+mc_status mc_attached_packed_set(mc_batch* b, int32_t on);
+int32_t mc_attached_packed_enabled(const mc_batch* b); /* 0 for a null batch */
 
 /* Host-side helpers shared by tests and the synthetic initialiser. */
 /* value in [-7,7] (bits = 4) or [-127,127] (bits = 8), zero mean, of element (row, col) of matrix `matrix_id` */

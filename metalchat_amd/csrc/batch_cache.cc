@@ -389,4 +389,21 @@ mc_kv_prefix_enabled(const mc_batch* b)
     return b && b->kv_prefix_on ? 1 : 0;
 }
 
+// ---- Part 2t: chunks and verify calls on attached rows (the admission and the launches: batch_rows.cc rows_pass) ----
+
+mc_status
+mc_attached_packed_set(mc_batch* b, int32_t on)
+{
+    if (!b) return fail(MC_ERR_INVALID_ARGUMENT, "mc_attached_packed_set: null argument");
+    if (mc_status s = refuse(attached_packed_switch_refusal(b->kv_format, on)); s != MC_OK) return s;
+    b->attached_packed_on = on == 1;
+    return MC_OK;
+}
+
+int32_t
+mc_attached_packed_enabled(const mc_batch* b)
+{
+    return b && b->attached_packed_on ? 1 : 0;
+}
+
 } // extern "C"

@@ -32,6 +32,8 @@
 // which 16 / n_rep rows share one K or V fragment.  A batch that never fills a prefix allocates, uploads and launches what it did before.
 // Part 2s (mc_kv_prefix_set): opt-in per batch, an fp8 batch holds its prefix as fp8 planes and its attached rows run the mc_sp8_* attention
 // (kv8_prefix_kernels.hip), which converts a prefix fragment to the bfloat16 operand once for all rows that share it.
+// Part 2t (mc_attached_packed_set): opt-in per batch, mc_extend_rows and mc_verify_rows take attached rows: their tiles run the mc_ax_* attention
+// (attached_kernels.hip), which loads a prefix fragment once for every (tile, head) of a unit.  A call that names no attached row launches what it did.
 //
 // WHAT is launched -- names, grids, blocks, LDS bytes, the admission and every check of a call that needs no device -- is decided in
 // batch_plan.h, and IN WHICH ORDER in batch_call_plan.h: an entry point plans its whole call once (plan_batch_token, plan_rows_tail,
@@ -188,6 +190,12 @@ struct mc_batch {
     std::vector<char> attached; // [B]
     int32_t* sp_dev = nullptr;
     std::vector<int32_t> sp_sent;
+    // Part 2t (mc_attached_packed_set): opt-in per batch, mc_extend_rows and mc_verify_rows take attached rows; the unit table of such a call
+    // (rows_plan.h rows_ranges), reserved by the first call that names an attached row
+    bool attached_packed_on = false;
+    mcimpl::ax_unit* ax_tab = nullptr;
+    int ax_tab_cap = 0;
+    std::vector<mcimpl::ax_unit> ax_host;
     int prefix_shared() const { return mcimpl::prefix_shared(prefix_n); }
     bool any_attached() const { return std::find(attached.begin(), attached.end(), (char)1) != attached.end(); }
     char* pkc_of(int layer) const { return (char*)pkc + (size_t)layer * cache_elems * kv_elem(); }

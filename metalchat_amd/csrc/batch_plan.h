@@ -317,6 +317,26 @@ check_ragged_attached(const char* what, const int32_t* positions, const std::vec
     return "";
 }
 
+// Part 2t (mc_attached_packed_set): a rows call against the attached rows it names.  `lifted`: the batch's switch is on and the call is
+// mc_extend_rows or mc_verify_rows -- the row is admitted, and its chunk starts in its own slots as a ragged step does; otherwise Part 2r's refusal
+inline std::string
+attached_packed_refusal(const char* who, const std::vector<char>& attached, const int32_t* lens, const int32_t* positions, int shared, bool lifted)
+{
+    if (!lifted) return attached_any_refusal(who, attached, lens);
+    for (size_t r = 0; r < attached.size(); r++)
+        if (attached[r] && lens[r] > 0 && positions[r] >= 0 && positions[r] < shared)
+            return std::string(who) + ": row " + std::to_string(r) + ": position " + std::to_string(positions[r]) + " lies inside the shared prefix (its first " +
+                   std::to_string(shared) + " slots)";
+    return "";
+}
+inline std::string
+attached_packed_switch_refusal(int kv_format, int on)
+{
+    if (on != 0 && on != 1) return "mc_attached_packed_set: on must be 0 or 1";
+    if (on == 1 && kv_format != MC_KV_BF16) return "mc_attached_packed_set: the batch holds an fp8 cache";
+    return "";
+}
+
 // ---------------------------------------------------------------- the pick
 
 // the decoder's sampler as a batch reads it (decoder_sampler_of), and a row's effective one

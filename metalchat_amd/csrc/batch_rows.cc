@@ -28,11 +28,15 @@ rows_pass(mc_batch* b, const char* who, bool extend, const int32_t* tokens, cons
     // (Part 2o: nothing enqueued, the lengths as they were; Part 2p: the batch's switch admits the three calls over plain chunks; Part 2q: a
     // switch of its own admits the tree)
     if (mc_status s = refuse(kv_packed_refusal(who, b->kv_format, b->kv_packed_on, v && v->parents, b->kv_tree_on)); s != MC_OK) return s;
-    // (Part 2r: the packed passes do not serve a row attached to the shared prefix)
-    if (lens)
-        if (mc_status s = refuse(attached_any_refusal(who, b->attached, lens)); s != MC_OK) return s;
-    // check (rows_plan.h: the admission, the tables and the scratch sizes are plain arithmetic there)
+    // (Part 2r: the packed passes do not serve a row attached to the shared prefix; Part 2t: the batch's switch admits such rows to chunks
+    // that see their context and to verify calls over plain chunks, behind the shared slots)
     const bool tree = v && v->parents;
+    const bool lifted = b->attached_packed_on && extend && !tree;
+    if (lens)
+        if (mc_status s = refuse(attached_packed_refusal(who, b->attached, lens, positions, b->prefix_shared(), lifted)); s != MC_OK) return s;
+    bool names_attached = false;
+    for (int r = 0; lifted && lens && r < B; r++) names_attached = names_attached || (b->attached[r] && lens[r] > 0);
+    // check (rows_plan.h: the admission, the tables and the scratch sizes are plain arithmetic there)
     const rows_counts n = rows_check(who, tokens, lens, positions, b->lengths.data(), B, c.max_seq_len, c.vocab, v != nullptr);
     if (!n.refusal.empty()) return fail(MC_ERR_INVALID_ARGUMENT, n.refusal);
     if (tree)
@@ -60,8 +64,20 @@ rows_pass(mc_batch* b, const char* who, bool extend, const int32_t* tokens, cons
         if ((s = b->reserve(b->px_sums, sums_slots, sc.per_tile, sc.slots, sizeof(float) * c.n_heads * PP_TILE_ROWS)) != MC_OK ||
             (s = b->reserve(b->px_part, b->px_slots, sc.per_tile, sc.slots, sc.per_slot)) != MC_OK)
             return s;
-        rows_ranges(b->pp_host, ntiles, b->px_slots, keys_override, b->px_host, b->px_groups);
+        // (Part 2t: a call that names an attached row lists those rows' tiles behind the others, in units of ax_unit_tiles tiles)
+        if (names_attached)
+            rows_ranges(b->pp_host, ntiles, b->px_slots, keys_override, b->px_host, b->px_groups, b->attached.data(),
+                        ax_unit_tiles(c.head_dim, c.n_heads / c.n_kv_heads), &b->ax_host);
+        else
+            rows_ranges(b->pp_host, ntiles, b->px_slots, keys_override, b->px_host, b->px_groups);
         if ((s = b->reserve(b->px_tab, b->px_tab_cap, (int)b->px_host.size(), sc.tiles_max * sc.per_tile)) != MC_OK) return s;
+        if (names_attached) {
+            if ((s = b->reserve(b->ax_tab, b->ax_tab_cap, (int)b->ax_host.size(), sc.tiles_max * sc.per_tile)) != MC_OK) return s;
+            pk.units = b->ax_tab;
+            pk.pkc = b->pkc;
+            pk.pvt = b->pvt;
+            pk.shared = b->prefix_shared();
+        }
         pk.extend = true;
         pk.ranges = b->px_tab;
         pk.groups = b->px_groups.data();
@@ -72,6 +88,7 @@ rows_pass(mc_batch* b, const char* who, bool extend, const int32_t* tokens, cons
     // upload
     MC_HIP(hipMemcpyAsync(b->pp_tab, b->pp_host.data(), b->pp_host.size(), hipMemcpyHostToDevice, b->p.stream));
     if (extend) MC_HIP(hipMemcpyAsync(b->px_tab, b->px_host.data(), sizeof(px_range) * b->px_host.size(), hipMemcpyHostToDevice, b->p.stream));
+    if (pk.units) MC_HIP(hipMemcpyAsync(b->ax_tab, b->ax_host.data(), sizeof(ax_unit) * b->ax_host.size(), hipMemcpyHostToDevice, b->p.stream));
     MC_HIP(hipMemcpyAsync(b->rows, b->rows_host.data(), sizeof(step_state) * B, hipMemcpyHostToDevice, b->p.stream));
     MC_HIP(hipMemsetAsync(b->tokens_dev, 0xFF, sizeof(int32_t) * B, b->p.stream));
     // prompt pass

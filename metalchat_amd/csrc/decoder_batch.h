@@ -89,6 +89,13 @@ struct packed_prefill {
     // mc_tree_verify (kernels/tree_kernels.hip): the chunks are trees.  One tv_node per packed row, on the device; the rope + cache
     // write and the extend attention then take their mc_tv_* names, with the table as one more argument behind their own.
     const tv_node* nodes = nullptr;
+    // Part 2t (kernels/attached_kernels.hip): a group with px_group::attached holds tiles of rows attached to the shared prefix and takes
+    // mc_ax_sums / mc_ax_pv over its units: the unit table on the device, the prefix planes (layer l at + l * cache_stride elements) and the
+    // slots they serve
+    const ax_unit* units = nullptr;
+    const void* pkc = nullptr;
+    const void* pvt = nullptr;
+    int shared = 0;
 };
 // run_prefill over `tokens` (M ids, host) with the packed rope + cache and attention launches, then the gather into x_out; the
 // decoder's cache, step state, sampler, taps and head are not touched (its prompt scratch is)

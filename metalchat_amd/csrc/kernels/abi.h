@@ -160,6 +160,24 @@ struct px_range {
     int32_t pad0, pad1;
 };
 static_assert(sizeof(px_range) == 32 && offsetof(px_range, k_lo) == 8 && offsetof(px_range, first) == 16, "px_range: eight words");
+// ---- chunks on rows attached to the shared prefix (attached_kernels.hip mc_ax_*; ABI Part 2t) ----
+// A workgroup serves NH query heads of one kv head and a unit of up to T tiles.  The P.V accumulators -- T * NH * hd / 16 tiles of four registers
+// a lane -- live in the 256 AGPRs, and the score MFMAs in flight want AGPRs as well, so the accumulators get AX_ACC_REGS = 192 of them: NH is the
+// most of 4, 2, 1 that divides n_rep with NH * hd <= 256 (a (tile, head) of hd 128 takes 32 registers: two heads and three tiles share a fragment
+// six ways, four heads and one tile four ways), T the most tiles that fit, at most AX_TILES_MAX
+constexpr int AX_TILES_MAX = 4;
+constexpr int AX_ACC_REGS = 192;
+constexpr int ax_heads(int hd, int n_rep) { return n_rep % 4 == 0 && 4 * hd <= 256 ? 4 : (n_rep % 2 == 0 && 2 * hd <= 256 ? 2 : 1); }
+constexpr int ax_tiles(int hd, int nh) { return AX_ACC_REGS / (nh * hd / 4) < AX_TILES_MAX ? (AX_ACC_REGS / (nh * hd / 4) < 1 ? 1 : AX_ACC_REGS / (nh * hd / 4)) : AX_TILES_MAX; }
+// one per (unit, range ordinal k): the k-th range of every tile of the unit that has one, as indices of the range table
+struct ax_unit {
+    int32_t n;                   // ranges named here, 1 .. T
+    int32_t range[AX_TILES_MAX];
+    int32_t pad[3];
+};
+static_assert(sizeof(ax_unit) == 32 && offsetof(ax_unit, range) == 4, "ax_unit: eight words");
+static_assert(ax_heads(128, 4) == 2 && ax_tiles(128, 2) == 3 && ax_heads(64, 4) == 4 && ax_tiles(64, 4) == 3 && ax_tiles(128, 1) == 4 && ax_tiles(64, 2) == 4,
+              "ax_heads, ax_tiles: the register budget of mc_ax_pv");
 // one per packed row of mc_tree_verify (tree_kernels.hip): node i of its segment's draft tree
 struct alignas(8) tv_node {
     int32_t depth; // edges from the root (node 0): the node sits at position pos + depth

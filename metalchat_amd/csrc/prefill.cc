@@ -356,6 +356,27 @@ mc_decoder::run_prefill(int M, int cache_pos, int rope_pos, int window, const vo
                 const extend_plan E = plan_extend_attention(penv(), pk->nodes != nullptr, pk->kv_format);
                 for (int g = 0; g < pk->ngroups; g++) {
                     const uint32_t e0 = (uint32_t)pk->groups[g].first, ne = (uint32_t)pk->groups[g].count;
+                    if (pk->groups[g].attached) {
+                        // Part 2t (kernels/attached_kernels.hip): tiles of rows attached to the shared prefix -- a workgroup per (heads of a kv
+                        // head, unit of tiles, range ordinal) loads a prefix fragment once for all of them; a split tile's reduce as below
+                        const ax_plan A = plan_attached_attention(H, KV, hd);
+                        const uint32_t u0 = (uint32_t)pk->groups[g].ufirst, nu = (uint32_t)pk->groups[g].ucount;
+                        const void* pkc = (const char*)pk->pkc + (size_t)li * pk->cache_stride * kvb;
+                        const void* pvt = (const char*)pk->pvt + (size_t)li * pk->cache_stride * kvb;
+                        mc_status ls = launch(A.sums, A.heads, nu, 1, 256, 0,
+                                              pack(pf_q, pk->segs, pk->ranges, pk->units, e0, u0, (const void*)pk_kc, pkc, pk->cache_stride, pk->sums, (uint32_t)H,
+                                                   (uint32_t)(H / KV), (uint32_t)cfg.max_seq_len, (uint32_t)pk->shared, scale_T, (const void*)pf_etab));
+                        if (ls != MC_OK) return ls;
+                        ls = launch(A.pv, A.heads, nu, 1, 256, 0,
+                                    pack(pf_q, pk->segs, pk->ranges, pk->units, e0, u0, (const void*)pk_kc, (const void*)pk_vt, pkc, pvt, pk->cache_stride,
+                                         (const void*)pk->sums, pk->part, pf_att, (uint32_t)H, (uint32_t)(H / KV), (uint32_t)cfg.max_seq_len, (uint32_t)pk->shared,
+                                         scale_T, (const void*)pf_etab));
+                        if (ls != MC_OK) return ls;
+                        if (!pk->groups[g].split) continue;
+                        ls = launch(A.reduce, H, ne, 1, 256, 0, pack(pk->segs, pk->ranges, e0, (const void*)pk->part, pf_att, (uint32_t)H));
+                        if (ls != MC_OK) return ls;
+                        continue;
+                    }
                     arg_pack as = pack(pf_q, pk->segs, pk->ranges, e0, (const void*)pk_kc);
                     if (f8) as.push((const void*)pk_kx);
                     as.push(pk->cache_stride);

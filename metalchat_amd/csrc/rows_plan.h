@@ -20,6 +20,10 @@ using namespace mc::abi;
 struct px_group {
     int first = 0, count = 0; // its ranges: [first, first + count) of the range table
     bool split = false;       // a tile of the group has several ranges (their partial outputs want mc_px_reduce)
+    // Part 2t: a group of tiles of rows attached to the shared prefix runs mc_ax_sums / mc_ax_pv over its units [ufirst, ufirst + ucount) of the
+    // unit table (and mc_px_reduce as any group); a group never mixes the two kinds
+    bool attached = false;
+    int ufirst = 0, ucount = 0;
 };
 
 // the tables inside one upload (mc_batch::pp_tab / pp_host.data()): MC_WIDE_BATCH_MAX segments, the call's tiles, a tree call's nodes
@@ -131,21 +135,85 @@ rows_tables(const int32_t* lens, const int32_t* positions, int B, int ntiles, st
 
 // step 3 (mc_extend_rows): the range table -- the keys [0, pos + last row of the tile] of every tile in ranges of px_range_keys --
 // and the launch groups: whole tiles, at most `slots` ranges each
+//
+// Part 2t (mc_attached_packed_set): `attached` names the batch rows attached to the shared prefix.  A call that names one lists the ordinary tiles'
+// ranges first and the attached tiles' behind them, in launch groups of their own (a row's bits do not depend on table order; a call that names
+// none builds what it built).  The attached tiles go, in table order, into UNITS of up to T tiles (ax_unit_tiles) whose ranges fit one group,
+// and `units` receives one ax_unit per (unit, range ordinal k): the k-th range of each tile of the unit that has one -- the workgroups of
+// mc_ax_sums / mc_ax_pv (kernels/attached_kernels.hip)
+inline int
+ax_unit_tiles(int head_dim, int n_rep)
+{
+    return ax_tiles(head_dim, ax_heads(head_dim, n_rep));
+}
+// the launches of a group of attached tiles: grid (heads, the group's units) for sums and pv, 256 threads; the reduce of a group with a split
+// tile is mc_px_reduce's, grid (n_heads, the group's ranges), as for any group
+struct ax_plan {
+    std::string sums, pv, reduce;
+    unsigned heads;
+};
+inline ax_plan
+plan_attached_attention(int n_heads, int n_kv_heads, int head_dim)
+{
+    const std::string sfx = "_bfloat_hd" + std::to_string(head_dim);
+    return {"mc_ax_sums" + sfx, "mc_ax_pv" + sfx, "mc_px_reduce" + sfx, (unsigned)(n_heads / ax_heads(head_dim, n_heads / n_kv_heads))};
+}
 inline void
-rows_ranges(const std::vector<char>& tab, int ntiles, int slots, int keys_override, std::vector<px_range>& ranges, std::vector<px_group>& groups)
+rows_ranges(const std::vector<char>& tab, int ntiles, int slots, int keys_override, std::vector<px_range>& ranges, std::vector<px_group>& groups,
+            const char* attached = nullptr, int T = 1, std::vector<ax_unit>* units = nullptr)
 {
     ranges.clear();
     groups.clear();
+    if (units) units->clear();
     char* base = const_cast<char*>(tab.data()); // (read only)
-    for (int ti = 0; ti < ntiles; ti++) {
+    struct tile_ranges {
+        pp_tile t;
+        int S, keys, n;
+    };
+    auto ranges_of = [&](int ti) {
         const pp_tile t = pp_tiles(base)[ti];
         const pp_seg g = pp_segs(base)[t.seg];
-        const int S = g.pos + std::min(t.r0 + PP_TILE_ROWS, g.len), keys = px_range_keys(S, g.len, keys_override), n = (S + keys - 1) / keys;
+        const int S = g.pos + std::min(t.r0 + PP_TILE_ROWS, g.len), keys = px_range_keys(S, g.len, keys_override);
+        return tile_ranges{t, S, keys, (S + keys - 1) / keys};
+    };
+    auto push = [&](const tile_ranges& r) {
         const int first = (int)ranges.size();
-        if (groups.empty() || groups.back().count + n > slots) groups.push_back({first, 0, false});
-        groups.back().count += n;
-        if (n > 1) groups.back().split = true;
-        for (int k = 0; k < n; k++) ranges.push_back({t.seg, t.r0, k * keys, std::min((k + 1) * keys, S), first, n, 0, 0});
+        groups.back().count += r.n;
+        if (r.n > 1) groups.back().split = true;
+        for (int k = 0; k < r.n; k++) ranges.push_back({r.t.seg, r.t.r0, k * r.keys, std::min((k + 1) * r.keys, r.S), first, r.n, 0, 0});
+        return first;
+    };
+    auto is_attached = [&](int ti) { return attached && units && attached[pp_segs(base)[pp_tiles(base)[ti].seg].row]; };
+    std::vector<int> behind;
+    for (int ti = 0; ti < ntiles; ti++) {
+        if (is_attached(ti)) {
+            behind.push_back(ti);
+            continue;
+        }
+        const tile_ranges r = ranges_of(ti);
+        if (groups.empty() || groups.back().count + r.n > slots) groups.push_back({(int)ranges.size(), 0, false});
+        push(r);
+    }
+    for (size_t i = 0; i < behind.size();) {
+        // the unit: tiles while there are fewer than T and their ranges fit the scratch
+        int first[AX_TILES_MAX], n[AX_TILES_MAX], nt = 0, total = 0, most = 0;
+        tile_ranges r[AX_TILES_MAX];
+        for (; i < behind.size() && nt < std::min(T, (int)AX_TILES_MAX); i++, nt++) {
+            r[nt] = ranges_of(behind[i]);
+            if (nt && total + r[nt].n > slots) break;
+            total += r[nt].n;
+            most = std::max(most, n[nt] = r[nt].n);
+        }
+        if (groups.empty() || !groups.back().attached || groups.back().count + total > slots)
+            groups.push_back({(int)ranges.size(), 0, false, true, (int)units->size(), 0});
+        for (int t = 0; t < nt; t++) first[t] = push(r[t]);
+        for (int k = 0; k < most; k++) {
+            ax_unit u{};
+            for (int t = 0; t < nt; t++)
+                if (k < n[t]) u.range[u.n++] = first[t] + k;
+            units->push_back(u);
+            groups.back().ucount++;
+        }
     }
 }
 

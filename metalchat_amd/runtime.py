@@ -232,6 +232,8 @@ def capi() -> C.CDLL:
         "mc_prefix_attached": (i32, [vp, i32]),
         "mc_kv_prefix_set": (i32, [vp, i32]),
         "mc_kv_prefix_enabled": (i32, [vp]),
+        "mc_attached_packed_set": (i32, [vp, i32]),
+        "mc_attached_packed_enabled": (i32, [vp]),
         "mc_row_sampler_set": (i32, [vp, i32, i32, i32, C.c_float, C.c_float]),
         "mc_row_sampler_get": (i32, [vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(f32), C.POINTER(f32)]),
         "mc_row_sampler_reset": (i32, [vp]),
@@ -889,6 +891,15 @@ class Batch:
 
     def kv_prefix(self) -> bool:
         return capi().mc_kv_prefix_enabled(self._h) == 1
+
+    def set_attached_packed(self, on: bool):
+        """Part 2t: extend_rows and verify_rows take rows attached to the shared prefix while the switch is on (bfloat16 batches); their tiles run
+        the mc_ax_* attention, which loads a prefix fragment once for every tile and head that shares it"""
+        _check(capi().mc_attached_packed_set(self._h, 1 if on else 0))
+
+    @property
+    def attached_packed(self) -> bool:
+        return capi().mc_attached_packed_enabled(self._h) == 1
 
     def size(self) -> int:
         return capi().mc_batch_size(self._h)
