@@ -971,13 +971,32 @@ int32_t mc_kv_prefix_enabled(const mc_batch* b); /* 0 for a null batch */
  * Refusals, all MC_ERR_INVALID_ARGUMENT, nothing enqueued, no length changed:
  *   mc_extend_rows, mc_verify_rows   positions[r] < shared for an attached row in the call: "<call>: row r: position p lies inside the shared
  *                                    prefix (its first <shared> slots)"
- *   mc_attached_packed_set           on = 1 on an fp8 batch: "mc_attached_packed_set: the batch holds an fp8 cache"; on other than 0 or 1:
- *                                    "mc_attached_packed_set: on must be 0 or 1"; a null batch: "mc_attached_packed_set: null argument"
+ *   mc_attached_packed_set           on = 1 on an fp8 batch whose mc_kv_prefix_set or mc_kv_packed_set switch is off (Part 2u admits it with both
+ *                                    on): "mc_attached_packed_set: the batch holds an fp8 cache (switch mc_kv_prefix_set and mc_kv_packed_set on
+ *                                    first ..)"; on other than 0 or 1: "mc_attached_packed_set: on must be 0 or 1"; a null batch:
+ *                                    "mc_attached_packed_set: null argument"
  * mc_rows_prefill, whose mask never sees the context, and mc_tree_verify stay refused on an attached row with Part 2r's text, whatever the switch says.
- * Not covered: fp8 batches, the tree, rolling batches, more than one prefix per batch.
+ * Not covered: the tree, rolling batches, more than one prefix per batch (fp8 batches: Part 2u).
  * ------------------------------------------------------------------------------------------ */
 mc_status mc_attached_packed_set(mc_batch* b, int32_t on);
 int32_t mc_attached_packed_enabled(const mc_batch* b); /* 0 for a null batch */
+
+/* ================================================================================================
+ * Part 2u -- packed chunks and speculative verify on attached rows of an fp8 batch.  No new call: mc_attached_packed_set(b, 1) is admitted on a
+ * batch from mc_kv_batch_create(.., MC_KV_FP8, ..) while BOTH mc_kv_prefix_set (Part 2s: the prefix is fp8 planes) and mc_kv_packed_set (Part 2p:
+ * the packed passes read and write fp8 planes) are on, and refused as above otherwise.  With the three switches on, mc_extend_rows and
+ * mc_verify_rows admit attached rows exactly as Part 2t says: the chunk's K / V are quantised into the row's OWN four planes at slots pos + i
+ * (mc_pp8_rope_cache* as it is), and the attention of the attached rows' tiles runs mc_ax8_sums / mc_ax8_pv (kernels/kv8_attached_kernels.hip) over
+ * Part 2t's units: a block of the prefix's K bytes and V bytes is loaded AND converted to the bfloat16 MFMA operand once for every (tile, head)
+ * of the unit -- mc_px8_* converts it once per (tile, head pair).  Ordinary rows of the same call keep mc_px8_*; mc_px_reduce is unchanged.
+ * Contract (Part 2s's and Part 2t's): an attached row of an fp8 batch computes bit for bit what the same row computes on an fp8 batch whose row
+ * holds a byte copy of the prefix -- the chunk's quantised K / V, the logits, the picks, the accepted counts, the records, mc_ragged_export_kv
+ * afterwards and the ragged steps that follow -- whatever B is, whatever the row's index, whoever else is in the call.
+ * A call made while mc_kv_packed_set is off is refused with Part 2o's text, which is checked first; Part 2t's refusals hold as they are, and
+ * mc_tree_verify -- with mc_kv_tree_set on, too -- and mc_rows_prefill stay refused on an attached row.  With the switch off, and on every bfloat16
+ * batch, every text, launch, upload and allocation is what it was.
+ * Not covered: the tree, mc_rows_prefill, rolling batches, more than one prefix per batch.
+ * ------------------------------------------------------------------------------------------ */
 
 /* Host-side helpers shared by tests and the synthetic initialiser. */
 /* value in [-7,7] (bits = 4) or [-127,127] (bits = 8), zero mean, of element (row, col) of matrix `matrix_id` */

@@ -395,7 +395,7 @@ mc_status
 mc_attached_packed_set(mc_batch* b, int32_t on)
 {
     if (!b) return fail(MC_ERR_INVALID_ARGUMENT, "mc_attached_packed_set: null argument");
-    if (mc_status s = refuse(attached_packed_switch_refusal(b->kv_format, on)); s != MC_OK) return s;
+    if (mc_status s = refuse(attached_packed_switch_refusal(b->kv_format, on, b->kv_prefix_on, b->kv_packed_on)); s != MC_OK) return s;
     b->attached_packed_on = on == 1;
     return MC_OK;
 }

@@ -329,11 +329,15 @@ attached_packed_refusal(const char* who, const std::vector<char>& attached, cons
                    std::to_string(shared) + " slots)";
     return "";
 }
+// Part 2u: an fp8 batch is admitted while both of its own switches are on -- without mc_kv_prefix_set there is no fp8 prefix, without
+// mc_kv_packed_set no packed pass to lift
 inline std::string
-attached_packed_switch_refusal(int kv_format, int on)
+attached_packed_switch_refusal(int kv_format, int on, bool kv_prefix_on = false, bool kv_packed_on = false)
 {
     if (on != 0 && on != 1) return "mc_attached_packed_set: on must be 0 or 1";
-    if (on == 1 && kv_format != MC_KV_BF16) return "mc_attached_packed_set: the batch holds an fp8 cache";
+    if (on == 1 && kv_format != MC_KV_BF16 && !(kv_prefix_on && kv_packed_on))
+        return "mc_attached_packed_set: the batch holds an fp8 cache (switch mc_kv_prefix_set and mc_kv_packed_set on first: its attached rows take chunks only "
+               "on an fp8 prefix, through the packed passes)";
     return "";
 }
 

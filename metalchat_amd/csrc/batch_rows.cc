@@ -29,7 +29,8 @@ rows_pass(mc_batch* b, const char* who, bool extend, const int32_t* tokens, cons
     // switch of its own admits the tree)
     if (mc_status s = refuse(kv_packed_refusal(who, b->kv_format, b->kv_packed_on, v && v->parents, b->kv_tree_on)); s != MC_OK) return s;
     // (Part 2r: the packed passes do not serve a row attached to the shared prefix; Part 2t: the batch's switch admits such rows to chunks
-    // that see their context and to verify calls over plain chunks, behind the shared slots)
+    // that see their context and to verify calls over plain chunks, behind the shared slots; Part 2u: on an fp8 batch too -- the switch is on
+    // only where mc_kv_prefix_set and mc_kv_packed_set were, the chunk's K / V go through mc_pp8_rope_cache* to the row's own planes)
     const bool tree = v && v->parents;
     const bool lifted = b->attached_packed_on && extend && !tree;
     if (lens)
@@ -76,6 +77,8 @@ rows_pass(mc_batch* b, const char* who, bool extend, const int32_t* tokens, cons
             pk.units = b->ax_tab;
             pk.pkc = b->pkc;
             pk.pvt = b->pvt;
+            pk.pkexp = b->pkexp; // (Part 2u: an fp8 batch's prefix, null on a bfloat16 batch)
+            pk.pvexp = b->pvexp;
             pk.shared = b->prefix_shared();
         }
         pk.extend = true;

@@ -96,6 +96,10 @@ struct packed_prefill {
     const void* pkc = nullptr;
     const void* pvt = nullptr;
     int shared = 0;
+    // Part 2u (kernels/kv8_attached_kernels.hip): on an fp8 batch the prefix planes hold bytes, these are their exponent planes (layer l at
+    // + l * exp_stride) and the group takes mc_ax8_sums / mc_ax8_pv
+    const int8_t* pkexp = nullptr;
+    const int8_t* pvexp = nullptr;
 };
 // run_prefill over `tokens` (M ids, host) with the packed rope + cache and attention launches, then the gather into x_out; the
 // decoder's cache, step state, sampler, taps and head are not touched (its prompt scratch is)

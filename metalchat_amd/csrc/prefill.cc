@@ -359,18 +359,32 @@ mc_decoder::run_prefill(int M, int cache_pos, int rope_pos, int window, const vo
                     if (pk->groups[g].attached) {
                         // Part 2t (kernels/attached_kernels.hip): tiles of rows attached to the shared prefix -- a workgroup per (heads of a kv
                         // head, unit of tiles, range ordinal) loads a prefix fragment once for all of them; a split tile's reduce as below
-                        const ax_plan A = plan_attached_attention(H, KV, hd);
+                        // Part 2u (kernels/kv8_attached_kernels.hip): on an fp8 batch the mc_ax8_* forms -- the exponent planes of the rows and of the
+                        // prefix behind their byte planes, and both strides
+                        const ax_plan A = plan_attached_attention(H, KV, hd, pk->kv_format);
                         const uint32_t u0 = (uint32_t)pk->groups[g].ufirst, nu = (uint32_t)pk->groups[g].ucount;
                         const void* pkc = (const char*)pk->pkc + (size_t)li * pk->cache_stride * kvb;
                         const void* pvt = (const char*)pk->pvt + (size_t)li * pk->cache_stride * kvb;
-                        mc_status ls = launch(A.sums, A.heads, nu, 1, 256, 0,
-                                              pack(pf_q, pk->segs, pk->ranges, pk->units, e0, u0, (const void*)pk_kc, pkc, pk->cache_stride, pk->sums, (uint32_t)H,
-                                                   (uint32_t)(H / KV), (uint32_t)cfg.max_seq_len, (uint32_t)pk->shared, scale_T, (const void*)pf_etab));
+                        const void* pkx = f8 ? pk->pkexp + (size_t)li * pk->exp_stride : nullptr;
+                        const void* pvx = f8 ? pk->pvexp + (size_t)li * pk->exp_stride : nullptr;
+                        arg_pack as = pack(pf_q, pk->segs, pk->ranges, pk->units, e0, u0, (const void*)pk_kc);
+                        if (f8) as.push((const void*)pk_kx);
+                        as.push(pkc);
+                        if (f8) as.push(pkx);
+                        as.push(pk->cache_stride);
+                        if (f8) as.push(pk->exp_stride);
+                        push_all(as, pk->sums, (uint32_t)H, (uint32_t)(H / KV), (uint32_t)cfg.max_seq_len, (uint32_t)pk->shared, scale_T, (const void*)pf_etab);
+                        mc_status ls = launch(A.sums, A.heads, nu, 1, 256, 0, std::move(as));
                         if (ls != MC_OK) return ls;
-                        ls = launch(A.pv, A.heads, nu, 1, 256, 0,
-                                    pack(pf_q, pk->segs, pk->ranges, pk->units, e0, u0, (const void*)pk_kc, (const void*)pk_vt, pkc, pvt, pk->cache_stride,
-                                         (const void*)pk->sums, pk->part, pf_att, (uint32_t)H, (uint32_t)(H / KV), (uint32_t)cfg.max_seq_len, (uint32_t)pk->shared,
-                                         scale_T, (const void*)pf_etab));
+                        arg_pack ap = pack(pf_q, pk->segs, pk->ranges, pk->units, e0, u0, (const void*)pk_kc, (const void*)pk_vt);
+                        if (f8) push_all(ap, (const void*)pk_kx, (const void*)pk_vx);
+                        push_all(ap, pkc, pvt);
+                        if (f8) push_all(ap, pkx, pvx);
+                        ap.push(pk->cache_stride);
+                        if (f8) ap.push(pk->exp_stride);
+                        push_all(ap, (const void*)pk->sums, pk->part, pf_att, (uint32_t)H, (uint32_t)(H / KV), (uint32_t)cfg.max_seq_len, (uint32_t)pk->shared,
+                                 scale_T, (const void*)pf_etab);
+                        ls = launch(A.pv, A.heads, nu, 1, 256, 0, std::move(ap));
                         if (ls != MC_OK) return ls;
                         if (!pk->groups[g].split) continue;
                         ls = launch(A.reduce, H, ne, 1, 256, 0, pack(pk->segs, pk->ranges, e0, (const void*)pk->part, pf_att, (uint32_t)H));

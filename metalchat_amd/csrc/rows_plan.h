@@ -10,6 +10,7 @@
 #include <string>
 #include <vector>
 
+#include "../../include/metalchat_hip.h" // MC_KV_*
 #include "kernels/abi.h"
 
 namespace mcimpl {
@@ -152,11 +153,12 @@ struct ax_plan {
     std::string sums, pv, reduce;
     unsigned heads;
 };
+// kv_format MC_KV_FP8 (Part 2u): the mc_ax8_* forms of sums and pv (kernels/kv8_attached_kernels.hip) over the same units and grid, the reduce as it is
 inline ax_plan
-plan_attached_attention(int n_heads, int n_kv_heads, int head_dim)
+plan_attached_attention(int n_heads, int n_kv_heads, int head_dim, int kv_format = MC_KV_BF16)
 {
-    const std::string sfx = "_bfloat_hd" + std::to_string(head_dim);
-    return {"mc_ax_sums" + sfx, "mc_ax_pv" + sfx, "mc_px_reduce" + sfx, (unsigned)(n_heads / ax_heads(head_dim, n_heads / n_kv_heads))};
+    const std::string sfx = "_bfloat_hd" + std::to_string(head_dim), ax = kv_format == MC_KV_FP8 ? "mc_ax8_" : "mc_ax_";
+    return {ax + "sums" + sfx, ax + "pv" + sfx, "mc_px_reduce" + sfx, (unsigned)(n_heads / ax_heads(head_dim, n_heads / n_kv_heads))};
 }
 inline void
 rows_ranges(const std::vector<char>& tab, int ntiles, int slots, int keys_override, std::vector<px_range>& ranges, std::vector<px_group>& groups,

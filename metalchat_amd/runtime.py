@@ -893,8 +893,9 @@ class Batch:
         return capi().mc_kv_prefix_enabled(self._h) == 1
 
     def set_attached_packed(self, on: bool):
-        """Part 2t: extend_rows and verify_rows take rows attached to the shared prefix while the switch is on (bfloat16 batches); their tiles run
-        the mc_ax_* attention, which loads a prefix fragment once for every tile and head that shares it"""
+        """Part 2t: extend_rows and verify_rows take rows attached to the shared prefix while the switch is on; their tiles run the mc_ax_*
+        attention, which loads a prefix fragment once for every tile and head that shares it.  Part 2u: an fp8 batch is admitted while
+        set_kv_prefix and set_kv_packed are both on, and runs mc_ax8_*, which also converts the fragment once for all of them"""
         _check(capi().mc_attached_packed_set(self._h, 1 if on else 0))
 
     @property

@@ -12,9 +12,12 @@ process's figure their median.  --processes N (default 3) runs N such processes 
 "faster": the attached median is below the full one by more than the larger min-max spread of the two.
 --only NAME: one variant alone (attached_verify_8, full_extend_64, ...), in this process, one sample and no file -- the process to put a
 kernel trace around.
-Prints one JSON line and writes it to --out (default profiles/attached_rows_bench.json).
+--kv fp8: both batches are fp8 (mc_kv_batch_create, a wide batch at either B) with mc_kv_packed_set on, the attached one with mc_kv_prefix_set
+on as well: mc_ax8_* against mc_px8_* on full byte copies.  A third form, bf16, is the bfloat16 attached batch above in the same process, for
+context; it enters no comparison.
+Prints one JSON line and writes it to --out (default profiles/attached_rows_bench.json, --kv fp8: profiles/attached_rows_fp8_bench.json).
 
-usage: python tools/attached_rows_bench.py [--out FILE] [--processes N] [--only NAME] [--layers N]"""
+usage: python tools/attached_rows_bench.py [--kv bf16|fp8] [--out FILE] [--processes N] [--only NAME] [--layers N]"""
 import json
 import os
 import statistics
@@ -37,9 +40,13 @@ def arg(name, default=None):
     return sys.argv[sys.argv.index(name) + 1] if name in sys.argv else default
 
 
-def rows_at_pos(mc, dec, B, attached, tokens):
-    batch = mc.Batch(dec, B, wide=B > 8)
+def rows_at_pos(mc, dec, B, attached, tokens, fp8=False):
+    batch = mc.Batch(dec, B, wide=True, kv="fp8") if fp8 else mc.Batch(dec, B, wide=B > 8)
+    if fp8:
+        batch.set_kv_packed(True)
     if attached:
+        if fp8:
+            batch.set_kv_prefix(True)
         batch.prefix_fork(PREFIX)
         batch.set_attached_packed(True)
     for r in range(B):
@@ -49,7 +56,7 @@ def rows_at_pos(mc, dec, B, attached, tokens):
     return batch
 
 
-def measure(only, layers):
+def measure(only, layers, fp8=False):
     """this process: {variant: ms per call}, the median of its timed rounds"""
     import metalchat_amd as mc
 
@@ -63,10 +70,10 @@ def measure(only, layers):
     variants = {}
     for B, n in SIZES.items():
         chunks = [rng.integers(0, shape["vocab"], n).astype(np.int32) for _ in range(B)]
-        for form in ("full", "attached"):
+        for form in ("full", "attached") + (("bf16",) if fp8 else ()):
             if only and not (only.startswith(form) and only.endswith(f"_{B}")):
                 continue
-            batch = rows_at_pos(mc, dec, B, form == "attached", tokens)
+            batch = rows_at_pos(mc, dec, B, form != "full", tokens, fp8 and form != "bf16")
             for call in ("verify", "extend"):
                 name = f"{form}_{call}_{B}"
                 if only and name != only:
@@ -93,24 +100,26 @@ def compare(a, b):
 
 
 def main():
-    only, layers = arg("--only"), int(arg("--layers", SHAPE["n_layers"]))
+    only, layers, kv = arg("--only"), int(arg("--layers", SHAPE["n_layers"])), arg("--kv", "bf16")
+    if kv not in ("bf16", "fp8"):
+        sys.exit("--kv: bf16 or fp8")
     if only or "--child" in sys.argv:
-        ms, device = measure(only, layers)
+        ms, device = measure(only, layers, kv == "fp8")
         print(json.dumps(dict(ms=ms, device=device)))
         return
     n = int(arg("--processes", 3))
-    runs = [json.loads(subprocess.check_output([sys.executable, os.path.abspath(__file__), "--child", "--layers", str(layers)], text=True).splitlines()[-1])
+    runs = [json.loads(subprocess.check_output([sys.executable, os.path.abspath(__file__), "--child", "--layers", str(layers), "--kv", kv], text=True).splitlines()[-1])
             for _ in range(n)]
     rows = {name: dict(B=int(name.split("_")[2]), ms_per_call=round(statistics.median(r["ms"][name] for r in runs), 4),
                        min=round(min(r["ms"][name] for r in runs), 4), max=round(max(r["ms"][name] for r in runs), 4)) for name in runs[0]["ms"]}
-    out = dict(metric="attached_rows_call", model="llama3-8b-int4-g128-synthetic", S=S, prefix=PREFIX, position=POS, layers=layers, calls=CALLS,
+    out = dict(metric="attached_rows_call", kv=kv, model="llama3-8b-int4-g128-synthetic", S=S, prefix=PREFIX, position=POS, layers=layers, calls=CALLS,
                rounds=ROUNDS, processes=n, tokens_per_row=SIZES, rows=rows, device=runs[0]["device"])
     for B in SIZES:
         for call in ("verify", "extend"):
             out[f"b{B}_{call}_attached_vs_full"] = compare(rows[f"full_{call}_{B}"], rows[f"attached_{call}_{B}"])
     line = json.dumps(out)
     print(line)
-    path = arg("--out", os.path.join(ROOT, "profiles", "attached_rows_bench.json"))
+    path = arg("--out", os.path.join(ROOT, "profiles", "attached_rows_fp8_bench.json" if kv == "fp8" else "attached_rows_bench.json"))
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     with open(path, "w") as f:
         f.write(line + "\n")
